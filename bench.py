@@ -16,7 +16,9 @@ there.  Before the timed region the same rotation runs for `--sustain` (5) secon
 the K timed steps run at the clocks the chip holds under load, not in a cold burst.  `value` = the K steps timed right
 behind it.  `burst` is the old figure: one batch replayed in place (cache resident), timed from idle.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C5|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C5|...] [--dump-outputs DIR]
+`--dump-outputs DIR` writes what the last timed step handed its caller (loss, predictions, pooled embedding, every gradient,
+the updated weights) as DIR/<name>.npy, so that two builds can be compared output for output.
 With --gpus N > 1 and no RANK in the environment this script starts its own N ranks (one per GPU, a child
 `python -m torch.distributed.run`), relays rank 0's JSON line and exits with the child's code; launched under an
 external torch.distributed.run it is one of the ranks.  Prints ONE JSON line on rank 0.
@@ -37,6 +39,7 @@ if REPO not in sys.path:
 
 T_START = time.perf_counter()
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs: all files together
 
 
 def parse():
@@ -71,7 +74,17 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step into a hipGraph (eager launches)")
     ap.add_argument("--forward-only", action="store_true",
                     help="BASELINE configs[1] (C2): plan build + forward only, no loss / backward (not the headline metric)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step handed its caller as DIR/<name>.npy (float32, "
+                         f"at most {DUMP_BUDGET_BYTES // 10**6} MB; a fixed sample of graphs beyond that).  The timed steps then "
+                         "start from the weights and optimiser state that set-up ended with, so the same arguments give that "
+                         "step the same inputs in every run")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def log(msg):
@@ -380,6 +393,31 @@ def parity_gate(model, r0, trainer, forward_only, dev):
             "seconds": time.perf_counter() - t0}
 
 
+def write_outputs(out_dir, arrays, per_graph, budget=DUMP_BUDGET_BYTES):
+    """arrays: {name: numpy array}, written as out_dir/<name>.npy in float32 (float64 stays float64).  `per_graph` names the
+    arrays whose rows are graphs of the batch: if everything together exceeds `budget` bytes, only a fixed sample of those
+    rows is written (seeded, sorted; their indices in `graph_rows.npy`).  -> the `dump_outputs` object of the JSON line."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32, order="C") for k, v in arrays.items()}
+    header = 128                                        # bytes of one .npy header (numpy pads it to a multiple of 64)
+    total = sum(a.nbytes + header for a in arrays.values())
+    rows, n_rows = None, (arrays[per_graph[0]].shape[0] if per_graph else 0)
+    if total > budget and per_graph:
+        row_bytes = sum(arrays[k].nbytes // max(n_rows, 1) for k in per_graph) + 8      # + its index in graph_rows
+        rest = total - sum(arrays[k].nbytes for k in per_graph) + header
+        keep = max(0, (budget - rest) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=min(keep, n_rows), replace=False))
+        for k in per_graph:
+            arrays[k] = arrays[k][rows]
+        arrays["graph_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in arrays),
+            "bytes": sum(os.path.getsize(os.path.join(out_dir, k + ".npy")) for k in arrays),
+            "graphs": n_rows, "graphs_written": n_rows if rows is None else len(rows)}
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -487,6 +525,9 @@ def main():
     # step buffers) per resident batch; `fwdbwd` stops after the backward (gradients only: secondary figure, batch 0)
     trainers = [FusedTrainStep(model, optimizer_step=True) for _ in res] if fused_ok else []
     fwdbwd = FusedTrainStep(model, optimizer_step=False) if fused_ok else None
+    if args.dump_outputs and not fused_ok:
+        raise SystemExit("bench.py: --dump-outputs covers the fused training step (train.FusedTrainStep); this model / flag "
+                         "combination times another path")
     dp = None
 
     # ---- parity gate: no timing is accepted unless step 0 of batch 0 matches the oracle
@@ -688,6 +729,35 @@ def main():
         dp = DataParallelGCN(model, combine=args.combine)    # broadcasts rank-0 weights (in place)
         log(f"{'gloo (rehearsal)' if rehearsal else 'RCCL'} process group up: world {rccl_world}")
 
+    # ---- --dump-outputs: the state set-up ended with (a fixed number of eager steps, weights replicated), copied back in place
+    #      in front of the timed steps -- the sustained run before them lasts a time, not a number of steps
+    dump_state = None
+    if args.dump_outputs:
+        fl = model.optimizer._flat[0]
+        dump_state = {k: fl[k].clone() for k in ("p", "m", "v")}
+        dump_state["step"] = fl["step_dev"][:1].clone()
+
+    def restore_dump_state():
+        fl = model.optimizer._flat[0]
+        for k in ("p", "m", "v"):
+            fl[k].copy_(dump_state[k])
+        fl["step_dev"][:1].copy_(dump_state["step"])        # (word 1, the exchange stamp, must never repeat: kept)
+
+    def step_outputs(i):
+        """What step `i` of the rotation handed its caller: loss, predictions, pooled embedding, the gradient of every
+        parameter (views of that trainer's flat buffer) and the updated weights.  -> {name: numpy array}"""
+        tr, B = trainers[i], res[i].B
+        cap = tr._bufs["cap"]
+        arrays = {"loss": cap["loss"][0], "out": cap["out"][:B], "emb": cap["emb"][:B]}
+        off = 0
+        for name, p in model.named_parameters():
+            arrays["grad." + name] = tr._flat[off:off + p.numel()].view_as(p)
+            arrays["param." + name] = p.detach()
+            off += p.numel()
+        if off != tr._flat.numel():
+            raise RuntimeError("bench.py: the trainer's flat gradient does not cover the model's parameters")
+        return {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+
     gc_frozen = [False]
 
     def freeze_gc():
@@ -711,15 +781,22 @@ def main():
         runner = lambda s, n: rot.run(form, s, n)
         sus_steps, sus_s, nxt = sustain(sustain_s, runner) if sustain_s > 0 else (0, 0.0, 0)
         tail_n = getattr(rot, "tail_n", 0)
-        if form == "window" and tail_n and nxt != NB - tail_n:
-            # (untimed) walk the rotation on to where the remainder window starts: the K timed steps are then that window + whole rotations
-            runner(nxt, (NB - tail_n - nxt) % NB)
-            nxt = NB - tail_n
-        dt = timed(args.steps, runner, start=nxt)
-        return {"launch": form, "ms_per_step": dt / args.steps * 1e3, "launch_forms_ms": per_form, "seconds": dt,
-                "sustained": {"steps": sus_steps, "seconds": sus_s, "ms_per_step": sus_s / max(sus_steps, 1) * 1e3},
-                "steps_per_graph_launch": NB if form == "window" else (1 if form == "graph" else None),
-                "errors": dict(rot.errors)}
+        start = NB - tail_n if form == "window" and tail_n else 0
+        if nxt != start:
+            # (untimed) walk the rotation on to a fixed start -- where the remainder window starts: the K timed steps are then
+            # that window + whole rotations; else batch 0 -- so that the last timed step is the same batch in every run
+            runner(nxt, (start - nxt) % NB)
+        if dump_state is not None:
+            restore_dump_state()
+        dt = timed(args.steps, runner, start=start)
+        m = {"launch": form, "ms_per_step": dt / args.steps * 1e3, "launch_forms_ms": per_form, "seconds": dt,
+             "sustained": {"steps": sus_steps, "seconds": sus_s, "ms_per_step": sus_s / max(sus_steps, 1) * 1e3},
+             "steps_per_graph_launch": NB if form == "window" else (1 if form == "graph" else None),
+             "errors": dict(rot.errors)}
+        if dump_state is not None:       # (read before anything else runs a step: the later figures overwrite these buffers)
+            last = (start + args.steps - 1) % NB
+            m["_outputs"] = (last, step_outputs(last))
+        return m
 
     # ---- kernel-level roofline: HIP events around the dominant entry point, inside a timed eager loop (before any graph)
     mid = r0.sb.max_nodes > 32
@@ -836,6 +913,9 @@ def main():
             fallback_reason = (fallback_reason + "; " if fallback_reason else "") + f"{exchange_mode}: unhealthy in the sustained run"
             exchange_mode, best = "rccl", dict(good["rccl"]) if "rccl" in good else best
     launch_mode, ms_step = best["launch"], best["ms_per_step"]
+    dumped = best.pop("_outputs", None)
+    for m in exchange_forms.values():
+        m.pop("_outputs", None)
     log(f"headline: {ms_step:.4f} ms/step ({launch_mode}; sustained {best['sustained']['ms_per_step']:.4f} over {best['sustained']['seconds']:.2f} s)")
 
     # ---- secondary: burst figures (round 1's headline: ONE batch replayed in place from an idle chip), gradients-only step
@@ -988,6 +1068,11 @@ def main():
             "launch": launch_mode, "steps_per_graph_launch": spg, "launch_forms_ms": best.get("launch_forms_ms"),
             "launch_errors": best.get("errors") or None, "eager_ms_per_step": dt_eager / args.steps * 1e3,
         }
+        if dumped is not None:
+            last, arrays = dumped
+            rec["dump_outputs"] = dict(write_outputs(args.dump_outputs, arrays, per_graph=("out", "emb")), batch=last,
+                                       note="the last timed step (resident batch `batch`), begun from the state set-up ended with")
+            log(f"outputs of the last timed step: {len(rec['dump_outputs']['files'])} files in {args.dump_outputs}")
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(cfg_name, args.num_graphs, args.cpu_steps)
         sys.stdout.flush()

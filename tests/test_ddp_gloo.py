@@ -20,6 +20,9 @@ def _free_port():
 
 
 def _worker(rank, world, port, q):
+    # the ranks are CPU processes and stay off the GPU: the model's seeding asks torch.cuda.is_available(), which starts the
+    # HIP runtime, and on a machine with a GPU eight ranks beside the test process would each open the device
+    torch.cuda.is_available = lambda: False
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
