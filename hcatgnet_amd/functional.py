@@ -9,6 +9,8 @@ readout Linear(+LeakyReLU) stack (model/gcn.py:70-71) and `loss.backward()` thro
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -183,199 +185,160 @@ class _LinearFn(torch.autograd.Function):
         return dx, dW, db, None, None
 
 
-class _FusedLayerFn(torch.autograd.Function):
-    """One fused launch per layer for batches of small graphs (csrc/fused.hip): returns the node
-    embeddings, or -- with `pool=True`, the last conv layer -- the pooled graph embedding
-    [max, mean] directly (the node embeddings stay internal, saved for the backward)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, plan: BatchPlan, gpt: int, apply_act: bool, slope: float, pool: bool):
-        lib = _lib.load()
-        _lib.require_gpu(x, weight, bias)
-        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
-        N, F = x.shape
-        D = weight.shape[0]
-        if weight.shape[1] != F or N != plan.N:
-            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, weight {tuple(weight.shape)}, plan N {plan.N}")
-        dev = x.device
-        out = torch.empty(N, D, dtype=torch.float32, device=dev)
-        emb = torch.empty(plan.B, 2 * D, dtype=torch.float32, device=dev) if pool else None
-        _lib.fused_forward(x=x, W1=weight, b1=bias, edge_index=plan.edge_index, E=plan.E, graph_ptr=plan.graph_ptr,
-                           edge_ptr=plan.edge_ptr, N=N, B=plan.B, F=F, D=D, graphs_per_tile=gpt, apply_act=int(apply_act),
-                           slope=slope, out1=out, emb=emb, status=plan.status)
-        ctx.plan, ctx.gpt, ctx.apply_act, ctx.slope, ctx.pool = plan, gpt, apply_act, slope, pool
-        if pool:
-            ctx.save_for_backward(x, weight, out, emb)
-            return emb
-        ctx.save_for_backward(x, weight, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad):
-        lib = _lib.load()
-        plan = ctx.plan
-        if ctx.pool:
-            x, weight, out, emb = ctx.saved_tensors
-            dout, demb = None, _f32c(grad)
-        else:
-            x, weight, out = ctx.saved_tensors
-            emb, dout, demb = None, _f32c(grad), None
-        N, F = x.shape
-        D = weight.shape[0]
-        dev = x.device
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dW = torch.empty_like(weight)
-        db = torch.empty(D, dtype=torch.float32, device=dev)
-        wsb = lib.hcg_fused_workspace_bytes(plan.B, F, D, ctx.gpt)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        rc = lib.hcg_fused_layer_bwd(_lib.ptr(dout), _lib.ptr(demb), _lib.ptr(emb), _lib.ptr(out), None, _lib.ptr(x),
-                                     _lib.ptr(weight), _lib.ptr(plan.edge_index), plan.E,
-                                     _lib.ptr(plan.graph_ptr), _lib.ptr(plan.edge_ptr), N, plan.B, F, D, ctx.gpt, ctx.slope,
-                                     int(ctx.apply_act), _lib.ptr(dx), _lib.ptr(plan.status), _lib.ptr(ws), wsb, _lib.stream_ptr())
-        _lib.check(rc, "hcg_fused_layer_bwd")
-        job = _lib.ReduceJob()
-        _lib.check(lib.hcg_fused_reduce_job(_lib.ptr(ws), wsb, N, plan.B, F, D, ctx.gpt, _lib.ptr(dW), _lib.ptr(db),
-                                            ctypes.addressof(job)), "hcg_fused_reduce_job")
-        _lib.reduce_jobs(ctypes.addressof(job), 1)
-        return dx, dW, db, None, None, None, None, None
+# ---- the fused conv kernel families -----------------------------------------------------------------------------------
+# One launcher per family: `forward`, `backward`, `workspace_bytes` and `reduce_jobs` (describes the gradient slabs a
+# backward left: -> number of hcg_reduce_job written) over a `Geometry`; `conv_route` picks the family of a layer.  Every
+# caller -- the autograd Functions below and `train.FusedTrainStep` -- launches through these.
+class Geometry(NamedTuple):
+    """Graphs [g0, g0 + B) of a blocked plan as the conv kernels see them (device pointers as integers).  Node rows stay
+    absolute: x and the activations need no offsets, graph_ptr / edge_ptr / emb / demb start at graph g0."""
+    edge_index: int
+    E: int
+    graph_ptr: int
+    edge_ptr: int
+    N: int
+    B: int
+    max_nodes: Optional[int]
+    max_edges: Optional[int]
+    status: int
+    g0: int
 
 
-class _MidLayerFn(torch.autograd.Function):
-    """One fused launch per layer for batches of mid-size graphs, one graph per workgroup (csrc/mid.hip): the size
-    range of the reference's own reaction graphs.  Same contract as `_FusedLayerFn`."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, plan: BatchPlan, apply_act: bool, slope: float, pool: bool):
-        lib = _lib.load()
-        _lib.require_gpu(x, weight, bias)
-        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
-        N, F = x.shape
-        D = weight.shape[0]
-        if weight.shape[1] != F or N != plan.N:
-            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, weight {tuple(weight.shape)}, plan N {plan.N}")
-        dev = x.device
-        out = torch.empty(N, D, dtype=torch.float32, device=dev)
-        emb = torch.empty(plan.B, 2 * D, dtype=torch.float32, device=dev) if pool else None
-        rc = lib.hcg_mid_layer_fwd(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(plan.edge_index), plan.E,
-                                   _lib.ptr(plan.graph_ptr), _lib.ptr(plan.edge_ptr), N, plan.B, F, D, plan.max_nodes,
-                                   plan.max_edges, slope, int(apply_act), _lib.ptr(out), _lib.ptr(emb), None, None, None, _lib.ptr(plan.status),
-                                   _lib.stream_ptr())
-        _lib.check(rc, "hcg_mid_layer_fwd")
-        ctx.plan, ctx.apply_act, ctx.slope, ctx.pool = plan, apply_act, slope, pool
-        if pool:
-            ctx.save_for_backward(x, weight, out, emb)
-            return emb
-        ctx.save_for_backward(x, weight, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad):
-        import ctypes
-        lib = _lib.load()
-        plan = ctx.plan
-        if ctx.pool:
-            x, weight, out, emb = ctx.saved_tensors
-            dout, demb = None, _f32c(grad)
-        else:
-            x, weight, out = ctx.saved_tensors
-            emb, dout, demb = None, _f32c(grad), None
-        N, F = x.shape
-        D = weight.shape[0]
-        dev = x.device
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dW = torch.empty_like(weight)
-        db = torch.empty(D, dtype=torch.float32, device=dev)
-        wsb = lib.hcg_mid_workspace_bytes(plan.B, F, D, plan.max_nodes, plan.max_edges)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        stream = _lib.stream_ptr()
-        rc = lib.hcg_mid_layer_bwd(_lib.ptr(dout), _lib.ptr(demb), _lib.ptr(emb), _lib.ptr(out), _lib.ptr(x), _lib.ptr(weight),
-                                   _lib.ptr(plan.edge_index), plan.E, _lib.ptr(plan.graph_ptr), _lib.ptr(plan.edge_ptr), N,
-                                   plan.B, F, D, plan.max_nodes, plan.max_edges, ctx.slope, int(ctx.apply_act), _lib.ptr(dx),
-                                   _lib.ptr(plan.status), _lib.ptr(ws), wsb, stream)
-        _lib.check(rc, "hcg_mid_layer_bwd")
-        jb, halves = _lib.job_bytes(), D // 64          # one slab set (= one job) per 64-column half
-        jobs = ctypes.create_string_buffer(jb * halves)
-        for half in range(halves):
-            _lib.check(lib.hcg_mid_reduce_job(_lib.ptr(ws), wsb, plan.B, F, D, plan.max_nodes, plan.max_edges, half,
-                                              _lib.ptr(dW), _lib.ptr(db), ctypes.addressof(jobs) + half * jb), "hcg_mid_reduce_job")
-        _lib.reduce_jobs(ctypes.addressof(jobs), halves)
-        return dx, dW, db, None, None, None, None
+def geometry(plan: BatchPlan, g0: int = 0, B: Optional[int] = None) -> Geometry:
+    """Graphs [g0, g0 + B) of `plan` (default: all graphs from g0 on)."""
+    return Geometry(plan.edge_index.data_ptr(), plan.E, plan.graph_ptr.data_ptr() + 4 * g0, plan.edge_ptr.data_ptr() + 4 * g0,
+                    plan.N, plan.B - g0 if B is None else B, plan.max_nodes, plan.max_edges, plan.status.data_ptr(), g0)
 
 
-def mid_supported(plan: BatchPlan, F: int, D: int) -> bool:
-    """True when the one-graph-per-workgroup kernels apply to this plan / layer shape."""
-    if (plan.mode != "blocked" or plan.ew_csr is not None or plan.max_nodes is None or plan.max_edges is None
-            or plan.B == 0 or plan.N == 0):
-        return False
-    return bool(_lib.load().hcg_mid_supported(F, D, plan.max_nodes, plan.max_edges))
+def _a(t):
+    """Device address: a tensor's, an address as is, None -> NULL."""
+    return t if t is None or t.__class__ is int else t.data_ptr()
 
 
-def mid_gcn_layer(x, weight, bias, plan: BatchPlan, apply_act=True, slope=LEAKY_SLOPE, pool=False):
-    return _MidLayerFn.apply(x, weight, bias, plan, apply_act, slope, pool)
+def _graph_rows(t, geo: Geometry, D: int):
+    """emb / demb [B, 2D] of the geometry's first graph on."""
+    return None if t is None else t.data_ptr() + 8 * D * geo.g0
 
 
-class _TallLayerFn(torch.autograd.Function):
-    """Layers cut into dense row-streaming parts + per-graph segmented sums (csrc/tall.hip): D = 128 over large graphs
-    (forward and backward), D = 64 over graphs of 65 .. 224 nodes (backward; the forward is `hcg_mid_layer_fwd`).
-    Same contract as `_MidLayerFn`."""
+def _tiles_forward(geo, gpt, x, W, b, act, *, out=None, emb=None, poolbits=None, slope=LEAKY_SLOPE, head_out=None,
+                   **fields):
+    """hcg_fused_forward; `fields`: the stacked (W2, b2, out2) and head forms of hcg_fused_fwd_args (`head_out`: its `out`)."""
+    _lib.fused_forward(x=x, W1=W, b1=b, edge_index=geo.edge_index, E=geo.E, graph_ptr=geo.graph_ptr, edge_ptr=geo.edge_ptr,
+                       N=geo.N, B=geo.B, F=x.shape[1], D=W.shape[0], graphs_per_tile=gpt, apply_act=act, slope=slope, out1=out,
+                       emb=_graph_rows(emb, geo, W.shape[0]), poolbits=poolbits, status=geo.status, out=head_out, **fields)
 
-    @staticmethod
-    def forward(ctx, x, weight, bias, plan: BatchPlan, apply_act: bool, slope: float, pool: bool):
-        lib = _lib.load()
-        _lib.require_gpu(x, weight, bias)
-        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
-        N, F = x.shape
-        D = weight.shape[0]
-        if weight.shape[1] != F or N != plan.N:
-            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, weight {tuple(weight.shape)}, plan N {plan.N}")
-        dev = x.device
-        out = torch.empty(N, D, dtype=torch.float32, device=dev)
-        emb = torch.empty(plan.B, 2 * D, dtype=torch.float32, device=dev) if pool else None
-        wsb = lib.hcg_tall_workspace_bytes(N, plan.B, F, D) if D != 64 else 0     # (64-wide: the forward needs none)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        rc = lib.hcg_tall_layer_fwd(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(plan.edge_index), plan.E,
-                                    _lib.ptr(plan.graph_ptr), _lib.ptr(plan.edge_ptr), N, plan.B, F, D, plan.max_nodes,
-                                    plan.max_edges, slope, int(apply_act), _lib.ptr(out), _lib.ptr(emb), None, None, None, _lib.ptr(plan.status),
-                                    _lib.ptr(ws), wsb, _lib.stream_ptr())
-        _lib.check(rc, "hcg_tall_layer_fwd")
-        ctx.plan, ctx.apply_act, ctx.slope, ctx.pool = plan, apply_act, slope, pool
-        if pool:
-            ctx.save_for_backward(x, weight, out, emb)
-            return emb
-        ctx.save_for_backward(x, weight, out)
-        return out
 
-    @staticmethod
-    def backward(ctx, grad):
-        import ctypes
-        lib = _lib.load()
-        plan = ctx.plan
-        if ctx.pool:
-            x, weight, out, emb = ctx.saved_tensors
-            dout, demb = None, _f32c(grad)
-        else:
-            x, weight, out = ctx.saved_tensors
-            emb, dout, demb = None, _f32c(grad), None
-        N, F = x.shape
-        D = weight.shape[0]
-        dev = x.device
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dW = torch.empty_like(weight)
-        db = torch.empty(D, dtype=torch.float32, device=dev)
-        wsb = lib.hcg_tall_workspace_bytes(N, plan.B, F, D)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        stream = _lib.stream_ptr()
-        rc = lib.hcg_tall_layer_bwd(_lib.ptr(dout), _lib.ptr(demb), _lib.ptr(emb), _lib.ptr(out), None, None, None, None, _lib.ptr(x), _lib.ptr(weight),
-                                    _lib.ptr(plan.edge_index), plan.E, _lib.ptr(plan.graph_ptr), _lib.ptr(plan.edge_ptr), N,
-                                    plan.B, F, D, plan.max_nodes, plan.max_edges, ctx.slope, int(ctx.apply_act), _lib.ptr(dx),
-                                    _lib.ptr(plan.status), _lib.ptr(ws), wsb, stream)
-        _lib.check(rc, "hcg_tall_layer_bwd")
-        jb = _lib.job_bytes()
-        jobs = ctypes.create_string_buffer(jb * 2)
-        _lib.check(lib.hcg_tall_reduce_jobs(_lib.ptr(ws), wsb, N, plan.B, F, D, 0, _lib.ptr(dW), _lib.ptr(db),
-                                            ctypes.addressof(jobs)), "hcg_tall_reduce_jobs")
-        _lib.reduce_jobs(ctypes.addressof(jobs), 2)
-        return dx, dW, db, None, None, None, None
+def _tiles_backward(geo, gpt, x, W, flags, *, dout=None, demb=None, emb=None, out=None, poolbits=None, dx=None, ws, wsb,
+                    slope=LEAKY_SLOPE, stream=None):
+    D = W.shape[0]
+    _lib.check(_lib.load().hcg_fused_layer_bwd(
+        _a(dout), _graph_rows(demb, geo, D), _graph_rows(emb, geo, D), _a(out), _a(poolbits), x.data_ptr(), W.data_ptr(), geo.edge_index,
+        geo.E, geo.graph_ptr, geo.edge_ptr, geo.N, geo.B, x.shape[1], D, gpt, slope, flags, _a(dx), geo.status, _a(ws), wsb,
+        _lib.stream_ptr() if stream is None else stream), "hcg_fused_layer_bwd")
+
+
+def _tiles_workspace_bytes(geo, gpt, F, D) -> int:
+    return _lib.load().hcg_fused_workspace_bytes(geo.B, F, D, gpt)
+
+
+def _tiles_reduce_jobs(geo, gpt, F, D, ws, wsb, dW, db, job) -> int:
+    _lib.check(_lib.load().hcg_fused_reduce_job(_a(ws), wsb, geo.N, geo.B, F, D, gpt, _a(dW), _a(db), job), "hcg_fused_reduce_job")
+    return 1
+
+
+def _mid_forward(geo, gpt, x, W, b, act, *, out=None, emb=None, poolbits=None, xagg=None, signs=None, slope=LEAKY_SLOPE,
+                 stream=None):
+    _lib.check(_lib.load().hcg_mid_layer_fwd(
+        x.data_ptr(), W.data_ptr(), b.data_ptr(), geo.edge_index, geo.E, geo.graph_ptr, geo.edge_ptr, geo.N, geo.B, x.shape[1], W.shape[0],
+        geo.max_nodes, geo.max_edges, slope, act, _a(out), _graph_rows(emb, geo, W.shape[0]), _a(poolbits), _a(xagg), _a(signs),
+        geo.status, _lib.stream_ptr() if stream is None else stream), "hcg_mid_layer_fwd")
+
+
+def _mid_backward(geo, gpt, x, W, flags, *, dout=None, demb=None, emb=None, out=None, dx=None, ws, wsb, slope=LEAKY_SLOPE,
+                  stream=None):
+    D = W.shape[0]
+    _lib.check(_lib.load().hcg_mid_layer_bwd(
+        _a(dout), _graph_rows(demb, geo, D), _graph_rows(emb, geo, D), _a(out), x.data_ptr(), W.data_ptr(), geo.edge_index, geo.E,
+        geo.graph_ptr, geo.edge_ptr, geo.N, geo.B, x.shape[1], D, geo.max_nodes, geo.max_edges, slope, flags, _a(dx), geo.status,
+        _a(ws), wsb, _lib.stream_ptr() if stream is None else stream), "hcg_mid_layer_bwd")
+
+
+def _mid_workspace_bytes(geo, gpt, F, D) -> int:
+    return _lib.load().hcg_mid_workspace_bytes(geo.B, F, D, geo.max_nodes, geo.max_edges)
+
+
+def _mid_reduce_jobs(geo, gpt, F, D, ws, wsb, dW, db, job) -> int:
+    lib, halves = _lib.load(), D // 64                 # one slab set (= one job) per 64-column half
+    for half in range(halves):
+        _lib.check(lib.hcg_mid_reduce_job(_a(ws), wsb, geo.B, F, D, geo.max_nodes, geo.max_edges, half, _a(dW), _a(db),
+                                          job + half * _JOB_BYTES), "hcg_mid_reduce_job")
+    return halves
+
+
+def _tall_forward(geo, gpt, x, W, b, act, *, out=None, emb=None, poolbits=None, xagg=None, signs=None, ws=None, wsb=0,
+                  slope=LEAKY_SLOPE, stream=None):
+    _lib.check(_lib.load().hcg_tall_layer_fwd(
+        x.data_ptr(), W.data_ptr(), b.data_ptr(), geo.edge_index, geo.E, geo.graph_ptr, geo.edge_ptr, geo.N, geo.B, x.shape[1], W.shape[0],
+        geo.max_nodes, geo.max_edges, slope, act, _a(out), _graph_rows(emb, geo, W.shape[0]), _a(poolbits), _a(xagg), _a(signs),
+        geo.status, _a(ws), wsb, _lib.stream_ptr() if stream is None else stream), "hcg_tall_layer_fwd")
+
+
+def _tall_backward(geo, gpt, x, W, flags, *, dout=None, demb=None, emb=None, out=None, poolbits=None, xagg=None, signs=None,
+                   nodes_dev=None, dx=None, ws, wsb, slope=LEAKY_SLOPE, stream=None):
+    D = W.shape[0]
+    _lib.check(_lib.load().hcg_tall_layer_bwd(
+        _a(dout), _graph_rows(demb, geo, D), _graph_rows(emb, geo, D), _a(out), _a(poolbits), _a(xagg), _a(signs), nodes_dev,
+        x.data_ptr(), W.data_ptr(), geo.edge_index, geo.E, geo.graph_ptr, geo.edge_ptr, geo.N, geo.B, x.shape[1], D, geo.max_nodes,
+        geo.max_edges, slope, flags, _a(dx), geo.status, _a(ws), wsb, _lib.stream_ptr() if stream is None else stream),
+        "hcg_tall_layer_bwd")
+
+
+def _tall_workspace_bytes(geo, gpt, F, D) -> int:
+    """H / dH round trip + gradient slabs: forward and backward share it."""
+    return _lib.load().hcg_tall_workspace_bytes(geo.N, geo.B, F, D)
+
+
+def _tall_reduce_jobs(geo, gpt, F, D, ws, wsb, dW, db, job, first: bool = False) -> int:
+    """`first`: the slabs of the first-layer form (xagg + signs given to the backward)."""
+    _lib.check(_lib.load().hcg_tall_reduce_jobs(_a(ws), wsb, geo.N, geo.B, F, D, int(first), _a(dW), _a(db), job),
+               "hcg_tall_reduce_jobs")
+    return 2                                           # dW, db
+
+
+# small-graph tiles (csrc/fused.hip, graphs up to 32 nodes), one graph per workgroup / wave (csrc/mid.hip, wave.hip), the
+# wide-layer route (csrc/tall.hip: dense row-streaming parts + per-graph segmented sums)
+TILES = SimpleNamespace(name="tiles", forward=_tiles_forward, backward=_tiles_backward, workspace_bytes=_tiles_workspace_bytes,
+                        reduce_jobs=_tiles_reduce_jobs)
+MID = SimpleNamespace(name="mid", forward=_mid_forward, backward=_mid_backward, workspace_bytes=_mid_workspace_bytes,
+                      reduce_jobs=_mid_reduce_jobs)
+TALL = SimpleNamespace(name="tall", forward=_tall_forward, backward=_tall_backward, workspace_bytes=_tall_workspace_bytes,
+                       reduce_jobs=_tall_reduce_jobs)
+
+_JOB_BYTES = _lib.job_bytes()
+
+
+class JobList:
+    """A host array of HCG_REDUCE_MAX_JOBS hcg_reduce_job: a family's `reduce_jobs` writes at `slot()`, the count it returns
+    goes to `n`; hcg_step_tail -- or `flush`, the reductions alone -- consumes them."""
+    __slots__ = ("buf", "addr", "n")
+
+    def __init__(self):
+        self.buf = ctypes.create_string_buffer(_JOB_BYTES * _lib.HCG_REDUCE_MAX_JOBS)
+        self.addr, self.n = ctypes.addressof(self.buf), 0
+
+    def slot(self) -> int:
+        return self.addr + self.n * _JOB_BYTES
+
+    def add(self, n: int):
+        """Count n more jobs; a full array is reduced right away (one launch)."""
+        self.n += n
+        if self.n == _lib.HCG_REDUCE_MAX_JOBS:
+            self.flush()
+
+    def flush(self):
+        if self.n:
+            _lib.reduce_jobs(self.addr, self.n)
+            self.n = 0
 
 
 # 64-wide layers: the dense-parts backward of csrc/tall.hip pays off once a batch fills the chip several times over; below
@@ -387,18 +350,102 @@ class _TallLayerFn(torch.autograd.Function):
 TALL_MIN_NODES_D64 = 140000
 
 
-def tall_supported(plan: BatchPlan, F: int, D: int) -> bool:
-    """True when the kernels of csrc/tall.hip apply to this plan / layer shape (D = 128; D = 64 over graphs > 64 nodes)."""
-    if (plan.mode != "blocked" or plan.ew_csr is not None or plan.max_nodes is None or plan.max_edges is None
-            or plan.B == 0 or plan.N == 0):
-        return False
-    if D == 64 and plan.N < TALL_MIN_NODES_D64:
+def fused_graphs_per_tile(plan: Optional[BatchPlan], F: int, D: int, max_nodes: Optional[int] = None) -> int:
+    """> 0 when the fused small-graph kernels apply to this plan / layer shape.  `max_nodes` replaces the plan's largest
+    graph; with `plan=None` it is all there is (a batch's collate metadata: no plan checks)."""
+    if plan is not None:
+        if plan.mode != "blocked" or plan.ew_csr is not None or plan.max_nodes is None or plan.B == 0:
+            return 0
+        max_nodes = plan.max_nodes if max_nodes is None else max_nodes
+    return int(_lib.load().hcg_fused_graphs_per_tile(F, D, max_nodes))
+
+
+def _per_graph_plan(plan: BatchPlan) -> bool:
+    return not (plan.mode != "blocked" or plan.ew_csr is not None or plan.max_nodes is None or plan.max_edges is None
+                or plan.B == 0 or plan.N == 0)
+
+
+def mid_supported(plan: Optional[BatchPlan], F: int, D: int, max_nodes: Optional[int] = None,
+                  max_edges: Optional[int] = None) -> bool:
+    """True when the one-graph-per-workgroup kernels apply to this plan / layer shape (`plan=None`, `max_nodes`: as
+    `fused_graphs_per_tile`)."""
+    if plan is not None:
+        if not _per_graph_plan(plan):
+            return False
+        max_nodes, max_edges = plan.max_nodes if max_nodes is None else max_nodes, plan.max_edges
+    return max_edges is not None and bool(_lib.load().hcg_mid_supported(F, D, max_nodes, max_edges))
+
+
+def tall_supported(plan: BatchPlan, F: int, D: int, any_rows: bool = False) -> bool:
+    """True when the kernels of csrc/tall.hip apply to this plan / layer shape (D = 128; D = 64 over graphs > 64 nodes in
+    batches of at least TALL_MIN_NODES_D64 rows -- `any_rows`: of any row count)."""
+    if not _per_graph_plan(plan) or (D == 64 and plan.N < TALL_MIN_NODES_D64 and not any_rows):
         return False
     return bool(_lib.load().hcg_tall_supported(F, D, plan.max_nodes, plan.max_edges))
 
 
-def tall_gcn_layer(x, weight, bias, plan: BatchPlan, apply_act=True, slope=LEAKY_SLOPE, pool=False):
-    return _TallLayerFn.apply(x, weight, bias, plan, apply_act, slope, pool)
+def conv_route(plan: Optional[BatchPlan], F: int, D: int, family: str = "auto", *, max_nodes=None, max_edges=None):
+    """Which fused family takes a conv layer F -> D: (TILES, graphs_per_tile), (TALL, 0), (MID, 0), or (None, 0) = none
+    (the any-shape kernels).  Tiles first; then, where the one-graph-per-workgroup kernels apply, the wide-layer route
+    unless `family == "mid"` (every layer it takes, mid.hip takes too), else mid.hip.  `max_nodes` replaces the plan's
+    largest graph; `plan=None` asks from a batch's collate metadata alone (`max_nodes`, `max_edges`: no plan checks, and
+    never the wide-layer route, which needs the batch's row count)."""
+    gpt = fused_graphs_per_tile(plan, F, D, max_nodes)
+    if gpt > 0:
+        return TILES, gpt
+    if not mid_supported(plan, F, D, max_nodes, max_edges):
+        return None, 0
+    return (TALL if plan is not None and family != "mid" and tall_supported(plan, F, D) else MID), 0
+
+
+class _ConvLayerFn(torch.autograd.Function):
+    """One launch per layer (and per direction) on a fused family (`conv_route`): returns the node embeddings, or -- with
+    `pool=True`, the last conv layer -- the pooled graph embedding [max, mean] directly (the node embeddings stay internal,
+    saved for the backward)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, plan: BatchPlan, fam, gpt: int, apply_act: bool, slope: float, pool: bool):
+        _lib.require_gpu(x, weight, bias)
+        x, weight, bias = _f32c(x), _f32c(weight), _f32c(bias)
+        N, F = x.shape
+        D = weight.shape[0]
+        if weight.shape[1] != F or N != plan.N:
+            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, weight {tuple(weight.shape)}, plan N {plan.N}")
+        dev, geo = x.device, geometry(plan)
+        out = torch.empty(N, D, dtype=torch.float32, device=dev)
+        emb = torch.empty(plan.B, 2 * D, dtype=torch.float32, device=dev) if pool else None
+        extra = {}
+        if fam is TALL:
+            wsb = TALL.workspace_bytes(geo, gpt, F, D) if D != 64 else 0     # (64-wide: the forward needs none)
+            extra = dict(ws=torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None, wsb=wsb)
+        fam.forward(geo, gpt, x, weight, bias, int(apply_act), out=out, emb=emb, slope=slope, **extra)
+        ctx.plan, ctx.fam, ctx.gpt, ctx.apply_act, ctx.slope, ctx.pool = plan, fam, gpt, apply_act, slope, pool
+        ctx.save_for_backward(x, weight, out, *([emb] if pool else []))
+        return emb if pool else out
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, weight, out, *emb = ctx.saved_tensors
+        fam, gpt, geo = ctx.fam, ctx.gpt, geometry(ctx.plan)
+        N, F = x.shape
+        D = weight.shape[0]
+        dev = x.device
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dW = torch.empty_like(weight)
+        db = torch.empty(D, dtype=torch.float32, device=dev)
+        wsb = fam.workspace_bytes(geo, gpt, F, D)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        up = dict(demb=_f32c(grad), emb=emb[0]) if ctx.pool else dict(dout=_f32c(grad))
+        fam.backward(geo, gpt, x, weight, int(ctx.apply_act), out=out, dx=dx, ws=ws, wsb=wsb, slope=ctx.slope, **up)
+        jobs = JobList()
+        jobs.n = fam.reduce_jobs(geo, gpt, F, D, ws, wsb, dW, db, jobs.slot())
+        jobs.flush()
+        return dx, dW, db, None, None, None, None, None, None
+
+
+def conv_layer(x, weight, bias, plan: BatchPlan, fam, gpt: int = 0, apply_act=True, slope=LEAKY_SLOPE, pool=False):
+    """A conv layer on the family `conv_route` picked (fam, gpt)."""
+    return _ConvLayerFn.apply(x, weight, bias, plan, fam, gpt, apply_act, slope, pool)
 
 
 class _Readout2Fn(torch.autograd.Function):
@@ -503,25 +550,19 @@ class _FusedModelFn(torch.autograd.Function):
         if N != plan.N:
             raise ValueError(f"x has {N} rows, plan was built for {plan.N}")
         D = convs[0].shape[0]
-        acts, h = [], x
+        acts, geo = [], geometry(plan)
         emb = torch.empty(plan.B, 2 * D, dtype=torch.float32, device=dev)
         if n_conv == 2 and gpts[0] == gpts[1]:
             # the reference's default depth: both conv layers in ONE launch (csrc/fused.hip, STACK2)
-            a1 = torch.empty(N, D, dtype=torch.float32, device=dev)
-            a2 = torch.empty(N, D, dtype=torch.float32, device=dev)
-            _lib.fused_forward(x=x, W1=convs[0], b1=convs[1], W2=convs[2], b2=convs[3], edge_index=plan.edge_index, E=plan.E,
-                               graph_ptr=plan.graph_ptr, edge_ptr=plan.edge_ptr, N=N, B=plan.B, F=x.shape[1], D=D,
-                               graphs_per_tile=gpts[0], apply_act=1, slope=slope, out1=a1, out2=a2, emb=emb, status=plan.status)
-            acts = [a1, a2]
+            acts = [torch.empty(N, D, dtype=torch.float32, device=dev) for _ in range(2)]
+            TILES.forward(geo, gpts[0], x, convs[0], convs[1], 1, out=acts[0], emb=emb, slope=slope, W2=convs[2], b2=convs[3],
+                          out2=acts[1])
         else:
             for l in range(n_conv):
-                W, b = convs[2 * l], convs[2 * l + 1]
-                out = torch.empty(N, D, dtype=torch.float32, device=dev)
-                _lib.fused_forward(x=h, W1=W, b1=b, edge_index=plan.edge_index, E=plan.E, graph_ptr=plan.graph_ptr,
-                                   edge_ptr=plan.edge_ptr, N=N, B=plan.B, F=h.shape[1], D=D, graphs_per_tile=gpts[l], apply_act=1,
-                                   slope=slope, out1=out, emb=emb if l == n_conv - 1 else None, status=plan.status)
-                acts.append(out)
-                h = out
+                h = torch.empty(N, D, dtype=torch.float32, device=dev)
+                TILES.forward(geo, gpts[l], acts[-1] if l else x, convs[2 * l], convs[2 * l + 1], 1, out=h,
+                              emb=emb if l == n_conv - 1 else None, slope=slope)
+                acts.append(h)
         C = R1w.shape[0]
         z = torch.empty(plan.B, D, dtype=torch.float32, device=dev)
         y = torch.empty(plan.B, C, dtype=torch.float32, device=dev)
@@ -541,16 +582,12 @@ class _FusedModelFn(torch.autograd.Function):
         x, emb, z = saved[0], saved[1], saved[2]
         acts, params = saved[3:3 + n_conv], saved[3 + n_conv:]
         convs, (R0w, R0b, R1w, R1b) = params[:2 * n_conv], params[2 * n_conv:]
-        N, dev, stream = x.shape[0], x.device, _lib.stream_ptr()
+        dev, stream = x.device, _lib.stream_ptr()
         D, C, B = convs[0].shape[0], R1w.shape[0], plan.B
         f32 = dict(dtype=torch.float32, device=dev)
-        # every backward kernel leaves per-workgroup slabs; ONE batched launch reduces them all at the end
-        import ctypes
-        jb = _lib.job_bytes()
-        batched = n_conv + 1 <= 8
-        jobs = ctypes.create_string_buffer(jb * 8) if batched else None
-        jaddr = ctypes.addressof(jobs) if batched else 0
-        keep = []                                   # workspaces must outlive the batched reduction's enqueue
+        # every backward kernel leaves per-workgroup slabs; ONE batched launch reduces them all at the end (a model deeper
+        # than seven conv layers: one launch per HCG_REDUCE_MAX_JOBS of them)
+        jobs, keep = JobList(), []                  # workspaces must outlive the reductions' enqueue
         # All weight gradients are views of ONE flat buffer laid out in nn.Module parameter order
         # (conv: bias, lin.weight; readout: weight, bias) -- the data-parallel wrapper can then all-reduce it
         # in place, without first concatenating 8 small tensors.
@@ -573,73 +610,39 @@ class _FusedModelFn(torch.autograd.Function):
         wsb = lib.hcg_general_workspace_bytes(_lib.HCG_WS_READOUT2, B, 0, 0, 0)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         keep.append(ws)
-        if batched:
-            rc = lib.hcg_readout2_bwd_partial(_lib.ptr(dy), _lib.ptr(emb), _lib.ptr(z), _lib.ptr(R0w), _lib.ptr(R1w), B, D, C,
-                                              slope, _lib.ptr(demb), _lib.ptr(ws), wsb, stream)
-            _lib.check(rc, "hcg_readout2_bwd_partial")
-            _lib.check(lib.hcg_readout2_reduce_job(_lib.ptr(ws), wsb, B, C, _lib.ptr(dR0w), _lib.ptr(dR0b), _lib.ptr(dR1w),
-                                                   _lib.ptr(dR1b), jaddr), "hcg_readout2_reduce_job")
-        else:
-            rc = lib.hcg_readout2_bwd_partial(_lib.ptr(dy), _lib.ptr(emb), _lib.ptr(z), _lib.ptr(R0w), _lib.ptr(R1w), B, D, C,
-                                              slope, _lib.ptr(demb), _lib.ptr(ws), wsb, stream)
-            _lib.check(rc, "hcg_readout2_bwd_partial")
-            rjob = _lib.ReduceJob()
-            _lib.check(lib.hcg_readout2_reduce_job(_lib.ptr(ws), wsb, B, C, _lib.ptr(dR0w), _lib.ptr(dR0b), _lib.ptr(dR1w),
-                                                   _lib.ptr(dR1b), ctypes.addressof(rjob)), "hcg_readout2_reduce_job")
-            _lib.reduce_jobs(ctypes.addressof(rjob), 1)
+        rc = lib.hcg_readout2_bwd_partial(_lib.ptr(dy), _lib.ptr(emb), _lib.ptr(z), _lib.ptr(R0w), _lib.ptr(R1w), B, D, C,
+                                          slope, _lib.ptr(demb), _lib.ptr(ws), wsb, stream)
+        _lib.check(rc, "hcg_readout2_bwd_partial")
+        _lib.check(lib.hcg_readout2_reduce_job(_lib.ptr(ws), wsb, B, C, _lib.ptr(dR0w), _lib.ptr(dR0b), _lib.ptr(dR1w),
+                                               _lib.ptr(dR1b), jobs.slot()), "hcg_readout2_reduce_job")
+        jobs.add(1)
         if demb_ext is not None:          # the caller also used graph_emb downstream
             demb = demb + _f32c(demb_ext)
         # conv stack, last layer first
+        geo = geometry(plan)
         grads = [None] * (2 * n_conv)
         dh = None
-        njobs = 1
         for l in reversed(range(n_conv)):
             W = convs[2 * l]
             inp = x if l == 0 else acts[l - 1]
             F = inp.shape[1]
-            need_dx = l > 0 or ctx.needs_input_grad[3]
-            dx = torch.empty_like(inp) if need_dx else None
+            dx = torch.empty_like(inp) if (l > 0 or ctx.needs_input_grad[3]) else None
             dW, db = conv_dW[l], conv_db[l]
-            wsb = lib.hcg_fused_workspace_bytes(B, F, D, gpts[l])
+            wsb = TILES.workspace_bytes(geo, gpts[l], F, D)
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
             keep.append(ws)
-            last = l == n_conv - 1
-            rc = lib.hcg_fused_layer_bwd(None if last else _lib.ptr(dh), _lib.ptr(demb) if last else None,
-                                         _lib.ptr(emb) if last else None, _lib.ptr(acts[l]), None, _lib.ptr(inp), _lib.ptr(W),
-                                         _lib.ptr(plan.edge_index), plan.E, _lib.ptr(plan.graph_ptr), _lib.ptr(plan.edge_ptr),
-                                         N, B, F, D, gpts[l], slope, 1, _lib.ptr(dx), _lib.ptr(plan.status), _lib.ptr(ws), wsb,
-                                         stream)
-            _lib.check(rc, "hcg_fused_layer_bwd")
-            if batched:
-                _lib.check(lib.hcg_fused_reduce_job(_lib.ptr(ws), wsb, N, B, F, D, gpts[l], _lib.ptr(dW), _lib.ptr(db),
-                                                    jaddr + njobs * jb), "hcg_fused_reduce_job")
-                njobs += 1
-            else:
-                job = _lib.ReduceJob()
-                _lib.check(lib.hcg_fused_reduce_job(_lib.ptr(ws), wsb, N, B, F, D, gpts[l], _lib.ptr(dW), _lib.ptr(db),
-                                                    ctypes.addressof(job)), "hcg_fused_reduce_job")
-                _lib.reduce_jobs(ctypes.addressof(job), 1)
+            up = dict(demb=demb, emb=emb) if l == n_conv - 1 else dict(dout=dh)
+            TILES.backward(geo, gpts[l], inp, W, 1, out=acts[l], dx=dx, ws=ws, wsb=wsb, slope=slope, stream=stream, **up)
+            jobs.add(TILES.reduce_jobs(geo, gpts[l], F, D, ws, wsb, dW, db, jobs.slot()))
             grads[2 * l], grads[2 * l + 1] = dW, db
             dh = dx
-        if batched:
-            _lib.reduce_jobs(jaddr, njobs)
+        jobs.flush()
         return (None, None, None, dh if ctx.needs_input_grad[3] else None, *grads, dR0w, dR0b, dR1w, dR1b)
 
 
 def fused_model(plan: BatchPlan, gpts, x, conv_params, readout_params, slope=LEAKY_SLOPE):
     """-> (out [B, C], graph_emb [B, 2D]).  conv_params = [W1, b1, W2, b2, ...], readout_params = [W0, b0, W1, b1]."""
     return _FusedModelFn.apply(plan, tuple(gpts), slope, x, *conv_params, *readout_params)
-
-
-def fused_graphs_per_tile(plan: BatchPlan, F: int, D: int) -> int:
-    """> 0 when the fused small-graph kernels apply to this plan / layer shape."""
-    if plan.mode != "blocked" or plan.ew_csr is not None or plan.max_nodes is None or plan.B == 0:
-        return 0
-    return int(_lib.load().hcg_fused_graphs_per_tile(F, D, plan.max_nodes))
-
-
-def fused_gcn_layer(x, weight, bias, plan: BatchPlan, gpt: int, apply_act=True, slope=LEAKY_SLOPE, pool=False):
-    return _FusedLayerFn.apply(x, weight, bias, plan, gpt, apply_act, slope, pool)
 
 
 def gcn_layer(x, weight, bias, plan: BatchPlan, use_edge_weight=False, apply_act=True, slope=LEAKY_SLOPE, edge_mult=None):

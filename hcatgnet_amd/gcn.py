@@ -57,13 +57,10 @@ class GCNConv(nn.Module):
             m = self._edge_mask.sigmoid() if self._apply_sigmoid else self._edge_mask
             h = HF.gcn_layer(x, self.lin.weight, self.bias, plan, use_edge_weight, apply_act, edge_mult=m)
             return HF.graph_pool(h, plan) if pool else h
-        gpt = 0 if (use_edge_weight or not fused) else HF.fused_graphs_per_tile(plan, self.in_channels, self.out_channels)
-        if gpt > 0:
-            return HF.fused_gcn_layer(x, self.lin.weight, self.bias, plan, gpt, apply_act, pool=pool)
-        if fused and not use_edge_weight and self.family != "mid" and HF.tall_supported(plan, self.in_channels, self.out_channels):
-            return HF.tall_gcn_layer(x, self.lin.weight, self.bias, plan, apply_act, pool=pool)  # wide layer, large graphs
-        if fused and not use_edge_weight and HF.mid_supported(plan, self.in_channels, self.out_channels):
-            return HF.mid_gcn_layer(x, self.lin.weight, self.bias, plan, apply_act, pool=pool)   # one graph per workgroup
+        if fused and not use_edge_weight:
+            fam, gpt = HF.conv_route(plan, self.in_channels, self.out_channels, self.family)
+            if fam is not None:
+                return HF.conv_layer(x, self.lin.weight, self.bias, plan, fam, gpt, apply_act, pool=pool)
         h = HF.gcn_layer(x, self.lin.weight, self.bias, plan, use_edge_weight, apply_act)
         return HF.graph_pool(h, plan) if pool else h
 

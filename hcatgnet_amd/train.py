@@ -35,8 +35,8 @@ from . import functional as HF
 class _Ctx:
     """Everything one step needs, resolved once: shapes, weights, buffers, the kernel family of every layer."""
     __slots__ = ("batch", "plan", "x", "y2", "convs", "l0", "l1", "N", "F", "B", "D", "C", "n_conv", "dev", "W", "bs",
-                 "gpts", "tall", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word",
-                 "jobs", "jaddr", "jb", "njobs", "loss_mode", "sse_split", "poolbits", "xagg")
+                 "routes", "geo", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
+                 "loss_mode", "sse_split", "poolbits", "xagg")
 
 
 class FusedTrainStep:
@@ -68,7 +68,6 @@ class FusedTrainStep:
     POOLBITS = True
     XAGG_MID = True                # ... and behind the one-graph-per-workgroup kernels (batches under functional.TALL_MIN_NODES_D64)
     XAGG = True                    # first layer on the wide-layer route: Ahat x + sign pieces from the forward, one dense backward launch
-    TALL_PREMASK = False           # (measured: the dense dx kernel's strided mask loads cost what the layer below saves -- DESIGN 7)
     PREMASK = True
     HEAD_IN_FORWARD = True
     OVERLAP_GROUPS = True          # captured size-grouped steps: the two kernel families as two branches of the hipGraph
@@ -136,7 +135,6 @@ class FusedTrainStep:
             return "fused kernels disabled on the model"
         if model.n_convolutions + 1 > 4:
             return "more than 3 conv layers"
-        lib = _lib.load()
         # (heads the one-launch kernel does not cover -- widths other than 64 / 128 -- run as five launches of the any-shape
         #  kernels inside the same no-autograd step)
         if type(model.loss).__name__ != "MSELoss":
@@ -152,8 +150,7 @@ class FusedTrainStep:
             me = getattr(batch, "max_edges", None)
             convs = [model.conv1] + list(model.conv_layers)
             for c in convs:
-                if lib.hcg_fused_graphs_per_tile(c.in_channels, c.out_channels, mx) <= 0 and not (
-                        me is not None and lib.hcg_mid_supported(c.in_channels, c.out_channels, mx, me)):
+                if HF.conv_route(None, c.in_channels, c.out_channels, max_nodes=mx, max_edges=me)[0] is None:
                     return "graph / layer shape outside the fused kernels (small-graph tiles and one-graph-per-workgroup)"
         return None
 
@@ -194,13 +191,10 @@ class FusedTrainStep:
             self._bufs = {"cap": cap, key: b}          # views of the current shape (one live shape at a time)
         return b
 
-    def _tall_ws(self, bufs, l, N, B, F, D, dev):
+    def _tall_ws(self, c: _Ctx, l, F):
         """Workspace of layer l's wide-layer kernels (H / dH round trip + gradient slabs): forward and backward share it."""
-        wsb = _lib.load().hcg_tall_workspace_bytes(N, B, F, D)
-        ws = bufs["ws"].get(("tall", l))
-        if ws is None or ws.numel() < wsb:
-            ws = bufs["ws"][("tall", l)] = torch.empty(int(wsb * 1.25), dtype=torch.uint8, device=dev)
-        return ws, wsb
+        wsb = HF.TALL.workspace_bytes(c.geo, 0, F, c.D)
+        return self._ws(c.bufs, ("tall", l), wsb, c.dev), wsb
 
     def _ws(self, bufs, key, nbytes, dev):
         ws = bufs["ws"].get(key)
@@ -261,22 +255,17 @@ class FusedTrainStep:
         c.y2 = HF._f32c(y).reshape(c.B, -1)
         if c.y2.shape[1] != c.C:
             raise ValueError(f"targets have {c.y2.shape[1]} columns, the model predicts {c.C}")
-        # kernel family per layer: gpt > 0 = small-graph tiles (csrc/fused.hip), 0 = one graph per workgroup (csrc/mid.hip)
-        c.gpts = [HF.fused_graphs_per_tile(plan, cv.in_channels, cv.out_channels) for cv in convs]
-        for cv, gpt in zip(convs, c.gpts):
-            if gpt <= 0 and not HF.mid_supported(plan, cv.in_channels, cv.out_channels):
-                raise _lib.HcgError("FusedTrainStep: graph / layer shape outside the fused kernels")
-        # 128-wide layers over large graphs: dense row-streaming transform + per-graph segmented sum (csrc/tall.hip)
-        c.tall = [gpt <= 0 and getattr(cv, "family", "auto") != "mid" and HF.tall_supported(plan, cv.in_channels, cv.out_channels)
-                  for cv, gpt in zip(convs, c.gpts)]
+        # (kernel family, graphs_per_tile) of every layer (functional.conv_route)
+        c.routes = [HF.conv_route(plan, cv.in_channels, cv.out_channels, getattr(cv, "family", "auto")) for cv in convs]
+        if (None, 0) in c.routes:
+            raise _lib.HcgError("FusedTrainStep: graph / layer shape outside the fused kernels")
+        c.geo = HF.geometry(plan)
         c.bufs = self._buffers((c.N, c.B, c.F, plan.E), c.N, c.B, c.F, c.D, c.C, c.n_conv, c.dev)
         c.W = [HF._f32c(cv.lin.weight) for cv in convs]
         c.bs = [HF._f32c(cv.bias) for cv in convs]
         c.head_fused = bool(lib.hcg_head_supported(c.D, c.C))
         c.n_small = self._size_groups(batch, plan, convs, c.D, c.C, c.n_conv)
-        c.jb = _lib.job_bytes()
-        c.jobs = ctypes.create_string_buffer(c.jb * _lib.HCG_REDUCE_MAX_JOBS)
-        c.jaddr, c.njobs = ctypes.addressof(c.jobs), 0
+        c.jobs = HF.JobList()
         c.flat = c.gaddr = c.step_word = None
         c.poolbits = None
         c.xagg = None
@@ -315,129 +304,103 @@ class FusedTrainStep:
         nodes, the others 33 .. 64) and both groups are non-empty: the small graphs then run in the small-graph tiles, the
         larger ones one graph per wave, instead of everything on the slower family."""
         ns = getattr(batch, "n_small", None)
-        lib = _lib.load()
-        if (ns is None or not (0 < ns < plan.B) or n_conv != 2 or D != 64 or not lib.hcg_head_supported(D, C)
+        if (ns is None or not (0 < ns < plan.B) or n_conv != 2 or D != 64 or not _lib.load().hcg_head_supported(D, C)
                 or plan.max_nodes is None or plan.max_nodes <= 32 or plan.max_edges is None):
             return None
-        for c in convs:
-            if lib.hcg_fused_graphs_per_tile(c.in_channels, c.out_channels, 32) <= 0:
-                return None
-            if not HF.mid_supported(plan, c.in_channels, c.out_channels):
+        for c in convs:       # (the larger graphs: one graph per wave whatever the conv's family preference)
+            if (HF.conv_route(plan, c.in_channels, c.out_channels, max_nodes=32)[0] is not HF.TILES
+                    or HF.conv_route(plan, c.in_channels, c.out_channels, "mid")[0] is not HF.MID):
                 return None
         return int(ns)
 
     def _g(self, c: _Ctx, prm) -> int:
         return c.gaddr[id(prm)]
 
-    def _job_slot(self, c: _Ctx) -> int:
-        return c.jaddr + c.njobs * c.jb
-
-    def _tiles_args(self, c: _Ctx, B, gpt, **extra):
-        plan = c.plan
-        return dict(x=c.x, W1=c.W[0], b1=c.bs[0], W2=c.W[1], b2=c.bs[1], edge_index=plan.edge_index, E=plan.E,
-                    graph_ptr=plan.graph_ptr, edge_ptr=plan.edge_ptr, N=c.N, B=B, F=c.F, D=c.D, graphs_per_tile=gpt,
-                    apply_act=1, slope=HF.LEAKY_SLOPE, out1=c.bufs["acts"][0], emb=c.bufs["emb"], status=plan.status, **extra)
+    def _tiles_stack(self, c: _Ctx, geo, gpt, **extra):
+        """Both conv layers (+ pooling) on the small-graph tiles: one launch."""
+        HF.TILES.forward(geo, gpt, c.x, c.W[0], c.bs[0], 1, out=c.bufs["acts"][0], emb=c.bufs["emb"], W2=c.W[1], b2=c.bs[1],
+                         **extra)
 
     def _head_in_forward(self, c: _Ctx) -> bool:
         """The C3 form: both conv layers on small-graph tiles, pooled layer on chip, one-launch head -> everything up to
         the loss is ONE launch."""
         return (self.HEAD_IN_FORWARD and self.POOLBITS and c.n_small is None and c.n_conv == 2 and c.head_fused
-                and c.gpts[0] == c.gpts[1] and c.gpts[0] > 0)
+                and c.routes[0][0] is HF.TILES and c.routes[0] == c.routes[1])
 
     def _forward_with_head(self, c: _Ctx):
         """conv stack + pooling + readout head (forward, squared error, unscaled readout backward): one launch."""
-        lib, bufs, gpt = _lib.load(), c.bufs, c.gpts[0]
+        lib, bufs, gpt = _lib.load(), c.bufs, c.routes[0][1]
         c.poolbits = self._ws(bufs, "poolbits", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, c.B, gpt), c.dev)
         l0, l1 = c.l0, c.l1
-        _lib.fused_forward(**self._tiles_args(
-            c, c.B, gpt, poolbits=c.poolbits, y=c.y2, head_W0=HF._f32c(l0.weight), head_b0=HF._f32c(l0.bias),
-            head_W1=HF._f32c(l1.weight), head_b1=HF._f32c(l1.bias), C=c.C, z=bufs["z"], out=bufs["out"], demb=bufs["demb"],
+        self._tiles_stack(
+            c, c.geo, gpt, poolbits=c.poolbits, y=c.y2, head_W0=HF._f32c(l0.weight), head_b0=HF._f32c(l0.bias),
+            head_W1=HF._f32c(l1.weight), head_b1=HF._f32c(l1.bias), C=c.C, z=bufs["z"], head_out=bufs["out"], demb=bufs["demb"],
             head_workspace=bufs["ws_head"], head_workspace_bytes=bufs["ws_head_bytes"], step_counter=c.step_word,
-            head_flags=_lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0))
+            head_flags=_lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0)
         g = (lambda q: self._g(c, q)) if not c.forward_only else (lambda q: None)
         _lib.check(lib.hcg_fused_head_reduce_job(_lib.ptr(bufs["ws_head"]), bufs["ws_head_bytes"], c.B, gpt, c.C, g(l0.weight),
-                                                 g(l0.bias), g(l1.weight), g(l1.bias), self._job_slot(c)),
+                                                 g(l0.bias), g(l1.weight), g(l1.bias), c.jobs.slot()),
                    "hcg_fused_head_reduce_job")
-        c.njobs += 1
+        c.jobs.n += 1
 
     def _forward_layers(self, c: _Ctx):
         """The conv stack (+ pooling) of every other shape: one launch per layer (stacked pair: one)."""
-        lib, plan, bufs = _lib.load(), c.plan, c.bufs
-        p, stream, slope = _lib.ptr, _lib.stream_ptr(), HF.LEAKY_SLOPE
-        acts, emb, gpts, n_conv, N, B, D = bufs["acts"], bufs["emb"], c.gpts, c.n_conv, c.N, c.B, c.D
-        mxn, mxe = plan.max_nodes, plan.max_edges
+        lib, bufs, geo = _lib.load(), c.bufs, c.geo
+        acts, emb, routes, n_conv, N, B, D = bufs["acts"], bufs["emb"], c.routes, c.n_conv, c.N, c.B, c.D
         # small-graph tiles: the pooled layer's activations stay on chip, two bits per element (sign, is-the-column-max)
         # are all its backward needs of them
-        if gpts[-1] > 0 and self.POOLBITS:
-            c.poolbits = self._ws(bufs, "poolbits", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, B, gpts[-1]), c.dev)
-        if n_conv == 2 and gpts[0] == gpts[1] and gpts[0] > 0:
-            _lib.fused_forward(**self._tiles_args(c, B, gpts[0], poolbits=c.poolbits,
-                                                  out2=None if c.poolbits is not None else acts[1]))
+        if routes[-1][0] is HF.TILES and self.POOLBITS:
+            c.poolbits = self._ws(bufs, "poolbits", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, B, routes[-1][1]), c.dev)
+        if n_conv == 2 and routes[0][0] is HF.TILES and routes[0] == routes[1]:
+            self._tiles_stack(c, geo, routes[0][1], poolbits=c.poolbits, out2=None if c.poolbits is not None else acts[1])
             return
         h = c.x
-        for l in range(n_conv):
+        for l, (fam, gpt) in enumerate(routes):
             pe = emb if l == n_conv - 1 else None
             Fl = h.shape[1]
-            if gpts[l] > 0:
+            if fam is HF.TILES:
                 bits = c.poolbits if pe is not None else None
-                _lib.fused_forward(x=h, W1=c.W[l], b1=c.bs[l], edge_index=plan.edge_index, E=plan.E, graph_ptr=plan.graph_ptr,
-                                   edge_ptr=plan.edge_ptr, N=N, B=B, F=Fl, D=D, graphs_per_tile=gpts[l], apply_act=1,
-                                   slope=slope, out1=None if bits is not None else acts[l], emb=pe, poolbits=bits,
-                                   status=plan.status)
-            elif c.tall[l]:
-                ws, wsb = self._tall_ws(bufs, l, N, B, Fl, D, c.dev)
+                fam.forward(geo, gpt, h, c.W[l], c.bs[l], 1, out=None if bits is not None else acts[l], emb=pe, poolbits=bits)
+            elif fam is HF.TALL:
+                ws, wsb = self._tall_ws(c, l, Fl)
                 bits = None
                 if pe is not None and self.POOLBITS and Fl <= (64 if D == 64 else 128):
                     # the pooled layer's activations stay on chip: one byte per (row, 4 columns) -- sign, is-the-column-max --
                     # is all its backward (csrc/tall.hip: k_gseg_bwd) needs of them
                     bits = c.poolbits = self._ws(bufs, "poolbits_tall", N * (D // 4), c.dev)
                 xagg = signs = None
-                if (l == 0 and n_conv >= 2 and (Fl <= 64 or D == 128) and self.XAGG and not c.forward_only and c.tall[1]):
+                if (l == 0 and n_conv >= 2 and (Fl <= 64 or D == 128) and self.XAGG and not c.forward_only
+                        and routes[1][0] is HF.TALL):
                     # training form of the FIRST layer: Ahat x [N, 32 | 64 | 128] and the sign pieces of its output leave too; its
                     # whole backward is then ONE dense launch (csrc/tall.hip: k_tall_dw<FIRST>) -- no transpose sum, no dH round trip
-                    kp = 32 if Fl <= 32 else (64 if Fl <= 64 else 128)
-                    xagg = self._ws(bufs, "xagg", N * kp * 4, c.dev)
-                    signs = self._ws(bufs, "signs", N * (D // 8), c.dev)
-                    c.xagg = (xagg, signs)
-                rc = lib.hcg_tall_layer_fwd(p(h), p(c.W[l]), p(c.bs[l]), p(plan.edge_index), plan.E, p(plan.graph_ptr),
-                                            p(plan.edge_ptr), N, B, Fl, D, mxn, mxe, slope, 1, None if bits is not None else p(acts[l]),
-                                            p(pe), p(bits), p(xagg), p(signs), p(plan.status), p(ws), wsb, stream)
-                _lib.check(rc, "hcg_tall_layer_fwd")
+                    xagg, signs = self._xagg(c, 32 if Fl <= 32 else (64 if Fl <= 64 else 128))
+                fam.forward(geo, 0, h, c.W[l], c.bs[l], 1, out=None if bits is not None else acts[l], emb=pe, poolbits=bits,
+                            xagg=xagg, signs=signs, ws=ws, wsb=wsb)
             else:
                 xagg = signs = None
                 if (l == 0 and n_conv >= 2 and D == 64 and Fl <= 64 and self.XAGG and self.XAGG_MID and not c.forward_only
-                        and gpts[1] <= 0 and lib.hcg_tall_supported(Fl, D, mxn, mxe)):
-                    kp = 32 if Fl <= 32 else 64            # (as on the wide-layer route: Ahat x + sign pieces for the dense backward)
-                    xagg = self._ws(bufs, "xagg", N * kp * 4, c.dev)
-                    signs = self._ws(bufs, "signs", N * (D // 8), c.dev)
-                    c.xagg = (xagg, signs)
-                rc = lib.hcg_mid_layer_fwd(p(h), p(c.W[l]), p(c.bs[l]), p(plan.edge_index), plan.E, p(plan.graph_ptr),
-                                           p(plan.edge_ptr), N, B, Fl, D, mxn, mxe, slope, 1, p(acts[l]), p(pe), None, p(xagg), p(signs),
-                                           p(plan.status), stream)
-                _lib.check(rc, "hcg_mid_layer_fwd")
+                        and routes[1][0] is not HF.TILES and HF.tall_supported(c.plan, Fl, D, any_rows=True)):
+                    # (as on the wide-layer route: Ahat x + sign pieces for the dense backward)
+                    xagg, signs = self._xagg(c, 32 if Fl <= 32 else 64)
+                fam.forward(geo, 0, h, c.W[l], c.bs[l], 1, out=acts[l], emb=pe, xagg=xagg, signs=signs)
             h = acts[l]
 
-    def _forward_routed(self, c: _Ctx, fork, join, stream_b):
+    def _xagg(self, c: _Ctx, kp):
+        """Buffers of the first layer's training form: Ahat x [N, kp] and the sign pieces of its output."""
+        c.xagg = (self._ws(c.bufs, "xagg", c.N * kp * 4, c.dev), self._ws(c.bufs, "signs", c.N * (c.D // 8), c.dev))
+        return c.xagg
+
+    def _forward_routed(self, c: _Ctx, geo_a, geo_b, gpt, fork, join, stream_b):
         """Size-grouped batch: graphs [0, n_small) through the tiles (both layers + pooling in one launch, pooled layer on
-        chip), graphs [n_small, B) one graph per wave -- every launch gets the sub-range of graph_ptr / edge_ptr / emb it
-        owns; node rows are absolute, so x and the activations need no offsets."""
-        lib, plan, bufs = _lib.load(), c.plan, c.bufs
-        p, slope = _lib.ptr, HF.LEAKY_SLOPE
-        Bs, Bb = c.n_small, c.B - c.n_small
-        gp_b, ep_b = plan.graph_ptr.data_ptr() + 4 * Bs, plan.edge_ptr.data_ptr() + 4 * Bs
-        acts, emb = bufs["acts"], bufs["emb"]
-        emb_b = emb.data_ptr() + 4 * 2 * c.D * Bs
-        gpt = int(lib.hcg_fused_graphs_per_tile(c.F, c.D, 32))
-        c.poolbits = self._ws(bufs, "poolbits_r", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, Bs, gpt), c.dev)
-        mxn, mxe = plan.max_nodes, plan.max_edges
+        chip), graphs [n_small, B) one graph per wave (`geo_a`, `geo_b`)."""
+        bufs = c.bufs
+        acts = bufs["acts"]
+        c.poolbits = self._ws(bufs, "poolbits_r", _lib.load().hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, geo_a.B, gpt), c.dev)
         fork()
-        _lib.fused_forward(**self._tiles_args(c, Bs, gpt, poolbits=c.poolbits))
-        _lib.check(lib.hcg_mid_layer_fwd(p(c.x), p(c.W[0]), p(c.bs[0]), p(plan.edge_index), plan.E, gp_b, ep_b, c.N, Bb, c.F, c.D,
-                                         mxn, mxe, slope, 1, p(acts[0]), None, None, None, None, p(plan.status), stream_b), "hcg_mid_layer_fwd")
-        _lib.check(lib.hcg_mid_layer_fwd(p(acts[0]), p(c.W[1]), p(c.bs[1]), p(plan.edge_index), plan.E, gp_b, ep_b, c.N, Bb, c.D,
-                                         c.D, mxn, mxe, slope, 1, p(acts[1]), emb_b, None, None, None, p(plan.status), stream_b), "hcg_mid_layer_fwd")
+        self._tiles_stack(c, geo_a, gpt, poolbits=c.poolbits)
+        HF.MID.forward(geo_b, 0, c.x, c.W[0], c.bs[0], 1, out=acts[0], stream=stream_b)
+        HF.MID.forward(geo_b, 0, acts[0], c.W[1], c.bs[1], 1, out=acts[1], emb=bufs["emb"], stream=stream_b)
         join()
-        return gpt
 
     def _head(self, c: _Ctx):
         """The readout head as a launch of its own (one-launch kernel for D = 64 / 128, C <= 8; five launches of the
@@ -454,8 +417,8 @@ class FusedTrainStep:
             _lib.check(rc, "hcg_head_fwd_bwd")
             g = (lambda q: self._g(c, q)) if not c.forward_only else (lambda q: None)
             _lib.check(lib.hcg_head_reduce_job(p(bufs["ws_head"]), bufs["ws_head_bytes"], B, D, C, g(l0.weight), g(l0.bias),
-                                               g(l1.weight), g(l1.bias), self._job_slot(c)), "hcg_head_reduce_job")
-            c.njobs += 1
+                                               g(l1.weight), g(l1.bias), c.jobs.slot()), "hcg_head_reduce_job")
+            c.jobs.n += 1
             return
         # any-shape head (widths other than 64 / 128, more than 8 classes): Linear + LeakyReLU, Linear, loss with its
         # (scaled) gradient, two Linear backwards that write straight into the flat gradient buffer
@@ -477,93 +440,62 @@ class FusedTrainStep:
         """Conv stack backward, last layer first.  A fused-tile layer can hand its dx down already multiplied by the
         activation derivative of the layer below (it holds those rows anyway, for dW); that layer then never reads its own
         output: one tensor less per step."""
-        lib, plan, bufs = _lib.load(), c.plan, c.bufs
-        p, stream, slope = _lib.ptr, _lib.stream_ptr(), HF.LEAKY_SLOPE
-        acts, emb, gpts, n_conv, N, B, D = bufs["acts"], bufs["emb"], c.gpts, c.n_conv, c.N, c.B, c.D
-        mxn, mxe = plan.max_nodes, plan.max_edges
+        bufs, geo, jobs = c.bufs, c.geo, c.jobs
+        acts, emb, demb, n_conv, D = bufs["acts"], bufs["emb"], bufs["demb"], c.n_conv, c.D
         g = lambda q: self._g(c, q)
         dh, premasked = None, False
         for l in reversed(range(n_conv)):
+            fam, gpt = c.routes[l]
             inp = c.x if l == 0 else acts[l - 1]
             Fl = inp.shape[1]
             dx = bufs["dacts"][l - 1] if l > 0 else None
-            small = gpts[l] > 0
-            wsb = (lib.hcg_fused_workspace_bytes(B, Fl, D, gpts[l]) if small else
-                   (0 if c.tall[l] else lib.hcg_mid_workspace_bytes(B, Fl, D, mxn, mxe)))
-            ws = self._ws(bufs, l, wsb, c.dev)
             last = l == n_conv - 1
-            cv = c.convs[l]
-            geo = (p(plan.edge_index), plan.E, p(plan.graph_ptr), p(plan.edge_ptr), N, B, Fl, D)
-            if small:
+            W, dW, db = c.W[l], g(c.W[l]), g(c.bs[l])         # (c.W / c.bs: the parameters themselves)
+            act = 1 if (last or not premasked) else 0
+            if fam is HF.TILES:
                 bits = c.poolbits if last else None
-                act = 1 if (last or not premasked) else 0
                 premasked = self.PREMASK and l > 0
-                a_out = p(acts[l]) if (bits is None and (act or last)) else None
-                rc = lib.hcg_fused_layer_bwd(None if last else p(dh), p(bufs["demb"]) if last else None,
-                                             p(emb) if (last and bits is None) else None, a_out, p(bits), p(inp), p(c.W[l]), *geo,
-                                             gpts[l], slope, act | (2 if premasked else 0), p(dx), p(plan.status), p(ws), wsb, stream)
-                _lib.check(rc, "hcg_fused_layer_bwd")
-                _lib.check(lib.hcg_fused_reduce_job(p(ws), wsb, N, B, Fl, D, gpts[l], g(cv.lin.weight), g(cv.bias),
-                                                    self._job_slot(c)), "hcg_fused_reduce_job")
+                wsb = fam.workspace_bytes(geo, gpt, Fl, D)
+                ws = self._ws(bufs, l, wsb, c.dev)
+                fam.backward(geo, gpt, inp, W, act | (2 if premasked else 0), dout=None if last else dh,
+                             demb=demb if last else None, emb=emb if (last and bits is None) else None,
+                             out=acts[l] if (bits is None and (act or last)) else None, poolbits=bits, dx=dx, ws=ws, wsb=wsb)
+                jobs.n += fam.reduce_jobs(geo, gpt, Fl, D, ws, wsb, dW, db, jobs.slot())
+            elif fam is HF.TALL:
+                premasked = False
+                ws, wsb = self._tall_ws(c, l, Fl)
+                bits = c.poolbits if last else None          # (the forward's bit form stands in for the layer's output and emb)
+                first = c.xagg if (l == 0 and not last and dx is None) else None     # (Ahat x, sign pieces) of the forward
+                fam.backward(geo, 0, inp, W, act, dout=None if last else dh, demb=demb if last else None,
+                             emb=emb if (last and bits is None) else None,
+                             out=acts[l] if ((act or last) and bits is None and first is None) else None, poolbits=bits,
+                             xagg=first[0] if first else None, signs=first[1] if first else None, dx=dx, ws=ws, wsb=wsb)
+                jobs.n += fam.reduce_jobs(geo, 0, Fl, D, ws, wsb, dW, db, jobs.slot(), first=first is not None)
+            elif l == 0 and not last and c.xagg is not None:
+                # the first layer's backward as ONE dense launch over the forward's Ahat x (csrc/tall.hip: k_tall_dw<FIRST>) also
+                # behind the one-graph-per-workgroup kernels; the batch's node count is read on the device (graph_ptr[B]): a
+                # captured epoch's slot has a CAPACITY of rows
+                premasked = False
+                ws, wsb = self._tall_ws(c, l, Fl)
+                HF.TALL.backward(geo, 0, inp, W, act, dout=dh, xagg=c.xagg[0], signs=c.xagg[1],
+                                 nodes_dev=geo.graph_ptr + 4 * geo.B, ws=ws, wsb=wsb)
+                jobs.n += HF.TALL.reduce_jobs(geo, 0, Fl, D, ws, wsb, dW, db, jobs.slot(), first=True)
             else:
-                up = (None if last else p(dh), p(bufs["demb"]) if last else None, p(emb) if last else None)
-                act = 0 if premasked else 1
-                if c.tall[l]:
-                    # (TALL_PREMASK: the dense dx kernel multiplies by leaky'(x) in its epilogue -- 4-byte strided loads of the
-                    #  rows it holds -- and the layer below reads ONE tensor instead of two)
-                    premasked = self.TALL_PREMASK and self.PREMASK and l > 0
-                    tws, twsb = self._tall_ws(bufs, l, N, B, Fl, D, c.dev)
-                    bits = c.poolbits if last else None          # (the forward's bit form stands in for the layer's output and emb)
-                    if bits is not None:
-                        up = (None, p(bufs["demb"]), None)
-                    first = c.xagg if (l == 0 and not last and dx is None) else None     # (Ahat x, sign pieces) of the forward
-                    a_out = p(acts[l]) if ((act or last) and bits is None and first is None) else None
-                    rc = lib.hcg_tall_layer_bwd(*up, a_out, p(bits), p(first[0]) if first else None, p(first[1]) if first else None,
-                                                None, p(inp), p(c.W[l]), *geo, mxn, mxe, slope, act | (2 if premasked else 0), p(dx),
-                                                p(plan.status), p(tws), twsb, stream)
-                    _lib.check(rc, "hcg_tall_layer_bwd")
-                    _lib.check(lib.hcg_tall_reduce_jobs(p(tws), twsb, N, B, Fl, D, 1 if first else 0, g(cv.lin.weight), g(cv.bias),
-                                                        self._job_slot(c)), "hcg_tall_reduce_jobs")
-                    c.njobs += 1                          # (two jobs: dW, db)
-                elif l == 0 and not last and c.xagg is not None:
-                    # the first layer's backward as ONE dense launch over the forward's Ahat x (csrc/tall.hip: k_tall_dw<FIRST>) also
-                    # behind the one-graph-per-workgroup kernels; the batch's node count is read on the device (graph_ptr[B]): a
-                    # captured epoch's slot has a CAPACITY of rows
-                    premasked = False
-                    tws, twsb = self._tall_ws(bufs, l, N, B, Fl, D, c.dev)
-                    rc = lib.hcg_tall_layer_bwd(p(dh), None, None, None, None, p(c.xagg[0]), p(c.xagg[1]),
-                                                plan.graph_ptr.data_ptr() + 4 * B, p(inp), p(c.W[l]), *geo, mxn, mxe, slope, act, None,
-                                                p(plan.status), p(tws), twsb, stream)
-                    _lib.check(rc, "hcg_tall_layer_bwd")
-                    _lib.check(lib.hcg_tall_reduce_jobs(p(tws), twsb, N, B, Fl, D, 1, g(cv.lin.weight), g(cv.bias),
-                                                        self._job_slot(c)), "hcg_tall_reduce_jobs")
-                    c.njobs += 1                          # (two jobs: dW, db)
-                else:
-                    premasked = self.PREMASK and l > 0
-                    rc = lib.hcg_mid_layer_bwd(*up, p(acts[l]) if (act or last) else None, p(inp), p(c.W[l]), *geo, mxn, mxe,
-                                               slope, act | (2 if premasked else 0), p(dx), p(plan.status), p(ws), wsb, stream)
-                    _lib.check(rc, "hcg_mid_layer_bwd")
-                    for half in range(D // 64):      # one slab set (= one job) per 64-column half
-                        if half > 0:
-                            c.njobs += 1
-                        _lib.check(lib.hcg_mid_reduce_job(p(ws), wsb, B, Fl, D, mxn, mxe, half, g(cv.lin.weight), g(cv.bias),
-                                                          self._job_slot(c)), "hcg_mid_reduce_job")
-            c.njobs += 1
+                premasked = self.PREMASK and l > 0
+                wsb = fam.workspace_bytes(geo, 0, Fl, D)
+                ws = self._ws(bufs, l, wsb, c.dev)
+                fam.backward(geo, 0, inp, W, act | (2 if premasked else 0), dout=None if last else dh,
+                             demb=demb if last else None, emb=emb if last else None, out=acts[l] if (act or last) else None,
+                             dx=dx, ws=ws, wsb=wsb)
+                jobs.n += fam.reduce_jobs(geo, 0, Fl, D, ws, wsb, dW, db, jobs.slot())
             dh = dx
 
-    def _backward_routed(self, c: _Ctx, gpt, fork, join, stream_b):
+    def _backward_routed(self, c: _Ctx, geo_a, geo_b, gpt, fork, join, stream_b):
         """Size-grouped batch: each layer's backward = tiles on the small graphs + waves on the others; both groups' slabs of
         a layer sit back to back and are ONE reduction job."""
-        lib, plan, bufs = _lib.load(), c.plan, c.bufs
-        p, stream, slope = _lib.ptr, _lib.stream_ptr(), HF.LEAKY_SLOPE
-        Bs, Bb, N, D = c.n_small, c.B - c.n_small, c.N, c.D
-        gp, ep = plan.graph_ptr, plan.edge_ptr
-        gp_b, ep_b = gp.data_ptr() + 4 * Bs, ep.data_ptr() + 4 * Bs
-        acts, emb, demb = bufs["acts"], bufs["emb"], bufs["demb"]
-        emb_b, demb_b = emb.data_ptr() + 4 * 2 * D * Bs, demb.data_ptr() + 4 * 2 * D * Bs
-        mxn, mxe = plan.max_nodes, plan.max_edges
-        g = lambda q: self._g(c, q)
-        tmp = ctypes.create_string_buffer(c.jb)
+        lib, bufs, jobs, D = _lib.load(), c.bufs, c.jobs, c.D
+        acts, demb = bufs["acts"], bufs["demb"]
+        tmp = ctypes.create_string_buffer(_lib.job_bytes())
         taddr = ctypes.addressof(tmp)
         premask = bool(self.PREMASK)
         dx = bufs["dacts"][0]
@@ -571,33 +503,25 @@ class FusedTrainStep:
         for l in (1, 0):
             inp = c.x if l == 0 else acts[0]
             Fl = inp.shape[1]
-            ws_a = lib.hcg_fused_workspace_bytes(Bs, Fl, D, gpt)
-            ws_b = lib.hcg_mid_workspace_bytes(Bb, Fl, D, mxn, mxe)
-            off_b = ws_a - 256                                  # = the tile launch's slabs, exactly (the query pads by 256)
+            off_b = HF.TILES.workspace_bytes(geo_a, gpt, Fl, D) - 256     # = the tile launch's slabs, exactly (the query pads by 256)
+            ws_b = HF.MID.workspace_bytes(geo_b, 0, Fl, D)
             ws = self._ws(bufs, ("r", l), off_b + ws_b, c.dev)
             wsb_ptr = ws.data_ptr() + off_b
-            geo_a = (p(plan.edge_index), plan.E, p(gp), p(ep), N, Bs, Fl, D)
-            geo_b = (p(plan.edge_index), plan.E, gp_b, ep_b, N, Bb, Fl, D)
-            cv = c.convs[l]
+            W, dW, db = c.W[l], self._g(c, c.W[l]), self._g(c, c.bs[l])
             if l == 1:
                 flags = 1 | (2 if premask else 0)
-                _lib.check(lib.hcg_fused_layer_bwd(None, p(demb), None, None, p(c.poolbits), p(inp), p(c.W[l]), *geo_a, gpt, slope,
-                                                   flags, p(dx), p(plan.status), p(ws), off_b, stream), "hcg_fused_layer_bwd")
-                _lib.check(lib.hcg_mid_layer_bwd(None, demb_b, emb_b, p(acts[1]), p(inp), p(c.W[l]), *geo_b, mxn, mxe, slope, flags,
-                                                 p(dx), p(plan.status), wsb_ptr, ws_b, stream_b), "hcg_mid_layer_bwd")
+                HF.TILES.backward(geo_a, gpt, inp, W, flags, demb=demb, poolbits=c.poolbits, dx=dx, ws=ws, wsb=off_b)
+                HF.MID.backward(geo_b, 0, inp, W, flags, demb=demb, emb=bufs["emb"], out=acts[1], dx=dx, ws=wsb_ptr, wsb=ws_b,
+                                stream=stream_b)
             else:
                 act = 0 if premask else 1
-                a_out = p(acts[0]) if act else None
-                _lib.check(lib.hcg_fused_layer_bwd(p(dx), None, None, a_out, None, p(inp), p(c.W[l]), *geo_a, gpt, slope, act, None,
-                                                   p(plan.status), p(ws), off_b, stream), "hcg_fused_layer_bwd")
-                _lib.check(lib.hcg_mid_layer_bwd(p(dx), None, None, a_out, p(inp), p(c.W[l]), *geo_b, mxn, mxe, slope, act, None,
-                                                 p(plan.status), wsb_ptr, ws_b, stream_b), "hcg_mid_layer_bwd")
-            _lib.check(lib.hcg_fused_reduce_job(p(ws), off_b, N, Bs, Fl, D, gpt, g(cv.lin.weight), g(cv.bias), self._job_slot(c)),
-                       "hcg_fused_reduce_job")
-            _lib.check(lib.hcg_mid_reduce_job(wsb_ptr, ws_b, Bb, Fl, D, mxn, mxe, 0, g(cv.lin.weight), g(cv.bias), taddr),
-                       "hcg_mid_reduce_job")
-            _lib.check(lib.hcg_reduce_job_append(self._job_slot(c), taddr), "hcg_reduce_job_append")
-            c.njobs += 1
+                a_out = acts[0] if act else None
+                HF.TILES.backward(geo_a, gpt, inp, W, act, dout=dx, out=a_out, ws=ws, wsb=off_b)
+                HF.MID.backward(geo_b, 0, inp, W, act, dout=dx, out=a_out, ws=wsb_ptr, wsb=ws_b, stream=stream_b)
+            HF.TILES.reduce_jobs(geo_a, gpt, Fl, D, ws, off_b, dW, db, jobs.slot())
+            HF.MID.reduce_jobs(geo_b, 0, Fl, D, wsb_ptr, ws_b, dW, db, taddr)
+            _lib.check(lib.hcg_reduce_job_append(jobs.slot(), taddr), "hcg_reduce_job_append")
+            jobs.n += 1
         join()
 
     def _tail(self, c: _Ctx):
@@ -609,13 +533,13 @@ class FusedTrainStep:
         if c.step_word is not None:
             if self.exchange is not None and self.pre_exchange_hook is not None:
                 self.pre_exchange_hook()
-            if not opt.step_with_reduction(c.jaddr, c.njobs, c.flat, next_plan=self.next_plan, exchange=self.exchange,
+            if not opt.step_with_reduction(c.jobs.addr, c.jobs.n, c.flat, next_plan=self.next_plan, exchange=self.exchange,
                                            flat_ext=self._flat_ext, mode=self.combine, loss_buf=bufs["loss"],
                                            loss_mode=c.loss_mode, loss_count=count):
                 raise _lib.HcgError("optimizer state changed between head launch and update")
             return
         sse_tail = self._flat_ext[c.flat.numel():] if (c.sse_split and c.head_fused) else None
-        _lib.step_tail(c.jaddr, c.njobs, loss=bufs["loss"], loss_mode=c.loss_mode, loss_count=count, sse_tail=sse_tail)
+        _lib.step_tail(c.jobs.addr, c.jobs.n, loss=bufs["loss"], loss_mode=c.loss_mode, loss_count=count, sse_tail=sse_tail)
         if self.next_plan is not None:
             self.next_plan.rebuild()                   # (no fused update to ride in: its own launch)
         if not self._capturing_split:
@@ -625,7 +549,7 @@ class FusedTrainStep:
         """Forward-only steps (the reference's eval_network body, utils/utils_model.py:75-78): the loss from the head's SSE
         partials, one tiny launch."""
         if c.head_fused:
-            _lib.check(_lib.load().hcg_loss_finalize(c.jaddr, float(c.B * c.C), c.loss_mode, _lib.ptr(c.bufs["loss"]), None,
+            _lib.check(_lib.load().hcg_loss_finalize(c.jobs.addr, float(c.B * c.C), c.loss_mode, _lib.ptr(c.bufs["loss"]), None,
                                                      _lib.stream_ptr()), "hcg_loss_finalize")
         self.last_out = c.bufs["out"]
         return c.bufs["loss"][0]
@@ -674,11 +598,14 @@ class FusedTrainStep:
         def join():
             if side_s is not None:
                 main_s.wait_stream(side_s)
-        gpt = self._forward_routed(c, fork, join, stream_b)
+        # graphs [0, n_small) on the tiles (all of <= 32 nodes), the others one graph per wave; node rows stay absolute
+        groups = (HF.geometry(c.plan, 0, c.n_small), HF.geometry(c.plan, c.n_small),
+                  HF.conv_route(c.plan, c.F, c.D, max_nodes=32)[1], fork, join, stream_b)
+        self._forward_routed(c, *groups)
         self._head(c)                                   # over all graphs
         if c.forward_only:
             return self._finish_forward_only(c)
-        self._backward_routed(c, gpt, fork, join, stream_b)
+        self._backward_routed(c, *groups)
         self._tail(c)
         self.last_out = c.bufs["out"]
         return c.bufs["loss"][0]
@@ -960,8 +887,8 @@ class EpochWindow:
             plan.rowptr = plan.col = plan.eid = plan.rowptr_t = plan.col_t = plan.eid_t = None
             plan.dinv = plan.ew_csr = plan.ew_csc = plan.dinv_unw = None
             batch._hcg_plan = plan
-            for c in [model.conv1] + list(model.conv_layers):
-                if HF.fused_graphs_per_tile(plan, c.in_channels, c.out_channels) <= 0 and HF.tall_supported(plan, c.in_channels, c.out_channels):
+            for c in [model.conv1] + list(model.conv_layers):      # (whatever the conv's family preference)
+                if HF.conv_route(plan, c.in_channels, c.out_channels)[0] is HF.TALL:
                     raise _lib.HcgError("EpochWindow: a layer would run on the dense row-streaming kernels (capacity-padded rows)")
             self.batches.append(batch)
             self.spans.append((i, B, off))

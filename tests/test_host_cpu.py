@@ -160,11 +160,12 @@ def test_fused_train_step_support_check_is_host_only():
     assert "readout" in FusedTrainStep.unsupported_reason(deep)
 
 
-def test_kernel_family_selection_is_host_only():
+def test_kernel_family_selection_is_host_only(monkeypatch):
     """Which kernel family takes a layer is decided on the host from (F, D, largest graph): 128-wide layers over graphs up
     to 224 nodes -> csrc/tall.hip when F is a multiple of 4; 64-wide layers over graphs of 65 .. 224 nodes -> its backward,
     but only for batches that fill the chip (`functional.TALL_MIN_NODES_D64`); everything up to 64 nodes stays with the
-    one-graph-per-wave kernels."""
+    one-graph-per-wave kernels.  The decision table below asks every caller of `functional.conv_route` its own question
+    (the answers were taken from the code before the routing rule had one home)."""
     from types import SimpleNamespace
     from hcatgnet_amd import _lib, functional as HF
     lib = _lib.load()
@@ -180,6 +181,83 @@ def test_kernel_family_selection_is_host_only():
     assert HF.tall_supported(plan(356553), 25, 64)
     assert HF.tall_supported(SimpleNamespace(mode="blocked", ew_csr=None, max_nodes=200, max_edges=424, B=24, N=4800), 128, 128)
     assert lib.hcg_head_supported(64, 1) == 1 and lib.hcg_head_supported(128, 8) == 1 and lib.hcg_head_supported(96, 1) == 0
+
+    # Per shape (F in, D wide, largest graph nodes / edges, N rows, B graphs, the convs' `family`, plan mode, edge weights), what
+    #   conv    GCNConv.forward (fused, unweighted) launches for conv1 / conv2 ("general": the any-shape kernels)
+    #   step    FusedTrainStep._prepare picks ("error": it raises)
+    #   support FusedTrainStep.unsupported_reason says -- from the batch's collate metadata alone: it does not see the plan's
+    #           mode or edge weights ("general", "weighted" rows) and never asks about the wide-layer route
+    #   groups  FusedTrainStep._size_groups returns with n_small = B // 2: tiles for the small group, one graph per wave for the
+    #           rest whatever the route of the whole batch or `family` ("REAL", "mid-REAL" rows)
+    #   epoch   EpochWindow decides (refuses the wide-layer route; it does not consult `family`: "mid-C5", "mid-REAL" rows)
+    from hcatgnet_amd.train import FusedTrainStep
+    T = HF.TALL_MIN_NODES_D64
+    table = [
+        (('C1', 64, 64, 30, 64, 30, 1, 'auto', 'blocked', False), ('tiles/tiles', 'tiles/tiles', 'ok', None, 'ok')),
+        (('C3', 64, 64, 30, 64, 122880, 4096, 'auto', 'blocked', False), ('tiles/tiles', 'tiles/tiles', 'ok', None, 'ok')),
+        (('W50', 64, 64, 63, 130, 204889, 4096, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 2048, 'ok')),
+        (('REAL', 25, 64, 117, 240, 356553, 4096, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', 2048, 'refuse')),
+        (('REAL40', 25, 64, 115, 236, 3473, 40, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 20, 'ok')),
+        (('C5', 128, 128, 200, 424, 204800, 1024, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('RAGGED', 64, 64, 36, 76, 122903, 4096, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 2048, 'ok')),
+        (('n32', 25, 64, 32, 74, 12800, 400, 'auto', 'blocked', False), ('tiles/tiles', 'tiles/tiles', 'ok', None, 'ok')),
+        (('n32-big', 64, 64, 32, 74, T + 5, 4000, 'auto', 'blocked', False), ('tiles/tiles', 'tiles/tiles', 'ok', None, 'ok')),
+        (('n32-d128', 128, 128, 32, 74, 12800, 400, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('n33', 25, 64, 33, 76, 13200, 400, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 200, 'ok')),
+        (('n33-big', 64, 64, 33, 76, T + 5, 4000, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 2000, 'ok')),
+        (('n33-d128', 128, 128, 33, 76, 13200, 400, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('n64', 25, 64, 64, 138, 25600, 400, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 200, 'ok')),
+        (('n64-big', 64, 64, 64, 138, T + 5, 4000, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 2000, 'ok')),
+        (('n64-d128', 128, 128, 64, 138, 25600, 400, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('n65', 25, 64, 65, 140, 26000, 400, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 200, 'ok')),
+        (('n65-big', 64, 64, 65, 140, T + 5, 4000, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', 2000, 'refuse')),
+        (('n65-d128', 128, 128, 65, 140, 26000, 400, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('n192', 25, 64, 192, 394, 76800, 400, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 200, 'ok')),
+        (('n192-big', 64, 64, 192, 394, T + 5, 4000, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', 2000, 'refuse')),
+        (('n192-d128', 128, 128, 192, 394, 76800, 400, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('n224', 25, 64, 224, 458, 89600, 400, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 200, 'ok')),
+        (('n224-big', 64, 64, 224, 458, T + 5, 4000, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', 2000, 'refuse')),
+        (('n224-d128', 128, 128, 224, 458, 89600, 400, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', None, 'refuse')),
+        (('n225', 25, 64, 225, 460, 90000, 400, 'auto', 'blocked', False), ('general/general', 'error', 'shape', None, 'ok')),
+        (('n225-big', 64, 64, 225, 460, T + 5, 4000, 'auto', 'blocked', False), ('general/general', 'error', 'shape', None, 'ok')),
+        (('n225-d128', 128, 128, 225, 460, 90000, 400, 'auto', 'blocked', False), ('general/general', 'error', 'shape', None, 'ok')),
+        (('e1024', 25, 64, 117, 1024, T, 2000, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', 1000, 'refuse')),
+        (('e1025', 25, 64, 117, 1025, T, 2000, 'auto', 'blocked', False), ('general/general', 'error', 'shape', None, 'ok')),
+        (('N=TM-1', 25, 64, 117, 240, T - 1, 2000, 'auto', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 1000, 'ok')),
+        (('N=TM', 25, 64, 117, 240, T, 2000, 'auto', 'blocked', False), ('tall/tall', 'tall/tall', 'ok', 1000, 'refuse')),
+        (('D96-small', 25, 96, 30, 64, 3000, 100, 'auto', 'blocked', False), ('general/general', 'error', 'shape', None, 'ok')),
+        (('D96-mid', 25, 96, 117, 240, 3473, 40, 'auto', 'blocked', False), ('general/general', 'error', 'shape', None, 'ok')),
+        (('D128-F126', 126, 128, 200, 424, 204800, 1024, 'auto', 'blocked', False), ('mid/tall', 'mid/tall', 'ok', None, 'refuse')),
+        (('D128-F25', 25, 128, 200, 424, 204800, 1024, 'auto', 'blocked', False), ('mid/tall', 'mid/tall', 'ok', None, 'refuse')),
+        (('mid-C5', 128, 128, 200, 424, 204800, 1024, 'mid', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', None, 'refuse')),
+        (('mid-REAL', 25, 64, 117, 240, 356553, 4096, 'mid', 'blocked', False), ('mid/mid', 'mid/mid', 'ok', 2048, 'refuse')),
+        (('general', 64, 64, 30, 64, 122880, 4096, 'auto', 'general', False), ('general/general', 'error', 'ok', None, 'ok')),
+        (('weighted', 64, 64, 30, 64, 122880, 4096, 'auto', 'blocked', True), ('general/general', 'error', 'ok', None, 'ok')),
+        (('weighted-mid', 25, 64, 117, 240, 3473, 40, 'auto', 'blocked', True), ('general/general', 'error', 'ok', None, 'ok')),
+    ]
+    picked = []
+    monkeypatch.setattr(HF, "conv_layer", lambda x, W, b, plan, fam, gpt, *a, **k: picked.append(fam.name) or x)
+    monkeypatch.setattr(HF, "gcn_layer", lambda x, *a, **k: picked.append("general") or x)
+    monkeypatch.setattr(HF, "graph_pool", lambda h, plan: h)
+    for (label, F, D, mxn, mxe, N, B, family, mode, ew), (conv, step, support, groups, epoch) in table:
+        plan = SimpleNamespace(mode=mode, ew_csr=object() if ew else None, max_nodes=mxn, max_edges=mxe, B=B, N=N)
+        m = H.make_network("GCN", H.default_options(embedding_dim=D), F)
+        convs = [m.conv1] + list(m.conv_layers)
+        for cv in convs:
+            cv.family = family
+        picked.clear()
+        for cv in convs:
+            cv(torch.zeros(1), plan, apply_act=True)
+        assert "/".join(picked) == conv, label
+        routes = [HF.conv_route(plan, cv.in_channels, cv.out_channels, cv.family) for cv in convs]       # as _prepare
+        assert ("error" if any(r[0] is None for r in routes) else "/".join(r[0].name for r in routes)) == step, label
+        batch = H.Batch(torch.zeros(4, F), torch.zeros(2, 0, dtype=torch.int64), torch.zeros(4, dtype=torch.int64), B,
+                        y=torch.zeros(B), max_nodes=mxn, max_edges=mxe, edges_grouped=True, n_small=B // 2 if B > 1 else None)
+        why = FusedTrainStep.unsupported_reason(m, batch)
+        assert (why is None and support == "ok") or (why is not None and support in why), label
+        assert FusedTrainStep(m, optimizer_step=False)._size_groups(batch, plan, convs, D, 1, len(convs)) == groups, label
+        refuse = any(HF.conv_route(plan, cv.in_channels, cv.out_channels)[0] is HF.TALL for cv in convs)       # as EpochWindow
+        assert ("refuse" if refuse else "ok") == epoch, label
 
 
 def test_base_network_dispatch_mirrors_the_reference():
