@@ -50,7 +50,8 @@ extern "C" int hcg_adam_step(float* param, const float* grad, float* exp_avg, fl
 namespace {
 
 // step count and learning rate read from device memory (hipGraph-capturable).  Bias corrections in double
-// like torch's host computation.  The last workgroup to take a ticket publishes step + 1.
+// like torch's host computation.  The last workgroup to take a ticket (step_dev[2], zero between launches) publishes
+// step + 1 and re-zeroes the ticket; step_dev[1], the exchange stamp, is not touched (a plain update exchanges nothing).
 // SSE: `g` = [n summed SSE/2-gradients | SSE | count] (data-parallel form HCG_LOSS_SSE): the
 // gradient of sqrt(MSE) over all ranks' graphs is g * 1 / (count * sqrt(SSE / count)); written back in place.
 template <bool SSE>
@@ -78,9 +79,9 @@ __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, float* 
   }
   __syncthreads();                                     // every thread of this block has read the step word
   if (threadIdx.x == 0) {
-    const int ticket = __hip_atomic_fetch_add(&step_dev[1], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    const int ticket = __hip_atomic_fetch_add(&step_dev[2], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (ticket == (int)gridDim.x - 1) {
-      __hip_atomic_store(&step_dev[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&step_dev[2], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&step_dev[0], t, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
   }

@@ -35,13 +35,14 @@ class FusedAdam(torch.optim.Optimizer):
                 self._make_dev_state(fl, group)
 
     def _make_dev_state(self, fl, group):
-        """step_dev = [Adam step count, exchange stamp].  Word 1 counts the steps this optimiser OBJECT has started and is
-        carried over every re-base / `load_state_dict` (`_keep_stamp`): the one-shot exchange (xgmi.py) stamps its granules
-        with it, and a stamp must never repeat although the Adam step count may go back to a checkpoint's."""
+        """step_dev = [Adam step count, exchange stamp, ticket, pad].  Word 1 counts the carried steps (hcg_step_tail) this
+        optimiser OBJECT has started and is carried over every re-base / `load_state_dict` (`_keep_stamp`): the one-shot
+        exchange (xgmi.py) stamps its granules with it, and a stamp must never repeat although the Adam step count may go
+        back to a checkpoint's.  Word 2 is the plain update's ticket (hcg_adam_step_dev[_sse]), zero between launches."""
         if "step_dev" not in fl:
             dev = fl["p"].device
             stamps = getattr(self, "_stamps", {})
-            fl["step_dev"] = torch.tensor([fl["step"], stamps.get(fl.get("gi", 0), 0)], dtype=torch.int32, device=dev)
+            fl["step_dev"] = torch.tensor([fl["step"], stamps.get(fl.get("gi", 0), 0), 0, 0], dtype=torch.int32, device=dev)
             fl["lr_dev"] = torch.tensor([float(group["lr"])], dtype=torch.float32, device=dev)
             fl["lr_host"] = float(group["lr"])
 

@@ -844,7 +844,7 @@ class EpochWindow:
     def build(model, loader):
         try:
             return EpochWindow(model, loader)
-        except _lib.HcgError:
+        except (_lib.HcgError, RuntimeError):       # refused, or the capture failed (memory, an unsupported launch)
             return None
 
     def __init__(self, model, loader):
@@ -918,7 +918,8 @@ class EpochWindow:
             raise _lib.HcgError(f"EpochWindow: {why}")
         self.counts = torch.tensor([float(B) for B in self.Bs], dtype=torch.float64, device=dev)
         # the capture's warm-up runs every step once: a hidden extra epoch.  It is undone: parameters, moments and the step
-        # count go back to what they were, in place (same storages, so the captured addresses stay valid)
+        # count go back to what they were, in place (same storages, so the captured addresses stay valid) -- also when the
+        # capture fails, since the caller then trains on in its per-batch loop.  The exchange stamp is never taken back
         self._layout(np.arange(G))
         opt = model.optimizer
         opt.enable_capturable()
@@ -931,14 +932,15 @@ class EpochWindow:
             with torch.no_grad():
                 fl = opt._rebase(0, opt.param_groups[0])
         opt._make_dev_state(fl, opt.param_groups[0])
-        saved = [fl["p"].clone(), fl["m"].clone(), fl["v"].clone(), fl["step_dev"].clone()]
-        self.window = StepWindow(self.steps, fns, counts64=self.counts)
-        fl2 = opt._flat.get(0)
-        if fl2 is not fl:
+        saved = [fl["p"].clone(), fl["m"].clone(), fl["v"].clone(), fl["step_dev"][:1].clone()]
+        try:
+            self.window = StepWindow(self.steps, fns, counts64=self.counts)
+        finally:
+            torch.cuda.synchronize()
+            with torch.no_grad():
+                fl["p"].copy_(saved[0]); fl["m"].copy_(saved[1]); fl["v"].copy_(saved[2]); fl["step_dev"][:1].copy_(saved[3])
+        if opt._flat.get(0) is not fl:
             raise _lib.HcgError("EpochWindow: the optimiser re-based its state during the capture")
-        torch.cuda.synchronize()
-        with torch.no_grad():
-            fl["p"].copy_(saved[0]); fl["m"].copy_(saved[1]); fl["v"].copy_(saved[2]); fl["step_dev"][:1].copy_(saved[3][:1])
 
     def _layout(self, order):
         """The epoch's index arrays [ids of every batch | graph_ptr of every batch | edge_ptr of every batch] -> device."""

@@ -157,7 +157,7 @@ class OneShotExchange:
                     slab.copy_(data)
                     flat_ext[n] = float(self.rank + 1) * (r + 1)        # "SSE"
                     flat_ext[n + 1] = 10.0 * (self.rank + 1)            # "count"
-                    fl["step_dev"] += 1                                 # what the head kernel does in a real step (count + stamp)
+                    fl["step_dev"][:2] += 1                             # what the head kernel does in a real step (count + stamp)
                     ref = torch.cat([data, flat_ext[n:].clone()])
                     self.launch(ctypes.addressof(job), 1, flat_ext, fl, 0.9, 0.999, 1e-9, "sse", loss)
                     torch.cuda.synchronize()

@@ -316,8 +316,8 @@ int hcg_readout2_fwd(const float* emb, const float* W0, const float* b0, const f
  *   z [B,D], out [B,C] : forward results
  *   demb [B,2D]        : d (SSE / 2) / d emb  -- unscaled
  *   workspace          : gradient slabs + SSE partials (describe them with hcg_head_reduce_job)
- *   step_counter       : nullable; one int32 device word incremented by 1 per launch -- the number of the training
- *                        step, read later in the same step by hcg_step_tail's update
+ *   step_counter       : nullable; two int32 device words, each incremented by 1 per launch: [0] the number of the
+ *                        training step, read later in the same step by hcg_step_tail's update, [1] the exchange stamp
  *   flags              : HCG_HEAD_FORWARD_ONLY = no backward (demb / gradient slabs untouched; the partials are written)
  * y is [B,C] like out.  D = 64 or 128 (8 waves per workgroup, W0 fragments from L2 instead of LDS), C <= 8
  * (hcg_head_supported). */
@@ -446,9 +446,10 @@ int hcg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   float lr, float beta1, float beta2, float eps, int64_t step, hcg_stream_t stream);
 
 /* Same update with the step count and the learning rate in DEVICE memory, so that the launch can sit inside a
- * captured hipGraph: `step_dev[0]` = number of updates done so far (the kernel uses step_dev[0] + 1 and the last
- * workgroup to finish stores the incremented count; `step_dev[1]` is its ticket word, zero between launches),
- * `lr_dev[0]` = learning rate (the host rewrites it when a scheduler changes it). */
+ * captured hipGraph.  `step_dev` = int32 [count, stamp, ticket, pad]: `step_dev[0]` = number of updates done so far (the
+ * kernel uses step_dev[0] + 1 and the last workgroup to finish stores the incremented count); `step_dev[1]` = the
+ * exchange stamp (hcg_step_tail), which this update neither reads nor writes; `step_dev[2]` is its ticket word, zero
+ * between launches.  `lr_dev[0]` = learning rate (the host rewrites it when a scheduler changes it). */
 int hcg_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                       const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_dev, hcg_stream_t stream);
 
@@ -470,7 +471,7 @@ int hcg_adam_step_dev_sse(float* param, float* flat, float* exp_avg, float* exp_
  * HCG_XCHG_MEAN = mean over the ranks of each rank's own loss gradient; HCG_XCHG_SSE = the gradient of sqrt(MSE) over the
  * concatenated batch (SSE and count travel as elements n, n + 1: from the head's partials, or, without a job that carries
  * them, from grad_flat[n], [n + 1]; loss[0..1] = the global sqrt(MSE), MSE).  Polls are bounded (2 s): HCG_XCHG_ERR_TIMEOUT
- * is ORed into xchg_err[0] and the element becomes NaN.  `step_dev[0]` stamps the granules: it must advance by one per
+ * is ORed into xchg_err[0] and the element becomes NaN.  `step_dev[1]` stamps the granules: it must advance by one per
  * exchange on every rank, and an inbox must be re-zeroed before it serves another optimiser. */
 #define HCG_XCHG_MAX_WORLD 8
 #define HCG_XCHG_HANDLE_BYTES 64
