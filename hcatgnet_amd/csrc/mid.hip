@@ -16,6 +16,7 @@
 // LDS is sized at launch from the batch's largest graph (dynamic shared memory): 2 workgroups per CU up to 96 nodes.
 #include "common.h"
 #include "split_mfma.h"
+#include "graph_csr.h"
 
 namespace {
 
@@ -97,15 +98,10 @@ __device__ __forceinline__ MidLds carve(char* base, int npad, int emax, int wl_r
 
 struct GraphInfo { int nbase, n, ebase, ne, nblk; };
 
-// host metadata that does not fit the kernel's tile: the graph is refused (n = ne = 0) and reported.  The selects stay
-// OUTSIDE the branch of the reporting thread: assigned inside it, n and ne became per-lane registers and every address
-// derived from them a 64-bit vector computation.
+// host metadata that does not fit the kernel's tile: the graph is refused (n = ne = 0) and reported
 __device__ __forceinline__ void graph_validate(GraphInfo& gi, int npad, int emax, int32_t* status) {
-  const bool bad = gi.n < 0 || gi.n > npad || gi.ne < 0 || gi.ne > emax;
-  gi.n = __builtin_amdgcn_readfirstlane(bad ? 0 : gi.n);
-  gi.ne = __builtin_amdgcn_readfirstlane(bad ? 0 : gi.ne);
+  graph_refuse(gi.n, gi.ne, npad, emax, threadIdx.x, status);
   gi.nblk = (gi.n + 31) / 32;
-  if (bad && threadIdx.x == 0) atomicOr(status, HCG_STATUS_SHAPE_LIMIT);
 }
 
 __device__ __forceinline__ GraphInfo graph_info(int g, const int32_t* __restrict__ graph_ptr, const int32_t* __restrict__ edge_ptr,
@@ -138,169 +134,28 @@ __device__ __forceinline__ GraphInfo graph_finish(int raw, int npad, int emax, i
   return gi;
 }
 
-// A graph's raw edges, two per thread, requested one graph AHEAD (loads only: unconditional, clamped index -- E >= 1 and
-// `ei` readable are guaranteed by the host wrappers) and consumed by build_csr of the next iteration.
+// A graph's raw edges, two per thread, requested one graph AHEAD and consumed by the CSR build of the next iteration
 constexpr int EPT = MID_MAX_EDGES / MT;
-struct EdgeRegs {
-  long long s[EPT], d[EPT];
-  // (workgroup-uniform bases + one unsigned 32-bit byte offset per slot = the scalar-base form of global_load; the clamps of
-  //  the graph's edge range are scalar work.  The kernels are bound by VALU issue: per-slot 64-bit index arithmetic counts.)
-  __device__ __forceinline__ void load(const GraphInfo& gi, const int64_t* __restrict__ ei, int64_t E) {
-    long long eb = gi.ebase;
-    eb = eb < 0 ? 0 : (eb > E - 1 ? E - 1 : eb);
-    const long long room = E - eb;
-    const int nec = (long long)gi.ne < room ? gi.ne : (int)room;
-    const int last = nec > 0 ? nec - 1 : 0;
-    const char* sb = reinterpret_cast<const char*>(ei + eb);
-    const char* db = reinterpret_cast<const char*>(ei + E + eb);
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-      const int e = threadIdx.x + j * MT;
-      const unsigned off = 8u * (unsigned)(e < last ? e : last);
-      s[j] = *reinterpret_cast<const long long*>(sb + off);
-      d[j] = *reinterpret_cast<const long long*>(db + off);
-    }
-  }
-};
+using MidEdges = EdgeRegs<EPT, MT>;
+constexpr int RPL = (MID_MAX_NODES + 63) / 64;   // rows per lane of the one-wave row scan
 
-// exclusive scan of the row sizes (cursor) into rowptr by ONE wave (<= 256 rows: 4 per lane); tid = lane of wave 0
-__device__ __forceinline__ void csr_scan_rows(const MidLds& L, int nrows) {
-  const int tid = threadIdx.x;
-  constexpr int RPL = (MID_MAX_NODES + 63) / 64;
-  int v[RPL], tot = 0;
-#pragma unroll
-  for (int j = 0; j < RPL; ++j) {
-    const int i = tid * RPL + j;
-    v[j] = i < nrows ? L.cursor[i] : 0;
-    tot += v[j];
-  }
-  int incl = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (tid >= off) incl += t;
-  }
-  int run = incl - tot;
-#pragma unroll
-  for (int j = 0; j < RPL; ++j) {
-    const int i = tid * RPL + j;
-    if (i < nrows) L.rowptr[i] = run;
-    run += v[j];
-  }
-  if (tid == 63) L.rowptr[nrows] = incl;
-}
-
-// In-degree -> dinv, and a CSR of the graph in LDS.  BY_SRC = false: rows = targets, col = sources (forward
-// aggregation); BY_SRC = true: rows = sources, col = targets (the transpose, for the backward).  dinv is always
-// (1 + in-degree)^-1/2.  Explicit (i, i) edges collapse into the unit self loop (PyG add_remaining_self_loops).
-// Every row ends up sorted by id, whatever order the LDS atomics ran in.  All MT threads; ends with a barrier.
-// PRECONDITION: cursor[0 .. npad) (and degin_scratch) are ZERO -- csr_counters_clear() before the graph loop; the fill
-// pass counts every row's cursor back down to zero, so the invariant holds from graph to graph with no clearing pass.
-// Four barriers: count | scan (wave 0) beside dinv (the other waves) | fill (csr_count_scan_fill) | sort (csr_sort_rows).
+// The per-graph gcn_norm of the forward and backward kernels (rules: graph_csr.h).  One pass over the graph's edges (in
+// registers since the previous graph) counts every row's size into cursor and writes the row's first NSLOT ids into its
+// slots in nbr; forward: rows = targets, slots = sources; backward: rows = sources (the transpose), plus in-degree counters
+// in degin_scratch.  After a barrier one thread per row turns the in-degree into dinv and sorts the row's slots.  A graph
+// with a row longer than NSLOT (flag[0]) also takes the CSR route: wave 0 scans the row sizes into rowptr
+// (csr_scan_rows), the fill pass counts every row's cursor back down to zero while it writes col, csr_sort_rows.
+// PRECONDITION: cursor[0 .. npad) and degin_scratch are ZERO -- csr_counters_clear() before the graph loop.  The
+// invariant holds from graph to graph with no clearing pass: the dinv pass zeroes degin_scratch, and the aggregation
+// (mid_agg_unit) resets its rows' slots and counters.
 __device__ __forceinline__ void csr_counters_clear(const MidLds& L, int npad, int* degin_scratch) {
   for (int i = threadIdx.x; i < npad; i += MT) { L.cursor[i] = 0; if (degin_scratch) degin_scratch[i] = 0; }
 }
 
-template <bool BY_SRC>
-__device__ __forceinline__ void csr_count_scan_fill(const MidLds& L, const GraphInfo& gi, const EdgeRegs& er, int32_t* status,
-                                                    int* degin_scratch, int mstamp_it = 4) {
-  static_assert(MT - 64 >= MID_MAX_NODES, "one dinv row per thread beside the scan wave");
-  const int tid = threadIdx.x;
-  const int nrows = gi.nblk * 32;
-  // this thread's edges (already in registers) -> local ids, kept from the counting pass to the fill pass
-  unsigned short es[EPT], ed[EPT];
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < EPT; ++j) {
-    const int e = tid + j * MT;
-    es[j] = 0xffff;
-    ed[j] = 0xffff;
-    if (e < gi.ne) {
-      const long long s = er.s[j], d = er.d[j];
-      const unsigned sl = (unsigned)((int)s - gi.nbase), dl = (unsigned)((int)d - gi.nbase);
-      const bool ok = sl < (unsigned)gi.n && dl < (unsigned)gi.n && (s >> 31) == 0 && (d >> 31) == 0;
-      bad |= !ok;
-      if (ok && sl != dl) {
-        es[j] = (unsigned short)sl;
-        ed[j] = (unsigned short)dl;
-        atomicAdd(&L.cursor[BY_SRC ? sl : dl], 1);
-        if (BY_SRC) atomicAdd(&degin_scratch[dl], 1);
-      }
-    }
-  }
-  if (__ballot(bad) != 0ull && (tid & 63) == 0) atomicOr(status, HCG_STATUS_EDGE_UNGROUPED);   // edge leaves its graph: ignored
-  __syncthreads();
-  MSTAMP(2);
-  if (tid < 64) {     // exclusive scan of the row sizes by wave 0 ...
-    csr_scan_rows(L, nrows);
-  } else if (tid - 64 < nrows) {     // ... while the other waves turn the in-degrees into dinv (MT - 64 >= MID_MAX_NODES rows)
-    const int i = tid - 64;
-    const int degin = BY_SRC ? degin_scratch[i] : L.cursor[i];
-    L.dinv[i] = i < gi.n ? 1.0f / sqrtf(1.0f + (float)degin) : 0.f;
-    if (BY_SRC) degin_scratch[i] = 0;
-  }
-  __syncthreads();
-  MSTAMP(3);
-#pragma unroll
-  for (int j = 0; j < EPT; ++j) {
-    if (es[j] != 0xffff) {
-      const int rowi = BY_SRC ? es[j] : ed[j];
-      const int left = atomicSub(&L.cursor[rowi], 1);          // counts the row back down to zero
-      L.col[L.rowptr[rowi] + left - 1] = BY_SRC ? ed[j] : es[j];
-    }
-  }
-  __syncthreads();
-  MSTAMP(4);
-}
-
-// second half of the CSR build: every row sorted by id (fixed summation order).  Ends with a barrier.
+// every row of the CSR sorted by id (fixed summation order).  Ends with a barrier.
 __device__ __forceinline__ void csr_sort_rows(const MidLds& L, const GraphInfo& gi) {
-  const int tid = threadIdx.x;
-  for (int i = tid; i < gi.n; i += MT) {
-    const int kb = L.rowptr[i], ke = L.rowptr[i + 1], len = ke - kb;
-    if (len > 1 && len <= 4) {                      // (every row of a molecular graph) a register network: no dependent LDS chain
-      unsigned a0 = L.col[kb], a1 = L.col[kb + 1], a2 = len > 2 ? L.col[kb + 2] : 0xffffu, a3 = len > 3 ? L.col[kb + 3] : 0xffffu;
-      unsigned t;
-      t = min(a0, a1); a1 = max(a0, a1); a0 = t;
-      t = min(a2, a3); a3 = max(a2, a3); a2 = t;
-      t = min(a0, a2); a2 = max(a0, a2); a0 = t;
-      t = min(a1, a3); a3 = max(a1, a3); a1 = t;
-      t = min(a1, a2); a2 = max(a1, a2); a1 = t;
-      L.col[kb] = (unsigned short)a0;
-      L.col[kb + 1] = (unsigned short)a1;
-      if (len > 2) L.col[kb + 2] = (unsigned short)a2;
-      if (len > 3) L.col[kb + 3] = (unsigned short)a3;
-    } else if (len > 4) {
-      for (int a = kb + 1; a < ke; ++a) {
-        const unsigned short key = L.col[a];
-        int b = a - 1;
-        while (b >= kb && L.col[b] > key) { L.col[b + 1] = L.col[b]; --b; }
-        L.col[b + 1] = key;
-      }
-    }
-  }
+  for (int i = threadIdx.x; i < gi.n; i += MT) csr_sort_row(L.col, L.rowptr[i], L.rowptr[i + 1]);
   __syncthreads();
-}
-
-// acc = t[row] + sum_{k in [kb, ke)} t[col[k]] for this lane's (row, 4q..4q+3) slot: the first four neighbours' indices and
-// rows are requested together (independent LDS reads instead of a chain of dependent ones), longer rows loop on
-__device__ __forceinline__ float4 mid_row_sum(const float* t, const unsigned short* col, int row, int kb, int ke, int q) {
-  float4 acc = *reinterpret_cast<const float4*>(t + row * HS + 4 * q);
-  int c[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) c[j] = kb + j < ke ? col[kb + j] : row;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float4 v = *reinterpret_cast<const float4*>(t + c[j] * HS + 4 * q);
-    if (kb + j < ke) { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
-  }
-  for (int k = kb + 4; __any(k < ke); ++k) {
-    if (k < ke) {
-      const float4 v = *reinterpret_cast<const float4*>(t + col[k] * HS + 4 * q);
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-  }
-  return acc;
 }
 
 // Stage columns [c0, c0 + KPAD) of rows [nbase, nbase + n) of a row-major [Nrows, F] matrix into t[row][0..KPAD) (zero
@@ -733,9 +588,9 @@ __global__ __launch_bounds__(MT, MULTIK ? 2 : 4) void k_mid_layer_fwd(const floa
   //  last graph again and drops it -- the prefetches are unconditional)
   const int G = (int)gridDim.x;
   GraphInfo gi = graph_info(blockIdx.x, graph_ptr, edge_ptr, npad, emax, status);
-  EdgeRegs er;
+  MidEdges er;
   XRows<KPAD, VEC, MULTIK ? 32 : NR> xr;
-  er.load(gi, ei, E);
+  er.load(gi, ei, E, tid);
   if constexpr (!MULTIK) xr.load(x, F, gi);
   int raw_next = graph_raw(min((int)blockIdx.x + G, B - 1), graph_ptr, edge_ptr);
 
@@ -807,20 +662,15 @@ __global__ __launch_bounds__(MT, MULTIK ? 2 : 4) void k_mid_layer_fwd(const floa
     const int wblk = (wave + rot) & (MW - 1);
     if (wblk < gcur.nblk && lane < 32) {
       const int i = wblk * 32 + lane;
-      L.dinv[i] = i < gcur.n ? 1.0f / sqrtf(1.0f + (float)L.cursor[i]) : 0.f;
+      L.dinv[i] = i < gcur.n ? gcn_dinv(L.cursor[i]) : 0.f;
       // the row's slots, filled in the order the atomics ran, sorted ONCE here by the row's own lane (in the aggregation the
       // 16 lanes of a row would each repeat the network: 10 VALU per pass): ascending ids, empty (= npad) last
       const uint2 nb = *reinterpret_cast<const uint2*>(L.nbr + i * NSLOT);
-      unsigned a0 = nb.x & 0xffffu, a1 = nb.x >> 16, a2 = nb.y & 0xffffu, a3 = nb.y >> 16, t;
-      t = min(a0, a1); a1 = max(a0, a1); a0 = t;
-      t = min(a2, a3); a3 = max(a2, a3); a2 = t;
-      t = min(a0, a2); a2 = max(a0, a2); a0 = t;
-      t = min(a1, a3); a3 = max(a1, a3); a1 = t;
-      t = min(a1, a2); a2 = max(a1, a2); a1 = t;
-      *reinterpret_cast<uint2*>(L.nbr + i * NSLOT) = make_uint2(a0 | (a1 << 16), a2 | (a3 << 16));
+      const Sorted4 o = sort4(nb.x & 0xffffu, nb.x >> 16, nb.y & 0xffffu, nb.y >> 16);
+      *reinterpret_cast<uint2*>(L.nbr + i * NSLOT) = make_uint2(o.a0 | (o.a1 << 16), o.a2 | (o.a3 << 16));
     }
     if (csr_route) {        // some in-degree > NSLOT: CSR of the graph (the counters hold the row sizes), rows sorted by id
-      if (tid < 64) csr_scan_rows(L, nrows);
+      if (tid < 64) csr_scan_rows<RPL>(L.cursor, L.rowptr, nrows, tid);
       __syncthreads();      // (also: every dinv above has read its counter before the fill pass counts them down)
 #pragma unroll
       for (int j = 0; j < EPT; ++j) {
@@ -905,7 +755,7 @@ __global__ __launch_bounds__(MT, MULTIK ? 2 : 4) void k_mid_layer_fwd(const floa
     // the NEXT graph's edges and x rows are requested here (its scalars were requested a graph ago): they land while this
     // graph is aggregated and stored; the scalars of the graph after next follow
     gi = graph_finish(raw_next, npad, emax, status);
-    er.load(gi, ei, E);
+    er.load(gi, ei, E, tid);
     if constexpr (!MULTIK) xr.load(x, F, gi);
     raw_next = graph_raw(min(g + 2 * G, B - 1), graph_ptr, edge_ptr);
     MSTAMP(8);
@@ -1005,10 +855,10 @@ __global__ __launch_bounds__(MT, 2) void k_mid_layer_bwd(
   // the first graph's scalars and edges are requested before the weight image is staged (one exposed round trip less at the
   // reference's batch size, where a launch is one graph long)
   GraphInfo gnext;
-  EdgeRegs er;
+  MidEdges er;
   if ((int)blockIdx.x < B) {
     gnext = graph_info(blockIdx.x, graph_ptr, edge_ptr, npad, emax, status);
-    er.load(gnext, ei, E);
+    er.load(gnext, ei, E, tid);
   }
   if (NEEDS_DX && NFC == 1) stage_weight_split<true, MT, KPAD, DD>(L.wl, W, DD, F);   // image row f, column d <- W[d][f]
   const bool xvec = F == KPAD && ((uintptr_t)x % 16 == 0);
@@ -1119,19 +969,14 @@ __global__ __launch_bounds__(MT, 2) void k_mid_layer_bwd(
     // one thread per row (waves 1..: wave 0 is the scan wave of the CSR route): dinv, the counter back to zero, slots sorted
     if (tid >= 64 && tid - 64 < rows) {
       const int i = tid - 64;
-      L.dinv[i] = i < gi.n ? 1.0f / sqrtf(1.0f + (float)degin[i]) : 0.f;
+      L.dinv[i] = i < gi.n ? gcn_dinv(degin[i]) : 0.f;
       degin[i] = 0;
       const uint2 nb = *reinterpret_cast<const uint2*>(L.nbr + i * NSLOT);
-      unsigned a0 = nb.x & 0xffffu, a1 = nb.x >> 16, a2 = nb.y & 0xffffu, a3 = nb.y >> 16, t;
-      t = min(a0, a1); a1 = max(a0, a1); a0 = t;
-      t = min(a2, a3); a3 = max(a2, a3); a2 = t;
-      t = min(a0, a2); a2 = max(a0, a2); a0 = t;
-      t = min(a1, a3); a3 = max(a1, a3); a1 = t;
-      t = min(a1, a2); a2 = max(a1, a2); a1 = t;
-      *reinterpret_cast<uint2*>(L.nbr + i * NSLOT) = make_uint2(a0 | (a1 << 16), a2 | (a3 << 16));
+      const Sorted4 o = sort4(nb.x & 0xffffu, nb.x >> 16, nb.y & 0xffffu, nb.y >> 16);
+      *reinterpret_cast<uint2*>(L.nbr + i * NSLOT) = make_uint2(o.a0 | (o.a1 << 16), o.a2 | (o.a3 << 16));
     }
     if (csr_route) {
-      if (tid < 64) csr_scan_rows(L, rows);
+      if (tid < 64) csr_scan_rows<RPL>(L.cursor, L.rowptr, rows, tid);
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < EPT; ++j) {
@@ -1149,7 +994,7 @@ __global__ __launch_bounds__(MT, 2) void k_mid_layer_bwd(
     if (tid == 0) L.flag[0] = 0;                           // (every thread read it before the barrier above)
     if (g + (int)gridDim.x < B) {                          // the NEXT graph's scalars and edges: in flight for the whole graph
       gnext = graph_info(g + gridDim.x, graph_ptr, edge_ptr, npad, emax, status);
-      er.load(gnext, ei, E);
+      er.load(gnext, ei, E, tid);
     }
     if (POOLG) {
       const float cntf = (float)(gi.n > 0 ? gi.n : 1);

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "split_mfma.h"
+#include "graph_csr.h"
 
 namespace {
 
@@ -414,9 +415,6 @@ __device__ __forceinline__ SegGraph seg_graph(int g, const int32_t* __restrict__
   gi.n = graph_ptr[g + 1] - gi.nbase;
   gi.ebase = edge_ptr[g];
   gi.ne = edge_ptr[g + 1] - gi.ebase;
-  // host metadata that does not fit: the graph is refused and reported.  The selects stay OUTSIDE the reporting thread's
-  // branch (assigned inside it, n and ne became per-lane registers and every address derived from them a 64-bit vector
-  // computation -- mid.hip, round 3)
   const bool bad = gi.n < 0 || gi.n > npad || gi.ne < 0 || gi.ne > SEG_MAX_EDGES;
   gi.n = __builtin_amdgcn_readfirstlane(bad ? 0 : gi.n);
   gi.ne = __builtin_amdgcn_readfirstlane(bad ? 0 : gi.ne);
@@ -425,21 +423,7 @@ __device__ __forceinline__ SegGraph seg_graph(int g, const int32_t* __restrict__
   return gi;
 }
 
-struct SegEdge {       // this thread's edge of the graph (loads only: unconditional, clamped)
-  long long s, d;
-  __device__ __forceinline__ void load(const SegGraph& gi, const int64_t* __restrict__ ei, int64_t E) {
-    // (workgroup-uniform bases + one unsigned 32-bit byte offset: the scalar-base form of global_load; clamps are scalar work)
-    long long eb = gi.ebase;
-    eb = eb < 0 ? 0 : (eb > E - 1 ? E - 1 : eb);
-    const long long room = E - eb;
-    const int nec = (long long)gi.ne < room ? gi.ne : (int)room;
-    const int last = nec > 0 ? nec - 1 : 0;
-    const int e = threadIdx.x;
-    const unsigned off = 8u * (unsigned)(e < last ? e : last);
-    s = *reinterpret_cast<const long long*>(reinterpret_cast<const char*>(ei + eb) + off);
-    d = *reinterpret_cast<const long long*>(reinterpret_cast<const char*>(ei + E + eb) + off);
-  }
-};
+using SegEdge = EdgeRegs<1, SN>;   // this thread's edge of the graph
 
 // this thread's share of a graph's rows of a [N, F] tensor, F <= 128 a multiple of 4: rows rg, rg + 32, ... (rg = tid / 32),
 // columns 4 c4 .. 4 c4 + 3 (c4 = tid % 32; columns past F: clamped loads, zeroed by the user)
@@ -459,113 +443,49 @@ struct SegRowsF {
   }
 };
 
-// The algorithm of mid.hip's build_csr for 1024 threads (one edge each): in-degree -> dinv = (1 + deg_in)^-1/2, counting
-// sort into rows (BY_SRC: rows = sources = the transpose), explicit (i, i) edges collapse into the unit self loop, every
-// row sorted by id.  Ends with a barrier.
+// The per-graph CSR build (rules: graph_csr.h) for 1024 threads, one edge each: in-degree -> dinv, counting sort into rows
+// (BY_SRC: rows = sources = the transpose), every row sorted by id.  Ends with a barrier.
 template <bool BY_SRC, class LDS>
 __device__ __forceinline__ void seg_build_csr(LDS& L, const SegGraph& gi, const SegEdge& er, int32_t* status) {
   const int tid = threadIdx.x;
   const int n = gi.n;
   if (tid < n) { L.cursor[tid] = 0; if (BY_SRC) L.degin[tid] = 0; }
   __syncthreads();
-  unsigned short es = 0xffff, ed = 0xffff;
+  unsigned short es[1] = {0xffff}, ed[1] = {0xffff};
   bool bad = false;
   if (tid < gi.ne) {
-    const unsigned sl = (unsigned)((int)er.s - gi.nbase), dl = (unsigned)((int)er.d - gi.nbase);
-    const bool ok = sl < (unsigned)n && dl < (unsigned)n && (er.s >> 31) == 0 && (er.d >> 31) == 0;
+    const unsigned sl = (unsigned)((int)er.s[0] - gi.nbase), dl = (unsigned)((int)er.d[0] - gi.nbase);
+    const bool ok = sl < (unsigned)n && dl < (unsigned)n && (er.s[0] >> 31) == 0 && (er.d[0] >> 31) == 0;
     bad = !ok;
     if (ok && sl != dl) {
-      es = (unsigned short)sl;
-      ed = (unsigned short)dl;
+      es[0] = (unsigned short)sl;
+      ed[0] = (unsigned short)dl;
       atomicAdd(&L.cursor[BY_SRC ? sl : dl], 1);
       if (BY_SRC) atomicAdd(&L.degin[dl], 1);
     }
   }
   if (__ballot(bad) != 0ull && (tid & 63) == 0) atomicOr(status, HCG_STATUS_EDGE_UNGROUPED);
   __syncthreads();
-  if (tid < 64) {     // exclusive scan of the row sizes (<= 224 rows: 4 per lane)
-    constexpr int RPL = (SEG_MAX_NODES + 63) / 64;
-    int v[RPL], tot = 0;
-#pragma unroll
-    for (int j = 0; j < RPL; ++j) {
-      const int i = tid * RPL + j;
-      v[j] = i < n ? L.cursor[i] : 0;
-      tot += v[j];
-    }
-    int incl = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int t = __shfl_up(incl, off, 64);
-      if (tid >= off) incl += t;
-    }
-    int run = incl - tot;
-#pragma unroll
-    for (int j = 0; j < RPL; ++j) {
-      const int i = tid * RPL + j;
-      if (i < n) L.rowptr[i] = run;
-      run += v[j];
-    }
-    if (tid == 63) L.rowptr[n] = incl;
+  if (tid < 64) {     // exclusive scan of the row sizes
+    csr_scan_rows<(SEG_MAX_NODES + 63) / 64>(L.cursor, L.rowptr, n, tid);
   } else if (tid >= SN - SEG_MAX_NODES) {      // (other waves, meanwhile) dinv of every row
     const int i = tid - (SN - SEG_MAX_NODES);
-    if (i < n) L.dinv[i] = 1.0f / sqrtf(1.0f + (float)(BY_SRC ? L.degin[i] : L.cursor[i]));
+    if (i < n) L.dinv[i] = gcn_dinv(BY_SRC ? L.degin[i] : L.cursor[i]);
   }
   __syncthreads();
   if (tid < n) L.cursor[tid] = L.rowptr[tid];
   __syncthreads();
-  if (es != 0xffff) {
-    const int p = atomicAdd(&L.cursor[BY_SRC ? es : ed], 1);
-    L.col[p] = BY_SRC ? ed : es;
+  if (es[0] != 0xffff) {
+    const int p = atomicAdd(&L.cursor[BY_SRC ? es[0] : ed[0]], 1);
+    L.col[p] = BY_SRC ? ed[0] : es[0];
   }
   __syncthreads();
-  if (tid < n) {
-    const int i = tid;
-    const int kb = L.rowptr[i], ke = L.rowptr[i + 1], len = ke - kb;
-    if (len > 1 && len <= 4) {
-      unsigned a0 = L.col[kb], a1 = L.col[kb + 1], a2 = len > 2 ? L.col[kb + 2] : 0xffffu, a3 = len > 3 ? L.col[kb + 3] : 0xffffu;
-      unsigned t;
-      t = min(a0, a1); a1 = max(a0, a1); a0 = t;
-      t = min(a2, a3); a3 = max(a2, a3); a2 = t;
-      t = min(a0, a2); a2 = max(a0, a2); a0 = t;
-      t = min(a1, a3); a3 = max(a1, a3); a1 = t;
-      t = min(a1, a2); a2 = max(a1, a2); a1 = t;
-      L.col[kb] = (unsigned short)a0;
-      L.col[kb + 1] = (unsigned short)a1;
-      if (len > 2) L.col[kb + 2] = (unsigned short)a2;
-      if (len > 3) L.col[kb + 3] = (unsigned short)a3;
-    } else if (len > 4) {
-      for (int a = kb + 1; a < ke; ++a) {
-        const unsigned short key = L.col[a];
-        int b = a - 1;
-        while (b >= kb && L.col[b] > key) { L.col[b + 1] = L.col[b]; --b; }
-        L.col[b + 1] = key;
-      }
-    }
-  }
+  if (tid < n) csr_sort_row(L.col, L.rowptr[tid], L.rowptr[tid + 1]);
   __syncthreads();
 }
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 f4_scale(float s, float4 v) { return make_float4(s * v.x, s * v.y, s * v.z, s * v.w); }
-__device__ __forceinline__ void f4_add(float4& a, const float4 v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-
-// acc = t[row] + sum_{k in [kb, ke)} t[col[k]] for this lane's (row, 4 c4 ..) slot: the first four neighbours' rows are
-// requested together (independent LDS reads instead of a chain of dependent ones), longer rows loop on
-__device__ __forceinline__ float4 seg_row_sum(const float* t, const unsigned short* col, int row, int kb, int ke, int c4) {
-  float4 acc = *reinterpret_cast<const float4*>(t + row * SEG_TS + 4 * c4);
-  int c[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) c[j] = kb + j < ke ? col[kb + j] : row;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float4 v = *reinterpret_cast<const float4*>(t + c[j] * SEG_TS + 4 * c4);
-    if (kb + j < ke) f4_add(acc, v);
-  }
-  for (int k = kb + 4; __any(k < ke); ++k) {
-    if (k < ke) f4_add(acc, *reinterpret_cast<const float4*>(t + col[k] * SEG_TS + 4 * c4));
-  }
-  return acc;
-}
 
 // ---- forward: H' = dinv . H;  out_i = LeakyReLU(dinv_i (H'_i + sum_k H'_k) + b), [max | mean] pooling
 // Pre-split image of a layer's weight in global memory for the fused forward: three bf16 planes of [128][KP] (zero past F),
@@ -642,7 +562,7 @@ __global__ __launch_bounds__(SN, 4) void k_seg_fwd(const float* __restrict__ src
   SegRowsF xrows;
   if ((int)blockIdx.x < B) {
     gnext = seg_graph(blockIdx.x, graph_ptr, edge_ptr, npad, status);
-    er.load(gnext, ei, E);
+    er.load(gnext, ei, E, threadIdx.x);
     xrows.load(src, F, gnext);
   }
   // (Per graph on C5, s_memtime stamps of tools/probe_seg.hip: CSR build 1.3 us, tile write 0.85 us, sums + stores 10 us -- the
@@ -699,7 +619,7 @@ __global__ __launch_bounds__(SN, 4) void k_seg_fwd(const float* __restrict__ src
               const bool valid = row < gi.n;
               const int rr = valid ? row : gi.n - 1;
               const int kb = valid ? L.rowptr[rr] : 0, ke = valid ? L.rowptr[rr + 1] : 0;
-              const float4 zs = seg_row_sum(tile, L.col, rr, kb, ke, c4);
+              const float4 zs = csr_row_sum<SEG_TS>(tile, L.col, rr, kb, ke, c4);
               if (valid) *reinterpret_cast<float4*>(zagg + (size_t)(gi.nbase + row) * zld + 4 * c4) = f4_scale(L.dinv[rr], zs);
             }
           }
@@ -754,19 +674,19 @@ __global__ __launch_bounds__(SN, 4) void k_seg_fwd(const float* __restrict__ src
     SSTAMP(sit, 3);
     if (g + (int)gridDim.x < B) {                     // the NEXT graph's scalars, edge and rows: in flight under this graph's sums
       gnext = seg_graph(g + gridDim.x, graph_ptr, edge_ptr, npad, status);
-      er.load(gnext, ei, E);
+      er.load(gnext, ei, E, threadIdx.x);
       xrows.load(src, F, gnext);                      // (requested before the MFMA loop instead: the same ~5 us of exposed load
     }                                                 //  time per graph moves into that phase -- measured equal, more spills)
     float4 pmax = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY), psum = f4_zero();
     unsigned sgn = 0, mxb = 0;                         // BITS: nibble j = this thread's row rg + 32 j, bit c = column 4 c4 + c
 #pragma unroll
     for (int j = 0; j < SEG_RPT; ++j) {
-      if (j * 32 < gi.n) {                             // (block-uniform: the tail loop of seg_row_sum votes per wave)
+      if (j * 32 < gi.n) {                             // (block-uniform: the tail loop of csr_row_sum votes per wave)
         const int row = rg + 32 * j;
         const bool valid = row < gi.n;
         const int rr = valid ? row : gi.n - 1;
         const int kb = valid ? L.rowptr[rr] : 0, ke = valid ? L.rowptr[rr + 1] : 0;
-        const float4 acc = seg_row_sum(tile, L.col, rr, kb, ke, c4);
+        const float4 acc = csr_row_sum<SEG_TS>(tile, L.col, rr, kb, ke, c4);
         const float di = L.dinv[rr];
         float4 y = make_float4(fmaf(di, acc.x, bq.x), fmaf(di, acc.y, bq.y), fmaf(di, acc.z, bq.z), fmaf(di, acc.w, bq.w));
         if (apply_act) { y.x = fmaxf(y.x, slope * y.x); y.y = fmaxf(y.y, slope * y.y); y.z = fmaxf(y.z, slope * y.z); y.w = fmaxf(y.w, slope * y.w); }
@@ -869,25 +789,7 @@ struct GS {
     unsigned short col[SEG_MAX_EDGES];
     float red[NW * D];
   };
-  struct Edges {       // this thread's edges of the graph (loads only: unconditional, clamped)
-    long long s[EPT], d[EPT];
-    __device__ __forceinline__ void load(const SegGraph& gi, const int64_t* __restrict__ ei, int64_t E) {
-      long long eb = gi.ebase;
-      eb = eb < 0 ? 0 : (eb > E - 1 ? E - 1 : eb);
-      const long long room = E - eb;
-      const int nec = (long long)gi.ne < room ? gi.ne : (int)room;
-      const int last = nec > 0 ? nec - 1 : 0;
-      const char* sb = reinterpret_cast<const char*>(ei + eb);
-      const char* db = reinterpret_cast<const char*>(ei + E + eb);
-#pragma unroll
-      for (int j = 0; j < EPT; ++j) {
-        const int e = threadIdx.x + j * NT;
-        const unsigned off = 8u * (unsigned)(e < last ? e : last);
-        s[j] = *reinterpret_cast<const long long*>(sb + off);
-        d[j] = *reinterpret_cast<const long long*>(db + off);
-      }
-    }
-  };
+  using Edges = EdgeRegs<EPT, NT>;     // this thread's edges of the graph
   // this thread's share of a graph's rows: rows rg, rg + RPP, ... (rg = tid / LPR), columns 4 c4 .. 4 c4 + 3 (c4 = tid % LPR)
   struct Rows {
     float4 v[RPT];
@@ -904,7 +806,7 @@ struct GS {
       }
     }
   };
-  // mid.hip's build_csr (see seg_build_csr above), any thread count
+  // seg_build_csr above, any thread count
   template <bool BY_SRC>
   static __device__ __forceinline__ void build_csr(Lds& L, const SegGraph& gi, const Edges& er, int32_t* status) {
     const int tid = threadIdx.x;
@@ -931,31 +833,10 @@ struct GS {
     }
     if (__ballot(bad) != 0ull && (tid & 63) == 0) atomicOr(status, HCG_STATUS_EDGE_UNGROUPED);
     __syncthreads();
-    if (tid < 64) {     // exclusive scan of the row sizes (<= 256 rows: 4 per lane)
-      constexpr int RPL = (NMAX + 63) / 64;
-      int v[RPL], tot = 0;
-#pragma unroll
-      for (int j = 0; j < RPL; ++j) {
-        const int i = tid * RPL + j;
-        v[j] = i < n ? L.cursor[i] : 0;
-        tot += v[j];
-      }
-      int incl = tot;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (tid >= off) incl += t;
-      }
-      int run = incl - tot;
-#pragma unroll
-      for (int j = 0; j < RPL; ++j) {
-        const int i = tid * RPL + j;
-        if (i < n) L.rowptr[i] = run;
-        run += v[j];
-      }
-      if (tid == 63) L.rowptr[n] = incl;
+    if (tid < 64) {     // exclusive scan of the row sizes
+      csr_scan_rows<(NMAX + 63) / 64>(L.cursor, L.rowptr, n, tid);
     } else {                                     // (the other waves, meanwhile) dinv of every row
-      for (int i = tid - 64; i < n; i += NT - 64) L.dinv[i] = 1.0f / sqrtf(1.0f + (float)(BY_SRC ? L.degin[i] : L.cursor[i]));
+      for (int i = tid - 64; i < n; i += NT - 64) L.dinv[i] = gcn_dinv(BY_SRC ? L.degin[i] : L.cursor[i]);
     }
     __syncthreads();
     for (int i = tid; i < n; i += NT) L.cursor[i] = L.rowptr[i];
@@ -968,45 +849,8 @@ struct GS {
       }
     }
     __syncthreads();
-    for (int i = tid; i < n; i += NT) {
-      const int kb = L.rowptr[i], ke = L.rowptr[i + 1], len = ke - kb;
-      if (len > 1 && len <= 4) {
-        unsigned a0 = L.col[kb], a1 = L.col[kb + 1], a2 = len > 2 ? L.col[kb + 2] : 0xffffu, a3 = len > 3 ? L.col[kb + 3] : 0xffffu;
-        unsigned t;
-        t = min(a0, a1); a1 = max(a0, a1); a0 = t;
-        t = min(a2, a3); a3 = max(a2, a3); a2 = t;
-        t = min(a0, a2); a2 = max(a0, a2); a0 = t;
-        t = min(a1, a3); a3 = max(a1, a3); a1 = t;
-        t = min(a1, a2); a2 = max(a1, a2); a1 = t;
-        L.col[kb] = (unsigned short)a0;
-        L.col[kb + 1] = (unsigned short)a1;
-        if (len > 2) L.col[kb + 2] = (unsigned short)a2;
-        if (len > 3) L.col[kb + 3] = (unsigned short)a3;
-      } else if (len > 4) {
-        for (int a = kb + 1; a < ke; ++a) {
-          const unsigned short key = L.col[a];
-          int b = a - 1;
-          while (b >= kb && L.col[b] > key) { L.col[b + 1] = L.col[b]; --b; }
-          L.col[b + 1] = key;
-        }
-      }
-    }
+    for (int i = tid; i < n; i += NT) csr_sort_row(L.col, L.rowptr[i], L.rowptr[i + 1]);
     __syncthreads();
-  }
-  static __device__ __forceinline__ float4 row_sum(const float* t, const unsigned short* col, int row, int kb, int ke, int c4) {
-    float4 acc = *reinterpret_cast<const float4*>(t + row * TS + 4 * c4);
-    int c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = kb + j < ke ? col[kb + j] : row;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 v = *reinterpret_cast<const float4*>(t + c[j] * TS + 4 * c4);
-      if (kb + j < ke) f4_add(acc, v);
-    }
-    for (int k = kb + 4; __any(k < ke); ++k) {
-      if (k < ke) f4_add(acc, *reinterpret_cast<const float4*>(t + col[k] * TS + 4 * c4));
-    }
-    return acc;
   }
   // the lanes of a wave that hold the same columns (64 / LPR of them) -> one value per column, fixed order
   static __device__ __forceinline__ float4 fold(float4 v) {
@@ -1048,7 +892,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void k_gseg_bwd(
   float4 gmx = f4_zero(), dmx = f4_zero(), dmean = f4_zero();
   auto request = [&](int g) {                          // everything of graph g this thread will need: loads only
     gnext = seg_graph(g, graph_ptr, edge_ptr, npad, status);
-    er.load(gnext, ei, E);
+    er.load(gnext, ei, E, threadIdx.x);
     if (!POOLG) drows.load(dout + coff, gnext, ld);
     if (NEED_A) arows.load(a_out + coff, gnext, ld);
     if constexpr (BITS) {
@@ -1136,7 +980,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void k_gseg_bwd(
         const bool valid = row < gi.n;
         const int rr = valid ? row : gi.n - 1;
         const int kb = valid ? L.rowptr[rr] : 0, ke = valid ? L.rowptr[rr + 1] : 0;
-        const float4 acc = G::row_sum(tile, L.col, rr, kb, ke, c4);
+        const float4 acc = csr_row_sum<TS>(tile, L.col, rr, kb, ke, c4);
         if (valid) *reinterpret_cast<float4*>(Z + (size_t)(gi.nbase + row) * ld + coff + 4 * c4) = f4_scale(L.dinv[rr], acc);
       }
     }

@@ -17,6 +17,7 @@
 // Same slab layout and reduction as the other families; selected inside hcg_mid_* (mid.hip) -- no API of its own.
 #include "common.h"
 #include "split_mfma.h"
+#include "graph_csr.h"
 
 namespace {
 
@@ -68,12 +69,7 @@ __device__ __forceinline__ WGraph w_graph(int g, int B, const int32_t* __restric
   gi.n = graph_ptr[g + 1] - gi.nbase;
   gi.ebase = edge_ptr[g];
   gi.ne = edge_ptr[g + 1] - gi.ebase;
-  // host metadata was wrong: the graph is refused and reported.  (The selects stay OUTSIDE the reporting lane's branch:
-  // assigned inside it, n and ne became per-lane registers and every address derived from them a 64-bit vector computation.)
-  const bool bad = gi.n < 0 || gi.n > WN || gi.ne < 0 || gi.ne > WE;
-  gi.n = __builtin_amdgcn_readfirstlane(bad ? 0 : gi.n);
-  gi.ne = __builtin_amdgcn_readfirstlane(bad ? 0 : gi.ne);
-  if (bad && lane == 0) atomicOr(status, HCG_STATUS_SHAPE_LIMIT);
+  graph_refuse(gi.n, gi.ne, WN, WE, lane, status);
   gi.nblk = (gi.n + 31) / 32;
   gi.nld = gi.n > 0 ? gi.nbase : 0;
   return gi;
@@ -93,26 +89,7 @@ __device__ __forceinline__ WGraph w_uniform(const WGraph& a) {
   return u;
 }
 
-struct WEdges {   // loads only (unconditional, clamped): consumed one graph later
-  long long s[WEPT], d[WEPT];
-  __device__ __forceinline__ void load(const WGraph& gi, const int64_t* __restrict__ ei, int64_t E, int lane) {
-    // (wave-uniform bases + one unsigned 32-bit byte offset per slot: the scalar-base form of global_load; clamps are scalar)
-    long long eb = gi.ebase;
-    eb = eb < 0 ? 0 : (eb > E - 1 ? E - 1 : eb);
-    const long long room = E - eb;
-    const int nec = (long long)gi.ne < room ? gi.ne : (int)room;
-    const int last = nec > 0 ? nec - 1 : 0;
-    const char* sb = reinterpret_cast<const char*>(ei + eb);
-    const char* db = reinterpret_cast<const char*>(ei + E + eb);
-#pragma unroll
-    for (int j = 0; j < WEPT; ++j) {
-      const int e = lane + 64 * j;
-      const unsigned off = 8u * (unsigned)(e < last ? e : last);
-      s[j] = *reinterpret_cast<const long long*>(sb + off);
-      d[j] = *reinterpret_cast<const long long*>(db + off);
-    }
-  }
-};
+using WEdges = EdgeRegs<WEPT, 64>;   // loaded one graph ahead, consumed by w_build_csr
 
 // dinv = (1 + in-degree)^-1/2 and a CSR of the graph in LDS; BY_SRC = false: rows = targets (forward aggregation),
 // true: rows = sources (the transpose).  Explicit (i, i) edges collapse into the unit self loop.  One wave.
@@ -153,7 +130,7 @@ __device__ __forceinline__ void w_build_csr(const WLds& L, const WGraph& gi, con
   L.rowptr[lane] = incl - cnt;
   if (lane == 63) L.rowptr[64] = incl;
   const int degin = BY_SRC ? L.degin[lane] : cnt;
-  L.dinv[lane] = lane < gi.n ? 1.0f / sqrtf(1.0f + (float)degin) : 0.f;
+  L.dinv[lane] = lane < gi.n ? gcn_dinv(degin) : 0.f;
   wave_sync();
   L.cursor[lane] = incl - cnt;
   wave_sync();
@@ -165,31 +142,7 @@ __device__ __forceinline__ void w_build_csr(const WLds& L, const WGraph& gi, con
     }
   }
   wave_sync();
-  {   // every row sorted by id: fixed summation order whatever order the LDS atomics ran in.  Rows of <= 4 entries (all
-      // of them in molecular graphs) through a register network, longer ones by insertion.
-    const int kb = lane < gi.n ? L.rowptr[lane] : 0, ke = lane < gi.n ? L.rowptr[lane + 1] : 0;
-    const int len = ke - kb;
-    if (len > 1 && len <= 4) {
-      unsigned a0 = L.col[kb], a1 = L.col[kb + 1], a2 = len > 2 ? L.col[kb + 2] : 0xffffu, a3 = len > 3 ? L.col[kb + 3] : 0xffffu;
-      unsigned t;
-      t = min(a0, a1); a1 = max(a0, a1); a0 = t;
-      t = min(a2, a3); a3 = max(a2, a3); a2 = t;
-      t = min(a0, a2); a2 = max(a0, a2); a0 = t;
-      t = min(a1, a3); a3 = max(a1, a3); a1 = t;
-      t = min(a1, a2); a2 = max(a1, a2); a1 = t;
-      L.col[kb] = (unsigned short)a0;
-      L.col[kb + 1] = (unsigned short)a1;
-      if (len > 2) L.col[kb + 2] = (unsigned short)a2;
-      if (len > 3) L.col[kb + 3] = (unsigned short)a3;
-    } else if (len > 4) {
-      for (int a = kb + 1; a < ke; ++a) {
-        const unsigned short key = L.col[a];
-        int b = a - 1;
-        while (b >= kb && L.col[b] > key) { L.col[b + 1] = L.col[b]; --b; }
-        L.col[b + 1] = key;
-      }
-    }
-  }
+  csr_sort_row(L.col, lane < gi.n ? L.rowptr[lane] : 0, lane < gi.n ? L.rowptr[lane + 1] : 0);   // every row sorted by id
   wave_sync();
 }
 

@@ -150,11 +150,11 @@ __global__ __launch_bounds__(MT, 2) void k_mid_dense_fwd(const float* __restrict
   (void)dstamp_it;
 
   GraphInfo gi;
-  EdgeRegs er;
+  MidEdges er;
   DenseRows<KPAD, VEC> xr;
   {   // (the grid never exceeds B: every workgroup has a first graph)
     gi = graph_info(blockIdx.x < (unsigned)B ? blockIdx.x : B - 1, graph_ptr, edge_ptr, npad, emax, status);
-    er.load(gi, ei, E);
+    er.load(gi, ei, E, tid);
     xr.load(x, F, gi);
   }
   __syncthreads();                                     // the weight image is staged
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(MT, 2) void k_mid_dense_fwd(const float* __restrict
     if (have_blk) {
       if (cb == 0 && lane < 32) {
         const int row = rb * 32 + lane, dg = L.deg[row];
-        L.dinv[row] = row < gcur.n ? 1.0f / sqrtf(1.0f + (float)dg) : 0.f;
+        L.dinv[row] = row < gcur.n ? gcn_dinv(dg) : 0.f;
         if (dg > 254) atomicOr(status, HCG_STATUS_SHAPE_LIMIT);      // a count byte may have wrapped
       }
       const float* blk = L.t0 + rb * 32 * HS;
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(MT, 2) void k_mid_dense_fwd(const float* __restrict
     {
       const int gn = g + (int)gridDim.x < B ? g + (int)gridDim.x : B - 1;
       gi = graph_info(gn, graph_ptr, edge_ptr, npad, emax, status);
-      er.load(gi, ei, E);
+      er.load(gi, ei, E, tid);
       xr.load(x, F, gi);
     }
     DSTAMP(9);
