@@ -16,7 +16,11 @@ there.  Before the timed region the same rotation runs for `--sustain` (5) secon
 the K timed steps run at the clocks the chip holds under load, not in a cold burst.  `value` = the K steps timed right
 behind it.  `burst` is the old figure: one batch replayed in place (cache resident), timed from idle.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C5|...] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C5|...] [--dump-outputs DIR] [--full]
+A plain run does only what `value` needs: set-up (batch 0 screened as the parity gate needs it, so that both kinds of run
+time the same inputs), warm-up, launch-form pick, sustained rotation, the K timed steps.  `--full` adds everything else
+the JSON line can carry: the parity gate against the fp64 oracle (a failure refuses the timing), launch counts, kernel
+roofline and eager timings, burst and gradients-only figures, the ragged variant and the CPU baseline.
 `--dump-outputs DIR` writes what the last timed step handed its caller (loss, predictions, pooled embedding, every gradient,
 the updated weights) as DIR/<name>.npy, so that two builds can be compared output for output.
 With --gpus N > 1 and no RANK in the environment this script starts its own N ranks (one per GPU, a child
@@ -60,12 +64,15 @@ def parse():
                     help="N > 1: 'rccl' = all-reduce of the flat gradient between two launches; 'oneshot' = every rank writes its "
                          "gradients into the peers' inboxes over the direct xGMI links inside the slab reduction + Adam launch; "
                          "'auto' = one-shot if it sets up and passes its self test on this machine, else RCCL")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: parity gate, launch counts, kernel roofline, "
+                         "eager / burst / gradients-only figures, ragged variant, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-parity-gate", action="store_true", help="development only: skip the oracle check in front of the timings "
-                    "(the JSON line then says parity_gate: null)")
-    ap.add_argument("--no-ragged", action="store_true", help="skip the secondary ragged-batch measurement")
-    ap.add_argument("--cpu-steps", type=int, default=40)
-    ap.add_argument("--roofline-entry", default=None, help="C-ABI entry point timed for the roofline object")
+                    "(--full: the JSON line then says parity_gate: null) and, in every run, the screening of batch 0 it needs")
+    ap.add_argument("--no-ragged", action="store_true", help="--full: skip the secondary ragged-batch measurement")
+    ap.add_argument("--cpu-steps", type=int, default=40, help="--full: CPU baseline steps")
+    ap.add_argument("--roofline-entry", default=None, help="--full: C-ABI entry point timed for the roofline object")
     ap.add_argument("--plan-overlap", default="fused", choices=("none", "fused", "fork"),
                     help="captured step: 'none' = the step's own plan build in front of its forward; 'fused' = every step derives "
                          "the NEXT batch's plan inside its last launch (slab reduction + Adam; -2.5 % at C3); 'fork' = on a forked "
@@ -335,21 +342,30 @@ def cpu_baseline(cfg_name, num_graphs, steps):
             "one_thread": {"value": sb.num_graphs / med_1t, "ms_per_step": med_1t * 1e3, "cores": 1, "steps": n_1t}}
 
 
-def parity_gate(model, r0, trainer, forward_only, dev):
-    """SURVEY 8(d): "parity gates -- run before any timing is accepted".  Step 0 on batch 0 of the rotation through the
-    product path (the same FusedTrainStep / C-ABI launches the timed loop issues, gradients only) against the fp64 CPU oracle:
-    loss, outputs, pooled embedding and EVERY gradient tensor.  Batch 0 is first made decidable (oracle/screen.py: the node
-    features of the few graphs that own an activation within 2e-6 of the LeakyReLU kink or a max-pool near-tie are re-drawn
-    -- one such element legitimately moves a weight gradient by ~1e-3); the timed rotation uses the screened batch.
-    The oracle is the CHECKER here, never the thing measured.  -> the `parity_gate` object of the JSON line."""
-    import torch
-    from oracle import gcn_oracle, screen
-    t0 = time.perf_counter()
+def screen_batch0(model, r0, dev):
+    """Batch 0 made decidable for the parity gate (oracle/screen.py: the node features of the few graphs that own an
+    activation within 2e-6 of the LeakyReLU kink or a max-pool near-tie are re-drawn -- one such element legitimately moves
+    a weight gradient by ~1e-3), on the host and in resident batch 0.  Every run that may gate does this, with or without
+    --full, so that the timed rotation runs on the same screened batch either way.  -> (the initial weights, graphs re-drawn)"""
+    from oracle import screen
     sb = r0.sb
     params = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     x_cpu, redrawn = screen.make_decidable(params, sb.x, sb.edge_index, sb.batch, sb.num_graphs, seed=sb.num_graphs)
     sb.x = x_cpu
     r0.x.copy_(x_cpu.to(dev))
+    return params, redrawn
+
+
+def parity_gate(model, r0, trainer, forward_only, dev):
+    """SURVEY 8(d): "parity gates -- run before any timing is accepted".  Step 0 on batch 0 of the rotation through the
+    product path (the same FusedTrainStep / C-ABI launches the timed loop issues, gradients only) against the fp64 CPU oracle:
+    loss, outputs, pooled embedding and EVERY gradient tensor, on batch 0 as `screen_batch0` leaves it.
+    The oracle is the CHECKER here, never the thing measured.  -> the `parity_gate` object of the JSON line."""
+    import torch
+    from oracle import gcn_oracle
+    t0 = time.perf_counter()
+    sb = r0.sb
+    params, redrawn = screen_batch0(model, r0, dev)
 
     def rel(a, ref, floor=1e-30):
         a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
@@ -530,11 +546,17 @@ def main():
                          "combination times another path")
     dp = None
 
-    # ---- parity gate: no timing is accepted unless step 0 of batch 0 matches the oracle
+    # ---- parity gate (--full): no timing is accepted unless step 0 of batch 0 matches the oracle.  A plain run
+    #      screens batch 0 all the same: the timed steps run on the same inputs with and without --full
     gate = None
     if not args.no_parity_gate:
-        gate = parity_gate(model, r0, fwdbwd, args.forward_only, dev)
-        log(f"parity gate: {'PASSED' if gate['passed'] else 'FAILED ' + str(gate['failed'])} (worst {gate['worst']:.2e}, {gate['seconds']:.1f} s)")
+        if args.full:
+            gate = parity_gate(model, r0, fwdbwd, args.forward_only, dev)
+            log(f"parity gate: {'PASSED' if gate['passed'] else 'FAILED ' + str(gate['failed'])} (worst {gate['worst']:.2e}, {gate['seconds']:.1f} s)")
+        else:
+            t_scr = time.perf_counter()
+            _, redrawn = screen_batch0(model, r0, dev)
+            log(f"batch 0 screened: {redrawn} graphs' features re-drawn ({time.perf_counter() - t_scr:.1f} s); parity gate: --full")
 
     def refuse_timing(why):
         """A failed parity gate: ONE JSON line without a `value` (no timing is accepted), exit code 1."""
@@ -707,7 +729,11 @@ def main():
         rot.eager(j % NB)
     torch.cuda.synchronize()
     log("warm-up done")
-    launch_counts = count_launching_calls()
+    if args.full:
+        launch_counts = count_launching_calls()
+    else:
+        rot.eager(0)        # the step --full counts launches in: the state --dump-outputs restores is the same either way
+        torch.cuda.synchronize()
 
     # ---- N > 1: process group, weights replicated
     rccl_world, xchg = None, None
@@ -798,7 +824,7 @@ def main():
             m["_outputs"] = (last, step_outputs(last))
         return m
 
-    # ---- kernel-level roofline: HIP events around the dominant entry point, inside a timed eager loop (before any graph)
+    # ---- kernel-level roofline (--full): HIP events around the dominant entry point, inside a timed eager loop (before any graph)
     mid = r0.sb.max_nodes > 32
     # 128-wide layers over large graphs run through csrc/tall.hip (one entry point = up to three launches)
     from hcatgnet_amd import functional as _HF
@@ -811,28 +837,29 @@ def main():
         for j in range(max(3, NB)):
             rot.eager(j % NB)
         torch.cuda.synchronize()
-    eager_runner = lambda s, n: rot.run("eager", s, n)
-    timer = EntryTimer(lib, entry)
-    timer.install()
-    timer.enabled = True
-    dt = timed(args.steps, eager_runner)
-    timer.enabled = False
-    k_ms, k_calls = timer.mean_ms()
-    timer.uninstall()
-    log(f"timed (with kernel events): {dt / args.steps * 1e3:.3f} ms/step")
-    dt_eager = timed(args.steps, eager_runner)
-    log(f"timed eager (full step, rotating batches): {dt_eager / args.steps * 1e3:.3f} ms/step")
-    # distribution of single steps (median, p10 / p90): HIP events around every step of one more pass
-    evs = []
-    for j in range(args.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rot.eager(j % NB)
-        e1.record()
-        evs.append((e0, e1))
-    torch.cuda.synchronize()
-    per_step = sorted(a.elapsed_time(b) for a, b in evs)
-    pct = {f"p{q}": per_step[min(len(per_step) - 1, int(len(per_step) * q / 100))] for q in (10, 50, 90)}
+    if args.full:
+        eager_runner = lambda s, n: rot.run("eager", s, n)
+        timer = EntryTimer(lib, entry)
+        timer.install()
+        timer.enabled = True
+        dt = timed(args.steps, eager_runner)
+        timer.enabled = False
+        k_ms, k_calls = timer.mean_ms()
+        timer.uninstall()
+        log(f"timed (with kernel events): {dt / args.steps * 1e3:.3f} ms/step")
+        dt_eager = timed(args.steps, eager_runner)
+        log(f"timed eager (full step, rotating batches): {dt_eager / args.steps * 1e3:.3f} ms/step")
+        # distribution of single steps (median, p10 / p90): HIP events around every step of one more pass
+        evs = []
+        for j in range(args.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rot.eager(j % NB)
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        per_step = sorted(a.elapsed_time(b) for a, b in evs)
+        pct = {f"p{q}": per_step[min(len(per_step) - 1, int(len(per_step) * q / 100))] for q in (10, 50, 90)}
 
     # ---- the headline.  One GPU: one form.  N > 1: EVERY exchange form that is usable here is measured, the plain RCCL form
     #      FIRST (so that whatever happens to a later form, a healthy number is banked), and `value` is the best healthy one
@@ -918,71 +945,74 @@ def main():
         m.pop("_outputs", None)
     log(f"headline: {ms_step:.4f} ms/step ({launch_mode}; sustained {best['sustained']['ms_per_step']:.4f} over {best['sustained']['seconds']:.2f} s)")
 
-    # ---- secondary: burst figures (round 1's headline: ONE batch replayed in place from an idle chip), gradients-only step
+    # ---- secondary (--full): burst figures (round 1's headline: ONE batch replayed in place from an idle chip), gradients-only step
     dt_fb = dt_graph_burst = None
-    one = lambda fn: (lambda s, n: [fn() for _ in range(n)])
-    if fused_ok and world == 1:
-        try:
-            if rot.graphs:
+    if args.full:
+        one = lambda fn: (lambda s, n: [fn() for _ in range(n)])
+        if fused_ok and world == 1:
+            try:
+                if rot.graphs:
+                    for _ in range(3):
+                        trainers[0].replay()
+                    dt_graph_burst = timed(args.steps, one(trainers[0].replay))
+                fwdbwd.capture(r0.fresh)
                 for _ in range(3):
-                    trainers[0].replay()
-                dt_graph_burst = timed(args.steps, one(trainers[0].replay))
-            fwdbwd.capture(r0.fresh)
-            for _ in range(3):
-                fwdbwd.replay()
-            dt_fb = timed(args.steps, one(fwdbwd.replay))
-        except Exception as exc:      # noqa: BLE001
-            log(f"burst figures skipped: {type(exc).__name__}: {exc}")
-    dt_eager_burst = timed(args.steps, lambda s, n: [rot.eager(0) for _ in range(n)])
+                    fwdbwd.replay()
+                dt_fb = timed(args.steps, one(fwdbwd.replay))
+            except Exception as exc:      # noqa: BLE001
+                log(f"burst figures skipped: {type(exc).__name__}: {exc}")
+        dt_eager_burst = timed(args.steps, lambda s, n: [rot.eager(0) for _ in range(n)])
 
     bd = algbytes.breakdown(N, E, B, F, D, opt.n_convolutions)
     step_bytes = sum(v for k, v in bd.items() if not args.forward_only or k.endswith("_fwd") or k == "csr_build")
-    # algorithmic bytes of ONE launch of the timed entry point, averaged over its launches in a step
-    # (layer 2 backward also carries the pool backward it fuses; layer 2 forward the pool forward)
-    entry_bytes = {"hcg_gcn_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"]) / 2.0,
-                   "hcg_gcn_layer_fwd": (bd["conv1_fwd"] + bd["conv2_fwd"]) / 2.0,
-                   "hcg_fused_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"] + bd["pool_bwd"]) / 2.0,
-                   "hcg_mid_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"] + bd["pool_bwd"]) / 2.0,
-                   "hcg_mid_layer_fwd": (bd["conv1_fwd"] + bd["conv2_fwd"] + bd["pool_fwd"]) / 2.0,
-                   "hcg_tall_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"] + bd["pool_bwd"]) / 2.0,
-                   "hcg_tall_layer_fwd": (bd["conv1_fwd"] + bd["conv2_fwd"] + bd["pool_fwd"]) / 2.0,
-                   # (training step: the launch also carries the readout head, forward and backward)
-                   "hcg_fused_forward": bd["conv1_fwd"] + bd["conv2_fwd"] + bd["pool_fwd"] +
-                                        (0 if args.forward_only else bd["readout_fwd"] + bd["readout_bwd"])}.get(entry, float("nan"))
-    achieved = entry_bytes / (k_ms * 1e-3) / 1e9 if k_ms == k_ms and k_ms > 0 else None
-    # HBM bytes per launch from the committed rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE, gfx950
-    # correction of MI355X_MICROARCH.md; tools/pmc_traffic.py) -- only valid for the config they were taken on
-    traffic, traffic_src = None, None
-    tpath = os.path.join(REPO, "profiles", "traffic_latest.json")
-    if cfg_name in ("C2", "C3", "C4", "C5", "REAL") and not extra and args.num_graphs is None and os.path.isfile(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if "C3" in tj or "C5" in tj or "REAL" in tj:      # per-config sections; (round-1 files: flat, C3 only)
-                tj = tj.get(cfg_name if cfg_name in ("C5", "REAL") else "C3", {})
-            elif cfg_name in ("C5", "REAL"):
-                tj = {}
-            prefix = {"hcg_fused_layer_bwd": "k_fused_layer_bwd", "hcg_mid_layer_bwd": "k_mid_layer_bwd",
-                      "hcg_fused_forward": "k_fused_layer_fwd", "hcg_mid_layer_fwd": "k_mid_layer_fwd"}.get(entry)
-            vals = [v["hbm_bytes"] for k, v in tj.items() if prefix and k.startswith(prefix)]
-            traffic = sum(vals) / len(vals) if vals else None
-            if traffic is not None and entry.startswith("hcg_mid_") and D > 64:
-                traffic *= D // 64            # one call of the entry point = one kernel launch per 64-column half
-            if entry.startswith("hcg_tall_layer_"):
-                # one call = several launches (bwd: k_seg_bwd + k_tall_dw + k_tall_mm; fwd: k_split_weight + k_seg_fwd):
-                # bytes of every launch of those kernels in the profiled run / calls of the entry point in it (2 per step)
-                bwd = entry.endswith("bwd")
-                fams = ("k_seg_bwd", "k_gseg_bwd", "k_tall_dw", "k_tall_mm") if bwd else ("k_seg_fwd", "k_split_weight", "k_mid_layer_fwd")
-                tot = sum(v["hbm_bytes"] * v["launches"] for k, v in tj.items() if k.startswith(fams))
-                calls = sum(v["launches"] for k, v in tj.items()
-                            if k.startswith(("k_seg_bwd", "k_gseg_bwd") if bwd else ("k_seg_fwd", "k_mid_layer_fwd")))
-                traffic = tot / calls if calls else None
-            traffic_src = "profiles/traffic_latest.json: builder-run rocprofv3 PMC passes of this command, not measured in this run"
-        except (OSError, ValueError, KeyError, AttributeError):
-            traffic = None
+    if args.full:
+        # algorithmic bytes of ONE launch of the timed entry point, averaged over its launches in a step
+        # (layer 2 backward also carries the pool backward it fuses; layer 2 forward the pool forward)
+        entry_bytes = {"hcg_gcn_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"]) / 2.0,
+                       "hcg_gcn_layer_fwd": (bd["conv1_fwd"] + bd["conv2_fwd"]) / 2.0,
+                       "hcg_fused_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"] + bd["pool_bwd"]) / 2.0,
+                       "hcg_mid_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"] + bd["pool_bwd"]) / 2.0,
+                       "hcg_mid_layer_fwd": (bd["conv1_fwd"] + bd["conv2_fwd"] + bd["pool_fwd"]) / 2.0,
+                       "hcg_tall_layer_bwd": (bd["conv1_bwd"] + bd["conv2_bwd"] + bd["pool_bwd"]) / 2.0,
+                       "hcg_tall_layer_fwd": (bd["conv1_fwd"] + bd["conv2_fwd"] + bd["pool_fwd"]) / 2.0,
+                       # (training step: the launch also carries the readout head, forward and backward)
+                       "hcg_fused_forward": bd["conv1_fwd"] + bd["conv2_fwd"] + bd["pool_fwd"] +
+                                            (0 if args.forward_only else bd["readout_fwd"] + bd["readout_bwd"])}.get(entry, float("nan"))
+        achieved = entry_bytes / (k_ms * 1e-3) / 1e9 if k_ms == k_ms and k_ms > 0 else None
+        # HBM bytes per launch from the committed rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE: the gfx950 correction
+        # applied by tools/pmc_traffic.py) -- only valid for the config they were taken on
+        traffic, traffic_src = None, None
+        tpath = os.path.join(REPO, "profiles", "traffic_latest.json")
+        if cfg_name in ("C2", "C3", "C4", "C5", "REAL") and not extra and args.num_graphs is None and os.path.isfile(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if "C3" in tj or "C5" in tj or "REAL" in tj:      # per-config sections; (round-1 files: flat, C3 only)
+                    tj = tj.get(cfg_name if cfg_name in ("C5", "REAL") else "C3", {})
+                elif cfg_name in ("C5", "REAL"):
+                    tj = {}
+                prefix = {"hcg_fused_layer_bwd": "k_fused_layer_bwd", "hcg_mid_layer_bwd": "k_mid_layer_bwd",
+                          "hcg_fused_forward": "k_fused_layer_fwd", "hcg_mid_layer_fwd": "k_mid_layer_fwd"}.get(entry)
+                vals = [v["hbm_bytes"] for k, v in tj.items() if prefix and k.startswith(prefix)]
+                traffic = sum(vals) / len(vals) if vals else None
+                if traffic is not None and entry.startswith("hcg_mid_") and D > 64:
+                    traffic *= D // 64            # one call of the entry point = one kernel launch per 64-column half
+                if entry.startswith("hcg_tall_layer_"):
+                    # one call = several launches (bwd: k_seg_bwd + k_tall_dw + k_tall_mm; fwd: k_split_weight + k_seg_fwd):
+                    # bytes of every launch of those kernels in the profiled run / calls of the entry point in it (2 per step)
+                    bwd = entry.endswith("bwd")
+                    fams = ("k_seg_bwd", "k_gseg_bwd", "k_tall_dw", "k_tall_mm") if bwd else ("k_seg_fwd", "k_split_weight", "k_mid_layer_fwd")
+                    tot = sum(v["hbm_bytes"] * v["launches"] for k, v in tj.items() if k.startswith(fams))
+                    calls = sum(v["launches"] for k, v in tj.items()
+                                if k.startswith(("k_seg_bwd", "k_gseg_bwd") if bwd else ("k_seg_fwd", "k_mid_layer_fwd")))
+                    traffic = tot / calls if calls else None
+                traffic_src = "profiles/traffic_latest.json: builder-run rocprofv3 PMC passes of this command, not measured in this run"
+            except (OSError, ValueError, KeyError, AttributeError):
+                traffic = None
 
-    # ---- secondary: the ragged variant of the same workload (n_g ~ U{24..36}, "report both")
+    # ---- secondary (--full): the ragged variant of the same workload (n_g ~ U{24..36}, "report both")
     ragged = None
-    if world == 1 and fused_ok and not extra and cfg_name in ("C2", "C3", "C4") and not args.no_ragged and not args.forward_only:
+    if (args.full and world == 1 and fused_ok and not extra and cfg_name in ("C2", "C3", "C4") and not args.no_ragged
+            and not args.forward_only):
         try:
             rr = [Resident(100 + i, **ragged_cfg) for i in range(NB)]
             rtr = [FusedTrainStep(model, optimizer_step=True) for _ in rr]
@@ -1025,6 +1055,7 @@ def main():
             "value": world * B * args.steps / best["seconds"], "unit": "graphs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"{'C2' if args.forward_only and cfg_name == 'C3' else args.config}: {B} synthetic graphs/GPU x "
                                    f"{N / B:.0f} atoms x {E / B:.0f} directed edges x "
                                    f"{F}-d features, {opt.n_convolutions}xGCNConv({D}) + [max,mean] pool + readout; "
@@ -1034,7 +1065,6 @@ def main():
                        "graphs_per_gpu": B, "nodes": N, "edges": E, "feat": F, "hidden": D,
                        "parallelism": f"dp{world} (batch-of-graphs, {'one-shot xGMI exchange' if exchange_mode == 'oneshot' else 'RCCL all-reduce'} "
                                       f"of {sum(p.numel() for p in model.parameters())} fp32 grads)"},
-            "parity_gate": gate,
             "rccl_world": rccl_world, "exchange": exchange_mode,
             # N > 1: every exchange form measured on this machine (the plain collective first), and why a form was not used
             "exchange_forms": exchange_forms or None, "exchange_fallback_reason": fallback_reason,
@@ -1045,35 +1075,40 @@ def main():
             "sustained": dict(best["sustained"], value=(world * B * best["sustained"]["steps"] / best["sustained"]["seconds"]
                                                         if best["sustained"]["seconds"] > 0 else None),
                               note="the same rotation, run right before the timed steps (one synchronize per 256 steps)"),
-            "burst": {"note": "ONE batch replayed in place from an idle chip (cache resident): round 1's headline figure",
-                      "hipgraph_ms_per_step": dt_graph_burst / args.steps * 1e3 if dt_graph_burst else None,
-                      "eager_ms_per_step": dt_eager_burst / args.steps * 1e3,
-                      "value": world * B * args.steps / min(x for x in (dt_graph_burst, dt_eager_burst) if x)},
-            "ragged": ragged,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": entry, "kernel_ms": k_ms, "kernel_launches_timed": k_calls,
-                         "algorithmic_bytes_per_launch": entry_bytes},
             "step_roofline": {"algorithmic_bytes_per_step": step_bytes, "achieved": step_bytes / (ms_step * 1e-3) / 1e9,
                               "unit": "GB/s", "frac": step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                               "breakdown": bd},
-            "fwd_bwd_only": None if dt_fb is None else {"value": world * B * args.steps / dt_fb, "unit": "graphs/s",
-                                                        "ms_per_step": dt_fb / args.steps * 1e3,
-                                                        "note": "burst form, same step without the Adam update (gradients only)"},
             "optimizer": type(model.optimizer).__name__ + "(lr=0.01, eps=1e-9), inside the timed step",
             "step_path": "forward only" if args.forward_only else ("FusedTrainStep (no autograd)" if fused_ok else "autograd"),
-            "library_launching_calls_per_step": {"total": sum(launch_counts.values()), "by_entry_point": launch_counts},
-            "ms_per_step_with_kernel_events": dt / args.steps * 1e3,
-            "eager_step_ms_percentiles_hip_events": pct,
             "launch": launch_mode, "steps_per_graph_launch": spg, "launch_forms_ms": best.get("launch_forms_ms"),
-            "launch_errors": best.get("errors") or None, "eager_ms_per_step": dt_eager / args.steps * 1e3,
+            "launch_errors": best.get("errors") or None,
         }
+        if args.full:
+            rec.update({
+                "parity_gate": gate,
+                "burst": {"note": "ONE batch replayed in place from an idle chip (cache resident): round 1's headline figure",
+                          "hipgraph_ms_per_step": dt_graph_burst / args.steps * 1e3 if dt_graph_burst else None,
+                          "eager_ms_per_step": dt_eager_burst / args.steps * 1e3,
+                          "value": world * B * args.steps / min(x for x in (dt_graph_burst, dt_eager_burst) if x)},
+                "ragged": ragged,
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": entry, "kernel_ms": k_ms, "kernel_launches_timed": k_calls,
+                             "algorithmic_bytes_per_launch": entry_bytes},
+                "fwd_bwd_only": None if dt_fb is None else {"value": world * B * args.steps / dt_fb, "unit": "graphs/s",
+                                                            "ms_per_step": dt_fb / args.steps * 1e3,
+                                                            "note": "burst form, same step without the Adam update (gradients only)"},
+                "library_launching_calls_per_step": {"total": sum(launch_counts.values()), "by_entry_point": launch_counts},
+                "ms_per_step_with_kernel_events": dt / args.steps * 1e3,
+                "eager_step_ms_percentiles_hip_events": pct,
+                "eager_ms_per_step": dt_eager / args.steps * 1e3,
+            })
         if dumped is not None:
             last, arrays = dumped
             rec["dump_outputs"] = dict(write_outputs(args.dump_outputs, arrays, per_graph=("out", "emb")), batch=last,
                                        note="the last timed step (resident batch `batch`), begun from the state set-up ended with")
             log(f"outputs of the last timed step: {len(rec['dump_outputs']['files'])} files in {args.dump_outputs}")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(cfg_name, args.num_graphs, args.cpu_steps)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(rec) + "\n").encode())

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cfgs=$1; shift
 for v in "$@"; do
   for c in $cfgs; do
-    HCG_LIB=$R/hcatgnet_amd/csrc/_variants/$v.so python $R/bench.py --config $c --steps 200 --warmup 20 --no-cpu-baseline --no-ragged --sustain 1.5 \
+    HCG_LIB=$R/hcatgnet_amd/csrc/_variants/$v.so python $R/bench.py --full --config $c --steps 200 --warmup 20 --no-cpu-baseline --no-ragged --sustain 1.5 \
       > /tmp/ab_${v}_$c.json 2> /tmp/ab_${v}_$c.log || { echo "$v $c FAILED"; tail -5 /tmp/ab_${v}_$c.log; exit 1; }
     python - /tmp/ab_${v}_$c.json "$v" "$c" <<'PY'
 import json, sys

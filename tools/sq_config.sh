@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cfg=${1:?config}
 cd /tmp && export TMPDIR=/tmp
-PMC="--steps 10 --warmup 5 --no-cpu-baseline --no-ragged --no-graph --sustain 0 --distinct-batches 2 --no-parity-gate"
+PMC="--full --steps 10 --warmup 5 --no-cpu-baseline --no-ragged --no-graph --sustain 0 --distinct-batches 2 --no-parity-gate"
 rm -rf /tmp/p_sq /tmp/p_sq2
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d /tmp/p_sq -- python $R/bench.py --config $cfg $PMC > /dev/null 2> /tmp/sq1.log || { tail -5 /tmp/sq1.log; exit 1; }
 python $R/tools/pmc_sq.py /tmp/p_sq
