@@ -7,6 +7,8 @@ Public surface (mirrors the reference's names for this path):
     BatchPlan                                   per-batch CSR / gcn_norm plan (GPU)
     DeviceGraphStore, DeviceLoader              dataset resident in HBM, batches collated on the GPU
     DataParallelGCN                             one-process-per-GPU gradient all-reduce (RCCL)
+    optim.FusedAdam / FusedSGD / FusedRMSprop   the reference's --optimizer Adam | SGD | rmsprop (model/networks.py:36-44),
+                                                updated on the device, carried in the step's last launch
     train.FusedTrainStep, train.train_network / eval_network / predict_network
                                                 the reference's loops (utils/utils_model.py:55-111); the step as 6 launches
     io.load_processed_dir / write_embeddings_csv the reference's on-disk formats (reaction_N.pt in, embeddings.csv out)

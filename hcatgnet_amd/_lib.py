@@ -20,6 +20,8 @@ HCG_HEAD_FORWARD_ONLY = 1
 HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2 = 0, 1, 2, 3        # hcg_general_workspace_bytes kinds
 HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                          # hcg_fused_aux_bytes kinds
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
+HCG_STRUCT_UPDATE_ARGS = 5
+HCG_UPDATE_ADAM, HCG_UPDATE_SGD, HCG_UPDATE_RMSPROP = 0, 1, 2      # update rules of hcg_step_tail / hcg_update_dev
 HCG_REDUCE_MAX_JOBS, HCG_REDUCE_MAX_SEGS = 8, 4
 HCG_XCHG_MEAN, HCG_XCHG_SSE, HCG_XCHG_ERR_TIMEOUT, HCG_XCHG_MAX_WORLD = 0, 1, 1, 8
 STATUS_BITS = {1: "edge_index entry outside [0, N)", 2: "batch vector not sorted (non-decreasing)",
@@ -43,12 +45,18 @@ class ReduceJob(ctypes.Structure):
 
 
 class TailArgs(ctypes.Structure):
-    """hcg_tail_args: the step's last launch (slab reductions, loss + deferred scale, exchange, Adam, next plan)."""
+    """hcg_tail_args: the step's last launch (slab reductions, loss + deferred scale, exchange, update, next plan)."""
     _fields_ = [("jobs_host", P), ("njobs", I32), ("loss_mode", I32), ("loss_count", F32), ("beta1", F32), ("beta2", F32),
                 ("eps", F32), ("loss", P), ("sse_tail", P), ("grad_flat", P), ("param", P), ("exp_avg", P), ("exp_avg_sq", P),
                 ("n", I64), ("lr_dev", P), ("step_dev", P), ("next_edge_index", P), ("next_batch", P), ("next_N", I64),
                 ("next_E", I64), ("next_B", I64), ("next_graph_ptr", P), ("next_edge_ptr", P), ("next_status", P), ("inbox", P),
-                ("peers_host", P), ("rank", I32), ("world", I32), ("xchg_mode", I32), ("reserved", I32), ("xchg_err", P)]
+                ("peers_host", P), ("rank", I32), ("world", I32), ("xchg_mode", I32), ("update_rule", I32), ("xchg_err", P)]
+
+
+class UpdateArgs(ctypes.Structure):
+    """hcg_update_args: every rule's capturable update, plain or in the data-parallel SSE form."""
+    _fields_ = [("param", P), ("grad", P), ("exp_avg", P), ("exp_avg_sq", P), ("n", I64), ("lr_dev", P), ("step_dev", P),
+                ("loss", P), ("beta1", F32), ("beta2", F32), ("eps", F32), ("update_rule", I32)]
 
 
 class FusedFwdArgs(ctypes.Structure):
@@ -119,9 +127,9 @@ SIGNATURES = {
     "hcg_head_workspace_bytes": (SZ, [I64, I64]),
     "hcg_head_fwd_bwd": (INT, [P, P, P, P, P, P, I64, I64, I64, F32, INT, P, P, P, P, SZ, P, P]),
     "hcg_head_reduce_job": (INT, [P, SZ, I64, I64, I64, P, P, P, P, P]),
-    "hcg_sse_finalize": (INT, [P, I64, P, P]),
     "hcg_adam_step_dev_sse": (INT, [P, P, P, P, I64, P, F32, F32, F32, P, P, P]),
     "hcg_adam_step_dev": (INT, [P, P, P, P, I64, P, F32, F32, F32, P, P]),
+    "hcg_update_dev": (INT, [P, P]),
     "hcg_xchg_inbox_bytes": (SZ, [I64, INT]),
     "hcg_xchg_resident_blocks": (INT, []),
     "hcg_xchg_alloc": (INT, [SZ, P]),
@@ -225,19 +233,22 @@ def fused_forward(**kw):
 
 
 def step_tail(jobs_addr: int, njobs: int, *, loss=None, loss_mode: int = HCG_LOSS_RMSE, loss_count: float = 0.0, sse_tail=None,
-              adam=None, next_plan=None, xchg=None):
+              update=None, next_plan=None, xchg=None):
     """hcg_step_tail.  `jobs_addr`: host address of `njobs` hcg_reduce_job; `loss` [2] / `sse_tail` [2] device tensors;
-    `adam`: dict(grad_flat, param, exp_avg, exp_avg_sq (tensors), n, lr_dev, step_dev (tensors), beta1, beta2, eps);
+    `update`: dict(rule (HCG_UPDATE_*), grad_flat, param, exp_avg, exp_avg_sq (tensors, None where the rule keeps no such
+    state), n, lr_dev, step_dev (tensors), beta1, beta2, eps);
     `next_plan`: a pointers-only blocked BatchPlan; `xchg`: dict(inbox (address), peers_host (address of the host pointer
     array), rank, world, mode, err (tensor))."""
     a = TailArgs()
     a.jobs_host, a.njobs, a.loss_mode, a.loss_count = jobs_addr, njobs, loss_mode, float(loss_count)
     a.loss, a.sse_tail = ptr(loss), ptr(sse_tail)
-    if adam is not None:
-        a.grad_flat, a.param, a.exp_avg, a.exp_avg_sq = (adam["grad_flat"].data_ptr(), adam["param"].data_ptr(),
-                                                         adam["exp_avg"].data_ptr(), adam["exp_avg_sq"].data_ptr())
-        a.n, a.lr_dev, a.step_dev = adam["n"], adam["lr_dev"].data_ptr(), adam["step_dev"].data_ptr()
-        a.beta1, a.beta2, a.eps = adam["beta1"], adam["beta2"], adam["eps"]
+    if update is not None:
+        u = update
+        a.update_rule = u["rule"]
+        a.grad_flat, a.param, a.exp_avg, a.exp_avg_sq = (u["grad_flat"].data_ptr(), u["param"].data_ptr(),
+                                                         ptr(u.get("exp_avg")), ptr(u.get("exp_avg_sq")))
+        a.n, a.lr_dev, a.step_dev = u["n"], u["lr_dev"].data_ptr(), u["step_dev"].data_ptr()
+        a.beta1, a.beta2, a.eps = u["beta1"], u["beta2"], u["eps"]
     if next_plan is not None:
         np_ = next_plan
         a.next_edge_index, a.next_batch = np_.edge_index.data_ptr(), np_.batch.data_ptr()
@@ -247,6 +258,17 @@ def step_tail(jobs_addr: int, njobs: int, *, loss=None, loss_mode: int = HCG_LOS
         a.inbox, a.peers_host, a.rank, a.world, a.xchg_mode = xchg["inbox"], xchg["peers_host"], xchg["rank"], xchg["world"], xchg["mode"]
         a.xchg_err = xchg["err"].data_ptr()
     check(load().hcg_step_tail(ctypes.addressof(a), stream_ptr()), "hcg_step_tail")
+
+
+def update_dev(grad, *, rule: int = HCG_UPDATE_ADAM, param=None, exp_avg=None, exp_avg_sq=None, n: int = 0, lr_dev=None,
+               step_dev=None, beta1: float = 0.0, beta2: float = 0.0, eps: float = 0.0, loss=None):
+    """hcg_update_dev: the capturable update of rule `rule` (HCG_UPDATE_*) on `n` elements; `loss` set = the SSE form
+    (`grad` = [n gradients | SSE | count], scaled in place); `param` None = that scale and the loss alone."""
+    a = UpdateArgs()
+    a.param, a.grad, a.exp_avg, a.exp_avg_sq = ptr(param), grad.data_ptr(), ptr(exp_avg), ptr(exp_avg_sq)
+    a.n, a.lr_dev, a.step_dev, a.loss = n, ptr(lr_dev), ptr(step_dev), ptr(loss)
+    a.beta1, a.beta2, a.eps, a.update_rule = beta1, beta2, eps, rule
+    check(load().hcg_update_dev(ctypes.addressof(a), stream_ptr()), "hcg_update_dev")
 
 
 def job_bytes() -> int:

@@ -53,6 +53,15 @@ __device__ __forceinline__ float hcg_adam_update(float p, float g, float& m, flo
   return __fsub_rn(p, __fmul_rn(step_size, __fdiv_rn(m, denom)));
 }
 
+// torch.optim.SGD's update (momentum / weight_decay / maximize off) and torch.optim.RMSprop's (momentum / centered /
+// weight_decay / maximize off), explicitly rounded for the same reason as hcg_adam_update
+__device__ __forceinline__ float hcg_sgd_update(float p, float g, float lr) { return __fsub_rn(p, __fmul_rn(lr, g)); }
+
+__device__ __forceinline__ float hcg_rmsprop_update(float p, float g, float& v, float alpha, float eps, float lr) {
+  v = __fmaf_rn(alpha, v, __fmul_rn(__fmul_rn(1.0f - alpha, g), g));
+  return __fsub_rn(p, __fmul_rn(lr, __fdiv_rn(g, __fadd_rn(__fsqrt_rn(v), eps))));
+}
+
 __device__ __forceinline__ float hcg_leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ float hcg_leaky_grad(float y_out, float slope) { return y_out > 0.f ? 1.f : slope; }
 

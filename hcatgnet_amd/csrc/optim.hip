@@ -5,6 +5,7 @@
 // (amsgrad=False, weight_decay=0, maximize=False):
 //   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / ( sqrt(v) / sqrt(1 - b2^t) + eps )
+// The capturable form also runs the reference's other two optimisers with torch's defaults (HCG_UPDATE_SGD, _RMSPROP).
 #include "common.h"
 
 namespace {
@@ -49,15 +50,16 @@ extern "C" int hcg_adam_step(float* param, const float* grad, float* exp_avg, fl
 
 namespace {
 
-// step count and learning rate read from device memory (hipGraph-capturable).  Bias corrections in double
-// like torch's host computation.  The last workgroup to take a ticket (step_dev[2], zero between launches) publishes
-// step + 1 and re-zeroes the ticket; step_dev[1], the exchange stamp, is not touched (a plain update exchanges nothing).
+// step count and learning rate read from device memory (hipGraph-capturable), one kernel per update rule (HCG_UPDATE_*).
+// Adam's bias corrections in double like torch's host computation.  The last workgroup to take a ticket (step_dev[2], zero
+// between launches) publishes step + 1 and re-zeroes the ticket; step_dev[1], the exchange stamp, is not touched (a plain
+// update exchanges nothing).  RMSprop: v = square_avg, b2 = alpha; SGD reads no state.
 // SSE: `g` = [n summed SSE/2-gradients | SSE | count] (data-parallel form HCG_LOSS_SSE): the
 // gradient of sqrt(MSE) over all ranks' graphs is g * 1 / (count * sqrt(SSE / count)); written back in place.
-template <bool SSE>
-__global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, int64_t n, const float* __restrict__ lr_dev, float b1,
-                                                  float b2, float eps, int* __restrict__ step_dev, float* __restrict__ loss) {
+template <int RULE, bool SSE>
+__global__ __launch_bounds__(256) void k_update_dev(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, int64_t n, const float* __restrict__ lr_dev, float b1,
+                                                    float b2, float eps, int* __restrict__ step_dev, float* __restrict__ loss) {
   const int t = step_dev[0] + 1;
   const float lr = lr_dev[0];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -68,14 +70,25 @@ __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, float* 
     if (i == 0) { loss[0] = lv; loss[1] = mse; }
   }
   if (i < n) {
-    const float bc1 = (float)(1.0 - hcg_powi((double)b1, t));
-    const float bc2_sqrt = (float)sqrt(1.0 - hcg_powi((double)b2, t));
+    float bc1 = 1.0f, bc2_sqrt = 1.0f;
+    if (RULE == HCG_UPDATE_ADAM) {
+      bc1 = (float)(1.0 - hcg_powi((double)b1, t));
+      bc2_sqrt = (float)sqrt(1.0 - hcg_powi((double)b2, t));
+    }
     const float gi = g[i] * gs;
     if (SSE) g[i] = gi;
-    float mi = m[i], vi = v[i];
-    p[i] = hcg_adam_update(p[i], gi, mi, vi, b1, b2, eps, lr / bc1, bc2_sqrt);
-    m[i] = mi;
-    v[i] = vi;
+    if (RULE == HCG_UPDATE_ADAM) {
+      float mi = m[i], vi = v[i];
+      p[i] = hcg_adam_update(p[i], gi, mi, vi, b1, b2, eps, lr / bc1, bc2_sqrt);
+      m[i] = mi;
+      v[i] = vi;
+    } else if (RULE == HCG_UPDATE_RMSPROP) {
+      float vi = v[i];
+      p[i] = hcg_rmsprop_update(p[i], gi, vi, b2, eps, lr);
+      v[i] = vi;
+    } else {
+      p[i] = hcg_sgd_update(p[i], gi, lr);
+    }
   }
   __syncthreads();                                     // every thread of this block has read the step word
   if (threadIdx.x == 0) {
@@ -87,14 +100,29 @@ __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, float* 
   }
 }
 
+template <int RULE>
+void launch_update_dev(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, float b1, float b2, float eps,
+                       int32_t* step_dev, float* loss, hipStream_t stream) {
+  const dim3 grid((unsigned)hcg_cdiv(n, 256));
+  if (loss) hipLaunchKernelGGL((k_update_dev<RULE, true>), grid, dim3(256), 0, stream, p, g, m, v, n, lr_dev, b1, b2, eps, (int*)step_dev, loss);
+  else hipLaunchKernelGGL((k_update_dev<RULE, false>), grid, dim3(256), 0, stream, p, g, m, v, n, lr_dev, b1, b2, eps, (int*)step_dev, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_sse_finalize(float* __restrict__ g, int64_t n, float* __restrict__ loss) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float sse = g[n], cnt = g[n + 1], mse = sse / cnt, lv = sqrtf(mse);
+  if (i == 0) { loss[0] = lv; loss[1] = mse; }
+  if (i < n) g[i] *= 1.0f / (cnt * lv);
+}
+
 }  // namespace
 
 extern "C" int hcg_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                  const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_dev,
                                  hcg_stream_t stream) {
   if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !lr_dev || !step_dev) return HCG_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(k_adam_dev<false>, dim3((unsigned)hcg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param,
-                     const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, (int*)step_dev, nullptr);
+  launch_update_dev<HCG_UPDATE_ADAM>(param, const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps,
+                                     step_dev, nullptr, (hipStream_t)stream);
   HCG_CHECK_LAUNCH();
   return HCG_OK;
 }
@@ -103,24 +131,40 @@ extern "C" int hcg_adam_step_dev_sse(float* param, float* flat, float* exp_avg, 
                                      const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_dev, float* loss,
                                      hcg_stream_t stream) {
   if (n <= 0 || !param || !flat || !exp_avg || !exp_avg_sq || !lr_dev || !step_dev || !loss) return HCG_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(k_adam_dev<true>, dim3((unsigned)hcg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param, flat,
-                     exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, (int*)step_dev, loss);
+  launch_update_dev<HCG_UPDATE_ADAM>(param, flat, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, step_dev, loss,
+                                     (hipStream_t)stream);
   HCG_CHECK_LAUNCH();
   return HCG_OK;
 }
 
-namespace {
-__global__ __launch_bounds__(256) void k_sse_finalize(float* __restrict__ g, int64_t n, float* __restrict__ loss) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const float sse = g[n], cnt = g[n + 1], mse = sse / cnt, lv = sqrtf(mse);
-  if (i == 0) { loss[0] = lv; loss[1] = mse; }
-  if (i < n) g[i] *= 1.0f / (cnt * lv);
-}
-}  // namespace
-
-extern "C" int hcg_sse_finalize(float* flat, int64_t n, float* loss, hcg_stream_t stream) {
-  if (n <= 0 || !flat || !loss) return HCG_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(k_sse_finalize, dim3((unsigned)hcg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, flat, n, loss);
+extern "C" int hcg_update_dev(const hcg_update_args* a, hcg_stream_t stream_) {
+  if (!a || a->n <= 0 || !a->grad) return HCG_ERR_INVALID_ARG;
+  const hipStream_t stream = (hipStream_t)stream_;
+  if (!a->param) {                                     // the SSE form's scale and loss alone
+    if (!a->loss) return HCG_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_sse_finalize, dim3((unsigned)hcg_cdiv(a->n, 256)), dim3(256), 0, stream, a->grad, a->n, a->loss);
+    HCG_CHECK_LAUNCH();
+    return HCG_OK;
+  }
+  if (!a->lr_dev || !a->step_dev) return HCG_ERR_INVALID_ARG;
+  switch (a->update_rule) {
+    case HCG_UPDATE_ADAM:
+      if (!a->exp_avg || !a->exp_avg_sq) return HCG_ERR_INVALID_ARG;
+      launch_update_dev<HCG_UPDATE_ADAM>(a->param, a->grad, a->exp_avg, a->exp_avg_sq, a->n, a->lr_dev, a->beta1, a->beta2,
+                                         a->eps, a->step_dev, a->loss, stream);
+      break;
+    case HCG_UPDATE_SGD:
+      launch_update_dev<HCG_UPDATE_SGD>(a->param, a->grad, nullptr, nullptr, a->n, a->lr_dev, 0.f, 0.f, 0.f, a->step_dev,
+                                        a->loss, stream);
+      break;
+    case HCG_UPDATE_RMSPROP:
+      if (!a->exp_avg_sq) return HCG_ERR_INVALID_ARG;
+      launch_update_dev<HCG_UPDATE_RMSPROP>(a->param, a->grad, nullptr, a->exp_avg_sq, a->n, a->lr_dev, 0.f, a->beta2, a->eps,
+                                            a->step_dev, a->loss, stream);
+      break;
+    default:
+      return HCG_ERR_INVALID_ARG;
+  }
   HCG_CHECK_LAUNCH();
   return HCG_OK;
 }

@@ -32,14 +32,16 @@ struct Jobs {
 constexpr int RS = 8;
 constexpr int RO = 256 / RS;   // output elements per 256-thread block
 
-// Adam state for the fused "reduce, then update" variant: every reduced gradient element is written to its place in
-// the flat gradient buffer AND immediately used for torch.optim.Adam's update of the parameter at the same offset
-// (one launch fewer per step; the reference's optimiser: model/networks.py:38).
-struct AdamArgs {
+// Optimiser state for the fused "reduce, then update" variant: every reduced gradient element is written to its place in
+// the flat gradient buffer AND immediately used for the optimiser's update of the parameter at the same offset
+// (one launch fewer per step; the reference's optimisers: model/networks.py:36-44).
+// The rule is the kernel's UPD parameter (HCG_UPDATE_*, or NO_UPDATE); RMSprop keeps square_avg in v and alpha in b2.
+constexpr int NO_UPDATE = -1;
+struct UpdateArgs {
   const float* grad_flat;   // base of the flat gradient buffer every segment's dst points into
   float* p;
-  float* m;
-  float* v;
+  float* m;                 // Adam only
+  float* v;                 // Adam, RMSprop
   const float* lr_dev;
   const int* step_dev;      // [0] = 1-based number of this update, [1] = exchange stamp (monotonic)
   float b1, b2, eps;
@@ -135,8 +137,9 @@ __device__ __forceinline__ float loss_sse_sum(const LossArgs& L, int lane) {
   return s;
 }
 
-template <bool ADAM, bool XCHG = false>
-__global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, AdamArgs A, PlanArgs P, LossArgs L, XchgArgs X = XchgArgs{}) {
+template <int UPD, bool XCHG = false>
+__global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, UpdateArgs A, PlanArgs P, LossArgs L, XchgArgs X = XchgArgs{}) {
+  static_assert(!XCHG || UPD == HCG_UPDATE_ADAM, "the exchange rides with Adam's update only");
   // a 1-D grid without idle workgroups: [blocks of job 0 | blocks of job 1 | ... | the plan's blocks] (as a 2-D grid of
   // njobs + 1 rows as wide as the widest -- the plan's -- two thirds of the 6 000 workgroups at C3 returned at once)
   int blk = blockIdx.x, jsel = 0;
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, AdamArgs A, PlanAr
   const hcg_reduce_job& J = jobs.job[jsel];
   const int o = threadIdx.x % RO, sl = threadIdx.x / RO;
   const int idx = blk * RO + o;
-  // [0] lr / bias-correction-1, [1] sqrt(bias-correction-2), [2] scale applied to this rank's sum (before an exchange),
+  // [0] lr / bias-correction-1 (SGD, RMSprop: lr), [1] sqrt(bias-correction-2), [2] scale applied to this rank's sum (before an exchange),
   // [3] scale applied to the exchanged total
   __shared__ float adam_c[4];
   // the exchange stamp is step_dev[1]: advanced with step_dev[0] by the step's first launch, but owned by no optimiser state --
@@ -159,10 +162,12 @@ __global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, AdamArgs A, PlanAr
   const unsigned xstep = XCHG ? (unsigned)A.step_dev[1] : 0u;
   const int parity = (int)(xstep & 1u);
   const bool first = blockIdx.x == 0;
-  if (ADAM && threadIdx.x == 0) {                    // bias corrections in double like torch's host computation
+  if (UPD == HCG_UPDATE_ADAM && threadIdx.x == 0) {  // bias corrections in double like torch's host computation
     const int t = A.step_dev[0];                     // number of THIS update (advanced earlier in the step)
     adam_c[0] = A.lr_dev[0] / (float)(1.0 - hcg_powi((double)A.b1, t));
     adam_c[1] = (float)sqrt(1.0 - hcg_powi((double)A.b2, t));
+  } else if (UPD != NO_UPDATE && threadIdx.x == 0) {
+    adam_c[0] = A.lr_dev[0];
   }
   if (threadIdx.x >= 192) {                          // wave 3: the loss, its scale, the exchange of [SSE, count]
     const int lane = threadIdx.x - 192;
@@ -214,10 +219,10 @@ __global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, AdamArgs A, PlanAr
         if (cc < S.row_out) gdst = S.dst + (size_t)rr * S.row_out + cc;
       }
     }
-    if (ADAM && gdst) {
+    if (UPD != NO_UPDATE && gdst) {
       off = (size_t)(gdst - A.grad_flat);
-      m0 = A.m[off];
-      v0 = A.v[off];
+      if (UPD == HCG_UPDATE_ADAM) m0 = A.m[off];
+      if (UPD == HCG_UPDATE_ADAM || UPD == HCG_UPDATE_RMSPROP) v0 = A.v[off];
       p0 = A.p[off];
     }
   }
@@ -238,11 +243,17 @@ __global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, AdamArgs A, PlanAr
       tot = xchg_gather(X, parity, (int64_t)off, tot, xstep) * adam_c[3];
     }
     *gdst = tot;
-    if (ADAM) {
+    if (UPD == HCG_UPDATE_ADAM) {
       float mi = m0, vi = v0;
       A.p[off] = hcg_adam_update(p0, tot, mi, vi, A.b1, A.b2, A.eps, adam_c[0], adam_c[1]);
       A.m[off] = mi;
       A.v[off] = vi;
+    } else if (UPD == HCG_UPDATE_RMSPROP) {
+      float vi = v0;
+      A.p[off] = hcg_rmsprop_update(p0, tot, vi, A.b2, A.eps, adam_c[0]);
+      A.v[off] = vi;
+    } else if (UPD == HCG_UPDATE_SGD) {
+      A.p[off] = hcg_sgd_update(p0, tot, adam_c[0]);
     }
   }
 }
@@ -289,7 +300,7 @@ extern "C" int hcg_xchg_resident_blocks(void) {
   if (cap >= 0) return cap;
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_step_tail<true, true>, 256, 0) != hipSuccess) per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_step_tail<HCG_UPDATE_ADAM, true>, 256, 0) != hipSuccess) per_cu = 0;
   cap = cus * per_cu;
   return cap;
 }
@@ -302,6 +313,7 @@ extern "C" size_t hcg_struct_bytes(int which) {
     case HCG_STRUCT_FUSED_FWD_ARGS: return sizeof(hcg_fused_fwd_args);
     case HCG_STRUCT_COLLATE_ARGS: return sizeof(hcg_collate_args);
     case HCG_STRUCT_COLLATE_SLOT: return sizeof(hcg_collate_slot);
+    case HCG_STRUCT_UPDATE_ARGS: return sizeof(hcg_update_args);
     default: return 0;
   }
 }
@@ -311,13 +323,22 @@ extern "C" int hcg_step_tail(const hcg_tail_args* a, hcg_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int njobs = a->njobs;
   const hcg_reduce_job* jobs_host = a->jobs_host;
-  const bool adam = a->param != nullptr, plan = a->next_batch != nullptr, xchg = a->inbox != nullptr;
+  const bool upd = a->param != nullptr, plan = a->next_batch != nullptr, xchg = a->inbox != nullptr;
+  const int rule = a->update_rule;
   if (njobs < 0 || njobs > HCG_REDUCE_MAX_JOBS || (njobs > 0 && !jobs_host)) return HCG_ERR_INVALID_ARG;
-  if (njobs == 0) return (adam || plan || xchg) ? HCG_ERR_INVALID_ARG : HCG_OK;
-  AdamArgs A{};
-  if (adam) {
-    if (a->n <= 0 || !a->grad_flat || !a->exp_avg || !a->exp_avg_sq || !a->lr_dev || !a->step_dev) return HCG_ERR_INVALID_ARG;
-    A = AdamArgs{a->grad_flat, a->param, a->exp_avg, a->exp_avg_sq, a->lr_dev, (const int*)a->step_dev, a->beta1, a->beta2, a->eps};
+  if (njobs == 0) return (upd || plan || xchg) ? HCG_ERR_INVALID_ARG : HCG_OK;
+  UpdateArgs A{};
+  if (upd) {
+    if (a->n <= 0 || !a->grad_flat || !a->lr_dev || !a->step_dev) return HCG_ERR_INVALID_ARG;
+    if (rule == HCG_UPDATE_ADAM) {
+      if (!a->exp_avg || !a->exp_avg_sq) return HCG_ERR_INVALID_ARG;
+    } else if (rule == HCG_UPDATE_RMSPROP) {
+      if (!a->exp_avg_sq) return HCG_ERR_INVALID_ARG;
+    } else if (rule != HCG_UPDATE_SGD) {
+      return HCG_ERR_INVALID_ARG;
+    }
+    A = UpdateArgs{a->grad_flat, a->param, rule == HCG_UPDATE_ADAM ? a->exp_avg : nullptr,
+                   rule == HCG_UPDATE_SGD ? nullptr : a->exp_avg_sq, a->lr_dev, (const int*)a->step_dev, a->beta1, a->beta2, a->eps};
   }
   PlanArgs P{};
   if (plan) {
@@ -328,7 +349,7 @@ extern "C" int hcg_step_tail(const hcg_tail_args* a, hcg_stream_t stream_) {
   }
   XchgArgs X{};
   if (xchg) {
-    if (!adam || !a->peers_host || !a->loss || !a->xchg_err) return HCG_ERR_INVALID_ARG;
+    if (!upd || rule != HCG_UPDATE_ADAM || !a->peers_host || !a->loss || !a->xchg_err) return HCG_ERR_INVALID_ARG;
     if (a->world < 1 || a->world > HCG_XCHG_MAX_WORLD || a->rank < 0 || a->rank >= a->world ||
         (a->xchg_mode != HCG_XCHG_MEAN && a->xchg_mode != HCG_XCHG_SSE))
       return HCG_ERR_INVALID_ARG;
@@ -351,7 +372,7 @@ extern "C" int hcg_step_tail(const hcg_tail_args* a, hcg_stream_t stream_) {
     for (int g = 0; g < J.nseg; ++g) {
       const hcg_reduce_seg& S = J.seg[g];
       if (!S.dst || S.row_in <= 0 || S.row_out <= 0 || S.row_out > S.row_in || S.count < 0) return HCG_ERR_INVALID_ARG;
-      if (adam) {   // the update addresses param / moments by the gradient's offset: every dst must lie in the flat buffer
+      if (upd) {    // the update addresses param / moments by the gradient's offset: every dst must lie in the flat buffer
         const int64_t rows = (S.count + S.row_in - 1) / S.row_in;
         if (S.dst < a->grad_flat || S.dst + rows * S.row_out > a->grad_flat + a->n) return HCG_ERR_INVALID_ARG;
       }
@@ -366,9 +387,11 @@ extern "C" int hcg_step_tail(const hcg_tail_args* a, hcg_stream_t stream_) {
   if (plan) total_blocks += (unsigned)hcg_cdiv(P.N + P.E + 2, 256);
   if (total_blocks == 0) return HCG_OK;
   const dim3 grid(total_blocks);
-  if (xchg) hipLaunchKernelGGL((k_step_tail<true, true>), grid, dim3(256), 0, stream, jobs, A, P, L, X);
-  else if (adam) hipLaunchKernelGGL((k_step_tail<true, false>), grid, dim3(256), 0, stream, jobs, A, P, L, XchgArgs{});
-  else hipLaunchKernelGGL((k_step_tail<false, false>), grid, dim3(256), 0, stream, jobs, A, P, L, XchgArgs{});
+  if (xchg) hipLaunchKernelGGL((k_step_tail<HCG_UPDATE_ADAM, true>), grid, dim3(256), 0, stream, jobs, A, P, L, X);
+  else if (!upd) hipLaunchKernelGGL((k_step_tail<NO_UPDATE, false>), grid, dim3(256), 0, stream, jobs, A, P, L, XchgArgs{});
+  else if (rule == HCG_UPDATE_ADAM) hipLaunchKernelGGL((k_step_tail<HCG_UPDATE_ADAM, false>), grid, dim3(256), 0, stream, jobs, A, P, L, XchgArgs{});
+  else if (rule == HCG_UPDATE_SGD) hipLaunchKernelGGL((k_step_tail<HCG_UPDATE_SGD, false>), grid, dim3(256), 0, stream, jobs, A, P, L, XchgArgs{});
+  else hipLaunchKernelGGL((k_step_tail<HCG_UPDATE_RMSPROP, false>), grid, dim3(256), 0, stream, jobs, A, P, L, XchgArgs{});
   HCG_CHECK_LAUNCH();
   return HCG_OK;
 }

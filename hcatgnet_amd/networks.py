@@ -50,14 +50,15 @@ class BaseNetwork(nn.Module):
             raise ValueError(f"Problem type {problem_type} not supported")
 
     def _make_optimizer(self, optimizer, lr):
+        # the reference's torch.optim.Adam(lr, eps=1e-9) / SGD(lr) / RMSprop(lr) (model/networks.py:36-44); same rules,
+        # one HIP launch (or none of their own: carried in the step's last launch)
+        from .optim import FusedAdam, FusedRMSprop, FusedSGD
         if optimizer == "Adam":
-            # torch.optim.Adam(lr, eps=1e-9) in the reference (model/networks.py:38); same rule, one HIP launch
-            from .optim import FusedAdam
             self.optimizer = FusedAdam(self.parameters(), lr=lr, eps=1e-9)
         elif optimizer == "SGD":
-            self.optimizer = torch.optim.SGD(self.parameters(), lr=lr)
+            self.optimizer = FusedSGD(self.parameters(), lr=lr)
         elif optimizer == "rmsprop":
-            self.optimizer = torch.optim.RMSprop(self.parameters(), lr=lr)
+            self.optimizer = FusedRMSprop(self.parameters(), lr=lr)
         else:
             raise NotImplementedError(f"Optimizer type {optimizer} not implemented")
 

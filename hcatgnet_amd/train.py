@@ -92,7 +92,7 @@ class FusedTrainStep:
         # data parallel: a `xgmi.OneShotExchange` (set by its `attach`): the gradient exchange then happens INSIDE the step's
         # last launch instead of as an RCCL collective between two launches
         self.exchange = None
-        self._last_carried = False              # the last step's tail launch carried reduction + (exchange) + Adam
+        self._last_carried = False              # the last step's tail launch carried reduction + (exchange) + update
         self.exchange_fallback_sync = None      # the collective hook `OneShotExchange.attach` took out of `grad_sync`
         # one-device rehearsals only (two ranks sharing a GPU): called right before the launch that carries the exchange.
         # A rank's polling launch fills every CU, and the OTHER process's conv kernels (488 of a SIMD's 512 VGPRs per
@@ -288,7 +288,7 @@ class FusedTrainStep:
                     off += q.numel()
                 ga = self._gaddr = (c.flat.data_ptr(), params, addr)
             c.gaddr = ga[2]
-            # without a collective between backward and update, the step's last launch applies Adam itself; the head
+            # without a collective between backward and update, the step's last launch applies the update itself; the head
             # advances the step number that launch reads
             opt = model.optimizer
             # (a one-shot exchange rides in that launch only when all its polling workgroups are resident at once: the
@@ -632,8 +632,7 @@ class FusedTrainStep:
                 self._flat_grads(self._trainable(), flat.device)
                 opt.step_sse(ext, loss_buf)                  # scale + update, one launch
             else:
-                _lib.check(lib.hcg_sse_finalize(_lib.ptr(ext), flat.numel(), _lib.ptr(loss_buf), _lib.stream_ptr()),
-                           "hcg_sse_finalize")
+                _lib.update_dev(ext, n=flat.numel(), loss=loss_buf)     # the scale and the loss alone
                 if self.optimizer_step:
                     opt.step()
             return
@@ -650,7 +649,7 @@ class FusedTrainStep:
         """Capture the step on `batch`'s tensors into a hipGraph; `replay()` re-runs it on whatever those tensors
         hold then (copy the next batch into them, or re-collate in place).  `batch` may be a callable returning the
         batch: whatever it enqueues (a device collate, the plan build of a fresh `Batch`) is captured too.  The optimiser switches to its
-        device-side step counter / learning rate (`FusedAdam.enable_capturable`); the gradient exchange
+        device-side step counter / learning rate (`optim.FusedFlatOptimizer.enable_capturable`); the gradient exchange
         (`grad_sync`) is NOT captured: with one, the graph ends after the slab reduction and `replay()` issues the
         collective and the (single-launch) update eagerly behind it.
         `prefetch`: a callable whose launches are captured on a FORKED branch of the graph (forks at the start of the
@@ -662,7 +661,8 @@ class FusedTrainStep:
         opt = self.model.optimizer
         if self.optimizer_step:
             if not hasattr(opt, "enable_capturable"):
-                raise _lib.HcgError("capture() with optimizer_step needs hcatgnet_amd.optim.FusedAdam")
+                raise _lib.HcgError("capture() with optimizer_step needs a fused optimiser of hcatgnet_amd.optim "
+                                    "(FusedAdam, FusedSGD, FusedRMSprop)")
             opt.enable_capturable()
         sync, do_opt = self.grad_sync, self.optimizer_step
 
@@ -713,7 +713,7 @@ class FusedTrainStep:
 
     def _graph_fingerprint(self):
         """Addresses a captured graph has baked in and that later calls could replace: step buffers, flat gradient,
-        the optimiser's flat parameter / moment storages."""
+        the optimiser's flat parameter / state storages."""
         cap = self._bufs.get("cap")
         fp = [t.data_ptr() for t in cap["acts"] + cap["dacts"]] if cap else []
         if cap:      # kernel workspaces (slabs, pooled bits, the wide-layer kernels' dH buffer): they grow on demand
@@ -721,9 +721,10 @@ class FusedTrainStep:
                    if torch.is_tensor(t)]
             fp.append(cap["ws_head"].data_ptr())
         fp.append(self._flat.data_ptr() if getattr(self, "_flat", None) is not None else 0)
-        fl = getattr(self.model.optimizer, "_flat", {}).get(0) if self.optimizer_step else None
+        opt = self.model.optimizer
+        fl = getattr(opt, "_flat", {}).get(0) if self.optimizer_step else None
         if fl is not None:
-            fp += [fl["p"].data_ptr(), fl["m"].data_ptr(), fl["v"].data_ptr()]
+            fp += [t.data_ptr() for t in [fl["p"]] + opt.flat_state(fl)]
         fp += [q.data_ptr() for q in self._trainable()]      # (cached walk: this runs on every replay)
         return tuple(fp)
 
@@ -777,7 +778,8 @@ class StepWindow:
                 raise _lib.HcgError("a step with a separate gradient collective (grad_sync) cannot be captured into a window "
                                     "(unless its `capture_exchange` is set: the collective is then recorded with the step)")
             if st.optimizer_step and not hasattr(model.optimizer, "enable_capturable"):
-                raise _lib.HcgError("StepWindow with optimizer_step needs hcatgnet_amd.optim.FusedAdam")
+                raise _lib.HcgError("StepWindow with optimizer_step needs a fused optimiser of hcatgnet_amd.optim "
+                                    "(FusedAdam, FusedSGD, FusedRMSprop)")
         self.forward_only = bool(forward_only)
         if steps[0].optimizer_step and not self.forward_only:
             model.optimizer.enable_capturable()
@@ -932,13 +934,15 @@ class EpochWindow:
             with torch.no_grad():
                 fl = opt._rebase(0, opt.param_groups[0])
         opt._make_dev_state(fl, opt.param_groups[0])
-        saved = [fl["p"].clone(), fl["m"].clone(), fl["v"].clone(), fl["step_dev"][:1].clone()]
+        live = [fl["p"]] + opt.flat_state(fl) + [fl["step_dev"][:1]]        # parameters, the rule's state, the step count
+        saved = [t.clone() for t in live]
         try:
             self.window = StepWindow(self.steps, fns, counts64=self.counts)
         finally:
             torch.cuda.synchronize()
             with torch.no_grad():
-                fl["p"].copy_(saved[0]); fl["m"].copy_(saved[1]); fl["v"].copy_(saved[2]); fl["step_dev"][:1].copy_(saved[3])
+                for t, u in zip(live, saved):
+                    t.copy_(u)
         if opt._flat.get(0) is not fl:
             raise _lib.HcgError("EpochWindow: the optimiser re-based its state during the capture")
 

@@ -87,8 +87,9 @@ class OneShotExchange:
                loss_mode=_lib.HCG_LOSS_SSE):
         """ONE launch: slab reductions, (loss scale,) exchange, Adam update, optionally the next batch's plan."""
         _lib.step_tail(jobs_addr, njobs, loss=loss_buf, loss_mode=loss_mode, loss_count=loss_count,
-                       adam=dict(grad_flat=flat_ext, param=fl["p"], exp_avg=fl["m"], exp_avg_sq=fl["v"], n=fl["n"],
-                                 lr_dev=fl["lr_dev"], step_dev=fl["step_dev"], beta1=b1, beta2=b2, eps=eps),
+                       update=dict(rule=_lib.HCG_UPDATE_ADAM, grad_flat=flat_ext, param=fl["p"], exp_avg=fl["m"],
+                                   exp_avg_sq=fl["v"], n=fl["n"], lr_dev=fl["lr_dev"], step_dev=fl["step_dev"], beta1=b1,
+                                   beta2=b2, eps=eps),
                        next_plan=next_plan, xchg=self.tail_args(mode))
 
     def attach(self, step):
@@ -101,6 +102,9 @@ class OneShotExchange:
             raise ValueError(f"exchange built for {self.n} gradients, the model has {n}")
         if not (step.optimizer_step and hasattr(step.model.optimizer, "step_with_reduction")):
             raise ValueError("the one-shot exchange rides in the fused update: it needs optimizer_step=True and FusedAdam")
+        if getattr(step.model.optimizer, "RULE", None) != _lib.HCG_UPDATE_ADAM:
+            raise ValueError(f"the one-shot exchange carries Adam's update only, not {type(step.model.optimizer).__name__}'s: "
+                             "keep the RCCL form (DataParallelGCN with its collective, combine='mean' or 'sse')")
         if step.grad_sync is None:
             raise ValueError("attach the trainer to a DataParallelGCN first (`dp.attach(step)` / `dp.make_train_step()`): its "
                              "collective stays behind as the fallback of the steps the fused update cannot carry")

@@ -333,7 +333,7 @@ int hcg_head_fwd_bwd(const float* emb, const float* y, const float* W0, const fl
 #define HCG_LOSS_MSE 0  /* nn.MSELoss                                  : scale 2 / count            */
 #define HCG_LOSS_RMSE 1 /* torch.sqrt(nn.MSELoss) (the reference's step): scale 1 / (count sqrt(MSE)) */
 #define HCG_LOSS_SSE 2  /* data parallel with a collective: gradients stay those of SSE / 2, [SSE, count] go to sse_tail;
-                           ranks sum gradients, SSE and count (ONE all-reduce) and hcg_sse_finalize / hcg_adam_step_dev_sse
+                           ranks sum gradients, SSE and count (ONE all-reduce) and hcg_update_dev / hcg_adam_step_dev_sse
                            scale by 1 / (count sqrt(SSE / count)): the gradient of sqrt(MSE) over the concatenated batch of
                            all ranks, which is what the reference's step computes on one device */
 
@@ -373,6 +373,7 @@ typedef struct hcg_reduce_job {
 #define HCG_STRUCT_FUSED_FWD_ARGS 2
 #define HCG_STRUCT_COLLATE_ARGS 3
 #define HCG_STRUCT_COLLATE_SLOT 4
+#define HCG_STRUCT_UPDATE_ARGS 5
 size_t hcg_struct_bytes(int which);
 int hcg_fused_reduce_job(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F,
                          int64_t D, int graphs_per_tile, float* dW, float* db, hcg_reduce_job* job_host);
@@ -400,10 +401,12 @@ int hcg_reduce_job_append(hcg_reduce_job* job_host, const hcg_reduce_job* more_h
  *       loss[1] = MSE, and every reduced element is multiplied by the scale (see hcg_head_fwd_bwd); HCG_LOSS_SSE leaves the
  *       gradients unscaled and stores this rank's [SSE, count] in sse_tail;
  *   (3) inbox != NULL: the data-parallel one-shot exchange over xGMI (below) between reduction and update;
- *   (4) param != NULL: torch.optim.Adam's update of the parameter / moments at the offset of each gradient element in the
- *       flat buffer [grad_flat, grad_flat + n) -- every segment's dst must point into it and every element of it must be
- *       covered by exactly one segment; `step_dev[0]` = 1-based number of THIS update, already advanced when the kernel
- *       runs (the head launch's step_counter does that earlier in the step; this launch only reads it), lr_dev[0] = lr;
+ *   (4) param != NULL: the optimiser's update (`update_rule`, HCG_UPDATE_*) of the parameter / its state at the offset of
+ *       each gradient element in the flat buffer [grad_flat, grad_flat + n) -- every segment's dst must point into it and
+ *       every element of it must be covered by exactly one segment; `step_dev[0]` = 1-based number of THIS update, already
+ *       advanced when the kernel runs (the head launch's step_counter does that earlier in the step; this launch only reads
+ *       it), lr_dev[0] = lr.  Adam: exp_avg, exp_avg_sq, beta1, beta2, eps; RMSprop: exp_avg_sq = square_avg, beta2 =
+ *       alpha, eps; SGD: no state (exp_avg / exp_avg_sq unused).  The exchange (3) rides with HCG_UPDATE_ADAM only;
  *   (5) next_batch != NULL: the pointers-only plan of the NEXT batch (what hcg_plan_build does with HCG_PLAN_BLOCKED |
  *       HCG_PLAN_PTRS_ONLY | HCG_PLAN_KEEP_STATUS): the one launch of the next step that depends on nothing of this one.
  * Replaces the four hcg_reduce_slabs* entry points of round 2 (one symbol per fusion combination).  HOST struct; zero it
@@ -432,13 +435,21 @@ typedef struct hcg_tail_args {
   void* inbox;                 /* NULL = no exchange */
   void* const* peers_host;     /* HOST array of `world` device pointers (peers_host[rank] = inbox) */
   int32_t rank, world, xchg_mode;
-  int32_t reserved;
+  int32_t update_rule;         /* HCG_UPDATE_*; 0 (a zeroed struct) = Adam */
   int32_t* xchg_err;
 } hcg_tail_args;
 int hcg_step_tail(const hcg_tail_args* args_host, hcg_stream_t stream);
 /* forward-only steps (the reference's eval_network body, utils/utils_model.py:75-78): the loss alone from a head job's partials */
 int hcg_loss_finalize(const hcg_reduce_job* head_job_host, float count, int loss_mode, float* loss,
                       float* sse_tail /*nullable*/, hcg_stream_t stream);
+
+/* update rules of hcg_step_tail / hcg_update_dev, torch's defaults for each (torch.optim.Adam(lr, betas, eps): amsgrad /
+ * weight_decay / maximize off; torch.optim.SGD(lr): momentum / dampening / nesterov / weight_decay / maximize off,
+ * p -= lr g; torch.optim.RMSprop(lr, alpha, eps): momentum / centered / weight_decay / maximize off,
+ * v = alpha v + (1 - alpha) g^2, p -= lr g / (sqrt(v) + eps)) */
+#define HCG_UPDATE_ADAM 0
+#define HCG_UPDATE_SGD 1
+#define HCG_UPDATE_RMSPROP 2
 
 /* ---- Adam update (f2) over one contiguous fp32 segment: torch.optim.Adam's rule (amsgrad / weight_decay /
  *      maximize off).  `step` = 1-based count of this update.  One launch. */
@@ -454,12 +465,33 @@ int hcg_adam_step_dev(float* param, const float* grad, float* exp_avg, float* ex
                       const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_dev, hcg_stream_t stream);
 
 /* Data-parallel SSE form (HCG_LOSS_SSE): `flat` = [n summed SSE/2-gradients | SSE | count].  Scales the n
- * gradients in place by 1 / (count * L), L = sqrt(SSE / count), and stores loss[0] = L, loss[1] = SSE / count.
- * hcg_adam_step_dev_sse does the same and applies hcg_adam_step_dev's update with the scaled gradient: one launch. */
-int hcg_sse_finalize(float* flat, int64_t n, float* loss, hcg_stream_t stream);
+ * gradients in place by 1 / (count * L), L = sqrt(SSE / count), and stores loss[0] = L, loss[1] = SSE / count, then
+ * applies hcg_adam_step_dev's update with the scaled gradient: one launch. */
 int hcg_adam_step_dev_sse(float* param, float* flat, float* exp_avg, float* exp_avg_sq, int64_t n,
                           const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_dev, float* loss,
                           hcg_stream_t stream);
+
+/* Every rule's capturable update (HCG_UPDATE_*) with hcg_adam_step_dev's step-word contract (step_dev = [count, stamp,
+ * ticket, pad]: count advanced by one, stamp untouched, ticket zero between launches), plain or in the SSE form.
+ *   loss == NULL: `grad` = [n] gradients;
+ *   loss != NULL: `grad` = [n summed SSE/2-gradients | SSE | count], scaled in place by 1 / (count * L), L = sqrt(SSE /
+ *                 count); loss[0] = L, loss[1] = SSE / count;
+ *   param == NULL: no update -- only the SSE form's scale and loss (needs loss; the other pointers and step_dev unused).
+ * State per rule as in hcg_tail_args (Adam: exp_avg, exp_avg_sq; RMSprop: exp_avg_sq = square_avg, beta2 = alpha;
+ * SGD: none).  HOST struct; zero it first. */
+typedef struct hcg_update_args {
+  float* param;                /* NULL = no update */
+  float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;
+  const float* lr_dev;
+  int32_t* step_dev;
+  float* loss;                 /* NULL = plain form */
+  float beta1, beta2, eps;
+  int32_t update_rule;         /* HCG_UPDATE_* */
+} hcg_update_args;
+int hcg_update_dev(const hcg_update_args* args_host, hcg_stream_t stream);
 
 /* ---- data parallel: one-shot gradient exchange over xGMI, fused between the slab reduction and the update ------------
  * Every rank owns an inbox (hcg_xchg_inbox_bytes: 2 x world x (n + 2) eight-byte {value, step} granules) in fine-grained

@@ -1,20 +1,25 @@
 #!/usr/bin/env python3
 """Dev tool: one training epoch as the reference runs it (scripts_experiments/train_GNN.py:73-80: 535 training graphs,
 batch_size 40, shuffle; utils/utils_model.py:55-70) -- hcatgnet_amd.train.train_network over a DeviceLoader vs the CPU
-oracle's loop on the same graphs.  Prints ms per epoch and graphs/s."""
-import sys, os, time
+oracle's loop on the same graphs.  Prints ms per epoch and graphs/s.  `--optimizer Adam | SGD | rmsprop`: the reference's
+`--optimizer` (model/networks.py:36-44); the CPU oracle's loop is Adam's and runs only for Adam."""
+import argparse, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import hcatgnet_amd as H
 from hcatgnet_amd import synth
 from hcatgnet_amd.train import train_network, eval_network
 from oracle import gcn_oracle
+ap = argparse.ArgumentParser()
+ap.add_argument("--optimizer", default="Adam", choices=["Adam", "SGD", "rmsprop"])
+OPT = ap.parse_args().optimizer
 G, BS = 535, 40
 sb = synth.make_config("REAL", num_graphs=G)
 graphs = sb.as_graph_list()
 store = H.DeviceGraphStore(graphs, device="cuda")
 loader = H.DeviceLoader(store, batch_size=BS, shuffle=True, seed=0)
-model = H.make_network("GCN", H.default_options(), 25).cuda()
+model = H.make_network("GCN", H.default_options(optimizer=OPT), 25).cuda()
+print(f"optimizer {OPT}: {type(model.optimizer).__name__}")
 import gc
 for _ in range(3):
     train_network(model, loader, "cuda")
@@ -32,7 +37,7 @@ print(f"MI355X  train_network: {dt * 1e3:8.2f} ms/epoch ({len(loader)} batches o
 from hcatgnet_amd import train as _train
 _train.EPOCH_WINDOW = False
 loader_b = H.DeviceLoader(store, batch_size=BS, shuffle=True, seed=0)
-model_b = H.make_network("GCN", H.default_options(), 25).cuda()      # (its own model: the window's 14 trainers stay out of the way)
+model_b = H.make_network("GCN", H.default_options(optimizer=OPT), 25).cuda()      # (its own model: the window's 14 trainers stay out of the way)
 for _ in range(3):
     train_network(model_b, loader_b, "cuda")
 torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -54,6 +59,8 @@ for _ in range(EP):
     eval_network(model, vloader, "cuda")
 torch.cuda.synchronize(); dtv = (time.perf_counter() - t0) / EP
 print(f"MI355X  eval_network : {dtv * 1e3:8.2f} ms/epoch (fixed loader: batches collated once, one graph launch per call)")
+if OPT != "Adam":
+    sys.exit(0)
 # CPU: the oracle's loop with the host collate (what the reference does through PyG on the CPU)
 torch.set_num_threads(min(16, os.cpu_count() or 1))
 params = {k: v.detach().cpu().clone() for k, v in H.make_network("GCN", H.default_options(), 25).state_dict().items()}
