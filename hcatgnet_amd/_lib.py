@@ -17,10 +17,11 @@ HCG_PLAN_GENERAL, HCG_PLAN_BLOCKED, HCG_PLAN_PTRS_ONLY, HCG_PLAN_KEEP_STATUS = 0
 HCG_ACT_NONE, HCG_ACT_LEAKY = 0, 1
 HCG_LOSS_MSE, HCG_LOSS_RMSE, HCG_LOSS_SSE = 0, 1, 2      # loss modes of hcg_step_tail / hcg_loss_finalize / hcg_loss_fwd_bwd
 HCG_HEAD_FORWARD_ONLY = 1
-HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2 = 0, 1, 2, 3        # hcg_general_workspace_bytes kinds
+HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2, HCG_WS_HEAD_DEEP = 0, 1, 2, 3, 4   # hcg_general_workspace_bytes kinds
 HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                          # hcg_fused_aux_bytes kinds
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
-HCG_STRUCT_UPDATE_ARGS = 5
+HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS = 5, 6
+HCG_HEAD_MAX_LAYERS = 4
 HCG_UPDATE_ADAM, HCG_UPDATE_SGD, HCG_UPDATE_RMSPROP = 0, 1, 2      # update rules of hcg_step_tail / hcg_update_dev
 HCG_REDUCE_MAX_JOBS, HCG_REDUCE_MAX_SEGS = 8, 4
 HCG_XCHG_MEAN, HCG_XCHG_SSE, HCG_XCHG_ERR_TIMEOUT, HCG_XCHG_MAX_WORLD = 0, 1, 1, 8
@@ -68,6 +69,13 @@ class FusedFwdArgs(ctypes.Structure):
                 ("demb", P), ("head_workspace", P), ("head_workspace_bytes", SZ), ("step_counter", P)]
 
 
+class HeadArgs(ctypes.Structure):
+    """hcg_head_args: the one-launch readout head of depth 1, 3 or 4 (hcg_head_deep_fwd_bwd)."""
+    _fields_ = [("emb", P), ("y", P), ("W", P * HCG_HEAD_MAX_LAYERS), ("b", P * HCG_HEAD_MAX_LAYERS), ("out", P), ("demb", P),
+                ("workspace", P), ("workspace_bytes", SZ), ("step_counter", P), ("grad", P * HCG_HEAD_MAX_LAYERS), ("B", I64), ("D", I64), ("C", I64), ("R", I32),
+                ("flags", I32), ("slope", F32), ("reserved", I32)]
+
+
 class CollateSlot(ctypes.Structure):
     """hcg_collate_slot: one batch of a collate launch."""
     _fields_ = [("ids", P), ("graph_ptr", P), ("edge_ptr", P), ("x_out", P), ("edge_index_out", P), ("batch_out", P),
@@ -112,8 +120,7 @@ SIGNATURES = {
     "hcg_tall_layer_bwd": (INT, [P, P, P, P, P, P, P, P, P, P, P, I64, P, P, I64, I64, I64, I64, I64, I64, F32, INT, P, P, P, SZ, P]),
     "hcg_tall_reduce_jobs": (INT, [P, SZ, I64, I64, I64, I64, INT, P, P, P]),
     "hcg_fused_reduce_job": (INT, [P, SZ, I64, I64, I64, I64, INT, P, P, P]),
-    "hcg_readout2_bwd_partial": (INT, [P, P, P, P, P, I64, I64, I64, F32, P, P, SZ, P]),
-    "hcg_readout2_reduce_job": (INT, [P, SZ, I64, I64, P, P, P, P, P]),
+    "hcg_readout2_bwd_partial": (INT, [P, P, P, P, P, I64, I64, I64, F32, P, P, SZ, P, P, P, P, P, P]),
     "hcg_reduce_job_append": (INT, [P, P]),
     "hcg_step_tail": (INT, [P, P]),
     "hcg_loss_finalize": (INT, [P, F32, INT, P, P, P]),
@@ -127,6 +134,7 @@ SIGNATURES = {
     "hcg_head_workspace_bytes": (SZ, [I64, I64]),
     "hcg_head_fwd_bwd": (INT, [P, P, P, P, P, P, I64, I64, I64, F32, INT, P, P, P, P, SZ, P, P]),
     "hcg_head_reduce_job": (INT, [P, SZ, I64, I64, I64, P, P, P, P, P]),
+    "hcg_head_deep_fwd_bwd": (INT, [P, P, P]),
     "hcg_adam_step_dev_sse": (INT, [P, P, P, P, I64, P, F32, F32, F32, P, P, P]),
     "hcg_adam_step_dev": (INT, [P, P, P, P, I64, P, F32, F32, F32, P, P]),
     "hcg_update_dev": (INT, [P, P]),

@@ -60,8 +60,8 @@ __global__ __launch_bounds__(hcg_head16::NT, 1) void k_head16(const float* __res
   h16::end<RC, BACKWARD>(L, S, C, slabs + (size_t)blockIdx.x * h16::SLAB, slabs + (size_t)gridDim.x * h16::SLAB + blockIdx.x);
 }
 
-int head_grid(int64_t B, int64_t D = 128) {
-  const int rt = D == 64 ? hcg_head16::RT : RT;
+// min(tiles of rt graphs, CUs)
+int head_grid_rt(int64_t B, int rt) {
   static int cus = 0;       // queried once per process (also keeps the query out of a stream capture)
   if (cus == 0) {
     int dev = 0, v = 0;
@@ -73,6 +73,7 @@ int head_grid(int64_t B, int64_t D = 128) {
   if (grid > cus) grid = cus;
   return grid < 1 ? 1 : grid;
 }
+int head_grid(int64_t B, int64_t D = 128) { return head_grid_rt(B, D == 64 ? hcg_head16::RT : RT); }
 size_t head_slab(int64_t D) { return D == 128 ? (size_t)HC<128>::SLAB : (size_t)HC<64>::SLAB; }
 
 }  // namespace
@@ -128,5 +129,218 @@ extern "C" int hcg_head_reduce_job(const void* workspace, size_t workspace_bytes
   if (workspace_bytes < hcg_head_workspace_bytes(B, D)) return HCG_ERR_WORKSPACE;
   if (D == 128) head_fill_job<128>((const float*)workspace, head_grid(B, D), (int)C, dW0, db0, dW1, db1, job);
   else head_fill_job<64>((const float*)workspace, head_grid(B, D), (int)C, dW0, db0, dW1, db1, job);
+  return HCG_OK;
+}
+
+// ======================================================================================================================
+// Readout heads of depth R = 1, 3, 4 in ONE launch (reference model/gcn.py:36-45: widths 2D -> D -> D/2 -> ..., LeakyReLU
+// behind every hidden layer, a last Linear(w, C) without one), with k_head's contract: forward, squared error, backward on
+// the unscaled error, one gradient slab + SSE partial per workgroup, the step counter.  One workgroup per 16-graph tile
+// (grid <= CUs, a workgroup loops over tiles beyond that); the tile's activations and errors stay in LDS, the weights come
+// from L2.  Plain f32 FMA: a few MFLOP per step, and every layer runs the same three loops.  Each gradient element has one
+// owning thread that adds its tile's graphs in order and its tiles in order: no atomics, bitwise repeatable.
+// ======================================================================================================================
+namespace {
+namespace deep {
+
+constexpr int TG = 16;     // graphs per tile
+constexpr int NT = 256;    // threads per workgroup
+
+__host__ __device__ constexpr int kin(int D, int i) { return (2 * D) >> i; }                 // input width of layer i
+// slab offset of layer i's [dW | db]: the hidden layers before it (out = in / 2)
+__host__ __device__ constexpr int seg_off(int D, int i) { return i == 0 ? 0 : seg_off(D, i - 1) + (kin(D, i - 1) / 2) * (kin(D, i - 1) + 1); }
+// LDS offset (per graph row) of layer i's input activations
+__host__ __device__ constexpr int act_off(int D, int i) { return i == 0 ? 0 : act_off(D, i - 1) + kin(D, i - 1); }
+inline int slab_floats(int D, int R, int C) {
+  return (int)hcg_align_up((size_t)seg_off(D, R - 1) + (size_t)C * (kin(D, R - 1) + 1), 8);
+}
+
+template <int D, int R>
+struct Lds {
+  float act[TG * act_off(D, R)];     // every layer's input rows, layer after layer (layer 0's = the embedding)
+  float d[2][TG * D];                // errors of a layer's outputs / of its input (ping-pong)
+  float red[NT];
+};
+
+// layer I: x [n, K] -> LeakyReLU(x W^T + b) [n, K/2] into the next layer's input rows; the last layer: out = x W^T + b
+// [n, C] to global memory, the error out - y into d[0], the squared error into this thread's partial
+template <int D, int R, int I>
+__device__ __forceinline__ void fwd_layer(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float& sse) {
+  constexpr int K = kin(D, I);
+  constexpr bool LAST = I == R - 1;
+  const int C = (int)a.C, O = LAST ? C : K / 2;
+  const float* __restrict__ W = a.W[I];
+  const float* __restrict__ b = a.b[I];
+  const float4* x4 = reinterpret_cast<const float4*>(L.act + TG * act_off(D, I));
+  for (int idx = threadIdx.x; idx < n * O; idx += NT) {
+    const int g = idx / O, o = idx - g * O;
+    const float4* w4 = reinterpret_cast<const float4*>(W + (size_t)o * K);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < K / 4; ++k) {
+      const float4 w = w4[k], v = x4[g * (K / 4) + k];
+      s0 = fmaf(v.x, w.x, s0); s1 = fmaf(v.y, w.y, s1); s2 = fmaf(v.z, w.z, s2); s3 = fmaf(v.w, w.w, s3);
+    }
+    const float v = ((s0 + s1) + (s2 + s3)) + b[o];
+    if constexpr (!LAST) {
+      L.act[TG * act_off(D, I + 1) + g * O + o] = hcg_leaky(v, a.slope);
+    } else {
+      const size_t row = (size_t)(g0 + g) * C + o;
+      a.out[row] = v;
+      const float e = v - a.y[row];
+      sse = fmaf(e, e, sse);
+      L.d[0][g * O + o] = e;
+    }
+  }
+}
+
+// layer I's backward from the errors of its outputs (d[P], [n, O]): dW += d^T x, db += sum d (this workgroup's slab; the
+// first tile writes, later ones add), dx = d W -- times the LeakyReLU derivative of layer I - 1 into d[P ^ 1], or, for the
+// first layer, demb to global memory
+template <int D, int R, int I, int P>
+__device__ __forceinline__ void bwd_layer(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float* __restrict__ slab,
+                                          bool first) {
+  constexpr int K = kin(D, I), K4 = K / 4;
+  constexpr bool LAST = I == R - 1;
+  const int O = LAST ? (int)a.C : K / 2;
+  const float* dl = L.d[P];
+  const float4* x4 = reinterpret_cast<const float4*>(L.act + TG * act_off(D, I));
+  float* __restrict__ dWb = slab + seg_off(D, I);
+  for (int idx = threadIdx.x; idx < O * K4; idx += NT) {
+    const int o = idx / K4, k4 = idx - o * K4;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int g = 0; g < n; ++g) {
+      const float e = dl[g * O + o];
+      const float4 v = x4[g * K4 + k4];
+      s.x = fmaf(e, v.x, s.x); s.y = fmaf(e, v.y, s.y); s.z = fmaf(e, v.z, s.z); s.w = fmaf(e, v.w, s.w);
+    }
+    float4* dst = reinterpret_cast<float4*>(dWb) + idx;
+    if (!first) {
+      const float4 p = *dst;
+      s = make_float4(p.x + s.x, p.y + s.y, p.z + s.z, p.w + s.w);
+    }
+    *dst = s;
+  }
+  for (int o = threadIdx.x; o < O; o += NT) {
+    float s = 0.f;
+    for (int g = 0; g < n; ++g) s += dl[g * O + o];
+    float* dst = dWb + O * K + o;
+    *dst = first ? s : *dst + s;
+  }
+  const float4* W4 = reinterpret_cast<const float4*>(a.W[I]);
+  for (int idx = threadIdx.x; idx < n * K4; idx += NT) {
+    const int g = idx / K4, k4 = idx - g * K4;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int o = 0; o < O; ++o) {
+      const float e = dl[g * O + o];
+      const float4 w = W4[o * K4 + k4];
+      s.x = fmaf(e, w.x, s.x); s.y = fmaf(e, w.y, s.y); s.z = fmaf(e, w.z, s.z); s.w = fmaf(e, w.w, s.w);
+    }
+    if constexpr (I == 0) {
+      reinterpret_cast<float4*>(a.demb + (size_t)(g0 + g) * (2 * D))[k4] = s;
+    } else {
+      const float4 v = x4[g * K4 + k4];
+      const float sl = a.slope;
+      s = make_float4(s.x * hcg_leaky_grad(v.x, sl), s.y * hcg_leaky_grad(v.y, sl), s.z * hcg_leaky_grad(v.z, sl),
+                      s.w * hcg_leaky_grad(v.w, sl));
+      reinterpret_cast<float4*>(L.d[P ^ 1])[g * K4 + k4] = s;
+    }
+  }
+}
+
+template <int D, int R, int I = 0>
+__device__ __forceinline__ void forward(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float& sse) {
+  fwd_layer<D, R, I>(L, a, n, g0, sse);
+  __syncthreads();
+  if constexpr (I + 1 < R) forward<D, R, I + 1>(L, a, n, g0, sse);
+}
+
+template <int D, int R, int I = R - 1>
+__device__ __forceinline__ void backward(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float* slab, bool first) {
+  bwd_layer<D, R, I, (R - 1 - I) & 1>(L, a, n, g0, slab, first);
+  __syncthreads();
+  if constexpr (I > 0) backward<D, R, I - 1>(L, a, n, g0, slab, first);
+}
+
+template <int D, int R, bool BACKWARD>
+__global__ __launch_bounds__(NT, 1) void k_head_deep(const hcg_head_args a, int slab) {
+  __shared__ Lds<D, R> L;
+  if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 0) { a.step_counter[0] += 1; a.step_counter[1] += 1; }
+  float* slabs = static_cast<float*>(a.workspace);
+  float* own = slabs + (size_t)blockIdx.x * slab;
+  const int B = (int)a.B, tiles = (B + TG - 1) / TG;
+  float sse = 0.f;
+  bool first = true;
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int g0 = t * TG, n = B - g0 < TG ? B - g0 : TG;
+    const float4* e4 = reinterpret_cast<const float4*>(a.emb + (size_t)g0 * (2 * D));
+    for (int idx = threadIdx.x; idx < n * (2 * D / 4); idx += NT) reinterpret_cast<float4*>(L.act)[idx] = e4[idx];
+    __syncthreads();
+    forward<D, R>(L, a, n, g0, sse);
+    if constexpr (BACKWARD) backward<D, R>(L, a, n, g0, own, first);
+    first = false;
+  }
+  // this workgroup's SSE partial: a fixed tree over the threads' fixed-order partials
+  L.red[threadIdx.x] = sse;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) L.red[threadIdx.x] += L.red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) slabs[(size_t)gridDim.x * slab + blockIdx.x] = L.red[0];
+}
+
+}  // namespace deep
+}  // namespace
+
+static bool deep_supported(int64_t D, int64_t C, int64_t R) {
+  return (D == 64 || D == 128) && C >= 1 && C <= RCMAX && (R == 1 || R == 3 || R == 4);
+}
+
+// workspace: [grid][slab] gradient slabs | [grid] SSE partials (hcg_general_workspace_bytes, HCG_WS_HEAD_DEEP)
+size_t hcg_head_deep_workspace_bytes_impl(int64_t B, int64_t D, int64_t C, int64_t R) {
+  if (B <= 0 || !deep_supported(D, C, R)) return 0;
+  return hcg_align_up((size_t)head_grid_rt(B, deep::TG) * (deep::slab_floats((int)D, (int)R, (int)C) + 1) * sizeof(float), 256) + 256;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int hcg_head_deep_fwd_bwd(const hcg_head_args* args, hcg_reduce_job* job, hcg_stream_t stream) {
+  if (!args) return HCG_ERR_INVALID_ARG;
+  const hcg_head_args& a = *args;
+  if (!deep_supported(a.D, a.C, a.R)) return HCG_ERR_UNSUPPORTED;
+  if (a.flags & ~HCG_HEAD_FORWARD_ONLY) return HCG_ERR_INVALID_ARG;
+  const bool bwd = !(a.flags & HCG_HEAD_FORWARD_ONLY);
+  if (a.B <= 0 || a.B * a.D * 2 > INT32_MAX || !a.emb || !a.y || !a.out || !a.workspace || !aligned16(a.emb)) return HCG_ERR_INVALID_ARG;
+  if (bwd && (!a.demb || !aligned16(a.demb))) return HCG_ERR_INVALID_ARG;
+  for (int i = 0; i < a.R; ++i)
+    if (!a.W[i] || !a.b[i] || !aligned16(a.W[i]) || (a.grad[0] && !a.grad[i])) return HCG_ERR_INVALID_ARG;
+  if (a.workspace_bytes < hcg_head_deep_workspace_bytes_impl(a.B, a.D, a.C, a.R)) return HCG_ERR_WORKSPACE;
+  const int grid = head_grid_rt(a.B, deep::TG), slab = deep::slab_floats((int)a.D, (int)a.R, (int)a.C);
+  if (job) {      // (the slabs this launch leaves, one segment per layer)
+    job->slabs = (const float*)a.workspace;
+    job->sse_part = (const float*)a.workspace + (size_t)grid * slab;
+    job->nslabs = grid;
+    job->slab_floats = slab;
+    job->nseg = bwd && a.grad[0] ? a.R : 0;
+    job->reserved = 0;
+    for (int g = 0; g < HCG_REDUCE_MAX_SEGS; ++g) job->seg[g] = hcg_reduce_seg{0, 0, 1, 1, nullptr};
+    for (int i = 0; i < job->nseg; ++i) {
+      const int K = deep::kin((int)a.D, i), n = (i == a.R - 1 ? (int)a.C : K / 2) * (K + 1);
+      job->seg[i] = hcg_reduce_seg{deep::seg_off((int)a.D, i), n, n, n, a.grad[i]};
+    }
+  }
+#define LAUNCH_DEEP(D_, R_)                                                                                             \
+  do {                                                                                                                  \
+    if (bwd) hipLaunchKernelGGL((deep::k_head_deep<D_, R_, true>), dim3(grid), dim3(deep::NT), 0, (hipStream_t)stream, a, slab);  \
+    else hipLaunchKernelGGL((deep::k_head_deep<D_, R_, false>), dim3(grid), dim3(deep::NT), 0, (hipStream_t)stream, a, slab);     \
+  } while (0)
+  if (a.D == 64) {
+    if (a.R == 1) LAUNCH_DEEP(64, 1); else if (a.R == 3) LAUNCH_DEEP(64, 3); else LAUNCH_DEEP(64, 4);
+  } else {
+    if (a.R == 1) LAUNCH_DEEP(128, 1); else if (a.R == 3) LAUNCH_DEEP(128, 3); else LAUNCH_DEEP(128, 4);
+  }
+#undef LAUNCH_DEEP
+  HCG_CHECK_LAUNCH();
   return HCG_OK;
 }

@@ -205,12 +205,14 @@ extern "C" int hcg_gcn_layer_fwd(const float* x, const float* W, const float* b,
 // workspace sizes of the any-shape entry points, one query (a, b, c as the kind names them)
 size_t hcg_plan_workspace_bytes_impl(int64_t N, int64_t E, int64_t B, int mode);   // plan.hip
 size_t hcg_readout2_workspace_bytes_impl(int64_t B);                               // readout.hip
+size_t hcg_head_deep_workspace_bytes_impl(int64_t B, int64_t D, int64_t C, int64_t R);   // head.hip
 extern "C" size_t hcg_general_workspace_bytes(int kind, int64_t a, int64_t b, int64_t c, int mode) {
   switch (kind) {
     case HCG_WS_PLAN: return hcg_plan_workspace_bytes_impl(a, b, c, mode);
     case HCG_WS_LINEAR: return linear_workspace_bytes(a, b, c);           // M, D_in, D_out
     case HCG_WS_GCN_LAYER_BWD: return linear_workspace_bytes(a, b, c);    // N, F, D: dW = dH^T X split-K + the bias column sum
     case HCG_WS_READOUT2: return hcg_readout2_workspace_bytes_impl(a);    // B
+    case HCG_WS_HEAD_DEEP: return hcg_head_deep_workspace_bytes_impl(a, b, c, mode);   // B, D, C, R
     default: return 0;
   }
 }

@@ -379,9 +379,14 @@ def mid_supported(plan: Optional[BatchPlan], F: int, D: int, max_nodes: Optional
 def tall_supported(plan: BatchPlan, F: int, D: int, any_rows: bool = False) -> bool:
     """True when the kernels of csrc/tall.hip apply to this plan / layer shape (D = 128; D = 64 over graphs > 64 nodes in
     batches of at least TALL_MIN_NODES_D64 rows -- `any_rows`: of any row count)."""
-    if not _per_graph_plan(plan) or (D == 64 and plan.N < TALL_MIN_NODES_D64 and not any_rows):
+    return _per_graph_plan(plan) and tall_shape_supported(plan.N, F, D, plan.max_nodes, plan.max_edges, any_rows)
+
+
+def tall_shape_supported(N: int, F: int, D: int, max_nodes: int, max_edges: int, any_rows: bool = False) -> bool:
+    """`tall_supported` from a batch's row count and collate metadata alone (no plan checks)."""
+    if D == 64 and N < TALL_MIN_NODES_D64 and not any_rows:
         return False
-    return bool(_lib.load().hcg_tall_supported(F, D, plan.max_nodes, plan.max_edges))
+    return bool(_lib.load().hcg_tall_supported(F, D, max_nodes, max_edges))
 
 
 def conv_route(plan: Optional[BatchPlan], F: int, D: int, family: str = "auto", *, max_nodes=None, max_edges=None):
@@ -481,12 +486,11 @@ class _Readout2Fn(torch.autograd.Function):
         db1 = torch.empty(C, dtype=torch.float32, device=dev)
         wsb = lib.hcg_general_workspace_bytes(_lib.HCG_WS_READOUT2, B, 0, 0, 0)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        rc = lib.hcg_readout2_bwd_partial(_lib.ptr(dout), _lib.ptr(emb), _lib.ptr(z), _lib.ptr(W0), _lib.ptr(W1), B, D, C, ctx.slope,
-                                          _lib.ptr(demb), _lib.ptr(ws), wsb, _lib.stream_ptr())
-        _lib.check(rc, "hcg_readout2_bwd_partial")
         job = _lib.ReduceJob()
-        _lib.check(lib.hcg_readout2_reduce_job(_lib.ptr(ws), wsb, B, C, _lib.ptr(dW0), _lib.ptr(db0), _lib.ptr(dW1), _lib.ptr(db1),
-                                               ctypes.addressof(job)), "hcg_readout2_reduce_job")
+        rc = lib.hcg_readout2_bwd_partial(_lib.ptr(dout), _lib.ptr(emb), _lib.ptr(z), _lib.ptr(W0), _lib.ptr(W1), B, D, C, ctx.slope,
+                                          _lib.ptr(demb), _lib.ptr(ws), wsb, _lib.ptr(dW0), _lib.ptr(db0), _lib.ptr(dW1),
+                                          _lib.ptr(db1), ctypes.addressof(job), _lib.stream_ptr())
+        _lib.check(rc, "hcg_readout2_bwd_partial")
         _lib.reduce_jobs(ctypes.addressof(job), 1)
         return demb, dW0, db0, dW1, db1, None
 
@@ -611,10 +615,9 @@ class _FusedModelFn(torch.autograd.Function):
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         keep.append(ws)
         rc = lib.hcg_readout2_bwd_partial(_lib.ptr(dy), _lib.ptr(emb), _lib.ptr(z), _lib.ptr(R0w), _lib.ptr(R1w), B, D, C,
-                                          slope, _lib.ptr(demb), _lib.ptr(ws), wsb, stream)
+                                          slope, _lib.ptr(demb), _lib.ptr(ws), wsb, _lib.ptr(dR0w), _lib.ptr(dR0b), _lib.ptr(dR1w),
+                                          _lib.ptr(dR1b), jobs.slot(), stream)
         _lib.check(rc, "hcg_readout2_bwd_partial")
-        _lib.check(lib.hcg_readout2_reduce_job(_lib.ptr(ws), wsb, B, C, _lib.ptr(dR0w), _lib.ptr(dR0b), _lib.ptr(dR1w),
-                                               _lib.ptr(dR1b), jobs.slot()), "hcg_readout2_reduce_job")
         jobs.add(1)
         if demb_ext is not None:          # the caller also used graph_emb downstream
             demb = demb + _f32c(demb_ext)

@@ -32,9 +32,14 @@ import torch.distributed
 from . import _lib
 from . import functional as HF
 
+def _head_deep_supported(D: int, C: int, R: int) -> bool:
+    """A readout of depth R at width D with C outputs has the one-launch head of csrc/head.hip (k_head_deep)."""
+    return _lib.load().hcg_general_workspace_bytes(_lib.HCG_WS_HEAD_DEEP, 1, D, C, R) > 0
+
+
 class _Ctx:
     """Everything one step needs, resolved once: shapes, weights, buffers, the kernel family of every layer."""
-    __slots__ = ("batch", "plan", "x", "y2", "convs", "l0", "l1", "N", "F", "B", "D", "C", "n_conv", "dev", "W", "bs",
+    __slots__ = ("batch", "plan", "x", "y2", "convs", "lins", "N", "F", "B", "D", "C", "n_conv", "dev", "W", "bs",
                  "routes", "geo", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
                  "loss_mode", "sse_split", "poolbits", "xagg")
 
@@ -124,17 +129,26 @@ class FusedTrainStep:
 
     def reason(self, batch=None) -> Optional[str]:
         """`unsupported_reason(self.model, batch)` with the cached parameter list."""
-        return self.unsupported_reason(self.model, batch, self._trainable())
+        return self.unsupported_reason(self.model, batch, self._trainable(), self)
 
     # ------------------------------------------------------------------ support check (host only)
     @staticmethod
-    def unsupported_reason(model, batch=None, _params=None) -> Optional[str]:
-        if getattr(model, "readout_layers", None) != 2:
-            return "readout depth other than 2"
+    def unsupported_reason(model, batch=None, _params=None, _step=None) -> Optional[str]:
+        """None when `model` takes the fused step on `batch`, else why not.  Without a batch the answer covers the model
+        alone, and only for readout depth 2: other depths (1, 3, 4 at widths 64 / 128 with up to 8 classes) are accepted
+        per batch, which is how the step and every epoch loop ask."""
+        lib = _lib.load()
+        R = getattr(model, "readout_layers", None)
+        if R != 2 and not (R is not None and _head_deep_supported(model.embedding_dim, model._n_classes, R)):
+            return ("readout depth other than 2, or other than 1 / 3 / 4 at widths 64 / 128 with up to 8 classes "
+                    f"(readout_layers = {R})")
         if not bool(getattr(model, "use_fused", True)):
             return "fused kernels disabled on the model"
-        if model.n_convolutions + 1 > 4:
-            return "more than 3 conv layers"
+        # every gradient slab of the step is reduced by ONE launch of at most HCG_REDUCE_MAX_JOBS jobs (hcg_step_tail)
+        head_jobs = 1 if (R != 2 or lib.hcg_head_supported(model.embedding_dim, model._n_classes)) else 0
+        if FusedTrainStep._conv_jobs(model) + head_jobs > _lib.HCG_REDUCE_MAX_JOBS:
+            return (f"{model.n_convolutions} conv layers of width {model.embedding_dim}: their gradient reductions and the "
+                    f"head's exceed the step tail's {_lib.HCG_REDUCE_MAX_JOBS} jobs")
         # (heads the one-launch kernel does not cover -- widths other than 64 / 128 -- run as five launches of the any-shape
         #  kernels inside the same no-autograd step)
         if type(model.loss).__name__ != "MSELoss":
@@ -152,7 +166,45 @@ class FusedTrainStep:
             for c in convs:
                 if HF.conv_route(None, c.in_channels, c.out_channels, max_nodes=mx, max_edges=me)[0] is None:
                     return "graph / layer shape outside the fused kernels (small-graph tiles and one-graph-per-workgroup)"
+            jobs = FusedTrainStep._conv_jobs(model, batch, _step)
+            if jobs + head_jobs > _lib.HCG_REDUCE_MAX_JOBS:
+                return (f"{model.n_convolutions} conv layers on this batch's kernel forms need {jobs} gradient reductions, "
+                        f"with the head's over the step tail's {_lib.HCG_REDUCE_MAX_JOBS} jobs")
+        elif R != 2:
+            return f"readout depth {R} is accepted per batch: ask with the batch (without one, only depth 2 is vouched for)"
         return None
+
+    @staticmethod
+    def _conv_jobs(model, batch=None, step=None) -> int:
+        """Reduction jobs the conv layers' backward leaves for the step tail, from the routes `_prepare` takes and the forms
+        `_backward_layers` picks (the families' `reduce_jobs`): 1 per 64-wide layer on the small-graph tiles or one graph
+        per workgroup; 2 per layer on the wide-layer route (dW, db), per 128-wide one-graph-per-workgroup layer (one per
+        64-column half) and for a 64-wide first layer in its dense training form.  Without a batch: the fewest any batch
+        could need (1 per 64-wide layer, 2 per wider one)."""
+        convs = [model.conv1] + list(model.conv_layers)
+        if batch is None:
+            return sum(1 if c.out_channels == 64 else 2 for c in convs)
+        sw = FusedTrainStep if step is None else step
+        mx, me, N = batch.max_nodes, getattr(batch, "max_edges", None), batch.x.shape[0]
+        fams = []
+        for c in convs:
+            fam = HF.conv_route(None, c.in_channels, c.out_channels, max_nodes=mx, max_edges=me)[0]
+            if (fam is HF.MID and getattr(c, "family", "auto") != "mid"
+                    and HF.tall_shape_supported(N, c.in_channels, c.out_channels, mx, me)):
+                fam = HF.TALL
+            fams.append(fam)
+        jobs = 0
+        for l, (c, fam) in enumerate(zip(convs, fams)):
+            if fam is HF.TILES:
+                jobs += 1
+            elif fam is HF.TALL or c.out_channels != 64:
+                jobs += 2
+            elif (l == 0 and len(convs) >= 2 and c.in_channels <= 64 and sw.XAGG and sw.XAGG_MID and fams[1] is not HF.TILES
+                  and HF.tall_shape_supported(N, c.in_channels, 64, mx, me, any_rows=True)):
+                jobs += 2                                   # (the first layer's dense training form: csrc/tall.hip slabs)
+            else:
+                jobs += 1
+        return jobs
 
     def _side_stream(self, dev):
         st = self._side_streams.get(dev)
@@ -161,12 +213,12 @@ class FusedTrainStep:
         return st
 
     # ------------------------------------------------------------------ buffers
-    def _buffers(self, key, N, B, F, D, C, n_conv, dev):
+    def _buffers(self, key, N, B, F, D, C, n_conv, dev, R=2):
         """Step buffers: allocated for the largest (N, B) seen so far and handed out as views -- the variable-size
         batches of a shuffled epoch then reuse one allocation instead of ~12 `torch.empty` per step."""
         lib = _lib.load()
         cap = self._bufs.get("cap")
-        sig = (F, D, C, n_conv, dev)
+        sig = (F, D, C, n_conv, dev, R)
         if cap is None or cap["sig"] != sig or cap["N"] < N or cap["B"] < B:
             capN = max(N, int(cap["N"] * 1.25) if cap and cap["sig"] == sig else 0)
             capB = max(B, cap["B"] if cap and cap["sig"] == sig else 0)
@@ -174,7 +226,8 @@ class FusedTrainStep:
             # head slabs: the stand-alone head's (<= one per CU) or the forward tail's (one per workgroup of the tile launch:
             # graphs_per_tile 1 bounds it)
             hb = max(lib.hcg_head_workspace_bytes(capB, D if lib.hcg_head_supported(D, C) else 64),
-                     lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_HEAD_WS, capB, 1))
+                     lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_HEAD_WS, capB, 1),
+                     lib.hcg_general_workspace_bytes(_lib.HCG_WS_HEAD_DEEP, capB, D, C, R))
             cap = {"sig": sig, "N": capN, "B": capB,
                    "acts": [torch.empty(capN, D, **f32) for _ in range(n_conv)],
                    "dacts": [torch.empty(capN, D, **f32) for _ in range(n_conv - 1)],
@@ -249,7 +302,8 @@ class FusedTrainStep:
         c.x = x = HF._f32c(x)
         c.plan = plan = model._plan_for(batch, x, batch.edge_index, batch.batch, None)
         c.convs = convs = [model.conv1] + list(model.conv_layers)
-        c.l0, c.l1 = model.readout[0][0], model.readout[1]
+        # readout linears: readout[i] = Sequential(Linear, LeakyReLU) for the hidden layers, the last a bare Linear
+        c.lins = [m[0] if isinstance(m, torch.nn.Sequential) else m for m in model.readout]
         c.N, c.F, c.B, c.D, c.C = x.shape[0], x.shape[1], plan.B, model.embedding_dim, model._n_classes
         c.n_conv, c.dev = len(convs), x.device
         c.y2 = HF._f32c(y).reshape(c.B, -1)
@@ -260,10 +314,11 @@ class FusedTrainStep:
         if (None, 0) in c.routes:
             raise _lib.HcgError("FusedTrainStep: graph / layer shape outside the fused kernels")
         c.geo = HF.geometry(plan)
-        c.bufs = self._buffers((c.N, c.B, c.F, plan.E), c.N, c.B, c.F, c.D, c.C, c.n_conv, c.dev)
+        c.bufs = self._buffers((c.N, c.B, c.F, plan.E), c.N, c.B, c.F, c.D, c.C, c.n_conv, c.dev, len(c.lins))
         c.W = [HF._f32c(cv.lin.weight) for cv in convs]
         c.bs = [HF._f32c(cv.bias) for cv in convs]
-        c.head_fused = bool(lib.hcg_head_supported(c.D, c.C))
+        c.head_fused = bool(lib.hcg_head_supported(c.D, c.C) if len(c.lins) == 2
+                            else _head_deep_supported(c.D, c.C, len(c.lins)))
         c.n_small = self._size_groups(batch, plan, convs, c.D, c.C, c.n_conv)
         c.jobs = HF.JobList()
         c.flat = c.gaddr = c.step_word = None
@@ -325,13 +380,13 @@ class FusedTrainStep:
         """The C3 form: both conv layers on small-graph tiles, pooled layer on chip, one-launch head -> everything up to
         the loss is ONE launch."""
         return (self.HEAD_IN_FORWARD and self.POOLBITS and c.n_small is None and c.n_conv == 2 and c.head_fused
-                and c.routes[0][0] is HF.TILES and c.routes[0] == c.routes[1])
+                and len(c.lins) == 2 and c.routes[0][0] is HF.TILES and c.routes[0] == c.routes[1])
 
     def _forward_with_head(self, c: _Ctx):
         """conv stack + pooling + readout head (forward, squared error, unscaled readout backward): one launch."""
         lib, bufs, gpt = _lib.load(), c.bufs, c.routes[0][1]
         c.poolbits = self._ws(bufs, "poolbits", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, c.B, gpt), c.dev)
-        l0, l1 = c.l0, c.l1
+        l0, l1 = c.lins
         self._tiles_stack(
             c, c.geo, gpt, poolbits=c.poolbits, y=c.y2, head_W0=HF._f32c(l0.weight), head_b0=HF._f32c(l0.bias),
             head_W1=HF._f32c(l1.weight), head_b1=HF._f32c(l1.bias), C=c.C, z=bufs["z"], head_out=bufs["out"], demb=bufs["demb"],
@@ -405,9 +460,11 @@ class FusedTrainStep:
     def _head(self, c: _Ctx):
         """The readout head as a launch of its own (one-launch kernel for D = 64 / 128, C <= 8; five launches of the
         any-shape kernels otherwise) -- reference model/gcn.py:70-71, utils/utils_model.py:64-65."""
+        if len(c.lins) != 2:
+            return self._head_deep(c)
         lib, bufs = _lib.load(), c.bufs
         p, stream, slope = _lib.ptr, _lib.stream_ptr(), HF.LEAKY_SLOPE
-        B, D, C, l0, l1 = c.B, c.D, c.C, c.l0, c.l1
+        B, D, C, (l0, l1) = c.B, c.D, c.C, c.lins
         W0, b0, W1, b1 = HF._f32c(l0.weight), HF._f32c(l0.bias), HF._f32c(l1.weight), HF._f32c(l1.bias)
         emb, z, out = bufs["emb"], bufs["z"], bufs["out"]
         if c.head_fused:
@@ -435,6 +492,28 @@ class FusedTrainStep:
                                       B, D, C, _lib.HCG_ACT_NONE, slope, p(hb["ws1"]), hb["ws1"].numel(), stream), "hcg_linear_bwd")
         _lib.check(lib.hcg_linear_bwd(p(hb["dz"]), p(z), p(emb), p(W0), p(bufs["demb"]), g(l0.weight), g(l0.bias), p(hb["dz_ws0"]),
                                       B, 2 * D, D, _lib.HCG_ACT_LEAKY, slope, p(hb["ws0"]), hb["ws0"].numel(), stream), "hcg_linear_bwd")
+
+    def _head_deep(self, c: _Ctx):
+        """Readout depth 1, 3 or 4: one launch with the contract of `hcg_head_fwd_bwd` (csrc/head.hip: k_head_deep), its
+        slabs ONE reduction job -- each layer's bias gradient sits right behind its weight gradient in the flat buffer."""
+        lib, bufs, R = _lib.load(), c.bufs, len(c.lins)
+        a = _lib.HeadArgs()
+        a.emb, a.y, a.out = bufs["emb"].data_ptr(), c.y2.data_ptr(), bufs["out"].data_ptr()
+        wb = [(HF._f32c(lin.weight), HF._f32c(lin.bias)) for lin in c.lins]     # (held until the launch is enqueued)
+        for i, (W, b) in enumerate(wb):
+            a.W[i], a.b[i] = W.data_ptr(), b.data_ptr()
+        a.demb = None if c.forward_only else bufs["demb"].data_ptr()
+        a.workspace, a.workspace_bytes = bufs["ws_head"].data_ptr(), bufs["ws_head_bytes"]
+        a.step_counter = _lib.ptr(c.step_word)
+        if not c.forward_only:
+            for i, lin in enumerate(c.lins):
+                a.grad[i] = self._g(c, lin.weight)
+                if self._g(c, lin.bias) != a.grad[i] + 4 * lin.weight.numel():      # (parameter order keeps them adjacent)
+                    raise _lib.HcgError("readout bias gradient not directly behind its weight's in the flat buffer")
+        a.B, a.D, a.C, a.R = c.B, c.D, c.C, R
+        a.flags, a.slope = (_lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0), HF.LEAKY_SLOPE
+        _lib.check(lib.hcg_head_deep_fwd_bwd(ctypes.addressof(a), c.jobs.slot(), _lib.stream_ptr()), "hcg_head_deep_fwd_bwd")
+        c.jobs.n += 1
 
     def _backward_layers(self, c: _Ctx):
         """Conv stack backward, last layer first.  A fused-tile layer can hand its dx down already multiplied by the

@@ -78,6 +78,7 @@ const char* hcg_error_string(int code);
 #define HCG_WS_LINEAR 1
 #define HCG_WS_GCN_LAYER_BWD 2
 #define HCG_WS_READOUT2 3
+#define HCG_WS_HEAD_DEEP 4   /* (B, D, C, mode = R): hcg_head_deep_fwd_bwd's workspace; 0 = shape not supported */
 size_t hcg_general_workspace_bytes(int kind, int64_t a, int64_t b, int64_t c, int mode);
 
 /* Outputs (all caller-allocated):
@@ -301,7 +302,7 @@ int hcg_tall_layer_bwd(const float* dout /*nullable*/, const float* demb, const 
 /* ---- fused readout head (a10 + its backward) for the reference's default shape (the autograd path's form):
  *      z = LeakyReLU(emb W0^T + b0) [B,2D]->[B,D];  out = z W1^T + b1 [B,D]->[B,C];  D = 64, C <= 8 (= hcg_head_supported
  *      with D = 64).  forward: one launch (z is kept for the backward).  backward: hcg_readout2_bwd_partial (below: demb
- *      + per-workgroup slabs, workspace HCG_WS_READOUT2) + hcg_readout2_reduce_job + hcg_step_tail. */
+ *      + per-workgroup slabs, workspace HCG_WS_READOUT2, described in job_host) + hcg_step_tail. */
 int hcg_readout2_fwd(const float* emb, const float* W0, const float* b0, const float* W1, const float* b1,
                      int64_t B, int64_t D, int64_t C, float slope, float* z, float* out, hcg_stream_t stream);
 
@@ -329,6 +330,35 @@ int hcg_head_fwd_bwd(const float* emb, const float* y, const float* W0, const fl
                      float* z, float* out, float* demb, void* workspace, size_t workspace_bytes,
                      int32_t* step_counter /*nullable*/, hcg_stream_t stream);
 
+/* ---- regression head of readout depth R = 1, 3, 4 in ONE launch: the contract of hcg_head_fwd_bwd (forward, squared
+ * error, backward on the unscaled error, one gradient slab + SSE partial per workgroup, step_counter, flags) for the
+ * reference's deeper readouts (model/gcn.py:36-45): layer i maps in_i = 2D >> i to in_i / 2 features followed by
+ * LeakyReLU(slope) for i < R - 1, the last layer maps in_{R-1} to C with no activation.  Depth 2 is hcg_head_fwd_bwd.
+ * D = 64 or 128, 1 <= C <= 8: the shapes for which hcg_general_workspace_bytes(HCG_WS_HEAD_DEEP, B, D, C, R) is not 0.
+ * Weights and emb / demb rows must be 16-byte aligned.  Gradient slab per workgroup: [dW_i | db_i] for i = 0 .. R-1, back
+ * to back.  job_host (nullable) receives their description for hcg_step_tail: ONE job of R segments, segment i reduced
+ * into grad[i] = layer i's dW with its db directly behind it (the parameter order of a flat gradient buffer); with
+ * grad[0] == NULL or HCG_HEAD_FORWARD_ONLY the job carries the SSE partials only (hcg_loss_finalize). */
+#define HCG_HEAD_MAX_LAYERS 4
+typedef struct hcg_head_args {
+  const float* emb;                      /* [B, 2D] pooled graph embedding */
+  const float* y;                        /* [B, C] targets */
+  const float* W[HCG_HEAD_MAX_LAYERS];   /* readout layer i: weight [out_i, in_i]; entries >= R unused */
+  const float* b[HCG_HEAD_MAX_LAYERS];   /* readout layer i: bias [out_i] */
+  float* out;                            /* [B, C] */
+  float* demb;                           /* [B, 2D] d (SSE / 2) / d emb, unscaled; unused with HCG_HEAD_FORWARD_ONLY */
+  void* workspace;                       /* HCG_WS_HEAD_DEEP bytes: gradient slabs + SSE partials */
+  size_t workspace_bytes;
+  int32_t* step_counter;                 /* nullable: as hcg_head_fwd_bwd */
+  float* grad[HCG_HEAD_MAX_LAYERS];      /* layer i's gradient destination [dW_i | db_i] (see job_host) */
+  int64_t B, D, C;
+  int32_t R;                             /* readout depth */
+  int32_t flags;                         /* 0 or HCG_HEAD_FORWARD_ONLY */
+  float slope;                           /* LeakyReLU negative slope of the hidden layers */
+  int32_t reserved;
+} hcg_head_args;
+int hcg_head_deep_fwd_bwd(const hcg_head_args* args_host, hcg_reduce_job* job_host, hcg_stream_t stream);
+
 /* loss modes of hcg_step_tail / hcg_loss_finalize / hcg_loss_fwd_bwd */
 #define HCG_LOSS_MSE 0  /* nn.MSELoss                                  : scale 2 / count            */
 #define HCG_LOSS_RMSE 1 /* torch.sqrt(nn.MSELoss) (the reference's step): scale 1 / (count sqrt(MSE)) */
@@ -351,7 +381,7 @@ int hcg_loss_fwd_bwd(const float* a, const float* b, int64_t n, int mode, float*
 
 /* ---- batched slab reduction: ONE launch for all pending gradient reductions of a backward pass.
  * hcg_fused_layer_bwd and hcg_readout2_bwd_partial leave per-workgroup slabs in their workspaces;
- * hcg_fused_reduce_job / hcg_readout2_reduce_job describe them (host-side, no launch), hcg_step_tail
+ * hcg_fused_reduce_job / hcg_readout2_bwd_partial describe them (host-side), hcg_step_tail
  * sums up to HCG_REDUCE_MAX_JOBS of them in a fixed order. */
 #define HCG_REDUCE_MAX_JOBS 8
 #define HCG_REDUCE_MAX_SEGS 4
@@ -374,14 +404,15 @@ typedef struct hcg_reduce_job {
 #define HCG_STRUCT_COLLATE_ARGS 3
 #define HCG_STRUCT_COLLATE_SLOT 4
 #define HCG_STRUCT_UPDATE_ARGS 5
+#define HCG_STRUCT_HEAD_ARGS 6
 size_t hcg_struct_bytes(int which);
 int hcg_fused_reduce_job(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F,
                          int64_t D, int graphs_per_tile, float* dW, float* db, hcg_reduce_job* job_host);
+/* the readout2 backward leaves its slabs and describes them (dW0 [D, 2D], db0 [D], dW1 [C, D], db1 [C]) in job_host */
 int hcg_readout2_bwd_partial(const float* dout, const float* emb, const float* z, const float* W0,
                              const float* W1, int64_t B, int64_t D, int64_t C, float slope, float* demb,
-                             void* workspace, size_t workspace_bytes, hcg_stream_t stream);
-int hcg_readout2_reduce_job(const void* workspace, size_t workspace_bytes, int64_t B, int64_t C,
-                            float* dW0, float* db0, float* dW1, float* db1, hcg_reduce_job* job_host);
+                             void* workspace, size_t workspace_bytes, float* dW0, float* db0, float* dW1, float* db1,
+                             hcg_reduce_job* job_host, hcg_stream_t stream);
 /* one job per 64-column half (half = 0 .. D/64 - 1): rows [64 half, 64 half + 64) of dW [D, F] / db [D] */
 int hcg_mid_reduce_job(const void* workspace, size_t workspace_bytes, int64_t B, int64_t F, int64_t D,
                        int64_t max_nodes, int64_t max_edges, int half, float* dW, float* db, hcg_reduce_job* job_host);

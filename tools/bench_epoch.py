@@ -2,7 +2,9 @@
 """Dev tool: one training epoch as the reference runs it (scripts_experiments/train_GNN.py:73-80: 535 training graphs,
 batch_size 40, shuffle; utils/utils_model.py:55-70) -- hcatgnet_amd.train.train_network over a DeviceLoader vs the CPU
 oracle's loop on the same graphs.  Prints ms per epoch and graphs/s.  `--optimizer Adam | SGD | rmsprop`: the reference's
-`--optimizer` (model/networks.py:36-44); the CPU oracle's loop is Adam's and runs only for Adam."""
+`--optimizer` (model/networks.py:36-44); the CPU oracle's loop is Adam's and runs only for Adam.  `--readout-layers` /
+`--n-convolutions`: the reference's depth options (options/base_options.py:185-197); away from the defaults the per-batch
+autograd loop such models took before the fused step covered them is timed too."""
 import argparse, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,14 +14,19 @@ from hcatgnet_amd.train import train_network, eval_network
 from oracle import gcn_oracle
 ap = argparse.ArgumentParser()
 ap.add_argument("--optimizer", default="Adam", choices=["Adam", "SGD", "rmsprop"])
-OPT = ap.parse_args().optimizer
+ap.add_argument("--readout-layers", type=int, default=2)
+ap.add_argument("--n-convolutions", type=int, default=2)
+args = ap.parse_args()
+OPT = args.optimizer
+DEPTH = dict(readout_layers=args.readout_layers, n_convolutions=args.n_convolutions)
+DEFAULT_DEPTH = DEPTH == dict(readout_layers=2, n_convolutions=2)
 G, BS = 535, 40
 sb = synth.make_config("REAL", num_graphs=G)
 graphs = sb.as_graph_list()
 store = H.DeviceGraphStore(graphs, device="cuda")
 loader = H.DeviceLoader(store, batch_size=BS, shuffle=True, seed=0)
-model = H.make_network("GCN", H.default_options(optimizer=OPT), 25).cuda()
-print(f"optimizer {OPT}: {type(model.optimizer).__name__}")
+model = H.make_network("GCN", H.default_options(optimizer=OPT, **DEPTH), 25).cuda()
+print(f"optimizer {OPT}: {type(model.optimizer).__name__}" + ("" if DEFAULT_DEPTH else f", {DEPTH}"))
 import gc
 for _ in range(3):
     train_network(model, loader, "cuda")
@@ -37,7 +44,7 @@ print(f"MI355X  train_network: {dt * 1e3:8.2f} ms/epoch ({len(loader)} batches o
 from hcatgnet_amd import train as _train
 _train.EPOCH_WINDOW = False
 loader_b = H.DeviceLoader(store, batch_size=BS, shuffle=True, seed=0)
-model_b = H.make_network("GCN", H.default_options(optimizer=OPT), 25).cuda()      # (its own model: the window's 14 trainers stay out of the way)
+model_b = H.make_network("GCN", H.default_options(optimizer=OPT, **DEPTH), 25).cuda()      # (its own model: the window's 14 trainers stay out of the way)
 for _ in range(3):
     train_network(model_b, loader_b, "cuda")
 torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -46,6 +53,19 @@ for _ in range(EP):
 torch.cuda.synchronize(); dtl = (time.perf_counter() - t0) / EP
 _train.EPOCH_WINDOW = True
 print(f"MI355X  train_network: {dtl * 1e3:8.2f} ms/epoch with the per-batch loop (round 2's form)")
+if not DEFAULT_DEPTH:
+    # the per-batch autograd loop: what train_network ran for such a model while the fused step refused it
+    real_reason = _train.FusedTrainStep.reason
+    _train.FusedTrainStep.reason = lambda self, batch=None: "timing the autograd loop"
+    model_c = H.make_network("GCN", H.default_options(optimizer=OPT, **DEPTH), 25).cuda()
+    for _ in range(3):
+        train_network(model_c, loader_b, "cuda")
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(EP):
+        train_network(model_c, loader_b, "cuda")
+    torch.cuda.synchronize(); dta = (time.perf_counter() - t0) / EP
+    _train.FusedTrainStep.reason = real_reason
+    print(f"MI355X  train_network: {dta * 1e3:8.2f} ms/epoch with the per-batch autograd loop (the form before the fused step)")
 t0 = time.perf_counter()
 for _ in range(EP):
     eval_network(model, loader, "cuda")
@@ -59,7 +79,7 @@ for _ in range(EP):
     eval_network(model, vloader, "cuda")
 torch.cuda.synchronize(); dtv = (time.perf_counter() - t0) / EP
 print(f"MI355X  eval_network : {dtv * 1e3:8.2f} ms/epoch (fixed loader: batches collated once, one graph launch per call)")
-if OPT != "Adam":
+if OPT != "Adam" or not DEFAULT_DEPTH:
     sys.exit(0)
 # CPU: the oracle's loop with the host collate (what the reference does through PyG on the CPU)
 torch.set_num_threads(min(16, os.cpu_count() or 1))
