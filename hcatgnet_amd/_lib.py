@@ -20,7 +20,10 @@ HCG_HEAD_FORWARD_ONLY = 1
 HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2, HCG_WS_HEAD_DEEP = 0, 1, 2, 3, 4   # hcg_general_workspace_bytes kinds
 HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                          # hcg_fused_aux_bytes kinds
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
-HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS = 5, 6
+HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS, HCG_STRUCT_EXPLAIN_ARGS = 5, 6, 7
+HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD = 0, 1               # modes of hcg_explain
+HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
+HCG_ERR_UNSUPPORTED = -3
 HCG_HEAD_MAX_LAYERS = 4
 HCG_UPDATE_ADAM, HCG_UPDATE_SGD, HCG_UPDATE_RMSPROP = 0, 1, 2      # update rules of hcg_step_tail / hcg_update_dev
 HCG_REDUCE_MAX_JOBS, HCG_REDUCE_MAX_SEGS = 8, 4
@@ -76,6 +79,17 @@ class HeadArgs(ctypes.Structure):
                 ("flags", I32), ("slope", F32), ("reserved", I32)]
 
 
+class ExplainArgs(ctypes.Structure):
+    """hcg_explain_args: a batch of graphs explained in one launch, or one any-shape layer's edge-multiplier gradient."""
+    _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
+                ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
+                ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
+                ("out", P), ("loss", P), ("d_edge_mask", P), ("d_node_mask", P), ("dx", P), ("status", P), ("workspace", P),
+                ("workspace_bytes", SZ), ("workspace_bytes_needed", SZ), ("N", I64), ("E", I64), ("B", I64), ("F", I64), ("D", I64),
+                ("C", I64), ("max_nodes", I64), ("max_edges", I64), ("n_conv", I32), ("R", I32), ("slope", F32), ("apply_act", I32),
+                ("layer_dout", P), ("layer_out", P), ("layer_h", P), ("rowptr", P), ("col", P), ("dinv", P), ("dew_csr", P)]
+
+
 class CollateSlot(ctypes.Structure):
     """hcg_collate_slot: one batch of a collate launch."""
     _fields_ = [("ids", P), ("graph_ptr", P), ("edge_ptr", P), ("x_out", P), ("edge_index_out", P), ("batch_out", P),
@@ -101,7 +115,7 @@ SIGNATURES = {
     "hcg_linear_bwd": (INT, [P, P, P, P, P, P, P, P, I64, I64, I64, INT, F32, P, SZ, P]),
     "hcg_gcn_layer_fwd": (INT, [P, P, P, P, P, P, P, F32, F32, INT, P, P, I64, I64, I64, I64, P]),
     "hcg_gcn_layer_bwd": (INT, [P, P, P, P, P, P, P, P, F32, F32, INT, P, P, P, P, I64, I64, I64, I64, P, SZ, P]),
-    "hcg_gcn_edge_weight_grad": (INT, [P, P, P, P, P, P, F32, INT, P, I64, I64, I64, P]),
+    "hcg_explain": (INT, [P, P]),
     "hcg_pool_fwd": (INT, [P, P, P, I64, I64, I64, P]),
     "hcg_pool_bwd": (INT, [P, P, P, P, P, I64, I64, I64, P]),
     "hcg_fused_graphs_per_tile": (INT, [I64, I64, I64]),
@@ -277,6 +291,16 @@ def update_dev(grad, *, rule: int = HCG_UPDATE_ADAM, param=None, exp_avg=None, e
     a.n, a.lr_dev, a.step_dev, a.loss = n, ptr(lr_dev), ptr(step_dev), ptr(loss)
     a.beta1, a.beta2, a.eps, a.update_rule = beta1, beta2, eps, rule
     check(load().hcg_update_dev(ctypes.addressof(a), stream_ptr()), "hcg_update_dev")
+
+
+def layer_edge_grad(dout, out, h, rowptr, col, dinv, slope: float, apply_act: int, dew_csr, N: int, E: int, D: int):
+    """hcg_explain, mode HCG_EXPLAIN_LAYER_EDGE_GRAD: d / d ew_csr of one any-shape conv layer (explain mode)."""
+    a = ExplainArgs()
+    a.mode = HCG_EXPLAIN_LAYER_EDGE_GRAD
+    a.layer_dout, a.layer_out, a.layer_h = ptr(dout), ptr(out), ptr(h)
+    a.rowptr, a.col, a.dinv, a.dew_csr = ptr(rowptr), ptr(col), ptr(dinv), ptr(dew_csr)
+    a.slope, a.apply_act, a.N, a.E, a.D = slope, apply_act, N, E, D
+    check(load().hcg_explain(ctypes.addressof(a), stream_ptr()), "hcg_explain (layer edge gradient)")
 
 
 def job_bytes() -> int:

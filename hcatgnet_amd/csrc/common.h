@@ -77,6 +77,11 @@ int hcg_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t s
 size_t hcg_colsum_partial_floats(int64_t M, int64_t D);
 int hcg_colsum(const float* src, float* out, int64_t M, int64_t D, float* partials, hipStream_t stream);
 
+// ---- the any-shape layer's edge-multiplier gradient (layer.hip), reached through hcg_explain (explain.hip) ----------
+int hcg_edge_weight_grad_launch(const float* dout, const float* out, const float* h, const int32_t* rowptr, const int32_t* col,
+                                const float* dinv, float slope, int apply_act, float* dew_csr, int64_t N, int64_t E, int64_t D,
+                                hipStream_t stream);
+
 // ---- one-graph-per-wave kernels (wave.hip), selected inside the hcg_mid_* entry points (mid.hip) ----------
 int hcg_w64_applicable(int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges);
 int hcg_w64_bwd_grid(int64_t B);

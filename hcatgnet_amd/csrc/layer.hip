@@ -242,15 +242,16 @@ extern "C" int hcg_gcn_layer_bwd(const float* dout, const float* out, const floa
   return HCG_OK;
 }
 
-// d loss / d ew_csr of hcg_gcn_layer_fwd (explain mode): `h` = x W^T (recompute it with hcg_linear_fwd), `out` = the
-// layer's saved output, `dout` the upstream gradient; entries of explicit self-loop edges (col < 0) get 0.
-extern "C" int hcg_gcn_edge_weight_grad(const float* dout, const float* out, const float* h, const int32_t* rowptr,
-                                        const int32_t* col, const float* dinv, float slope, int apply_act, float* dew_csr,
-                                        int64_t N, int64_t E, int64_t D, hcg_stream_t stream) {
+// d loss / d ew_csr of hcg_gcn_layer_fwd (explain mode; hcg_explain's HCG_EXPLAIN_LAYER_EDGE_GRAD): `h` = x W^T (recompute it
+// with hcg_linear_fwd), `out` = the layer's saved output, `dout` the upstream gradient; entries of explicit self-loop edges
+// (col < 0) get 0.
+int hcg_edge_weight_grad_launch(const float* dout, const float* out, const float* h, const int32_t* rowptr,
+                                const int32_t* col, const float* dinv, float slope, int apply_act, float* dew_csr,
+                                int64_t N, int64_t E, int64_t D, hipStream_t stream) {
   if (N < 0 || E < 0 || D <= 0) return HCG_ERR_INVALID_ARG;
   if (N == 0 || E == 0) return HCG_OK;
   if (!dout || !out || !h || !rowptr || !col || !dinv || !dew_csr) return HCG_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(k_edge_weight_grad, dim3((unsigned)hcg_cdiv(N, 16)), dim3(256), 0, (hipStream_t)stream, dout, out, h,
+  hipLaunchKernelGGL(k_edge_weight_grad, dim3((unsigned)hcg_cdiv(N, 16)), dim3(256), 0, stream, dout, out, h,
                      rowptr, col, dinv, slope, apply_act, dew_csr, N, (int)D);
   HCG_CHECK_LAUNCH();
   return HCG_OK;

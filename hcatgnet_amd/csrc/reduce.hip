@@ -315,6 +315,7 @@ extern "C" size_t hcg_struct_bytes(int which) {
     case HCG_STRUCT_COLLATE_SLOT: return sizeof(hcg_collate_slot);
     case HCG_STRUCT_UPDATE_ARGS: return sizeof(hcg_update_args);
     case HCG_STRUCT_HEAD_ARGS: return sizeof(hcg_head_args);
+    case HCG_STRUCT_EXPLAIN_ARGS: return sizeof(hcg_explain_args);
     default: return 0;
   }
 }

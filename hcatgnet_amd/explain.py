@@ -9,13 +9,19 @@ elementwise product on `x` done by the caller.
 
 This module provides the same two functions for `hcatgnet_amd.GCNConv`; the forward then runs the any-shape HIP
 kernels with the mask as per-edge multiplier and autograd delivers d out / d mask (csrc/layer.hip:
-k_edge_weight_grad) and d out / d x.  The optimisation loop of GNNExplainer itself (and the plotting around it) is
-outside this package: any torch optimiser over (node_mask, edge_mask) works on these gradients.
+k_edge_weight_grad) and d out / d x.  `ExplainStep` delivers the same outputs and mask gradients for a whole batch of
+graphs in ONE launch (csrc/explain.hip: one workgroup per graph, mask gradients only, weights frozen).  The
+optimisation loop of GNNExplainer itself (and the plotting around it) is outside this package: any torch optimiser
+over (node_mask, edge_mask) works on these gradients.
 """
 from __future__ import annotations
 
+import ctypes
+from typing import NamedTuple, Optional
+
 import torch
 
+from . import _lib
 from .gcn import GCNConv
 
 
@@ -37,3 +43,174 @@ def clear_masks(model: torch.nn.Module):
             module.explain = False
             module._edge_mask = None
             module._apply_sigmoid = True
+
+
+class ExplainResult(NamedTuple):
+    out: torch.Tensor                       # [B, C]
+    loss: Optional[torch.Tensor]            # [B] per-graph mean_c (out - target)^2; None without target
+    d_edge_mask: Optional[torch.Tensor]     # [E], the batch's edge order; None for a forward-only call
+    d_node_mask: Optional[torch.Tensor]     # [N, F]; None without a node mask (or forward only)
+    dx: Optional[torch.Tensor]              # [N, F] = dJ/dx; None unless asked for
+
+
+class ExplainStep:
+    """Outputs and mask gradients of a frozen model for a whole batch of graphs, one launch per call.
+
+        step = ExplainStep(model, apply_sigmoid=True)
+        r = step(batch, edge_mask, node_mask=None, target=None, dout=None, want_dx=False)
+
+    The values equal autograd through the model run on `x * s(node_mask)` with the edge mask `s(edge_mask)` multiplied
+    into every message of every conv layer (s = sigmoid with `apply_sigmoid`, else the identity; self loops keep 1), of
+    J = sum_g l_g with l_g = mean_c (out_gc - target_gc)^2 (`target` [B, C]) or of J = sum(dout * out) (`dout` [B, C]);
+    with neither, the call is forward only.  At most one of `target` / `dout`.
+
+    The graphs of a batch are independent, so J's gradient restricted to graph g's mask entries is exactly what a
+    batch-of-one explainer run on g computes: one call serves one iteration of an explainer for EVERY graph of a dataset.
+    The regularisers of an explainer (mask size, mask entropy) are functions of the masks alone; the caller adds their
+    gradients with torch ops and keeps the optimiser loop.
+
+    The weights are read, never written; no parameter's `.grad` is touched and no mask stays attached to the model.
+    `batch` needs the collate metadata `FusedTrainStep` needs (`max_nodes`, `max_edges`, grouped edges).  Buffers are
+    allocated for the largest batch seen and reused: in steady state a call allocates nothing and can be captured with
+    `torch.cuda.graph` -- and the returned tensors are views of those buffers, overwritten by the next call (clone what
+    must outlive it).  When `reason(batch)` is not None the step runs the existing path itself (`set_masks`, forward,
+    `torch.autograd.grad` with respect to the masks and x only, `clear_masks`) and returns the same fields;
+    `last_path` says which one ran ("fused" / "autograd")."""
+
+    def __init__(self, model: torch.nn.Module, apply_sigmoid: bool = True):
+        self.model, self.apply_sigmoid = model, bool(apply_sigmoid)
+        self.last_path: Optional[str] = None
+        self._cap = None            # (N, E, B) capacity of the buffers
+        self._bufs = None
+        self._args = _lib.ExplainArgs()
+
+    # ------------------------------------------------------------------ support check (host only, no sync)
+    def _shape_args(self, a, batch) -> Optional[str]:
+        m = self.model
+        need = ("embedding_dim", "n_node_features", "n_convolutions", "readout_layers", "_n_classes", "conv1", "readout")
+        if any(not hasattr(m, k) for k in need):
+            return "not a hcatgnet_amd GCN model"
+        if not bool(getattr(m, "use_fused", True)):
+            return "fused kernels disabled on the model"
+        a.mode, a.flags = _lib.HCG_EXPLAIN_GRAPHS, _lib.HCG_EXPLAIN_QUERY
+        a.F, a.D, a.C = int(m.n_node_features), int(m.embedding_dim), int(m._n_classes)
+        a.n_conv, a.R = int(m.n_convolutions), int(m.readout_layers)
+        a.N = a.E = a.B = a.max_nodes = a.max_edges = 0
+        if batch is not None:
+            mx, me = getattr(batch, "max_nodes", None), getattr(batch, "max_edges", None)
+            if mx is None or me is None or not getattr(batch, "edges_grouped", False):
+                return "batch lacks collate metadata (max_nodes / max_edges / grouped edges)"
+            if getattr(batch, "edge_weight", None) is not None:
+                return "explicit edge weights cannot be combined with masks"
+            if batch.x.shape[1] != a.F:
+                return f"batch has {batch.x.shape[1]} node features, the model takes {a.F}"
+            a.N, a.E, a.B = int(batch.x.shape[0]), int(batch.edge_index.shape[1]), int(batch.num_graphs)
+            a.max_nodes, a.max_edges = int(mx), int(me)
+        rc = _lib.load().hcg_explain(ctypes.addressof(a), None)
+        if rc == _lib.HCG_ERR_UNSUPPORTED:
+            return ("model / graph shape outside the one-launch explain kernel (embedding_dim 64, <= 64 node features, <= 4 conv "
+                    "layers, readout depth <= 4, <= 8 classes, graphs of <= 224 nodes and <= 1024 directed edges)")
+        _lib.check(rc, "hcg_explain (query)")
+        return None
+
+    def reason(self, batch=None) -> Optional[str]:
+        """None when this model (and `batch`) takes the one-launch kernel, else why not.  Host metadata only."""
+        return self._shape_args(_lib.ExplainArgs(), batch)
+
+    # ------------------------------------------------------------------ buffers
+    def _buffers(self, N, E, B, F, C, ws_bytes, dev):
+        cap = self._cap
+        if cap is None or N > cap[0] or E > cap[1] or B > cap[2] or ws_bytes > cap[3] or self._bufs["out"].device != dev:
+            cap = (max(N, cap[0] if cap else 0), max(E, cap[1] if cap else 0), max(B, cap[2] if cap else 0),
+                   max(ws_bytes, cap[3] if cap else 0))
+            f32 = dict(dtype=torch.float32, device=dev)
+            self._bufs = dict(out=torch.zeros(cap[2], C, **f32), loss=torch.zeros(cap[2], **f32),
+                              d_edge=torch.zeros(max(cap[1], 1), **f32), d_node=torch.zeros(max(cap[0], 1), F, **f32),
+                              dx=torch.zeros(max(cap[0], 1), F, **f32),
+                              ws=torch.empty(max(cap[3], 256), dtype=torch.uint8, device=dev))
+            self._cap = cap
+        return self._bufs
+
+    @staticmethod
+    def _mask(t, shape, what):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)}; got {t.dtype} {tuple(t.shape)}")
+        return t.detach()
+
+    # ------------------------------------------------------------------ the call
+    def __call__(self, batch, edge_mask, node_mask=None, target=None, dout=None, want_dx: bool = False) -> ExplainResult:
+        if target is not None and dout is not None:
+            raise ValueError("at most one of target / dout")
+        a = self._args
+        why = self._shape_args(a, batch)
+        if why is not None:
+            return self._autograd(batch, edge_mask, node_mask, target, dout, want_dx)
+        m = self.model
+        x = batch.x
+        _lib.require_gpu(x, batch.edge_index, edge_mask, node_mask, target, dout)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("batch.x must be contiguous float32")
+        N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
+        em = self._mask(edge_mask, (E,), "edge_mask")
+        nm = self._mask(node_mask, (N, F), "node_mask") if node_mask is not None else None
+        tg = self._mask(target, (B, C), "target") if target is not None else None
+        do = self._mask(dout, (B, C), "dout") if dout is not None else None
+        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
+        bwd = tg is not None or do is not None
+        bufs = self._buffers(N, E, B, F, C, int(a.workspace_bytes_needed), x.device)
+        convs = [m.conv1] + list(m.conv_layers)
+        lins = [q[0] if isinstance(q, torch.nn.Sequential) else q for q in m.readout]
+        p = _lib.ptr
+        a.flags = _lib.HCG_EXPLAIN_SIGMOID if self.apply_sigmoid else 0
+        a.x, a.edge_index, a.graph_ptr, a.edge_ptr = p(x), p(plan.edge_index), p(plan.graph_ptr), p(plan.edge_ptr)
+        a.edge_mask, a.node_mask, a.target, a.dout = p(em), p(nm), p(tg), p(do)
+        for l in range(_lib.HCG_EXPLAIN_MAX_CONVS):
+            a.conv_W[l] = p(convs[l].lin.weight) if l < len(convs) else None
+            a.conv_b[l] = p(convs[l].bias) if l < len(convs) else None
+        for i in range(_lib.HCG_HEAD_MAX_LAYERS):
+            a.head_W[i] = p(lins[i].weight) if i < len(lins) else None
+            a.head_b[i] = p(lins[i].bias) if i < len(lins) else None
+        for q in [c.lin.weight for c in convs] + [c.bias for c in convs] + [t for li in lins for t in (li.weight, li.bias)]:
+            if q.dtype != torch.float32 or not q.is_contiguous() or q.device != x.device:
+                raise _lib.HcgError("ExplainStep: the model's weights must be contiguous float32 on the batch's device")
+        a.out, a.loss, a.d_edge_mask = p(bufs["out"]), p(bufs["loss"]), p(bufs["d_edge"])
+        a.d_node_mask = p(bufs["d_node"]) if nm is not None else None
+        a.dx = p(bufs["dx"]) if want_dx else None
+        a.status, a.workspace, a.workspace_bytes = p(plan.status), p(bufs["ws"]), bufs["ws"].numel()
+        a.slope = 0.01                      # nn.LeakyReLU() default (reference model/gcn.py:21, :63)
+        _lib.check(_lib.load().hcg_explain(ctypes.addressof(a), _lib.stream_ptr()), "hcg_explain")
+        self.last_path = "fused"
+        return ExplainResult(bufs["out"][:B], bufs["loss"][:B] if tg is not None else None,
+                             bufs["d_edge"][:E] if bwd else None,
+                             bufs["d_node"][:N] if bwd and nm is not None else None,
+                             bufs["dx"][:N] if bwd and want_dx else None)
+
+    # ------------------------------------------------------------------ the existing path (any shape), under autograd
+    def _autograd(self, batch, edge_mask, node_mask, target, dout, want_dx) -> ExplainResult:
+        m = self.model
+        bwd = target is not None or dout is not None
+        s = torch.sigmoid if self.apply_sigmoid else (lambda t: t)
+        em = edge_mask.detach().requires_grad_(bwd)
+        nm = node_mask.detach().requires_grad_(bwd) if node_mask is not None else None
+        x = batch.x.detach().requires_grad_(bwd and want_dx)
+        xin = x * s(nm) if nm is not None else x
+        set_masks(m, em, batch.edge_index, apply_sigmoid=self.apply_sigmoid)
+        try:
+            with torch.enable_grad() if bwd else torch.no_grad():
+                out = m(x=xin, edge_index=batch.edge_index, batch=batch.batch)
+                loss = d_e = d_n = dx = None
+                if bwd:
+                    if target is not None:
+                        loss = ((out - target.detach()) ** 2).mean(dim=1)
+                        J = loss.sum()
+                    else:
+                        J = (dout.detach() * out).sum()
+                    wrt = [em] + ([nm] if nm is not None else []) + ([x] if want_dx else [])
+                    grads = list(torch.autograd.grad(J, wrt))         # (no parameter's .grad is touched)
+                    d_e = grads.pop(0)
+                    d_n = grads.pop(0) if nm is not None else None
+                    dx = grads.pop(0) if want_dx else None
+        finally:
+            clear_masks(m)
+        self.last_path = "autograd"
+        return ExplainResult(out.detach(), loss.detach() if loss is not None else None, d_e, d_n, dx)

@@ -94,10 +94,7 @@ class _GCNLayerFn(torch.autograd.Function):
         if ctx.masked and ctx.needs_input_grad[7]:
             h = saved[4]                                     # x W^T of the forward
             dew = torch.zeros(max(plan.E, 1), dtype=torch.float32, device=dev)
-            rc = lib.hcg_gcn_edge_weight_grad(_lib.ptr(dout), _lib.ptr(out), _lib.ptr(h), _lib.ptr(plan.rowptr),
-                                              _lib.ptr(plan.col), _lib.ptr(dinv), ctx.slope, int(ctx.apply_act),
-                                              _lib.ptr(dew), N, plan.E, D, _lib.stream_ptr())
-            _lib.check(rc, "hcg_gcn_edge_weight_grad")
+            _lib.layer_edge_grad(dout, out, h, plan.rowptr, plan.col, dinv, ctx.slope, int(ctx.apply_act), dew, N, plan.E, D)
             dmult = torch.zeros(plan.E, dtype=torch.float32, device=dev)
             if plan.E:
                 dmult[plan.eid.long()[:plan.E]] = dew[:plan.E]    # CSR order -> the caller's edge order (a permutation)

@@ -132,14 +132,76 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
                       int64_t N, int64_t E, int64_t F, int64_t D,
                       void* workspace, size_t workspace_bytes, hcg_stream_t stream);
 
-/* explain mode (f4): gradient of the layer w.r.t. the per-edge multipliers ew_csr handed to hcg_gcn_layer_fwd --
- * PyG's Explainer multiplies every message by an edge mask inside each MessagePassing layer (reference
- * scripts_experiments/explain_gnn.py:39-50: edge_mask_type='object').  dew_csr[k] = dinv_i dinv_{col k} <dY_i, h_{col k}>
- * with dY = dout * act'(out) and h = x W^T (recompute with hcg_linear_fwd); 0 for explicit self-loop entries. */
-int hcg_gcn_edge_weight_grad(const float* dout, const float* out, const float* h,
-                             const int32_t* rowptr, const int32_t* col, const float* dinv,
-                             float slope, int apply_act, float* dew_csr,
-                             int64_t N, int64_t E, int64_t D, hcg_stream_t stream);
+/* ---- explain mode (f4): ONE entry point, two jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
+ * PyG's Explainer multiplies every message by an edge mask inside each MessagePassing layer, AFTER gcn_norm, self loops keep 1
+ * (reference scripts_experiments/explain_gnn.py:39-50: edge_mask_type='object'); the node mask multiplies x.
+ *
+ * HCG_EXPLAIN_GRAPHS: a whole batch of graphs in ONE launch, one workgroup per graph (csrc/explain.hip), weights frozen:
+ *     x~ = x s(node_mask);  every conv layer  A = LeakyReLU(Ahat_m (A_prev W^T) + b)  with the message of edge e multiplied by
+ *     m_e = s(edge_mask_e);  [max, mean] pooling;  readout of depth R  ->  out [B, C]
+ *   s = sigmoid with HCG_EXPLAIN_SIGMOID in `flags`, else the identity.  Upstream gradient per graph g:
+ *     target != NULL: l_g = mean_c (out_gc - target_gc)^2 (stored in loss [B]) and dout = 2 (out - target) / C;
+ *     dout   != NULL: that row as given;   neither: forward only (no gradient output is touched).
+ *   Gradients of J = sum_g l_g (or sum(dout * out)) with respect to the masks ONLY -- no dW, no db:
+ *     d_edge_mask [E] in the caller's edge order (an explicit (i, i) edge collapses into the unit self loop: exactly 0),
+ *     d_node_mask [N, F] (with node_mask), dx [N, F] = dJ/dx (nullable).
+ *   Graphs are independent: no float atomics, no exchange between workgroups; every result is bitwise reproducible and
+ *   bitwise independent of which other graphs share the batch.
+ *   Shapes: D = 64, F <= 64, graphs of <= 224 nodes and <= 1024 directed edges (`max_nodes` / `max_edges` = largest graph of
+ *   the batch, host metadata; a graph that exceeds them is refused: HCG_STATUS_SHAPE_LIMIT, its outputs zero), n_conv 1..4,
+ *   R 1..4 (readout layer i maps 2D >> i to half of it + LeakyReLU, the last one to C), C <= 8.  Anything else:
+ *   HCG_ERR_UNSUPPORTED.  Needs graph_ptr / edge_ptr / status of a BLOCKED plan and the raw int64 edge_index grouped by graph.
+ *   `workspace`: the layers' H = A_prev W^T and A, which the backward reads again (workspace_bytes_needed, written by every
+ *   call; only a call with target / dout uses it).
+ *   HCG_EXPLAIN_QUERY in `flags`: validate the shapes (D, F, C, n_conv, R, max_nodes, max_edges, N, E, B), write
+ *   workspace_bytes_needed, launch nothing, touch no GPU: HCG_OK or HCG_ERR_UNSUPPORTED.
+ * HCG_EXPLAIN_LAYER_EDGE_GRAD: one layer of the any-shape path -- the gradient with respect to the per-edge multipliers ew_csr
+ *   handed to hcg_gcn_layer_fwd:  dew_csr[k] = dinv_i dinv_{col k} <dY_i, h_{col k}>  with dY = layer_dout * act'(layer_out) and
+ *   h = x W^T (recompute with hcg_linear_fwd); 0 for explicit self-loop entries.  Reads layer_dout, layer_out, layer_h [N, D],
+ *   rowptr, col, dinv, slope, apply_act, N, E, D; writes dew_csr [E]. */
+#define HCG_EXPLAIN_GRAPHS 0
+#define HCG_EXPLAIN_LAYER_EDGE_GRAD 1
+#define HCG_EXPLAIN_QUERY 1    /* flags */
+#define HCG_EXPLAIN_SIGMOID 2  /* flags */
+#define HCG_EXPLAIN_MAX_CONVS 4
+typedef struct hcg_explain_args {
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / HCG_EXPLAIN_LAYER_EDGE_GRAD */
+  int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID */
+  const float* x;                        /* [N, F] */
+  const int64_t* edge_index;             /* [2, E], grouped by graph */
+  const int32_t* graph_ptr;              /* [B + 1] */
+  const int32_t* edge_ptr;               /* [B + 1] */
+  const float* edge_mask;                /* [E], the caller's edge order */
+  const float* node_mask;                /* [N, F], nullable */
+  const float* target;                   /* [B, C], nullable */
+  const float* dout;                     /* [B, C], nullable (at most one of target / dout) */
+  const float* conv_W[HCG_EXPLAIN_MAX_CONVS];   /* conv layer l: lin.weight [D, F or D]; entries >= n_conv unused */
+  const float* conv_b[HCG_EXPLAIN_MAX_CONVS];   /* conv layer l: bias [D] */
+  const float* head_W[4];                /* readout layer i: weight [out_i, in_i]; entries >= R unused (HCG_HEAD_MAX_LAYERS) */
+  const float* head_b[4];                /* readout layer i: bias [out_i] */
+  float* out;                            /* [B, C] */
+  float* loss;                           /* [B]; required with target */
+  float* d_edge_mask;                    /* [E] */
+  float* d_node_mask;                    /* [N, F]; required with node_mask, NULL without */
+  float* dx;                             /* [N, F], nullable */
+  int32_t* status;                       /* the plan's status words */
+  void* workspace;
+  size_t workspace_bytes;
+  size_t workspace_bytes_needed;         /* OUT */
+  int64_t N, E, B, F, D, C;
+  int64_t max_nodes, max_edges;
+  int32_t n_conv, R;
+  float slope;                           /* LeakyReLU negative slope (conv layers and readout) */
+  int32_t apply_act;                     /* HCG_EXPLAIN_LAYER_EDGE_GRAD */
+  const float* layer_dout;               /* HCG_EXPLAIN_LAYER_EDGE_GRAD from here on */
+  const float* layer_out;
+  const float* layer_h;
+  const int32_t* rowptr;
+  const int32_t* col;
+  const float* dinv;
+  float* dew_csr;
+} hcg_explain_args;
+int hcg_explain(hcg_explain_args* args_host, hcg_stream_t stream);
 
 /* ---- graph pooling (a9): emb[g] = [ max_i a_i , mean_i a_i ]  (max FIRST, model/gcn.py:65-66) */
 int hcg_pool_fwd(const float* a, const int32_t* graph_ptr, float* emb /*[B,2D]*/,
@@ -405,6 +467,7 @@ typedef struct hcg_reduce_job {
 #define HCG_STRUCT_COLLATE_SLOT 4
 #define HCG_STRUCT_UPDATE_ARGS 5
 #define HCG_STRUCT_HEAD_ARGS 6
+#define HCG_STRUCT_EXPLAIN_ARGS 7
 size_t hcg_struct_bytes(int which);
 int hcg_fused_reduce_job(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F,
                          int64_t D, int graphs_per_tile, float* dW, float* db, hcg_reduce_job* job_host);

@@ -1,0 +1,106 @@
+"""Host side of the one-launch explain step (no GPU): the hcg_explain argument block, its shape / workspace query, the
+folded C symbol, and `ExplainStep.reason`."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+import hcatgnet_amd as H
+from hcatgnet_amd import _lib
+from hcatgnet_amd.explain import ExplainStep
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    if not os.path.isfile(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+
+
+def _query(F=25, D=64, nodes=184, edges=390, n_conv=2, R=2, C=1, N=None, B=1):
+    a = _lib.ExplainArgs()
+    a.mode, a.flags = _lib.HCG_EXPLAIN_GRAPHS, _lib.HCG_EXPLAIN_QUERY
+    a.F, a.D, a.C, a.n_conv, a.R = F, D, C, n_conv, R
+    a.max_nodes, a.max_edges = nodes, edges
+    a.N, a.E, a.B = nodes if N is None else N, edges, B
+    rc = _lib.load().hcg_explain(ctypes.addressof(a), None)
+    return rc, int(a.workspace_bytes_needed)
+
+
+def test_explain_args_mirror_matches_the_library():
+    lib = _lib.load()
+    assert ctypes.sizeof(_lib.ExplainArgs) == lib.hcg_struct_bytes(_lib.HCG_STRUCT_EXPLAIN_ARGS)
+    assert _lib.HCG_STRUCT_EXPLAIN_ARGS == 7
+    assert lib.hcg_explain(None, None) == -1
+    a = _lib.ExplainArgs()
+    a.mode = 9
+    assert lib.hcg_explain(ctypes.addressof(a), None) == -1
+
+
+def test_query_accepts_and_refuses_without_a_gpu():
+    """HCG_EXPLAIN_QUERY validates the shapes and reports the workspace; nothing is launched (this machine may have no
+    GPU at all).  The workspace holds H and A of every conv layer for the backward: 2 * n_conv * N * 64 floats."""
+    rc, ws = _query()
+    assert rc == 0 and ws >= 2 * 2 * 184 * 64 * 4
+    rc, ws = _query(F=64, nodes=224, edges=1024, n_conv=4, R=4, C=8)
+    assert rc == 0 and ws >= 2 * 4 * 224 * 64 * 4
+    rc, ws = _query(nodes=120, edges=250, N=535 * 120, B=535)
+    assert rc == 0 and ws >= 2 * 2 * 535 * 120 * 64 * 4
+    for n_conv in (1, 2, 3, 4):
+        for R in (1, 2, 3, 4):
+            assert _query(n_conv=n_conv, R=R)[0] == 0
+    for kw in (dict(D=128), dict(F=65), dict(nodes=225), dict(edges=1025), dict(C=9), dict(R=5), dict(n_conv=5), dict(F=0),
+               dict(C=0), dict(n_conv=0), dict(R=0)):
+        assert _query(**kw)[0] == -3, kw
+
+
+def test_old_edge_gradient_symbol_is_folded_into_hcg_explain():
+    hdr = open(os.path.join(REPO, "include", "hcatgnet_hip.h")).read()
+    assert "hcg_gcn_edge_weight_grad" not in hdr
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = set(re.findall(r"\b(hcg_[a-z0-9_]+)\s*\(", code))
+    assert "hcg_explain" in declared and len(declared) <= 55
+    assert "hcg_gcn_edge_weight_grad" not in _lib.SIGNATURES and "hcg_explain" in _lib.SIGNATURES
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    assert not hasattr(lib, "hcg_gcn_edge_weight_grad")
+    assert hasattr(lib, "hcg_explain")
+    assert _lib.load().hcg_version() == 1
+    # the layer mode's query needs no workspace; its launch arguments are validated like the old entry point's
+    a = _lib.ExplainArgs()
+    a.mode, a.flags = _lib.HCG_EXPLAIN_LAYER_EDGE_GRAD, _lib.HCG_EXPLAIN_QUERY
+    assert _lib.load().hcg_explain(ctypes.addressof(a), None) == 0 and a.workspace_bytes_needed == 0
+    a.flags, a.N, a.E, a.D = 0, 4, 3, 0
+    assert _lib.load().hcg_explain(ctypes.addressof(a), None) == -1           # D <= 0
+    a.D, a.N = 64, 0
+    assert _lib.load().hcg_explain(ctypes.addressof(a), None) == 0            # no nodes: nothing to do
+
+
+def test_explain_step_support_check_is_host_only():
+    """`ExplainStep.reason` decides on the host (no GPU, no sync) whether a model / batch takes the one-launch kernel."""
+    x = torch.zeros(4, 25); ei = torch.zeros(2, 0, dtype=torch.int64); bv = torch.zeros(4, dtype=torch.int64)
+    mk = lambda **kw: H.Batch(x, ei, bv, 1, **kw)
+    step = ExplainStep(H.make_network("GCN", H.default_options(), 25))
+    assert step.reason() is None
+    assert step.reason(mk(max_nodes=30, max_edges=64, edges_grouped=True)) is None
+    assert step.reason(mk(max_nodes=184, max_edges=390, edges_grouped=True)) is None
+    assert step.reason(mk(max_nodes=224, max_edges=1024, edges_grouped=True)) is None
+    assert "shape" in step.reason(mk(max_nodes=225, max_edges=390, edges_grouped=True))
+    assert "shape" in step.reason(mk(max_nodes=184, max_edges=1025, edges_grouped=True))
+    assert "metadata" in step.reason(mk())
+    assert "metadata" in step.reason(mk(max_nodes=30, max_edges=64))
+    wrong = H.Batch(torch.zeros(4, 32), ei, bv, 1, max_nodes=30, max_edges=64, edges_grouped=True)
+    assert "features" in step.reason(wrong)
+    for kw in (dict(embedding_dim=128), dict(n_convolutions=5), dict(n_classes=9)):
+        assert "shape" in ExplainStep(H.make_network("GCN", H.default_options(**kw), 25)).reason(), kw
+    assert "shape" in ExplainStep(H.make_network("GCN", H.default_options(), 65)).reason()
+    for kw in (dict(n_convolutions=1, readout_layers=1), dict(n_convolutions=3, readout_layers=3, n_classes=2),
+               dict(n_convolutions=4, readout_layers=4, n_classes=8)):
+        deep = ExplainStep(H.make_network("GCN", H.default_options(**kw), 32))
+        assert deep.reason() is None, kw
+    off = H.make_network("GCN", H.default_options(use_fused=False), 25)
+    assert "disabled" in ExplainStep(off).reason()
+    assert step.last_path is None
