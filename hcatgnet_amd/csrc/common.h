@@ -82,6 +82,9 @@ int hcg_edge_weight_grad_launch(const float* dout, const float* out, const float
                                 const float* dinv, float slope, int apply_act, float* dew_csr, int64_t N, int64_t E, int64_t D,
                                 hipStream_t stream);
 
+// ---- the ensemble forward (ensemble.hip), reached through hcg_explain, mode HCG_EXPLAIN_ENSEMBLE (explain.hip) ----------
+int hcg_ensemble_launch(hcg_explain_args* p, hipStream_t stream);
+
 // ---- one-graph-per-wave kernels (wave.hip), selected inside the hcg_mid_* entry points (mid.hip) ----------
 int hcg_w64_applicable(int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges);
 int hcg_w64_bwd_grid(int64_t B);

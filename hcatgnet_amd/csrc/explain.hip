@@ -22,18 +22,9 @@
 // ([2 n_conv][N][64] f32, each graph's rows written and read by its own workgroup only).
 #include "common.h"
 #include "graph_csr.h"
+#include "explain_tile.h"
 
 namespace {
-
-constexpr int XW = 8;                  // waves per workgroup
-constexpr int XT = XW * 64;            // threads
-constexpr int X_MAX_NODES = 224;
-constexpr int X_MAX_EDGES = 1024;
-constexpr int XD = 64;                 // embedding_dim
-constexpr int XS = XD + 4;             // tile row stride in floats (rows 16-byte aligned, four rows of a wave on different banks)
-constexpr int X_EPT = X_MAX_EDGES / XT;
-constexpr int X_HEAD = 256;            // floats of the readout's activation / gradient vectors (128 + 64 + 32 + 16 + 8 used)
-constexpr int X_RPL = (X_MAX_NODES + 63) / 64;
 
 struct XArgs {     // the kernel's argument block (device pointers by value)
   const float* x;
@@ -102,54 +93,7 @@ __device__ __forceinline__ XLds x_carve(char* base, int npad, int emax) {
   return L;
 }
 
-struct XGraph { int ebase, ne; };   // what EdgeRegs::load reads of a graph
-
-// (a select chain, not an index: a dynamically indexed kernel-argument array would be copied to scratch)
-__device__ __forceinline__ const float* x_pick(const float* const (&p)[4], int i) {
-  return i == 0 ? p[0] : i == 1 ? p[1] : i == 2 ? p[2] : p[3];
-}
-
 __device__ __forceinline__ float x_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-// entries [kb, ke) of a packed list in ascending order (neighbour id, then edge position)
-__device__ __forceinline__ void x_sort_row(unsigned* ent, int kb, int ke) {
-  const int len = ke - kb;
-  if (len > 1 && len <= 4) {
-    const Sorted4 o = sort4(ent[kb], ent[kb + 1], len > 2 ? ent[kb + 2] : 0xffffffffu, len > 3 ? ent[kb + 3] : 0xffffffffu);
-    ent[kb] = o.a0;
-    ent[kb + 1] = o.a1;
-    if (len > 2) ent[kb + 2] = o.a2;
-    if (len > 3) ent[kb + 3] = o.a3;
-  } else if (len > 4) {
-    for (int a = kb + 1; a < ke; ++a) {
-      const unsigned key = ent[a];
-      int b = a - 1;
-      while (b >= kb && ent[b] > key) { ent[b + 1] = ent[b]; --b; }
-      ent[b + 1] = key;
-    }
-  }
-}
-
-// res(r, lane) = sum_k in[r][k] w[k] for the rows r < n of an LDS tile: a wave takes one row at a time; four partial sums
-// (k = 0, 1, 2, 3 mod 4, each ascending) combined as (p0 + p1) + (p2 + p3): the same order for every row.  (Four rows at a time
-// kept every row's tile reads live at once -- 192 registers beside the 64 of w -- and spilled.)
-template <class Store>
-__device__ __forceinline__ void x_gemm(const float* in, const float (&w)[XD], int n, int wave, Store store) {
-#pragma nounroll
-  for (int r = wave; r < n; r += XW) {
-    const float* row = in + r * XS;
-    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-#pragma unroll
-    for (int k4 = 0; k4 < XD / 4; ++k4) {
-      const float4 a = *reinterpret_cast<const float4*>(row + 4 * k4);
-      p0 = fmaf(a.x, w[4 * k4], p0);
-      p1 = fmaf(a.y, w[4 * k4 + 1], p1);
-      p2 = fmaf(a.z, w[4 * k4 + 2], p2);
-      p3 = fmaf(a.w, w[4 * k4 + 3], p3);
-    }
-    store(r, (p0 + p1) + (p2 + p3));
-  }
-}
 
 // acc = self * t[row] + sum_{k in [kb, ke)} mval[e_k] dinv[c_k] t[c_k]  for this lane's four columns
 __device__ __forceinline__ float4 x_row_sum(const float* t, const unsigned* ent, const float* mval, const float* dinv,
@@ -272,17 +216,8 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   for (int l = 0; l < n_conv; ++l) {
     const int K = __builtin_amdgcn_readfirstlane(l == 0 ? F : XD);   // (uniform: keeps the weight addressing scalar)
     {
-      // the lane's weight row: ONE uniform base + a 32-bit byte offset per element (the scalar-base form of global_load; a
-      // 64-bit address per element, vector or scalar, is 128 registers), unconditional loads on a clamped flat index
-      const char* Wb = reinterpret_cast<const char*>(x_pick(a.cW, l));
-      const unsigned row0 = (unsigned)(lane * K), last = (unsigned)(XD * K - 1);
       float w[XD];
-#pragma unroll
-      for (int k = 0; k < XD; ++k) {
-        const float v = *reinterpret_cast<const float*>(Wb + 4u * min(row0 + (unsigned)k, last));
-        w[k] = k < K ? v : 0.f;
-        if ((k & 15) == 15) __builtin_amdgcn_sched_barrier(0);
-      }
+      x_weight_row(w, reinterpret_cast<const char*>(x_pick(a.cW, l)), lane, K);
       float* hws = wsg + (size_t)(2 * l) * plane;
       x_gemm(L.t0, w, n, wave, [&](int r, float v) {
         L.t1[r * XS + lane] = v;
@@ -492,12 +427,6 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   }
 }
 
-int explain_shapes_ok(const hcg_explain_args* p) {
-  return p->D == XD && p->F >= 1 && p->F <= XD && p->C >= 1 && p->C <= 8 && p->n_conv >= 1 && p->n_conv <= HCG_EXPLAIN_MAX_CONVS &&
-         p->R >= 1 && p->R <= HCG_HEAD_MAX_LAYERS && p->max_nodes >= 0 && p->max_nodes <= X_MAX_NODES && p->max_edges >= 0 &&
-         p->max_edges <= X_MAX_EDGES && p->N >= 0 && p->E >= 0 && p->B >= 0 && p->N < (1ll << 31) / XD && p->E < (1ll << 31);
-}
-
 hipError_t explain_allow_big_lds() {   // dynamic LDS above 64 KB: allowed once per process (not per launch: it may be under capture)
   static hipError_t st = hipFuncSetAttribute((const void*)k_explain_graphs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return st;
@@ -513,8 +442,9 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
     return hcg_edge_weight_grad_launch(p->layer_dout, p->layer_out, p->layer_h, p->rowptr, p->col, p->dinv, p->slope,
                                        p->apply_act, p->dew_csr, p->N, p->E, p->D, stream);
   }
+  if (p->mode == HCG_EXPLAIN_ENSEMBLE) return hcg_ensemble_launch(p, stream);
   if (p->mode != HCG_EXPLAIN_GRAPHS) return HCG_ERR_INVALID_ARG;
-  if (!explain_shapes_ok(p)) return HCG_ERR_UNSUPPORTED;
+  if (!x_shapes_ok(p)) return HCG_ERR_UNSUPPORTED;
   // H_l and A_l of every layer, [N][64] f32 each: the backward reads them again
   p->workspace_bytes_needed = hcg_align_up((size_t)2 * p->n_conv * (size_t)(p->N > 0 ? p->N : 1) * XD * sizeof(float), 256);
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;

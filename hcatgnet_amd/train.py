@@ -1359,3 +1359,44 @@ def predict_network(model, loader, return_emb: bool = False, device=None):
     frame["ddG_pred"] = y_pred
     frame["index"] = idx
     return y_pred, y_true, idx, frame
+
+
+def predict_networks(models, loader, return_emb: bool = False, device=None):
+    """`[predict_network(model_k, loader, return_emb, device) for model_k in models]` -- the same tuples and frames -- with ONE
+    ensemble call per batch of the shared loader instead of one forward per model and batch (reference
+    scripts_experiments/predict_test.py:19-103: every model of the nested cross-validation predicts the same set).  The
+    ensemble is built from the models' weights at call time (`ensemble.EnsemblePredict`); models or batches outside its
+    kernel run model by model inside it."""
+    from .ensemble import EnsemblePredict
+    models = list(models)
+    for m in models:
+        m.eval()
+    if device is None:
+        device = next(models[0].parameters()).device
+    ens = EnsemblePredict(models)
+    M = len(models)
+    y_pred, embs, y_true, idx = [], [], [], []
+    with torch.no_grad():
+        for batch in loader:
+            batch = batch.to(device)
+            r = ens(batch, return_emb=return_emb, stats=False)
+            y_pred.append(r.out.reshape(M, -1).clone())
+            y_true.append(batch.y.reshape(-1))
+            idx.append(batch.idx.reshape(-1) if batch.idx is not None else torch.full((batch.num_graphs,), -1, device=r.out.device))
+            if return_emb:
+                embs.append(r.emb.clone())
+    y_pred = torch.cat(y_pred, 1).cpu().numpy()
+    y_true = torch.cat(y_true).cpu().numpy().ravel()
+    idx = torch.cat(idx).cpu().numpy().ravel()
+    if not return_emb:
+        return [(y_pred[k].ravel(), y_true, idx) for k in range(M)]
+    import pandas as pd
+    emb = torch.cat(embs, 1).cpu().numpy()
+    res = []
+    for k in range(M):
+        frame = pd.DataFrame(emb[k])
+        frame["ddG_exp"] = y_true
+        frame["ddG_pred"] = y_pred[k].ravel()
+        frame["index"] = idx
+        res.append((y_pred[k].ravel(), y_true, idx, frame))
+    return res

@@ -132,7 +132,7 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
                       int64_t N, int64_t E, int64_t F, int64_t D,
                       void* workspace, size_t workspace_bytes, hcg_stream_t stream);
 
-/* ---- explain mode (f4): ONE entry point, two jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
+/* ---- explain mode (f4): ONE entry point, three jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
  * PyG's Explainer multiplies every message by an edge mask inside each MessagePassing layer, AFTER gcn_norm, self loops keep 1
  * (reference scripts_experiments/explain_gnn.py:39-50: edge_mask_type='object'); the node mask multiplies x.
  *
@@ -158,14 +158,25 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  * HCG_EXPLAIN_LAYER_EDGE_GRAD: one layer of the any-shape path -- the gradient with respect to the per-edge multipliers ew_csr
  *   handed to hcg_gcn_layer_fwd:  dew_csr[k] = dinv_i dinv_{col k} <dY_i, h_{col k}>  with dY = layer_dout * act'(layer_out) and
  *   h = x W^T (recompute with hcg_linear_fwd); 0 for explicit self-loop entries.  Reads layer_dout, layer_out, layer_h [N, D],
- *   rowptr, col, dinv, slope, apply_act, N, E, D; writes dew_csr [E]. */
+ *   rowptr, col, dinv, slope, apply_act, N, E, D; writes dew_csr [E].
+ * HCG_EXPLAIN_ENSEMBLE: `n_models` frozen models of ONE architecture predict the same batch of graphs in ONE launch, forward
+ *   only (csrc/ensemble.hip; reference scripts_experiments/predict_test.py:19-103).  One workgroup per (graph, group of
+ *   `models_per_group` models): gcn_norm and the row list are built once per workgroup and reused by its models.
+ *   conv_W[l] / conv_b[l] / head_W[i] / head_b[i] point at the models' tensors stacked along a leading M axis
+ *   ([M, D, F or D], [M, D], [M, out_i, in_i], [M, out_i]; contiguous).  out is [M, B, C]; emb ([M, B, 2D], max first) is
+ *   written when not NULL.  edge_mask, node_mask, target and dout must be NULL (HCG_ERR_INVALID_ARG); loss, the gradient
+ *   outputs and the workspace are not used (workspace_bytes_needed = 0).  Shapes and refusals as HCG_EXPLAIN_GRAPHS, plus
+ *   1 <= n_models and 1 <= models_per_group <= n_models; a refused graph's rows of out / emb are zero for every model.  The
+ *   result for (model, graph) is bitwise independent of n_models, of models_per_group and of the rest of the batch.
+ *   HCG_EXPLAIN_QUERY as above. */
 #define HCG_EXPLAIN_GRAPHS 0
 #define HCG_EXPLAIN_LAYER_EDGE_GRAD 1
+#define HCG_EXPLAIN_ENSEMBLE 2
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / HCG_EXPLAIN_LAYER_EDGE_GRAD */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / HCG_EXPLAIN_LAYER_EDGE_GRAD / HCG_EXPLAIN_ENSEMBLE */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -200,6 +211,9 @@ typedef struct hcg_explain_args {
   const int32_t* col;
   const float* dinv;
   float* dew_csr;
+  float* emb;                            /* HCG_EXPLAIN_ENSEMBLE from here on: [M, B, 2D], nullable */
+  int32_t n_models;                      /* M */
+  int32_t models_per_group;              /* models one workgroup runs on its graph, 1 .. M */
 } hcg_explain_args;
 int hcg_explain(hcg_explain_args* args_host, hcg_stream_t stream);
 
