@@ -15,6 +15,8 @@ Public surface (mirrors the reference's names for this path):
     explain.set_masks / clear_masks             explain-mode edge masks (PyG Explainer hooks)
     EnsemblePredict, stack_weights              M trained models predict one batch in one launch (the reference's
                                                 predict_test.py loop); train.predict_networks is its loader form
+    ShapleySampling, draw_permutations          Shapley value sampling of a batch of graphs, the permutation walk on chip
+                                                (the reference's second explain algorithm, explain_gnn.py)
 Compute lives in csrc/libhcatgnet_hip.so (hand-written HIP for gfx950) behind include/hcatgnet_hip.h.
 """
 from .batch import Batch, Data, DataLoader, collate  # noqa: F401
@@ -23,8 +25,9 @@ from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F4
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
 from .networks import BaseNetwork  # noqa: F401
 from .plan import BatchPlan  # noqa: F401
+from .shapley import ShapleyResult, ShapleySampling, draw_permutations  # noqa: F401
 from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
 
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
-           "stack_weights"]
+           "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations"]

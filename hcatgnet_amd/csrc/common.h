@@ -84,6 +84,8 @@ int hcg_edge_weight_grad_launch(const float* dout, const float* out, const float
 
 // ---- the ensemble forward (ensemble.hip), reached through hcg_explain, mode HCG_EXPLAIN_ENSEMBLE (explain.hip) ----------
 int hcg_ensemble_launch(hcg_explain_args* p, hipStream_t stream);
+// ---- Shapley value sampling (shapley.hip), reached through hcg_explain, mode HCG_EXPLAIN_SHAPLEY -------------------------
+int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream);
 
 // ---- one-graph-per-wave kernels (wave.hip), selected inside the hcg_mid_* entry points (mid.hip) ----------
 int hcg_w64_applicable(int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges);

@@ -95,24 +95,6 @@ __device__ __forceinline__ XLds x_carve(char* base, int npad, int emax) {
 
 __device__ __forceinline__ float x_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-// acc = self * t[row] + sum_{k in [kb, ke)} mval[e_k] dinv[c_k] t[c_k]  for this lane's four columns
-__device__ __forceinline__ float4 x_row_sum(const float* t, const unsigned* ent, const float* mval, const float* dinv,
-                                            int row, int kb, int ke, int c4, float self) {
-  const float4 s = *reinterpret_cast<const float4*>(t + row * XS + 4 * c4);
-  float4 acc = make_float4(self * s.x, self * s.y, self * s.z, self * s.w);
-  for (int k = kb; k < ke; ++k) {
-    const unsigned en = ent[k];
-    const int c = (int)(en >> 16);
-    const float coef = mval[en & 0xffffu] * dinv[c];
-    const float4 v = *reinterpret_cast<const float4*>(t + c * XS + 4 * c4);
-    acc.x = fmaf(coef, v.x, acc.x);
-    acc.y = fmaf(coef, v.y, acc.y);
-    acc.z = fmaf(coef, v.z, acc.z);
-    acc.w = fmaf(coef, v.w, acc.w);
-  }
-  return acc;
-}
-
 __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const XLds L = x_carve(smem, a.npad, a.emax);
@@ -443,6 +425,7 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
                                        p->apply_act, p->dew_csr, p->N, p->E, p->D, stream);
   }
   if (p->mode == HCG_EXPLAIN_ENSEMBLE) return hcg_ensemble_launch(p, stream);
+  if (p->mode == HCG_EXPLAIN_SHAPLEY) return hcg_shapley_launch(p, stream);
   if (p->mode != HCG_EXPLAIN_GRAPHS) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p)) return HCG_ERR_UNSUPPORTED;
   // H_l and A_l of every layer, [N][64] f32 each: the backward reads them again

@@ -1,6 +1,7 @@
 // The pieces the one-workgroup-per-graph, weights-in-registers kernels share (explain.hip: one frozen model, masks, backward;
-// ensemble.hip: many frozen models, forward only): the tile geometry, the shape limits, the sorted packed row list and the
-// lane-per-column f32 GEMM off an LDS tile.  Everything is inlined into the callers; the build's edge pass stays in each kernel
+// ensemble.hip: many frozen models, forward only; shapley.hip: one frozen model, a permutation walk of masked forwards): the
+// tile geometry, the shape limits, the sorted packed row list, the masked row sum and the lane-per-column f32 GEMM off an LDS
+// tile.  Everything is inlined into the callers; the build's edge pass stays in each kernel
 // (graph_csr.h explains why).
 #pragma once
 #include "common.h"
@@ -78,7 +79,25 @@ __device__ __forceinline__ void x_gemm(const float* in, const float (&w)[XD], in
   }
 }
 
-// the model / graph shapes both kernels take (hcg_explain's HCG_ERR_UNSUPPORTED)
+// acc = self * t[row] + sum_{k in [kb, ke)} mval[e_k] dinv[c_k] t[c_k]  for this lane's four columns
+__device__ __forceinline__ float4 x_row_sum(const float* t, const unsigned* ent, const float* mval, const float* dinv,
+                                            int row, int kb, int ke, int c4, float self) {
+  const float4 s = *reinterpret_cast<const float4*>(t + row * XS + 4 * c4);
+  float4 acc = make_float4(self * s.x, self * s.y, self * s.z, self * s.w);
+  for (int k = kb; k < ke; ++k) {
+    const unsigned en = ent[k];
+    const int c = (int)(en >> 16);
+    const float coef = mval[en & 0xffffu] * dinv[c];
+    const float4 v = *reinterpret_cast<const float4*>(t + c * XS + 4 * c4);
+    acc.x = fmaf(coef, v.x, acc.x);
+    acc.y = fmaf(coef, v.y, acc.y);
+    acc.z = fmaf(coef, v.z, acc.z);
+    acc.w = fmaf(coef, v.w, acc.w);
+  }
+  return acc;
+}
+
+// the model / graph shapes these kernels take (hcg_explain's HCG_ERR_UNSUPPORTED)
 inline int x_shapes_ok(const hcg_explain_args* p) {
   return p->D == XD && p->F >= 1 && p->F <= XD && p->C >= 1 && p->C <= 8 && p->n_conv >= 1 && p->n_conv <= HCG_EXPLAIN_MAX_CONVS &&
          p->R >= 1 && p->R <= HCG_HEAD_MAX_LAYERS && p->max_nodes >= 0 && p->max_nodes <= X_MAX_NODES && p->max_edges >= 0 &&

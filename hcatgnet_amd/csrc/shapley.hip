@@ -1,0 +1,421 @@
+// Shapley value sampling (Captum's ShapleyValueSampling with baselines 0 and one feature per step, as the reference uses it
+// through torch_geometric.explain.Explainer on GCN_explain: scripts_experiments/explain_gnn.py) for a BATCH of graphs.
+//
+// The features of a graph are its n F node-feature entries and its e directed edges (the header states the indexing).  One
+// permutation of them costs one masked forward per feature; the graph and the model are the same for all of them.  So the grid
+// runs over (graph, permutation): one workgroup of 8 waves builds its graph once, keeps it in LDS and walks its permutation on
+// chip -- switch a feature on, evaluate, record the difference -- with no launch and no HBM round trip between evaluations.
+// Workgroups never depend on each other, nothing is reduced across them, no float atomics: every sum has one owner and a fixed
+// order, so the differences of (graph, permutation) are bitwise the same run to run and whatever else shares the launch.
+// Per workgroup:
+//   build     once: gcn_norm on chip from the raw COO edges (rules: graph_csr.h) -- in-degree, dinv from the UNMASKED
+//             in-degree, the by-destination entry list ((source << 16) | local edge, rows sorted).  Forward only: no
+//             by-source list, no workspace of activations.  mval[e] = 0 (off) for an edge with an entry, -1 for one without
+//             (an explicit (i, i) edge is part of the unit self loop; an ungrouped edge is ignored): switching such an edge on
+//             changes nothing.
+//   state     h1 = x~ W1^T [n][64], starting at 0 (everything off).  A node entry (i, f) switched on is the rank-1 update
+//             h1[i, :] += x[i, f] W1[:, f] (64 FMAs by one wave); an edge switched on sets mval[e] = 1 and touches no row of
+//             h1.  Layer 1's GEMM is therefore never recomputed.
+//   evaluate  A1 = leaky(dinv_i (dinv_i h1_i + sum_k m_k dinv_c h1_c) + b1) (h1 -> t0);  per further layer  H = A_prev W^T
+//             (t0 -> t1: explain_tile.h x_gemm, the lane's weight row in 64 registers) and the same aggregation (t1 -> t0);
+//             [max, mean] pooling;  readout of depth R;  v = out[class_index].
+//   walk      the permutation is read a chunk of 256 steps at a time: every thread classifies one step -- a node entry whose x
+//             is exactly 0, an edge without an entry or an index outside the graph cannot change the output, its difference
+//             (exactly 0) is written at once and no evaluation is spent on it -- the others go through LDS to the serial walk.
+// What is the same for every evaluation of a workgroup stays in registers where it fits: the second conv layer's weight row
+// (models of two conv layers, the reference's: 64 registers; deeper stacks reload the row per layer from L2) and the first
+// readout layer's weights (16 registers per thread).
+// LDS holds three [npad][64 + 4] f32 tiles (h1, t0, t1; the pooling partials alias t1), the entry list and mask values and
+// ~5 KB of structure, sized at launch from the batch's largest graph: 160 KB less 208 bytes at this mode's limit of 184 nodes
+// and 1024 directed edges (the reference's largest graph has 184 atoms).
+// The differences go to the caller's workspace, one row per permutation of the launch; k_shapley_reduce then adds the rows onto
+// the accumulator, p ascending, continuing from what earlier launches left: the mean over all permutations is one fixed-order
+// sum however the permutations are split into launches.
+#include "common.h"
+#include "graph_csr.h"
+#include "explain_tile.h"
+
+namespace {
+
+constexpr int S_MAX_NODES = 184;
+constexpr int S_CHUNK = 256;           // walk steps classified at a time
+constexpr int S_NPAD_MIN = 16;         // (the pooling partials, XW * 128 floats, alias t1)
+
+struct SArgs {     // the kernel's argument block (device pointers by value)
+  const float* x;
+  const int64_t* ei;
+  const int32_t* graph_ptr;
+  const int32_t* edge_ptr;
+  const int32_t* perm;                      // [P][row]
+  const float* cW[HCG_EXPLAIN_MAX_CONVS];
+  const float* cb[HCG_EXPLAIN_MAX_CONVS];
+  const float* hW[HCG_HEAD_MAX_LAYERS];
+  const float* hb[HCG_HEAD_MAX_LAYERS];
+  float* out;                               // [B][C] everything on
+  float* out_base;                          // [B][C] everything off
+  float* ws;                                // [count][row] the differences of this launch's permutations
+  int32_t* status;
+  long long E;                              // edges the edge loads may index (>= 1)
+  long long NF, Etot, row;                  // N F, E, N F + E
+  int F, C, n_conv, R, npad, emax, max_nodes, max_edges, first, cls;
+  float slope;
+};
+
+struct SLds {
+  float* h1;            // [npad][XS]  x~ W1^T of the features switched on so far
+  float* t0;            // [npad][XS]
+  float* t1;            // [npad][XS]  (pooling partials: its first XW * 128 floats)
+  unsigned* ent;        // [emax]  by destination: (source << 16) | local edge
+  float* mval;          // [emax]  1 on, 0 off, -1 no entry
+  int* rowptr;          // [npad + 4]
+  int* cnt;             // [npad]  in-degree, then the fill cursor
+  float* dinv;          // [npad]
+  float* hv;            // [X_HEAD] readout activations: emb | v1 | v2 | ... | out
+  int* pj;              // [S_CHUNK] the chunk's steps: local feature index, -1 = nothing to evaluate
+  float* pv;            // [S_CHUNK] the x value of a node entry
+};
+
+__host__ __device__ inline unsigned s_lds_bytes(int npad, int emax) {
+  return 3u * npad * XS * 4 + 2u * emax * 4 + (unsigned)(npad + 4) * 4 + 2u * npad * 4 + X_HEAD * 4 + 2 * S_CHUNK * 4;
+}
+
+// (integer offsets, as mid.hip's carve: the arrays must stay LDS pointers for the compiler)
+__device__ __forceinline__ SLds s_carve(char* base, int npad, int emax) {
+  SLds L;
+  unsigned off = 0;
+  L.h1 = reinterpret_cast<float*>(base + off); off += (unsigned)npad * XS * 4;
+  L.t0 = reinterpret_cast<float*>(base + off); off += (unsigned)npad * XS * 4;
+  L.t1 = reinterpret_cast<float*>(base + off); off += (unsigned)npad * XS * 4;
+  L.ent = reinterpret_cast<unsigned*>(base + off); off += (unsigned)emax * 4;
+  L.mval = reinterpret_cast<float*>(base + off); off += (unsigned)emax * 4;
+  L.rowptr = reinterpret_cast<int*>(base + off); off += (unsigned)(npad + 4) * 4;
+  L.cnt = reinterpret_cast<int*>(base + off); off += (unsigned)npad * 4;
+  L.dinv = reinterpret_cast<float*>(base + off); off += (unsigned)npad * 4;
+  L.hv = reinterpret_cast<float*>(base + off); off += X_HEAD * 4;
+  L.pj = reinterpret_cast<int*>(base + off); off += S_CHUNK * 4;
+  L.pv = reinterpret_cast<float*>(base + off);
+  return L;
+}
+
+__device__ __forceinline__ float s_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+__global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const SLds L = s_carve(smem, a.npad, a.emax);
+  float* const red = L.t1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x;
+  const int F = a.F, C = a.C, R = a.R, n_conv = a.n_conv;
+  const float slope = a.slope;
+  const bool p0 = a.first + (int)blockIdx.y == 0;          // permutation 0 of the whole call writes out / out_base
+  float* const wsrow = a.ws + (size_t)blockIdx.y * (size_t)a.row;
+
+  const int nbase = __builtin_amdgcn_readfirstlane(a.graph_ptr[g]), ebase = __builtin_amdgcn_readfirstlane(a.edge_ptr[g]);
+  const int n_raw = a.graph_ptr[g + 1] - nbase, ne_raw = a.edge_ptr[g + 1] - ebase;
+  int n = n_raw, ne = ne_raw;
+  graph_refuse(n, ne, a.max_nodes, a.max_edges, tid, a.status);
+  if (n != n_raw || ne != ne_raw) {
+    // refused (HCG_STATUS_SHAPE_LIMIT): the graph's rows are zero -- over whatever part of its ranges lies inside the arrays
+    if (p0)
+      for (int c = tid; c < C; c += XT) { a.out[(size_t)g * C + c] = 0.f; a.out_base[(size_t)g * C + c] = 0.f; }
+    for (long long e = tid; e < ne_raw; e += XT) {
+      const long long p = (long long)ebase + e;
+      if (p >= 0 && p < a.Etot) wsrow[a.NF + p] = 0.f;
+    }
+    for (long long i = tid; i < (long long)n_raw * F; i += XT) {
+      const long long p = (long long)nbase * F + i;
+      if (p >= 0 && p < a.NF) wsrow[p] = 0.f;
+    }
+    return;
+  }
+
+  // ---------------------------------------------------------------------------------------------- build (once per workgroup)
+  XGraph gi{ebase, ne};
+  EdgeRegs<X_EPT, XT> er;
+  er.load(gi, a.ei, a.E, tid);
+  for (int i = tid; i < a.npad; i += XT) L.cnt[i] = 0;
+  for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;       // everything off
+  int es[X_EPT], ed[X_EPT];
+  bool live[X_EPT];
+#pragma unroll
+  for (int j = 0; j < X_EPT; ++j) {
+    const int e = tid + j * XT;
+    const long long s = er.s[j] - nbase, d = er.d[j] - nbase;
+    const bool in = e < ne;
+    const bool ok = s >= 0 && s < n && d >= 0 && d < n;
+    if (in && !ok) atomicOr(a.status, HCG_STATUS_EDGE_UNGROUPED);      // (such edges are ignored)
+    es[j] = (int)s;
+    ed[j] = (int)d;
+    live[j] = in && ok && s != d;                                      // an explicit (i, i) edge is the unit self loop
+    if (in) L.mval[e] = live[j] ? 0.f : -1.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < X_EPT; ++j)
+    if (live[j]) atomicAdd(&L.cnt[ed[j]], 1);
+  __syncthreads();
+  if (wave == 0) csr_scan_rows<X_RPL>(L.cnt, L.rowptr, n, lane);
+  for (int i = tid; i < n; i += XT) L.dinv[i] = gcn_dinv(L.cnt[i]);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < X_EPT; ++j)
+    if (live[j]) {
+      const unsigned e = (unsigned)(tid + j * XT);
+      const int pd = L.rowptr[ed[j]] + atomicSub(&L.cnt[ed[j]], 1) - 1;
+      L.ent[pd] = ((unsigned)es[j] << 16) | e;
+    }
+  __syncthreads();
+  if (tid < n) x_sort_row(L.ent, L.rowptr[tid], L.rowptr[tid + 1]);
+  __syncthreads();
+
+  // ---------------------------------------------------------------------------------------------- what every evaluation reuses
+  const int arow = tid >> 4, c4 = tid & 15;               // aggregation: 16 lanes x float4 per row, 32 rows per pass
+  const int ro = tid >> 3, rsub = tid & 7;                // readout: 8 lanes per output
+  float w[XD];                                            // the lane's weight row of a conv layer >= 2
+  if (n_conv == 2) x_weight_row(w, reinterpret_cast<const char*>(a.cW[1]), lane, XD);
+  float rw0[16];                                          // readout layer 0: W[ro][rsub + 8 k]
+  {
+    const int out0 = R == 1 ? C : XD;
+    const float* W = a.hW[0] + (size_t)(ro < out0 ? ro : 0) * (2 * XD) + rsub;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const float v = W[8 * k];
+      rw0[k] = ro < out0 ? v : 0.f;
+    }
+  }
+
+  const int nF = n * F, K = nF + ne;                      // the graph's features
+  const long long seg = (long long)nbase * F + ebase;     // its segment of a permutation row
+  const int32_t* const prow = a.perm + (size_t)(a.first + (int)blockIdx.y) * (size_t)a.row;
+  int knext = 0, nq = 0, qi = 0;
+  bool base = true;
+  float vprev = 0.f;
+  int off = 0;                                            // position of the output row in hv (set by the readout)
+
+#pragma nounroll
+  while (true) {
+    int j = 0;
+    if (!base) {
+      // ------------------------------------------------------------------------------------------ the next step that needs an evaluation
+      bool found = false;
+      while (!found) {
+        if (qi == nq) {
+          if (knext >= K) break;
+          const int cnt = min(S_CHUNK, K - knext);
+          __syncthreads();                                 // (the chunk before has been walked)
+          if (tid < cnt) {
+            long long at = seg + knext + tid;
+            at = at < a.row ? at : a.row - 1;
+            const int jj = prow[at];
+            int code = -1;
+            float xv = 0.f;
+            if (jj >= 0 && jj < nF) {
+              const size_t p = (size_t)nbase * F + jj;
+              xv = a.x[p];
+              if (xv != 0.f) code = jj; else wsrow[p] = 0.f;
+            } else if (jj >= nF && jj < K) {
+              if (L.mval[jj - nF] >= 0.f) code = jj; else wsrow[a.NF + ebase + (jj - nF)] = 0.f;
+            }
+            L.pj[tid] = code;
+            L.pv[tid] = xv;
+          }
+          __syncthreads();
+          knext += cnt;
+          nq = cnt;
+          qi = 0;
+          continue;
+        }
+        j = __builtin_amdgcn_readfirstlane(L.pj[qi]);
+        found = j >= 0;
+        ++qi;
+      }
+      if (!found) break;
+      if (j < nF) {
+        if (wave == 0) {
+          const float xv = s_uniform(L.pv[qi - 1]);
+          const int i = j / F, f = j - i * F;
+          L.h1[i * XS + lane] = fmaf(xv, a.cW[0][lane * F + f], L.h1[i * XS + lane]);
+        }
+      } else if (tid == 0) {
+        L.mval[j - nF] = 1.f;
+      }
+      __syncthreads();
+    }
+
+    // -------------------------------------------------------------------------------------------- evaluate: conv stack
+#pragma nounroll
+    for (int l = 0; l < n_conv; ++l) {
+      if (l > 0) {
+        if (n_conv > 2) x_weight_row(w, reinterpret_cast<const char*>(x_pick(a.cW, l)), lane, XD);
+        x_gemm(L.t0, w, n, wave, [&](int r, float v) { L.t1[r * XS + lane] = v; });
+        __syncthreads();
+      }
+      const float* src = l == 0 ? L.h1 : L.t1;
+      float bb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bb[q] = x_pick(a.cb, l)[4 * c4 + q];
+      for (int row = arow; row < n; row += XT / 16) {
+        const float di = L.dinv[row];
+        const float4 s = x_row_sum(src, L.ent, L.mval, L.dinv, row, L.rowptr[row], L.rowptr[row + 1], c4, di);
+        float4 y = make_float4(fmaf(di, s.x, bb[0]), fmaf(di, s.y, bb[1]), fmaf(di, s.z, bb[2]), fmaf(di, s.w, bb[3]));
+        y = make_float4(hcg_leaky(y.x, slope), hcg_leaky(y.y, slope), hcg_leaky(y.z, slope), hcg_leaky(y.w, slope));
+        *reinterpret_cast<float4*>(L.t0 + row * XS + 4 * c4) = y;
+      }
+      __syncthreads();
+    }
+
+    // -------------------------------------------------------------------------------------------- pooling: t0 = A of the last layer
+    {
+      float mx = -INFINITY, sm = 0.f;
+      for (int r = wave; r < n; r += XW) {
+        const float v = L.t0[r * XS + lane];
+        mx = fmaxf(mx, v);
+        sm += v;
+      }
+      red[wave * 128 + lane] = mx;
+      red[wave * 128 + 64 + lane] = sm;
+    }
+    __syncthreads();
+    if (tid < 64) {
+      float mx = red[tid], sm = red[64 + tid];
+#pragma unroll
+      for (int q = 1; q < XW; ++q) {
+        mx = fmaxf(mx, red[q * 128 + tid]);
+        sm += red[q * 128 + 64 + tid];
+      }
+      L.hv[tid] = n > 0 ? mx : 0.f;
+      L.hv[64 + tid] = n > 0 ? sm / (float)n : 0.f;
+    }
+    __syncthreads();
+
+    // -------------------------------------------------------------------------------------------- readout (8 lanes per output)
+    off = 0;
+    for (int i = 0; i < R; ++i) {
+      const int in_i = (2 * XD) >> i, out_i = i == R - 1 ? C : in_i / 2;
+      float p = 0.f;
+      if (i == 0) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) p = fmaf(rw0[k], L.hv[rsub + 8 * k], p);
+      } else if (ro < out_i) {
+        const float* W = x_pick(a.hW, i) + (size_t)ro * in_i;
+        for (int k = rsub; k < in_i; k += 8) p = fmaf(W[k], L.hv[off + k], p);
+      }
+      p += __shfl_xor(p, 1, 8);
+      p += __shfl_xor(p, 2, 8);
+      p += __shfl_xor(p, 4, 8);
+      if (ro < out_i && rsub == 0) {
+        const float y = p + x_pick(a.hb, i)[ro];
+        L.hv[off + in_i + ro] = i == R - 1 ? y : hcg_leaky(y, slope);
+      }
+      off += in_i;
+      __syncthreads();
+    }
+    const float v = L.hv[off + a.cls];
+    if (base) {
+      if (p0 && tid < C) a.out_base[(size_t)g * C + tid] = L.hv[off + tid];
+    } else if (tid == 0) {
+      wsrow[j < nF ? (size_t)nbase * F + j : (size_t)(a.NF + ebase + (j - nF))] = v - vprev;
+    }
+    vprev = v;
+    base = false;
+    // (hv is next written behind the barriers of the next evaluation's conv stack)
+  }
+  // hv still holds the last evaluation: everything on (features that were skipped change nothing)
+  if (p0 && tid < C) a.out[(size_t)g * C + tid] = L.hv[off + tid];
+}
+
+// acc[i] (+)= sum_p ws[p][i], p ascending; the call that ends at the last permutation divides by their number
+__global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict__ ws, float* __restrict__ acc, long long row,
+                                                        int count, int fresh, int last, float n_perm) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= row) return;
+  float s = fresh ? 0.f : acc[i];
+  for (int p = 0; p < count; ++p) s += ws[(size_t)p * (size_t)row + i];
+  acc[i] = last ? s / n_perm : s;
+}
+
+hipError_t shapley_allow_big_lds() {   // dynamic LDS above 64 KB: allowed once per process (not per launch: it may be under capture)
+  static hipError_t st = hipFuncSetAttribute((const void*)k_shapley_walk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return st;
+}
+
+inline int s_npad(long long max_nodes) {
+  const long long r = (max_nodes + 3) / 4 * 4;
+  return (int)(r > S_NPAD_MIN ? r : S_NPAD_MIN);
+}
+inline int s_emax(long long max_edges) {
+  const long long r = (max_edges + 3) / 4 * 4;
+  return (int)(r > 4 ? r : 4);
+}
+
+}  // namespace
+
+// hcg_explain, mode HCG_EXPLAIN_SHAPLEY (explain.hip dispatches here)
+int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->edge_mask || p->node_mask || p->target || p->dout) return HCG_ERR_INVALID_ARG;
+  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  const long long NF = (long long)p->N * p->F, row = NF + p->E;
+  const int count = p->perm_count > 0 ? p->perm_count : 1;
+  if (row >= (1ll << 31) || count > 65535) return HCG_ERR_UNSUPPORTED;
+  const int npad = s_npad(p->max_nodes), emax = s_emax(p->max_edges);
+  const unsigned lds = s_lds_bytes(npad, emax);
+  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
+  p->lds_bytes = (int32_t)lds;
+  // one row of differences per permutation of this call
+  p->workspace_bytes_needed = hcg_align_up((size_t)count * (size_t)(row > 0 ? row : 1) * sizeof(float), 256);
+  if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
+  if (p->n_perm < 1 || p->perm_count < 1 || p->perm_first < 0 || (long long)p->perm_first + p->perm_count > p->n_perm ||
+      p->class_index < 0 || p->class_index >= p->C)
+    return HCG_ERR_INVALID_ARG;
+  if (p->B == 0) return HCG_OK;
+  if (!p->graph_ptr || !p->edge_ptr || !p->out || !p->out_base || !p->status || (p->N > 0 && !p->x) || (p->E > 0 && !p->edge_index) ||
+      (row > 0 && (!p->perm || !p->shap_acc)))
+    return HCG_ERR_INVALID_ARG;
+  for (int l = 0; l < p->n_conv; ++l)
+    if (!p->conv_W[l] || !p->conv_b[l]) return HCG_ERR_INVALID_ARG;
+  for (int i = 0; i < p->R; ++i)
+    if (!p->head_W[i] || !p->head_b[i]) return HCG_ERR_INVALID_ARG;
+  if (row > 0 && (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed)) return HCG_ERR_WORKSPACE;
+
+  SArgs a;
+  a.x = p->x;
+  a.ei = p->edge_index;
+  a.E = p->E;
+  if (p->E == 0) { a.ei = reinterpret_cast<const int64_t*>(p->graph_ptr); a.E = 1; }   // readable dummy; no graph has edges
+  a.graph_ptr = p->graph_ptr;
+  a.edge_ptr = p->edge_ptr;
+  a.perm = p->perm;
+  for (int l = 0; l < HCG_EXPLAIN_MAX_CONVS; ++l) { a.cW[l] = p->conv_W[l]; a.cb[l] = p->conv_b[l]; }
+  for (int i = 0; i < HCG_HEAD_MAX_LAYERS; ++i) { a.hW[i] = p->head_W[i]; a.hb[i] = p->head_b[i]; }
+  a.out = p->out;
+  a.out_base = p->out_base;
+  a.ws = (float*)p->workspace;
+  a.status = p->status;
+  a.NF = NF;
+  a.Etot = p->E;
+  a.row = row;
+  a.F = (int)p->F;
+  a.C = (int)p->C;
+  a.n_conv = p->n_conv;
+  a.R = p->R;
+  a.npad = npad;
+  a.emax = emax;
+  a.max_nodes = (int)p->max_nodes;
+  a.max_edges = (int)p->max_edges;
+  a.first = p->perm_first;
+  a.cls = p->class_index;
+  a.slope = p->slope;
+  if (lds > 64 * 1024) {
+    const hipError_t e = shapley_allow_big_lds();
+    if (e != hipSuccess) return hcg_hip_err(e);
+  }
+  hipLaunchKernelGGL(k_shapley_walk, dim3((unsigned)p->B, (unsigned)p->perm_count), dim3(XT), lds, stream, a);
+  HCG_CHECK_LAUNCH();
+  if (row > 0) {
+    hipLaunchKernelGGL(k_shapley_reduce, dim3((unsigned)hcg_cdiv(row, 256)), dim3(256), 0, stream, (const float*)p->workspace,
+                       p->shap_acc, row, p->perm_count, p->perm_first == 0 ? 1 : 0,
+                       p->perm_first + p->perm_count == p->n_perm ? 1 : 0, (float)p->n_perm);
+    HCG_CHECK_LAUNCH();
+  }
+  return HCG_OK;
+}

@@ -132,7 +132,7 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
                       int64_t N, int64_t E, int64_t F, int64_t D,
                       void* workspace, size_t workspace_bytes, hcg_stream_t stream);
 
-/* ---- explain mode (f4): ONE entry point, three jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
+/* ---- explain mode (f4): ONE entry point, four jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
  * PyG's Explainer multiplies every message by an edge mask inside each MessagePassing layer, AFTER gcn_norm, self loops keep 1
  * (reference scripts_experiments/explain_gnn.py:39-50: edge_mask_type='object'); the node mask multiplies x.
  *
@@ -168,15 +168,34 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   outputs and the workspace are not used (workspace_bytes_needed = 0).  Shapes and refusals as HCG_EXPLAIN_GRAPHS, plus
  *   1 <= n_models and 1 <= models_per_group <= n_models; a refused graph's rows of out / emb are zero for every model.  The
  *   result for (model, graph) is bitwise independent of n_models, of models_per_group and of the rest of the batch.
- *   HCG_EXPLAIN_QUERY as above. */
+ *   HCG_EXPLAIN_QUERY as above.
+ * HCG_EXPLAIN_SHAPLEY: Shapley value sampling (Captum's ShapleyValueSampling, baselines 0, one feature per step) of ONE frozen
+ *   model for a batch of graphs, forward only (csrc/shapley.hip; reference scripts_experiments/explain_gnn.py).  Graph g with n
+ *   nodes and e directed edges has K = n F + e features: local index j < n F is node-feature entry (j / F, j % F), j >= n F is
+ *   local edge j - n F (the caller's edge order).  Off = the entry of x replaced by 0 / the edge's mask 0 (mask semantics of
+ *   HCG_EXPLAIN_GRAPHS without sigmoid: after gcn_norm, every conv layer, dinv from the unmasked in-degree, self loops keep 1).
+ *   `perm` [n_perm][N F + E] int32: row p holds, for every graph g at offset graph_ptr[g] F + edge_ptr[g], a permutation of
+ *   0 .. K_g - 1 (contents are trusted; an index outside [0, K_g) is skipped).  One workgroup per (graph, permutation) keeps the
+ *   graph in LDS and walks its permutation on chip: v_0 = out[class_index] with everything off, v_k with perm_1 .. perm_k on,
+ *   phi_p[perm_k] = v_k - v_(k-1).  A node entry whose x is exactly 0 and an explicit (i, i) edge cannot change the output:
+ *   their difference is exactly 0 and no evaluation is spent on them.  A call runs the permutations perm_first ..
+ *   perm_first + perm_count - 1 into `workspace` ([perm_count][N F + E] f32 rows, workspace_bytes_needed) and then adds the
+ *   rows, p ascending, onto shap_acc [N F + E] (node entries [N, F] first, then the E edges; a call with perm_first = 0 starts
+ *   from 0, the call that ends at n_perm divides by n_perm): the mean over n_perm permutations in the fixed order 0, 1, ..,
+ *   bitwise independent of how the permutations are split into calls.  out [B, C] = the output with everything on and
+ *   out_base [B, C] = with everything off, both written by permutation 0's workgroups.  edge_mask, node_mask, target and dout
+ *   must be NULL (HCG_ERR_INVALID_ARG).  Shapes: as HCG_EXPLAIN_GRAPHS but graphs of <= 184 nodes (three [n][64] tiles are kept
+ *   in LDS) and perm_count <= 65535; refusals as there (HCG_STATUS_SHAPE_LIMIT: the graph's rows of every output zero).
+ *   HCG_EXPLAIN_QUERY as above (reads perm_count too). */
 #define HCG_EXPLAIN_GRAPHS 0
 #define HCG_EXPLAIN_LAYER_EDGE_GRAD 1
 #define HCG_EXPLAIN_ENSEMBLE 2
+#define HCG_EXPLAIN_SHAPLEY 3
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / HCG_EXPLAIN_LAYER_EDGE_GRAD / HCG_EXPLAIN_ENSEMBLE */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -214,6 +233,15 @@ typedef struct hcg_explain_args {
   float* emb;                            /* HCG_EXPLAIN_ENSEMBLE from here on: [M, B, 2D], nullable */
   int32_t n_models;                      /* M */
   int32_t models_per_group;              /* models one workgroup runs on its graph, 1 .. M */
+  const int32_t* perm;                   /* HCG_EXPLAIN_SHAPLEY from here on: [n_perm][N F + E] */
+  float* out_base;                       /* [B, C] */
+  float* shap_acc;                       /* [N F + E]: running sum, the mean after the last call */
+  int32_t n_perm;                        /* P */
+  int32_t perm_first;                    /* first permutation of this call */
+  int32_t perm_count;                    /* permutations of this call */
+  int32_t class_index;                   /* the explained output column, 0 .. C - 1 */
+  int32_t lds_bytes;                     /* OUT: dynamic LDS of one workgroup for max_nodes / max_edges (also by a query) */
+  int32_t reserved;
 } hcg_explain_args;
 int hcg_explain(hcg_explain_args* args_host, hcg_stream_t stream);
 
