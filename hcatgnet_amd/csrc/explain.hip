@@ -20,6 +20,8 @@
 // graph; 149 KB at the 224 / 1024 limit).  The weights (16 KB per layer, the same for every workgroup) are read from global
 // memory / L2 into registers.  H_l and A_l of every layer, which the backward reads again, go to the caller's workspace
 // ([2 n_conv][N][64] f32, each graph's rows written and read by its own workgroup only).
+// The build and the forward are the pieces of explain_tile.h, shared with ensemble.hip and shapley.hip (here: both row
+// lists in one build, the packed entry word, the workspace store as the aggregation's extra); the backward is this file's.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -27,28 +29,18 @@
 namespace {
 
 struct XArgs {     // the kernel's argument block (device pointers by value)
-  const float* x;
-  const int64_t* ei;
-  const int32_t* graph_ptr;
-  const int32_t* edge_ptr;
+  XCommon c;
   const float* edge_mask;
   const float* node_mask;
   const float* target;
   const float* dout;
-  const float* cW[HCG_EXPLAIN_MAX_CONVS];
-  const float* cb[HCG_EXPLAIN_MAX_CONVS];
-  const float* hW[HCG_HEAD_MAX_LAYERS];
-  const float* hb[HCG_HEAD_MAX_LAYERS];
   float* out;
   float* loss;
   float* d_edge_mask;
   float* d_node_mask;
   float* dx;
-  int32_t* status;
   float* ws;
-  long long E;
-  int N, F, C, n_conv, R, npad, emax, max_nodes, max_edges, sigmoid;
-  float slope;
+  int N, sigmoid;
 };
 
 struct XLds {
@@ -97,26 +89,25 @@ __device__ __forceinline__ float x_sigmoid(float v) { return 1.0f / (1.0f + expf
 
 __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const XLds L = x_carve(smem, a.npad, a.emax);
+  const XCommon& cm = a.c;
+  const XLds L = x_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x;
-  const int F = a.F, C = a.C, R = a.R, n_conv = a.n_conv;
-  const float slope = a.slope;
+  const int F = cm.F, C = cm.C, n_conv = cm.n_conv;
+  const float slope = cm.slope;
   const bool bwd = a.target != nullptr || a.dout != nullptr;
   const bool need_dx = a.d_node_mask != nullptr || a.dx != nullptr;
 
-  const int nbase = __builtin_amdgcn_readfirstlane(a.graph_ptr[g]), ebase = __builtin_amdgcn_readfirstlane(a.edge_ptr[g]);
-  const int n_raw = a.graph_ptr[g + 1] - nbase, ne_raw = a.edge_ptr[g + 1] - ebase;
-  int n = n_raw, ne = ne_raw;
-  graph_refuse(n, ne, a.max_nodes, a.max_edges, tid, a.status);
-  if (n != n_raw || ne != ne_raw) {
-    // refused (HCG_STATUS_SHAPE_LIMIT): the graph's outputs are zero -- over whatever part of its ranges lies inside the arrays
-    for (int c = tid; c < C; c += XT) a.out[(size_t)g * C + c] = 0.f;
+  XSpan sp;
+  if (x_refused(sp, cm, g, tid)) {
+    // the graph's outputs are zero -- over whatever part of its ranges lies inside the arrays
+    const int nbase = sp.nbase, ebase = sp.ebase, n_raw = sp.n_raw, ne_raw = sp.ne_raw;
+    for (int k = tid; k < C; k += XT) a.out[(size_t)g * C + k] = 0.f;
     if (a.loss && tid == 0) a.loss[g] = 0.f;
     if (bwd) {
       for (long long e = tid; e < ne_raw; e += XT) {
         const long long p = (long long)ebase + e;
-        if (p >= 0 && p < a.E) a.d_edge_mask[p] = 0.f;
+        if (p >= 0 && p < cm.E) a.d_edge_mask[p] = 0.f;
       }
       for (long long i = tid; i < (long long)n_raw * F; i += XT) {
         const long long p = (long long)nbase * F + i;
@@ -130,10 +121,10 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   }
 
   // ---------------------------------------------------------------------------------------------- build
-  XGraph gi{ebase, ne};
+  const int nbase = sp.nbase, ebase = sp.ebase, n = sp.n, ne = sp.ne;
   EdgeRegs<X_EPT, XT> er;
-  er.load(gi, a.ei, a.E, tid);
-  for (int i = tid; i < a.npad; i += XT) { L.cnt_d[i] = 0; L.cnt_s[i] = 0; }
+  er.load(XGraph{sp.ebase, sp.ne}, cm.ei, cm.E, tid);
+  for (int i = tid; i < cm.npad; i += XT) { L.cnt_d[i] = 0; L.cnt_s[i] = 0; }
   for (int e = tid; e < ne; e += XT) {
     const float v = a.edge_mask[(size_t)ebase + e];
     L.mval[e] = a.sigmoid ? x_sigmoid(v) : v;
@@ -145,7 +136,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
     float v = 0.f;
     if (k < F) {
       const size_t p = (size_t)(nbase + r) * F + k;
-      v = a.x[p];
+      v = cm.x[p];
       if (a.node_mask) {
         const float m = a.node_mask[p];
         v *= a.sigmoid ? x_sigmoid(m) : m;
@@ -153,45 +144,14 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
     }
     L.t0[r * XS + k] = v;
   }
-  int es[X_EPT], ed[X_EPT];
-  bool live[X_EPT];
-#pragma unroll
-  for (int j = 0; j < X_EPT; ++j) {
-    const int e = tid + j * XT;
-    const long long s = er.s[j] - nbase, d = er.d[j] - nbase;
-    const bool in = e < ne;
-    const bool ok = s >= 0 && s < n && d >= 0 && d < n;
-    if (in && !ok) atomicOr(a.status, HCG_STATUS_EDGE_UNGROUPED);      // (such edges are ignored)
-    es[j] = (int)s;
-    ed[j] = (int)d;
-    live[j] = in && ok && s != d;                                      // an explicit (i, i) edge is the unit self loop
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < X_EPT; ++j)
-    if (live[j]) { atomicAdd(&L.cnt_d[ed[j]], 1); atomicAdd(&L.cnt_s[es[j]], 1); }
-  __syncthreads();
-  if (wave == 0) csr_scan_rows<X_RPL>(L.cnt_d, L.rowptr_d, n, lane);
-  else if (wave == 1) csr_scan_rows<X_RPL>(L.cnt_s, L.rowptr_s, n, lane);
-  for (int i = tid; i < n; i += XT) L.dinv[i] = gcn_dinv(L.cnt_d[i]);
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < X_EPT; ++j)
-    if (live[j]) {
-      const unsigned e = (unsigned)(tid + j * XT);
-      const int pd = L.rowptr_d[ed[j]] + atomicSub(&L.cnt_d[ed[j]], 1) - 1;
-      L.ent_d[pd] = ((unsigned)es[j] << 16) | e;
-      const int ps = L.rowptr_s[es[j]] + atomicSub(&L.cnt_s[es[j]], 1) - 1;
-      L.ent_s[ps] = ((unsigned)ed[j] << 16) | e;
-    }
-  __syncthreads();
-  if (tid < n) x_sort_row(L.ent_d, L.rowptr_d[tid], L.rowptr_d[tid + 1]);
-  else if (tid >= XT / 2 && tid - XT / 2 < n) x_sort_row(L.ent_s, L.rowptr_s[tid - XT / 2], L.rowptr_s[tid - XT / 2 + 1]);
+  XEdges q;
+  x_edge_pass(q, er, sp, tid, cm.status);
+  const XMasked fmt{L.mval};
+  x_build_rows<XMasked, true>(q, {L.ent_d, L.rowptr_d, L.cnt_d}, {L.ent_s, L.rowptr_s, L.cnt_s}, L.dinv, n, tid);
   __syncthreads();
 
   const size_t plane = (size_t)a.N * XD;                  // one [N][64] tensor of the workspace
   float* const wsg = a.ws + (size_t)nbase * XD;           // this graph's rows of plane 0
-  const int arow = tid >> 4, c4 = tid & 15;               // aggregation: 16 lanes x float4 per row, 32 rows per pass
 
   // ---------------------------------------------------------------------------------------------- forward
 #pragma nounroll
@@ -199,7 +159,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
     const int K = __builtin_amdgcn_readfirstlane(l == 0 ? F : XD);   // (uniform: keeps the weight addressing scalar)
     {
       float w[XD];
-      x_weight_row(w, reinterpret_cast<const char*>(x_pick(a.cW, l)), lane, K);
+      x_weight_row(w, reinterpret_cast<const char*>(x_pick(cm.cW, l)), lane, K);
       float* hws = wsg + (size_t)(2 * l) * plane;
       x_gemm(L.t0, w, n, wave, [&](int r, float v) {
         L.t1[r * XS + lane] = v;
@@ -207,67 +167,16 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
       });
     }
     __syncthreads();
-    {
-      float bb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bb[j] = x_pick(a.cb, l)[4 * c4 + j];
-      float* aws = wsg + (size_t)(2 * l + 1) * plane;
-      for (int row = arow; row < n; row += XT / 16) {
-        const float di = L.dinv[row];
-        const float4 s = x_row_sum(L.t1, L.ent_d, L.mval, L.dinv, row, L.rowptr_d[row], L.rowptr_d[row + 1], c4, di);
-        float4 y = make_float4(fmaf(di, s.x, bb[0]), fmaf(di, s.y, bb[1]), fmaf(di, s.z, bb[2]), fmaf(di, s.w, bb[3]));
-        y = make_float4(hcg_leaky(y.x, slope), hcg_leaky(y.y, slope), hcg_leaky(y.z, slope), hcg_leaky(y.w, slope));
-        *reinterpret_cast<float4*>(L.t0 + row * XS + 4 * c4) = y;
-        if (bwd && l + 1 < n_conv) *reinterpret_cast<float4*>(aws + (size_t)row * XD + 4 * c4) = y;
-      }
-    }
+    float* aws = wsg + (size_t)(2 * l + 1) * plane;
+    x_conv_out(L.t1, L.t0, L.ent_d, L.rowptr_d, fmt, L.dinv, x_pick(cm.cb, l), n, tid, slope, [&](int row, int c4, float4 y) {
+      if (bwd && l + 1 < n_conv) *reinterpret_cast<float4*>(aws + (size_t)row * XD + 4 * c4) = y;
+    });
     __syncthreads();
   }
 
-  // ---------------------------------------------------------------------------------------------- pooling: t0 = A of the last layer
-  {
-    float mx = -INFINITY, sm = 0.f;
-    for (int r = wave; r < n; r += XW) {
-      const float v = L.t0[r * XS + lane];
-      mx = fmaxf(mx, v);
-      sm += v;
-    }
-    L.red[wave * 128 + lane] = mx;
-    L.red[wave * 128 + 64 + lane] = sm;
-  }
-  __syncthreads();
-  if (tid < 64) {
-    float mx = L.red[tid], sm = L.red[64 + tid];
-#pragma unroll
-    for (int w = 1; w < XW; ++w) {
-      mx = fmaxf(mx, L.red[w * 128 + tid]);
-      sm += L.red[w * 128 + 64 + tid];
-    }
-    L.hv[tid] = n > 0 ? mx : 0.f;
-    L.hv[64 + tid] = n > 0 ? sm / (float)n : 0.f;
-  }
-  __syncthreads();
-
-  // ---------------------------------------------------------------------------------------------- readout (8 lanes per output)
-  int off = 0;
-  for (int i = 0; i < R; ++i) {
-    const int in_i = (2 * XD) >> i, out_i = i == R - 1 ? C : in_i / 2;
-    const int o = tid >> 3, sub = tid & 7;
-    float p = 0.f;
-    if (o < out_i) {
-      const float* W = x_pick(a.hW, i) + (size_t)o * in_i;
-      for (int k = sub; k < in_i; k += 8) p = fmaf(W[k], L.hv[off + k], p);
-    }
-    p += __shfl_xor(p, 1, 8);
-    p += __shfl_xor(p, 2, 8);
-    p += __shfl_xor(p, 4, 8);
-    if (o < out_i && sub == 0) {
-      const float y = p + x_pick(a.hb, i)[o];
-      L.hv[off + in_i + o] = i == R - 1 ? y : hcg_leaky(y, slope);
-    }
-    off += in_i;
-    __syncthreads();
-  }
+  // ---------------------------------------------------------------------------------------------- pooling (t0 = A of the last layer), readout
+  x_pool(L.t0, L.red, L.hv, n, tid);
+  int off = x_readout(L.hv, cm, 0, tid);
   // off = position of the output row in hv / hg
   if (tid < C) {
     const float o = L.hv[off + tid];
@@ -286,11 +195,11 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   if (!bwd) return;
 
   // ---------------------------------------------------------------------------------------------- readout backward
-  for (int i = R - 1; i >= 0; --i) {
-    const int in_i = (2 * XD) >> i, out_i = i == R - 1 ? C : in_i / 2;
+  for (int i = cm.R - 1; i >= 0; --i) {
+    const int in_i = (2 * XD) >> i, out_i = i == cm.R - 1 ? C : in_i / 2;
     off -= in_i;                                        // layer i's input vector; its output sits at off + in_i
     if (tid < in_i) {
-      const float* W = x_pick(a.hW, i) + tid;
+      const float* W = x_pick(cm.hW, i) + tid;
       float s = 0.f;
       for (int o = 0; o < out_i; ++o) s = fmaf(W[(size_t)o * in_i], L.hg[off + in_i + o], s);
       if (i > 0) s *= hcg_leaky_grad(L.hv[off + tid], slope);
@@ -337,6 +246,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
     }
     __syncthreads();
     // edge gradient: every by-destination entry owns its edge's slot
+    const int arow = tid >> 4, c4 = tid & 15;             // 16 lanes x float4 per row, 32 rows per pass
     for (int row = arow; row < n; row += XT / 16) {
       const float4 dy = *reinterpret_cast<const float4*>(L.t0 + row * XS + 4 * c4);
       const float di = L.dinv[row];
@@ -358,14 +268,14 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
     // dH = Ahat_m^T dY: rows of the by-source list
     for (int row = arow; row < n; row += XT / 16) {
       const float di = L.dinv[row];
-      const float4 s = x_row_sum(L.t0, L.ent_s, L.mval, L.dinv, row, L.rowptr_s[row], L.rowptr_s[row + 1], c4, di);
+      const float4 s = x_row_sum(L.t0, L.ent_s, fmt, L.dinv, row, L.rowptr_s[row], L.rowptr_s[row + 1], c4, di);
       *reinterpret_cast<float4*>(L.t1 + row * XS + 4 * c4) = make_float4(di * s.x, di * s.y, di * s.z, di * s.w);
     }
     __syncthreads();
     // dA_prev = dH W (lane = input column k), times leaky'(A_prev) for a hidden layer
     {
       float w[XD];
-      const char* Wb = reinterpret_cast<const char*>(x_pick(a.cW, l));
+      const char* Wb = reinterpret_cast<const char*>(x_pick(cm.cW, l));
       const unsigned col = (unsigned)(lane < K ? lane : K - 1);
       unsigned Kv = (unsigned)K;
       asm volatile("" : "+v"(Kv));          // (opaque: the row offsets stay 32-bit vector offsets on the one uniform base)
@@ -401,17 +311,12 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
           const float m = a.node_mask[p];
           s = a.sigmoid ? x_sigmoid(m) : m;
           ds = a.sigmoid ? s * (1.f - s) : 1.f;
-          a.d_node_mask[p] = dxt * a.x[p] * ds;
+          a.d_node_mask[p] = dxt * cm.x[p] * ds;
         }
         if (a.dx) a.dx[p] = dxt * s;
       }
     }
   }
-}
-
-hipError_t explain_allow_big_lds() {   // dynamic LDS above 64 KB: allowed once per process (not per launch: it may be under capture)
-  static hipError_t st = hipFuncSetAttribute((const void*)k_explain_graphs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  return st;
 }
 
 }  // namespace
@@ -434,53 +339,24 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (p->B == 0) return HCG_OK;
   const bool bwd = p->target || p->dout;
   if (p->target && p->dout) return HCG_ERR_INVALID_ARG;
-  if (!p->graph_ptr || !p->edge_ptr || !p->out || !p->status || (p->N > 0 && !p->x) || (p->E > 0 && (!p->edge_index || !p->edge_mask)))
-    return HCG_ERR_INVALID_ARG;
+  if (!x_common_ok(p) || (p->E > 0 && !p->edge_mask)) return HCG_ERR_INVALID_ARG;
   if (bwd && ((p->E > 0 && !p->d_edge_mask) || (p->node_mask && !p->d_node_mask) || (p->target && !p->loss))) return HCG_ERR_INVALID_ARG;
   if (!p->node_mask && p->d_node_mask) return HCG_ERR_INVALID_ARG;
-  for (int l = 0; l < p->n_conv; ++l)
-    if (!p->conv_W[l] || !p->conv_b[l]) return HCG_ERR_INVALID_ARG;
-  for (int i = 0; i < p->R; ++i)
-    if (!p->head_W[i] || !p->head_b[i]) return HCG_ERR_INVALID_ARG;
   if (bwd && (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed)) return HCG_ERR_WORKSPACE;
 
   XArgs a;
-  a.x = p->x;
-  a.ei = p->edge_index;
-  a.E = p->E;
-  if (p->E == 0) { a.ei = reinterpret_cast<const int64_t*>(p->graph_ptr); a.E = 1; }   // readable dummy; no graph has edges
-  a.graph_ptr = p->graph_ptr;
-  a.edge_ptr = p->edge_ptr;
+  x_fill_common(a.c, p);
   a.edge_mask = p->edge_mask;
   a.node_mask = p->node_mask;
   a.target = p->target;
   a.dout = p->dout;
-  for (int l = 0; l < HCG_EXPLAIN_MAX_CONVS; ++l) { a.cW[l] = p->conv_W[l]; a.cb[l] = p->conv_b[l]; }
-  for (int i = 0; i < HCG_HEAD_MAX_LAYERS; ++i) { a.hW[i] = p->head_W[i]; a.hb[i] = p->head_b[i]; }
   a.out = p->out;
   a.loss = p->loss;
   a.d_edge_mask = p->d_edge_mask;
   a.d_node_mask = bwd ? p->d_node_mask : nullptr;
   a.dx = bwd ? p->dx : nullptr;
-  a.status = p->status;
   a.ws = (float*)p->workspace;
   a.N = (int)p->N;
-  a.F = (int)p->F;
-  a.C = (int)p->C;
-  a.n_conv = p->n_conv;
-  a.R = p->R;
-  a.npad = (int)((p->max_nodes + 3) / 4 * 4 > 4 ? (p->max_nodes + 3) / 4 * 4 : 4);
-  a.emax = (int)((p->max_edges + 3) / 4 * 4 > 4 ? (p->max_edges + 3) / 4 * 4 : 4);
-  a.max_nodes = (int)p->max_nodes;
-  a.max_edges = (int)p->max_edges;
   a.sigmoid = (p->flags & HCG_EXPLAIN_SIGMOID) ? 1 : 0;
-  a.slope = p->slope;
-  const unsigned lds = x_lds_bytes(a.npad, a.emax);
-  if (lds > 64 * 1024) {
-    const hipError_t e = explain_allow_big_lds();
-    if (e != hipSuccess) return hcg_hip_err(e);
-  }
-  hipLaunchKernelGGL(k_explain_graphs, dim3((unsigned)p->B), dim3(XT), lds, stream, a);
-  HCG_CHECK_LAUNCH();
-  return HCG_OK;
+  return x_launch<k_explain_graphs>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax), stream, a);
 }

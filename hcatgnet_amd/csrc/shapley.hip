@@ -22,6 +22,8 @@
 //   walk      the permutation is read a chunk of 256 steps at a time: every thread classifies one step -- a node entry whose x
 //             is exactly 0, an edge without an entry or an index outside the graph cannot change the output, its difference
 //             (exactly 0) is written at once and no evaluation is spent on it -- the others go through LDS to the serial walk.
+// Build, aggregation and pooling are explain_tile.h's, shared with explain.hip and ensemble.hip; the readout loop is this
+// file's own (explain_tile.h's header says why).
 // What is the same for every evaluation of a workgroup stays in registers where it fits: the second conv layer's weight row
 // (models of two conv layers, the reference's: 64 registers; deeper stacks reload the row per layer from L2) and the first
 // readout layer's weights (16 registers per thread).
@@ -42,23 +44,13 @@ constexpr int S_CHUNK = 256;           // walk steps classified at a time
 constexpr int S_NPAD_MIN = 16;         // (the pooling partials, XW * 128 floats, alias t1)
 
 struct SArgs {     // the kernel's argument block (device pointers by value)
-  const float* x;
-  const int64_t* ei;
-  const int32_t* graph_ptr;
-  const int32_t* edge_ptr;
+  XCommon c;
   const int32_t* perm;                      // [P][row]
-  const float* cW[HCG_EXPLAIN_MAX_CONVS];
-  const float* cb[HCG_EXPLAIN_MAX_CONVS];
-  const float* hW[HCG_HEAD_MAX_LAYERS];
-  const float* hb[HCG_HEAD_MAX_LAYERS];
   float* out;                               // [B][C] everything on
   float* out_base;                          // [B][C] everything off
   float* ws;                                // [count][row] the differences of this launch's permutations
-  int32_t* status;
-  long long E;                              // edges the edge loads may index (>= 1)
   long long NF, Etot, row;                  // N F, E, N F + E
-  int F, C, n_conv, R, npad, emax, max_nodes, max_edges, first, cls;
-  float slope;
+  int first, cls;
 };
 
 struct SLds {
@@ -101,23 +93,20 @@ __device__ __forceinline__ float s_uniform(float v) { return __int_as_float(__bu
 
 __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const SLds L = s_carve(smem, a.npad, a.emax);
-  float* const red = L.t1;
+  const XCommon& cm = a.c;
+  const SLds L = s_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x;
-  const int F = a.F, C = a.C, R = a.R, n_conv = a.n_conv;
-  const float slope = a.slope;
+  const int F = cm.F, C = cm.C, R = cm.R, n_conv = cm.n_conv;
   const bool p0 = a.first + (int)blockIdx.y == 0;          // permutation 0 of the whole call writes out / out_base
   float* const wsrow = a.ws + (size_t)blockIdx.y * (size_t)a.row;
 
-  const int nbase = __builtin_amdgcn_readfirstlane(a.graph_ptr[g]), ebase = __builtin_amdgcn_readfirstlane(a.edge_ptr[g]);
-  const int n_raw = a.graph_ptr[g + 1] - nbase, ne_raw = a.edge_ptr[g + 1] - ebase;
-  int n = n_raw, ne = ne_raw;
-  graph_refuse(n, ne, a.max_nodes, a.max_edges, tid, a.status);
-  if (n != n_raw || ne != ne_raw) {
-    // refused (HCG_STATUS_SHAPE_LIMIT): the graph's rows are zero -- over whatever part of its ranges lies inside the arrays
+  XSpan sp;
+  if (x_refused(sp, cm, g, tid)) {
+    // the graph's rows are zero -- over whatever part of its ranges lies inside the arrays
+    const int nbase = sp.nbase, ebase = sp.ebase, n_raw = sp.n_raw, ne_raw = sp.ne_raw;
     if (p0)
-      for (int c = tid; c < C; c += XT) { a.out[(size_t)g * C + c] = 0.f; a.out_base[(size_t)g * C + c] = 0.f; }
+      for (int k = tid; k < C; k += XT) { a.out[(size_t)g * C + k] = 0.f; a.out_base[(size_t)g * C + k] = 0.f; }
     for (long long e = tid; e < ne_raw; e += XT) {
       const long long p = (long long)ebase + e;
       if (p >= 0 && p < a.Etot) wsrow[a.NF + p] = 0.f;
@@ -130,53 +119,28 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
   }
 
   // ---------------------------------------------------------------------------------------------- build (once per workgroup)
-  XGraph gi{ebase, ne};
+  const int nbase = sp.nbase, ebase = sp.ebase, n = sp.n, ne = sp.ne;
   EdgeRegs<X_EPT, XT> er;
-  er.load(gi, a.ei, a.E, tid);
-  for (int i = tid; i < a.npad; i += XT) L.cnt[i] = 0;
+  er.load(XGraph{sp.ebase, sp.ne}, cm.ei, cm.E, tid);
+  for (int i = tid; i < cm.npad; i += XT) L.cnt[i] = 0;
   for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;       // everything off
-  int es[X_EPT], ed[X_EPT];
-  bool live[X_EPT];
-#pragma unroll
-  for (int j = 0; j < X_EPT; ++j) {
-    const int e = tid + j * XT;
-    const long long s = er.s[j] - nbase, d = er.d[j] - nbase;
-    const bool in = e < ne;
-    const bool ok = s >= 0 && s < n && d >= 0 && d < n;
-    if (in && !ok) atomicOr(a.status, HCG_STATUS_EDGE_UNGROUPED);      // (such edges are ignored)
-    es[j] = (int)s;
-    ed[j] = (int)d;
-    live[j] = in && ok && s != d;                                      // an explicit (i, i) edge is the unit self loop
-    if (in) L.mval[e] = live[j] ? 0.f : -1.f;
-  }
-  __syncthreads();
+  XEdges q;
+  x_edge_pass(q, er, sp, tid, cm.status);
+  const XMasked fmt{L.mval};
+  x_build_rows<XMasked, false>(q, {L.ent, L.rowptr, L.cnt}, {}, L.dinv, n, tid);
 #pragma unroll
   for (int j = 0; j < X_EPT; ++j)
-    if (live[j]) atomicAdd(&L.cnt[ed[j]], 1);
-  __syncthreads();
-  if (wave == 0) csr_scan_rows<X_RPL>(L.cnt, L.rowptr, n, lane);
-  for (int i = tid; i < n; i += XT) L.dinv[i] = gcn_dinv(L.cnt[i]);
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < X_EPT; ++j)
-    if (live[j]) {
-      const unsigned e = (unsigned)(tid + j * XT);
-      const int pd = L.rowptr[ed[j]] + atomicSub(&L.cnt[ed[j]], 1) - 1;
-      L.ent[pd] = ((unsigned)es[j] << 16) | e;
-    }
-  __syncthreads();
-  if (tid < n) x_sort_row(L.ent, L.rowptr[tid], L.rowptr[tid + 1]);
+    if (tid + j * XT < ne) L.mval[tid + j * XT] = q.live[j] ? 0.f : -1.f;
   __syncthreads();
 
   // ---------------------------------------------------------------------------------------------- what every evaluation reuses
-  const int arow = tid >> 4, c4 = tid & 15;               // aggregation: 16 lanes x float4 per row, 32 rows per pass
   const int ro = tid >> 3, rsub = tid & 7;                // readout: 8 lanes per output
   float w[XD];                                            // the lane's weight row of a conv layer >= 2
-  if (n_conv == 2) x_weight_row(w, reinterpret_cast<const char*>(a.cW[1]), lane, XD);
+  if (n_conv == 2) x_weight_row(w, reinterpret_cast<const char*>(cm.cW[1]), lane, XD);
   float rw0[16];                                          // readout layer 0: W[ro][rsub + 8 k]
   {
     const int out0 = R == 1 ? C : XD;
-    const float* W = a.hW[0] + (size_t)(ro < out0 ? ro : 0) * (2 * XD) + rsub;
+    const float* W = cm.hW[0] + (size_t)(ro < out0 ? ro : 0) * (2 * XD) + rsub;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const float v = W[8 * k];
@@ -211,7 +175,7 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
             float xv = 0.f;
             if (jj >= 0 && jj < nF) {
               const size_t p = (size_t)nbase * F + jj;
-              xv = a.x[p];
+              xv = cm.x[p];
               if (xv != 0.f) code = jj; else wsrow[p] = 0.f;
             } else if (jj >= nF && jj < K) {
               if (L.mval[jj - nF] >= 0.f) code = jj; else wsrow[a.NF + ebase + (jj - nF)] = 0.f;
@@ -234,7 +198,7 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
         if (wave == 0) {
           const float xv = s_uniform(L.pv[qi - 1]);
           const int i = j / F, f = j - i * F;
-          L.h1[i * XS + lane] = fmaf(xv, a.cW[0][lane * F + f], L.h1[i * XS + lane]);
+          L.h1[i * XS + lane] = fmaf(xv, cm.cW[0][lane * F + f], L.h1[i * XS + lane]);
         }
       } else if (tid == 0) {
         L.mval[j - nF] = 1.f;
@@ -246,49 +210,17 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
 #pragma nounroll
     for (int l = 0; l < n_conv; ++l) {
       if (l > 0) {
-        if (n_conv > 2) x_weight_row(w, reinterpret_cast<const char*>(x_pick(a.cW, l)), lane, XD);
+        if (n_conv > 2) x_weight_row(w, reinterpret_cast<const char*>(x_pick(cm.cW, l)), lane, XD);
         x_gemm(L.t0, w, n, wave, [&](int r, float v) { L.t1[r * XS + lane] = v; });
         __syncthreads();
       }
-      const float* src = l == 0 ? L.h1 : L.t1;
-      float bb[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bb[q] = x_pick(a.cb, l)[4 * c4 + q];
-      for (int row = arow; row < n; row += XT / 16) {
-        const float di = L.dinv[row];
-        const float4 s = x_row_sum(src, L.ent, L.mval, L.dinv, row, L.rowptr[row], L.rowptr[row + 1], c4, di);
-        float4 y = make_float4(fmaf(di, s.x, bb[0]), fmaf(di, s.y, bb[1]), fmaf(di, s.z, bb[2]), fmaf(di, s.w, bb[3]));
-        y = make_float4(hcg_leaky(y.x, slope), hcg_leaky(y.y, slope), hcg_leaky(y.z, slope), hcg_leaky(y.w, slope));
-        *reinterpret_cast<float4*>(L.t0 + row * XS + 4 * c4) = y;
-      }
+      x_conv_out(l == 0 ? L.h1 : L.t1, L.t0, L.ent, L.rowptr, fmt, L.dinv, x_pick(cm.cb, l), n, tid, cm.slope,
+                 [](int, int, float4) {});
       __syncthreads();
     }
 
-    // -------------------------------------------------------------------------------------------- pooling: t0 = A of the last layer
-    {
-      float mx = -INFINITY, sm = 0.f;
-      for (int r = wave; r < n; r += XW) {
-        const float v = L.t0[r * XS + lane];
-        mx = fmaxf(mx, v);
-        sm += v;
-      }
-      red[wave * 128 + lane] = mx;
-      red[wave * 128 + 64 + lane] = sm;
-    }
-    __syncthreads();
-    if (tid < 64) {
-      float mx = red[tid], sm = red[64 + tid];
-#pragma unroll
-      for (int q = 1; q < XW; ++q) {
-        mx = fmaxf(mx, red[q * 128 + tid]);
-        sm += red[q * 128 + 64 + tid];
-      }
-      L.hv[tid] = n > 0 ? mx : 0.f;
-      L.hv[64 + tid] = n > 0 ? sm / (float)n : 0.f;
-    }
-    __syncthreads();
-
-    // -------------------------------------------------------------------------------------------- readout (8 lanes per output)
+    // -------------------------------------------------------------------------------------------- pooling (t0 = A of the last layer; the partials alias t1), readout
+    x_pool(L.t0, L.t1, L.hv, n, tid);
     off = 0;
     for (int i = 0; i < R; ++i) {
       const int in_i = (2 * XD) >> i, out_i = i == R - 1 ? C : in_i / 2;
@@ -297,15 +229,15 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) p = fmaf(rw0[k], L.hv[rsub + 8 * k], p);
       } else if (ro < out_i) {
-        const float* W = x_pick(a.hW, i) + (size_t)ro * in_i;
+        const float* W = x_pick(cm.hW, i) + (size_t)ro * in_i;
         for (int k = rsub; k < in_i; k += 8) p = fmaf(W[k], L.hv[off + k], p);
       }
       p += __shfl_xor(p, 1, 8);
       p += __shfl_xor(p, 2, 8);
       p += __shfl_xor(p, 4, 8);
       if (ro < out_i && rsub == 0) {
-        const float y = p + x_pick(a.hb, i)[ro];
-        L.hv[off + in_i + ro] = i == R - 1 ? y : hcg_leaky(y, slope);
+        const float y = p + x_pick(cm.hb, i)[ro];
+        L.hv[off + in_i + ro] = i == R - 1 ? y : hcg_leaky(y, cm.slope);
       }
       off += in_i;
       __syncthreads();
@@ -334,20 +266,6 @@ __global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict_
   acc[i] = last ? s / n_perm : s;
 }
 
-hipError_t shapley_allow_big_lds() {   // dynamic LDS above 64 KB: allowed once per process (not per launch: it may be under capture)
-  static hipError_t st = hipFuncSetAttribute((const void*)k_shapley_walk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  return st;
-}
-
-inline int s_npad(long long max_nodes) {
-  const long long r = (max_nodes + 3) / 4 * 4;
-  return (int)(r > S_NPAD_MIN ? r : S_NPAD_MIN);
-}
-inline int s_emax(long long max_edges) {
-  const long long r = (max_edges + 3) / 4 * 4;
-  return (int)(r > 4 ? r : 4);
-}
-
 }  // namespace
 
 // hcg_explain, mode HCG_EXPLAIN_SHAPLEY (explain.hip dispatches here)
@@ -357,8 +275,7 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   const long long NF = (long long)p->N * p->F, row = NF + p->E;
   const int count = p->perm_count > 0 ? p->perm_count : 1;
   if (row >= (1ll << 31) || count > 65535) return HCG_ERR_UNSUPPORTED;
-  const int npad = s_npad(p->max_nodes), emax = s_emax(p->max_edges);
-  const unsigned lds = s_lds_bytes(npad, emax);
+  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
   if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
   p->lds_bytes = (int32_t)lds;
   // one row of differences per permutation of this call
@@ -368,49 +285,22 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
       p->class_index < 0 || p->class_index >= p->C)
     return HCG_ERR_INVALID_ARG;
   if (p->B == 0) return HCG_OK;
-  if (!p->graph_ptr || !p->edge_ptr || !p->out || !p->out_base || !p->status || (p->N > 0 && !p->x) || (p->E > 0 && !p->edge_index) ||
-      (row > 0 && (!p->perm || !p->shap_acc)))
-    return HCG_ERR_INVALID_ARG;
-  for (int l = 0; l < p->n_conv; ++l)
-    if (!p->conv_W[l] || !p->conv_b[l]) return HCG_ERR_INVALID_ARG;
-  for (int i = 0; i < p->R; ++i)
-    if (!p->head_W[i] || !p->head_b[i]) return HCG_ERR_INVALID_ARG;
+  if (!x_common_ok(p) || !p->out_base || (row > 0 && (!p->perm || !p->shap_acc))) return HCG_ERR_INVALID_ARG;
   if (row > 0 && (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed)) return HCG_ERR_WORKSPACE;
 
   SArgs a;
-  a.x = p->x;
-  a.ei = p->edge_index;
-  a.E = p->E;
-  if (p->E == 0) { a.ei = reinterpret_cast<const int64_t*>(p->graph_ptr); a.E = 1; }   // readable dummy; no graph has edges
-  a.graph_ptr = p->graph_ptr;
-  a.edge_ptr = p->edge_ptr;
+  x_fill_common(a.c, p, S_NPAD_MIN);
   a.perm = p->perm;
-  for (int l = 0; l < HCG_EXPLAIN_MAX_CONVS; ++l) { a.cW[l] = p->conv_W[l]; a.cb[l] = p->conv_b[l]; }
-  for (int i = 0; i < HCG_HEAD_MAX_LAYERS; ++i) { a.hW[i] = p->head_W[i]; a.hb[i] = p->head_b[i]; }
   a.out = p->out;
   a.out_base = p->out_base;
   a.ws = (float*)p->workspace;
-  a.status = p->status;
   a.NF = NF;
   a.Etot = p->E;
   a.row = row;
-  a.F = (int)p->F;
-  a.C = (int)p->C;
-  a.n_conv = p->n_conv;
-  a.R = p->R;
-  a.npad = npad;
-  a.emax = emax;
-  a.max_nodes = (int)p->max_nodes;
-  a.max_edges = (int)p->max_edges;
   a.first = p->perm_first;
   a.cls = p->class_index;
-  a.slope = p->slope;
-  if (lds > 64 * 1024) {
-    const hipError_t e = shapley_allow_big_lds();
-    if (e != hipSuccess) return hcg_hip_err(e);
-  }
-  hipLaunchKernelGGL(k_shapley_walk, dim3((unsigned)p->B, (unsigned)p->perm_count), dim3(XT), lds, stream, a);
-  HCG_CHECK_LAUNCH();
+  const int rc = x_launch<k_shapley_walk>(dim3((unsigned)p->B, (unsigned)p->perm_count), lds, stream, a);
+  if (rc != HCG_OK) return rc;
   if (row > 0) {
     hipLaunchKernelGGL(k_shapley_reduce, dim3((unsigned)hcg_cdiv(row, 256)), dim3(256), 0, stream, (const float*)p->workspace,
                        p->shap_acc, row, p->perm_count, p->perm_first == 0 ? 1 : 0,

@@ -13,9 +13,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _frozen, _lib
 
-_MODEL_ATTRS = ("embedding_dim", "n_node_features", "n_convolutions", "readout_layers", "_n_classes", "conv1", "readout")
 TARGET_WORKGROUPS = 512       # 2 per CU of an MI355X: what the default `models_per_group` keeps when the batch allows it
 MAX_DEFAULT_GROUP = 4         # profiles/ensemble_bench.json: the sweep's best or within 3 % of it in every case; 8 loses 14 %
 
@@ -95,9 +94,9 @@ class EnsemblePredict:
         if not self.models:
             raise ValueError("EnsemblePredict needs at least one model")
         for k, m in enumerate(self.models):
-            if any(not hasattr(m, a) for a in _MODEL_ATTRS):
+            if any(not hasattr(m, a) for a in _frozen.MODEL_ATTRS):
                 raise ValueError(f"model {k} is not a hcatgnet_amd GCN model")
-        sig = [self._signature(m) for m in self.models]
+        sig = [_frozen.model_shape(m) for m in self.models]
         for k, s in enumerate(sig):
             if s != sig[0]:
                 raise ValueError(f"model {k} has (features, embedding_dim, classes, conv layers, readout layers) = {s}, "
@@ -111,10 +110,6 @@ class EnsemblePredict:
         self._cap = None            # (B,) capacity of the buffers
         self._bufs = None
         self._args = _lib.ExplainArgs()
-
-    @staticmethod
-    def _signature(m):
-        return (int(m.n_node_features), int(m.embedding_dim), int(m._n_classes), int(m.n_convolutions), int(m.readout_layers))
 
     @property
     def n_models(self) -> int:
@@ -133,30 +128,13 @@ class EnsemblePredict:
     def _shape_args(self, a, batch) -> Optional[str]:
         if not all(bool(getattr(m, "use_fused", True)) for m in self.models):
             return "fused kernels disabled on a model"
+        why = _frozen.batch_reason(batch, self.F, "models") if batch is not None else None
+        if why is not None:
+            return why
         M = len(self.models)
-        a.mode, a.flags = _lib.HCG_EXPLAIN_ENSEMBLE, _lib.HCG_EXPLAIN_QUERY
-        a.F, a.D, a.C, a.n_conv, a.R = self.F, self.D, self.C, self.n_conv, self.R
-        a.N = a.E = a.B = a.max_nodes = a.max_edges = 0
-        a.n_models = M
-        a.models_per_group = self.models_per_group or 1
-        if batch is not None:
-            mx, me = getattr(batch, "max_nodes", None), getattr(batch, "max_edges", None)
-            if mx is None or me is None or not getattr(batch, "edges_grouped", False):
-                return "batch lacks collate metadata (max_nodes / max_edges / grouped edges)"
-            if getattr(batch, "edge_weight", None) is not None:
-                return "explicit edge weights are outside the ensemble kernel"
-            if batch.x.shape[1] != a.F:
-                return f"batch has {batch.x.shape[1]} node features, the models take {a.F}"
-            a.N, a.E, a.B = int(batch.x.shape[0]), int(batch.edge_index.shape[1]), int(batch.num_graphs)
-            a.max_nodes, a.max_edges = int(mx), int(me)
-            if self.models_per_group is None:
-                a.models_per_group = default_models_per_group(M, a.B)
-        rc = _lib.load().hcg_explain(ctypes.addressof(a), None)
-        if rc == _lib.HCG_ERR_UNSUPPORTED:
-            return ("model / graph shape outside the one-launch ensemble kernel (embedding_dim 64, <= 64 node features, <= 4 conv "
-                    "layers, readout depth <= 4, <= 8 classes, graphs of <= 224 nodes and <= 1024 directed edges)")
-        _lib.check(rc, "hcg_explain (ensemble query)")
-        return None
+        mpg = self.models_per_group or (default_models_per_group(M, int(batch.num_graphs)) if batch is not None else 1)
+        return _frozen.query(a, _lib.HCG_EXPLAIN_ENSEMBLE, (self.F, self.D, self.C, self.n_conv, self.R), batch,
+                             n_models=M, models_per_group=mpg)
 
     def reason(self, batch=None) -> Optional[str]:
         """None when these models (and `batch`) take the one-launch kernel, else why not.  Host metadata only."""
@@ -183,31 +161,20 @@ class EnsemblePredict:
         why = self._shape_args(a, batch)
         if why is not None:
             return self._loop(batch, return_emb, stats)
-        x = batch.x
-        _lib.require_gpu(x, batch.edge_index)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError("batch.x must be contiguous float32")
+        x = _frozen.batch_x(batch)
         B = a.B
         S = self.stacked
-        if any(t.device != x.device for t in S.values()):
-            raise _lib.HcgError("EnsemblePredict: the stacked weights must be on the batch's device (construct the ensemble from "
-                                "models on that device)")
+        _frozen.check_weights(S.values(), x.device, "EnsemblePredict: the stacked weights must be on the batch's device "
+                              "(construct the ensemble from models on that device)")
         plan = self.models[0]._plan_for(batch, x, batch.edge_index, batch.batch, None)
         out, emb, mean, std = self._buffers(B, x.device)
-        cw, cb, hw, hb = weight_names(self.n_conv, self.R)
         p = _lib.ptr
         a.flags = 0
-        a.x, a.edge_index, a.graph_ptr, a.edge_ptr = p(x), p(plan.edge_index), p(plan.graph_ptr), p(plan.edge_ptr)
+        _frozen.fill_graph(a, x, plan)
+        _frozen.fill_weights(a, *([S[n] for n in names] for names in weight_names(self.n_conv, self.R)))
         a.edge_mask = a.node_mask = a.target = a.dout = None
-        for l in range(_lib.HCG_EXPLAIN_MAX_CONVS):
-            a.conv_W[l] = p(S[cw[l]]) if l < self.n_conv else None
-            a.conv_b[l] = p(S[cb[l]]) if l < self.n_conv else None
-        for i in range(_lib.HCG_HEAD_MAX_LAYERS):
-            a.head_W[i] = p(S[hw[i]]) if i < self.R else None
-            a.head_b[i] = p(S[hb[i]]) if i < self.R else None
         a.out, a.emb = p(out), (p(emb) if return_emb else None)
-        a.status = p(plan.status)
-        a.slope = 0.01                      # nn.LeakyReLU() default (reference model/gcn.py:21, :63)
+        a.slope = _frozen.SLOPE
         _lib.check(_lib.load().hcg_explain(ctypes.addressof(a), _lib.stream_ptr()), "hcg_explain (ensemble)")
         self.last_path = "fused"
         if stats:

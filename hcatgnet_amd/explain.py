@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _frozen, _lib
 from .gcn import GCNConv
 
 
@@ -87,31 +87,10 @@ class ExplainStep:
     # ------------------------------------------------------------------ support check (host only, no sync)
     def _shape_args(self, a, batch) -> Optional[str]:
         m = self.model
-        need = ("embedding_dim", "n_node_features", "n_convolutions", "readout_layers", "_n_classes", "conv1", "readout")
-        if any(not hasattr(m, k) for k in need):
-            return "not a hcatgnet_amd GCN model"
-        if not bool(getattr(m, "use_fused", True)):
-            return "fused kernels disabled on the model"
-        a.mode, a.flags = _lib.HCG_EXPLAIN_GRAPHS, _lib.HCG_EXPLAIN_QUERY
-        a.F, a.D, a.C = int(m.n_node_features), int(m.embedding_dim), int(m._n_classes)
-        a.n_conv, a.R = int(m.n_convolutions), int(m.readout_layers)
-        a.N = a.E = a.B = a.max_nodes = a.max_edges = 0
-        if batch is not None:
-            mx, me = getattr(batch, "max_nodes", None), getattr(batch, "max_edges", None)
-            if mx is None or me is None or not getattr(batch, "edges_grouped", False):
-                return "batch lacks collate metadata (max_nodes / max_edges / grouped edges)"
-            if getattr(batch, "edge_weight", None) is not None:
-                return "explicit edge weights cannot be combined with masks"
-            if batch.x.shape[1] != a.F:
-                return f"batch has {batch.x.shape[1]} node features, the model takes {a.F}"
-            a.N, a.E, a.B = int(batch.x.shape[0]), int(batch.edge_index.shape[1]), int(batch.num_graphs)
-            a.max_nodes, a.max_edges = int(mx), int(me)
-        rc = _lib.load().hcg_explain(ctypes.addressof(a), None)
-        if rc == _lib.HCG_ERR_UNSUPPORTED:
-            return ("model / graph shape outside the one-launch explain kernel (embedding_dim 64, <= 64 node features, <= 4 conv "
-                    "layers, readout depth <= 4, <= 8 classes, graphs of <= 224 nodes and <= 1024 directed edges)")
-        _lib.check(rc, "hcg_explain (query)")
-        return None
+        why = _frozen.model_reason(m)
+        if why is None and batch is not None:
+            why = _frozen.batch_reason(batch, int(m.n_node_features), "model")
+        return why or _frozen.query(a, _lib.HCG_EXPLAIN_GRAPHS, _frozen.model_shape(m), batch)
 
     def reason(self, batch=None) -> Optional[str]:
         """None when this model (and `batch`) takes the one-launch kernel, else why not.  Host metadata only."""
@@ -146,10 +125,7 @@ class ExplainStep:
         if why is not None:
             return self._autograd(batch, edge_mask, node_mask, target, dout, want_dx)
         m = self.model
-        x = batch.x
-        _lib.require_gpu(x, batch.edge_index, edge_mask, node_mask, target, dout)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError("batch.x must be contiguous float32")
+        x = _frozen.batch_x(batch, edge_mask, node_mask, target, dout)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         em = self._mask(edge_mask, (E,), "edge_mask")
         nm = self._mask(node_mask, (N, F), "node_mask") if node_mask is not None else None
@@ -158,26 +134,16 @@ class ExplainStep:
         plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
         bwd = tg is not None or do is not None
         bufs = self._buffers(N, E, B, F, C, int(a.workspace_bytes_needed), x.device)
-        convs = [m.conv1] + list(m.conv_layers)
-        lins = [q[0] if isinstance(q, torch.nn.Sequential) else q for q in m.readout]
         p = _lib.ptr
         a.flags = _lib.HCG_EXPLAIN_SIGMOID if self.apply_sigmoid else 0
-        a.x, a.edge_index, a.graph_ptr, a.edge_ptr = p(x), p(plan.edge_index), p(plan.graph_ptr), p(plan.edge_ptr)
+        _frozen.fill_graph(a, x, plan)
+        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ExplainStep"))
         a.edge_mask, a.node_mask, a.target, a.dout = p(em), p(nm), p(tg), p(do)
-        for l in range(_lib.HCG_EXPLAIN_MAX_CONVS):
-            a.conv_W[l] = p(convs[l].lin.weight) if l < len(convs) else None
-            a.conv_b[l] = p(convs[l].bias) if l < len(convs) else None
-        for i in range(_lib.HCG_HEAD_MAX_LAYERS):
-            a.head_W[i] = p(lins[i].weight) if i < len(lins) else None
-            a.head_b[i] = p(lins[i].bias) if i < len(lins) else None
-        for q in [c.lin.weight for c in convs] + [c.bias for c in convs] + [t for li in lins for t in (li.weight, li.bias)]:
-            if q.dtype != torch.float32 or not q.is_contiguous() or q.device != x.device:
-                raise _lib.HcgError("ExplainStep: the model's weights must be contiguous float32 on the batch's device")
         a.out, a.loss, a.d_edge_mask = p(bufs["out"]), p(bufs["loss"]), p(bufs["d_edge"])
         a.d_node_mask = p(bufs["d_node"]) if nm is not None else None
         a.dx = p(bufs["dx"]) if want_dx else None
-        a.status, a.workspace, a.workspace_bytes = p(plan.status), p(bufs["ws"]), bufs["ws"].numel()
-        a.slope = 0.01                      # nn.LeakyReLU() default (reference model/gcn.py:21, :63)
+        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
+        a.slope = _frozen.SLOPE
         _lib.check(_lib.load().hcg_explain(ctypes.addressof(a), _lib.stream_ptr()), "hcg_explain")
         self.last_path = "fused"
         return ExplainResult(bufs["out"][:B], bufs["loss"][:B] if tg is not None else None,

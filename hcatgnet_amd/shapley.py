@@ -20,7 +20,8 @@ from typing import NamedTuple, Optional
 import torch
 import torch.nn.functional as Fn
 
-from . import _lib
+from . import _frozen, _lib
+from ._frozen import SLOPE
 from .explain import ExplainStep
 
 WORKSPACE_CAP_BYTES = 256 << 20    # the per-permutation rows of one launch
@@ -28,7 +29,6 @@ CUS = 256                          # compute units of an MI355X
 LAUNCH_SECONDS = 1.0               # what one launch should stay near (the machines are shared)
 EVAL_SECONDS = 60e-6               # one evaluation at the shape limits: an estimate (default_samples_per_launch)
 MAX_WORKGROUPS_PER_CU = 4
-SLOPE = 0.01                       # nn.LeakyReLU() default (reference model/gcn.py:21, :63)
 
 
 class ShapleyResult(NamedTuple):
@@ -73,7 +73,7 @@ def draw_permutations(batch, F: int, n_samples: int, generator: Optional[torch.G
 def _torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):
     """The model's masked forward in plain torch ops, for CPU tensors (the package's layers are HIP kernels and take GPU
     tensors only).  The loop path uses it when the batch lives on the CPU; nothing on a GPU ever runs it."""
-    convs = [model.conv1] + list(model.conv_layers)
+    convs, lins = _frozen.model_layers(model)
     N = x.shape[0]
     src, dst = edge_index[0], edge_index[1]
     keep = src != dst                                   # an explicit (i, i) edge is part of the unit self loop
@@ -91,11 +91,9 @@ def _torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):
     mx = h.new_zeros(B, h.shape[1]).scatter_reduce(0, idx, h, reduce="amax", include_self=False)
     cnt = torch.bincount(batch_vec, minlength=B).clamp_min(1).to(h.dtype).unsqueeze(1)
     z = torch.cat([mx, h.new_zeros(B, h.shape[1]).index_add(0, batch_vec, h) / cnt], 1)
-    for q in model.readout:
-        if isinstance(q, torch.nn.Sequential):
-            z = Fn.leaky_relu(Fn.linear(z, q[0].weight, q[0].bias), SLOPE)
-        else:
-            z = Fn.linear(z, q.weight, q.bias)
+    for li in lins[:-1]:
+        z = Fn.leaky_relu(Fn.linear(z, li.weight, li.bias), SLOPE)
+    z = Fn.linear(z, lins[-1].weight, lins[-1].bias)
     return z
 
 
@@ -138,35 +136,11 @@ class ShapleySampling:
     # ------------------------------------------------------------------ support check (host only, no sync)
     def _shape_args(self, a, batch, perm_count: int = 1) -> Optional[str]:
         m = self.model
-        need = ("embedding_dim", "n_node_features", "n_convolutions", "readout_layers", "_n_classes", "conv1", "readout")
-        if any(not hasattr(m, k) for k in need):
-            return "not a hcatgnet_amd GCN model"
-        if not bool(getattr(m, "use_fused", True)):
-            return "fused kernels disabled on the model"
-        a.mode, a.flags = _lib.HCG_EXPLAIN_SHAPLEY, _lib.HCG_EXPLAIN_QUERY
-        a.F, a.D, a.C = int(m.n_node_features), int(m.embedding_dim), int(m._n_classes)
-        a.n_conv, a.R = int(m.n_convolutions), int(m.readout_layers)
-        a.N = a.E = a.B = a.max_nodes = a.max_edges = 0
-        a.perm_count = int(perm_count)
-        a.edge_mask = a.node_mask = a.target = a.dout = None
-        if batch is not None:
-            if not batch.x.is_cuda:
-                return "the batch is on the CPU"
-            mx, me = getattr(batch, "max_nodes", None), getattr(batch, "max_edges", None)
-            if mx is None or me is None or not getattr(batch, "edges_grouped", False):
-                return "batch lacks collate metadata (max_nodes / max_edges / grouped edges)"
-            if getattr(batch, "edge_weight", None) is not None:
-                return "explicit edge weights cannot be combined with masks"
-            if batch.x.shape[1] != a.F:
-                return f"batch has {batch.x.shape[1]} node features, the model takes {a.F}"
-            a.N, a.E, a.B = int(batch.x.shape[0]), int(batch.edge_index.shape[1]), int(batch.num_graphs)
-            a.max_nodes, a.max_edges = int(mx), int(me)
-        rc = _lib.load().hcg_explain(ctypes.addressof(a), None)
-        if rc == _lib.HCG_ERR_UNSUPPORTED:
-            return ("model / graph shape outside the on-chip Shapley kernel (embedding_dim 64, <= 64 node features, <= 4 conv "
-                    "layers, readout depth <= 4, <= 8 classes, graphs of <= 184 nodes and <= 1024 directed edges)")
-        _lib.check(rc, "hcg_explain (shapley query)")
-        return None
+        why = _frozen.model_reason(m)
+        if why is None and batch is not None:
+            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, int(m.n_node_features), "model")
+        return why or _frozen.query(a, _lib.HCG_EXPLAIN_SHAPLEY, _frozen.model_shape(m), batch, perm_count=int(perm_count),
+                                    edge_mask=None, node_mask=None, target=None, dout=None)
 
     def reason(self, batch=None) -> Optional[str]:
         """None when this model (and `batch`) takes the on-chip kernel, else why not.  Host metadata only."""
@@ -225,10 +199,7 @@ class ShapleySampling:
         if why is not None:
             return self.loop(batch, n_samples, permutations, generator, class_index)
         m = self.model
-        x = batch.x
-        _lib.require_gpu(x, batch.edge_index)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError("batch.x must be contiguous float32")
+        x = _frozen.batch_x(batch)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         if not 0 <= int(class_index) < C:
             raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
@@ -241,22 +212,12 @@ class ShapleySampling:
         self._shape_args(a, batch, spl)                     # the workspace of a launch of `spl` permutations
         plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
         bufs = self._buffers(row, B, C, int(a.workspace_bytes_needed), x.device)
-        convs = [m.conv1] + list(m.conv_layers)
-        lins = [q[0] if isinstance(q, torch.nn.Sequential) else q for q in m.readout]
-        for q in [c.lin.weight for c in convs] + [c.bias for c in convs] + [t for li in lins for t in (li.weight, li.bias)]:
-            if q.dtype != torch.float32 or not q.is_contiguous() or q.device != x.device:
-                raise _lib.HcgError("ShapleySampling: the model's weights must be contiguous float32 on the batch's device")
         p = _lib.ptr
         a.flags = 0
-        a.x, a.edge_index, a.graph_ptr, a.edge_ptr = p(x), p(plan.edge_index), p(plan.graph_ptr), p(plan.edge_ptr)
-        for l in range(_lib.HCG_EXPLAIN_MAX_CONVS):
-            a.conv_W[l] = p(convs[l].lin.weight) if l < len(convs) else None
-            a.conv_b[l] = p(convs[l].bias) if l < len(convs) else None
-        for i in range(_lib.HCG_HEAD_MAX_LAYERS):
-            a.head_W[i] = p(lins[i].weight) if i < len(lins) else None
-            a.head_b[i] = p(lins[i].bias) if i < len(lins) else None
+        _frozen.fill_graph(a, x, plan)
+        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ShapleySampling"))
         a.out, a.out_base, a.shap_acc, a.perm = p(bufs["out"]), p(bufs["base"]), p(bufs["acc"]), p(perm)
-        a.status, a.workspace, a.workspace_bytes = p(plan.status), p(bufs["ws"]), bufs["ws"].numel()
+        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
         a.slope, a.n_perm, a.class_index = SLOPE, P, int(class_index)
         lib, stream = _lib.load(), _lib.stream_ptr()
         for first in range(0, P, spl):

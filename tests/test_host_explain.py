@@ -104,3 +104,44 @@ def test_explain_step_support_check_is_host_only():
     off = H.make_network("GCN", H.default_options(use_fused=False), 25)
     assert "disabled" in ExplainStep(off).reason()
     assert step.last_path is None
+
+
+_LIMITS = "embedding_dim 64, <= 64 node features, <= 4 conv layers, readout depth <= 4, <= 8 classes, graphs of <= {} nodes and <= 1024 directed edges)"
+_FROZEN = {
+    "explain": dict(make=lambda m: ExplainStep(m), nodes=224, off="fused kernels disabled on the model",
+                    weight="explicit edge weights cannot be combined with masks",
+                    feat="batch has 32 node features, the model takes 25",
+                    limit="model / graph shape outside the one-launch explain kernel (" + _LIMITS.format(224)),
+    "ensemble": dict(make=lambda m: H.ensemble.EnsemblePredict([m]), nodes=224, off="fused kernels disabled on a model",
+                     weight="explicit edge weights are outside the ensemble kernel",
+                     feat="batch has 32 node features, the models take 25",
+                     limit="model / graph shape outside the one-launch ensemble kernel (" + _LIMITS.format(224)),
+    "shapley": dict(make=lambda m: H.shapley.ShapleySampling(m), nodes=184, off="fused kernels disabled on the model",
+                    weight="explicit edge weights cannot be combined with masks",
+                    feat="batch has 32 node features, the model takes 25",
+                    limit="model / graph shape outside the on-chip Shapley kernel (" + _LIMITS.format(184)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_FROZEN))
+def test_frozen_classes_keep_their_own_reason_strings(name):
+    """The three frozen-model classes share one support check (hcatgnet_amd/_frozen.py); each still answers in its own
+    words.  `reason` reads host metadata only, so a stand-in batch serves (its x claims to be on a GPU: ShapleySampling
+    asks that first)."""
+    from types import SimpleNamespace as NS
+    import hcatgnet_amd.ensemble, hcatgnet_amd.shapley  # noqa: F401
+
+    def mk(F=25, **kw):
+        return NS(x=NS(is_cuda=True, shape=(4, F)), edge_index=NS(shape=(2, 0)), num_graphs=1, **kw)
+
+    w = _FROZEN[name]
+    meta = dict(max_nodes=30, max_edges=64, edges_grouped=True)
+    obj = w["make"](H.make_network("GCN", H.default_options(), 25))
+    assert obj.reason() is None and obj.reason(mk(**meta)) is None
+    assert obj.reason(mk(max_nodes=w["nodes"], max_edges=1024, edges_grouped=True)) is None
+    assert obj.reason(mk()) == "batch lacks collate metadata (max_nodes / max_edges / grouped edges)"
+    assert obj.reason(mk(edge_weight=torch.ones(0), **meta)) == w["weight"]
+    assert obj.reason(mk(F=32, **meta)) == w["feat"]
+    assert obj.reason(mk(max_nodes=w["nodes"] + 1, max_edges=64, edges_grouped=True)) == w["limit"]
+    assert w["make"](H.make_network("GCN", H.default_options(use_fused=False), 25)).reason() == w["off"]
+    assert obj.last_path is None
