@@ -24,6 +24,7 @@ HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS, HCG_STRUCT_EXPLAIN_ARGS = 5, 6, 7
 HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY = 0, 1, 2, 3   # modes of hcg_explain
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_ERR_UNSUPPORTED = -3
+HCG_FUSED_FORWARD, HCG_FUSED_BWD_PAIR, HCG_FUSED_PAIR_QUERY = 0, 1, 1      # modes of hcg_fused_forward's block; the pair's flag
 HCG_HEAD_MAX_LAYERS = 4
 HCG_UPDATE_ADAM, HCG_UPDATE_SGD, HCG_UPDATE_RMSPROP = 0, 1, 2      # update rules of hcg_step_tail / hcg_update_dev
 HCG_REDUCE_MAX_JOBS, HCG_REDUCE_MAX_SEGS = 8, 4
@@ -69,7 +70,11 @@ class FusedFwdArgs(ctypes.Structure):
                 ("edge_ptr", P), ("N", I64), ("B", I64), ("F", I64), ("D", I64), ("graphs_per_tile", I32), ("apply_act", I32),
                 ("slope", F32), ("head_flags", I32), ("out1", P), ("out2", P), ("emb", P), ("poolbits", P), ("status", P),
                 ("y", P), ("head_W0", P), ("head_b0", P), ("head_W1", P), ("head_b1", P), ("C", I64), ("z", P), ("out", P),
-                ("demb", P), ("head_workspace", P), ("head_workspace_bytes", SZ), ("step_counter", P)]
+                ("demb", P), ("head_workspace", P), ("head_workspace_bytes", SZ), ("step_counter", P),
+                # mode HCG_FUSED_BWD_PAIR: two conv layers' backward in one launch
+                ("mode", I32), ("pair_flags", I32), ("pair_dx", P), ("pair_dout", P), ("pair_ws_upper", P),
+                ("pair_ws_upper_bytes", SZ), ("pair_ws_lower", P), ("pair_ws_lower_bytes", SZ), ("pair_act_upper", I32),
+                ("pair_act_lower", I32), ("pair_graphs_per_tile_upper", I32), ("pair_reserved", I32)]
 
 
 class HeadArgs(ctypes.Structure):
@@ -256,6 +261,20 @@ def fused_forward(**kw):
     for k, v in kw.items():
         setattr(a, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
     check(load().hcg_fused_forward(ctypes.addressof(a), stream_ptr()), "hcg_fused_forward")
+
+
+def fused_bwd_pair(query: bool = False, **kw) -> bool:
+    """Mode HCG_FUSED_BWD_PAIR of hcg_fused_forward (keywords as `fused_forward`).  `query`: validate only (the GPU is not
+    touched) -> whether the pair applies; otherwise launch, and raise on any error."""
+    a = FusedFwdArgs()
+    for k, v in kw.items():
+        setattr(a, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
+    a.mode, a.pair_flags = HCG_FUSED_BWD_PAIR, (HCG_FUSED_PAIR_QUERY if query else 0)
+    rc = load().hcg_fused_forward(ctypes.addressof(a), None if query else stream_ptr())
+    if query and rc == HCG_ERR_UNSUPPORTED:
+        return False
+    check(rc, "hcg_fused_forward (backward pair)")
+    return True
 
 
 def step_tail(jobs_addr: int, njobs: int, *, loss=None, loss_mode: int = HCG_LOSS_RMSE, loss_count: float = 0.0, sse_tail=None,

@@ -660,17 +660,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_fwd(
 // =====================================================================================================
 // BITS (needs POOLG): the layer's output was never stored; its sign / is-the-column-max bits (`poolbits`, written by the
 // BITS forward over the same tiles) stand in for a_out and emb.
-template <int KPAD, bool VEC, bool NEEDS_DX, bool POOLG, bool BITS = false, bool DEAL = false>
-__global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_bwd(
+// The whole backward of one layer is a PHASE: prologue loads, weight staging, tile loop, wave combine, slab store.  The
+// single-layer kernel runs one phase; the pair kernel (below) runs two in sequence over the same LDS.  Every wave of the
+// workgroup, with tiles or without, takes part in every barrier of a phase.
+//   lds : the workgroup's WAVES tile regions;  wtl : the dx operand (NEEDS_DX only): image row f, column d <- W[d][f],
+//         three bf16 planes, shared by the 8 waves
+template <int KPAD, bool VEC, bool NEEDS_DX, bool POOLG, bool BITS, bool DEAL>
+__device__ __forceinline__ void fused_bwd_phase(
+    WaveLdsB* lds, short* wtl,
     const float* __restrict__ dout, const float* __restrict__ demb, const float* __restrict__ emb,
     const float* __restrict__ a_out, const uint32_t* __restrict__ poolbits, const float* __restrict__ x, int F,
     const float* __restrict__ W,
     const int64_t* __restrict__ ei, int64_t E, const int32_t* __restrict__ graph_ptr,
     const int32_t* __restrict__ edge_ptr, int64_t N, int gpt, int B, int num_tiles, float slope, int apply_act,
     float* __restrict__ dx, float* __restrict__ partials, int32_t* __restrict__ status) {
-  __shared__ WaveLdsB lds[WAVES];
-  // dx operand: image row f, column d <- W[d][f], three bf16 planes, shared by the 8 waves
-  __shared__ __attribute__((aligned(16))) short wtl[NEEDS_DX ? 3 * KPAD * (DD + WPAD) : 8];
   BSTAMP_DECL
   int bstamp_it = 0;
   const int lane = threadIdx.x & 63;
@@ -1067,6 +1070,75 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_bwd(
   BSTAMP_FLUSH();
 }
 
+template <int KPAD, bool VEC, bool NEEDS_DX, bool POOLG, bool BITS = false, bool DEAL = false>
+__global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_bwd(
+    const float* __restrict__ dout, const float* __restrict__ demb, const float* __restrict__ emb,
+    const float* __restrict__ a_out, const uint32_t* __restrict__ poolbits, const float* __restrict__ x, int F,
+    const float* __restrict__ W,
+    const int64_t* __restrict__ ei, int64_t E, const int32_t* __restrict__ graph_ptr,
+    const int32_t* __restrict__ edge_ptr, int64_t N, int gpt, int B, int num_tiles, float slope, int apply_act,
+    float* __restrict__ dx, float* __restrict__ partials, int32_t* __restrict__ status) {
+  __shared__ WaveLdsB lds[WAVES];
+  __shared__ __attribute__((aligned(16))) short wtl[NEEDS_DX ? 3 * KPAD * (DD + WPAD) : 8];
+  fused_bwd_phase<KPAD, VEC, NEEDS_DX, POOLG, BITS, DEAL>(lds, wtl, dout, demb, emb, a_out, poolbits, x, F, W, ei, E, graph_ptr,
+                                                          edge_ptr, N, gpt, B, num_tiles, slope, apply_act, dx, partials, status);
+}
+
+// =====================================================================================================
+// backward of TWO layers in one launch: the upper layer (input width D, dx handed down premasked), then the layer below it.
+// =====================================================================================================
+// Tile t of the lower layer reads only the dx rows tile t of the upper layer wrote, and both phases walk the same TileSeq
+// from round 0: the wave that consumes a row is the wave that produced it, so a workgroup barrier orders all that the
+// boundary between two launches did.  One layer's dW accumulators are live at a time (registers = the larger phase, not the
+// sum); per-tile arithmetic, per-wave accumulation order, combine order and slabs are those of the two single launches, so
+// every result is bitwise theirs.  Phase B: NEEDS_DX = false, not pooled, activation bits clear, dout = the dx of phase A.
+struct BwdPairArgs {
+  const float* dout;           // upper layer, the arguments of k_fused_layer_bwd
+  const float* demb;
+  const float* emb;
+  const float* a_out;
+  const uint32_t* poolbits;
+  const float* x;
+  const float* W;
+  const int64_t* ei;           // both layers
+  int64_t E;
+  const int32_t* graph_ptr;
+  const int32_t* edge_ptr;
+  int64_t N;
+  int gpt, B, num_tiles;
+  float slope;
+  int apply_act;               // upper layer (bit 1 set)
+  float* dx;
+  float* partials;
+  int32_t* status;
+  const float* x0;             // lower layer
+  float* partials0;
+  int F0;
+};
+
+template <bool POOLG, bool BITS, int KPAD0, bool VEC0, bool DEAL>
+__global__ __launch_bounds__(WAVES * 64, 2) void k_fused_bwd_pair(const BwdPairArgs a) {
+  __shared__ WaveLdsB lds[WAVES];
+  __shared__ __attribute__((aligned(16))) short wtl[3 * DD * (DD + WPAD)];
+  fused_bwd_phase<DD, true, true, POOLG, BITS, DEAL>(lds, wtl, a.dout, a.demb, a.emb, a.a_out, a.poolbits, a.x, DD, a.W, a.ei, a.E,
+                                                     a.graph_ptr, a.edge_ptr, a.N, a.gpt, a.B, a.num_tiles, a.slope, a.apply_act,
+                                                     a.dx, a.partials, a.status);
+  // this workgroup's dx rows are visible to it, and every wave has left the combine's view of the LDS
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  // the lower layer's own arguments are read from the argument block only now: held in registers across phase A they
+  // would add to its spills
+  const __attribute__((address_space(4))) BwdPairArgs* kp =
+      (const __attribute__((address_space(4))) BwdPairArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  const float* x0 = kp->x0;
+  float* partials0 = kp->partials0;
+  const int F0 = kp->F0;
+  fused_bwd_phase<KPAD0, VEC0, false, false, false, DEAL>(lds, wtl, a.dx, nullptr, nullptr, nullptr, nullptr, x0, F0, nullptr, a.ei,
+                                                          a.E, a.graph_ptr, a.edge_ptr, a.N, a.gpt, a.B, a.num_tiles, a.slope, 0,
+                                                          nullptr, partials0, a.status);
+}
 
 int pick_grid(int num_tiles) {
   int dev = 0, cus = 256;
@@ -1114,9 +1186,13 @@ extern "C" int hcg_fused_head_reduce_job(const void* workspace, size_t workspace
 // Every forward form of the small-graph tiles: one or two stacked conv layers, optional [max, mean] pooling of the last one,
 // optional training form (the pooled layer's activations stay on chip, 2 bits per element leave), optional readout head in
 // the tail of the launch.
+static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream);
+
 extern "C" int hcg_fused_forward(const hcg_fused_fwd_args* a, hcg_stream_t stream_) {
   if (!a) return HCG_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
+  if (a->mode == HCG_FUSED_BWD_PAIR) return launch_fused_bwd_pair(a, stream);
+  if (a->mode != HCG_FUSED_FORWARD) return HCG_ERR_INVALID_ARG;
   const float *x = a->x, *W = a->W1, *b = a->b1, *W2 = a->W2, *b2 = a->b2;
   const int64_t* edge_index = a->edge_index;
   int64_t E = a->E;
@@ -1253,6 +1329,87 @@ extern "C" int hcg_fused_layer_bwd(const float* dout, const float* demb, const f
   if (poolbits && (dout || emb || out || !demb)) return HCG_ERR_INVALID_ARG;
   return launch_fused_bwd(dout, demb, emb, out, poolbits, x, W, edge_index, E, graph_ptr, edge_ptr, N, B, F, D,
                           graphs_per_tile, slope, apply_act, dx, status, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// mode HCG_FUSED_BWD_PAIR of hcg_fused_forward's argument block: the backward of two consecutive conv layers, F -> D (lower:
+// x, W1, output out1) and D -> D (upper: input out1, W2), in ONE launch (k_fused_bwd_pair).  The block's fields keep their
+// forward meaning; the upper layer takes the three forms of hcg_fused_layer_bwd.
+static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream) {
+  const int64_t N = a->N, B = a->B, F = a->F, D = a->D;
+  const int gpt = a->graphs_per_tile;
+  if (a->pair_flags & ~HCG_FUSED_PAIR_QUERY) return HCG_ERR_INVALID_ARG;
+  if ((a->pair_act_upper & ~3) || (a->pair_act_lower & ~3)) return HCG_ERR_INVALID_ARG;
+  if (N < 0 || B < 0 || a->E < 0) return HCG_ERR_INVALID_ARG;
+#ifdef HCG_NO_BWD_PAIR
+  return HCG_ERR_UNSUPPORTED;      // (A/B builds: the caller then issues the two single launches)
+#endif
+  // where the pair applies: both layers on the small-graph tiles over the same tiles, the upper layer hands dx down
+  // premasked, so the lower one runs with its activation bits clear
+  if (D != DD || F < 1 || F > 64 || gpt < 1 || a->pair_graphs_per_tile_upper != gpt) return HCG_ERR_UNSUPPORTED;
+  if (!(a->pair_act_upper & 2) || a->pair_act_lower != 0 || !a->pair_dx) return HCG_ERR_UNSUPPORTED;
+  if ((uintptr_t)a->out1 % 16 != 0 || (uintptr_t)a->pair_dx % 16 != 0) return HCG_ERR_UNSUPPORTED;   // wide rows of the D-wide tensors
+  const bool bits = a->poolbits != nullptr;
+  const bool poolg = bits || a->pair_dout == nullptr;
+  if (bits && (a->pair_dout || a->emb || a->out2)) return HCG_ERR_INVALID_ARG;
+  if (poolg && (!a->demb || (!bits && (!a->emb || !a->out2)))) return HCG_ERR_INVALID_ARG;
+  if (!poolg && (a->pair_act_upper & 1) && !a->out2) return HCG_ERR_INVALID_ARG;
+  if (!a->x || !a->W1 || !a->W2 || !a->out1 || !a->graph_ptr || !a->edge_ptr || !a->status || (a->E > 0 && !a->edge_index))
+    return HCG_ERR_INVALID_ARG;
+  if (a->pair_flags & HCG_FUSED_PAIR_QUERY) return HCG_OK;
+  if (!a->pair_ws_upper || !a->pair_ws_lower) return HCG_ERR_INVALID_ARG;
+  const int kpad0 = F <= 32 ? 32 : 64;
+  const int tiles = (int)((B + gpt - 1) / gpt);
+  const int grid = (N > 0 && B > 0) ? pick_grid(tiles) : 0;
+  if (a->pair_ws_upper_bytes < (size_t)grid * (DD * DD + DD) * sizeof(float) ||
+      a->pair_ws_lower_bytes < (size_t)grid * (DD * kpad0 + DD) * sizeof(float))
+    return HCG_ERR_WORKSPACE;
+  if (grid == 0) return HCG_OK;
+  const int64_t* edge_index = a->edge_index;
+  int64_t E = a->E;
+  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(a->graph_ptr); E = 1; }  // readable dummy
+  BwdPairArgs k{};
+  k.dout = poolg ? nullptr : a->pair_dout;
+  k.demb = a->demb;
+  k.emb = bits ? a->demb : a->emb;                    // (bits: never read)
+  k.a_out = (poolg || (a->pair_act_upper & 1)) ? (bits ? a->out1 : a->out2) : nullptr;
+  k.poolbits = a->poolbits;
+  k.x = a->out1;
+  k.W = a->W2;
+  k.ei = edge_index;
+  k.E = E;
+  k.graph_ptr = a->graph_ptr;
+  k.edge_ptr = a->edge_ptr;
+  k.N = N;
+  k.gpt = gpt;
+  k.B = (int)B;
+  k.num_tiles = tiles;
+  k.slope = a->slope;
+  k.apply_act = a->pair_act_upper;
+  k.dx = a->pair_dx;
+  k.partials = (float*)a->pair_ws_upper;
+  k.status = a->status;
+  k.x0 = a->x;
+  k.partials0 = (float*)a->pair_ws_lower;
+  k.F0 = (int)F;
+  const bool vec0 = (F == 64 || F == 32) && ((uintptr_t)a->x % 16 == 0);
+  const bool deal = tiles % (grid * WAVES) != 0 && tiles > grid * WAVES;     // (as the single launches: TileSeq)
+  const dim3 g(grid), blk(WAVES * 64);
+#define LAUNCH_PAIR_D(PG, BT, KP, VC, DL) hipLaunchKernelGGL((k_fused_bwd_pair<PG, BT, KP, VC, DL>), g, blk, 0, stream, k)
+#define LAUNCH_PAIR(PG, BT, KP, VC) \
+  do { if (deal) LAUNCH_PAIR_D(PG, BT, KP, VC, true); else LAUNCH_PAIR_D(PG, BT, KP, VC, false); } while (0)
+#define DISPATCH_PAIR(KP, VC)                                                  \
+  do {                                                                         \
+    if (bits) LAUNCH_PAIR(true, true, KP, VC);                                 \
+    else if (poolg) LAUNCH_PAIR(true, false, KP, VC);                          \
+    else LAUNCH_PAIR(false, false, KP, VC);                                    \
+  } while (0)
+  if (kpad0 == 32) { if (vec0) DISPATCH_PAIR(32, true); else DISPATCH_PAIR(32, false); }
+  else             { if (vec0) DISPATCH_PAIR(64, true); else DISPATCH_PAIR(64, false); }
+#undef DISPATCH_PAIR
+#undef LAUNCH_PAIR
+#undef LAUNCH_PAIR_D
+  HCG_CHECK_LAUNCH();
+  return HCG_OK;
 }
 
 // host-side description of this layer's slab set for hcg_step_tail (no launch)

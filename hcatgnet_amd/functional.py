@@ -234,6 +234,20 @@ def _tiles_backward(geo, gpt, x, W, flags, *, dout=None, demb=None, emb=None, ou
         _lib.stream_ptr() if stream is None else stream), "hcg_fused_layer_bwd")
 
 
+def _tiles_backward_pair(geo, gpt, x, W, h, W_up, flags_up, *, gpt_up=None, dout=None, demb=None, emb=None, out=None,
+                         poolbits=None, dx, ws_up=None, wsb_up=0, ws=None, wsb=0, slope=LEAKY_SLOPE, query=False) -> bool:
+    """Two consecutive conv layers' backward as ONE launch (csrc/fused.hip: k_fused_bwd_pair): the upper layer (input `h`,
+    weight `W_up`, `flags_up` with the premask bit; dout / demb / emb / out / poolbits as `_tiles_backward`) hands `dx`
+    down to the lower one (input `x`, weight `W`).  `query`: only ask whether the pair applies (host only)."""
+    D = W.shape[0]
+    return _lib.fused_bwd_pair(
+        query, x=x, W1=W, out1=h, W2=W_up, edge_index=geo.edge_index, E=geo.E, graph_ptr=geo.graph_ptr, edge_ptr=geo.edge_ptr,
+        N=geo.N, B=geo.B, F=x.shape[1], D=D, graphs_per_tile=gpt, pair_graphs_per_tile_upper=gpt if gpt_up is None else gpt_up,
+        slope=slope, out2=_a(out), emb=_graph_rows(emb, geo, D), demb=_graph_rows(demb, geo, D), poolbits=_a(poolbits),
+        status=geo.status, pair_dx=_a(dx), pair_dout=_a(dout), pair_ws_upper=_a(ws_up), pair_ws_upper_bytes=wsb_up,
+        pair_ws_lower=_a(ws), pair_ws_lower_bytes=wsb, pair_act_upper=flags_up, pair_act_lower=0)
+
+
 def _tiles_workspace_bytes(geo, gpt, F, D) -> int:
     return _lib.load().hcg_fused_workspace_bytes(geo.B, F, D, gpt)
 
@@ -305,7 +319,7 @@ def _tall_reduce_jobs(geo, gpt, F, D, ws, wsb, dW, db, job, first: bool = False)
 # small-graph tiles (csrc/fused.hip, graphs up to 32 nodes), one graph per workgroup / wave (csrc/mid.hip, wave.hip), the
 # wide-layer route (csrc/tall.hip: dense row-streaming parts + per-graph segmented sums)
 TILES = SimpleNamespace(name="tiles", forward=_tiles_forward, backward=_tiles_backward, workspace_bytes=_tiles_workspace_bytes,
-                        reduce_jobs=_tiles_reduce_jobs)
+                        reduce_jobs=_tiles_reduce_jobs, backward_pair=_tiles_backward_pair)
 MID = SimpleNamespace(name="mid", forward=_mid_forward, backward=_mid_backward, workspace_bytes=_mid_workspace_bytes,
                       reduce_jobs=_mid_reduce_jobs)
 TALL = SimpleNamespace(name="tall", forward=_tall_forward, backward=_tall_backward, workspace_bytes=_tall_workspace_bytes,

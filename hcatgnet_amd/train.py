@@ -41,12 +41,13 @@ class _Ctx:
     """Everything one step needs, resolved once: shapes, weights, buffers, the kernel family of every layer."""
     __slots__ = ("batch", "plan", "x", "y2", "convs", "lins", "N", "F", "B", "D", "C", "n_conv", "dev", "W", "bs",
                  "routes", "geo", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
-                 "loss_mode", "sse_split", "poolbits", "xagg")
+                 "loss_mode", "sse_split", "poolbits", "xagg", "bwd_pair")
 
 
 class FusedTrainStep:
     """One training step of the reference's loop as FOUR enqueued launches on small-graph tiles (conv stack + pooling +
-    readout head, two conv backward launches, the step tail), n_conv + 4 in general -- no autograd, no host sync.
+    readout head, two conv backward launches -- ONE with `BWD_PAIR` --, the step tail), n_conv + 4 in general -- no
+    autograd, no host sync.
 
         step = FusedTrainStep(model)            # model: hcatgnet_amd.GCN on the GPU
         loss = step(batch)                      # 0-d device tensor: sqrt(MSE) of this batch, weights already updated
@@ -74,6 +75,9 @@ class FusedTrainStep:
     XAGG_MID = True                # ... and behind the one-graph-per-workgroup kernels (batches under functional.TALL_MIN_NODES_D64)
     XAGG = True                    # first layer on the wide-layer route: Ahat x + sign pieces from the forward, one dense backward launch
     PREMASK = True
+    # conv layers 1 and 0 on the small-graph tiles: their backward as two phases of ONE launch (csrc/fused.hip:
+    # k_fused_bwd_pair; bitwise the two launches).  Off until its A/B is on record (profiles/bwd_pair_ab.txt)
+    BWD_PAIR = False
     HEAD_IN_FORWARD = True
     OVERLAP_GROUPS = True          # captured size-grouped steps: the two kernel families as two branches of the hipGraph
 
@@ -109,6 +113,7 @@ class FusedTrainStep:
         # Default False: the graph ends after the slab reduction, `replay()` issues collective + update eagerly behind it
         self.capture_exchange = False
         self._pcache = None
+        self._pair_ok = {}                      # answers of the backward pair's query (`_pair_applies`)
 
     def _trainable(self):
         """The model's parameters in `model.parameters()` order, from a cache: the module walk of `nn.Module.parameters()`
@@ -324,6 +329,7 @@ class FusedTrainStep:
         c.flat = c.gaddr = c.step_word = None
         c.poolbits = None
         c.xagg = None
+        c.bwd_pair = False
         # how the loss scale reaches the gradients (see the class docstring).  "sse" with a collective between backward and
         # update: the tail leaves the gradients unscaled and [SSE, count] behind the flat buffer; everything else: the tail
         # applies this rank's own scale ("sse" without any exchange IS sqrt(MSE) of the own batch)
@@ -352,7 +358,24 @@ class FusedTrainStep:
             if (self.optimizer_step and self.grad_sync is None and not self._capturing_split and c.head_fused
                     and hasattr(opt, "fused_update_ready") and (self.exchange is None or c.D == 64)):
                 c.step_word = opt.fused_update_ready(c.flat)
+            c.bwd_pair = self._pair_applies(c)
         return c
+
+    def _pair_applies(self, c: _Ctx) -> bool:
+        """Decided here, before anything is launched: conv layers 1 and 0 both on the small-graph tiles, layer 1 handing
+        its dx down premasked, and the library agreeing (the query touches no GPU; its answer is kept per shape and
+        buffer set)."""
+        if not (self.BWD_PAIR and self.PREMASK and c.n_small is None and c.n_conv >= 2
+                and c.routes[0][0] is HF.TILES and c.routes[1][0] is HF.TILES):
+            return False
+        acts0, dx = c.bufs["acts"][0], c.bufs["dacts"][0]
+        key = (c.F, c.D, c.routes[0][1], c.routes[1][1], c.x.data_ptr() % 16, acts0.data_ptr() % 16, dx.data_ptr() % 16)
+        ok = self._pair_ok.get(key)
+        if ok is None:
+            # (the upper layer's form does not enter the answer: asked as the not-pooled one)
+            ok = self._pair_ok[key] = HF.TILES.backward_pair(c.geo, c.routes[0][1], c.x, c.W[0], acts0, c.W[1], 2,
+                                                             gpt_up=c.routes[1][1], dout=dx, dx=dx, query=True)
+        return ok
 
     def _size_groups(self, batch, plan, convs, D, C, n_conv):
         """-> n_small when the batch is size-grouped (`collate(..., group_by_size=True)`: the first n_small graphs have <= 32
@@ -531,6 +554,21 @@ class FusedTrainStep:
             last = l == n_conv - 1
             W, dW, db = c.W[l], g(c.W[l]), g(c.bs[l])         # (c.W / c.bs: the parameters themselves)
             act = 1 if (last or not premasked) else 0
+            if l == 1 and c.bwd_pair:
+                # layers 1 and 0 in ONE launch: layer 1's phase, a workgroup barrier, layer 0's phase over the same tiles
+                bits = c.poolbits if last else None
+                F0 = c.x.shape[1]
+                wsb = fam.workspace_bytes(geo, gpt, Fl, D)
+                ws = self._ws(bufs, l, wsb, c.dev)
+                wsb0 = fam.workspace_bytes(geo, gpt, F0, D)
+                ws0 = self._ws(bufs, 0, wsb0, c.dev)
+                fam.backward_pair(geo, gpt, c.x, c.W[0], inp, W, act | 2, dout=None if last else dh,
+                                  demb=demb if last else None, emb=emb if (last and bits is None) else None,
+                                  out=acts[l] if (bits is None and (act or last)) else None, poolbits=bits, dx=dx,
+                                  ws_up=ws, wsb_up=wsb, ws=ws0, wsb=wsb0)
+                jobs.n += fam.reduce_jobs(geo, gpt, Fl, D, ws, wsb, dW, db, jobs.slot())
+                jobs.n += fam.reduce_jobs(geo, gpt, F0, D, ws0, wsb0, g(c.W[0]), g(c.bs[0]), jobs.slot())
+                return
             if fam is HF.TILES:
                 bits = c.poolbits if last else None
                 premasked = self.PREMASK and l > 0

@@ -280,9 +280,26 @@ size_t hcg_fused_workspace_bytes(int64_t B, int64_t F, int64_t D, int graphs_per
  *                    readout forward, squared error and (unless head_flags = HCG_HEAD_FORWARD_ONLY) the unscaled readout
  *                    backward over its own graphs -- see hcg_head_fwd_bwd for the contract of y / z / out / demb /
  *                    step_counter; head_workspace (hcg_fused_aux_bytes) gets one gradient slab + SSE partial per
- *                    workgroup, described by hcg_fused_head_reduce_job.  A training step is then FOUR launches: this one,
- *                    two backward launches, hcg_step_tail.
- * Replaces reference model/gcn.py:58-66 (+ :70-71 with the head). */
+ *                    workgroup, described by hcg_fused_head_reduce_job.  A training step is then this launch, the conv
+ *                    backward -- two hcg_fused_layer_bwd launches, or ONE pair launch (below) -- and hcg_step_tail: four
+ *                    launches, three with the pair.
+ * Replaces reference model/gcn.py:58-66 (+ :70-71 with the head).
+ *
+ * mode = HCG_FUSED_BWD_PAIR: the same block describes the BACKWARD of two consecutive conv layers, F -> D (lower: input x,
+ * weight W1, output out1) and D -> D (upper: input out1, weight W2, output out2), as ONE launch: each workgroup runs
+ * hcg_fused_layer_bwd's work for the upper layer over its tiles, then -- behind a workgroup barrier, the same waves over the
+ * same tiles in the same order -- for the lower layer.  Every result (pair_dx, both slab workspaces) is bitwise that of the two
+ * hcg_fused_layer_bwd launches.  The upper layer takes the forms of hcg_fused_layer_bwd: poolbits != NULL (demb given;
+ * pair_dout, emb, out2 = NULL), pooled plain (pair_dout = NULL; demb, emb, out2 given) or not pooled (pair_dout given;
+ * out2 required with bit 0 of pair_act_upper).  Workspaces and reduce jobs are the single launches': one
+ * hcg_fused_workspace_bytes / hcg_fused_reduce_job per layer.  b1, b2, and the head fields are ignored.
+ *   HCG_ERR_UNSUPPORTED  the pair does not apply -- D != 64, F > 64, pair_graphs_per_tile_upper != graphs_per_tile, bit 1
+ *                        of pair_act_upper clear (dx must go down premasked), pair_act_lower != 0, pair_dx = NULL, out1 or
+ *                        pair_dx not 16-byte aligned, or a library built without the pair: issue the two launches instead
+ *   pair_flags = HCG_FUSED_PAIR_QUERY  validate only: the same codes, no workspace needed, the GPU is not touched */
+#define HCG_FUSED_FORWARD 0
+#define HCG_FUSED_BWD_PAIR 1
+#define HCG_FUSED_PAIR_QUERY 1
 typedef struct hcg_fused_fwd_args {
   const float* x;
   const float* W1;
@@ -315,6 +332,18 @@ typedef struct hcg_fused_fwd_args {
   void* head_workspace;
   size_t head_workspace_bytes;
   int32_t* step_counter;      /* nullable */
+  int32_t mode;               /* HCG_FUSED_FORWARD (0) or HCG_FUSED_BWD_PAIR; the fields below: the pair only */
+  int32_t pair_flags;         /* 0 or HCG_FUSED_PAIR_QUERY */
+  float* pair_dx;             /* [N, D] gradient between the two layers (written, then read by the same launch) */
+  const float* pair_dout;     /* [N, D] upstream gradient of an upper layer that is not pooled; NULL = pooled */
+  void* pair_ws_upper;        /* slab workspace of the upper layer (hcg_fused_workspace_bytes with F = D) */
+  size_t pair_ws_upper_bytes;
+  void* pair_ws_lower;        /* slab workspace of the lower layer */
+  size_t pair_ws_lower_bytes;
+  int32_t pair_act_upper;     /* apply_act bits of hcg_fused_layer_bwd for the upper layer (bit 1 required) */
+  int32_t pair_act_lower;     /* ... for the lower layer: 0 */
+  int32_t pair_graphs_per_tile_upper;   /* the upper layer's graphs per tile: must equal graphs_per_tile */
+  int32_t pair_reserved;
 } hcg_fused_fwd_args;
 int hcg_fused_forward(const hcg_fused_fwd_args* args_host, hcg_stream_t stream);
 #define HCG_FUSED_POOLBITS 0 /* bytes of `poolbits` */
