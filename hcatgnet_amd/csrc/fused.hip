@@ -37,6 +37,7 @@
 #include "common.h"
 #include "split_mfma.h"
 #include "head_tile.h"
+#include "pair_query.h"
 
 // Diagnostic builds only (tools/probe_fused.hip defines HCG_STAMP): s_memtime stamps of a few waves go to
 // a buffer of their own; the product build compiles STAMP() to nothing and executes no stamp.
@@ -64,12 +65,31 @@ __device__ unsigned long long* g_stamp_buf = nullptr;
 #define STAMP(idx) do { } while (0)
 #endif
 // the backward's stamps (same buffer): only with -DHCG_STAMP -DHCG_STAMP_BWD, and the probe then runs a backward last
+// One LDS array for both phases of the pair kernel: 128 stamps per wave, a phase with NEEDS_DX (the pair's upper layer) writes
+// 0..63, one without (its lower layer, and the single-launch layer-1 kernel) 64..127 and flushes all 128 at its end -- the
+// upper phase never flushes: the 64 stores of a flush would sit in front of the very barrier being timed.  The buffer is
+// [4 workgroups][8 waves][128].
 #if defined(HCG_STAMP) && defined(HCG_STAMP_BWD)
-#define BSTAMP_DECL STAMP_DECL
-#define BSTAMP(idx) STAMP(idx)
-#define BSTAMP_FLUSH() STAMP_FLUSH()
+__shared__ unsigned long long s_bstamp[8][128];
+#define BSTAMP_DECL const int bstamp_base = NEEDS_DX ? 0 : 64;
+#define BSTAMP_AT(base, idx)                                                                                \
+  do {                                                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                                      \
+    unsigned long long _t;                                                                                  \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");                              \
+    __builtin_amdgcn_sched_barrier(0);                                                                      \
+    if ((threadIdx.x & 63) == 0) s_bstamp[threadIdx.x >> 6][(base) + (idx)] = _t;                            \
+  } while (0)
+#define BSTAMP(idx) BSTAMP_AT(bstamp_base, idx)
+#define BSTAMP_FLUSH()                                                                                      \
+  do {                                                                                                      \
+    if (bstamp_base == 64 && g_stamp_buf && blockIdx.x < 4 && (threadIdx.x & 63) == 0)                      \
+      for (int _i = 0; _i < 128; ++_i)                                                                      \
+        g_stamp_buf[((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 128 + _i] = s_bstamp[threadIdx.x >> 6][_i]; \
+  } while (0)
 #else
 #define BSTAMP_DECL
+#define BSTAMP_AT(base, idx) do { } while (0)
 #define BSTAMP(idx) do { } while (0)
 #define BSTAMP_FLUSH() do { } while (0)
 #endif
@@ -1060,6 +1080,7 @@ __device__ __forceinline__ void fused_bwd_phase(
       if (idx < SLABF) tot[j] += ((flat[idx] + flat[SLABF + idx]) + flat[2 * SLABF + idx]) + flat[3 * SLABF + idx];
     }
   }
+  BSTAMP(62);
   float* slab = partials + (size_t)blockIdx.x * SLABF;
 #pragma unroll
   for (int j = 0; j < PER_T; ++j) {
@@ -1135,6 +1156,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_bwd_pair(const BwdPairA
   const float* x0 = kp->x0;
   float* partials0 = kp->partials0;
   const int F0 = kp->F0;
+  BSTAMP_AT(64, 56);   // behind the barrier between the phases
   fused_bwd_phase<KPAD0, VEC0, false, false, false, DEAL>(lds, wtl, a.dx, nullptr, nullptr, nullptr, nullptr, x0, F0, nullptr, a.ei,
                                                           a.E, a.graph_ptr, a.edge_ptr, a.N, a.gpt, a.B, a.num_tiles, a.slope, 0,
                                                           nullptr, partials0, a.status);
@@ -1335,26 +1357,14 @@ extern "C" int hcg_fused_layer_bwd(const float* dout, const float* demb, const f
 // x, W1, output out1) and D -> D (upper: input out1, W2), in ONE launch (k_fused_bwd_pair).  The block's fields keep their
 // forward meaning; the upper layer takes the three forms of hcg_fused_layer_bwd.
 static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream) {
-  const int64_t N = a->N, B = a->B, F = a->F, D = a->D;
+  const int64_t N = a->N, B = a->B, F = a->F;
   const int gpt = a->graphs_per_tile;
-  if (a->pair_flags & ~HCG_FUSED_PAIR_QUERY) return HCG_ERR_INVALID_ARG;
-  if ((a->pair_act_upper & ~3) || (a->pair_act_lower & ~3)) return HCG_ERR_INVALID_ARG;
-  if (N < 0 || B < 0 || a->E < 0) return HCG_ERR_INVALID_ARG;
-#ifdef HCG_NO_BWD_PAIR
-  return HCG_ERR_UNSUPPORTED;      // (A/B builds: the caller then issues the two single launches)
-#endif
-  // where the pair applies: both layers on the small-graph tiles over the same tiles, the upper layer hands dx down
-  // premasked, so the lower one runs with its activation bits clear
-  if (D != DD || F < 1 || F > 64 || gpt < 1 || a->pair_graphs_per_tile_upper != gpt) return HCG_ERR_UNSUPPORTED;
-  if (!(a->pair_act_upper & 2) || a->pair_act_lower != 0 || !a->pair_dx) return HCG_ERR_UNSUPPORTED;
-  if ((uintptr_t)a->out1 % 16 != 0 || (uintptr_t)a->pair_dx % 16 != 0) return HCG_ERR_UNSUPPORTED;   // wide rows of the D-wide tensors
+  // ALL validation of the block -- flags, shapes, alignment, every pointer the kernel dereferences except the two workspaces
+  // checked below -- is hcg_bwd_pair_applies (pair_query.h); a -DHCG_NO_BWD_PAIR build answers unsupported there
+  const int rc = hcg_bwd_pair_applies(a, DD);
+  if (rc != HCG_OK) return rc;
   const bool bits = a->poolbits != nullptr;
   const bool poolg = bits || a->pair_dout == nullptr;
-  if (bits && (a->pair_dout || a->emb || a->out2)) return HCG_ERR_INVALID_ARG;
-  if (poolg && (!a->demb || (!bits && (!a->emb || !a->out2)))) return HCG_ERR_INVALID_ARG;
-  if (!poolg && (a->pair_act_upper & 1) && !a->out2) return HCG_ERR_INVALID_ARG;
-  if (!a->x || !a->W1 || !a->W2 || !a->out1 || !a->graph_ptr || !a->edge_ptr || !a->status || (a->E > 0 && !a->edge_index))
-    return HCG_ERR_INVALID_ARG;
   if (a->pair_flags & HCG_FUSED_PAIR_QUERY) return HCG_OK;
   if (!a->pair_ws_upper || !a->pair_ws_lower) return HCG_ERR_INVALID_ARG;
   const int kpad0 = F <= 32 ? 32 : 64;

@@ -45,9 +45,9 @@ class _Ctx:
 
 
 class FusedTrainStep:
-    """One training step of the reference's loop as FOUR enqueued launches on small-graph tiles (conv stack + pooling +
-    readout head, two conv backward launches -- ONE with `BWD_PAIR` --, the step tail), n_conv + 4 in general -- no
-    autograd, no host sync.
+    """One training step of the reference's loop as THREE enqueued launches on small-graph tiles (conv stack + pooling +
+    readout head, the two conv backward layers as one pair launch -- two launches with `BWD_PAIR = False` or where the pair
+    does not apply --, the step tail), n_conv + 4 in general -- no autograd, no host sync.
 
         step = FusedTrainStep(model)            # model: hcatgnet_amd.GCN on the GPU
         loss = step(batch)                      # 0-d device tensor: sqrt(MSE) of this batch, weights already updated
@@ -76,8 +76,9 @@ class FusedTrainStep:
     XAGG = True                    # first layer on the wide-layer route: Ahat x + sign pieces from the forward, one dense backward launch
     PREMASK = True
     # conv layers 1 and 0 on the small-graph tiles: their backward as two phases of ONE launch (csrc/fused.hip:
-    # k_fused_bwd_pair; bitwise the two launches).  Off until its A/B is on record (profiles/bwd_pair_ab.txt)
-    BWD_PAIR = False
+    # k_fused_bwd_pair; bitwise the two launches).  On since its A/B (profiles/bwd_pair_ab.txt): the slowest of 5
+    # pair runs of the C3 bench beat the fastest of 5 two-launch runs, 0.0999 against 0.1019 ms/step (means 0.0995 / 0.1024)
+    BWD_PAIR = True
     HEAD_IN_FORWARD = True
     OVERLAP_GROUPS = True          # captured size-grouped steps: the two kernel families as two branches of the hipGraph
 
