@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
-"""Explain every graph of a dataset at once: a GNNExplainer-style mask optimisation on `hcatgnet_amd.explain.ExplainStep`.
+"""Explain every graph of a dataset at once: GNNExplainer on `hcatgnet_amd.explain.ExplainFit`.
 
 The reference explains one molecule at a time with torch_geometric's `Explainer(GNNExplainer(epochs=...),
-node_mask_type='attributes', edge_mask_type='object')` (scripts_experiments/explain_gnn.py:39-50).  Here one call of
-`ExplainStep` delivers, for ALL graphs of the batch, the model's outputs and the gradients of each graph's own prediction
-loss with respect to its edge mask and node-feature mask; the graphs are independent, so this is the batch-of-one loop of
-every graph run side by side.  The regularisers (mask size, mask entropy) are functions of the masks alone and are written
-out below with torch ops; `torch.optim.Adam` updates both masks.
+node_mask_type='attributes', edge_mask_type='object')` (scripts_experiments/explain_gnn.py:39-50).  Here ONE call of
+`ExplainFit` runs the whole mask optimisation of ALL graphs of the batch -- every epoch's forward, backward, regularisers
+and Adam step, one workgroup per graph -- in one launch; the graphs are independent, so this is the batch-of-one fit of
+every graph run side by side.
 
-This is an EXAMPLE, not a parity claim: no artefact of the reference pins GNNExplainer's loop (initialisation, coefficients,
-the loss's exact form are those of the published algorithm as commonly implemented), and torch_geometric is not a
-dependency of this package.
+`--hand-loop` runs the loop a caller had to write before `ExplainFit` existed: one `ExplainStep` call per epoch for the
+prediction loss's gradients, the regularisers (mask size, mask entropy) written out with torch ops, `torch.optim.Adam` on
+both masks.  It regularises every entry over the whole batch (no hard masks, no per-graph means), so its numbers differ
+from `ExplainFit`'s, which follows the published algorithm graph by graph.
+
+This is an EXAMPLE, not a parity claim: no artefact of the reference pins GNNExplainer (`ExplainFit`'s docstring states the
+definition used), and torch_geometric is not a dependency of this package.
 
     python examples/explain_like_reference.py --graphs 64 --epochs 100
+    python examples/explain_like_reference.py --graphs 64 --epochs 100 --hand-loop
 """
 from __future__ import annotations
 
@@ -26,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import hcatgnet_amd as H  # noqa: E402
 from hcatgnet_amd import synth  # noqa: E402
-from hcatgnet_amd.explain import ExplainStep  # noqa: E402
+from hcatgnet_amd.explain import ExplainFit, ExplainStep  # noqa: E402
 
 EPS = 1e-15
 
@@ -38,10 +42,21 @@ def regulariser(mask_logits, size_coeff, ent_coeff, reduction):
     return size_coeff * reduction(m) + ent_coeff * ent.mean()
 
 
-def explain(model, batch, target, epochs=100, lr=0.01, edge_size=0.005, edge_ent=1.0, node_feat_size=1.0,
-            node_feat_ent=0.1, seed=0):
-    """-> (edge_mask [E], node_mask [N, F]) after `epochs` Adam steps; `target` [B, C] = what each graph's prediction is held to
-    (the model's own unmasked prediction: `explanation_type='model'`)."""
+def explain(model, batch, target, epochs=100, lr=0.01, seed=0, **coeffs):
+    """-> (edge_mask [E], node_mask [N, F]) of GNNExplainer's fit of every graph, ONE launch; `target` [B, C] = what each
+    graph's prediction is held to (the model's own unmasked prediction: `explanation_type='model'`)."""
+    fit = ExplainFit(model, epochs=epochs, lr=lr, coeffs=coeffs)
+    r = fit(batch, target=target, generator=torch.Generator().manual_seed(seed))
+    for epoch in list(range(0, epochs, 20)) + [epochs - 1]:
+        print(f"epoch {epoch:4d}  mean prediction loss {float(r.loss_history[epoch].mean()):.5f}")
+    hard = r.state.hard_count.sum(dim=0).tolist()
+    print(f"path {fit.last_path}: {r.state.step} Adam steps, {hard[0]} hard edges, {hard[1]} hard node entries")
+    return r.edge_mask, r.node_mask
+
+
+def explain_hand_loop(model, batch, target, epochs=100, lr=0.01, edge_size=0.005, edge_ent=1.0, node_feat_size=1.0,
+                      node_feat_ent=0.1, seed=0):
+    """The hand-written loop on `ExplainStep` (see the module docstring) -> (edge_mask [E], node_mask [N, F])."""
     gen = torch.Generator().manual_seed(seed)
     dev = batch.x.device
     edge_mask = torch.randn(batch.edge_index.shape[1], generator=gen).to(dev).requires_grad_(True)
@@ -72,12 +87,15 @@ def main():
     ap.add_argument("--edge-ent", type=float, default=1.0)
     ap.add_argument("--node-feat-size", type=float, default=1.0)
     ap.add_argument("--node-feat-ent", type=float, default=0.1)
+    ap.add_argument("--hand-loop", action="store_true", help="the caller-side loop on ExplainStep instead of ExplainFit")
     a = ap.parse_args()
     model = H.make_network("GCN", H.default_options(), 25).cuda()
     batch = synth.make_batch(num_graphs=a.graphs, nodes=87, nodes_jitter=30, extra_bonds=4, max_degree=4, feat=25).as_batch("cuda")
     with torch.no_grad():
         target = model(batch).reshape(batch.num_graphs, -1).clone()
-    em, nm = explain(model, batch, target, a.epochs, a.lr, a.edge_size, a.edge_ent, a.node_feat_size, a.node_feat_ent)
+    run = explain_hand_loop if a.hand_loop else explain
+    em, nm = run(model, batch, target, a.epochs, a.lr, edge_size=a.edge_size, edge_ent=a.edge_ent,
+                 node_feat_size=a.node_feat_size, node_feat_ent=a.node_feat_ent)
     top = torch.topk(em, min(10, em.numel())).indices.tolist()
     print("ten most important edges (batch edge positions):", top)
     print("node-feature mask: mean %.3f, max %.3f" % (float(nm.mean()), float(nm.max())))

@@ -13,6 +13,8 @@ Public surface (mirrors the reference's names for this path):
                                                 the reference's loops (utils/utils_model.py:55-111); the step as 6 launches
     io.load_processed_dir / write_embeddings_csv the reference's on-disk formats (reaction_N.pt in, embeddings.csv out)
     explain.set_masks / clear_masks             explain-mode edge masks (PyG Explainer hooks)
+    ExplainFit                                  GNNExplainer's whole mask optimisation of a batch of graphs in one launch
+                                                (the reference's first explain algorithm, explain_gnn.py)
     EnsemblePredict, stack_weights              M trained models predict one batch in one launch (the reference's
                                                 predict_test.py loop); train.predict_networks is its loader form
     ShapleySampling, draw_permutations          Shapley value sampling of a batch of graphs, the permutation walk on chip
@@ -22,6 +24,7 @@ Compute lives in csrc/libhcatgnet_hip.so (hand-written HIP for gfx950) behind in
 from .batch import Batch, Data, DataLoader, collate  # noqa: F401
 from .call_methods import default_options, make_network  # noqa: F401
 from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F401
+from .explain import ExplainFit, ExplainFitResult, ExplainFitState  # noqa: F401
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
 from .networks import BaseNetwork  # noqa: F401
 from .plan import BatchPlan  # noqa: F401
@@ -30,4 +33,5 @@ from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
 
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
-           "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations"]
+           "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "ExplainFit", "ExplainFitResult",
+           "ExplainFitState"]

@@ -21,7 +21,7 @@ HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2, HCG_WS_HEAD_D
 HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                          # hcg_fused_aux_bytes kinds
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
 HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS, HCG_STRUCT_EXPLAIN_ARGS = 5, 6, 7
-HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY = 0, 1, 2, 3   # modes of hcg_explain
+HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY, HCG_EXPLAIN_FIT = 0, 1, 2, 3, 4   # modes of hcg_explain
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_ERR_UNSUPPORTED = -3
 HCG_FUSED_FORWARD, HCG_FUSED_BWD_PAIR, HCG_FUSED_PAIR_QUERY = 0, 1, 1      # modes of hcg_fused_forward's block; the pair's flag
@@ -86,7 +86,8 @@ class HeadArgs(ctypes.Structure):
 
 class ExplainArgs(ctypes.Structure):
     """hcg_explain_args: a batch of graphs explained in one launch, one any-shape layer's edge-multiplier gradient, an
-    ensemble of models predicting one batch in one launch, or Shapley value sampling of a batch of graphs."""
+    ensemble of models predicting one batch in one launch, Shapley value sampling of a batch of graphs, or the whole
+    GNNExplainer mask fit of a batch of graphs."""
     _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
                 ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
                 ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
@@ -96,7 +97,12 @@ class ExplainArgs(ctypes.Structure):
                 ("layer_dout", P), ("layer_out", P), ("layer_h", P), ("rowptr", P), ("col", P), ("dinv", P), ("dew_csr", P),
                 ("emb", P), ("n_models", I32), ("models_per_group", I32), ("perm", P), ("out_base", P), ("shap_acc", P),
                 ("n_perm", I32), ("perm_first", I32), ("perm_count", I32), ("class_index", I32),
-                ("lds_bytes", I32), ("reserved", I32)]
+                ("lds_bytes", I32), ("reserved", I32),
+                ("fit_edge_logit", P), ("fit_edge_exp_avg", P), ("fit_edge_exp_avg_sq", P), ("fit_edge_hard", P),
+                ("fit_node_logit", P), ("fit_node_exp_avg", P), ("fit_node_exp_avg_sq", P), ("fit_node_hard", P),
+                ("fit_hard_count", P), ("fit_loss_hist", P), ("fit_edge_mask_out", P), ("fit_node_mask_out", P),
+                ("step_first", I32), ("epoch_count", I32), ("fit_lr", F32), ("fit_beta1", F32), ("fit_beta2", F32),
+                ("fit_eps", F32), ("fit_coeffs", F32 * 4)]
 
 
 class CollateSlot(ctypes.Structure):

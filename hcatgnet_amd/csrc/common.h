@@ -53,6 +53,19 @@ __device__ __forceinline__ float hcg_adam_update(float p, float g, float& m, flo
   return __fsub_rn(p, __fmul_rn(step_size, __fdiv_rn(m, denom)));
 }
 
+// b^t for an integer t >= 0 by squaring, in double: a few ulp of double, far inside the float the caller rounds to
+// (torch computes `1 - beta ** step` in Python doubles); ~20 multiplications instead of a library pow().  Adam's bias
+// corrections from a step count held on the device (optim.hip, reduce.hip, explain.hip).
+__device__ __forceinline__ double hcg_powi(double b, int t) {
+  double r = 1.0;
+  while (t > 0) {
+    if (t & 1) r *= b;
+    b *= b;
+    t >>= 1;
+  }
+  return r;
+}
+
 // torch.optim.SGD's update (momentum / weight_decay / maximize off) and torch.optim.RMSprop's (momentum / centered /
 // weight_decay / maximize off), explicitly rounded for the same reason as hcg_adam_update
 __device__ __forceinline__ float hcg_sgd_update(float p, float g, float lr) { return __fsub_rn(p, __fmul_rn(lr, g)); }

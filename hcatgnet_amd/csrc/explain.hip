@@ -22,6 +22,16 @@
 // ([2 n_conv][N][64] f32, each graph's rows written and read by its own workgroup only).
 // The build and the forward are the pieces of explain_tile.h, shared with ensemble.hip and shapley.hip (here: both row
 // lists in one build, the packed entry word, the workspace store as the aggregation's extra); the backward is this file's.
+//
+// HCG_EXPLAIN_FIT is the same kernel body instantiated with FIT = true (k_explain_graphs<true>): the whole GNNExplainer
+// mask optimisation of every graph in one launch.  The graph is built once; then `epochs` times: mask values and the masked
+// input tile from the LOGITS in the caller's state buffers, the forward, the prediction loss, the backward above, and --
+// instead of storing the gradients -- the regularisers' gradients, one Adam step on the graph's own entries of the state
+// (logit, exp_avg, exp_avg_sq; the rule of common.h hcg_adam_update, bias corrections from the integer step as optim.hip
+// derives them) and, in the step-0 epoch, the hard flags (gradient != 0) and their per-graph counts.  Every entry of the
+// state is read and written by ONE thread of the graph's workgroup (the same in every epoch); the counts are integers.  So a
+// fit split into several launches repeats the single launch bit for bit.  FIT = false compiles to what the kernel was
+// before the template existed (same VGPRs, no scratch, same LDS): every FIT branch is `if constexpr`.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -42,6 +52,25 @@ struct XArgs {     // the kernel's argument block (device pointers by value)
   float* ws;
   int N, sigmoid;
 };
+
+struct XFit {      // what HCG_EXPLAIN_FIT adds (FIT = true only)
+  float* e_logit; float* e_m; float* e_v; unsigned char* e_hard;     // [E]     edge state
+  float* n_logit; float* n_m; float* n_v; unsigned char* n_hard;     // [N][F]  node-feature state
+  int32_t* hard_count;                                               // [B][2]  hard edges, hard node entries
+  float* loss_hist;                                                  // [epochs][B]
+  float* edge_out;                                                   // [E]     s(logit) of the hard entries, else 0
+  float* node_out;                                                   // [N][F]
+  int step_first, epochs, B;
+  float lr, b1, b2, eps;
+  float edge_size, edge_ent, node_size, node_ent;
+};
+
+struct XFitArgs { XArgs a; XFit f; };
+
+template <bool FIT> struct XKernelArgs { using type = XArgs; };
+template <> struct XKernelArgs<true> { using type = XFitArgs; };
+__device__ __forceinline__ const XArgs& x_base(const XArgs& a) { return a; }
+__device__ __forceinline__ const XArgs& x_base(const XFitArgs& a) { return a.a; }
 
 struct XLds {
   float* t0;            // [npad][XS]
@@ -87,32 +116,51 @@ __device__ __forceinline__ XLds x_carve(char* base, int npad, int emax) {
 
 __device__ __forceinline__ float x_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-__global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
+// d ent(m) / d m of ent(m) = -m log(m + EPS) - (1 - m) log(1 - m + EPS), differentiated as written
+__device__ __forceinline__ float x_dent(float m) {
+  constexpr float EPS = 1e-15f;
+  const float a = m + EPS, b = (1.f - m) + EPS;
+  return (logf(b) + (1.f - m) / b) - (logf(a) + m / a);
+}
+
+template <bool FIT>
+__global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArgs<FIT>::type args) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const XArgs& a = x_base(args);
   const XCommon& cm = a.c;
   const XLds L = x_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x;
   const int F = cm.F, C = cm.C, n_conv = cm.n_conv;
   const float slope = cm.slope;
-  const bool bwd = a.target != nullptr || a.dout != nullptr;
-  const bool need_dx = a.d_node_mask != nullptr || a.dx != nullptr;
+  const bool bwd = FIT || a.target != nullptr || a.dout != nullptr;
+  const bool need_dx = FIT || a.d_node_mask != nullptr || a.dx != nullptr;
+  const bool sig = FIT || a.sigmoid;
 
   XSpan sp;
   if (x_refused(sp, cm, g, tid)) {
     // the graph's outputs are zero -- over whatever part of its ranges lies inside the arrays
     const int nbase = sp.nbase, ebase = sp.ebase, n_raw = sp.n_raw, ne_raw = sp.ne_raw;
     for (int k = tid; k < C; k += XT) a.out[(size_t)g * C + k] = 0.f;
-    if (a.loss && tid == 0) a.loss[g] = 0.f;
+    // (FIT: the masks and the loss history; the graph's state is left as it came)
+    float* d_e = a.d_edge_mask;
+    float* d_n = a.d_node_mask;
+    if constexpr (FIT) {
+      d_e = args.f.edge_out;
+      d_n = args.f.node_out;
+      for (int t = tid; t < args.f.epochs; t += XT) args.f.loss_hist[(size_t)t * args.f.B + g] = 0.f;
+    } else {
+      if (a.loss && tid == 0) a.loss[g] = 0.f;
+    }
     if (bwd) {
       for (long long e = tid; e < ne_raw; e += XT) {
         const long long p = (long long)ebase + e;
-        if (p >= 0 && p < cm.E) a.d_edge_mask[p] = 0.f;
+        if (p >= 0 && p < cm.E) d_e[p] = 0.f;
       }
       for (long long i = tid; i < (long long)n_raw * F; i += XT) {
         const long long p = (long long)nbase * F + i;
         if (p >= 0 && p < (long long)a.N * F) {
-          if (a.d_node_mask) a.d_node_mask[p] = 0.f;
+          if (d_n) d_n[p] = 0.f;
           if (a.dx) a.dx[p] = 0.f;
         }
       }
@@ -125,25 +173,28 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   EdgeRegs<X_EPT, XT> er;
   er.load(XGraph{sp.ebase, sp.ne}, cm.ei, cm.E, tid);
   for (int i = tid; i < cm.npad; i += XT) { L.cnt_d[i] = 0; L.cnt_s[i] = 0; }
-  for (int e = tid; e < ne; e += XT) {
-    const float v = a.edge_mask[(size_t)ebase + e];
-    L.mval[e] = a.sigmoid ? x_sigmoid(v) : v;
-    L.eg[e] = 0.f;
-  }
-  // x~ = x s(node_mask), zero-padded to 64 columns
-  for (int idx = tid; idx < n * XD; idx += XT) {
-    const int r = idx >> 6, k = idx & 63;
-    float v = 0.f;
-    if (k < F) {
-      const size_t p = (size_t)(nbase + r) * F + k;
-      v = cm.x[p];
-      if (a.node_mask) {
-        const float m = a.node_mask[p];
-        v *= a.sigmoid ? x_sigmoid(m) : m;
-      }
+  // the mask values, and x~ = x s(node_mask), zero-padded to 64 columns (once; FIT: from the logits, at every epoch's start)
+  auto stage_masks = [&](const float* em, const float* nm) {
+    for (int e = tid; e < ne; e += XT) {
+      const float v = em[(size_t)ebase + e];
+      L.mval[e] = sig ? x_sigmoid(v) : v;
+      L.eg[e] = 0.f;
     }
-    L.t0[r * XS + k] = v;
-  }
+    for (int idx = tid; idx < n * XD; idx += XT) {
+      const int r = idx >> 6, k = idx & 63;
+      float v = 0.f;
+      if (k < F) {
+        const size_t p = (size_t)(nbase + r) * F + k;
+        v = cm.x[p];
+        if (nm) {
+          const float m = nm[p];
+          v *= sig ? x_sigmoid(m) : m;
+        }
+      }
+      L.t0[r * XS + k] = v;
+    }
+  };
+  if constexpr (!FIT) stage_masks(a.edge_mask, a.node_mask);
   XEdges q;
   x_edge_pass(q, er, sp, tid, cm.status);
   const XMasked fmt{L.mval};
@@ -152,6 +203,23 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
 
   const size_t plane = (size_t)a.N * XD;                  // one [N][64] tensor of the workspace
   float* const wsg = a.ws + (size_t)nbase * XD;           // this graph's rows of plane 0
+
+  // FIT: the hard counts (behind the tiles and lists in LDS), from the state unless this launch holds the step-0 epoch
+  [[maybe_unused]] int* const hc = reinterpret_cast<int*>(smem + x_lds_bytes(cm.npad, cm.emax));
+  int epochs = 1;
+  if constexpr (FIT) {
+    epochs = args.f.epochs;
+    if (tid < 2) hc[tid] = args.f.step_first > 0 ? args.f.hard_count[2 * g + tid] : 0;
+  }
+
+#pragma nounroll
+  for (int t = 0; t < epochs; ++t) {
+  float* loss_out = a.loss;
+  if constexpr (FIT) {
+    loss_out = args.f.loss_hist + (size_t)t * args.f.B;
+    stage_masks(args.f.e_logit, args.f.n_logit);
+    __syncthreads();
+  }
 
   // ---------------------------------------------------------------------------------------------- forward
 #pragma nounroll
@@ -187,10 +255,10 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
     L.hg[off + tid] = a.target ? 2.f * d / (float)C : (a.dout ? a.dout[(size_t)g * C + tid] : 0.f);
   }
   __syncthreads();
-  if (a.loss && tid == 0) {
+  if (loss_out && tid == 0) {
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += L.red[c];
-    a.loss[g] = a.target ? s / (float)C : 0.f;
+    loss_out[g] = a.target ? s / (float)C : 0.f;
   }
   if (!bwd) return;
 
@@ -295,6 +363,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
   }
   __syncthreads();
 
+  if constexpr (!FIT) {
   // ---------------------------------------------------------------------------------------------- outputs
   for (int e = tid; e < ne; e += XT) {
     const float m = L.mval[e];
@@ -317,6 +386,112 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const XArgs a) {
       }
     }
   }
+  } else {
+  // ---------------------------------------------------------------------------------------------- FIT: regularisers, Adam, hard flags
+  // Entry p of the state belongs to the thread that staged it (same index maps as stage_masks), in every epoch.
+  const XFit& f = args.f;
+  const int step = f.step_first + t;                      // Adam steps taken before this epoch
+  const bool reg = step > 0;                              // the hard masks exist from the epoch after step 0
+  const float step_size = f.lr / (float)(1.0 - hcg_powi((double)f.b1, step + 1));
+  const float bc2_sqrt = (float)sqrt(1.0 - hcg_powi((double)f.b2, step + 1));
+  const int hce = hc[0], hcn = hc[1];                     // (written before the barrier that ended the last epoch)
+  const float inv_e = hce > 0 ? 1.f / (float)hce : 0.f, inv_n = hcn > 0 ? 1.f / (float)hcn : 0.f;
+  int found_e = 0, found_n = 0;
+  for (int e = tid; e < ne; e += XT) {
+    const size_t p = (size_t)ebase + e;
+    const float m = L.mval[e], ds = m * (1.f - m);
+    float gr = L.eg[e] * ds;
+    if (reg && f.e_hard[p]) gr += (f.edge_size + f.edge_ent * inv_e * x_dent(m)) * ds;
+    float mi = f.e_m[p], vi = f.e_v[p];
+    f.e_logit[p] = hcg_adam_update(f.e_logit[p], gr, mi, vi, f.b1, f.b2, f.eps, step_size, bc2_sqrt);
+    f.e_m[p] = mi;
+    f.e_v[p] = vi;
+    if (step == 0) {
+      f.e_hard[p] = gr != 0.f ? 1 : 0;
+      found_e += gr != 0.f ? 1 : 0;
+    }
+  }
+  for (int idx = tid; idx < n * XD; idx += XT) {
+    const int r = idx >> 6, k = idx & 63;
+    if (k < F) {
+      const size_t p = (size_t)(nbase + r) * F + k;
+      const float s = x_sigmoid(f.n_logit[p]), ds = s * (1.f - s);
+      float gr = L.t0[r * XS + k] * cm.x[p] * ds;
+      if (reg && f.n_hard[p]) gr += (f.node_size * inv_n + f.node_ent * inv_n * x_dent(s)) * ds;
+      float mi = f.n_m[p], vi = f.n_v[p];
+      f.n_logit[p] = hcg_adam_update(f.n_logit[p], gr, mi, vi, f.b1, f.b2, f.eps, step_size, bc2_sqrt);
+      f.n_m[p] = mi;
+      f.n_v[p] = vi;
+      if (step == 0) {
+        f.n_hard[p] = gr != 0.f ? 1 : 0;
+        found_n += gr != 0.f ? 1 : 0;
+      }
+    }
+  }
+  if (step == 0) {                                        // (integer counts: any order gives the same number)
+    if (found_e) atomicAdd(&hc[0], found_e);
+    if (found_n) atomicAdd(&hc[1], found_n);
+    __syncthreads();
+    if (tid < 2) f.hard_count[2 * g + tid] = hc[tid];
+  }
+  __syncthreads();
+  }
+  }  // epochs
+
+  if constexpr (FIT) {
+    // the post-processed masks: s(logit) of the hard entries, 0 elsewhere (each thread reads the logits it wrote)
+    const XFit& f = args.f;
+    for (int e = tid; e < ne; e += XT) {
+      const size_t p = (size_t)ebase + e;
+      f.edge_out[p] = f.e_hard[p] ? x_sigmoid(f.e_logit[p]) : 0.f;
+    }
+    for (int idx = tid; idx < n * XD; idx += XT) {
+      const int r = idx >> 6, k = idx & 63;
+      if (k < F) {
+        const size_t p = (size_t)(nbase + r) * F + k;
+        f.node_out[p] = f.n_hard[p] ? x_sigmoid(f.n_logit[p]) : 0.f;
+      }
+    }
+  }
+}
+
+constexpr unsigned X_FIT_LDS_EXTRA = 16;
+
+// hcg_explain, mode HCG_EXPLAIN_FIT, behind the shape check and the query
+int x_fit_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->epoch_count < 1 || p->step_first < 0 || (long long)p->step_first + p->epoch_count >= (1ll << 31)) return HCG_ERR_INVALID_ARG;
+  if (p->edge_mask || p->node_mask || p->dout || p->dx) return HCG_ERR_INVALID_ARG;
+  if (p->B == 0) return HCG_OK;
+  if (!x_common_ok(p) || !p->target || !p->fit_hard_count || !p->fit_loss_hist) return HCG_ERR_INVALID_ARG;
+  if (p->E > 0 && (!p->fit_edge_logit || !p->fit_edge_exp_avg || !p->fit_edge_exp_avg_sq || !p->fit_edge_hard || !p->fit_edge_mask_out))
+    return HCG_ERR_INVALID_ARG;
+  if (p->N > 0 && (!p->fit_node_logit || !p->fit_node_exp_avg || !p->fit_node_exp_avg_sq || !p->fit_node_hard || !p->fit_node_mask_out))
+    return HCG_ERR_INVALID_ARG;
+  if (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed) return HCG_ERR_WORKSPACE;
+
+  XFitArgs k;
+  XArgs& a = k.a;
+  x_fill_common(a.c, p);
+  a.edge_mask = a.node_mask = a.dout = nullptr;
+  a.target = p->target;
+  a.out = p->out;
+  a.loss = a.d_edge_mask = a.d_node_mask = a.dx = nullptr;
+  a.ws = (float*)p->workspace;
+  a.N = (int)p->N;
+  a.sigmoid = 1;
+  XFit& f = k.f;
+  f.e_logit = p->fit_edge_logit; f.e_m = p->fit_edge_exp_avg; f.e_v = p->fit_edge_exp_avg_sq; f.e_hard = p->fit_edge_hard;
+  f.n_logit = p->fit_node_logit; f.n_m = p->fit_node_exp_avg; f.n_v = p->fit_node_exp_avg_sq; f.n_hard = p->fit_node_hard;
+  f.hard_count = p->fit_hard_count;
+  f.loss_hist = p->fit_loss_hist;
+  f.edge_out = p->fit_edge_mask_out;
+  f.node_out = p->fit_node_mask_out;
+  f.step_first = p->step_first;
+  f.epochs = p->epoch_count;
+  f.B = (int)p->B;
+  f.lr = p->fit_lr; f.b1 = p->fit_beta1; f.b2 = p->fit_beta2; f.eps = p->fit_eps;
+  f.edge_size = p->fit_coeffs[0]; f.edge_ent = p->fit_coeffs[1]; f.node_size = p->fit_coeffs[2]; f.node_ent = p->fit_coeffs[3];
+  return x_launch<k_explain_graphs<true>>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax) + X_FIT_LDS_EXTRA, stream, k);
 }
 
 }  // namespace
@@ -331,11 +506,15 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   }
   if (p->mode == HCG_EXPLAIN_ENSEMBLE) return hcg_ensemble_launch(p, stream);
   if (p->mode == HCG_EXPLAIN_SHAPLEY) return hcg_shapley_launch(p, stream);
-  if (p->mode != HCG_EXPLAIN_GRAPHS) return HCG_ERR_INVALID_ARG;
+  const bool fit = p->mode == HCG_EXPLAIN_FIT;
+  if (p->mode != HCG_EXPLAIN_GRAPHS && !fit) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p)) return HCG_ERR_UNSUPPORTED;
+  // (FIT: the tiles and lists of HCG_EXPLAIN_GRAPHS and two hard counts behind them)
+  if (fit) p->lds_bytes = (int32_t)(x_lds_bytes(x_round4(p->max_nodes, 4), x_round4(p->max_edges, 4)) + X_FIT_LDS_EXTRA);
   // H_l and A_l of every layer, [N][64] f32 each: the backward reads them again
   p->workspace_bytes_needed = hcg_align_up((size_t)2 * p->n_conv * (size_t)(p->N > 0 ? p->N : 1) * XD * sizeof(float), 256);
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
+  if (fit) return x_fit_launch(p, stream);
   if (p->B == 0) return HCG_OK;
   const bool bwd = p->target || p->dout;
   if (p->target && p->dout) return HCG_ERR_INVALID_ARG;
@@ -358,5 +537,5 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   a.ws = (float*)p->workspace;
   a.N = (int)p->N;
   a.sigmoid = (p->flags & HCG_EXPLAIN_SIGMOID) ? 1 : 0;
-  return x_launch<k_explain_graphs>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax), stream, a);
+  return x_launch<k_explain_graphs<false>>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax), stream, a);
 }

@@ -10,18 +10,6 @@
 
 namespace {
 
-// b^t for an integer t >= 0 by squaring, in double: a few ulp of double, far inside the float the caller rounds to
-// (torch computes `1 - beta ** step` in Python doubles); ~20 multiplications instead of a library pow().
-__device__ __forceinline__ double hcg_powi(double b, int t) {
-  double r = 1.0;
-  while (t > 0) {
-    if (t & 1) r *= b;
-    b *= b;
-    t >>= 1;
-  }
-  return r;
-}
-
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                               float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
                                               float bc1, float bc2_sqrt) {

@@ -9,18 +9,6 @@
 
 namespace {
 
-// b^t for an integer t >= 0 by squaring, in double: a few ulp of double, far inside the float the caller rounds to
-// (torch computes `1 - beta ** step` in Python doubles); ~20 multiplications instead of a library pow().
-__device__ __forceinline__ double hcg_powi(double b, int t) {
-  double r = 1.0;
-  while (t > 0) {
-    if (t & 1) r *= b;
-    b *= b;
-    t >>= 1;
-  }
-  return r;
-}
-
 struct Jobs {
   int njobs;
   int nblk[HCG_REDUCE_MAX_JOBS];     // workgroups of job j: ceil(slab_floats / RO) -- the grid is their sum (+ the plan's)

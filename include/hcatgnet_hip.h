@@ -132,7 +132,7 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
                       int64_t N, int64_t E, int64_t F, int64_t D,
                       void* workspace, size_t workspace_bytes, hcg_stream_t stream);
 
-/* ---- explain mode (f4): ONE entry point, four jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
+/* ---- explain mode (f4): ONE entry point, five jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
  * PyG's Explainer multiplies every message by an edge mask inside each MessagePassing layer, AFTER gcn_norm, self loops keep 1
  * (reference scripts_experiments/explain_gnn.py:39-50: edge_mask_type='object'); the node mask multiplies x.
  *
@@ -186,16 +186,34 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   out_base [B, C] = with everything off, both written by permutation 0's workgroups.  edge_mask, node_mask, target and dout
  *   must be NULL (HCG_ERR_INVALID_ARG).  Shapes: as HCG_EXPLAIN_GRAPHS but graphs of <= 184 nodes (three [n][64] tiles are kept
  *   in LDS) and perm_count <= 65535; refusals as there (HCG_STATUS_SHAPE_LIMIT: the graph's rows of every output zero).
- *   HCG_EXPLAIN_QUERY as above (reads perm_count too). */
+ *   HCG_EXPLAIN_QUERY as above (reads perm_count too).
+ * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
+ *   node_mask_type 'attributes', edge_mask_type 'object', regression) for a batch of graphs in ONE launch: the kernel of
+ *   HCG_EXPLAIN_GRAPHS with an epoch loop around forward and backward, one workgroup per graph, run as a batch-of-one fit
+ *   per graph.  The parameters are the LOGITS fit_edge_logit [E] / fit_node_logit [N, F]; every epoch evaluates
+ *   HCG_EXPLAIN_GRAPHS with HCG_EXPLAIN_SIGMOID on them against `target` (required; loss of epoch t in fit_loss_hist[t, g]),
+ *   adds -- from the epoch after the hard flags exist -- the gradients of
+ *     coeffs[0] sum(m) + coeffs[1] mean(ent(m)) over the graph's hard edges and
+ *     coeffs[2] mean(m) + coeffs[3] mean(ent(m)) over its hard node entries,  m = sigmoid(logit),
+ *     ent(m) = -m log(m + 1e-15) - (1 - m) log(1 - m + 1e-15)  (a term over an empty set is 0),
+ *   and takes one Adam step (fit_lr, fit_beta1, fit_beta2, fit_eps; the update of hcg_adam_step, bias corrections from the
+ *   integer step) on both masks.  The epoch at step 0 then sets hard = (gradient != 0) and counts the hard entries per graph
+ *   (fit_hard_count); an entry that is not hard never moves.  step_first = steps the state has taken, epoch_count = epochs of
+ *   this launch: a fit split into several launches is bitwise the single launch.  out [B, C] = the last epoch's outputs;
+ *   fit_edge_mask_out / fit_node_mask_out = sigmoid(logit) of the hard entries, 0 elsewhere.  edge_mask, node_mask, dout and dx
+ *   must be NULL.  Shapes, workspace and refusals as HCG_EXPLAIN_GRAPHS (a refused graph: its rows of out, fit_loss_hist and
+ *   the two mask outputs zero, its state untouched).  No float atomics, no exchange between workgroups.
+ *   HCG_EXPLAIN_QUERY as above; this mode also writes lds_bytes. */
 #define HCG_EXPLAIN_GRAPHS 0
 #define HCG_EXPLAIN_LAYER_EDGE_GRAD 1
 #define HCG_EXPLAIN_ENSEMBLE 2
 #define HCG_EXPLAIN_SHAPLEY 3
+#define HCG_EXPLAIN_FIT 4
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -242,6 +260,22 @@ typedef struct hcg_explain_args {
   int32_t class_index;                   /* the explained output column, 0 .. C - 1 */
   int32_t lds_bytes;                     /* OUT: dynamic LDS of one workgroup for max_nodes / max_edges (also by a query) */
   int32_t reserved;
+  float* fit_edge_logit;                 /* HCG_EXPLAIN_FIT from here on.  IN/OUT state of the edge mask, [E] each */
+  float* fit_edge_exp_avg;
+  float* fit_edge_exp_avg_sq;
+  uint8_t* fit_edge_hard;                /* 1: the entry's first gradient was not 0 (written by the step-0 epoch) */
+  float* fit_node_logit;                 /* IN/OUT state of the node-feature mask, [N, F] each */
+  float* fit_node_exp_avg;
+  float* fit_node_exp_avg_sq;
+  uint8_t* fit_node_hard;
+  int32_t* fit_hard_count;               /* IN/OUT [B, 2]: hard edges, hard node entries of every graph (read when step_first > 0) */
+  float* fit_loss_hist;                  /* OUT [epoch_count, B]: the prediction loss of every epoch */
+  float* fit_edge_mask_out;              /* OUT [E]: sigmoid(logit) of the hard entries, 0 elsewhere */
+  float* fit_node_mask_out;              /* OUT [N, F] */
+  int32_t step_first;                    /* Adam steps the state has taken */
+  int32_t epoch_count;                   /* epochs of this launch, >= 1 */
+  float fit_lr, fit_beta1, fit_beta2, fit_eps;
+  float fit_coeffs[4];                   /* edge_size (on a sum), edge_ent, node_feat_size (on a mean), node_feat_ent */
 } hcg_explain_args;
 int hcg_explain(hcg_explain_args* args_host, hcg_stream_t stream);
 
