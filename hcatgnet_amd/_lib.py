@@ -16,7 +16,9 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libhcatgnet_hip.so")
 HCG_PLAN_GENERAL, HCG_PLAN_BLOCKED, HCG_PLAN_PTRS_ONLY, HCG_PLAN_KEEP_STATUS = 0, 1, 2, 4
 HCG_ACT_NONE, HCG_ACT_LEAKY = 0, 1
 HCG_LOSS_MSE, HCG_LOSS_RMSE, HCG_LOSS_SSE = 0, 1, 2      # loss modes of hcg_step_tail / hcg_loss_finalize / hcg_loss_fwd_bwd
-HCG_HEAD_FORWARD_ONLY = 1
+HCG_LOSS_CE = 3                                          # ... cross-entropy (hcg_step_tail / hcg_loss_finalize; count = B)
+HCG_LOSS_CE_CLASSES_SHIFT = 8                            # hcg_loss_fwd_bwd: mode = HCG_LOSS_CE | (C << shift), n = B * C
+HCG_HEAD_FORWARD_ONLY, HCG_HEAD_LOSS_CE = 1, 2           # flags of hcg_head_fwd_bwd / hcg_head_deep_fwd_bwd
 HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2, HCG_WS_HEAD_DEEP = 0, 1, 2, 3, 4   # hcg_general_workspace_bytes kinds
 HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                          # hcg_fused_aux_bytes kinds
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
@@ -330,6 +332,14 @@ def layer_edge_grad(dout, out, h, rowptr, col, dinv, slope: float, apply_act: in
     a.rowptr, a.col, a.dinv, a.dew_csr = ptr(rowptr), ptr(col), ptr(dinv), ptr(dew_csr)
     a.slope, a.apply_act, a.N, a.E, a.D = slope, apply_act, N, E, D
     check(load().hcg_explain(ctypes.addressof(a), stream_ptr()), "hcg_explain (layer edge gradient)")
+
+
+def ce_fwd_bwd(logits, labels, loss, dout=None):
+    """hcg_loss_fwd_bwd in its cross-entropy mode: `logits` [B, C], `labels` [B] float32 class indices -> loss[0] = loss[1] =
+    nn.CrossEntropyLoss()(logits, labels.long()), `dout` (optional) = its gradient."""
+    B, C = logits.shape
+    check(load().hcg_loss_fwd_bwd(ptr(logits), ptr(labels), B * C, HCG_LOSS_CE | (C << HCG_LOSS_CE_CLASSES_SHIFT), ptr(loss),
+                                  ptr(dout), None, stream_ptr()), "hcg_loss_fwd_bwd (cross-entropy)")
 
 
 def job_bytes() -> int:

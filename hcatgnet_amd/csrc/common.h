@@ -78,6 +78,33 @@ __device__ __forceinline__ float hcg_rmsprop_update(float p, float g, float& v, 
 __device__ __forceinline__ float hcg_leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ float hcg_leaky_grad(float y_out, float slope) { return y_out > 0.f ? 1.f : slope; }
 
+// Cross-entropy of ONE graph (nn.CrossEntropyLoss with default settings on class-index targets): v[0 .. C) holds the
+// logits on entry and the error softmax(v)[c] - [c == label] on return (entries >= C: 0); returns the loss term
+// logsumexp(v) - v[label] as log(sum exp(v - max)) - (v[label] - max).  Class and label meet by comparing (float)c == label,
+// nothing is indexed by the label: a label that equals none of 0 .. C-1 (out of range, negative, not an integer, NaN) leaves
+// the NaN the term starts from.  expf / logf, not the fast intrinsics: at most RC values per graph.
+template <int RC>
+__device__ __forceinline__ float hcg_ce_row(float (&v)[RC], int C, float label) {
+  float m = v[0];
+#pragma unroll
+  for (int c = 1; c < RC; ++c)
+    if (c < C) m = fmaxf(m, v[c]);
+  float sum = 0.f, picked = __builtin_nanf("");
+#pragma unroll
+  for (int c = 0; c < RC; ++c) {
+    if (c < C) {
+      const float sh = v[c] - m;
+      if ((float)c == label) picked = sh;
+      v[c] = expf(sh);
+      sum += v[c];
+    }
+  }
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int c = 0; c < RC; ++c) v[c] = c < C ? v[c] * inv - ((float)c == label ? 1.f : 0.f) : 0.f;
+  return logf(sum) - picked;
+}
+
 // ---- internal launchers implemented in gemm.hip -------------------------------------------
 // C[M,N] = sum_k A(m,k) B(k,n), A(m,k) at A[m*sam + k*sak], B(k,n) at B[k*sbk + n*sbn];
 // epilogue: + bias[n] (nullable), LeakyReLU when act.  splits > 1: deterministic split-K through

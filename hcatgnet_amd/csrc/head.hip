@@ -11,7 +11,7 @@
 namespace {
 using namespace hcg_head;
 
-template <int RD, int RC, bool BACKWARD>
+template <int RD, int RC, bool BACKWARD, int LOSS = LOSS_SQ>
 __global__ __launch_bounds__(HC<RD>::NT, 1) void k_head(const float* __restrict__ emb, const float* __restrict__ y,
                                                        const float* __restrict__ W0, const float* __restrict__ b0,
                                                        const float* __restrict__ W1, const float* __restrict__ b1, int B, int C,
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(HC<RD>::NT, 1) void k_head(const float* __restrict_
   head_begin<RD, RC>(L, S, W0, b0, W1, b1, C);
   for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int g0 = t * RT, n = B - g0 < RT ? B - g0 : RT;
-    head_tile<RD, RC, BACKWARD>(L, S, [g0](int row) { return g0 + row; }, n, C, slope, emb, y, W0, z, out, demb);
+    head_tile<RD, RC, BACKWARD, LOSS>(L, S, [g0](int row) { return g0 + row; }, n, C, slope, emb, y, W0, z, out, demb);
   }
   head_end<RD, RC, BACKWARD>(L, S, C, slabs + (size_t)blockIdx.x * HC<RD>::SLAB, slabs + (size_t)gridDim.x * HC<RD>::SLAB + blockIdx.x);
 }
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(HC<RD>::NT, 1) void k_head(const float* __restrict_
 // waves, weight fragments in registers straight from L2): its per-tile chain is about half the 32-row code's, and without a
 // grid-wide exchange nothing ties the grid to one workgroup per 32 graphs -- 16 graphs per tile fill twice the CUs
 // (B = 4096: 256 workgroups instead of 128).
-template <int RC, bool BACKWARD>
+template <int RC, bool BACKWARD, int LOSS = LOSS_SQ>
 __global__ __launch_bounds__(hcg_head16::NT, 1) void k_head16(const float* __restrict__ emb, const float* __restrict__ y,
                                                              const float* __restrict__ W0, const float* __restrict__ b0,
                                                              const float* __restrict__ W1, const float* __restrict__ b1, int B,
@@ -45,19 +45,19 @@ __global__ __launch_bounds__(hcg_head16::NT, 1) void k_head16(const float* __res
   __shared__ h16::Lds L;
   if (step_counter && blockIdx.x == 0 && threadIdx.x == 0) { step_counter[0] += 1; step_counter[1] += 1; }
   h16::Prefetch<RC> P;
-  h16::prefetch<RC>(P, W0, b0, W1, C);
+  h16::prefetch<RC, LOSS>(P, W0, b0, W1, C);
   h16::State<RC> S;
-  h16::begin<RC>(S, b1, C);
+  h16::begin<RC, LOSS>(S, b1, C);
   constexpr int T16 = h16::RT;
   const int tiles = (B + T16 - 1) / T16;
   bool first = true;
   for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int g0 = t * T16, n = B - g0 < T16 ? B - g0 : T16;
-    h16::tile<RC, BACKWARD>(L, S, P, [g0](int row) { return g0 + row; }, n, C, slope, nullptr, emb, y, z, out, demb, first);
+    h16::tile<RC, BACKWARD, LOSS>(L, S, P, [g0](int row) { return g0 + row; }, n, C, slope, nullptr, emb, y, z, out, demb, first);
     first = false;
   }
   __syncthreads();
-  h16::end<RC, BACKWARD>(L, S, C, slabs + (size_t)blockIdx.x * h16::SLAB, slabs + (size_t)gridDim.x * h16::SLAB + blockIdx.x);
+  h16::end<RC, BACKWARD, LOSS>(L, S, C, slabs + (size_t)blockIdx.x * h16::SLAB, slabs + (size_t)gridDim.x * h16::SLAB + blockIdx.x);
 }
 
 // min(tiles of rt graphs, CUs)
@@ -91,24 +91,28 @@ extern "C" int hcg_head_fwd_bwd(const float* emb, const float* y, const float* W
                                 float* out, float* demb, void* workspace, size_t workspace_bytes, int32_t* step_counter,
                                 hcg_stream_t stream) {
   if (!hcg_head_supported(D, C)) return HCG_ERR_UNSUPPORTED;
-  if (flags & ~HCG_HEAD_FORWARD_ONLY) return HCG_ERR_INVALID_ARG;
-  const bool bwd = !(flags & HCG_HEAD_FORWARD_ONLY);
+  if (flags & ~(HCG_HEAD_FORWARD_ONLY | HCG_HEAD_LOSS_CE)) return HCG_ERR_INVALID_ARG;
+  const bool bwd = !(flags & HCG_HEAD_FORWARD_ONLY), ce = (flags & HCG_HEAD_LOSS_CE) != 0;
+  if (ce && C < 2) return HCG_ERR_INVALID_ARG;          // (a softmax over one class has nothing to learn)
   if (B <= 0 || !emb || !y || !W0 || !b0 || !W1 || !b1 || !z || !out || (bwd && !demb) || !workspace) return HCG_ERR_INVALID_ARG;
   if (workspace_bytes < hcg_head_workspace_bytes(B, D)) return HCG_ERR_WORKSPACE;
   const int grid = head_grid(B, D);
   float* slabs = (float*)workspace;
-#define LAUNCH_HEAD(RD_, RC_, BW)                                                                                         \
-  hipLaunchKernelGGL((k_head<RD_, RC_, BW>), dim3(grid), dim3(HC<RD_>::NT), 0, (hipStream_t)stream, emb, y, W0, b0, W1, b1,   \
-                     (int)B, (int)C, slope, z, out, demb, slabs, (int*)step_counter)
+#define LAUNCH_HEAD(RD_, RC_, BW, ...)                                                                                    \
+  hipLaunchKernelGGL((k_head<RD_, RC_, BW, ##__VA_ARGS__>), dim3(grid), dim3(HC<RD_>::NT), 0, (hipStream_t)stream, emb, y, W0, \
+                     b0, W1, b1, (int)B, (int)C, slope, z, out, demb, slabs, (int*)step_counter)
 #define DISPATCH_HEAD(RD_)                                                                            \
   do {                                                                                                \
     if (C == 1) { if (bwd) LAUNCH_HEAD(RD_, 1, true); else LAUNCH_HEAD(RD_, 1, false); }              \
     else        { if (bwd) LAUNCH_HEAD(RD_, RCMAX, true); else LAUNCH_HEAD(RD_, RCMAX, false); }      \
   } while (0)
-#define LAUNCH_HEAD16(RC_, BW)                                                                                            \
-  hipLaunchKernelGGL((k_head16<RC_, BW>), dim3(grid), dim3(hcg_head16::NT), 0, (hipStream_t)stream, emb, y, W0, b0, W1, b1,    \
-                     (int)B, (int)C, slope, z, out, demb, slabs, (int*)step_counter)
-  if (D == 128) {
+#define LAUNCH_HEAD16(RC_, BW, ...)                                                                                       \
+  hipLaunchKernelGGL((k_head16<RC_, BW, ##__VA_ARGS__>), dim3(grid), dim3(hcg_head16::NT), 0, (hipStream_t)stream, emb, y, W0, \
+                     b0, W1, b1, (int)B, (int)C, slope, z, out, demb, slabs, (int*)step_counter)
+  if (ce) {       // (two classes or more: the eight-class instantiations)
+    if (D == 128) { if (bwd) LAUNCH_HEAD(128, RCMAX, true, LOSS_CE); else LAUNCH_HEAD(128, RCMAX, false, LOSS_CE); }
+    else          { if (bwd) LAUNCH_HEAD16(RCMAX, true, LOSS_CE); else LAUNCH_HEAD16(RCMAX, false, LOSS_CE); }
+  } else if (D == 128) {
     DISPATCH_HEAD(128);
   } else if (C == 1) {
     if (bwd) LAUNCH_HEAD16(1, true); else LAUNCH_HEAD16(1, false);
@@ -163,8 +167,10 @@ struct Lds {
 };
 
 // layer I: x [n, K] -> LeakyReLU(x W^T + b) [n, K/2] into the next layer's input rows; the last layer: out = x W^T + b
-// [n, C] to global memory, the error out - y into d[0], the squared error into this thread's partial
-template <int D, int R, int I>
+// [n, C] to global memory, the error out - y into d[0], the squared error into this thread's partial.  LOSS_CE: the logits
+// go into d[0], and behind a barrier thread g < n turns graph g's row into softmax - onehot and adds the graph's loss term
+// to its partial (a second pass per row: the error needs all of a row's logits)
+template <int D, int R, int I, int LOSS = LOSS_SQ>
 __device__ __forceinline__ void fwd_layer(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float& sse) {
   constexpr int K = kin(D, I);
   constexpr bool LAST = I == R - 1;
@@ -187,9 +193,26 @@ __device__ __forceinline__ void fwd_layer(Lds<D, R>& L, const hcg_head_args& a, 
     } else {
       const size_t row = (size_t)(g0 + g) * C + o;
       a.out[row] = v;
-      const float e = v - a.y[row];
-      sse = fmaf(e, e, sse);
-      L.d[0][g * O + o] = e;
+      if constexpr (LOSS == LOSS_CE) {
+        L.d[0][g * O + o] = v;
+      } else {
+        const float e = v - a.y[row];
+        sse = fmaf(e, e, sse);
+        L.d[0][g * O + o] = e;
+      }
+    }
+  }
+  if constexpr (LAST && LOSS == LOSS_CE) {
+    __syncthreads();
+    if ((int)threadIdx.x < n) {
+      float* row = L.d[0] + threadIdx.x * C;
+      float v[RCMAX];
+#pragma unroll
+      for (int c = 0; c < RCMAX; ++c) v[c] = row[c < C ? c : 0];
+      sse += hcg_ce_row<RCMAX>(v, C, a.y[g0 + threadIdx.x]);
+#pragma unroll
+      for (int c = 0; c < RCMAX; ++c)
+        if (c < C) row[c] = v[c];
     }
   }
 }
@@ -197,7 +220,9 @@ __device__ __forceinline__ void fwd_layer(Lds<D, R>& L, const hcg_head_args& a, 
 // layer I's backward from the errors of its outputs (d[P], [n, O]): dW += d^T x, db += sum d (this workgroup's slab; the
 // first tile writes, later ones add), dx = d W -- times the LeakyReLU derivative of layer I - 1 into d[P ^ 1], or, for the
 // first layer, demb to global memory
-template <int D, int R, int I, int P>
+// (LOSS: the code does not depend on it, but an instantiation shared by the kernels of both losses changed the register
+//  allocation of the regression kernels that inline it)
+template <int D, int R, int I, int P, int LOSS = LOSS_SQ>
 __device__ __forceinline__ void bwd_layer(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float* __restrict__ slab,
                                           bool first) {
   constexpr int K = kin(D, I), K4 = K / 4;
@@ -248,21 +273,21 @@ __device__ __forceinline__ void bwd_layer(Lds<D, R>& L, const hcg_head_args& a, 
   }
 }
 
-template <int D, int R, int I = 0>
+template <int D, int R, int LOSS = LOSS_SQ, int I = 0>
 __device__ __forceinline__ void forward(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float& sse) {
-  fwd_layer<D, R, I>(L, a, n, g0, sse);
+  fwd_layer<D, R, I, LOSS>(L, a, n, g0, sse);
   __syncthreads();
-  if constexpr (I + 1 < R) forward<D, R, I + 1>(L, a, n, g0, sse);
+  if constexpr (I + 1 < R) forward<D, R, LOSS, I + 1>(L, a, n, g0, sse);
 }
 
-template <int D, int R, int I = R - 1>
+template <int D, int R, int LOSS = LOSS_SQ, int I = R - 1>
 __device__ __forceinline__ void backward(Lds<D, R>& L, const hcg_head_args& a, int n, int g0, float* slab, bool first) {
-  bwd_layer<D, R, I, (R - 1 - I) & 1>(L, a, n, g0, slab, first);
+  bwd_layer<D, R, I, (R - 1 - I) & 1, LOSS>(L, a, n, g0, slab, first);
   __syncthreads();
-  if constexpr (I > 0) backward<D, R, I - 1>(L, a, n, g0, slab, first);
+  if constexpr (I > 0) backward<D, R, LOSS, I - 1>(L, a, n, g0, slab, first);
 }
 
-template <int D, int R, bool BACKWARD>
+template <int D, int R, bool BACKWARD, int LOSS = LOSS_SQ>
 __global__ __launch_bounds__(NT, 1) void k_head_deep(const hcg_head_args a, int slab) {
   __shared__ Lds<D, R> L;
   if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 0) { a.step_counter[0] += 1; a.step_counter[1] += 1; }
@@ -276,8 +301,8 @@ __global__ __launch_bounds__(NT, 1) void k_head_deep(const hcg_head_args a, int 
     const float4* e4 = reinterpret_cast<const float4*>(a.emb + (size_t)g0 * (2 * D));
     for (int idx = threadIdx.x; idx < n * (2 * D / 4); idx += NT) reinterpret_cast<float4*>(L.act)[idx] = e4[idx];
     __syncthreads();
-    forward<D, R>(L, a, n, g0, sse);
-    if constexpr (BACKWARD) backward<D, R>(L, a, n, g0, own, first);
+    forward<D, R, LOSS>(L, a, n, g0, sse);
+    if constexpr (BACKWARD) backward<D, R, LOSS>(L, a, n, g0, own, first);
     first = false;
   }
   // this workgroup's SSE partial: a fixed tree over the threads' fixed-order partials
@@ -309,8 +334,9 @@ extern "C" int hcg_head_deep_fwd_bwd(const hcg_head_args* args, hcg_reduce_job* 
   if (!args) return HCG_ERR_INVALID_ARG;
   const hcg_head_args& a = *args;
   if (!deep_supported(a.D, a.C, a.R)) return HCG_ERR_UNSUPPORTED;
-  if (a.flags & ~HCG_HEAD_FORWARD_ONLY) return HCG_ERR_INVALID_ARG;
-  const bool bwd = !(a.flags & HCG_HEAD_FORWARD_ONLY);
+  if (a.flags & ~(HCG_HEAD_FORWARD_ONLY | HCG_HEAD_LOSS_CE)) return HCG_ERR_INVALID_ARG;
+  const bool bwd = !(a.flags & HCG_HEAD_FORWARD_ONLY), ce = (a.flags & HCG_HEAD_LOSS_CE) != 0;
+  if (ce && a.C < 2) return HCG_ERR_INVALID_ARG;
   if (a.B <= 0 || a.B * a.D * 2 > INT32_MAX || !a.emb || !a.y || !a.out || !a.workspace || !aligned16(a.emb)) return HCG_ERR_INVALID_ARG;
   if (bwd && (!a.demb || !aligned16(a.demb))) return HCG_ERR_INVALID_ARG;
   for (int i = 0; i < a.R; ++i)
@@ -330,10 +356,13 @@ extern "C" int hcg_head_deep_fwd_bwd(const hcg_head_args* args, hcg_reduce_job* 
       job->seg[i] = hcg_reduce_seg{deep::seg_off((int)a.D, i), n, n, n, a.grad[i]};
     }
   }
+#define LAUNCH_DEEP_(D_, R_, BW, LOSS_) \
+  hipLaunchKernelGGL((deep::k_head_deep<D_, R_, BW, LOSS_>), dim3(grid), dim3(deep::NT), 0, (hipStream_t)stream, a, slab)
 #define LAUNCH_DEEP(D_, R_)                                                                                             \
   do {                                                                                                                  \
-    if (bwd) hipLaunchKernelGGL((deep::k_head_deep<D_, R_, true>), dim3(grid), dim3(deep::NT), 0, (hipStream_t)stream, a, slab);  \
-    else hipLaunchKernelGGL((deep::k_head_deep<D_, R_, false>), dim3(grid), dim3(deep::NT), 0, (hipStream_t)stream, a, slab);     \
+    if (ce) { if (bwd) LAUNCH_DEEP_(D_, R_, true, LOSS_CE); else LAUNCH_DEEP_(D_, R_, false, LOSS_CE); }                \
+    else if (bwd) LAUNCH_DEEP_(D_, R_, true, LOSS_SQ);                                                                  \
+    else LAUNCH_DEEP_(D_, R_, false, LOSS_SQ);                                                                          \
   } while (0)
   if (a.D == 64) {
     if (a.R == 1) LAUNCH_DEEP(64, 1); else if (a.R == 3) LAUNCH_DEEP(64, 3); else LAUNCH_DEEP(64, 4);
@@ -341,6 +370,7 @@ extern "C" int hcg_head_deep_fwd_bwd(const hcg_head_args* args, hcg_reduce_job* 
     if (a.R == 1) LAUNCH_DEEP(128, 1); else if (a.R == 3) LAUNCH_DEEP(128, 3); else LAUNCH_DEEP(128, 4);
   }
 #undef LAUNCH_DEEP
+#undef LAUNCH_DEEP_
   HCG_CHECK_LAUNCH();
   return HCG_OK;
 }

@@ -22,6 +22,12 @@ __device__ __forceinline__ void results_fence(f32x16& a) { asm volatile("s_nop 1
 
 constexpr int RT = 32;            // graphs per tile
 constexpr int RCMAX = 8;
+// The loss behind the head, a template parameter of the tile code that defaults to the squared error (the regression
+// instantiations -- and the tail of the small-graph forward, regression only -- compile as they always did).  LOSS_CE =
+// nn.CrossEntropyLoss()(out, y.long()): y holds ONE float per graph, the class index; the error the backward runs on is
+// softmax(out) - onehot, the per-graph loss term logsumexp(out) - out[label] takes the place of the squared error in the
+// workgroup's partial, and the deferred scale is 1 / B (common.h: hcg_ce_row; reduce.hip: HCG_LOSS_CE).
+constexpr int LOSS_SQ = 0, LOSS_CE = 1;
 
 // Shapes of the head for hidden width RD (= embedding_dim: 64, the reference's default, options/base_options.py:199-204;
 // 128 = BASELINE configs[4]).  Wave roles: forward = RD/32 output column blocks x 2 K halves -> HW = RD/16 waves (4 / 8);
@@ -133,7 +139,7 @@ __device__ __forceinline__ void head_begin(HeadLds<RD>& L, HeadState<RD, RC>& S,
 
 // One tile: rows [0, n) are graphs gmap(row) (ascending), rows >= n are padding.  `BACKWARD` false: forward + squared
 // error only.  Every thread of the block must call it (workgroup barriers inside); threads >= NT only take the barriers.
-template <int RD, int RC, bool BACKWARD, class GMap>
+template <int RD, int RC, bool BACKWARD, int LOSS = LOSS_SQ, class GMap>
 __device__ __forceinline__ void head_tile(HeadLds<RD>& L, HeadState<RD, RC>& S, GMap gmap, int n, int C, float slope,
                                           const float* __restrict__ emb, const float* __restrict__ y,
                                           const float* __restrict__ W0, float* __restrict__ z, float* __restrict__ out,
@@ -154,8 +160,12 @@ __device__ __forceinline__ void head_tile(HeadLds<RD>& L, HeadState<RD, RC>& S, 
   float4 ev[ITER];
   if (active) {
     const int gy = gmap(orow < n ? orow : last);
+    if constexpr (LOSS == LOSS_CE) {
+      yv[0] = y[gy];                                    // the graph's class index
+    } else {
 #pragma unroll
-    for (int c = 0; c < RC; ++c) yv[c] = y[(size_t)gy * C + (c < C ? c : C - 1)];
+      for (int c = 0; c < RC; ++c) yv[c] = y[(size_t)gy * C + (c < C ? c : C - 1)];
+    }
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
       const int idx = threadIdx.x + it * NT, row = idx / PER_ROW, c4 = idx - row * PER_ROW;
@@ -241,17 +251,35 @@ __device__ __forceinline__ void head_tile(HeadLds<RD>& L, HeadState<RD, RC>& S, 
 #pragma unroll
         for (int off = 1; off < OJ; off <<= 1) s += __shfl_xor(s, off, 64);
         if (oj == 0) {
-          float d = 0.f;
-          if (orow < n) {
+          if constexpr (LOSS == LOSS_CE) {
             s += S.b1v[c];
-            out[(size_t)go * C + c] = s;
-            d = s - yv[c];
-            S.sse += d * d;
+            if (orow < n) out[(size_t)go * C + c] = s;
+            L.diff[orow][c] = s;                       // the logit: this thread turns its row into errors below
+          } else {
+            float d = 0.f;
+            if (orow < n) {
+              s += S.b1v[c];
+              out[(size_t)go * C + c] = s;
+              d = s - yv[c];
+              S.sse += d * d;
+            }
+            L.diff[orow][c] = d;
           }
-          L.diff[orow][c] = d;
         }
       } else if (oj == 0) {
         L.diff[orow][c] = 0.f;
+      }
+    }
+    if constexpr (LOSS == LOSS_CE) {
+      // the row's logits (this thread's own LDS entries) -> softmax - onehot, and the graph's loss term
+      if (oj == 0) {
+        float v[RC];
+#pragma unroll
+        for (int c = 0; c < RC; ++c) v[c] = L.diff[orow][c];
+        const float term = hcg_ce_row<RC>(v, C, yv[0]);
+        if (orow < n) S.sse += term;
+#pragma unroll
+        for (int c = 0; c < RC; ++c) L.diff[orow][c] = orow < n ? v[c] : 0.f;
       }
     }
   }
@@ -468,6 +496,8 @@ __device__ unsigned long long g_h16_stamp[4][8][16];
 namespace hcg_head16 {
 
 using hcg_head::RCMAX;
+using hcg_head::LOSS_SQ;
+using hcg_head::LOSS_CE;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void results_fence(f32x4& a) { asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(a)); }
 
@@ -517,7 +547,9 @@ struct State {
 };
 
 // loads only (no LDS access): safe while other waves are still inside their tiles
-template <int RC>
+// (prefetch / begin / end take the tile's LOSS although their code does not depend on it: an instantiation shared by the
+//  kernels of both losses changed the register allocation of the regression kernel that inlines it)
+template <int RC, int LOSS = LOSS_SQ>
 __device__ __forceinline__ void prefetch(Prefetch<RC>& P, const float* __restrict__ W0, const float* __restrict__ b0,
                                          const float* __restrict__ W1, int C) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -533,7 +565,7 @@ __device__ __forceinline__ void prefetch(Prefetch<RC>& P, const float* __restric
   P.bz = b0[cb * 16 + r16];
 }
 
-template <int RC>
+template <int RC, int LOSS = LOSS_SQ>
 __device__ __forceinline__ void begin(State<RC>& S, const float* __restrict__ b1, int C) {
   S.sse = 0.f;
 #pragma unroll
@@ -545,7 +577,7 @@ __device__ __forceinline__ void begin(State<RC>& S, const float* __restrict__ b1
 
 // One tile of n <= 16 graphs.  `erows`: their pooled rows in LDS (stride ES), or nullptr -> copied from global `emb`.
 // The caller has put a workgroup barrier between the writers of `erows` and this call.
-template <int RC, bool BACKWARD, class GMap>
+template <int RC, bool BACKWARD, int LOSS = LOSS_SQ, class GMap>
 __device__ __forceinline__ void tile(Lds& L, State<RC>& S, const Prefetch<RC>& P, GMap gmap, int n, int C, float slope,
                                      const float* erows, const float* __restrict__ emb, const float* __restrict__ y,
                                      float* __restrict__ z, float* __restrict__ out, float* __restrict__ demb, bool first) {
@@ -557,8 +589,12 @@ __device__ __forceinline__ void tile(Lds& L, State<RC>& S, const Prefetch<RC>& P
   float yv[RC];
   if (threadIdx.x < 256) {
     const int gy = gmap(prow < n ? prow : last);
+    if constexpr (LOSS == LOSS_CE) {
+      yv[0] = y[gy];                                    // the graph's class index
+    } else {
 #pragma unroll
-    for (int c = 0; c < RC; ++c) yv[c] = y[(size_t)gy * C + (c < C ? c : C - 1)];
+      for (int c = 0; c < RC; ++c) yv[c] = y[(size_t)gy * C + (c < C ? c : C - 1)];
+    }
   }
   if (erows == nullptr) {       // block-uniform: more graphs per workgroup than the caller keeps in LDS
     const int row = threadIdx.x >> 5, c4 = threadIdx.x & 31;     // 16 rows x 32 float4
@@ -619,6 +655,38 @@ __device__ __forceinline__ void tile(Lds& L, State<RC>& S, const Prefetch<RC>& P
     const bool live = prow < n;
     float4 dz = make_float4(0.f, 0.f, 0.f, 0.f);
     const int go = gmap(live ? prow : last);
+    if constexpr (LOSS == LOSS_CE) {
+      // the butterflies leave ALL of the row's logits in every lane of the row: each lane derives the row's errors itself
+      // (the same arithmetic on the same values), still without an exchange
+      float ev[RC];
+#pragma unroll
+      for (int c = 0; c < RC; ++c) {
+        ev[c] = 0.f;
+        if (c < C) {                                   // block-uniform
+          const float4 w = P.w1r[c];
+          float s = __fmaf_rn(zz.w, w.w, __fmaf_rn(zz.z, w.z, __fmaf_rn(zz.y, w.y, zz.x * w.x)));
+#pragma unroll
+          for (int off = 1; off < 16; off <<= 1) s += __shfl_xor(s, off, 64);
+          s += S.b1v[c];
+          if (q == 0 && live) out[(size_t)go * C + c] = s;
+          ev[c] = s;
+        }
+      }
+      const float term = hcg_ce_row<RC>(ev, C, yv[0]);
+      if (q == 0 && live) S.sse += term;
+      if (BACKWARD) {
+#pragma unroll
+        for (int c = 0; c < RC; ++c) {
+          if (c < C) {
+            const float4 w = P.w1r[c];
+            const float d = live ? ev[c] : 0.f;
+            dz.x += d * w.x; dz.y += d * w.y; dz.z += d * w.z; dz.w += d * w.w;
+            S.dw1[c].x += d * zz.x; S.dw1[c].y += d * zz.y; S.dw1[c].z += d * zz.z; S.dw1[c].w += d * zz.w;
+            if (q == 0) S.db1[c] += d;
+          }
+        }
+      }
+    } else {
 #pragma unroll
     for (int c = 0; c < RC; ++c) {
       if (c < C) {                                     // block-uniform
@@ -640,6 +708,7 @@ __device__ __forceinline__ void tile(Lds& L, State<RC>& S, const Prefetch<RC>& P
           if (q == 0) S.db1[c] += d;
         }
       }
+    }
     }
     if (BACKWARD) {
       dz.x *= hcg_leaky_grad(zz.x, slope); dz.y *= hcg_leaky_grad(zz.y, slope);
@@ -688,7 +757,7 @@ __device__ __forceinline__ void tile(Lds& L, State<RC>& S, const Prefetch<RC>& P
   H16STAMP(8);
 }
 
-template <int RC, bool BACKWARD>
+template <int RC, bool BACKWARD, int LOSS = LOSS_SQ>
 __device__ __forceinline__ void end(Lds& L, State<RC>& S, int C, float* __restrict__ slab, float* __restrict__ sse_out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, kq = lane >> 4, q = threadIdx.x & 15;

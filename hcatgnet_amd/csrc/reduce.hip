@@ -107,11 +107,13 @@ __device__ __forceinline__ float xchg_gather(const XchgArgs& X, int parity, int6
 // of squared errors per workgroup behind its slabs (hcg_reduce_job.sse_part); every block of THIS launch adds them in the same
 // fixed order (bitwise the same scale everywhere), and the scale multiplies each gradient element as it is reduced --
 // no grid-wide exchange, no launch of its own (round 2's head kernel spent a grid barrier on this scalar).
+// HCG_LOSS_CE (a head launched with HCG_HEAD_LOSS_CE): the backward ran on softmax(out) - onehot, the partials are sums of
+// per-graph terms logsumexp(out) - out[label], count = B: loss = sum / count, scale 1 / count.
 struct LossArgs {
   const float* sse_part;    // [nparts] partials; nullptr = the slabs hold final gradients (scale 1)
   int nparts;
-  float count;              // elements of the squared-error sum on this rank (B * C)
-  int mode;                 // HCG_LOSS_MSE / HCG_LOSS_RMSE / HCG_LOSS_SSE
+  float count;              // elements of the squared-error sum on this rank (B * C); HCG_LOSS_CE: graphs (B)
+  int mode;                 // HCG_LOSS_MSE / HCG_LOSS_RMSE / HCG_LOSS_SSE / HCG_LOSS_CE
   float* loss;              // [2] nullable: the loss, the MSE
   float* sse_tail;          // [2] nullable: this rank's SSE and count (data-parallel "sse" form with a collective)
 };
@@ -167,8 +169,9 @@ __global__ __launch_bounds__(256) void k_step_tail(Jobs jobs, UpdateArgs A, Plan
       const float mse = sse / cnt, lv = sqrtf(mse);
       if (L.mode == HCG_LOSS_RMSE) pre = 1.0f / (cnt * lv);
       else if (L.mode == HCG_LOSS_MSE) pre = 2.0f / cnt;
+      else if (L.mode == HCG_LOSS_CE) pre = 1.0f / cnt;
       if (first && lane == 0) {
-        if (L.loss && !(XCHG && X.mode == HCG_XCHG_SSE)) { L.loss[0] = L.mode == HCG_LOSS_MSE ? mse : lv; L.loss[1] = mse; }
+        if (L.loss && !(XCHG && X.mode == HCG_XCHG_SSE)) { L.loss[0] = L.mode == HCG_LOSS_RMSE || L.mode == HCG_LOSS_SSE ? lv : mse; L.loss[1] = mse; }
         if (L.sse_tail) { L.sse_tail[0] = sse; L.sse_tail[1] = cnt; }
       }
     } else if (XCHG) {
@@ -251,7 +254,7 @@ __global__ __launch_bounds__(64) void k_loss_finalize(LossArgs L) {
   const float sse = loss_sse_sum(L, threadIdx.x);
   if (threadIdx.x == 0) {
     const float mse = sse / L.count;
-    L.loss[0] = L.mode == HCG_LOSS_MSE ? mse : sqrtf(mse);
+    L.loss[0] = L.mode == HCG_LOSS_MSE || L.mode == HCG_LOSS_CE ? mse : sqrtf(mse);
     L.loss[1] = mse;
     if (L.sse_tail) { L.sse_tail[0] = sse; L.sse_tail[1] = L.count; }
   }
@@ -271,7 +274,8 @@ static int loss_args_from_jobs(const hcg_reduce_job* jobs_host, int njobs, float
     L.nparts = J.nslabs;
   }
   if (L.sse_part) {
-    if (!(count > 0.f) || (mode != HCG_LOSS_MSE && mode != HCG_LOSS_RMSE && mode != HCG_LOSS_SSE)) return HCG_ERR_INVALID_ARG;
+    if (!(count > 0.f) || (mode != HCG_LOSS_MSE && mode != HCG_LOSS_RMSE && mode != HCG_LOSS_SSE && mode != HCG_LOSS_CE))
+      return HCG_ERR_INVALID_ARG;
     L.count = count; L.mode = mode; L.loss = loss; L.sse_tail = sse_tail;
   }
   *out = L;
@@ -343,6 +347,7 @@ extern "C" int hcg_step_tail(const hcg_tail_args* a, hcg_stream_t stream_) {
     if (a->world < 1 || a->world > HCG_XCHG_MAX_WORLD || a->rank < 0 || a->rank >= a->world ||
         (a->xchg_mode != HCG_XCHG_MEAN && a->xchg_mode != HCG_XCHG_SSE))
       return HCG_ERR_INVALID_ARG;
+    if (a->xchg_mode == HCG_XCHG_SSE && a->loss_mode == HCG_LOSS_CE) return HCG_ERR_INVALID_ARG;   // (sqrt(MSE) over all ranks: squared error only)
     X.inbox = (unsigned long long*)a->inbox;
     for (int p = 0; p < a->world; ++p) {
       if (!a->peers_host[p]) return HCG_ERR_INVALID_ARG;

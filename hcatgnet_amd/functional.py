@@ -539,6 +539,36 @@ def mse_loss(inp, target):
     return _MSEFn.apply(inp, target)
 
 
+class _CrossEntropyFn(torch.autograd.Function):
+    """`nn.CrossEntropyLoss()(logits, target.long())` -- mean over the graphs of logsumexp(logits) - logits[target], default
+    settings, no sqrt -- in one launch (csrc/loss.hip: k_ce_fwd_bwd leaves the loss AND d loss / d logits); the backward is
+    that gradient times the incoming one."""
+
+    @staticmethod
+    def forward(ctx, logits, target):
+        _lib.require_gpu(logits, target)
+        if logits.dim() != 2 or target.shape != logits.shape[:1]:
+            raise ValueError(f"CrossEntropyLoss: logits {tuple(logits.shape)} need class-index targets of shape "
+                             f"({logits.shape[0]},), got {tuple(target.shape)}")
+        a = _f32c(logits)
+        y = target.to(torch.float32).contiguous()           # (class indices: exact in float32)
+        loss = torch.empty(2, dtype=torch.float32, device=a.device)
+        dout = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        _lib.ce_fwd_bwd(a, y, loss, dout)
+        ctx.save_for_backward(dout)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dout,) = ctx.saved_tensors
+        return (None if dout is None else dout * g), None
+
+
+def cross_entropy(logits, target):
+    """Cross-entropy of float32 GPU logits [B, C] against class indices [B] (int64, or floats holding integers)."""
+    return _CrossEntropyFn.apply(logits, target)
+
+
 def readout2_supported(D: int, C: int) -> bool:
     return D == 64 and bool(_lib.load().hcg_head_supported(D, C))
 

@@ -22,6 +22,26 @@ class MSELoss(nn.Module):
         return HF.mse_loss(inp, target)
 
 
+class CrossEntropyLoss(nn.CrossEntropyLoss):
+    """`nn.CrossEntropyLoss` for `--problem_type classification`.  The reference's own training line cannot execute for a
+    classification model (`torch.sqrt(model.loss(out, y.unsqueeze(1)))` is rejected by torch), so the definition here is
+    the minimal reading of it: `loss = nn.CrossEntropyLoss()(out, y.long())` with `out` [B, C] and `y` [B] holding class
+    indices, the mean over the graphs of the batch, no sqrt and no unsqueeze.  With default settings, float32 MI355X logits
+    and class-index targets it is one HIP launch each way (csrc/loss.hip: k_ce_fwd_bwd); anything else -- class weights,
+    label smoothing, another reduction, `ignore_index`, class-probability targets, CPU tensors -- is torch's own forward."""
+
+    def default_settings(self) -> bool:
+        return (self.weight is None and self.reduction == "mean" and self.label_smoothing == 0.0
+                and self.ignore_index == -100)
+
+    def forward(self, inp, target):
+        if (self.default_settings() and inp.is_cuda and inp.dtype == torch.float32 and inp.dim() == 2
+                and target.dim() == 1 and target.dtype == torch.int64 and target.shape[0] == inp.shape[0]):
+            from . import functional as HF
+            return HF.cross_entropy(inp, target)
+        return super().forward(inp, target)
+
+
 class BaseNetwork(nn.Module):
     def __init__(self, opt: argparse.Namespace, n_node_features: int):
         super().__init__()
@@ -43,7 +63,7 @@ class BaseNetwork(nn.Module):
 
     def _make_loss(self, problem_type, mae=None):
         if problem_type == "classification":
-            self.loss = nn.CrossEntropyLoss()
+            self.loss = CrossEntropyLoss()
         elif problem_type == "regression" and mae is None:
             self.loss = MSELoss()
         else:

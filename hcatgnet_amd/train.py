@@ -32,6 +32,28 @@ import torch.distributed
 from . import _lib
 from . import functional as HF
 
+def _is_cross_entropy(model) -> bool:
+    """`--problem_type classification`: the model's loss is an `nn.CrossEntropyLoss` (networks.CrossEntropyLoss)."""
+    return isinstance(getattr(model, "loss", None), torch.nn.CrossEntropyLoss)
+
+
+def _cross_entropy_reason(model) -> Optional[str]:
+    """Why the fused step does not take this cross-entropy model (None: it does).  The kernels compute
+    `nn.CrossEntropyLoss()(out, y.long())` with default settings over two classes or more."""
+    loss = model.loss
+    if loss.weight is not None:
+        return "cross-entropy with class weights (weight is not None)"
+    if loss.reduction != "mean":
+        return f"cross-entropy with reduction={loss.reduction!r} (only 'mean')"
+    if loss.label_smoothing != 0.0:
+        return f"cross-entropy with label_smoothing={loss.label_smoothing}"
+    if loss.ignore_index != -100:
+        return f"cross-entropy with ignore_index={loss.ignore_index}"
+    if model._n_classes < 2:
+        return f"cross-entropy with n_classes={model._n_classes} (needs 2 or more)"
+    return None
+
+
 def _head_deep_supported(D: int, C: int, R: int) -> bool:
     """A readout of depth R at width D with C outputs has the one-launch head of csrc/head.hip (k_head_deep)."""
     return _lib.load().hcg_general_workspace_bytes(_lib.HCG_WS_HEAD_DEEP, 1, D, C, R) > 0
@@ -66,6 +88,15 @@ class FusedTrainStep:
     ranks and ONE scale 1 / (count * sqrt(SSE / count)) gives the gradient of sqrt(MSE) over the concatenated batch of all
     ranks -- what the reference's step computes on one device (utils/utils_model.py:64-65); the loss returned is then that
     global loss.
+
+    Classification (`--problem_type classification`, a model whose loss is `nn.CrossEntropyLoss` with default settings --
+    no class weights, reduction "mean", no label smoothing -- and two classes or more): the reference's training line
+    cannot execute for such a model, so the loss is the minimal reading of it, `nn.CrossEntropyLoss()(out, y.long())`
+    with `out` [B, C] and `y` [B] holding class indices: the mean over the graphs of the batch, no sqrt, no unsqueeze
+    (`rmse` does not apply).  The same split carries it: the head runs its backward on softmax(out) - onehot and leaves a
+    partial sum of per-graph terms logsumexp(out) - out[label], the deferred scale is 1 / B (HCG_LOSS_CE).  The head is a
+    launch of its own (the one riding in the forward launch is regression-only), `y` may be int64 or float32, a label outside
+    0 .. C-1 makes the loss NaN, and `combine="sse"` is refused: it is a property of the squared error.
     """
 
     # development switches for A/B measurements (tools/ab_env.sh sets them from the environment; never set in product
@@ -87,6 +118,9 @@ class FusedTrainStep:
             raise ValueError(f"combine must be 'mean' or 'sse', got {combine!r}")
         if combine == "sse" and not rmse:
             raise ValueError("combine='sse' reproduces sqrt(MSE) over the concatenated batch: it needs rmse=True")
+        if combine == "sse" and _is_cross_entropy(model):
+            raise ValueError("combine='sse' reproduces sqrt(MSE) over the concatenated batch: a cross-entropy model takes "
+                             "combine='mean'")
         self.model, self.rmse, self.optimizer_step, self.grad_sync = model, rmse, optimizer_step, grad_sync
         self.combine = combine
         if optimizer_step and hasattr(model.optimizer, "enable_capturable"):
@@ -157,8 +191,12 @@ class FusedTrainStep:
                     f"head's exceed the step tail's {_lib.HCG_REDUCE_MAX_JOBS} jobs")
         # (heads the one-launch kernel does not cover -- widths other than 64 / 128 -- run as five launches of the any-shape
         #  kernels inside the same no-autograd step)
-        if type(model.loss).__name__ != "MSELoss":
-            return "loss other than MSE"
+        if _is_cross_entropy(model):
+            why = _cross_entropy_reason(model)
+            if why is not None:
+                return why
+        elif type(model.loss).__name__ != "MSELoss":
+            return "loss other than MSE or cross-entropy"
         if not all(q.requires_grad for q in (model.parameters() if _params is None else _params)):
             return "frozen parameters (the fused backward writes every gradient)"
         if batch is not None:
@@ -312,9 +350,16 @@ class FusedTrainStep:
         c.lins = [m[0] if isinstance(m, torch.nn.Sequential) else m for m in model.readout]
         c.N, c.F, c.B, c.D, c.C = x.shape[0], x.shape[1], plan.B, model.embedding_dim, model._n_classes
         c.n_conv, c.dev = len(convs), x.device
-        c.y2 = HF._f32c(y).reshape(c.B, -1)
-        if c.y2.shape[1] != c.C:
-            raise ValueError(f"targets have {c.y2.shape[1]} columns, the model predicts {c.C}")
+        ce = _is_cross_entropy(model)
+        if ce:
+            # one class index per graph, as float32 (what the stores and loaders keep; int64 labels are converted)
+            c.y2 = (y if y.dtype == torch.float32 else y.to(torch.float32)).contiguous().reshape(-1)
+            if c.y2.shape[0] != c.B:
+                raise ValueError(f"classification targets hold {c.y2.shape[0]} class indices for {c.B} graphs")
+        else:
+            c.y2 = HF._f32c(y).reshape(c.B, -1)
+            if c.y2.shape[1] != c.C:
+                raise ValueError(f"targets have {c.y2.shape[1]} columns, the model predicts {c.C}")
         # (kernel family, graphs_per_tile) of every layer (functional.conv_route)
         c.routes = [HF.conv_route(plan, cv.in_channels, cv.out_channels, getattr(cv, "family", "auto")) for cv in convs]
         if (None, 0) in c.routes:
@@ -337,6 +382,8 @@ class FusedTrainStep:
         dp_sync = self.grad_sync is not None or self.exchange is not None or self._capturing_split
         c.sse_split = self.combine == "sse" and dp_sync and not forward_only
         c.loss_mode = _lib.HCG_LOSS_SSE if c.sse_split else (_lib.HCG_LOSS_RMSE if self.rmse else _lib.HCG_LOSS_MSE)
+        if ce:
+            c.loss_mode = _lib.HCG_LOSS_CE              # (`rmse` does not apply; "sse" was refused at construction)
         if not forward_only:
             params = self._trainable()
             c.flat = self._flat_grads(params, c.dev)
@@ -404,6 +451,7 @@ class FusedTrainStep:
         """The C3 form: both conv layers on small-graph tiles, pooled layer on chip, one-launch head -> everything up to
         the loss is ONE launch."""
         return (self.HEAD_IN_FORWARD and self.POOLBITS and c.n_small is None and c.n_conv == 2 and c.head_fused
+                and c.loss_mode != _lib.HCG_LOSS_CE      # (the head in the forward launch is regression-only)
                 and len(c.lins) == 2 and c.routes[0][0] is HF.TILES and c.routes[0] == c.routes[1])
 
     def _forward_with_head(self, c: _Ctx):
@@ -493,7 +541,7 @@ class FusedTrainStep:
         emb, z, out = bufs["emb"], bufs["z"], bufs["out"]
         if c.head_fused:
             rc = lib.hcg_head_fwd_bwd(p(emb), p(c.y2), p(W0), p(b0), p(W1), p(b1), B, D, C, slope,
-                                      _lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0, p(z), p(out), p(bufs["demb"]),
+                                      self._head_flags(c), p(z), p(out), p(bufs["demb"]),
                                       p(bufs["ws_head"]), bufs["ws_head_bytes"], p(c.step_word), stream)
             _lib.check(rc, "hcg_head_fwd_bwd")
             g = (lambda q: self._g(c, q)) if not c.forward_only else (lambda q: None)
@@ -507,8 +555,11 @@ class FusedTrainStep:
         tail = self._flat_ext[c.flat.numel():] if c.sse_split else None
         _lib.check(lib.hcg_linear_fwd(p(emb), p(W0), p(b0), p(z), B, 2 * D, D, _lib.HCG_ACT_LEAKY, slope, stream), "hcg_linear_fwd")
         _lib.check(lib.hcg_linear_fwd(p(z), p(W1), p(b1), p(out), B, D, C, _lib.HCG_ACT_NONE, slope, stream), "hcg_linear_fwd")
-        _lib.check(lib.hcg_loss_fwd_bwd(p(out), p(c.y2), B * C, c.loss_mode, p(bufs["loss"]), p(hb["dout"]), p(tail), stream),
-                   "hcg_loss_fwd_bwd")
+        if c.loss_mode == _lib.HCG_LOSS_CE:
+            _lib.ce_fwd_bwd(out, c.y2, bufs["loss"], None if c.forward_only else hb["dout"])
+        else:
+            _lib.check(lib.hcg_loss_fwd_bwd(p(out), p(c.y2), B * C, c.loss_mode, p(bufs["loss"]), p(hb["dout"]), p(tail),
+                                            stream), "hcg_loss_fwd_bwd")
         if c.forward_only:
             return
         g = lambda q: self._g(c, q)
@@ -516,6 +567,11 @@ class FusedTrainStep:
                                       B, D, C, _lib.HCG_ACT_NONE, slope, p(hb["ws1"]), hb["ws1"].numel(), stream), "hcg_linear_bwd")
         _lib.check(lib.hcg_linear_bwd(p(hb["dz"]), p(z), p(emb), p(W0), p(bufs["demb"]), g(l0.weight), g(l0.bias), p(hb["dz_ws0"]),
                                       B, 2 * D, D, _lib.HCG_ACT_LEAKY, slope, p(hb["ws0"]), hb["ws0"].numel(), stream), "hcg_linear_bwd")
+
+    @staticmethod
+    def _head_flags(c: _Ctx) -> int:
+        return ((_lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0)
+                | (_lib.HCG_HEAD_LOSS_CE if c.loss_mode == _lib.HCG_LOSS_CE else 0))
 
     def _head_deep(self, c: _Ctx):
         """Readout depth 1, 3 or 4: one launch with the contract of `hcg_head_fwd_bwd` (csrc/head.hip: k_head_deep), its
@@ -535,7 +591,7 @@ class FusedTrainStep:
                 if self._g(c, lin.bias) != a.grad[i] + 4 * lin.weight.numel():      # (parameter order keeps them adjacent)
                     raise _lib.HcgError("readout bias gradient not directly behind its weight's in the flat buffer")
         a.B, a.D, a.C, a.R = c.B, c.D, c.C, R
-        a.flags, a.slope = (_lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0), HF.LEAKY_SLOPE
+        a.flags, a.slope = self._head_flags(c), HF.LEAKY_SLOPE
         _lib.check(lib.hcg_head_deep_fwd_bwd(ctypes.addressof(a), c.jobs.slot(), _lib.stream_ptr()), "hcg_head_deep_fwd_bwd")
         c.jobs.n += 1
 
@@ -646,7 +702,7 @@ class FusedTrainStep:
         """The step's last launch: slab reductions -> ONE flat gradient, the loss and its scale, (exchange,) update, the next
         batch's plan.  With a collective between backward and update the launch stops at the gradient."""
         opt, bufs = self.model.optimizer, c.bufs
-        count = float(c.B * c.C)
+        count = self._loss_count(c)
         self._last_carried = c.step_word is not None
         if c.step_word is not None:
             if self.exchange is not None and self.pre_exchange_hook is not None:
@@ -663,11 +719,16 @@ class FusedTrainStep:
         if not self._capturing_split:
             self._exchange_and_update(bufs["loss"], c.sse_split)
 
+    @staticmethod
+    def _loss_count(c: _Ctx) -> float:
+        """Terms of the head's partial sums: B * C squared errors, or B per-graph cross-entropy terms."""
+        return float(c.B if c.loss_mode == _lib.HCG_LOSS_CE else c.B * c.C)
+
     def _finish_forward_only(self, c: _Ctx):
         """Forward-only steps (the reference's eval_network body, utils/utils_model.py:75-78): the loss from the head's SSE
         partials, one tiny launch."""
         if c.head_fused:
-            _lib.check(_lib.load().hcg_loss_finalize(c.jobs.addr, float(c.B * c.C), c.loss_mode, _lib.ptr(c.bufs["loss"]), None,
+            _lib.check(_lib.load().hcg_loss_finalize(c.jobs.addr, self._loss_count(c), c.loss_mode, _lib.ptr(c.bufs["loss"]), None,
                                                      _lib.stream_ptr()), "hcg_loss_finalize")
         self.last_out = c.bufs["out"]
         return c.bufs["loss"][0]
@@ -1104,7 +1165,12 @@ class EpochWindow:
 # the reference's loops (same names / arguments / return values)
 # ---------------------------------------------------------------------------------------------------------------
 def _rmse_autograd(model, batch):
+    """The batch's loss through autograd, for models / batches outside the fused step: the reference's
+    sqrt(MSELoss(out, y.unsqueeze(1))); for a classification model, CrossEntropyLoss(out, y.long()) (no sqrt, no unsqueeze:
+    see `FusedTrainStep`)."""
     out = model(batch)
+    if _is_cross_entropy(model):
+        return model.loss(out, batch.y.long())
     return torch.sqrt(model.loss(out, batch.y.unsqueeze(1)))
 
 

@@ -487,9 +487,18 @@ int hcg_readout2_fwd(const float* emb, const float* W0, const float* b0, const f
  *   step_counter       : nullable; two int32 device words, each incremented by 1 per launch: [0] the number of the
  *                        training step, read later in the same step by hcg_step_tail's update, [1] the exchange stamp
  *   flags              : HCG_HEAD_FORWARD_ONLY = no backward (demb / gradient slabs untouched; the partials are written)
+ *                        HCG_HEAD_LOSS_CE = the classification head (below) instead of the squared error
  * y is [B,C] like out.  D = 64 or 128 (8 waves per workgroup, W0 fragments from L2 instead of LDS), C <= 8
- * (hcg_head_supported). */
+ * (hcg_head_supported).
+ * Classification (HCG_HEAD_LOSS_CE, with hcg_head_fwd_bwd and hcg_head_deep_fwd_bwd): the loss is
+ * nn.CrossEntropyLoss()(out, y.long()) -- mean over the B graphs of logsumexp(out[g]) - out[g][label], default settings, no
+ * sqrt.  y is then [B] float32 holding the class index of every graph.  The error the backward runs on is
+ * d[c] = softmax(out[g])[c] - [c == label], the workgroup's partial is its sum of per-graph loss terms, and the deferred
+ * scale (HCG_LOSS_CE) is 1 / B.  The row maximum is subtracted before the exponentials; label and class are matched by
+ * comparing (float)c == y[g], nothing is indexed by the label: a label that equals none of 0 .. C-1 (out of range,
+ * negative, not an integer) makes that graph's loss term -- and so the batch loss -- NaN, `out` is written as usual. */
 #define HCG_HEAD_FORWARD_ONLY 1
+#define HCG_HEAD_LOSS_CE 2
 int hcg_head_supported(int64_t D, int64_t C);
 size_t hcg_head_workspace_bytes(int64_t B, int64_t D);
 int hcg_head_fwd_bwd(const float* emb, const float* y, const float* W0, const float* b0, const float* W1,
@@ -509,7 +518,7 @@ int hcg_head_fwd_bwd(const float* emb, const float* y, const float* W0, const fl
 #define HCG_HEAD_MAX_LAYERS 4
 typedef struct hcg_head_args {
   const float* emb;                      /* [B, 2D] pooled graph embedding */
-  const float* y;                        /* [B, C] targets */
+  const float* y;                        /* [B, C] targets; HCG_HEAD_LOSS_CE: [B] class indices */
   const float* W[HCG_HEAD_MAX_LAYERS];   /* readout layer i: weight [out_i, in_i]; entries >= R unused */
   const float* b[HCG_HEAD_MAX_LAYERS];   /* readout layer i: bias [out_i] */
   float* out;                            /* [B, C] */
@@ -520,7 +529,7 @@ typedef struct hcg_head_args {
   float* grad[HCG_HEAD_MAX_LAYERS];      /* layer i's gradient destination [dW_i | db_i] (see job_host) */
   int64_t B, D, C;
   int32_t R;                             /* readout depth */
-  int32_t flags;                         /* 0 or HCG_HEAD_FORWARD_ONLY */
+  int32_t flags;                         /* HCG_HEAD_FORWARD_ONLY | HCG_HEAD_LOSS_CE, or 0 */
   float slope;                           /* LeakyReLU negative slope of the hidden layers */
   int32_t reserved;
 } hcg_head_args;
@@ -533,6 +542,11 @@ int hcg_head_deep_fwd_bwd(const hcg_head_args* args_host, hcg_reduce_job* job_ho
                            ranks sum gradients, SSE and count (ONE all-reduce) and hcg_update_dev / hcg_adam_step_dev_sse
                            scale by 1 / (count sqrt(SSE / count)): the gradient of sqrt(MSE) over the concatenated batch of
                            all ranks, which is what the reference's step computes on one device */
+#define HCG_LOSS_CE 3   /* nn.CrossEntropyLoss() behind a head launched with HCG_HEAD_LOSS_CE (hcg_step_tail and
+                           hcg_loss_finalize only): the partials are sums of per-graph loss terms, count = B,
+                           scale 1 / count, loss[0] = loss[1] = sum / count.  hcg_loss_fwd_bwd takes it with the class
+                           count in the bits above HCG_LOSS_CE_CLASSES_SHIFT (see there) */
+#define HCG_LOSS_CE_CLASSES_SHIFT 8
 
 /* ---- MSE loss (a12 / f2): loss[0] = mean((a - b)^2) over n elements, fixed-order reduction;
  *      backward: da = grad_loss[0] * 2 (a - b) / n, db = -da (either may be NULL). */
@@ -542,8 +556,14 @@ int hcg_mse_bwd(const float* a, const float* b, const float* grad_loss, int64_t 
 
 /* Loss AND its gradient in one launch, for heads the fused kernel does not cover (other widths): mode 0 = MSE,
  * 1 = sqrt(MSE) (the reference's step, utils/utils_model.py:64), HCG_LOSS_SSE = unscaled da = a - b with [SSE, n] stored
- * in sse_tail.  loss[0] = the loss, loss[1] = MSE; da [n] = d loss / d a. */
-int hcg_loss_fwd_bwd(const float* a, const float* b, int64_t n, int mode, float* loss, float* da,
+ * in sse_tail.  loss[0] = the loss, loss[1] = MSE; da [n] = d loss / d a.
+ * mode = HCG_LOSS_CE | (C << HCG_LOSS_CE_CLASSES_SHIFT) -- a mode of this entry point rather than a symbol of its own --:
+ * nn.CrossEntropyLoss()(a, b.long()) with default settings, for heads the one-launch kernels do not cover (more than 8
+ * classes, other widths) and for the eager loss module.  a [B, C] logits with n = B * C, b [B] float32 class indices
+ * (matched by (float)c == b[g], as with HCG_HEAD_LOSS_CE: a label outside 0 .. C-1 gives a NaN loss), loss[0] = loss[1] =
+ * the mean over the graphs of logsumexp(a[g]) - a[g][label] (fixed-order sum), da [B, C] (nullable in this mode) =
+ * (softmax(a[g]) - onehot) / B, the gradient already scaled; sse_tail is not used. */
+int hcg_loss_fwd_bwd(const float* a, const float* b, int64_t n, int mode, float* loss, float* da /*nullable with HCG_LOSS_CE*/,
                      float* sse_tail /*nullable unless mode = HCG_LOSS_SSE*/, hcg_stream_t stream);
 
 /* ---- batched slab reduction: ONE launch for all pending gradient reductions of a backward pass.
@@ -614,7 +634,7 @@ typedef struct hcg_tail_args {
   const hcg_reduce_job* jobs_host;
   int32_t njobs;
   int32_t loss_mode;           /* HCG_LOSS_*; only read when a job has sse_part */
-  float loss_count;            /* elements of the squared-error sum on this rank: B * C */
+  float loss_count;            /* elements of the squared-error sum on this rank: B * C; HCG_LOSS_CE: B */
   float beta1, beta2, eps;
   float* loss;                 /* [2], nullable without exchange */
   float* sse_tail;             /* [2], nullable */

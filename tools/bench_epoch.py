@@ -4,7 +4,9 @@ batch_size 40, shuffle; utils/utils_model.py:55-70) -- hcatgnet_amd.train.train_
 oracle's loop on the same graphs.  Prints ms per epoch and graphs/s.  `--optimizer Adam | SGD | rmsprop`: the reference's
 `--optimizer` (model/networks.py:36-44); the CPU oracle's loop is Adam's and runs only for Adam.  `--readout-layers` /
 `--n-convolutions`: the reference's depth options (options/base_options.py:185-197); away from the defaults the per-batch
-autograd loop such models took before the fused step covered them is timed too."""
+autograd loop such models took before the fused step covered them is timed too.  `--problem-type classification
+--n-classes C`: the reference's `--problem_type` (model/networks.py:30-34) with labels drawn uniformly from 0 .. C-1 -- the
+cross-entropy step (train.FusedTrainStep) -- with the same legs."""
 import argparse, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,12 +18,21 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--optimizer", default="Adam", choices=["Adam", "SGD", "rmsprop"])
 ap.add_argument("--readout-layers", type=int, default=2)
 ap.add_argument("--n-convolutions", type=int, default=2)
+ap.add_argument("--problem-type", default="regression", choices=["regression", "classification"])
+ap.add_argument("--n-classes", type=int, default=None, help="classification: number of classes (default 3)")
 args = ap.parse_args()
 OPT = args.optimizer
+CLS = args.problem_type == "classification"
+if args.n_classes is not None and not CLS:
+    ap.error("--n-classes goes with --problem-type classification")
 DEPTH = dict(readout_layers=args.readout_layers, n_convolutions=args.n_convolutions)
-DEFAULT_DEPTH = DEPTH == dict(readout_layers=2, n_convolutions=2)
+DEFAULT_DEPTH = DEPTH == dict(readout_layers=2, n_convolutions=2) and not CLS     # (False: the autograd loop is timed too)
+if CLS:
+    DEPTH.update(problem_type="classification", n_classes=3 if args.n_classes is None else args.n_classes)
 G, BS = 535, 40
 sb = synth.make_config("REAL", num_graphs=G)
+if CLS:
+    sb.y = torch.randint(0, DEPTH["n_classes"], (G,), generator=torch.Generator().manual_seed(1)).float()
 graphs = sb.as_graph_list()
 store = H.DeviceGraphStore(graphs, device="cuda")
 loader = H.DeviceLoader(store, batch_size=BS, shuffle=True, seed=0)
