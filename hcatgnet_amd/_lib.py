@@ -25,6 +25,7 @@ HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRU
 HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS, HCG_STRUCT_EXPLAIN_ARGS = 5, 6, 7
 HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY, HCG_EXPLAIN_FIT = 0, 1, 2, 3, 4   # modes of hcg_explain
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
+HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
 HCG_ERR_UNSUPPORTED = -3
 HCG_FUSED_FORWARD, HCG_FUSED_BWD_PAIR, HCG_FUSED_PAIR_QUERY = 0, 1, 1      # modes of hcg_fused_forward's block; the pair's flag
 HCG_HEAD_MAX_LAYERS = 4

@@ -13,6 +13,9 @@
 //   forward   x~ = x s(node_mask) -> t0;  per layer  H = A_prev W^T (t0 -> t1; lane = output column, the lane's weight row in
 //             64 registers, the tile row broadcast out of LDS, plain f32 FMAs),  A = leaky(dinv_i (dinv_i H_i + sum_k m_k dinv_c
 //             H_c) + b) (t1 -> t0);  [max, mean] pooling;  readout of depth R.
+//   upstream  at the output row, one of three forms (uniform per launch): target [B, C] -> mean squared error, 2 (out - target) / C;
+//             dout [B, C] as given;  target_class [B] (int64 class index) -> cross-entropy -log_softmax(out)[y],
+//             softmax(out) - onehot(y), float32 with the maximum subtracted, the index compared and never used as an address.
 //   backward  readout, pooling (max: even split among exact ties), then per layer from the last:  dY = dA leaky'(A) (t0),
 //             d m_e += dinv_dst dinv_src <dY_dst, H_src> (owner: the edge's by-destination entry; layers add in layer order),
 //             dH = Ahat_m^T dY (t1),  dA_prev = dH W (t1 -> t0).  No dW, no db.
@@ -44,6 +47,7 @@ struct XArgs {     // the kernel's argument block (device pointers by value)
   const float* node_mask;
   const float* target;
   const float* dout;
+  const int64_t* target_class;
   float* out;
   float* loss;
   float* d_edge_mask;
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   const int g = blockIdx.x;
   const int F = cm.F, C = cm.C, n_conv = cm.n_conv;
   const float slope = cm.slope;
-  const bool bwd = FIT || a.target != nullptr || a.dout != nullptr;
+  const bool bwd = FIT || a.target != nullptr || a.dout != nullptr || a.target_class != nullptr;
   const bool need_dx = FIT || a.d_node_mask != nullptr || a.dx != nullptr;
   const bool sig = FIT || a.sigmoid;
 
@@ -249,16 +253,40 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   if (tid < C) {
     const float o = L.hv[off + tid];
     a.out[(size_t)g * C + tid] = o;
-    float d = 0.f;
-    if (a.target) d = o - a.target[(size_t)g * C + tid];
-    L.red[tid] = d * d;
-    L.hg[off + tid] = a.target ? 2.f * d / (float)C : (a.dout ? a.dout[(size_t)g * C + tid] : 0.f);
+    if (a.target_class) {
+      // cross-entropy against class y (uniform per launch): every thread below C restates the row from hv.  y is compared,
+      // never used as an address: outside 0 .. C - 1 no class matches -- the loss is NaN, the gradient softmax(out)
+      const long long y = a.target_class[g];
+      float mx = L.hv[off];
+      for (int c = 1; c < C; ++c) mx = fmaxf(mx, L.hv[off + c]);
+      // s = sum_c exp(o_c - mx), c ascending; `others` leaves out class y, `rest` the first maximal class (whose term is 1)
+      float s = 0.f, others = 0.f, rest = 0.f, oy = __builtin_nanf("");
+      bool first = true;
+      for (int c = 0; c < C; ++c) {
+        const float v = L.hv[off + c], ex = expf(v - mx);
+        s += ex;
+        if (c == y) oy = v; else others += ex;
+        if (first && v == mx) first = false; else rest += ex;
+      }
+      // softmax(out)_c - [c == y]; for c = y that is -(sum of the others) / s, formed without the cancelling subtraction
+      L.hg[off + tid] = tid == y ? -others / s : expf(o - mx) / s;
+      L.red[tid] = log1pf(rest) + (mx - oy);              // -log_softmax(out)[y]: two terms that are not negative
+    } else {
+      float d = 0.f;
+      if (a.target) d = o - a.target[(size_t)g * C + tid];
+      L.red[tid] = d * d;
+      L.hg[off + tid] = a.target ? 2.f * d / (float)C : (a.dout ? a.dout[(size_t)g * C + tid] : 0.f);
+    }
   }
   __syncthreads();
   if (loss_out && tid == 0) {
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += L.red[c];
-    loss_out[g] = a.target ? s / (float)C : 0.f;
+    if (a.target_class) {
+      loss_out[g] = L.red[0];
+    } else {
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += L.red[c];
+      loss_out[g] = a.target ? s / (float)C : 0.f;
+    }
   }
   if (!bwd) return;
 
@@ -473,7 +501,9 @@ int x_fit_launch(hcg_explain_args* p, hipStream_t stream) {
   XArgs& a = k.a;
   x_fill_common(a.c, p);
   a.edge_mask = a.node_mask = a.dout = nullptr;
-  a.target = p->target;
+  const bool cls = (p->flags & HCG_EXPLAIN_TARGET_CLASS) != 0;        // which of the slot's two readings
+  a.target = cls ? nullptr : p->target;
+  a.target_class = cls ? p->target_class : nullptr;
   a.out = p->out;
   a.loss = a.d_edge_mask = a.d_node_mask = a.dx = nullptr;
   a.ws = (float*)p->workspace;
@@ -499,6 +529,9 @@ int x_fit_launch(hcg_explain_args* p, hipStream_t stream) {
 extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (!p) return HCG_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
+  // the class-index form of the upstream gradient belongs to HCG_EXPLAIN_GRAPHS and HCG_EXPLAIN_FIT alone
+  if ((p->flags & HCG_EXPLAIN_TARGET_CLASS) && (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD || p->mode == HCG_EXPLAIN_ENSEMBLE || p->mode == HCG_EXPLAIN_SHAPLEY))
+    return HCG_ERR_INVALID_ARG;
   if (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD) {
     if (p->flags & HCG_EXPLAIN_QUERY) { p->workspace_bytes_needed = 0; return HCG_OK; }
     return hcg_edge_weight_grad_launch(p->layer_dout, p->layer_out, p->layer_h, p->rowptr, p->col, p->dinv, p->slope,
@@ -509,6 +542,8 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   const bool fit = p->mode == HCG_EXPLAIN_FIT;
   if (p->mode != HCG_EXPLAIN_GRAPHS && !fit) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p)) return HCG_ERR_UNSUPPORTED;
+  const bool cls = (p->flags & HCG_EXPLAIN_TARGET_CLASS) != 0;
+  if (cls && p->C < 2) return HCG_ERR_UNSUPPORTED;          // a cross-entropy needs two classes or more
   // (FIT: the tiles and lists of HCG_EXPLAIN_GRAPHS and two hard counts behind them)
   if (fit) p->lds_bytes = (int32_t)(x_lds_bytes(x_round4(p->max_nodes, 4), x_round4(p->max_edges, 4)) + X_FIT_LDS_EXTRA);
   // H_l and A_l of every layer, [N][64] f32 each: the backward reads them again
@@ -516,8 +551,8 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (fit) return x_fit_launch(p, stream);
   if (p->B == 0) return HCG_OK;
-  const bool bwd = p->target || p->dout;
-  if (p->target && p->dout) return HCG_ERR_INVALID_ARG;
+  const bool bwd = p->target || p->dout;                       // (target: the slot in either reading)
+  if ((p->target && p->dout) || (cls && !p->target_class)) return HCG_ERR_INVALID_ARG;
   if (!x_common_ok(p) || (p->E > 0 && !p->edge_mask)) return HCG_ERR_INVALID_ARG;
   if (bwd && ((p->E > 0 && !p->d_edge_mask) || (p->node_mask && !p->d_node_mask) || (p->target && !p->loss))) return HCG_ERR_INVALID_ARG;
   if (!p->node_mask && p->d_node_mask) return HCG_ERR_INVALID_ARG;
@@ -527,8 +562,9 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   x_fill_common(a.c, p);
   a.edge_mask = p->edge_mask;
   a.node_mask = p->node_mask;
-  a.target = p->target;
+  a.target = cls ? nullptr : p->target;
   a.dout = p->dout;
+  a.target_class = cls ? p->target_class : nullptr;
   a.out = p->out;
   a.loss = p->loss;
   a.d_edge_mask = p->d_edge_mask;

@@ -13,7 +13,8 @@ k_edge_weight_grad) and d out / d x.  `ExplainStep` delivers the same outputs an
 graphs in ONE launch (csrc/explain.hip: one workgroup per graph, mask gradients only, weights frozen); any torch
 optimiser over (node_mask, edge_mask) works on these gradients.  `ExplainFit` is GNNExplainer itself: the whole mask
 optimisation of every graph of a batch -- forward, backward, regularisers, Adam, hard masks, all epochs -- in ONE launch
-of the same kernel with an epoch loop inside.  The plotting around an explanation is outside this package.
+of the same kernel with an epoch loop inside.  Both take a regression model (mean squared error against a target row) and a
+classification model (cross-entropy against a class index per graph).  The plotting around an explanation is outside this package.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from dataclasses import dataclass, fields
 from typing import NamedTuple, Optional
 
 import torch
+import torch.nn.functional as F_
 
 from . import _frozen, _lib
 from .gcn import GCNConv
@@ -50,7 +52,8 @@ def clear_masks(model: torch.nn.Module):
 
 class ExplainResult(NamedTuple):
     out: torch.Tensor                       # [B, C]
-    loss: Optional[torch.Tensor]            # [B] per-graph mean_c (out - target)^2; None without target
+    loss: Optional[torch.Tensor]            # [B] per graph: mean_c (out - target)^2 with `target`, -log_softmax(out)[y] with
+                                            # `target_class`; None with `dout` and forward only
     d_edge_mask: Optional[torch.Tensor]     # [E], the batch's edge order; None for a forward-only call
     d_node_mask: Optional[torch.Tensor]     # [N, F]; None without a node mask (or forward only)
     dx: Optional[torch.Tensor]              # [N, F] = dJ/dx; None unless asked for
@@ -60,12 +63,16 @@ class ExplainStep:
     """Outputs and mask gradients of a frozen model for a whole batch of graphs, one launch per call.
 
         step = ExplainStep(model, apply_sigmoid=True)
-        r = step(batch, edge_mask, node_mask=None, target=None, dout=None, want_dx=False)
+        r = step(batch, edge_mask, node_mask=None, target=None, dout=None, want_dx=False, target_class=None)
 
     The values equal autograd through the model run on `x * s(node_mask)` with the edge mask `s(edge_mask)` multiplied
     into every message of every conv layer (s = sigmoid with `apply_sigmoid`, else the identity; self loops keep 1), of
-    J = sum_g l_g with l_g = mean_c (out_gc - target_gc)^2 (`target` [B, C]) or of J = sum(dout * out) (`dout` [B, C]);
-    with neither, the call is forward only.  At most one of `target` / `dout`.
+    J = sum_g l_g with l_g = mean_c (out_gc - target_gc)^2 (`target` [B, C]), of J = sum(dout * out) (`dout` [B, C]), or of
+    J = sum_g l_g with the cross-entropy l_g = -log_softmax(out_g)[y_g] (`target_class`: y [B] int64 class indices, a model
+    of two classes or more; `F.cross_entropy` of one row); with none of them, the call is forward only.  At most one of
+    `target` / `dout` / `target_class`.  `loss` holds l_g of the form that has one.  The kernel never uses a class index as
+    an address and does not check its range (that would cost a sync): an index outside 0 .. C - 1 gives that graph a NaN
+    loss and the gradient of softmax(out_g) alone; the autograd path leaves the index to `F.cross_entropy`.
 
     The graphs of a batch are independent, so J's gradient restricted to graph g's mask entries is exactly what a
     batch-of-one explainer run on g computes: one call serves one iteration of an explainer for EVERY graph of a dataset.
@@ -120,28 +127,41 @@ class ExplainStep:
         return t.detach()
 
     # ------------------------------------------------------------------ the call
-    def __call__(self, batch, edge_mask, node_mask=None, target=None, dout=None, want_dx: bool = False) -> ExplainResult:
-        if target is not None and dout is not None:
-            raise ValueError("at most one of target / dout")
+    def __call__(self, batch, edge_mask, node_mask=None, target=None, dout=None, want_dx: bool = False,
+                 target_class=None) -> ExplainResult:
+        if sum(t is not None for t in (target, dout, target_class)) > 1:
+            raise ValueError("at most one of target / dout / target_class")
+        if target_class is not None:
+            B = int(batch.num_graphs)
+            if (not torch.is_tensor(target_class) or target_class.dtype != torch.int64 or tuple(target_class.shape) != (B,)
+                    or not target_class.is_contiguous()):
+                raise ValueError(f"target_class must be a contiguous int64 tensor of shape {(B,)} (one class index per graph); got "
+                                 f"{getattr(target_class, 'dtype', type(target_class))} {tuple(getattr(target_class, 'shape', ()))}")
+            if target_class.device != batch.x.device:
+                raise ValueError(f"target_class is on {target_class.device}, the batch on {batch.x.device}")
+            if int(getattr(self.model, "_n_classes", 2)) < 2:
+                raise ValueError(f"target_class needs a model of two classes or more; this one has {int(self.model._n_classes)}")
         a = self._args
         why = self._shape_args(a, batch)
         if why is not None:
-            return self._autograd(batch, edge_mask, node_mask, target, dout, want_dx)
+            return self._autograd(batch, edge_mask, node_mask, target, dout, want_dx, target_class)
         m = self.model
-        x = _frozen.batch_x(batch, edge_mask, node_mask, target, dout)
+        x = _frozen.batch_x(batch, edge_mask, node_mask, target, dout, target_class)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         em = self._mask(edge_mask, (E,), "edge_mask")
         nm = self._mask(node_mask, (N, F), "node_mask") if node_mask is not None else None
         tg = self._mask(target, (B, C), "target") if target is not None else None
         do = self._mask(dout, (B, C), "dout") if dout is not None else None
+        tc = target_class.detach() if target_class is not None else None
         plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        bwd = tg is not None or do is not None
+        bwd = tg is not None or do is not None or tc is not None
         bufs = self._buffers(N, E, B, F, C, int(a.workspace_bytes_needed), x.device)
         p = _lib.ptr
-        a.flags = _lib.HCG_EXPLAIN_SIGMOID if self.apply_sigmoid else 0
+        a.flags = (_lib.HCG_EXPLAIN_SIGMOID if self.apply_sigmoid else 0) | (_lib.HCG_EXPLAIN_TARGET_CLASS if tc is not None else 0)
         _frozen.fill_graph(a, x, plan)
         _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ExplainStep"))
-        a.edge_mask, a.node_mask, a.target, a.dout = p(em), p(nm), p(tg), p(do)
+        a.edge_mask, a.node_mask, a.dout = p(em), p(nm), p(do)
+        a.target = p(tc) if tc is not None else p(tg)        # (one slot of the argument block, read by the flag)
         a.out, a.loss, a.d_edge_mask = p(bufs["out"]), p(bufs["loss"]), p(bufs["d_edge"])
         a.d_node_mask = p(bufs["d_node"]) if nm is not None else None
         a.dx = p(bufs["dx"]) if want_dx else None
@@ -149,15 +169,15 @@ class ExplainStep:
         a.slope = _frozen.SLOPE
         _lib.check(_lib.load().hcg_explain(ctypes.addressof(a), _lib.stream_ptr()), "hcg_explain")
         self.last_path = "fused"
-        return ExplainResult(bufs["out"][:B], bufs["loss"][:B] if tg is not None else None,
+        return ExplainResult(bufs["out"][:B], bufs["loss"][:B] if tg is not None or tc is not None else None,
                              bufs["d_edge"][:E] if bwd else None,
                              bufs["d_node"][:N] if bwd and nm is not None else None,
                              bufs["dx"][:N] if bwd and want_dx else None)
 
     # ------------------------------------------------------------------ the existing path (any shape), under autograd
-    def _autograd(self, batch, edge_mask, node_mask, target, dout, want_dx) -> ExplainResult:
+    def _autograd(self, batch, edge_mask, node_mask, target, dout, want_dx, target_class=None) -> ExplainResult:
         m = self.model
-        bwd = target is not None or dout is not None
+        bwd = target is not None or dout is not None or target_class is not None
         s = torch.sigmoid if self.apply_sigmoid else (lambda t: t)
         em = edge_mask.detach().requires_grad_(bwd)
         nm = node_mask.detach().requires_grad_(bwd) if node_mask is not None else None
@@ -171,6 +191,9 @@ class ExplainStep:
                 if bwd:
                     if target is not None:
                         loss = ((out - target.detach()) ** 2).mean(dim=1)
+                        J = loss.sum()
+                    elif target_class is not None:
+                        loss = F_.cross_entropy(out, target_class.detach(), reduction="none")
                         J = loss.sum()
                     else:
                         J = (dout.detach() * out).sum()
@@ -235,15 +258,21 @@ def _entropy_grad(m):
 class ExplainFit:
     """GNNExplainer for a whole batch of graphs: every graph's mask optimisation, all epochs, in ONE launch.
 
-        fit = ExplainFit(model, epochs=100, lr=0.01, coeffs=None)
+        fit = ExplainFit(model, epochs=100, lr=0.01, coeffs=None, mode="regression")
         r = fit(batch, target=None, state=None, epochs=None, generator=None, epochs_per_launch=None)
         # ExplainFitResult(edge_mask [E], node_mask [N, F], out [B, C], loss_history [T, B], state)
 
     The algorithm is the published torch_geometric 2.3 / 2.4 `GNNExplainer` with `explanation_type='model'`,
-    `node_mask_type='attributes'`, `edge_mask_type='object'` in regression mode, run as a batch-of-one fit per graph
-    (the graphs of a batch never interact).  Per graph g: logits e [E_g] and n [N_g, F]; every epoch runs
-    `ExplainStep(apply_sigmoid=True)`'s model on them against `target` (default: the model's own unmasked prediction),
-    l_g = mean_c (out_gc - target_gc)^2; from the epoch after the hard masks exist the loss also holds
+    `node_mask_type='attributes'`, `edge_mask_type='object'`, in regression mode or (`mode="multiclass_classification"`,
+    `return_type='raw'`) for a model of two classes or more, run as a batch-of-one fit per graph (the graphs of a batch
+    never interact).  Per graph g: logits e [E_g] and n [N_g, F]; every epoch runs `ExplainStep(apply_sigmoid=True)`'s
+    model on them against `target`.  Regression: `target` is float32 [B, C] (default: the model's own unmasked prediction)
+    and l_g = mean_c (out_gc - target_gc)^2.  Classification: `target` is int64 [B], a class index per graph (default: the
+    argmax of the model's own unmasked output, the first maximal index on a tie -- the 'model' explanation; the true labels
+    give the 'phenomenon' one) and l_g = -log_softmax(out_g)[target_g], `F.cross_entropy` of one row.  On CPU tensors the
+    class indices are range-checked; on the GPU they are not (that would cost a sync): an index outside 0 .. C - 1 gives
+    that graph a NaN loss history, and its masks follow softmax(out_g) alone.
+    From the epoch after the hard masks exist the loss also holds
     edge_size * sum(m) + edge_ent * mean(ent(m)) over g's hard edges and node_feat_size * mean(m) + node_feat_ent *
     mean(ent(m)) over its hard node entries (m = sigmoid(logit), ent(m) = -m log(m + 1e-15) - (1 - m) log(1 - m + 1e-15);
     a term over an empty set is 0); one torch-default Adam step (`lr`, betas 0.9 / 0.999, eps 1e-8; the rule of
@@ -262,9 +291,18 @@ class ExplainFit:
     identical semantics and state, one `ExplainStep` call per epoch for the gradients (plain torch autograd on CPU
     tensors) and torch ops for the regularisers and Adam.  `last_path` says which one ran ("fused" / "loop")."""
 
-    def __init__(self, model: torch.nn.Module, epochs: int = 100, lr: float = 0.01, coeffs: Optional[dict] = None):
+    MODES = ("regression", "multiclass_classification")
+
+    def __init__(self, model: torch.nn.Module, epochs: int = 100, lr: float = 0.01, coeffs: Optional[dict] = None,
+                 mode: str = "regression"):
         if int(epochs) < 1:
             raise ValueError(f"epochs must be at least 1; got {epochs}")
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {self.MODES}; got {mode!r}")
+        self.mode = mode
+        self._ce = mode == "multiclass_classification"
+        if self._ce and int(getattr(model, "_n_classes", 2)) < 2:
+            raise ValueError(f"mode {mode!r} needs a model of two classes or more (n_classes >= 2); this one has {int(model._n_classes)}")
         self.model, self.epochs, self.lr = model, int(epochs), float(lr)
         self.coeffs = dict(DEFAULT_COEFFS)
         for k, v in (coeffs or {}).items():
@@ -338,6 +376,8 @@ class ExplainFit:
 
     def _target(self, batch, target):
         B, C = int(batch.num_graphs), int(self.model._n_classes)
+        if self._ce and C < 2:
+            raise ValueError(f"mode {self.mode!r} needs a model of two classes or more (n_classes >= 2); this one has {C}")
         if target is None:
             with torch.no_grad():
                 if batch.x.is_cuda:
@@ -346,6 +386,15 @@ class ExplainFit:
                     from .shapley import _torch_forward
                     ones = torch.ones(batch.edge_index.shape[1], dtype=batch.x.dtype)
                     target = _torch_forward(self.model, batch.x, batch.edge_index, batch.batch, B, ones).reshape(B, C)
+                if self._ce:
+                    target = target.argmax(dim=1)           # (on the batch's device, no sync; a tie: the first maximal index)
+        if self._ce:
+            if not torch.is_tensor(target) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or not target.is_contiguous():
+                raise ValueError(f"in mode {self.mode!r} target must be a contiguous int64 tensor of shape {(B,)} (one class index "
+                                 f"per graph); got {getattr(target, 'dtype', type(target))} {tuple(getattr(target, 'shape', ()))}")
+            if not target.is_cuda and B > 0 and (int(target.min()) < 0 or int(target.max()) >= C):
+                raise ValueError(f"target holds class indices outside 0 .. {C - 1}")
+            return target.detach()
         if target.dtype != torch.float32 or tuple(target.shape) != (B, C) or not target.is_contiguous():
             raise ValueError(f"target must be a contiguous float32 tensor of shape {(B, C)}; got {target.dtype} {tuple(target.shape)}")
         return target.detach()
@@ -386,7 +435,7 @@ class ExplainFit:
         plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
         bufs = self._buffers(N, E, B, F, C, T * B, int(a.workspace_bytes_needed), x.device)
         p = _lib.ptr
-        a.flags = 0
+        a.flags = _lib.HCG_EXPLAIN_TARGET_CLASS if self._ce else 0      # (how the library reads the target slot)
         _frozen.fill_graph(a, x, plan)
         _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ExplainFit"))
         a.target, a.out = p(tg), p(bufs["out"])
@@ -412,7 +461,7 @@ class ExplainFit:
     def _grads(self, batch, s, target):
         """-> (out [B, C], loss [B], d loss / d edge logits, d loss / d node logits) of one epoch"""
         if batch.x.is_cuda:
-            r = self._step(batch, s.edge_logit, s.node_logit, target=target)
+            r = self._step(batch, s.edge_logit, s.node_logit, **{"target_class" if self._ce else "target": target})
             return r.out, r.loss, r.d_edge_mask, r.d_node_mask
         from .shapley import _torch_forward                 # (the package's layers take GPU tensors only)
         em = s.edge_logit.detach().clone().requires_grad_(True)
@@ -420,7 +469,7 @@ class ExplainFit:
         B = int(batch.num_graphs)
         with torch.enable_grad():
             out = _torch_forward(self.model, batch.x * nm.sigmoid(), batch.edge_index, batch.batch, B, em.sigmoid()).reshape(B, -1)
-            loss = ((out - target) ** 2).mean(dim=1)
+            loss = F_.cross_entropy(out, target, reduction="none") if self._ce else ((out - target) ** 2).mean(dim=1)
             d_e, d_n = torch.autograd.grad(loss.sum(), [em, nm])           # (no parameter's .grad is touched)
         return out.detach(), loss.detach(), d_e, d_n
 

@@ -141,7 +141,15 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *     m_e = s(edge_mask_e);  [max, mean] pooling;  readout of depth R  ->  out [B, C]
  *   s = sigmoid with HCG_EXPLAIN_SIGMOID in `flags`, else the identity.  Upstream gradient per graph g:
  *     target != NULL: l_g = mean_c (out_gc - target_gc)^2 (stored in loss [B]) and dout = 2 (out - target) / C;
- *     dout   != NULL: that row as given;   neither: forward only (no gradient output is touched).
+ *     dout   != NULL: that row as given;
+ *     HCG_EXPLAIN_TARGET_CLASS in `flags`: the target slot holds `target_class` [B], an int64 class index y_g per graph
+ *       (the two names share one pointer of the struct, so its size and every offset are what they were; C >= 2 or
+ *       HCG_ERR_UNSUPPORTED; the pointer must not be NULL): the cross-entropy of one row,
+ *       l_g = -log_softmax(out_g)[y_g] (stored in loss [B]) and dout_gc = softmax(out_g)_c - [c == y_g], in float32 with the
+ *       row's maximum subtracted.  y_g is compared, never used as an address: outside 0 .. C - 1 the graph's loss is NaN and
+ *       its gradient that of "no class matched" (softmax(out_g));
+ *     none of them: forward only (no gradient output is touched).  At most one of the three (HCG_ERR_INVALID_ARG).
+ *     The flag belongs to HCG_EXPLAIN_GRAPHS and HCG_EXPLAIN_FIT: in every other mode it must be clear (HCG_ERR_INVALID_ARG).
  *   Gradients of J = sum_g l_g (or sum(dout * out)) with respect to the masks ONLY -- no dW, no db:
  *     d_edge_mask [E] in the caller's edge order (an explicit (i, i) edge collapses into the unit self loop: exactly 0),
  *     d_node_mask [N, F] (with node_mask), dx [N, F] = dJ/dx (nullable).
@@ -152,19 +160,19 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   R 1..4 (readout layer i maps 2D >> i to half of it + LeakyReLU, the last one to C), C <= 8.  Anything else:
  *   HCG_ERR_UNSUPPORTED.  Needs graph_ptr / edge_ptr / status of a BLOCKED plan and the raw int64 edge_index grouped by graph.
  *   `workspace`: the layers' H = A_prev W^T and A, which the backward reads again (workspace_bytes_needed, written by every
- *   call; only a call with target / dout uses it).
+ *   call; only a call with target / dout / target_class uses it).
  *   HCG_EXPLAIN_QUERY in `flags`: validate the shapes (D, F, C, n_conv, R, max_nodes, max_edges, N, E, B), write
  *   workspace_bytes_needed, launch nothing, touch no GPU: HCG_OK or HCG_ERR_UNSUPPORTED.
  * HCG_EXPLAIN_LAYER_EDGE_GRAD: one layer of the any-shape path -- the gradient with respect to the per-edge multipliers ew_csr
  *   handed to hcg_gcn_layer_fwd:  dew_csr[k] = dinv_i dinv_{col k} <dY_i, h_{col k}>  with dY = layer_dout * act'(layer_out) and
  *   h = x W^T (recompute with hcg_linear_fwd); 0 for explicit self-loop entries.  Reads layer_dout, layer_out, layer_h [N, D],
- *   rowptr, col, dinv, slope, apply_act, N, E, D; writes dew_csr [E].
+ *   rowptr, col, dinv, slope, apply_act, N, E, D; writes dew_csr [E].  HCG_EXPLAIN_TARGET_CLASS must be clear (HCG_ERR_INVALID_ARG).
  * HCG_EXPLAIN_ENSEMBLE: `n_models` frozen models of ONE architecture predict the same batch of graphs in ONE launch, forward
  *   only (csrc/ensemble.hip; reference scripts_experiments/predict_test.py:19-103).  One workgroup per (graph, group of
  *   `models_per_group` models): gcn_norm and the row list are built once per workgroup and reused by its models.
  *   conv_W[l] / conv_b[l] / head_W[i] / head_b[i] point at the models' tensors stacked along a leading M axis
  *   ([M, D, F or D], [M, D], [M, out_i, in_i], [M, out_i]; contiguous).  out is [M, B, C]; emb ([M, B, 2D], max first) is
- *   written when not NULL.  edge_mask, node_mask, target and dout must be NULL (HCG_ERR_INVALID_ARG); loss, the gradient
+ *   written when not NULL.  edge_mask, node_mask, target / target_class and dout must be NULL (HCG_ERR_INVALID_ARG); loss, the gradient
  *   outputs and the workspace are not used (workspace_bytes_needed = 0).  Shapes and refusals as HCG_EXPLAIN_GRAPHS, plus
  *   1 <= n_models and 1 <= models_per_group <= n_models; a refused graph's rows of out / emb are zero for every model.  The
  *   result for (model, graph) is bitwise independent of n_models, of models_per_group and of the rest of the batch.
@@ -183,15 +191,18 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   rows, p ascending, onto shap_acc [N F + E] (node entries [N, F] first, then the E edges; a call with perm_first = 0 starts
  *   from 0, the call that ends at n_perm divides by n_perm): the mean over n_perm permutations in the fixed order 0, 1, ..,
  *   bitwise independent of how the permutations are split into calls.  out [B, C] = the output with everything on and
- *   out_base [B, C] = with everything off, both written by permutation 0's workgroups.  edge_mask, node_mask, target and dout
- *   must be NULL (HCG_ERR_INVALID_ARG).  Shapes: as HCG_EXPLAIN_GRAPHS but graphs of <= 184 nodes (three [n][64] tiles are kept
+ *   out_base [B, C] = with everything off, both written by permutation 0's workgroups.  edge_mask, node_mask, target /
+ *   target_class and dout must be NULL (HCG_ERR_INVALID_ARG).  Shapes: as HCG_EXPLAIN_GRAPHS but graphs of <= 184 nodes (three [n][64] tiles are kept
  *   in LDS) and perm_count <= 65535; refusals as there (HCG_STATUS_SHAPE_LIMIT: the graph's rows of every output zero).
  *   HCG_EXPLAIN_QUERY as above (reads perm_count too).
  * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
- *   node_mask_type 'attributes', edge_mask_type 'object', regression) for a batch of graphs in ONE launch: the kernel of
+ *   node_mask_type 'attributes', edge_mask_type 'object'; regression, or multiclass classification on raw outputs) for a
+ *   batch of graphs in ONE launch: the kernel of
  *   HCG_EXPLAIN_GRAPHS with an epoch loop around forward and backward, one workgroup per graph, run as a batch-of-one fit
  *   per graph.  The parameters are the LOGITS fit_edge_logit [E] / fit_node_logit [N, F]; every epoch evaluates
- *   HCG_EXPLAIN_GRAPHS with HCG_EXPLAIN_SIGMOID on them against `target` (required; loss of epoch t in fit_loss_hist[t, g]),
+ *   HCG_EXPLAIN_GRAPHS with HCG_EXPLAIN_SIGMOID on them against `target` (regression: the mean squared error) or, with
+ *   HCG_EXPLAIN_TARGET_CLASS, `target_class` (classification: the cross-entropy, as above) -- the slot is required; loss of
+ *   epoch t in fit_loss_hist[t, g] --,
  *   adds -- from the epoch after the hard flags exist -- the gradients of
  *     coeffs[0] sum(m) + coeffs[1] mean(ent(m)) over the graph's hard edges and
  *     coeffs[2] mean(m) + coeffs[3] mean(ent(m)) over its hard node entries,  m = sigmoid(logit),
@@ -211,24 +222,28 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
 #define HCG_EXPLAIN_FIT 4
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
+#define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
   int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT */
-  int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID */
+  int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
   const int32_t* graph_ptr;              /* [B + 1] */
   const int32_t* edge_ptr;               /* [B + 1] */
   const float* edge_mask;                /* [E], the caller's edge order */
   const float* node_mask;                /* [N, F], nullable */
-  const float* target;                   /* [B, C], nullable */
-  const float* dout;                     /* [B, C], nullable (at most one of target / dout) */
+  union {                                /* ONE pointer, read by the flag HCG_EXPLAIN_TARGET_CLASS: */
+    const float* target;                 /*   clear: [B, C], nullable */
+    const int64_t* target_class;         /*   set: [B] class indices (HCG_EXPLAIN_GRAPHS / _FIT) */
+  };
+  const float* dout;                     /* [B, C], nullable (at most one of target / dout / target_class) */
   const float* conv_W[HCG_EXPLAIN_MAX_CONVS];   /* conv layer l: lin.weight [D, F or D]; entries >= n_conv unused */
   const float* conv_b[HCG_EXPLAIN_MAX_CONVS];   /* conv layer l: bias [D] */
   const float* head_W[4];                /* readout layer i: weight [out_i, in_i]; entries >= R unused (HCG_HEAD_MAX_LAYERS) */
   const float* head_b[4];                /* readout layer i: bias [out_i] */
   float* out;                            /* [B, C] */
-  float* loss;                           /* [B]; required with target */
+  float* loss;                           /* [B]; required with target and with target_class */
   float* d_edge_mask;                    /* [E] */
   float* d_node_mask;                    /* [N, F]; required with node_mask, NULL without */
   float* dx;                             /* [N, F], nullable */

@@ -5,6 +5,11 @@ process, legs alternating, on 52, 535 and 4096 graphs (87 +- 30 nodes, F = 25, 2
   (a) the loop path: per epoch one `ExplainStep` launch, torch ops for the regularisers' gradients and Adam (`ExplainFit.loop`).
   (b) the one-launch fit: every graph's 100 epochs inside one launch of k_explain_graphs<true>.
 
+`--problem-type classification` (with `--n-classes`, default 3) times the same two legs on a classifier in
+`mode="multiclass_classification"` (cross-entropy against the predicted class) and, in the same windows, the two legs of the
+regression fit of a one-output model of the same depth (`c_loop_regression`, `d_fused_regression`), so that both objectives
+are measured side by side in one process.
+
 Both legs start every call from the same fresh state (nine small device copies, counted in both) and hold the model's own
 prediction.  Warm-up first; then `--windows` rounds of the legs, each window device-synchronised at both ends and at least
 `--seconds` long; a window's figure is its time per call (one call = the whole fit of every graph); reported: median, p10,
@@ -67,18 +72,28 @@ def main():
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--graphs", type=int, nargs="+", default=[52, 535, 4096])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--problem-type", choices=["regression", "classification"], default="regression")
+    ap.add_argument("--n-classes", type=int, default=None, help="outputs of the model (default: 1 for regression, 3 for classification)")
     ap.add_argument("--profile-calls", type=int, default=0, help="only this many fused calls on the first batch (for a kernel trace)")
     a = ap.parse_args()
 
+    classify = a.problem_type == "classification"
+    n_classes = a.n_classes if a.n_classes is not None else (3 if classify else 1)
+    if classify and n_classes < 2:
+        ap.error("--problem-type classification needs --n-classes of 2 or more")
     torch.manual_seed(0)
-    model = H.make_network("GCN", H.default_options(), 25).cuda().eval()
-    fit = ExplainFit(model, epochs=a.epochs)
+    model = H.make_network("GCN", H.default_options(problem_type=a.problem_type, n_classes=n_classes), 25).cuda().eval()
+    fit = ExplainFit(model, epochs=a.epochs, mode="multiclass_classification" if classify else "regression")
+    fit_reg = ExplainFit(H.make_network("GCN", H.default_options(), 25).cuda().eval(), epochs=a.epochs) if classify else None
     cases = []
     for B in a.graphs:
         batch = make_batch(B)
         assert fit.reason(batch) is None, fit.reason(batch)
         with torch.no_grad():
             target = model(batch).reshape(B, -1).clone()
+            if classify:
+                target = target.argmax(dim=1)
+                target_reg = fit_reg.model(batch).reshape(B, -1).clone()
         fresh = fit.init_state(batch, torch.Generator().manual_seed(1))
         state = fresh.clone()
 
@@ -105,6 +120,18 @@ def main():
             return
 
         legs = {"a_loop": loop, "b_fused": fused}
+        if classify:
+            def loop_reg():
+                reset()
+                return fit_reg.loop(batch, target=target_reg, state=state)
+
+            def fused_reg():
+                reset()
+                return fit_reg(batch, target=target_reg, state=state)
+
+            fused_reg()
+            assert fit_reg.last_path == "fused"
+            legs.update(c_loop_regression=loop_reg, d_fused_regression=fused_reg)
         r_loop = loop()
         loop_masks = (r_loop.edge_mask.clone(), r_loop.node_mask.clone())
         assert fit.last_path == "loop"
@@ -121,12 +148,15 @@ def main():
         rec.update({k: stats(v) for k, v in t.items()})
         rec["b_p90_below_a_p10"] = rec["b_fused"]["p90_us"] < rec["a_loop"]["p10_us"]
         rec["a_over_b_median"] = round(rec["a_loop"]["median_us"] / rec["b_fused"]["median_us"], 2)
+        if classify:
+            rec["b_over_d_median"] = round(rec["b_fused"]["median_us"] / rec["d_fused_regression"]["median_us"], 3)
         cases.append(rec)
         print(json.dumps(rec), file=sys.stderr)
-    out = dict(bench="explain_fit", device=torch.cuda.get_device_name(0), window_seconds=a.seconds, graph_shape=REAL,
+    out = dict(bench="explain_fit", problem_type=a.problem_type, n_classes=n_classes, device=torch.cuda.get_device_name(0), window_seconds=a.seconds, graph_shape=REAL,
                x_nonzero_share=KEEP, cases=cases,
                note="one call = the whole fit of every graph of the batch from a fresh state; (a) is ExplainFit.loop (one ExplainStep "
-                    "launch per epoch plus torch ops), (b) the one-launch kernel; both legs copy the fresh state in first")
+                    "launch per epoch plus torch ops), (b) the one-launch kernel; both legs copy the fresh state in first"
+                    + ("; (c) / (d) are the same two legs of the regression fit of a one-output model, alternated in the same windows" if classify else ""))
     line = json.dumps(out)
     print(line)
     if a.out:
