@@ -280,6 +280,24 @@ struct AdjFrags {
   }
 };
 
+// selects on a bit of a mask word without a compare: all ones / all zeros from the bit (v_bfe_i32), then v_and / v_bfi
+__device__ __forceinline__ uint32_t bit_mask(uint32_t w, int i) { return (uint32_t)((int32_t)(w << (31 - i)) >> 31); }
+__device__ __forceinline__ float and_mask(float v, uint32_t m) { return __uint_as_float(__float_as_uint(v) & m); }
+__device__ __forceinline__ float sel_mask(uint32_t m, float a, float b) {
+  return __uint_as_float((__float_as_uint(a) & m) | (__float_as_uint(b) & ~m));
+}
+
+// v_permlane32_swap: lanes 32-63 of `a` change places with lanes 0-31 of `b`; the other two halves stay
+// (accumulator registers 8s + b and 8s + 4 + b of `v`, in place)
+__device__ __forceinline__ void half_swap(f32x16& v, int ia, int ib) {
+  // (scalars first: __builtin_bit_cast applied to an element of an ext vector reads element 0 whatever the index)
+  const float a = v[ia], b = v[ib];
+  const auto u = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  const unsigned ua = u[0], ub = u[1];
+  v[ia] = __uint_as_float(ua);
+  v[ib] = __uint_as_float(ub);
+}
+
 __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4_shfl_xor(float4 v, int m) {
   return make_float4(__shfl_xor(v.x, m, 64), __shfl_xor(v.y, m, 64), __shfl_xor(v.z, m, 64), __shfl_xor(v.w, m, 64));
@@ -752,16 +770,19 @@ __device__ __forceinline__ void fused_bwd_phase(
     te.build(L.cnt, L.ldinv, L.lgp, ti, ei, E, lane, status);
     BSTAMP(1 + 8 * bstamp_it);
 
-    // ---- 1. dY' = dinv (.) dA (.) leaky'(A) -> buf (rows >= n zero); A / dA stay in registers
+    // ---- 1. dY' = dinv (.) dA (.) leaky'(A) -> buf (rows >= n zero; BITS: -> registers); A / dA stay in registers
     float4 dy[TM / 4];
+    // BITS only: dinv of this lane's 16 accumulator rows (read once, used again behind the aggregation) and dY' itself,
+    // columns r / 32 + r -- it never goes to LDS, step 2 takes its B operand from these registers
+    f32x16 dvb, dy0, dy1;
     if constexpr (BITS) {
-      // accumulator layout (lane = column, 16 rows in registers): the pooled gradient is two scalars per lane and graph
-      // every row < n belongs to exactly one graph of the tile: each graph writes its own rows of dY', the rest are zero
+      // accumulator layout (lane = column, 16 rows krow(i, h) in registers): the pooled gradient is two scalars per lane and
+      // graph.  Every row < n belongs to exactly one graph of the tile: each graph's rows are taken by selects on its row
+      // mask -- no per-row branch, no LDS round trip per row; rows of no graph stay zero.
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = krow(i, h);
-        if (row >= ti.n) { L.buf[row * HS + r] = 0.f; L.buf[row * HS + 32 + r] = 0.f; }
-      }
+      for (int i = 0; i < 16; ++i) dvb[i] = L.ldinv[krow(i, h)];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { dy0[i] = 0.f; dy1[i] = 0.f; }
       for (int g = ti.g0; g < ti.g1; ++g) {
         const int gb = L.lgp[g - ti.g0], ge = L.lgp[g - ti.g0 + 1];
         if (ge <= gb) continue;
@@ -778,18 +799,29 @@ __device__ __forceinline__ void fused_bwd_phase(
         const float share0 = dmx0 / fmaxf(t0, 1.f), share1 = dmx1 / fmaxf(t1, 1.f);   // ties of the max split evenly
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          if (rows >> i & 1) {
-            const int row = krow(i, h);
-            const float g0 = (dme0 + ((ismax >> i & 1) ? share0 : 0.f)) * ((pos >> i & 1) ? 1.f : slope_eff);
-            const float g1 = (dme1 + ((ismax >> (16 + i) & 1) ? share1 : 0.f)) * ((pos >> (16 + i) & 1) ? 1.f : slope_eff);
-            dbl0 += g0;
-            dbl1 += g1;
-            const float di = L.ldinv[row];
-            L.buf[row * HS + r] = di * g0;
-            L.buf[row * HS + 32 + r] = di * g1;
-          }
+          const uint32_t mine = bit_mask(rows, i);
+          const float a0 = dme0 + and_mask(share0, bit_mask(ismax, i)), f0 = sel_mask(bit_mask(pos, i), 1.f, slope_eff);
+          const float a1 = dme1 + and_mask(share1, bit_mask(ismax, 16 + i)), f1 = sel_mask(bit_mask(pos, 16 + i), 1.f, slope_eff);
+          // db: graphs ascending, rows ascending, one fused multiply-add per own row -- the order and the rounding db has
+          // always been summed with (a row of another graph adds 0 * f)
+          dbl0 = fmaf(and_mask(a0, mine), f0, dbl0);
+          dbl1 = fmaf(and_mask(a1, mine), f1, dbl1);
+          dy0[i] = sel_mask(mine, dvb[i] * (a0 * f0), dy0[i]);
+          dy1[i] = sel_mask(mine, dvb[i] * (a1 * f1), dy1[i]);
         }
       }
+      // accumulator rows -> the aggregation's k order.  Step 2 wants, on lane-half h, rows 16s + 8h + j in slot j of k-step s
+      // (the order every form of this phase reads dY' in, so all of them sum a k-step alike and agree bitwise); register
+      // 8s + 4c + b holds row 16s + 8c + 4h + b.  Bits 2 and 3 of the row change places between the halves: one half
+      // exchange per register pair (8s + b, 8s + 4 + b) -- the upper half's rows 16s + 4 + b go down, the lower half's rows
+      // 16s + 8 + b go up -- and register 8s + j holds row 16s + 8h + j.
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          half_swap(dy0, 8 * s + b, 8 * s + 4 + b);
+          half_swap(dy1, 8 * s + b, 8 * s + 4 + b);
+        }
     } else {
     if (POOLG) {
 #pragma unroll
@@ -878,14 +910,22 @@ __device__ __forceinline__ void fused_bwd_phase(
       float g0[8], g1[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        g0[j] = L.buf[(16 * s + 8 * h + j) * HS + r];
-        g1[j] = L.buf[(16 * s + 8 * h + j) * HS + 32 + r];
+        if constexpr (BITS) {
+          g0[j] = dy0[8 * s + j];
+          g1[j] = dy1[8 * s + j];
+        } else {
+          g0[j] = L.buf[(16 * s + 8 * h + j) * HS + r];
+          g1[j] = L.buf[(16 * s + 8 * h + j) * HS + 32 + r];
+        }
       }
       mfma_exact_a(dh0, adj.f[s], split3(g0));
       mfma_exact_a(dh1, adj.f[s], split3(g1));
     }
     mfma_results_fence(dh0, dh1);
-    {
+    if constexpr (BITS) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { dh0[i] *= dvb[i]; dh1[i] *= dvb[i]; }
+    } else {
       float dvr[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) dvr[i] = L.ldinv[krow(i, h)];
