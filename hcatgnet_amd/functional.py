@@ -317,13 +317,14 @@ def _tall_reduce_jobs(geo, gpt, F, D, ws, wsb, dW, db, job, first: bool = False)
 
 
 # small-graph tiles (csrc/fused.hip, graphs up to 32 nodes), one graph per workgroup / wave (csrc/mid.hip, wave.hip), the
-# wide-layer route (csrc/tall.hip: dense row-streaming parts + per-graph segmented sums)
+# wide-layer route (csrc/tall.hip: dense row-streaming parts + per-graph segmented sums).  `row_streaming`: the family's
+# kernels walk all N rows of the batch (N must be the exact row count) and its forward and backward share one workspace
 TILES = SimpleNamespace(name="tiles", forward=_tiles_forward, backward=_tiles_backward, workspace_bytes=_tiles_workspace_bytes,
-                        reduce_jobs=_tiles_reduce_jobs, backward_pair=_tiles_backward_pair)
+                        reduce_jobs=_tiles_reduce_jobs, backward_pair=_tiles_backward_pair, row_streaming=False)
 MID = SimpleNamespace(name="mid", forward=_mid_forward, backward=_mid_backward, workspace_bytes=_mid_workspace_bytes,
-                      reduce_jobs=_mid_reduce_jobs)
+                      reduce_jobs=_mid_reduce_jobs, row_streaming=False)
 TALL = SimpleNamespace(name="tall", forward=_tall_forward, backward=_tall_backward, workspace_bytes=_tall_workspace_bytes,
-                       reduce_jobs=_tall_reduce_jobs)
+                       reduce_jobs=_tall_reduce_jobs, row_streaming=True)
 
 _JOB_BYTES = _lib.job_bytes()
 
@@ -400,18 +401,20 @@ def tall_shape_supported(N: int, F: int, D: int, max_nodes: int, max_edges: int,
     return bool(_lib.load().hcg_tall_supported(F, D, max_nodes, max_edges))
 
 
-def conv_route(plan: Optional[BatchPlan], F: int, D: int, family: str = "auto", *, max_nodes=None, max_edges=None):
+def conv_route(plan: Optional[BatchPlan], F: int, D: int, family: str = "auto", *, max_nodes=None, max_edges=None, rows=None):
     """Which fused family takes a conv layer F -> D: (TILES, graphs_per_tile), (TALL, 0), (MID, 0), or (None, 0) = none
     (the any-shape kernels).  Tiles first; then, where the one-graph-per-workgroup kernels apply, the wide-layer route
     unless `family == "mid"` (every layer it takes, mid.hip takes too), else mid.hip.  `max_nodes` replaces the plan's
-    largest graph; `plan=None` asks from a batch's collate metadata alone (`max_nodes`, `max_edges`: no plan checks, and
-    never the wide-layer route, which needs the batch's row count)."""
+    largest graph; `plan=None` asks from a batch's collate metadata alone (`max_nodes`, `max_edges`: no plan checks), and
+    the wide-layer route, which needs the batch's row count, is considered only when `rows` gives it."""
     gpt = fused_graphs_per_tile(plan, F, D, max_nodes)
     if gpt > 0:
         return TILES, gpt
     if not mid_supported(plan, F, D, max_nodes, max_edges):
         return None, 0
-    return (TALL if plan is not None and family != "mid" and tall_supported(plan, F, D) else MID), 0
+    tall = family != "mid" and (tall_supported(plan, F, D) if plan is not None
+                                else rows is not None and tall_shape_supported(rows, F, D, max_nodes, max_edges))
+    return (TALL if tall else MID), 0
 
 
 class _ConvLayerFn(torch.autograd.Function):

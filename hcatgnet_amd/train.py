@@ -24,7 +24,7 @@ the autograd path with the same arithmetic contract.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed
@@ -59,10 +59,79 @@ def _head_deep_supported(D: int, C: int, R: int) -> bool:
     return _lib.load().hcg_general_workspace_bytes(_lib.HCG_WS_HEAD_DEEP, 1, D, C, R) > 0
 
 
+class LayerForm(NamedTuple):
+    """How one conv layer runs in a step: everything `layer_forms` decides and the step's phases then only read."""
+    fam: object             # kernel family (functional.TILES / MID / TALL)
+    gpt: int                # graphs per tile (0 off the small-graph tiles)
+    stacked: bool           # forward: the two layers of a two-layer stack on the tiles, one launch
+    bits: Optional[str]     # pooled layer kept as sign / is-the-column-max bits only: the workspace that holds them
+    #                         ("poolbits": tiles; "poolbits_tall": wide-layer route); None = its activations are stored
+    kp: int                 # dense first layer: the forward also leaves Ahat x [N, kp] (32 / 64 / 128) and the sign pieces of
+    #                         its output, the whole backward is ONE dense launch (csrc/tall.hip: k_tall_dw<FIRST>); 0 = not
+    flags: int              # the backward's flag word: 1 = applies its own activation derivative (0: dout arrives premasked,
+    #                         the layer never reads its own output), 2 = hands dx down premasked
+    pair: Optional[str]     # "upper" (layer 1) / "lower" (layer 0) of a backward pair candidate: both on the tiles, dx premasked
+    jobs: int               # reduction jobs its backward leaves for the step tail
+
+
+def _layer_shapes(model):
+    """(in_channels, out_channels, family preference) of every conv layer."""
+    return [(c.in_channels, c.out_channels, getattr(c, "family", "auto")) for c in [model.conv1] + list(model.conv_layers)]
+
+
+def layer_forms(shapes, N, max_nodes, max_edges, forward_only=False, sw=None, plan=None):
+    """The form of every conv layer of a step -> [LayerForm], or None when a layer has no fused kernel family.  Pure host
+    arithmetic on plain values: `shapes` = `_layer_shapes`, the batch's row count and largest graph, `sw` = whoever holds the
+    development switches (a step, default the class), `plan` (whose own N and largest graph the caller passes) adds
+    `conv_route`'s plan-level checks.  The support check asks with a batch's collate metadata, `_prepare` with its plan: the
+    jobs the one predicts are the jobs the other leaves."""
+    sw = FusedTrainStep if sw is None else sw
+    # a step keeps the answers by the inputs (it asks twice per step: the support check, then `_prepare` with the plan, whose
+    # own checks -- passed -- add nothing); without the memo the eager step's host time was 0.113 against 0.104 ms
+    memo = sw._forms_memo if (plan is None or HF._per_graph_plan(plan)) else None
+    key = (tuple(shapes), N, max_nodes, max_edges, forward_only, sw.POOLBITS, sw.XAGG, sw.XAGG_MID, sw.PREMASK, sw.BWD_PAIR,
+           HF.TALL_MIN_NODES_D64)
+    if memo is not None and key in memo:
+        return memo[key]
+    routes = [HF.conv_route(plan, F, D, family, max_nodes=max_nodes, max_edges=max_edges, rows=N) for F, D, family in shapes]
+    if (None, 0) in routes:
+        return None
+    n, fams = len(routes), [fam for fam, _ in routes]
+    stacked = n == 2 and fams[0] is HF.TILES and routes[0] == routes[1]
+    pair = sw.BWD_PAIR and sw.PREMASK and not forward_only and n >= 2 and fams[0] is HF.TILES and fams[1] is HF.TILES
+    # a layer on the tiles or one graph per workgroup can hand its dx down already multiplied by the activation derivative
+    # of the layer below (it holds those rows anyway, for dW): one tensor less per step
+    premask = [bool(sw.PREMASK) and l > 0 and fam is not HF.TALL for l, fam in enumerate(fams)]
+    forms = []
+    for l, ((F, D, _), (fam, gpt)) in enumerate(zip(shapes, routes)):
+        last = l == n - 1
+        bits = None
+        if last and sw.POOLBITS and (fam is HF.TILES or (fam is HF.TALL and F <= (64 if D == 64 else 128))):
+            bits = "poolbits" if fam is HF.TILES else "poolbits_tall"
+        dense = False
+        if l == 0 and n >= 2 and sw.XAGG and not forward_only:
+            if fam is HF.TALL:
+                dense = (F <= 64 or D == 128) and fams[1] is HF.TALL
+            elif fam is HF.MID:     # (behind the one-graph-per-workgroup kernels: batches under functional.TALL_MIN_NODES_D64)
+                dense = (D == 64 and F <= 64 and sw.XAGG_MID and fams[1] is not HF.TILES
+                         and HF.tall_shape_supported(N, F, D, max_nodes, max_edges, any_rows=True))
+        kp = (32 if F <= 32 else (64 if F <= 64 else 128)) if dense else 0
+        flags = (1 if (last or not premask[l + 1]) else 0) | (2 if premask[l] else 0)
+        # jobs: the families' `reduce_jobs` -- the tiles 1; the wide-layer route and the dense first layer dW, db; one graph
+        # per workgroup one per 64-column half
+        jobs = 1 if fam is HF.TILES else (2 if (fam is HF.TALL or kp) else D // 64)
+        forms.append(LayerForm(fam, gpt, stacked, bits, kp, flags, ("lower", "upper")[l] if (pair and l < 2) else None, jobs))
+    if memo is not None:
+        if len(memo) >= 64:         # (a shuffled epoch's batches differ in N: bounded, not kept for ever)
+            memo.clear()
+        memo[key] = forms
+    return forms
+
+
 class _Ctx:
-    """Everything one step needs, resolved once: shapes, weights, buffers, the kernel family of every layer."""
+    """Everything one step needs, resolved once: shapes, weights, buffers, the form of every layer (`layer_forms`)."""
     __slots__ = ("batch", "plan", "x", "y2", "convs", "lins", "N", "F", "B", "D", "C", "n_conv", "dev", "W", "bs",
-                 "routes", "geo", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
+                 "forms", "geo", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
                  "loss_mode", "sse_split", "poolbits", "xagg", "bwd_pair")
 
 
@@ -112,6 +181,7 @@ class FusedTrainStep:
     BWD_PAIR = True
     HEAD_IN_FORWARD = True
     OVERLAP_GROUPS = True          # captured size-grouped steps: the two kernel families as two branches of the hipGraph
+    _forms_memo = None             # (`layer_forms` asked with the class, or a step made without __init__: nothing is kept)
 
     def __init__(self, model, rmse: bool = True, optimizer_step: bool = True, grad_sync=None, combine: str = "mean"):
         if combine not in ("mean", "sse"):
@@ -149,6 +219,7 @@ class FusedTrainStep:
         self.capture_exchange = False
         self._pcache = None
         self._pair_ok = {}                      # answers of the backward pair's query (`_pair_applies`)
+        self._forms_memo = {}                   # ... and of `layer_forms`
 
     def _trainable(self):
         """The model's parameters in `model.parameters()` order, from a cache: the module walk of `nn.Module.parameters()`
@@ -205,12 +276,9 @@ class FusedTrainStep:
             mx = getattr(batch, "max_nodes", None)
             if mx is None or not getattr(batch, "edges_grouped", False):
                 return "batch lacks collate metadata (max_nodes / grouped edges)"
-            me = getattr(batch, "max_edges", None)
-            convs = [model.conv1] + list(model.conv_layers)
-            for c in convs:
-                if HF.conv_route(None, c.in_channels, c.out_channels, max_nodes=mx, max_edges=me)[0] is None:
-                    return "graph / layer shape outside the fused kernels (small-graph tiles and one-graph-per-workgroup)"
             jobs = FusedTrainStep._conv_jobs(model, batch, _step)
+            if jobs is None:
+                return "graph / layer shape outside the fused kernels (small-graph tiles and one-graph-per-workgroup)"
             if jobs + head_jobs > _lib.HCG_REDUCE_MAX_JOBS:
                 return (f"{model.n_convolutions} conv layers on this batch's kernel forms need {jobs} gradient reductions, "
                         f"with the head's over the step tail's {_lib.HCG_REDUCE_MAX_JOBS} jobs")
@@ -219,36 +287,14 @@ class FusedTrainStep:
         return None
 
     @staticmethod
-    def _conv_jobs(model, batch=None, step=None) -> int:
-        """Reduction jobs the conv layers' backward leaves for the step tail, from the routes `_prepare` takes and the forms
-        `_backward_layers` picks (the families' `reduce_jobs`): 1 per 64-wide layer on the small-graph tiles or one graph
-        per workgroup; 2 per layer on the wide-layer route (dW, db), per 128-wide one-graph-per-workgroup layer (one per
-        64-column half) and for a 64-wide first layer in its dense training form.  Without a batch: the fewest any batch
-        could need (1 per 64-wide layer, 2 per wider one)."""
-        convs = [model.conv1] + list(model.conv_layers)
+    def _conv_jobs(model, batch=None, step=None) -> Optional[int]:
+        """Reduction jobs the conv layers' backward leaves for the step tail: the sum over the batch's `layer_forms` (asked
+        with its collate metadata), the same plan `_backward_layers` executes; None = a layer outside the fused kernels.
+        Without a batch: the fewest any batch could need (1 per 64-wide layer, 2 per wider one)."""
         if batch is None:
-            return sum(1 if c.out_channels == 64 else 2 for c in convs)
-        sw = FusedTrainStep if step is None else step
-        mx, me, N = batch.max_nodes, getattr(batch, "max_edges", None), batch.x.shape[0]
-        fams = []
-        for c in convs:
-            fam = HF.conv_route(None, c.in_channels, c.out_channels, max_nodes=mx, max_edges=me)[0]
-            if (fam is HF.MID and getattr(c, "family", "auto") != "mid"
-                    and HF.tall_shape_supported(N, c.in_channels, c.out_channels, mx, me)):
-                fam = HF.TALL
-            fams.append(fam)
-        jobs = 0
-        for l, (c, fam) in enumerate(zip(convs, fams)):
-            if fam is HF.TILES:
-                jobs += 1
-            elif fam is HF.TALL or c.out_channels != 64:
-                jobs += 2
-            elif (l == 0 and len(convs) >= 2 and c.in_channels <= 64 and sw.XAGG and sw.XAGG_MID and fams[1] is not HF.TILES
-                  and HF.tall_shape_supported(N, c.in_channels, 64, mx, me, any_rows=True)):
-                jobs += 2                                   # (the first layer's dense training form: csrc/tall.hip slabs)
-            else:
-                jobs += 1
-        return jobs
+            return sum(1 if D == 64 else 2 for _, D, _ in _layer_shapes(model))
+        forms = layer_forms(_layer_shapes(model), batch.x.shape[0], batch.max_nodes, getattr(batch, "max_edges", None), sw=step)
+        return None if forms is None else sum(f.jobs for f in forms)
 
     def _side_stream(self, dev):
         st = self._side_streams.get(dev)
@@ -288,10 +334,11 @@ class FusedTrainStep:
             self._bufs = {"cap": cap, key: b}          # views of the current shape (one live shape at a time)
         return b
 
-    def _tall_ws(self, c: _Ctx, l, F):
-        """Workspace of layer l's wide-layer kernels (H / dH round trip + gradient slabs): forward and backward share it."""
-        wsb = HF.TALL.workspace_bytes(c.geo, 0, F, c.D)
-        return self._ws(c.bufs, ("tall", l), wsb, c.dev), wsb
+    def _layer_ws(self, c: _Ctx, l, fam, gpt, F):
+        """Workspace of layer l's kernels of family `fam` (gradient slabs; the wide-layer kernels' also holds the H / dH round
+        trip, and their forward and backward share it) -> (buffer, bytes)."""
+        wsb = fam.workspace_bytes(c.geo, gpt, F, c.D)
+        return self._ws(c.bufs, (fam.name, l) if fam.row_streaming else l, wsb, c.dev), wsb
 
     def _ws(self, bufs, key, nbytes, dev):
         ws = bufs["ws"].get(key)
@@ -360,9 +407,8 @@ class FusedTrainStep:
             c.y2 = HF._f32c(y).reshape(c.B, -1)
             if c.y2.shape[1] != c.C:
                 raise ValueError(f"targets have {c.y2.shape[1]} columns, the model predicts {c.C}")
-        # (kernel family, graphs_per_tile) of every layer (functional.conv_route)
-        c.routes = [HF.conv_route(plan, cv.in_channels, cv.out_channels, getattr(cv, "family", "auto")) for cv in convs]
-        if (None, 0) in c.routes:
+        c.forms = layer_forms(_layer_shapes(model), plan.N, plan.max_nodes, plan.max_edges, forward_only, self, plan)
+        if c.forms is None:
             raise _lib.HcgError("FusedTrainStep: graph / layer shape outside the fused kernels")
         c.geo = HF.geometry(plan)
         c.bufs = self._buffers((c.N, c.B, c.F, plan.E), c.N, c.B, c.F, c.D, c.C, c.n_conv, c.dev, len(c.lins))
@@ -410,19 +456,18 @@ class FusedTrainStep:
         return c
 
     def _pair_applies(self, c: _Ctx) -> bool:
-        """Decided here, before anything is launched: conv layers 1 and 0 both on the small-graph tiles, layer 1 handing
-        its dx down premasked, and the library agreeing (the query touches no GPU; its answer is kept per shape and
-        buffer set)."""
-        if not (self.BWD_PAIR and self.PREMASK and c.n_small is None and c.n_conv >= 2
-                and c.routes[0][0] is HF.TILES and c.routes[1][0] is HF.TILES):
+        """Decided here, before anything is launched: conv layers 1 and 0 a pair candidate of the plan (both on the
+        small-graph tiles, layer 1 handing its dx down premasked), and the library agreeing (the query touches no GPU; its
+        answer is kept per shape and buffer set)."""
+        if not (c.n_small is None and c.forms[0].pair):
             return False
-        acts0, dx = c.bufs["acts"][0], c.bufs["dacts"][0]
-        key = (c.F, c.D, c.routes[0][1], c.routes[1][1], c.x.data_ptr() % 16, acts0.data_ptr() % 16, dx.data_ptr() % 16)
+        acts0, dx, gpt, gpt_up = c.bufs["acts"][0], c.bufs["dacts"][0], c.forms[0].gpt, c.forms[1].gpt
+        key = (c.F, c.D, gpt, gpt_up, c.x.data_ptr() % 16, acts0.data_ptr() % 16, dx.data_ptr() % 16)
         ok = self._pair_ok.get(key)
         if ok is None:
             # (the upper layer's form does not enter the answer: asked as the not-pooled one)
-            ok = self._pair_ok[key] = HF.TILES.backward_pair(c.geo, c.routes[0][1], c.x, c.W[0], acts0, c.W[1], 2,
-                                                             gpt_up=c.routes[1][1], dout=dx, dx=dx, query=True)
+            ok = self._pair_ok[key] = HF.TILES.backward_pair(c.geo, gpt, c.x, c.W[0], acts0, c.W[1], 2, gpt_up=gpt_up,
+                                                             dout=dx, dx=dx, query=True)
         return ok
 
     def _size_groups(self, batch, plan, convs, D, C, n_conv):
@@ -450,14 +495,25 @@ class FusedTrainStep:
     def _head_in_forward(self, c: _Ctx) -> bool:
         """The C3 form: both conv layers on small-graph tiles, pooled layer on chip, one-launch head -> everything up to
         the loss is ONE launch."""
-        return (self.HEAD_IN_FORWARD and self.POOLBITS and c.n_small is None and c.n_conv == 2 and c.head_fused
-                and c.loss_mode != _lib.HCG_LOSS_CE      # (the head in the forward launch is regression-only)
-                and len(c.lins) == 2 and c.routes[0][0] is HF.TILES and c.routes[0] == c.routes[1])
+        return bool(self.HEAD_IN_FORWARD and c.n_small is None and c.head_fused
+                    and c.loss_mode != _lib.HCG_LOSS_CE      # (the head in the forward launch is regression-only)
+                    and len(c.lins) == 2 and c.forms[-1].stacked and c.forms[-1].bits)
+
+    def _pooled_bits(self, c: _Ctx):
+        """The pooled layer's activations stay on chip: the bits its backward needs of them (sign, is-the-column-max) are all
+        that is stored -- two bits per element on the small-graph tiles, one byte per (row, 4 columns) on the wide-layer
+        route (csrc/tall.hip: k_gseg_bwd).  -> their workspace, None for a pooled layer in the plain form."""
+        top = c.forms[-1]
+        if top.bits:
+            nbytes = (_lib.load().hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, c.B, top.gpt) if top.bits == "poolbits"
+                      else c.N * (c.D // 4))
+            c.poolbits = self._ws(c.bufs, top.bits, nbytes, c.dev)
+        return c.poolbits
 
     def _forward_with_head(self, c: _Ctx):
         """conv stack + pooling + readout head (forward, squared error, unscaled readout backward): one launch."""
-        lib, bufs, gpt = _lib.load(), c.bufs, c.routes[0][1]
-        c.poolbits = self._ws(bufs, "poolbits", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, c.B, gpt), c.dev)
+        lib, bufs, gpt = _lib.load(), c.bufs, c.forms[0].gpt
+        self._pooled_bits(c)
         l0, l1 = c.lins
         self._tiles_stack(
             c, c.geo, gpt, poolbits=c.poolbits, y=c.y2, head_W0=HF._f32c(l0.weight), head_b0=HF._f32c(l0.bias),
@@ -472,50 +528,26 @@ class FusedTrainStep:
 
     def _forward_layers(self, c: _Ctx):
         """The conv stack (+ pooling) of every other shape: one launch per layer (stacked pair: one)."""
-        lib, bufs, geo = _lib.load(), c.bufs, c.geo
-        acts, emb, routes, n_conv, N, B, D = bufs["acts"], bufs["emb"], c.routes, c.n_conv, c.N, c.B, c.D
-        # small-graph tiles: the pooled layer's activations stay on chip, two bits per element (sign, is-the-column-max)
-        # are all its backward needs of them
-        if routes[-1][0] is HF.TILES and self.POOLBITS:
-            c.poolbits = self._ws(bufs, "poolbits", lib.hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, B, routes[-1][1]), c.dev)
-        if n_conv == 2 and routes[0][0] is HF.TILES and routes[0] == routes[1]:
-            self._tiles_stack(c, geo, routes[0][1], poolbits=c.poolbits, out2=None if c.poolbits is not None else acts[1])
+        bufs, geo, forms = c.bufs, c.geo, c.forms
+        acts, top = bufs["acts"], c.n_conv - 1
+        bits = self._pooled_bits(c)
+        if forms[top].stacked:
+            self._tiles_stack(c, geo, forms[0].gpt, poolbits=bits, out2=None if bits is not None else acts[1])
             return
         h = c.x
-        for l, (fam, gpt) in enumerate(routes):
-            pe = emb if l == n_conv - 1 else None
-            Fl = h.shape[1]
-            if fam is HF.TILES:
-                bits = c.poolbits if pe is not None else None
-                fam.forward(geo, gpt, h, c.W[l], c.bs[l], 1, out=None if bits is not None else acts[l], emb=pe, poolbits=bits)
-            elif fam is HF.TALL:
-                ws, wsb = self._tall_ws(c, l, Fl)
-                bits = None
-                if pe is not None and self.POOLBITS and Fl <= (64 if D == 64 else 128):
-                    # the pooled layer's activations stay on chip: one byte per (row, 4 columns) -- sign, is-the-column-max --
-                    # is all its backward (csrc/tall.hip: k_gseg_bwd) needs of them
-                    bits = c.poolbits = self._ws(bufs, "poolbits_tall", N * (D // 4), c.dev)
-                xagg = signs = None
-                if (l == 0 and n_conv >= 2 and (Fl <= 64 or D == 128) and self.XAGG and not c.forward_only
-                        and routes[1][0] is HF.TALL):
-                    # training form of the FIRST layer: Ahat x [N, 32 | 64 | 128] and the sign pieces of its output leave too; its
-                    # whole backward is then ONE dense launch (csrc/tall.hip: k_tall_dw<FIRST>) -- no transpose sum, no dH round trip
-                    xagg, signs = self._xagg(c, 32 if Fl <= 32 else (64 if Fl <= 64 else 128))
-                fam.forward(geo, 0, h, c.W[l], c.bs[l], 1, out=None if bits is not None else acts[l], emb=pe, poolbits=bits,
-                            xagg=xagg, signs=signs, ws=ws, wsb=wsb)
-            else:
-                xagg = signs = None
-                if (l == 0 and n_conv >= 2 and D == 64 and Fl <= 64 and self.XAGG and self.XAGG_MID and not c.forward_only
-                        and routes[1][0] is not HF.TILES and HF.tall_supported(c.plan, Fl, D, any_rows=True)):
-                    # (as on the wide-layer route: Ahat x + sign pieces for the dense backward)
-                    xagg, signs = self._xagg(c, 32 if Fl <= 32 else 64)
-                fam.forward(geo, 0, h, c.W[l], c.bs[l], 1, out=acts[l], emb=pe, xagg=xagg, signs=signs)
+        for l, f in enumerate(forms):
+            kw = dict(out=acts[l])
+            if l == top:
+                kw = dict(out=None if bits is not None else acts[l], emb=bufs["emb"], poolbits=bits)
+            if f.fam.row_streaming:
+                kw["ws"], kw["wsb"] = self._layer_ws(c, l, f.fam, f.gpt, h.shape[1])
+            if f.kp:
+                # training form of the FIRST layer: Ahat x [N, kp] and the sign pieces of its output leave too, for the dense
+                # backward -- no transpose sum, no dH round trip
+                c.xagg = (self._ws(bufs, "xagg", c.N * f.kp * 4, c.dev), self._ws(bufs, "signs", c.N * (c.D // 8), c.dev))
+                kw["xagg"], kw["signs"] = c.xagg
+            f.fam.forward(geo, f.gpt, h, c.W[l], c.bs[l], 1, **kw)
             h = acts[l]
-
-    def _xagg(self, c: _Ctx, kp):
-        """Buffers of the first layer's training form: Ahat x [N, kp] and the sign pieces of its output."""
-        c.xagg = (self._ws(c.bufs, "xagg", c.N * kp * 4, c.dev), self._ws(c.bufs, "signs", c.N * (c.D // 8), c.dev))
-        return c.xagg
 
     def _forward_routed(self, c: _Ctx, geo_a, geo_b, gpt, fork, join, stream_b):
         """Size-grouped batch: graphs [0, n_small) through the tiles (both layers + pooling in one launch, pooled layer on
@@ -596,73 +628,48 @@ class FusedTrainStep:
         c.jobs.n += 1
 
     def _backward_layers(self, c: _Ctx):
-        """Conv stack backward, last layer first.  A fused-tile layer can hand its dx down already multiplied by the
-        activation derivative of the layer below (it holds those rows anyway, for dW); that layer then never reads its own
-        output: one tensor less per step."""
-        bufs, geo, jobs = c.bufs, c.geo, c.jobs
-        acts, emb, demb, n_conv, D = bufs["acts"], bufs["emb"], bufs["demb"], c.n_conv, c.D
-        g = lambda q: self._g(c, q)
-        dh, premasked = None, False
-        for l in reversed(range(n_conv)):
-            fam, gpt = c.routes[l]
+        """Conv stack backward, last layer first, each layer in the form the plan gave it (`LayerForm.flags`: who applies
+        which activation derivative)."""
+        bufs, geo, jobs, forms, D = c.bufs, c.geo, c.jobs, c.forms, c.D
+        acts, top = bufs["acts"], c.n_conv - 1
+
+        def reduce(l, fam, gpt, ws, wsb, **kw):
+            F = c.W[l].shape[1]
+            jobs.n += fam.reduce_jobs(geo, gpt, F, D, ws, wsb, self._g(c, c.W[l]), self._g(c, c.bs[l]), jobs.slot(), **kw)
+
+        for l in reversed(range(c.n_conv)):
+            f, last = forms[l], l == top
             inp = c.x if l == 0 else acts[l - 1]
-            Fl = inp.shape[1]
-            dx = bufs["dacts"][l - 1] if l > 0 else None
-            last = l == n_conv - 1
-            W, dW, db = c.W[l], g(c.W[l]), g(c.bs[l])         # (c.W / c.bs: the parameters themselves)
-            act = 1 if (last or not premasked) else 0
-            if l == 1 and c.bwd_pair:
+            # the gradient comes in from the head (demb) or the layer above (its dx), goes out as dx; of the layer's own output
+            # the launch reads what its form leaves it to need: nothing where the pooled layer's bits or the dense first
+            # layer's sign pieces stand in for it, or where the layer above premasked dout
+            bits = c.poolbits if last else None
+            kw = dict(dout=None if last else bufs["dacts"][l], demb=bufs["demb"] if last else None,
+                      emb=bufs["emb"] if (last and bits is None) else None,
+                      out=acts[l] if (bits is None and not f.kp and (last or f.flags & 1)) else None,
+                      dx=bufs["dacts"][l - 1] if l > 0 else None)
+            if bits is not None:
+                kw["poolbits"] = bits
+            if f.pair == "upper" and c.bwd_pair:
                 # layers 1 and 0 in ONE launch: layer 1's phase, a workgroup barrier, layer 0's phase over the same tiles
-                bits = c.poolbits if last else None
-                F0 = c.x.shape[1]
-                wsb = fam.workspace_bytes(geo, gpt, Fl, D)
-                ws = self._ws(bufs, l, wsb, c.dev)
-                wsb0 = fam.workspace_bytes(geo, gpt, F0, D)
-                ws0 = self._ws(bufs, 0, wsb0, c.dev)
-                fam.backward_pair(geo, gpt, c.x, c.W[0], inp, W, act | 2, dout=None if last else dh,
-                                  demb=demb if last else None, emb=emb if (last and bits is None) else None,
-                                  out=acts[l] if (bits is None and (act or last)) else None, poolbits=bits, dx=dx,
-                                  ws_up=ws, wsb_up=wsb, ws=ws0, wsb=wsb0)
-                jobs.n += fam.reduce_jobs(geo, gpt, Fl, D, ws, wsb, dW, db, jobs.slot())
-                jobs.n += fam.reduce_jobs(geo, gpt, F0, D, ws0, wsb0, g(c.W[0]), g(c.bs[0]), jobs.slot())
+                ws, wsb = self._layer_ws(c, 1, f.fam, f.gpt, D)
+                ws0, wsb0 = self._layer_ws(c, 0, f.fam, f.gpt, c.F)
+                f.fam.backward_pair(geo, f.gpt, c.x, c.W[0], inp, c.W[1], f.flags, ws_up=ws, wsb_up=wsb, ws=ws0, wsb=wsb0, **kw)
+                reduce(1, f.fam, f.gpt, ws, wsb)
+                reduce(0, f.fam, f.gpt, ws0, wsb0)
                 return
-            if fam is HF.TILES:
-                bits = c.poolbits if last else None
-                premasked = self.PREMASK and l > 0
-                wsb = fam.workspace_bytes(geo, gpt, Fl, D)
-                ws = self._ws(bufs, l, wsb, c.dev)
-                fam.backward(geo, gpt, inp, W, act | (2 if premasked else 0), dout=None if last else dh,
-                             demb=demb if last else None, emb=emb if (last and bits is None) else None,
-                             out=acts[l] if (bits is None and (act or last)) else None, poolbits=bits, dx=dx, ws=ws, wsb=wsb)
-                jobs.n += fam.reduce_jobs(geo, gpt, Fl, D, ws, wsb, dW, db, jobs.slot())
-            elif fam is HF.TALL:
-                premasked = False
-                ws, wsb = self._tall_ws(c, l, Fl)
-                bits = c.poolbits if last else None          # (the forward's bit form stands in for the layer's output and emb)
-                first = c.xagg if (l == 0 and not last and dx is None) else None     # (Ahat x, sign pieces) of the forward
-                fam.backward(geo, 0, inp, W, act, dout=None if last else dh, demb=demb if last else None,
-                             emb=emb if (last and bits is None) else None,
-                             out=acts[l] if ((act or last) and bits is None and first is None) else None, poolbits=bits,
-                             xagg=first[0] if first else None, signs=first[1] if first else None, dx=dx, ws=ws, wsb=wsb)
-                jobs.n += fam.reduce_jobs(geo, 0, Fl, D, ws, wsb, dW, db, jobs.slot(), first=first is not None)
-            elif l == 0 and not last and c.xagg is not None:
-                # the first layer's backward as ONE dense launch over the forward's Ahat x (csrc/tall.hip: k_tall_dw<FIRST>) also
-                # behind the one-graph-per-workgroup kernels; the batch's node count is read on the device (graph_ptr[B]): a
-                # captured epoch's slot has a CAPACITY of rows
-                premasked = False
-                ws, wsb = self._tall_ws(c, l, Fl)
-                HF.TALL.backward(geo, 0, inp, W, act, dout=dh, xagg=c.xagg[0], signs=c.xagg[1],
-                                 nodes_dev=geo.graph_ptr + 4 * geo.B, ws=ws, wsb=wsb)
-                jobs.n += HF.TALL.reduce_jobs(geo, 0, Fl, D, ws, wsb, dW, db, jobs.slot(), first=True)
-            else:
-                premasked = self.PREMASK and l > 0
-                wsb = fam.workspace_bytes(geo, 0, Fl, D)
-                ws = self._ws(bufs, l, wsb, c.dev)
-                fam.backward(geo, 0, inp, W, act | (2 if premasked else 0), dout=None if last else dh,
-                             demb=demb if last else None, emb=emb if last else None, out=acts[l] if (act or last) else None,
-                             dx=dx, ws=ws, wsb=wsb)
-                jobs.n += fam.reduce_jobs(geo, 0, Fl, D, ws, wsb, dW, db, jobs.slot())
-            dh = dx
+            fam, first = f.fam, {}
+            if f.kp:
+                # the first layer's backward as ONE dense launch over the forward's Ahat x: the wide-layer route's launcher
+                # whatever the layer's family.  Behind the per-graph kernels the batch's node count is read on the device
+                # (graph_ptr[B]): a captured epoch's slot has a CAPACITY of rows
+                fam, first = HF.TALL, dict(first=True)
+                kw.update(xagg=c.xagg[0], signs=c.xagg[1])
+                if not f.fam.row_streaming:
+                    kw["nodes_dev"] = geo.graph_ptr + 4 * geo.B
+            ws, wsb = self._layer_ws(c, l, fam, f.gpt, inp.shape[1])
+            fam.backward(geo, f.gpt, inp, c.W[l], f.flags, ws=ws, wsb=wsb, **kw)
+            reduce(l, fam, f.gpt, ws, wsb, **first)
 
     def _backward_routed(self, c: _Ctx, geo_a, geo_b, gpt, fork, join, stream_b):
         """Size-grouped batch: each layer's backward = tiles on the small graphs + waves on the others; both groups' slabs of
@@ -1068,9 +1075,9 @@ class EpochWindow:
             plan.rowptr = plan.col = plan.eid = plan.rowptr_t = plan.col_t = plan.eid_t = None
             plan.dinv = plan.ew_csr = plan.ew_csc = plan.dinv_unw = None
             batch._hcg_plan = plan
-            for c in [model.conv1] + list(model.conv_layers):      # (whatever the conv's family preference)
-                if HF.conv_route(plan, c.in_channels, c.out_channels)[0] is HF.TALL:
-                    raise _lib.HcgError("EpochWindow: a layer would run on the dense row-streaming kernels (capacity-padded rows)")
+            shapes = [(Fl, D, "auto") for Fl, D, _ in _layer_shapes(model)]      # (whatever the conv's family preference)
+            if any(f.fam.row_streaming for f in layer_forms(shapes, Ncap, maxn, maxe, plan=plan) or ()):
+                raise _lib.HcgError("EpochWindow: a layer would run on the dense row-streaming kernels (capacity-padded rows)")
             self.batches.append(batch)
             self.spans.append((i, B, off))
 
@@ -1206,13 +1213,7 @@ def train_network(model, train_loader, device):
     """reference utils/utils_model.py:55-70: one epoch; returns sum(loss * num_graphs) / len(dataset).
     The per-batch `loss.item()` of the reference is replaced by a device-side accumulation and ONE sync."""
     model.train()
-    fused = getattr(model, "_hcg_train_step", None)
-    if fused is None:
-        fused = FusedTrainStep(model)
-        try:
-            model._hcg_train_step = fused
-        except Exception:
-            pass
+    fused = _fused_of(model)
     val = _epoch_window(model, train_loader)
     if val is not None:
         return val
@@ -1322,13 +1323,7 @@ def _eval_window(model, loader, fused, launch_only: bool = False):
 def eval_network(model, loader, device):
     """reference utils/utils_model.py:72-79 (forward + sqrt(MSE) per batch; no parameter update)."""
     model.eval()
-    fused = getattr(model, "_hcg_train_step", None)
-    if fused is None:
-        fused = FusedTrainStep(model)
-        try:
-            model._hcg_train_step = fused
-        except Exception:
-            pass
+    fused = _fused_of(model)
     total = _eval_window(model, loader, fused)
     if total is not None:
         return total

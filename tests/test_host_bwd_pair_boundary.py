@@ -14,7 +14,7 @@ import torch
 
 from hcatgnet_amd import _lib
 from hcatgnet_amd import functional as HF
-from hcatgnet_amd.train import FusedTrainStep, _Ctx
+from hcatgnet_amd.train import FusedTrainStep, _Ctx, layer_forms
 from tests.test_host_bwd_pair import _pair_block
 
 OK, INVALID, UNSUPPORTED = 0, -1, -3
@@ -63,8 +63,9 @@ def test_the_library_answers_with_the_same_function(queries):
         assert lib.hcg_fused_forward(ctypes.addressof(a), None) == on(a), kw
 
 
-def _ctx(F=64, D=64, B=3, nodes=30, routes=None, n_small=None, n_conv=2):
-    """What `_pair_applies` reads of a prepared step, on CPU tensors: the query dereferences none of them."""
+def _ctx(F=64, D=64, B=3, nodes=30, routes=None, n_small=None, n_conv=2, step=None):
+    """What `_pair_applies` reads of a prepared step, on CPU tensors: the query dereferences none of them.  `routes`: what
+    `conv_route` is made to answer for the layers (default: what it does answer, the tiles at one graph per tile)."""
     c = _Ctx()
     N = B * nodes
     c.F, c.D, c.n_conv, c.n_small = F, D, n_conv, n_small
@@ -75,7 +76,10 @@ def _ctx(F=64, D=64, B=3, nodes=30, routes=None, n_small=None, n_conv=2):
             torch.zeros(4, dtype=torch.int32)]
     c.batch = keep                                        # (kept alive beside the addresses below)
     c.geo = HF.Geometry(keep[0].data_ptr(), 8, keep[1].data_ptr(), keep[2].data_ptr(), N, B, nodes, 64, keep[3].data_ptr(), 0)
-    c.routes = routes if routes is not None else [(HF.TILES, 1), (HF.TILES, 1)]
+    answers = iter(routes if routes is not None else [(HF.TILES, 1), (HF.TILES, 1)])
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(HF, "conv_route", lambda *a, **kw: next(answers))
+        c.forms = layer_forms([(F, D, "auto"), (D, D, "auto")][:n_conv], N, nodes, 64, sw=step)
     return c
 
 
@@ -95,13 +99,14 @@ def test_pair_applies_only_where_the_step_can_use_it(monkeypatch):
     asked = []
     real = HF.TILES.backward_pair
     monkeypatch.setattr(HF.TILES, "backward_pair", lambda *a, **kw: (asked.append(kw.get("query")), real(*a, **kw))[1])
-    assert _step()._pair_applies(_ctx()) is True and asked == [True]          # the control: the flagship form is accepted
+    applies = lambda step, **kw: step._pair_applies(_ctx(step=step, **kw))     # (the context's plan: made for that step)
+    assert applies(_step()) is True and asked == [True]                       # the control: the flagship form is accepted
     del asked[:]
-    assert _step()._pair_applies(_ctx(n_small=2)) is False                    # size-grouped batch
-    assert _step(PREMASK=False)._pair_applies(_ctx()) is False                # dx would not go down premasked
-    assert _step()._pair_applies(_ctx(routes=[(HF.MID, 0), (HF.TILES, 1)])) is False    # first layer off the tile family
-    assert _step()._pair_applies(_ctx(routes=[(HF.TALL, 0), (HF.TILES, 1)])) is False
-    assert _step()._pair_applies(_ctx(n_conv=1)) is False
-    assert _step(BWD_PAIR=False)._pair_applies(_ctx()) is False
+    assert applies(_step(), n_small=2) is False                               # size-grouped batch
+    assert applies(_step(PREMASK=False)) is False                             # dx would not go down premasked
+    assert applies(_step(), routes=[(HF.MID, 0), (HF.TILES, 1)]) is False     # first layer off the tile family
+    assert applies(_step(), routes=[(HF.TALL, 0), (HF.TILES, 1)]) is False
+    assert applies(_step(), n_conv=1) is False
+    assert applies(_step(BWD_PAIR=False)) is False
     assert asked == []                                                        # ... all of them before the library is asked
-    assert _step()._pair_applies(_ctx(routes=[(HF.TILES, 3), (HF.TILES, 1)])) is False and asked == [True]   # the library's refusal
+    assert applies(_step(), routes=[(HF.TILES, 3), (HF.TILES, 1)]) is False and asked == [True]   # the library's refusal

@@ -190,7 +190,7 @@ def test_kernel_family_selection_is_host_only(monkeypatch):
     #   groups  FusedTrainStep._size_groups returns with n_small = B // 2: tiles for the small group, one graph per wave for the
     #           rest whatever the route of the whole batch or `family` ("REAL", "mid-REAL" rows)
     #   epoch   EpochWindow decides (refuses the wide-layer route; it does not consult `family`: "mid-C5", "mid-REAL" rows)
-    from hcatgnet_amd.train import FusedTrainStep
+    from hcatgnet_amd.train import FusedTrainStep, layer_forms
     T = HF.TALL_MIN_NODES_D64
     table = [
         (('C1', 64, 64, 30, 64, 30, 1, 'auto', 'blocked', False), ('tiles/tiles', 'tiles/tiles', 'ok', None, 'ok')),
@@ -249,14 +249,16 @@ def test_kernel_family_selection_is_host_only(monkeypatch):
         for cv in convs:
             cv(torch.zeros(1), plan, apply_act=True)
         assert "/".join(picked) == conv, label
-        routes = [HF.conv_route(plan, cv.in_channels, cv.out_channels, cv.family) for cv in convs]       # as _prepare
-        assert ("error" if any(r[0] is None for r in routes) else "/".join(r[0].name for r in routes)) == step, label
+        shapes = [(cv.in_channels, cv.out_channels, cv.family) for cv in convs]
+        forms = layer_forms(shapes, plan.N, plan.max_nodes, plan.max_edges, plan=plan)                   # as _prepare
+        assert ("error" if forms is None else "/".join(f.fam.name for f in forms)) == step, label
         batch = H.Batch(torch.zeros(4, F), torch.zeros(2, 0, dtype=torch.int64), torch.zeros(4, dtype=torch.int64), B,
                         y=torch.zeros(B), max_nodes=mxn, max_edges=mxe, edges_grouped=True, n_small=B // 2 if B > 1 else None)
         why = FusedTrainStep.unsupported_reason(m, batch)
         assert (why is None and support == "ok") or (why is not None and support in why), label
         assert FusedTrainStep(m, optimizer_step=False)._size_groups(batch, plan, convs, D, 1, len(convs)) == groups, label
-        refuse = any(HF.conv_route(plan, cv.in_channels, cv.out_channels)[0] is HF.TALL for cv in convs)       # as EpochWindow
+        auto = layer_forms([(Fl, Dl, "auto") for Fl, Dl, _ in shapes], plan.N, plan.max_nodes, plan.max_edges, plan=plan)
+        refuse = any(f.fam is HF.TALL for f in auto or ())                                               # as EpochWindow
         assert ("refuse" if refuse else "ok") == epoch, label
 
 
