@@ -104,6 +104,40 @@ constexpr int BUF_FLOATS = TM * HS;
 constexpr int CNT_EXACT = 256;  // adjacency counts up to here are exact in one bf16 piece
 static_assert(CNT_WORDS * 4 <= BUF_FLOATS * 4, "the count matrix must fit inside the tile buffer it aliases");
 
+// Wave priority inside the tile loops.  Waves w and w + 4 of a workgroup share a SIMD; at equal priority the older one (w) wins
+// every VALU issue contest, leaves the loop ~10 k cycles early and idles at the barrier behind it while its partner finishes
+// alone (profiles/prio_rotation_ab.txt).  So the winner changes once per round: tile_prio_begin() in front of a
+// wave's first tile puts waves 4-7 at priority 1, tile_prio_next() behind every round exchanges the two halves,
+// tile_prio_end() behind the loop returns every wave -- with tiles or without, after an even or an odd number of rounds -- to
+// priority 0 for the barrier and all that follows it.
+// tile_prio_next() reads the wave's own priority back from the STATUS register (USER_PRIO, bits 4:3) instead of working it
+// out from the wave and round numbers: that keeps no register alive across the tile (with them, 71 of the 136 tile kernels
+// compiled to other register and spill counts; so they did with the first set under `if (have)` in the backward).
+// Each call is a scalar branch around two s_setprio with constant operands.
+// ON = the plain tile sequence behind the wide row stager.  Not the dealt form: in its partial last round the waves that run
+// once more are the low-numbered ones, so there the older wave winning the rounds before is what ends the loop soonest --
+// with waves 4-7 ahead in round 0 the ragged batch's step was 4 % slower.  Not the scalar-stager forms: they are short of
+// registers (every placement tried moved their spill counts).  Both keep the code they had.
+template <bool ON>
+__device__ __forceinline__ void tile_prio_begin(int wave) {
+  if constexpr (ON) {
+    if (wave & 4) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+  }
+}
+template <bool ON>
+__device__ __forceinline__ void tile_prio_next() {
+  if constexpr (ON) {
+    constexpr int USER_PRIO = 2 | (3 << 6) | (1 << 11);   // hwreg(HW_REG_STATUS, offset 3, 2 bits)
+    if (__builtin_amdgcn_s_getreg(USER_PRIO)) __builtin_amdgcn_s_setprio(0);
+    else __builtin_amdgcn_s_setprio(1);
+  }
+}
+template <bool ON>
+__device__ __forceinline__ void tile_prio_end() {
+  if constexpr (ON) __builtin_amdgcn_s_setprio(0);
+}
+
 // per-wave LDS.  Forward: the count matrix occupies the first CNT_WORDS words of `buf` while the tile's
 // adjacency fragments are being built, then the x tile is staged over it.  Backward: `cnt` is separate.
 struct WaveLdsF {
@@ -502,6 +536,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_fwd(
   AdjFrags adj;
   float dvr[16];
   if (have) {
+    tile_prio_begin<VEC && !DEAL>(wave);
     te.build(cnt, L.ldinv, L.lgp, ti, ei, E, lane, status);
     adj.read<false>(cnt, r, h, lane, status);
 #pragma unroll
@@ -665,6 +700,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_fwd(
     have = have_next;
     ++round_it;
     if (have_next) {
+      tile_prio_next<VEC && !DEAL>();
       if (!VEC) {
         tin = tile_finish(raw_cur, gpt, lane, status);
         sxn.load(x, F, N, tin.nbase, tin.n, lane);
@@ -682,6 +718,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_layer_fwd(
       STAMP(58);
     }
   }
+  tile_prio_end<VEC && !DEAL>();
   STAMP(63);
   STAMP_FLUSH();
   if constexpr (HEAD != 0) {
@@ -766,6 +803,7 @@ __device__ __forceinline__ void fused_bwd_phase(
   float dbl0 = 0.f, dbl1 = 0.f;   // BITS: column r / 32 + r of db (this lane's half of the rows)
   BSTAMP(0);
 
+  tile_prio_begin<VEC && !DEAL>(wave);
   while (have) {
     te.build(L.cnt, L.ldinv, L.lgp, ti, ei, E, lane, status);
     BSTAMP(1 + 8 * bstamp_it);
@@ -1073,10 +1111,12 @@ __device__ __forceinline__ void fused_bwd_phase(
       sa = san;
       if (!POOLG) sd = sdn;
       te = ten;
+      tile_prio_next<VEC && !DEAL>();
     }
     BSTAMP(8 + 8 * bstamp_it);
     if (bstamp_it < 5) ++bstamp_it;
   }
+  tile_prio_end<VEC && !DEAL>();
   BSTAMP(60);
 
   // ---- combine the waves of this workgroup (fixed order, two rounds of four waves through a flat
@@ -1099,6 +1139,7 @@ __device__ __forceinline__ void fused_bwd_phase(
 #pragma unroll
   for (int round = 0; round < 2; ++round) {
     __syncthreads();   // tile buffers (round 0) / the previous round's regions (round 1) are free
+    if (round == 0) BSTAMP(61);   // the barrier behind the tile loop is passed
     if ((wave >> 2) == round) {
       float* mine = flat + (size_t)(wave & 3) * SLABF;
 #pragma unroll

@@ -92,9 +92,9 @@ int main() {
   std::vector<unsigned long long> sb(nst);
   CK(hipMemcpy(sb.data(), dstamp, nst * 8, hipMemcpyDeviceToHost));
   // A = upper layer (stamps 0..63), B = lower layer (64..127); cycles since the workgroup's first stamp
-  const int idx[] = {0, 60, 62, 63, 64 + 56, 64 + 0, 64 + 1, 64 + 2, 64 + 3, 64 + 60, 64 + 63};
-  const char* nm[] = {"A.loop", "A.loop-end", "A.combined", "A.slab", "barrier", "B.begin-issued", "B.count-built",
-                      "B.first-MFMA", "B.agg-done", "B.loop-end", "B.slab"};
+  const int idx[] = {0, 60, 61, 62, 63, 64 + 56, 64 + 0, 64 + 1, 64 + 2, 64 + 3, 64 + 60, 64 + 61, 64 + 63};
+  const char* nm[] = {"A.loop", "A.loop-end", "A.loop-barrier", "A.combined", "A.slab", "barrier", "B.begin-issued", "B.count-built",
+                      "B.first-MFMA", "B.agg-done", "B.loop-end", "B.loop-barrier", "B.slab"};
   for (int wg = 0; wg < 2; ++wg) {
     const unsigned long long* s0 = sb.data() + (size_t)wg * WAVES * 128;
     unsigned long long base = ~0ull;
@@ -111,6 +111,13 @@ int main() {
     for (size_t k = 0; k < sizeof(idx) / sizeof(idx[0]); ++k) {
       printf("  %-14s", nm[k]);
       for (int w = 0; w < WAVES; ++w) printf(" %9llu", s0[w * 128 + idx[k]] - base);
+      printf("\n");
+    }
+    // SIMD partners w and w + 4: how much later the younger one leaves each tile loop
+    for (int ph = 0; ph < 2; ++ph) {
+      printf("  %s partner skew (wave w+4 - wave w) ", ph ? "B.loop-end" : "A.loop-end");
+      for (int w = 0; w < WAVES / 2; ++w)
+        printf(" %9lld", (long long)s0[(w + 4) * 128 + 64 * ph + 60] - (long long)s0[w * 128 + 64 * ph + 60]);
       printf("\n");
     }
   }

@@ -1,6 +1,8 @@
 // Dev probe (not product): the stacked forward with the readout head in its tail (hcg_fused_forward, training form) on a
 // C3-like batch, with s_memtime stamps of the head phases (head_tile.h: H16STAMP) of the first workgroups' waves.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-slp-vectorize -DHCG_HEAD_STAMP -o tools/probe_head_tail tools/probe_head_tail.hip
+// With -DHCG_STAMP as well: the eight waves' stamps around the forward's tile loop (entry, end, barrier passed) and the skew
+// between the two waves of a SIMD.
 #include "../hcatgnet_amd/csrc/fused.hip"
 #include <cstdio>
 #include <vector>
@@ -70,6 +72,39 @@ int main() {
       for (int i = 1; i <= 10; ++i) printf(" %s %llu |", nm[i], st[blk][w][i] - st[blk][w][i - 1]);
       printf(" total %llu\n", st[blk][w][10] - st[blk][w][0]);
     }
+#endif
+#if defined(HCG_STAMP) && defined(HCG_HEAD_STAMP)
+  // with -DHCG_STAMP as well: one more launch (head on), alone on the device, with the tile loop's stamp buffer set -- when
+  // each wave enters the tile loop (STAMP 0), leaves it (STAMP 63) and passes the barrier in front of the head tail
+  // (H16STAMP 1); cycles since the workgroup's first loop entry
+  {
+    unsigned long long* dstamp;
+    const size_t nst = 4 * 8 * 64;
+    CK(hipMalloc(&dstamp, nst * 8)); CK(hipMemset(dstamp, 0, nst * 8));
+    CK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &dstamp, sizeof(dstamp)));
+    int rc = hcg_fused_forward(&a, 0);
+    if (rc) { printf("rc %d\n", rc); return 1; }
+    CK(hipDeviceSynchronize());
+    std::vector<unsigned long long> sb(nst);
+    CK(hipMemcpy(sb.data(), dstamp, nst * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_h16_stamp), sizeof(st)));
+    for (int wg = 0; wg < 2; ++wg) {
+      const unsigned long long* s0 = sb.data() + (size_t)wg * 8 * 64;
+      unsigned long long base = ~0ull;
+      for (int w = 0; w < 8; ++w) base = s0[w * 64] < base ? s0[w * 64] : base;
+      printf("workgroup %d\n  %-14s", wg, "stamp");
+      for (int w = 0; w < 8; ++w) printf(" %8s%d", "wave", w);
+      printf("\n  %-14s", "F.loop");
+      for (int w = 0; w < 8; ++w) printf(" %9llu", s0[w * 64] - base);
+      printf("\n  %-14s", "F.loop-end");
+      for (int w = 0; w < 8; ++w) printf(" %9llu", s0[w * 64 + 63] - base);
+      printf("\n  %-14s", "F.loop-barrier");
+      for (int w = 0; w < 8; ++w) printf(" %9llu", st[wg][w][1] - base);
+      printf("\n  F.loop-end partner skew (wave w+4 - wave w) ");
+      for (int w = 0; w < 4; ++w) printf(" %9lld", (long long)s0[(w + 4) * 64 + 63] - (long long)s0[w * 64 + 63]);
+      printf("\n");
+    }
+  }
 #endif
   return 0;
 }
