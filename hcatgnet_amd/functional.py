@@ -331,12 +331,14 @@ _JOB_BYTES = _lib.job_bytes()
 
 class JobList:
     """A host array of HCG_REDUCE_MAX_JOBS hcg_reduce_job: a family's `reduce_jobs` writes at `slot()`, the count it returns
-    goes to `n`; hcg_step_tail -- or `flush`, the reductions alone -- consumes them."""
-    __slots__ = ("buf", "addr", "n")
+    goes to `n`; hcg_step_tail -- or `flush`, the reductions alone -- consumes them.  `spare`: one more descriptor behind
+    the array, for a job on its way into another through hcg_reduce_job_append."""
+    __slots__ = ("buf", "addr", "n", "spare")
 
     def __init__(self):
-        self.buf = ctypes.create_string_buffer(_JOB_BYTES * _lib.HCG_REDUCE_MAX_JOBS)
+        self.buf = ctypes.create_string_buffer(_JOB_BYTES * (_lib.HCG_REDUCE_MAX_JOBS + 1))
         self.addr, self.n = ctypes.addressof(self.buf), 0
+        self.spare = self.addr + _JOB_BYTES * _lib.HCG_REDUCE_MAX_JOBS
 
     def slot(self) -> int:
         return self.addr + self.n * _JOB_BYTES

@@ -65,40 +65,53 @@ class LayerForm(NamedTuple):
     gpt: int                # graphs per tile (0 off the small-graph tiles)
     stacked: bool           # forward: the two layers of a two-layer stack on the tiles, one launch
     bits: Optional[str]     # pooled layer kept as sign / is-the-column-max bits only: the workspace that holds them
-    #                         ("poolbits": tiles; "poolbits_tall": wide-layer route); None = its activations are stored
+    #                         ("poolbits": tiles, "poolbits_r": as a part; "poolbits_tall": wide-layer route); None = stored
+    head: bool              # pooled layer of a stack on the tiles, kept as bits: its forward launch can carry the readout head
     kp: int                 # dense first layer: the forward also leaves Ahat x [N, kp] (32 / 64 / 128) and the sign pieces of
     #                         its output, the whole backward is ONE dense launch (csrc/tall.hip: k_tall_dw<FIRST>); 0 = not
     flags: int              # the backward's flag word: 1 = applies its own activation derivative (0: dout arrives premasked,
     #                         the layer never reads its own output), 2 = hands dx down premasked
     pair: Optional[str]     # "upper" (layer 1) / "lower" (layer 0) of a backward pair candidate: both on the tiles, dx premasked
-    jobs: int               # reduction jobs its backward leaves for the step tail
+    jobs: int               # reduction jobs its backward leaves for the step tail (a later part: 0, its slabs join the first's)
 
 
-def _layer_shapes(model):
-    """(in_channels, out_channels, family preference) of every conv layer."""
-    return [(c.in_channels, c.out_channels, getattr(c, "family", "auto")) for c in [model.conv1] + list(model.conv_layers)]
+class Part(NamedTuple):
+    """A graph range of a step's batch.  An ordinary batch is one part; a size-grouped one (`collate(..., group_by_size=True)`)
+    is two: graphs [0, n_small) on the small-graph tiles, the others one graph per wave / workgroup (disjoint rows and slabs)."""
+    geo: object             # functional.Geometry of the range (node rows stay absolute)
+    forms: list             # the LayerForm of every conv layer on it (`step_parts`)
+    stream: object          # hipStream_t its launches go to: None = the current stream
 
 
-def layer_forms(shapes, N, max_nodes, max_edges, forward_only=False, sw=None, plan=None):
+def _convs(model):
+    """[model.conv1] + list(model.conv_layers) from `_modules`: no `nn.Module.__getattr__` (~0.5 us each, twice per step)."""
+    return [model._modules["conv1"], *model._modules["conv_layers"]._modules.values()]
+
+
+def _layer_shapes(model, convs=None):
+    """(in_channels, out_channels, family preference) of every conv layer (`convs`: the caller has listed them already)."""
+    return [(c.in_channels, c.out_channels, getattr(c, "family", "auto")) for c in (_convs(model) if convs is None else convs)]
+
+
+def layer_forms(shapes, N, max_nodes, max_edges, forward_only=False, sw=None, plan=None, part=None):
     """The form of every conv layer of a step -> [LayerForm], or None when a layer has no fused kernel family.  Pure host
     arithmetic on plain values: `shapes` = `_layer_shapes`, the batch's row count and largest graph, `sw` = whoever holds the
     development switches (a step, default the class), `plan` (whose own N and largest graph the caller passes) adds
     `conv_route`'s plan-level checks.  The support check asks with a batch's collate metadata, `_prepare` with its plan: the
-    jobs the one predicts are the jobs the other leaves."""
+    jobs the one predicts are the jobs the other leaves.
+    `part`: the forms of a graph range of a size-grouped batch, the part-th of `step_parts` (`max_nodes`: its largest graph).
+    A range takes no row-streaming form (family "mid" whatever the convs prefer, no dense first layer: those kernels walk all
+    N rows), is no backward pair candidate, carries no head and keeps the tiles' pooled layer as bits whatever POOLBITS says."""
     sw = FusedTrainStep if sw is None else sw
-    # a step keeps the answers by the inputs (it asks twice per step: the support check, then `_prepare` with the plan, whose
-    # own checks -- passed -- add nothing); without the memo the eager step's host time was 0.113 against 0.104 ms
-    memo = sw._forms_memo if (plan is None or HF._per_graph_plan(plan)) else None
-    key = (tuple(shapes), N, max_nodes, max_edges, forward_only, sw.POOLBITS, sw.XAGG, sw.XAGG_MID, sw.PREMASK, sw.BWD_PAIR,
-           HF.TALL_MIN_NODES_D64)
-    if memo is not None and key in memo:
-        return memo[key]
-    routes = [HF.conv_route(plan, F, D, family, max_nodes=max_nodes, max_edges=max_edges, rows=N) for F, D, family in shapes]
+    whole = part is None
+    routes = [HF.conv_route(plan, F, D, family if whole else "mid", max_nodes=max_nodes, max_edges=max_edges, rows=N)
+              for F, D, family in shapes]
     if (None, 0) in routes:
         return None
     n, fams = len(routes), [fam for fam, _ in routes]
     stacked = n == 2 and fams[0] is HF.TILES and routes[0] == routes[1]
-    pair = sw.BWD_PAIR and sw.PREMASK and not forward_only and n >= 2 and fams[0] is HF.TILES and fams[1] is HF.TILES
+    pair = (whole and sw.BWD_PAIR and sw.PREMASK and not forward_only and n >= 2 and fams[0] is HF.TILES
+            and fams[1] is HF.TILES)
     # a layer on the tiles or one graph per workgroup can hand its dx down already multiplied by the activation derivative
     # of the layer below (it holds those rows anyway, for dW): one tensor less per step
     premask = [bool(sw.PREMASK) and l > 0 and fam is not HF.TALL for l, fam in enumerate(fams)]
@@ -106,10 +119,12 @@ def layer_forms(shapes, N, max_nodes, max_edges, forward_only=False, sw=None, pl
     for l, ((F, D, _), (fam, gpt)) in enumerate(zip(shapes, routes)):
         last = l == n - 1
         bits = None
-        if last and sw.POOLBITS and (fam is HF.TILES or (fam is HF.TALL and F <= (64 if D == 64 else 128))):
+        if not whole:
+            bits = "poolbits_r" if last and fam is HF.TILES else None
+        elif last and sw.POOLBITS and (fam is HF.TILES or (fam is HF.TALL and F <= (64 if D == 64 else 128))):
             bits = "poolbits" if fam is HF.TILES else "poolbits_tall"
         dense = False
-        if l == 0 and n >= 2 and sw.XAGG and not forward_only:
+        if whole and l == 0 and n >= 2 and sw.XAGG and not forward_only:
             if fam is HF.TALL:
                 dense = (F <= 64 or D == 128) and fams[1] is HF.TALL
             elif fam is HF.MID:     # (behind the one-graph-per-workgroup kernels: batches under functional.TALL_MIN_NODES_D64)
@@ -120,18 +135,46 @@ def layer_forms(shapes, N, max_nodes, max_edges, forward_only=False, sw=None, pl
         # jobs: the families' `reduce_jobs` -- the tiles 1; the wide-layer route and the dense first layer dW, db; one graph
         # per workgroup one per 64-column half
         jobs = 1 if fam is HF.TILES else (2 if (fam is HF.TALL or kp) else D // 64)
-        forms.append(LayerForm(fam, gpt, stacked, bits, kp, flags, ("lower", "upper")[l] if (pair and l < 2) else None, jobs))
-    if memo is not None:
-        if len(memo) >= 64:         # (a shuffled epoch's batches differ in N: bounded, not kept for ever)
-            memo.clear()
-        memo[key] = forms
+        forms.append(LayerForm(fam, gpt, stacked, bits, bool(whole and last and stacked and bits), kp, flags,
+                               ("lower", "upper")[l] if (pair and l < 2) else None, jobs if part in (None, 0) else 0))
     return forms
 
 
+def step_parts(shapes, N, B, max_nodes, max_edges, n_small=None, C=1, forward_only=False, sw=None, plan=None):
+    """The graph ranges a step runs as its parts -> [(first graph, graphs, [LayerForm])], None when a layer has no fused kernel
+    family.  Two for a size-grouped batch (`n_small`: where `Batch.n_small` says the second group starts) of a model the
+    grouping covers -- two conv layers of width 64, the one-launch head -- with both groups non-empty, a largest graph over
+    32 nodes, every layer of the first group on the tiles and of the second one graph per wave / workgroup; else the batch."""
+    sw = FusedTrainStep if sw is None else sw
+    # a step keeps the answers by the inputs (it asks twice per step: the support check, then `_prepare` with the plan, whose
+    # own checks -- passed -- add nothing); without the memo the eager step's host time was 0.113 against 0.104 ms
+    memo = sw._forms_memo if (plan is None or HF._per_graph_plan(plan)) else None
+    key = (tuple(shapes), N, B, max_nodes, max_edges, n_small, C, forward_only, sw.POOLBITS, sw.XAGG, sw.XAGG_MID, sw.PREMASK,
+           sw.BWD_PAIR, HF.TALL_MIN_NODES_D64)
+    if memo is not None and key in memo:
+        return memo[key]
+    parts = None
+    if (n_small is not None and 0 < n_small < B and len(shapes) == 2 and shapes[0][1] == 64 and max_nodes is not None
+            and max_nodes > 32 and max_edges is not None and _lib.load().hcg_head_supported(64, C)):
+        a = layer_forms(shapes, N, 32, max_edges, forward_only, sw, plan, part=0)
+        b = layer_forms(shapes, N, max_nodes, max_edges, forward_only, sw, plan, part=1)
+        if a and b and all(f.fam is HF.TILES for f in a) and all(f.fam is HF.MID for f in b):
+            parts = [(0, int(n_small), a), (int(n_small), B - int(n_small), b)]
+    if parts is None:
+        forms = layer_forms(shapes, N, max_nodes, max_edges, forward_only, sw, plan)
+        parts = None if forms is None else [(0, B, forms)]
+    if memo is not None:
+        if len(memo) >= 64:         # (a shuffled epoch's batches differ in N: bounded, not kept for ever)
+            memo.clear()
+        memo[key] = parts
+    return parts
+
+
 class _Ctx:
-    """Everything one step needs, resolved once: shapes, weights, buffers, the form of every layer (`layer_forms`)."""
+    """Everything one step needs, resolved once: shapes, weights, buffers, its parts (`step_parts`: the form of every layer).
+    `main`, `side`: the current stream and the later parts' while a size-grouped step is captured; `poolbits`: per part."""
     __slots__ = ("batch", "plan", "x", "y2", "convs", "lins", "N", "F", "B", "D", "C", "n_conv", "dev", "W", "bs",
-                 "forms", "geo", "bufs", "n_small", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
+                 "parts", "main", "side", "bufs", "head_fused", "forward_only", "flat", "gaddr", "step_word", "jobs",
                  "loss_mode", "sse_split", "poolbits", "xagg", "bwd_pair")
 
 
@@ -181,7 +224,7 @@ class FusedTrainStep:
     BWD_PAIR = True
     HEAD_IN_FORWARD = True
     OVERLAP_GROUPS = True          # captured size-grouped steps: the two kernel families as two branches of the hipGraph
-    _forms_memo = None             # (`layer_forms` asked with the class, or a step made without __init__: nothing is kept)
+    _forms_memo = None             # (`step_parts` asked with the class, or a step made without __init__: nothing is kept)
 
     def __init__(self, model, rmse: bool = True, optimizer_step: bool = True, grad_sync=None, combine: str = "mean"):
         if combine not in ("mean", "sse"):
@@ -219,7 +262,7 @@ class FusedTrainStep:
         self.capture_exchange = False
         self._pcache = None
         self._pair_ok = {}                      # answers of the backward pair's query (`_pair_applies`)
-        self._forms_memo = {}                   # ... and of `layer_forms`
+        self._forms_memo = {}                   # ... and of `step_parts`
 
     def _trainable(self):
         """The model's parameters in `model.parameters()` order, from a cache: the module walk of `nn.Module.parameters()`
@@ -257,7 +300,8 @@ class FusedTrainStep:
             return "fused kernels disabled on the model"
         # every gradient slab of the step is reduced by ONE launch of at most HCG_REDUCE_MAX_JOBS jobs (hcg_step_tail)
         head_jobs = 1 if (R != 2 or lib.hcg_head_supported(model.embedding_dim, model._n_classes)) else 0
-        if FusedTrainStep._conv_jobs(model) + head_jobs > _lib.HCG_REDUCE_MAX_JOBS:
+        shapes = _layer_shapes(model)
+        if FusedTrainStep._conv_jobs(model, shapes=shapes) + head_jobs > _lib.HCG_REDUCE_MAX_JOBS:
             return (f"{model.n_convolutions} conv layers of width {model.embedding_dim}: their gradient reductions and the "
                     f"head's exceed the step tail's {_lib.HCG_REDUCE_MAX_JOBS} jobs")
         # (heads the one-launch kernel does not cover -- widths other than 64 / 128 -- run as five launches of the any-shape
@@ -276,7 +320,7 @@ class FusedTrainStep:
             mx = getattr(batch, "max_nodes", None)
             if mx is None or not getattr(batch, "edges_grouped", False):
                 return "batch lacks collate metadata (max_nodes / grouped edges)"
-            jobs = FusedTrainStep._conv_jobs(model, batch, _step)
+            jobs = FusedTrainStep._conv_jobs(model, batch, _step, shapes)
             if jobs is None:
                 return "graph / layer shape outside the fused kernels (small-graph tiles and one-graph-per-workgroup)"
             if jobs + head_jobs > _lib.HCG_REDUCE_MAX_JOBS:
@@ -287,14 +331,18 @@ class FusedTrainStep:
         return None
 
     @staticmethod
-    def _conv_jobs(model, batch=None, step=None) -> Optional[int]:
-        """Reduction jobs the conv layers' backward leaves for the step tail: the sum over the batch's `layer_forms` (asked
+    def _conv_jobs(model, batch=None, step=None, shapes=None) -> Optional[int]:
+        """Reduction jobs the conv layers' backward leaves for the step tail: the sum over the batch's `step_parts` (asked
         with its collate metadata), the same plan `_backward_layers` executes; None = a layer outside the fused kernels.
         Without a batch: the fewest any batch could need (1 per 64-wide layer, 2 per wider one)."""
+        shapes = _layer_shapes(model) if shapes is None else shapes
         if batch is None:
-            return sum(1 if D == 64 else 2 for _, D, _ in _layer_shapes(model))
-        forms = layer_forms(_layer_shapes(model), batch.x.shape[0], batch.max_nodes, getattr(batch, "max_edges", None), sw=step)
-        return None if forms is None else sum(f.jobs for f in forms)
+            return sum(1 if D == 64 else 2 for _, D, _ in shapes)
+        ns = getattr(batch, "n_small", None)
+        # (the arguments `_prepare` will ask with: the two questions of a step are one entry of the step's memo)
+        parts = step_parts(shapes, batch.x.shape[0], batch.num_graphs, batch.max_nodes, getattr(batch, "max_edges", None), ns,
+                           model._n_classes, sw=step)
+        return None if parts is None else sum(f.jobs for _, _, forms in parts for f in forms)
 
     def _side_stream(self, dev):
         st = self._side_streams.get(dev)
@@ -334,11 +382,23 @@ class FusedTrainStep:
             self._bufs = {"cap": cap, key: b}          # views of the current shape (one live shape at a time)
         return b
 
-    def _layer_ws(self, c: _Ctx, l, fam, gpt, F):
-        """Workspace of layer l's kernels of family `fam` (gradient slabs; the wide-layer kernels' also holds the H / dH round
-        trip, and their forward and backward share it) -> (buffer, bytes)."""
-        wsb = fam.workspace_bytes(c.geo, gpt, F, c.D)
-        return self._ws(c.bufs, (fam.name, l) if fam.row_streaming else l, wsb, c.dev), wsb
+    def _layer_ws(self, c: _Ctx, l, fams, F):
+        """Workspace of layer l's kernels, of family `fams[i]` on part i (gradient slabs; the wide-layer kernels' also holds
+        the H / dH round trip, and their forward and backward share it) -> per part (buffer or address, bytes).  The parts'
+        slabs share one buffer, back to back: an earlier part's are its launch's slabs exactly (its query less the 256-byte pad)."""
+        if len(c.parts) == 1:
+            p, fam = c.parts[0], fams[0]
+            wsb = fam.workspace_bytes(p.geo, p.forms[l].gpt, F, c.D)
+            return [(self._ws(c.bufs, (fam.name, l) if fam.row_streaming else l, wsb, c.dev), wsb)]
+        sizes = []
+        for i, (p, fam) in enumerate(zip(c.parts, fams)):
+            is_last = i == len(fams) - 1
+            sizes.append(fam.workspace_bytes(p.geo, p.forms[l].gpt, F, c.D) - (0 if is_last else 256))
+        ws, slabs, off = self._ws(c.bufs, ("r", l), sum(sizes), c.dev), [], 0
+        for nbytes in sizes:                # (the first part is handed the buffer, the later ones an address inside it)
+            slabs.append((ws if off == 0 else ws.data_ptr() + off, nbytes))
+            off += nbytes
+        return slabs
 
     def _ws(self, bufs, key, nbytes, dev):
         ws = bufs["ws"].get(key)
@@ -392,7 +452,7 @@ class FusedTrainStep:
         _lib.require_gpu(x, y, batch.edge_index)
         c.x = x = HF._f32c(x)
         c.plan = plan = model._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        c.convs = convs = [model.conv1] + list(model.conv_layers)
+        c.convs = convs = _convs(model)
         # readout linears: readout[i] = Sequential(Linear, LeakyReLU) for the hidden layers, the last a bare Linear
         c.lins = [m[0] if isinstance(m, torch.nn.Sequential) else m for m in model.readout]
         c.N, c.F, c.B, c.D, c.C = x.shape[0], x.shape[1], plan.B, model.embedding_dim, model._n_classes
@@ -407,19 +467,29 @@ class FusedTrainStep:
             c.y2 = HF._f32c(y).reshape(c.B, -1)
             if c.y2.shape[1] != c.C:
                 raise ValueError(f"targets have {c.y2.shape[1]} columns, the model predicts {c.C}")
-        c.forms = layer_forms(_layer_shapes(model), plan.N, plan.max_nodes, plan.max_edges, forward_only, self, plan)
-        if c.forms is None:
+        parts = step_parts(_layer_shapes(model, convs), plan.N, c.B, plan.max_nodes, plan.max_edges, getattr(batch, "n_small", None),
+                           c.C, forward_only, self, plan)
+        if parts is None:
             raise _lib.HcgError("FusedTrainStep: graph / layer shape outside the fused kernels")
-        c.geo = HF.geometry(plan)
+        # while a size-grouped step is being CAPTURED the later part's launches go to a second stream, forked before each conv
+        # phase and joined behind it = two branches of the hipGraph: each family's last workgroups fill the CUs the other has
+        # already left (neither fills the chip: ~1.4 tiles per wave / ~0.6 graphs per wave slot at 4096 graphs).  Ragged bench:
+        # replay 0.1975 -> 0.188 ms/step; the four event calls cost the host-bound eager step 0.196 -> 0.215: it keeps one stream
+        c.main = c.side = side = None
+        if len(parts) > 1:
+            side = _lib.stream_ptr()            # (asked once for the later parts' launches)
+            if self.OVERLAP_GROUPS and torch.cuda.is_current_stream_capturing():
+                c.main, c.side = torch.cuda.current_stream(c.dev), self._side_stream(c.dev)
+                side = ctypes.c_void_p(c.side.cuda_stream)
+        c.parts = [Part(HF.geometry(plan, g0, nB), forms, side if g0 else None) for g0, nB, forms in parts]
         c.bufs = self._buffers((c.N, c.B, c.F, plan.E), c.N, c.B, c.F, c.D, c.C, c.n_conv, c.dev, len(c.lins))
         c.W = [HF._f32c(cv.lin.weight) for cv in convs]
         c.bs = [HF._f32c(cv.bias) for cv in convs]
         c.head_fused = bool(lib.hcg_head_supported(c.D, c.C) if len(c.lins) == 2
                             else _head_deep_supported(c.D, c.C, len(c.lins)))
-        c.n_small = self._size_groups(batch, plan, convs, c.D, c.C, c.n_conv)
         c.jobs = HF.JobList()
         c.flat = c.gaddr = c.step_word = None
-        c.poolbits = None
+        c.poolbits = [None] * len(c.parts)
         c.xagg = None
         c.bwd_pair = False
         # how the loss scale reaches the gradients (see the class docstring).  "sse" with a collective between backward and
@@ -459,30 +529,17 @@ class FusedTrainStep:
         """Decided here, before anything is launched: conv layers 1 and 0 a pair candidate of the plan (both on the
         small-graph tiles, layer 1 handing its dx down premasked), and the library agreeing (the query touches no GPU; its
         answer is kept per shape and buffer set)."""
-        if not (c.n_small is None and c.forms[0].pair):
+        geo, forms, _ = c.parts[0]
+        if not forms[0].pair:
             return False
-        acts0, dx, gpt, gpt_up = c.bufs["acts"][0], c.bufs["dacts"][0], c.forms[0].gpt, c.forms[1].gpt
+        acts0, dx, gpt, gpt_up = c.bufs["acts"][0], c.bufs["dacts"][0], forms[0].gpt, forms[1].gpt
         key = (c.F, c.D, gpt, gpt_up, c.x.data_ptr() % 16, acts0.data_ptr() % 16, dx.data_ptr() % 16)
         ok = self._pair_ok.get(key)
         if ok is None:
             # (the upper layer's form does not enter the answer: asked as the not-pooled one)
-            ok = self._pair_ok[key] = HF.TILES.backward_pair(c.geo, gpt, c.x, c.W[0], acts0, c.W[1], 2, gpt_up=gpt_up,
+            ok = self._pair_ok[key] = HF.TILES.backward_pair(geo, gpt, c.x, c.W[0], acts0, c.W[1], 2, gpt_up=gpt_up,
                                                              dout=dx, dx=dx, query=True)
         return ok
-
-    def _size_groups(self, batch, plan, convs, D, C, n_conv):
-        """-> n_small when the batch is size-grouped (`collate(..., group_by_size=True)`: the first n_small graphs have <= 32
-        nodes, the others 33 .. 64) and both groups are non-empty: the small graphs then run in the small-graph tiles, the
-        larger ones one graph per wave, instead of everything on the slower family."""
-        ns = getattr(batch, "n_small", None)
-        if (ns is None or not (0 < ns < plan.B) or n_conv != 2 or D != 64 or not _lib.load().hcg_head_supported(D, C)
-                or plan.max_nodes is None or plan.max_nodes <= 32 or plan.max_edges is None):
-            return None
-        for c in convs:       # (the larger graphs: one graph per wave whatever the conv's family preference)
-            if (HF.conv_route(plan, c.in_channels, c.out_channels, max_nodes=32)[0] is not HF.TILES
-                    or HF.conv_route(plan, c.in_channels, c.out_channels, "mid")[0] is not HF.MID):
-                return None
-        return int(ns)
 
     def _g(self, c: _Ctx, prm) -> int:
         return c.gaddr[id(prm)]
@@ -495,28 +552,27 @@ class FusedTrainStep:
     def _head_in_forward(self, c: _Ctx) -> bool:
         """The C3 form: both conv layers on small-graph tiles, pooled layer on chip, one-launch head -> everything up to
         the loss is ONE launch."""
-        return bool(self.HEAD_IN_FORWARD and c.n_small is None and c.head_fused
+        return bool(self.HEAD_IN_FORWARD and c.head_fused
                     and c.loss_mode != _lib.HCG_LOSS_CE      # (the head in the forward launch is regression-only)
-                    and len(c.lins) == 2 and c.forms[-1].stacked and c.forms[-1].bits)
+                    and len(c.lins) == 2 and c.parts[0].forms[-1].head)
 
-    def _pooled_bits(self, c: _Ctx):
+    def _pooled_bits(self, c: _Ctx, i=0):
         """The pooled layer's activations stay on chip: the bits its backward needs of them (sign, is-the-column-max) are all
         that is stored -- two bits per element on the small-graph tiles, one byte per (row, 4 columns) on the wide-layer
-        route (csrc/tall.hip: k_gseg_bwd).  -> their workspace, None for a pooled layer in the plain form."""
-        top = c.forms[-1]
+        route (csrc/tall.hip: k_gseg_bwd).  -> their workspace on part i, None for a pooled layer in the plain form."""
+        geo, top = c.parts[i].geo, c.parts[i].forms[-1]
         if top.bits:
-            nbytes = (_lib.load().hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, c.B, top.gpt) if top.bits == "poolbits"
-                      else c.N * (c.D // 4))
-            c.poolbits = self._ws(c.bufs, top.bits, nbytes, c.dev)
-        return c.poolbits
+            nbytes = (c.N * (c.D // 4) if top.bits == "poolbits_tall"
+                      else _lib.load().hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, geo.B, top.gpt))
+            c.poolbits[i] = self._ws(c.bufs, top.bits, nbytes, c.dev)
+        return c.poolbits[i]
 
     def _forward_with_head(self, c: _Ctx):
         """conv stack + pooling + readout head (forward, squared error, unscaled readout backward): one launch."""
-        lib, bufs, gpt = _lib.load(), c.bufs, c.forms[0].gpt
-        self._pooled_bits(c)
+        lib, bufs, geo, gpt = _lib.load(), c.bufs, c.parts[0].geo, c.parts[0].forms[0].gpt
         l0, l1 = c.lins
         self._tiles_stack(
-            c, c.geo, gpt, poolbits=c.poolbits, y=c.y2, head_W0=HF._f32c(l0.weight), head_b0=HF._f32c(l0.bias),
+            c, geo, gpt, poolbits=self._pooled_bits(c), y=c.y2, head_W0=HF._f32c(l0.weight), head_b0=HF._f32c(l0.bias),
             head_W1=HF._f32c(l1.weight), head_b1=HF._f32c(l1.bias), C=c.C, z=bufs["z"], head_out=bufs["out"], demb=bufs["demb"],
             head_workspace=bufs["ws_head"], head_workspace_bytes=bufs["ws_head_bytes"], step_counter=c.step_word,
             head_flags=_lib.HCG_HEAD_FORWARD_ONLY if c.forward_only else 0)
@@ -527,39 +583,34 @@ class FusedTrainStep:
         c.jobs.n += 1
 
     def _forward_layers(self, c: _Ctx):
-        """The conv stack (+ pooling) of every other shape: one launch per layer (stacked pair: one)."""
-        bufs, geo, forms = c.bufs, c.geo, c.forms
-        acts, top = bufs["acts"], c.n_conv - 1
-        bits = self._pooled_bits(c)
-        if forms[top].stacked:
-            self._tiles_stack(c, geo, forms[0].gpt, poolbits=bits, out2=None if bits is not None else acts[1])
-            return
-        h = c.x
-        for l, f in enumerate(forms):
-            kw = dict(out=acts[l])
-            if l == top:
-                kw = dict(out=None if bits is not None else acts[l], emb=bufs["emb"], poolbits=bits)
-            if f.fam.row_streaming:
-                kw["ws"], kw["wsb"] = self._layer_ws(c, l, f.fam, f.gpt, h.shape[1])
-            if f.kp:
-                # training form of the FIRST layer: Ahat x [N, kp] and the sign pieces of its output leave too, for the dense
-                # backward -- no transpose sum, no dH round trip
-                c.xagg = (self._ws(bufs, "xagg", c.N * f.kp * 4, c.dev), self._ws(bufs, "signs", c.N * (c.D // 8), c.dev))
-                kw["xagg"], kw["signs"] = c.xagg
-            f.fam.forward(geo, f.gpt, h, c.W[l], c.bs[l], 1, **kw)
-            h = acts[l]
-
-    def _forward_routed(self, c: _Ctx, geo_a, geo_b, gpt, fork, join, stream_b):
-        """Size-grouped batch: graphs [0, n_small) through the tiles (both layers + pooling in one launch, pooled layer on
-        chip), graphs [n_small, B) one graph per wave (`geo_a`, `geo_b`)."""
-        bufs = c.bufs
-        acts = bufs["acts"]
-        c.poolbits = self._ws(bufs, "poolbits_r", _lib.load().hcg_fused_aux_bytes(_lib.HCG_FUSED_POOLBITS, geo_a.B, gpt), c.dev)
-        fork()
-        self._tiles_stack(c, geo_a, gpt, poolbits=c.poolbits)
-        HF.MID.forward(geo_b, 0, c.x, c.W[0], c.bs[0], 1, out=acts[0], stream=stream_b)
-        HF.MID.forward(geo_b, 0, acts[0], c.W[1], c.bs[1], 1, out=acts[1], emb=bufs["emb"], stream=stream_b)
-        join()
+        """The conv stack (+ pooling) of every other shape: per part one launch per layer (stacked pair: one), layer by layer."""
+        bufs, acts, top = c.bufs, c.bufs["acts"], c.n_conv - 1
+        if c.side is not None:
+            c.side.wait_stream(c.main)      # fork: the side stream starts behind everything issued so far
+        for l in range(c.n_conv):
+            h = c.x if l == 0 else acts[l - 1]
+            for i, (geo, forms, stream) in enumerate(c.parts):
+                f = forms[l]
+                if f.stacked:
+                    if l == 0:
+                        bits = self._pooled_bits(c, i)
+                        self._tiles_stack(c, geo, f.gpt, poolbits=bits, out2=None if bits is not None else acts[1])
+                    continue
+                kw = dict(out=acts[l])
+                if l == top:
+                    bits = self._pooled_bits(c, i) if f.bits else None
+                    kw = dict(out=None if bits is not None else acts[l], emb=bufs["emb"], poolbits=bits)
+                if f.fam.row_streaming:
+                    (kw["ws"], kw["wsb"]), = self._layer_ws(c, l, [f.fam], h.shape[1])
+                if f.kp:
+                    # training form of the FIRST layer: Ahat x [N, kp] and its output's sign pieces leave too, for the dense backward
+                    c.xagg = (self._ws(bufs, "xagg", c.N * f.kp * 4, c.dev), self._ws(bufs, "signs", c.N * (c.D // 8), c.dev))
+                    kw["xagg"], kw["signs"] = c.xagg
+                if stream is not None:
+                    kw["stream"] = stream
+                f.fam.forward(geo, f.gpt, h, c.W[l], c.bs[l], 1, **kw)
+        if c.side is not None:
+            c.main.wait_stream(c.side)      # join: what follows waits for the side stream's launches too
 
     def _head(self, c: _Ctx):
         """The readout head as a launch of its own (one-launch kernel for D = 64 / 128, C <= 8; five launches of the
@@ -628,82 +679,59 @@ class FusedTrainStep:
         c.jobs.n += 1
 
     def _backward_layers(self, c: _Ctx):
-        """Conv stack backward, last layer first, each layer in the form the plan gave it (`LayerForm.flags`: who applies
-        which activation derivative)."""
-        bufs, geo, jobs, forms, D = c.bufs, c.geo, c.jobs, c.forms, c.D
+        """Conv stack backward, last layer first, each layer in the form the plan gave it on each part (`LayerForm.flags`: who
+        applies which activation derivative).  A layer's slabs are ONE reduction job: later parts' descriptors join the first's."""
+        bufs, jobs, parts, D = c.bufs, c.jobs, c.parts, c.D
         acts, top = bufs["acts"], c.n_conv - 1
+        append = _lib.load().hcg_reduce_job_append if len(parts) > 1 else None
 
-        def reduce(l, fam, gpt, ws, wsb, **kw):
-            F = c.W[l].shape[1]
-            jobs.n += fam.reduce_jobs(geo, gpt, F, D, ws, wsb, self._g(c, c.W[l]), self._g(c, c.bs[l]), jobs.slot(), **kw)
+        def reduce(l, fams, slabs):
+            F, dW, db = c.W[l].shape[1], self._g(c, c.W[l]), self._g(c, c.bs[l])
+            for p, fam, (ws, wsb) in zip(parts, fams, slabs):
+                kw = dict(first=True) if p.forms[l].kp else {}
+                if p is parts[0]:
+                    jobs.n += fam.reduce_jobs(p.geo, p.forms[l].gpt, F, D, ws, wsb, dW, db, jobs.slot(), **kw)
+                else:           # (one job per part and layer at the grouping's width: `step_parts`)
+                    fam.reduce_jobs(p.geo, p.forms[l].gpt, F, D, ws, wsb, dW, db, jobs.spare, **kw)
+                    _lib.check(append(jobs.slot() - HF._JOB_BYTES, jobs.spare), "hcg_reduce_job_append")
 
+        if c.side is not None:
+            c.side.wait_stream(c.main)
         for l in reversed(range(c.n_conv)):
-            f, last = forms[l], l == top
-            inp = c.x if l == 0 else acts[l - 1]
-            # the gradient comes in from the head (demb) or the layer above (its dx), goes out as dx; of the layer's own output
-            # the launch reads what its form leaves it to need: nothing where the pooled layer's bits or the dense first
-            # layer's sign pieces stand in for it, or where the layer above premasked dout
-            bits = c.poolbits if last else None
-            kw = dict(dout=None if last else bufs["dacts"][l], demb=bufs["demb"] if last else None,
-                      emb=bufs["emb"] if (last and bits is None) else None,
-                      out=acts[l] if (bits is None and not f.kp and (last or f.flags & 1)) else None,
-                      dx=bufs["dacts"][l - 1] if l > 0 else None)
-            if bits is not None:
-                kw["poolbits"] = bits
-            if f.pair == "upper" and c.bwd_pair:
-                # layers 1 and 0 in ONE launch: layer 1's phase, a workgroup barrier, layer 0's phase over the same tiles
-                ws, wsb = self._layer_ws(c, 1, f.fam, f.gpt, D)
-                ws0, wsb0 = self._layer_ws(c, 0, f.fam, f.gpt, c.F)
-                f.fam.backward_pair(geo, f.gpt, c.x, c.W[0], inp, c.W[1], f.flags, ws_up=ws, wsb_up=wsb, ws=ws0, wsb=wsb0, **kw)
-                reduce(1, f.fam, f.gpt, ws, wsb)
-                reduce(0, f.fam, f.gpt, ws0, wsb0)
-                return
-            fam, first = f.fam, {}
-            if f.kp:
-                # the first layer's backward as ONE dense launch over the forward's Ahat x: the wide-layer route's launcher
-                # whatever the layer's family.  Behind the per-graph kernels the batch's node count is read on the device
-                # (graph_ptr[B]): a captured epoch's slot has a CAPACITY of rows
-                fam, first = HF.TALL, dict(first=True)
-                kw.update(xagg=c.xagg[0], signs=c.xagg[1])
-                if not f.fam.row_streaming:
-                    kw["nodes_dev"] = geo.graph_ptr + 4 * geo.B
-            ws, wsb = self._layer_ws(c, l, fam, f.gpt, inp.shape[1])
-            fam.backward(geo, f.gpt, inp, c.W[l], f.flags, ws=ws, wsb=wsb, **kw)
-            reduce(l, fam, f.gpt, ws, wsb, **first)
-
-    def _backward_routed(self, c: _Ctx, geo_a, geo_b, gpt, fork, join, stream_b):
-        """Size-grouped batch: each layer's backward = tiles on the small graphs + waves on the others; both groups' slabs of
-        a layer sit back to back and are ONE reduction job."""
-        lib, bufs, jobs, D = _lib.load(), c.bufs, c.jobs, c.D
-        acts, demb = bufs["acts"], bufs["demb"]
-        tmp = ctypes.create_string_buffer(_lib.job_bytes())
-        taddr = ctypes.addressof(tmp)
-        premask = bool(self.PREMASK)
-        dx = bufs["dacts"][0]
-        fork()
-        for l in (1, 0):
-            inp = c.x if l == 0 else acts[0]
-            Fl = inp.shape[1]
-            off_b = HF.TILES.workspace_bytes(geo_a, gpt, Fl, D) - 256     # = the tile launch's slabs, exactly (the query pads by 256)
-            ws_b = HF.MID.workspace_bytes(geo_b, 0, Fl, D)
-            ws = self._ws(bufs, ("r", l), off_b + ws_b, c.dev)
-            wsb_ptr = ws.data_ptr() + off_b
-            W, dW, db = c.W[l], self._g(c, c.W[l]), self._g(c, c.bs[l])
-            if l == 1:
-                flags = 1 | (2 if premask else 0)
-                HF.TILES.backward(geo_a, gpt, inp, W, flags, demb=demb, poolbits=c.poolbits, dx=dx, ws=ws, wsb=off_b)
-                HF.MID.backward(geo_b, 0, inp, W, flags, demb=demb, emb=bufs["emb"], out=acts[1], dx=dx, ws=wsb_ptr, wsb=ws_b,
-                                stream=stream_b)
-            else:
-                act = 0 if premask else 1
-                a_out = acts[0] if act else None
-                HF.TILES.backward(geo_a, gpt, inp, W, act, dout=dx, out=a_out, ws=ws, wsb=off_b)
-                HF.MID.backward(geo_b, 0, inp, W, act, dout=dx, out=a_out, ws=wsb_ptr, wsb=ws_b, stream=stream_b)
-            HF.TILES.reduce_jobs(geo_a, gpt, Fl, D, ws, off_b, dW, db, jobs.slot())
-            HF.MID.reduce_jobs(geo_b, 0, Fl, D, wsb_ptr, ws_b, dW, db, taddr)
-            _lib.check(lib.hcg_reduce_job_append(jobs.slot(), taddr), "hcg_reduce_job_append")
-            jobs.n += 1
-        join()
+            last, inp, slabs = l == top, (c.x if l == 0 else acts[l - 1]), None
+            for i, (geo, forms, stream) in enumerate(parts):
+                # the gradient comes in from the head (demb) or the layer above (its dx), goes out as dx; of its own output the
+                # layer reads nothing where the pooled bits / the dense form's sign pieces stand in, or dout came premasked
+                f, bits = forms[l], (c.poolbits[i] if last else None)
+                kw = dict(dout=None if last else bufs["dacts"][l], demb=bufs["demb"] if last else None,
+                          emb=bufs["emb"] if (last and bits is None) else None,
+                          out=acts[l] if (bits is None and not f.kp and (last or f.flags & 1)) else None,
+                          dx=bufs["dacts"][l - 1] if l > 0 else None)
+                if bits is not None:
+                    kw["poolbits"] = bits
+                if f.pair == "upper" and c.bwd_pair:
+                    # layers 1 and 0 in ONE launch: layer 1's phase, a workgroup barrier, layer 0's phase over the same tiles
+                    fams, up, low = [f.fam], self._layer_ws(c, 1, [f.fam], D), self._layer_ws(c, 0, [f.fam], c.F)
+                    f.fam.backward_pair(geo, f.gpt, c.x, c.W[0], inp, c.W[1], f.flags, ws_up=up[0][0], wsb_up=up[0][1],
+                                        ws=low[0][0], wsb=low[0][1], **kw)
+                    reduce(1, fams, up)
+                    reduce(0, fams, low)
+                    return          # (a pair is the whole batch: one part, nothing to join)
+                if slabs is None:
+                    # (a dense first layer's backward is ONE launch over the forward's Ahat x: the wide-layer route's launcher)
+                    fams = [HF.TALL if p.forms[l].kp else p.forms[l].fam for p in parts]
+                    slabs = self._layer_ws(c, l, fams, inp.shape[1])
+                if f.kp:
+                    kw.update(xagg=c.xagg[0], signs=c.xagg[1])
+                    if not f.fam.row_streaming:
+                        # the node count is read on the device (graph_ptr[B]): a captured epoch's slot has a CAPACITY of rows
+                        kw["nodes_dev"] = geo.graph_ptr + 4 * geo.B
+                if stream is not None:
+                    kw["stream"] = stream
+                fams[i].backward(geo, f.gpt, inp, c.W[l], f.flags, ws=slabs[i][0], wsb=slabs[i][1], **kw)
+            reduce(l, fams, slabs)
+        if c.side is not None:
+            c.main.wait_stream(c.side)
 
     def _tail(self, c: _Ctx):
         """The step's last launch: slab reductions -> ONE flat gradient, the loss and its scale, (exchange,) update, the next
@@ -751,47 +779,14 @@ class FusedTrainStep:
             if why is not None:
                 raise _lib.HcgError(f"FusedTrainStep does not cover this model/batch: {why}")
         c = self._prepare(batch, _forward_only)
-        if c.n_small is not None:
-            return self._routed_step(c)
         if self._head_in_forward(c):
             self._forward_with_head(c)
         else:
             self._forward_layers(c)
-            self._head(c)
+            self._head(c)                               # over all graphs
         if _forward_only:
             return self._finish_forward_only(c)
         self._backward_layers(c)
-        self._tail(c)
-        self.last_out = c.bufs["out"]
-        return c.bufs["loss"][0]
-
-    def _routed_step(self, c: _Ctx):
-        """The step for a size-grouped batch.  The two groups' launches touch disjoint rows, graphs and slabs.  While the step
-        is being CAPTURED the larger graphs' launches go to a second stream, forked before each conv phase and joined behind
-        it = two branches of the hipGraph: each family's last workgroups fill the CUs the other has already left (neither
-        fills the chip: ~1.4 tiles per wave / ~0.6 graphs per wave slot at 4096 graphs).  Measured on the ragged bench: replay
-        0.1975 -> 0.188 ms/step; the eager step is host-bound and the four extra event calls cost it 0.196 -> 0.215, so eager
-        steps stay on one stream."""
-        dev = c.dev
-        main_s = torch.cuda.current_stream(dev)
-        side_s = self._side_stream(dev) if (self.OVERLAP_GROUPS and torch.cuda.is_current_stream_capturing()) else None
-        stream_b = ctypes.c_void_p(side_s.cuda_stream) if side_s is not None else _lib.stream_ptr()
-
-        def fork():
-            if side_s is not None:
-                side_s.wait_stream(main_s)
-
-        def join():
-            if side_s is not None:
-                main_s.wait_stream(side_s)
-        # graphs [0, n_small) on the tiles (all of <= 32 nodes), the others one graph per wave; node rows stay absolute
-        groups = (HF.geometry(c.plan, 0, c.n_small), HF.geometry(c.plan, c.n_small),
-                  HF.conv_route(c.plan, c.F, c.D, max_nodes=32)[1], fork, join, stream_b)
-        self._forward_routed(c, *groups)
-        self._head(c)                                   # over all graphs
-        if c.forward_only:
-            return self._finish_forward_only(c)
-        self._backward_routed(c, *groups)
         self._tail(c)
         self.last_out = c.bufs["out"]
         return c.bufs["loss"][0]

@@ -11,8 +11,9 @@ from tests.test_gpu_parity import H  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
-# (graph sizes, F, D) -> families of the two layers, Ahat x columns of the dense first layer
+# (graph sizes, F, D) -> families of the two layers on every part of the step, Ahat x columns of the dense first layer
 ROUTES = {"tiles": ((30, 30, 30), 25, 64, ["tiles", "tiles"], 0),
+          "size-grouped": ((30, 30, 40, 40), 25, 64, ["tiles", "tiles", "mid", "mid"], 0),
           "mid, dense first layer": ((70, 40), 25, 64, ["mid", "mid"], 32),
           "wide-layer": ((70, 70), 28, 128, ["tall", "tall"], 32)}
 
@@ -23,12 +24,12 @@ def test_the_tail_gets_the_jobs_the_plan_predicted(H, monkeypatch, route):
     graphs = []
     for i, n in enumerate(sizes):
         graphs += synth.make_batch(1, n, extra_bonds=3, max_degree=4, feat=F, seed=synth.BASE_SEED + i).as_graph_list()
-    batch = H.collate(graphs).to("cuda")
+    batch = H.collate(graphs, group_by_size=route == "size-grouped").to("cuda")
     torch.manual_seed(0)
     model = H.make_network("GCN", H.default_options(embedding_dim=D), F).cuda()
     step = FusedTrainStep(model)
     assert step.reason(batch) is None
-    forms = step._prepare(batch, False).forms
+    forms = [f for p in step._prepare(batch, False).parts for f in p.forms]
     assert [f.fam.name for f in forms] == fams and forms[0].kp == kp          # the shapes reach the route class
 
     # the step's last launch, with or without the optimiser's update riding in it (`optimizer.step_with_reduction` ends

@@ -648,6 +648,37 @@ def test_fused_train_step_embedding_dim_128(H, oracle, combine):
         assert abs(la - lb) <= 1e-5 * abs(lb)
 
 
+def test_size_grouped_batch_with_a_second_group_over_64_nodes(H, oracle):
+    """Four graphs of 20, 30 | 40, 70 nodes collated with group_by_size: the second group's largest graph has more than 64
+    nodes, so it runs one graph per WORKGROUP (csrc/mid.hip) beside the first group's tiles.  Loss / outputs / every gradient
+    vs the oracle."""
+    from types import SimpleNamespace
+    from hcatgnet_amd import synth
+    from hcatgnet_amd.train import FusedTrainStep
+    graphs = []
+    for i, n in enumerate((20, 30, 40, 70)):
+        graphs += synth.make_batch(1, n, extra_bonds=3, max_degree=4, feat=25, seed=synth.BASE_SEED + 40 + i).as_graph_list()
+    batch = H.collate(graphs, group_by_size=True).to("cuda")
+    assert batch.n_small == 2 and batch.num_graphs == 4 and batch.max_nodes == 70
+    m = H.make_network("GCN", H.default_options(), 25).cuda()
+    with torch.no_grad():
+        for prm in m.parameters():
+            if prm.dim() == 1:
+                prm.add_(0.05)
+    step = FusedTrainStep(m, optimizer_step=False)
+    parts = step._prepare(batch, False).parts
+    assert [(p.geo.g0, p.geo.B, p.forms[0].fam.name) for p in parts] == [(0, 2, "tiles"), (2, 2, "mid")]
+    loss = float(step(batch))
+    assert batch._hcg_plan.check_status() == 0
+    sb = SimpleNamespace(x=batch.x.cpu(), edge_index=batch.edge_index.cpu(), batch=batch.batch.cpu(), y=batch.y.cpu(),
+                         num_graphs=batch.num_graphs)
+    l_ref, out_ref, _, g_ref = _oracle_grads(oracle, m, sb)
+    assert abs(loss - float(l_ref)) <= TOL * abs(float(l_ref))
+    assert rel_inf(step.last_out, out_ref, floor=1.0) <= TOL
+    for name, prm in m.named_parameters():
+        assert rel_inf(prm.grad, g_ref[name]) <= TOL, name
+
+
 @pytest.mark.parametrize("feat,seed", [(64, 3), (25, 4)])
 def test_size_grouped_batch_runs_two_kernel_families(H, oracle, feat, seed):
     """A ragged batch (n_g ~ U{24..36}) collated with group_by_size: graphs <= 32 nodes through the small-graph tiles, the
@@ -666,8 +697,8 @@ def test_size_grouped_batch_runs_two_kernel_families(H, oracle, feat, seed):
                 prm.add_(0.05)
     step = FusedTrainStep(m, optimizer_step=False)
     batch = sb.as_batch("cuda")
-    assert step._size_groups(batch, m._plan_for(batch, batch.x, batch.edge_index, batch.batch, None),
-                             [m.conv1] + list(m.conv_layers), 64, 1, 2) == sb.n_small
+    parts = step._prepare(batch, False).parts
+    assert [(p.geo.g0, p.geo.B) for p in parts] == [(0, sb.n_small), (sb.n_small, sb.num_graphs - sb.n_small)]
     loss = float(step(batch))
     grads = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
     l_ref, out_ref, _, g_ref = _oracle_grads(oracle, m, sb)

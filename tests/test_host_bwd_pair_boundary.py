@@ -14,7 +14,7 @@ import torch
 
 from hcatgnet_amd import _lib
 from hcatgnet_amd import functional as HF
-from hcatgnet_amd.train import FusedTrainStep, _Ctx, layer_forms
+from hcatgnet_amd.train import FusedTrainStep, Part, _Ctx, step_parts
 from tests.test_host_bwd_pair import _pair_block
 
 OK, INVALID, UNSUPPORTED = 0, -1, -3
@@ -68,18 +68,23 @@ def _ctx(F=64, D=64, B=3, nodes=30, routes=None, n_small=None, n_conv=2, step=No
     `conv_route` is made to answer for the layers (default: what it does answer, the tiles at one graph per tile)."""
     c = _Ctx()
     N = B * nodes
-    c.F, c.D, c.n_conv, c.n_small = F, D, n_conv, n_small
+    c.F, c.D, c.n_conv = F, D, n_conv
     c.x = torch.zeros(N, F)
     c.W = [torch.zeros(D, F), torch.zeros(D, D)]
     c.bufs = {"acts": [torch.zeros(N, D)], "dacts": [torch.zeros(N, D)]}
     keep = [torch.zeros(2, 8, dtype=torch.int64), torch.zeros(B + 1, dtype=torch.int32), torch.zeros(B + 1, dtype=torch.int32),
             torch.zeros(4, dtype=torch.int32)]
     c.batch = keep                                        # (kept alive beside the addresses below)
-    c.geo = HF.Geometry(keep[0].data_ptr(), 8, keep[1].data_ptr(), keep[2].data_ptr(), N, B, nodes, 64, keep[3].data_ptr(), 0)
-    answers = iter(routes if routes is not None else [(HF.TILES, 1), (HF.TILES, 1)])
-    with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(HF, "conv_route", lambda *a, **kw: next(answers))
-        c.forms = layer_forms([(F, D, "auto"), (D, D, "auto")][:n_conv], N, nodes, 64, sw=step)
+    geo = HF.Geometry(keep[0].data_ptr(), 8, keep[1].data_ptr(), keep[2].data_ptr(), N, B, nodes, 64, keep[3].data_ptr(), 0)
+    if n_small is not None:           # a size-grouped batch: its larger graphs have 40 nodes (the real routes answer)
+        parts = step_parts([(F, D, "auto"), (D, D, "auto")][:n_conv], N, B, 40, 90, n_small, sw=step)
+        assert len(parts) == 2
+    else:
+        answers = iter(routes if routes is not None else [(HF.TILES, 1), (HF.TILES, 1)])
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setattr(HF, "conv_route", lambda *a, **kw: next(answers))
+            parts = step_parts([(F, D, "auto"), (D, D, "auto")][:n_conv], N, B, nodes, 64, sw=step)
+    c.parts = [Part(geo._replace(g0=g0, B=nB), forms, None) for g0, nB, forms in parts]
     return c
 
 

@@ -187,10 +187,11 @@ def test_kernel_family_selection_is_host_only(monkeypatch):
     #   step    FusedTrainStep._prepare picks ("error": it raises)
     #   support FusedTrainStep.unsupported_reason says -- from the batch's collate metadata alone: it does not see the plan's
     #           mode or edge weights ("general", "weighted" rows) and never asks about the wide-layer route
-    #   groups  FusedTrainStep._size_groups returns with n_small = B // 2: tiles for the small group, one graph per wave for the
-    #           rest whatever the route of the whole batch or `family` ("REAL", "mid-REAL" rows)
+    #   groups  where `step_parts` starts the second part with n_small = B // 2 (None: one part): tiles for the small group,
+    #           one graph per wave / workgroup for the rest whatever the route of the whole batch or `family` ("REAL",
+    #           "mid-REAL" rows)
     #   epoch   EpochWindow decides (refuses the wide-layer route; it does not consult `family`: "mid-C5", "mid-REAL" rows)
-    from hcatgnet_amd.train import FusedTrainStep, layer_forms
+    from hcatgnet_amd.train import FusedTrainStep, layer_forms, step_parts
     T = HF.TALL_MIN_NODES_D64
     table = [
         (('C1', 64, 64, 30, 64, 30, 1, 'auto', 'blocked', False), ('tiles/tiles', 'tiles/tiles', 'ok', None, 'ok')),
@@ -256,7 +257,11 @@ def test_kernel_family_selection_is_host_only(monkeypatch):
                         y=torch.zeros(B), max_nodes=mxn, max_edges=mxe, edges_grouped=True, n_small=B // 2 if B > 1 else None)
         why = FusedTrainStep.unsupported_reason(m, batch)
         assert (why is None and support == "ok") or (why is not None and support in why), label
-        assert FusedTrainStep(m, optimizer_step=False)._size_groups(batch, plan, convs, D, 1, len(convs)) == groups, label
+        parts = step_parts(shapes, plan.N, plan.B, plan.max_nodes, plan.max_edges, batch.n_small, 1, plan=plan)         # as _prepare
+        assert (None if parts is None or len(parts) == 1 else parts[1][0]) == groups, label
+        if groups is not None:
+            assert [(g0, nB, [f.fam.name for f in forms]) for g0, nB, forms in parts] == [
+                (0, groups, ["tiles", "tiles"]), (groups, B - groups, ["mid", "mid"])], label
         auto = layer_forms([(Fl, Dl, "auto") for Fl, Dl, _ in shapes], plan.N, plan.max_nodes, plan.max_edges, plan=plan)
         refuse = any(f.fam is HF.TALL for f in auto or ())                                               # as EpochWindow
         assert ("refuse" if refuse else "ok") == epoch, label
