@@ -76,8 +76,7 @@ class Rotation:
         self.graphs = all_ranks_agree(err is None, self._device())
         if not self.graphs:
             self.errors["graph"] = err or "capture failed on another rank"
-            for tr in self.trainers:
-                tr._graph = None
+            self.drop_graphs()
         return self.graphs
 
     def build_windows(self, k_steps: int) -> bool:
@@ -109,7 +108,7 @@ class Rotation:
     def drop_graphs(self):
         self.graphs, self.window, self.tail_window, self.tail_n = False, None, None, 0
         for tr in self.trainers:
-            tr._graph = None
+            tr.drop_graph()
 
     def _device(self):
         return self.plans[0].graph_ptr.device
@@ -157,9 +156,9 @@ class Rotation:
         """Synchronising: every trainer's last loss is finite (a timed-out exchange leaves NaN)."""
         ok = True
         for tr in self.trainers:
-            cap = tr._bufs.get("cap")
-            if cap is not None:
-                ok = ok and bool(torch.isfinite(cap["loss"]).all().item())
+            loss = tr.captured_loss()
+            if loss is not None:
+                ok = ok and bool(torch.isfinite(loss).all().item())
         return ok
 
 
@@ -173,7 +172,7 @@ def set_exchange_form(trainers: List[FusedTrainStep], dp, form: str, xchg=None):
         tr.exchange = None
         tr.exchange_fallback_sync = None
         tr.capture_exchange = form == "rccl-captured"
-        tr._graph = None
+        tr.drop_graph()
         if form == "oneshot":
             if xchg is None:
                 raise _lib.HcgError("exchange form 'oneshot' needs a OneShotExchange that passed its self test")

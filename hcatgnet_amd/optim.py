@@ -54,6 +54,24 @@ class FusedFlatOptimizer:
             if fl is not None:
                 self._make_dev_state(fl, group)
 
+    def capture_state(self, gi: int = 0) -> list:
+        """Ready group `gi` for a capture that takes its own warm-up back: capturable mode, flat storages (re-based now if
+        need be), device words.  -> the live tensors its steps modify: flat parameters, the rule's `STATE` storages, the
+        step-count word (NOT the exchange stamp, which never goes back).  `on_storages`: still the group's afterwards?"""
+        self.enable_capturable()
+        group, fl = self.param_groups[gi], self._flat.get(gi)
+        ps = [q for q in group["params"] if q.requires_grad]
+        if (fl is None or len(fl["params"]) != len(ps) or any(a is not b for a, b in zip(fl["params"], ps))
+                or ps[0].data_ptr() != fl["p"].data_ptr()):
+            with torch.no_grad():
+                fl = self._rebase(gi, group)
+        self._make_dev_state(fl, group)
+        return [fl["p"]] + self.flat_state(fl) + [fl["step_dev"][:1]]
+
+    def on_storages(self, live: list, gi: int = 0) -> bool:
+        """No re-base of group `gi` since `capture_state` returned `live`."""
+        return self._flat.get(gi, {}).get("p") is live[0]
+
     def _make_dev_state(self, fl, group):
         """step_dev = [step count, exchange stamp, ticket, pad].  Word 1 counts the carried steps (hcg_step_tail) this
         optimiser OBJECT has started and is carried over every re-base / `load_state_dict` (`_keep_stamp`): the one-shot

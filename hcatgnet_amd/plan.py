@@ -112,6 +112,23 @@ class BatchPlan:
         return self
 
     @staticmethod
+    def from_pointers(edge_index, batch, graph_ptr, edge_ptr, N, E, B, max_nodes, max_edges, edge_weight=None, fill=1.0,
+                      mode="blocked", validated=True, status=None) -> "BatchPlan":
+        """The plan of a batch whose graph_ptr / edge_ptr the caller already holds on the device (a device collate: the host
+        knows every graph's size): trusted, blocked, pointers only -- nothing is launched.  The keywords are `build`'s, whose
+        plans start here too so that no slot is left unset (`status`: its own word; None = the device's shared one)."""
+        p = BatchPlan()
+        p.N, p.E, p.B, p.fill, p.mode = N, E, B, fill, mode
+        p.edge_index, p.batch, p.edge_weight = edge_index, batch, edge_weight
+        p.graph_ptr, p.edge_ptr = graph_ptr, edge_ptr
+        p.max_nodes, p.max_edges, p.validated, p.has_csr = max_nodes, max_edges, validated, False
+        p.shared_status, p.want_eid = status is None, False
+        p.status = _shared_status(edge_index.device) if status is None else status
+        p.rowptr = p.col = p.eid = p.rowptr_t = p.col_t = p.eid_t = None
+        p.dinv = p.ew_csr = p.ew_csc = p.dinv_unw = None
+        return p
+
+    @staticmethod
     def build(edge_index: torch.Tensor, batch: Optional[torch.Tensor], num_nodes: int,
               num_graphs: Optional[int] = None, edge_weight: Optional[torch.Tensor] = None,
               improved: bool = False, mode: str = "auto", validate: bool = True,
@@ -150,18 +167,10 @@ class BatchPlan:
             mode = "general"
         want = "blocked" if mode in ("auto", "blocked") else "general"
 
-        p = BatchPlan()
-        p.N, p.E, p.B, p.fill = N, E, B, fill
-        p.edge_index, p.batch, p.edge_weight = edge_index, batch, edge_weight
-        p.max_nodes, p.max_edges, p.validated, p.has_csr = max_nodes, max_edges, False, False
-        p.want_eid = False
         i32 = dict(dtype=torch.int32, device=dev)
-        p.graph_ptr = torch.empty(B + 1, **i32)
-        p.edge_ptr = torch.empty(B + 1, **i32)
-        p.shared_status = not validate
-        p.status = _shared_status(dev) if p.shared_status else torch.empty(4, **i32)
-        p.rowptr = p.col = p.eid = p.rowptr_t = p.col_t = p.eid_t = None
-        p.dinv = p.ew_csr = p.ew_csc = p.dinv_unw = None
+        p = BatchPlan.from_pointers(edge_index, batch, torch.empty(B + 1, **i32), torch.empty(B + 1, **i32), N, E, B, max_nodes,
+                                    max_edges, edge_weight, fill, want, validated=False,
+                                    status=torch.empty(4, **i32) if validate else None)
 
         def want_csr(which):
             if csr is not None:

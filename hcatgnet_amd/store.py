@@ -16,7 +16,37 @@ import torch
 
 from . import _lib
 from .batch import Batch, Data
-from .plan import BatchPlan, _shared_status
+from .plan import BatchPlan
+
+
+def epoch_layout(n_host, e_host, batch_size, drop_last, order, out=None):
+    """The index arrays of one epoch over the graphs in `order` (`n_host` / `e_host`: nodes / edges of every graph): [ids of
+    every batch | graph_ptr of every batch | edge_ptr of every batch] as int64 words -- the pointers are int32, two per
+    word, every batch's block starts on a word: (B + 2) // 2 words hold B + 1.  `out`: an int64 buffer to refill instead.
+    -> (buffer, [(i, B, off)]: batch order[i:i + B], its pointers at int32 offsets off and 2 * tot + off behind the ids, tot)."""
+    G = len(order)
+    Bs = [(i, min(batch_size, G - i)) for i in range(0, G, batch_size) if not (drop_last and G - i < batch_size)]
+    tot = sum((B + 2) // 2 for _, B in Bs)
+    buf = np.zeros(G + 2 * tot, np.int64) if out is None else out
+    buf[:] = 0
+    buf[:G] = order
+    ptr32 = buf[G:].view(np.int32)
+    cn, ce = np.cumsum(n_host[order]), np.cumsum(e_host[order])      # (over the epoch: a batch's prefix sums less its start's)
+    spans, off = [], 0
+    for i, B in Bs:
+        ptr32[off + 1:off + B + 1] = cn[i:i + B] - (cn[i - 1] if i else 0)
+        ptr32[2 * tot + off + 1:2 * tot + off + B + 1] = ce[i:i + B] - (ce[i - 1] if i else 0)
+        spans.append((i, B, off))
+        off += 2 * ((B + 2) // 2)
+    return buf, spans, tot
+
+
+def fill_collate_slot(sl, ids, gp, ep, x, ei, bvec, y, idx, B, N, E):
+    """Point a `_lib.CollateSlot` at one batch: the index views its gather reads, the tensors it writes."""
+    p = _lib.ptr
+    sl.ids, sl.graph_ptr, sl.edge_ptr, sl.x_out, sl.edge_index_out, sl.batch_out = p(ids), p(gp), p(ep), p(x), p(ei), p(bvec)
+    sl.y_out, sl.idx_out, sl.B, sl.N_out, sl.E_out = p(y), p(idx), B, N, E
+    return sl
 
 
 class DeviceGraphStore:
@@ -89,23 +119,12 @@ class DeviceGraphStore:
         bvec = torch.empty(N, dtype=torch.int64, device=dev)
         y = torch.empty(B, dtype=torch.float32, device=dev) if self.y_all is not None else None
         idx = torch.empty(B, dtype=torch.int64, device=dev) if self.idx_all is not None else None
-        p = _lib.ptr
         a = self.collate_args()
-        sl = a.slot
-        sl.ids, sl.graph_ptr, sl.edge_ptr, sl.x_out, sl.edge_index_out, sl.batch_out = p(ids_d), p(gp_d), p(ep_d), p(x), p(ei), p(bvec)
-        sl.y_out, sl.idx_out, sl.B, sl.N_out, sl.E_out = p(y), p(idx), B, N, E
+        fill_collate_slot(a.slot, ids_d, gp_d, ep_d, x, ei, bvec, y, idx, B, N, E)
         _lib.check(lib.hcg_collate(ctypes.byref(a), _lib.stream_ptr()), "hcg_collate")
         batch = Batch(x, ei, bvec, B, y=y, idx=idx, max_nodes=int(n.max()), max_edges=int(e.max()), edges_grouped=True)
         # the plan of the fused path is exactly (graph_ptr, edge_ptr): attach it, nothing left to launch
-        plan = BatchPlan()
-        plan.N, plan.E, plan.B, plan.fill, plan.mode = N, E, B, 1.0, "blocked"
-        plan.edge_index, plan.batch, plan.edge_weight = ei, bvec, None
-        plan.graph_ptr, plan.edge_ptr = gp_d, ep_d
-        plan.max_nodes, plan.max_edges, plan.validated, plan.has_csr = batch.max_nodes, batch.max_edges, True, False
-        plan.shared_status, plan.status, plan.want_eid = True, _shared_status(dev), False
-        plan.rowptr = plan.col = plan.eid = plan.rowptr_t = plan.col_t = plan.eid_t = None
-        plan.dinv = plan.ew_csr = plan.ew_csc = plan.dinv_unw = None
-        batch._hcg_plan = plan
+        batch._hcg_plan = BatchPlan.from_pointers(ei, bvec, gp_d, ep_d, N, E, B, batch.max_nodes, batch.max_edges)
         return batch
 
 
@@ -126,27 +145,11 @@ class DeviceLoader:
     def __iter__(self):
         st = self.store
         order = self.rng.permutation(len(st)) if self.shuffle else np.arange(len(st))
-        starts = [i for i in range(0, len(order), self.batch_size)
-                  if not (self.drop_last and len(order) - i < self.batch_size)]
-        # the epoch's index arrays in ONE upload: [ids of every batch | graph_ptr of every batch | edge_ptr of every batch]
-        # as int64 words (graph_ptr / edge_ptr are int32: two per word, every batch's block starts on a word) -- a batch
-        # then costs its gather launch and no host-to-device copy of its own (three ~10 us copies per step otherwise)
-        G = len(order)
-        words = lambda B: (B + 2) // 2                       # int64 words that hold B + 1 int32
-        tot = sum(words(min(self.batch_size, G - i)) for i in starts)
-        buf = np.zeros(G + 2 * tot, np.int64)
-        buf[:G] = order
-        ptr32 = buf[G:].view(np.int32)
-        spans, off = [], 0
-        for i in starts:
-            ids = order[i:i + self.batch_size]
-            B = ids.size
-            ptr32[off + 1:off + B + 1] = np.cumsum(st.n_host[ids])
-            ptr32[2 * tot + off + 1:2 * tot + off + B + 1] = np.cumsum(st.e_host[ids])
-            spans.append((i, B, off))
-            off += 2 * words(B)
+        # the epoch's index arrays in ONE upload (`epoch_layout`): a batch then costs its gather launch and no host-to-device
+        # copy of its own (three ~10 us copies per step otherwise)
+        buf, spans, tot = epoch_layout(st.n_host, st.e_host, self.batch_size, self.drop_last, order)
         dbuf = torch.from_numpy(buf).to(st.device)
-        d32 = dbuf[G:].view(torch.int32)
+        d32 = dbuf[len(order):].view(torch.int32)
         for i, B, off in spans:
             yield st.collate(order[i:i + B], _uploaded=(dbuf[i:i + B], d32[off:off + B + 1],
                                                          d32[2 * tot + off:2 * tot + off + B + 1]))

@@ -839,13 +839,6 @@ class FusedTrainStep:
         `next_plan`: sets `self.next_plan` (see `__init__`) for the captured step."""
         if next_plan is not None:
             self.next_plan = next_plan
-        opt = self.model.optimizer
-        if self.optimizer_step:
-            if not hasattr(opt, "enable_capturable"):
-                raise _lib.HcgError("capture() with optimizer_step needs a fused optimiser of hcatgnet_amd.optim "
-                                    "(FusedAdam, FusedSGD, FusedRMSprop)")
-            opt.enable_capturable()
-        sync, do_opt = self.grad_sync, self.optimizer_step
 
         def get():
             if callable(batch):
@@ -858,14 +851,9 @@ class FusedTrainStep:
             except Exception:
                 pass
             return batch
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):                       # warm-up: every buffer allocated, optimiser state re-based
-                self(get())
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        orig_sync = sync
+        # warm-up (two runs): every buffer allocated, optimiser state re-based
+        cap = _Capture(self.model.optimizer if self.optimizer_step else None, True, lambda: (self(get()), self(get())))
+        sync = orig_sync = self.grad_sync
         if sync is None and self.exchange is not None and not self._last_carried:
             sync = self.exchange_fallback_sync         # (this step's update cannot carry the one-shot exchange: collective form)
         split = sync is not None and not self.capture_exchange
@@ -874,11 +862,8 @@ class FusedTrainStep:
                 self.grad_sync = None
             self._capturing_split = split              # with an exchange, the graph ends after the slab reduction
                                                        # (unless `capture_exchange`: collective + update are recorded too)
-            g_main = torch.cuda.CUDAGraph()
             fork = torch.cuda.Stream() if prefetch is not None else None
-            # (a live process group has helper threads that query events: their calls must not fail this capture)
-            mode = "thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"
-            with torch.cuda.graph(g_main, capture_error_mode=mode):
+            with cap.recording():
                 if fork is not None:
                     main = torch.cuda.current_stream()
                     fork.wait_stream(main)
@@ -889,7 +874,7 @@ class FusedTrainStep:
                     main.wait_stream(fork)
         finally:
             self.grad_sync, self._capturing_split = orig_sync, False
-        self._graph = (g_main, loss, split, self._graph_fingerprint())
+        self._graph = (cap.graph, loss, split, self._graph_fingerprint())
         return self
 
     def _graph_fingerprint(self):
@@ -914,12 +899,10 @@ class FusedTrainStep:
             raise _lib.HcgError("replay(): no captured step (never captured, or its buffers were re-allocated by a larger "
                                 "eager batch): call capture() again")
         g_main, loss, split, fp = self._graph
-        if fp != self._graph_fingerprint():
+        if not _replayable((self,), (fp,), self.optimizer_step):
             self._graph = None
             raise _lib.HcgError("replay(): parameter / optimiser / step buffers changed since capture() "
                                 "(load_state_dict, a larger eager batch): call capture() again")
-        if self.optimizer_step:
-            self.model.optimizer.sync_lr()
         g_main.replay()
         if split:                                     # exchange between the captured backward and the update:
             self._exchange_and_update(loss_buf=self._bufs["cap"]["loss"])   # one collective, then ONE eager launch
@@ -928,6 +911,51 @@ class FusedTrainStep:
             # may have re-pointed them since the capture)
             self._flat_grads(self._trainable(), self._flat.device)
         return loss
+
+    def drop_graph(self):
+        self._graph = None
+
+    def captured_loss(self):
+        """The loss buffer the captured step writes, or None before any step ran on capture buffers."""
+        cap = self._bufs.get("cap")
+        return None if cap is None else cap["loss"]
+
+
+class _Capture:
+    """The capture protocol of a step and of a window of steps.  Making one is its first half: `opt`, the optimiser the steps
+    update (None: none), must be a fused one and with `enable` switches to its device-side step count / learning rate;
+    `warm_up()` runs on a side stream bracketed by the current one; the device is synchronised.  `with recording()`, the
+    second, puts the block into `graph`; in between the caller settles what it learnt from the warm-up."""
+
+    def __init__(self, opt, enable, warm_up):
+        if opt is not None:
+            if not hasattr(opt, "enable_capturable"):
+                raise _lib.HcgError("capturing steps with optimizer_step needs a fused optimiser of hcatgnet_amd.optim "
+                                    "(FusedAdam, FusedSGD, FusedRMSprop)")
+            if enable:
+                opt.enable_capturable()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm_up()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+
+    def recording(self):
+        # (a live process group has helper threads that query events: their calls must not fail this capture)
+        mode = "thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"
+        return torch.cuda.graph(self.graph, capture_error_mode=mode)
+
+
+def _replayable(steps, fingerprints, updates) -> bool:
+    """Before a replay: False when an address the graph of `steps` has baked in was replaced, else the learning rate is synced."""
+    for st, fp in zip(steps, fingerprints):
+        if fp != st._graph_fingerprint():
+            return False
+    if updates:
+        steps[0].model.optimizer.sync_lr()
+    return True
 
 
 class StepWindow:
@@ -958,31 +986,21 @@ class StepWindow:
             if st.grad_sync is not None and not st.capture_exchange:
                 raise _lib.HcgError("a step with a separate gradient collective (grad_sync) cannot be captured into a window "
                                     "(unless its `capture_exchange` is set: the collective is then recorded with the step)")
-            if st.optimizer_step and not hasattr(model.optimizer, "enable_capturable"):
-                raise _lib.HcgError("StepWindow with optimizer_step needs a fused optimiser of hcatgnet_amd.optim "
-                                    "(FusedAdam, FusedSGD, FusedRMSprop)")
-        self.forward_only = bool(forward_only)
-        if steps[0].optimizer_step and not self.forward_only:
-            model.optimizer.enable_capturable()
-        self.steps, self.model = steps, model
-        get = lambda b: b() if callable(b) else b
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                      # warm-up: every buffer allocated, optimiser state re-based
-            for st, b in zip(steps, batches):
-                st(get(b), _forward_only=self.forward_only)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        mode = "thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"
+        self.steps, self.model, self.forward_only = steps, model, bool(forward_only)
+        self.updates = steps[0].optimizer_step and not self.forward_only
+        self.batches, self.counts64 = batches, counts64      # (kept alive: the graph reads their storages)
+        run = lambda: [st(b() if callable(b) else b, _forward_only=self.forward_only) for st, b in zip(steps, batches)]
+        # warm-up (every step once): every buffer allocated, optimiser state re-based
+        cap = _Capture(model.optimizer if any(st.optimizer_step for st in steps) else None, self.updates, run)
         self.value_host = None
         if counts64 is not None:
             self.value_host = torch.zeros(1, dtype=torch.float64).pin_memory()
             _weighted_loss_dev([counts64.new_zeros((), dtype=torch.float32) for _ in steps], counts64)   # (its kernels loaded before the capture)
             self.value_host.copy_(counts64[:1], non_blocking=True)
             torch.cuda.synchronize()
-        with torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.losses = [st(get(b), _forward_only=self.forward_only) for st, b in zip(steps, batches)]
+        self.graph = cap.graph
+        with cap.recording():
+            self.losses = run()
             if counts64 is not None:
                 self.value_dev = _weighted_loss_dev(self.losses, counts64)
                 self.value_host.copy_(self.value_dev.reshape(1), non_blocking=True)
@@ -995,10 +1013,8 @@ class StepWindow:
 
     def replay(self):
         """-> the steps' loss tensors (device scalars, overwritten by the next replay)."""
-        if self._fp != [st._graph_fingerprint() for st in self.steps]:
+        if not _replayable(self.steps, self._fp, self.updates):
             raise _lib.HcgError("StepWindow.replay(): parameter / optimiser / step buffers changed since the capture: build it again")
-        if self.steps[0].optimizer_step and not self.forward_only:
-            self.model.optimizer.sync_lr()
         self.graph.replay()
         return self.losses
 
@@ -1033,26 +1049,23 @@ class EpochWindow:
     def __init__(self, model, loader):
         import numpy as np
         from .batch import Batch
-        from .plan import BatchPlan, _shared_status
-        st, bs = loader.store, loader.batch_size
+        from .plan import BatchPlan
+        from .store import epoch_layout, fill_collate_slot
+        st = loader.store
         G, dev, F = len(st), st.device, st.F
-        starts = [i for i in range(0, G, bs) if not (loader.drop_last and G - i < bs)]
-        if not starts or len(starts) > self.MAX_BATCHES or st.y_all is None:
+        self.batching = (loader.batch_size, loader.drop_last)
+        buf, spans, tot = epoch_layout(st.n_host, st.e_host, *self.batching, np.arange(G))
+        if not spans or len(spans) > self.MAX_BATCHES or st.y_all is None:
             raise _lib.HcgError("EpochWindow: no batches, too many batches, or a dataset without targets")
         self.model, self.loader, self.G = model, loader, G
-        self.Bs = [min(bs, G - i) for i in starts]
-        self.starts = starts
+        self.Bs = [B for _, B, _ in spans]
         n_desc, e_desc = np.sort(st.n_host)[::-1], np.sort(st.e_host)[::-1]
         maxn, maxe = int(n_desc[0]), int(e_desc[0])
-        words = lambda B: (B + 2) // 2                       # int64 words that hold B + 1 int32 (as DeviceLoader.__iter__)
-        tot = sum(words(B) for B in self.Bs)
-        self.tot = tot
-        self.host = torch.zeros(G + 2 * tot, dtype=torch.int64).pin_memory()
-        self.dbuf = torch.zeros(G + 2 * tot, dtype=torch.int64, device=dev)
+        self.host = torch.zeros(buf.size, dtype=torch.int64).pin_memory()
+        self.dbuf = torch.zeros(buf.size, dtype=torch.int64, device=dev)
         d32 = self.dbuf[G:].view(torch.int32)
-        lib, p = _lib.load(), _lib.ptr
-        self.batches, self.spans, slots, off = [], [], [], 0
-        for i, B in zip(starts, self.Bs):
+        self.batches, slots = [], []
+        for i, B, off in spans:
             Ncap, Ecap = int(n_desc[:B].sum()), max(int(e_desc[:B].sum()), 1)
             x = torch.zeros(Ncap, F, dtype=torch.float32, device=dev)
             ei = torch.zeros(2, Ecap, dtype=torch.int64, device=dev)
@@ -1061,38 +1074,24 @@ class EpochWindow:
             idx = torch.zeros(B, dtype=torch.int64, device=dev) if st.idx_all is not None else None
             ids_d, gp_d, ep_d = self.dbuf[i:i + B], d32[off:off + B + 1], d32[2 * tot + off:2 * tot + off + B + 1]
             batch = Batch(x, ei, bvec, B, y=y, idx=idx, max_nodes=maxn, max_edges=maxe, edges_grouped=True)
-            plan = BatchPlan()
-            plan.N, plan.E, plan.B, plan.fill, plan.mode = Ncap, Ecap, B, 1.0, "blocked"
-            plan.edge_index, plan.batch, plan.edge_weight = ei, bvec, None
-            plan.graph_ptr, plan.edge_ptr = gp_d, ep_d
-            plan.max_nodes, plan.max_edges, plan.validated, plan.has_csr = maxn, maxe, True, False
-            plan.shared_status, plan.status, plan.want_eid = True, _shared_status(dev), False
-            plan.rowptr = plan.col = plan.eid = plan.rowptr_t = plan.col_t = plan.eid_t = None
-            plan.dinv = plan.ew_csr = plan.ew_csc = plan.dinv_unw = None
-            batch._hcg_plan = plan
+            batch._hcg_plan = plan = BatchPlan.from_pointers(ei, bvec, gp_d, ep_d, Ncap, Ecap, B, maxn, maxe)
             shapes = [(Fl, D, "auto") for Fl, D, _ in _layer_shapes(model)]      # (whatever the conv's family preference)
             if any(f.fam.row_streaming for f in layer_forms(shapes, Ncap, maxn, maxe, plan=plan) or ()):
                 raise _lib.HcgError("EpochWindow: a layer would run on the dense row-streaming kernels (capacity-padded rows)")
             self.batches.append(batch)
-            self.spans.append((i, B, off))
-
-            sl = _lib.CollateSlot()
-            sl.ids, sl.graph_ptr, sl.edge_ptr, sl.x_out, sl.edge_index_out, sl.batch_out = p(ids_d), p(gp_d), p(ep_d), p(x), p(ei), p(bvec)
-            sl.y_out, sl.idx_out, sl.B, sl.N_out, sl.E_out = p(y), p(idx), B, Ncap, Ecap
-            slots.append(sl)
-            off += 2 * words(B)
+            slots.append(fill_collate_slot(_lib.CollateSlot(), ids_d, gp_d, ep_d, x, ei, bvec, y, idx, B, Ncap, Ecap))
         # ONE collate launch for the whole epoch, in front of its first step (every slot owns its buffers; the launch reads the
         # slot descriptors from a device array): a collate per batch was 14 launches of 40 workgroups, a tenth of the epoch
         arr = (_lib.CollateSlot * len(slots))(*slots)
         self.slots_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
         src = st.collate_args()
         self.cargs = _lib.CollateArgs.from_buffer_copy(src)
-        self.cargs.nslots, self.cargs.slots_dev, self.cargs.max_B = len(slots), p(self.slots_dev), max(self.Bs)
+        self.cargs.nslots, self.cargs.slots_dev, self.cargs.max_B = len(slots), _lib.ptr(self.slots_dev), max(self.Bs)
         if len(slots) == 1:
             self.cargs.slot = slots[0]
 
         def first_batch():
-            _lib.check(lib.hcg_collate(ctypes.byref(self.cargs), _lib.stream_ptr()), "hcg_collate")
+            _lib.check(_lib.load().hcg_collate(ctypes.byref(self.cargs), _lib.stream_ptr()), "hcg_collate")
             return self.batches[0]
         fns = [first_batch] + [(lambda b=b: b) for b in self.batches[1:]]
         self.steps = [FusedTrainStep(model) for _ in self.Bs]
@@ -1104,18 +1103,10 @@ class EpochWindow:
         # count go back to what they were, in place (same storages, so the captured addresses stay valid) -- also when the
         # capture fails, since the caller then trains on in its per-batch loop.  The exchange stamp is never taken back
         self._layout(np.arange(G))
-        opt = model.optimizer
-        opt.enable_capturable()
-        for q in model.parameters():                    # re-base onto the optimiser's flat storages BEFORE the snapshot
+        for q in model.parameters():
             _lib.require_gpu(q)
-        fl = opt._flat.get(0)
-        ps = [q for q in opt.param_groups[0]["params"] if q.requires_grad]
-        if (fl is None or len(fl["params"]) != len(ps) or any(a is not b for a, b in zip(fl["params"], ps))
-                or ps[0].data_ptr() != fl["p"].data_ptr()):
-            with torch.no_grad():
-                fl = opt._rebase(0, opt.param_groups[0])
-        opt._make_dev_state(fl, opt.param_groups[0])
-        live = [fl["p"]] + opt.flat_state(fl) + [fl["step_dev"][:1]]        # parameters, the rule's state, the step count
+        opt = model.optimizer
+        live = opt.capture_state()          # (re-based onto the optimiser's flat storages BEFORE the snapshot)
         saved = [t.clone() for t in live]
         try:
             self.window = StepWindow(self.steps, fns, counts64=self.counts)
@@ -1124,21 +1115,14 @@ class EpochWindow:
             with torch.no_grad():
                 for t, u in zip(live, saved):
                     t.copy_(u)
-        if opt._flat.get(0) is not fl:
+        if not opt.on_storages(live):
             raise _lib.HcgError("EpochWindow: the optimiser re-based its state during the capture")
 
     def _layout(self, order):
-        """The epoch's index arrays [ids of every batch | graph_ptr of every batch | edge_ptr of every batch] -> device."""
-        import numpy as np
-        st, G, tot = self.loader.store, self.G, self.tot
-        buf = self.host.numpy()
-        buf[:] = 0
-        buf[:G] = order
-        ptr32 = buf[G:].view(np.int32)
-        for i, B, off in self.spans:
-            ids = order[i:i + B]
-            ptr32[off + 1:off + B + 1] = np.cumsum(st.n_host[ids])
-            ptr32[2 * tot + off + 1:2 * tot + off + B + 1] = np.cumsum(st.e_host[ids])
+        """The epoch's index arrays (`store.epoch_layout`) for the graphs in this order -> device."""
+        from .store import epoch_layout
+        st = self.loader.store
+        epoch_layout(st.n_host, st.e_host, *self.batching, order, out=self.host.numpy())
         self.dbuf.copy_(self.host, non_blocking=True)
 
     def draw_order(self):
@@ -1180,7 +1164,7 @@ class _EpochSum:
     """sum(loss_i * num_graphs_i) of an epoch, on the device, in float64 like the reference's Python-float accumulation
     (`loss.item() * batch.num_graphs`, utils/utils_model.py:68): the per-batch losses are kept (one tiny copy each, no
     sync) and meet in ONE dot product at the end of the epoch -- the same operation the one-graph epoch forms
-    (`EpochWindow`, `_eval_window`) apply to their loss buffers, so both forms return bitwise the same value."""
+    (`EpochWindow`, `_build_eval_window`) apply to their loss buffers, so both forms return bitwise the same value."""
 
     def __init__(self):
         self.vals, self.ns = [], []
@@ -1209,9 +1193,9 @@ def train_network(model, train_loader, device):
     The per-batch `loss.item()` of the reference is replaced by a device-side accumulation and ONE sync."""
     model.train()
     fused = _fused_of(model)
-    val = _epoch_window(model, train_loader)
-    if val is not None:
-        return val
+    got = _EPOCH_WINDOWS.launch(model, train_loader)
+    if got is not None:
+        return got[0].finish_epoch(got[1])
     total = _EpochSum()
     for batch in train_loader:
         batch = batch.to(device)
@@ -1230,98 +1214,106 @@ def train_network(model, train_loader, device):
 EPOCH_WINDOW = True      # train_network over a DeviceLoader: whole epochs as one hipGraph (EpochWindow); False = per-batch loop
 
 
-def _epoch_window_launch(model, loader):
-    """Issue one epoch through the loader's cached `EpochWindow` (built on first use; rebuilt when the model or the
-    optimiser's storages changed) on the current stream -> (window, losses) for `window.finish_epoch(losses)`, or None
-    when that form does not apply."""
-    from .store import DeviceLoader
-    if not (EPOCH_WINDOW and isinstance(loader, DeviceLoader) and hasattr(model.optimizer, "enable_capturable")):
-        return None
-    if dist_initialized_multi():
-        return None                          # (data parallel epochs keep the per-batch loop: the exchange form is the caller's)
-    order = None
-    for attempt in range(2):
-        cache = getattr(loader, "_hcg_epoch_window", None)
-        key = (id(model), loader.batch_size, loader.drop_last, len(loader.store))
-        if cache is None or cache[0] != key:
-            win = EpochWindow.build(model, loader)
-            cache = (key, win)
-            try:
-                loader._hcg_epoch_window = cache
-            except Exception:
-                pass
-        if cache[1] is None:
+class _LoaderWindows:
+    """One kind of captured window that a `store.DeviceLoader` keeps for a model: ONE entry (model, key, window or None) on
+    its attribute `attr`.  `key(model, loader)`: what the window depends on besides the model, None = the kind does not
+    apply; `build(model, loader)` -> window or None."""
+
+    def __init__(self, attr, key, build, launch, draw=None):
+        self.attr, self.key, self.build, self._launch, self.draw = attr, key, build, launch, draw
+
+    def of(self, model, loader, build: bool = False):
+        """The loader's window for this model, or None: there is none (`build`: make it now) or the kind does not apply.
+        The model is compared by identity and held (an `id` can be reused); a None is kept like a window: what could not be
+        built is not tried again for the same model and key.  A loader that refuses attributes keeps nothing."""
+        key = self.key(model, loader)
+        if key is None:
             return None
+        ent = getattr(loader, self.attr, None)
+        if ent is not None and ent[0] is model and ent[1] == key:
+            return ent[2]
+        if not build:
+            return None
+        win = self.build(model, loader)
         try:
-            if order is None:
-                order = cache[1].draw_order()            # (drawn once: a rebuild must not skip a permutation)
-            return cache[1], cache[1].launch_epoch(order)
-        except _lib.HcgError:                 # parameters / optimiser re-based since the capture: build again
-            try:
-                loader._hcg_epoch_window = None
-            except Exception:
+            setattr(loader, self.attr, (model, key, win))
+        except Exception:
+            pass
+        return win
+
+    def launch(self, model, loader):
+        """Issue the loader's window (built on first use) on the current stream -> (window, `launch(window, drawn)`), or None
+        without one.  A launch that raises `HcgError` (parameters / optimiser re-based since the capture) drops the entry and
+        is repeated ONCE on a rebuilt window; `draw(window)` runs once per call (an epoch's permutation: a rebuild skips none)."""
+        drawn = None
+        for attempt in range(2):
+            win = self.of(model, loader, build=True)
+            if win is None:
                 return None
-    return None
-
-
-def _epoch_window(model, loader):
-    """-> the epoch's value through `_epoch_window_launch`, or None when that form does not apply."""
-    got = _epoch_window_launch(model, loader)
-    return None if got is None else got[0].finish_epoch(got[1])
+            try:
+                if attempt == 0 and self.draw is not None:
+                    drawn = self.draw(win)
+                return win, self._launch(win, drawn)
+            except _lib.HcgError:
+                try:
+                    setattr(loader, self.attr, None)
+                except Exception:
+                    return None
+        return None
 
 
 def dist_initialized_multi() -> bool:
     return torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
 
 
+def _epoch_window_key(model, loader):
+    from .store import DeviceLoader
+    if (not (EPOCH_WINDOW and isinstance(loader, DeviceLoader) and hasattr(model.optimizer, "enable_capturable"))
+            or dist_initialized_multi()):    # (data parallel epochs keep the per-batch loop: the exchange form is the caller's)
+        return None
+    return (loader.batch_size, loader.drop_last, len(loader.store))
+
+
 EVAL_WINDOW_MAX_BATCHES = 64
 
 
-def _eval_window(model, loader, fused, launch_only: bool = False):
-    """(`launch_only`: issue the graph on the current stream and return its window without synchronising: `window.value()`.)
-    A `store.DeviceLoader` that does not shuffle yields the same batches every epoch (the reference's validation / test
-    loaders, call_methods.py:41-46): they are collated once, their `evaluate` steps captured as ONE hipGraph
-    (`StepWindow(forward_only=True)`) and an `eval_network` call is one graph launch + one reduction instead of
-    (collate + 3 launches) per batch.  -> the epoch's value, or None when this path does not apply (the caller loops)."""
+def _eval_window_key(model, loader):
     from .store import DeviceLoader
     if not (isinstance(loader, DeviceLoader) and not loader.shuffle and 0 < len(loader) <= EVAL_WINDOW_MAX_BATCHES):
         return None
-    cache = getattr(loader, "_hcg_eval_window", None)
-    key = (loader.batch_size, loader.drop_last, len(loader.store), bool(getattr(model, "use_fused", True)))
-    for attempt in range(2):
-        if cache is None or cache["model"] is not model or cache.get("key") != key:
-            batches = list(loader)
-            if not all(fused.reason(b) is None for b in batches):
-                return None
-            try:
-                steps = [FusedTrainStep(model, optimizer_step=False) for _ in batches]
-                counts = torch.tensor([float(b.num_graphs) for b in batches], dtype=torch.float64, device=batches[0].x.device)
-                win = StepWindow(steps, batches, forward_only=True, counts64=counts)
-            except (_lib.HcgError, RuntimeError):        # capture failed (memory, an unsupported launch): the per-batch loop runs
-                return None
-            cache = {"model": model, "key": key, "window": win, "batches": batches, "counts": counts}
-            try:
-                loader._hcg_eval_window = cache
-            except Exception:
-                pass
-        try:
-            losses = cache["window"].replay()
-        except _lib.HcgError:                 # parameters re-based since the capture (load_state_dict on new storages ...)
-            cache = None
-            continue
-        if launch_only:
-            return cache["window"]
-        return cache["window"].value() / len(loader.dataset)
-    return None
+    return (loader.batch_size, loader.drop_last, len(loader.store), bool(getattr(model, "use_fused", True)))
+
+
+def _build_eval_window(model, loader):
+    """A `store.DeviceLoader` that does not shuffle yields the same batches every epoch (the reference's validation / test
+    loaders, call_methods.py:41-46): they are collated once, their `evaluate` steps captured as ONE hipGraph
+    (`StepWindow(forward_only=True)`) and an `eval_network` call is one graph launch + one reduction instead of
+    (collate + 3 launches) per batch.  -> the window, or None (a batch outside the fused step, a failed capture): the loop runs."""
+    batches, fused = list(loader), _fused_of(model)
+    if not all(fused.reason(b) is None for b in batches):
+        return None
+    try:
+        steps = [FusedTrainStep(model, optimizer_step=False) for _ in batches]
+        counts = torch.tensor([float(b.num_graphs) for b in batches], dtype=torch.float64, device=batches[0].x.device)
+        return StepWindow(steps, batches, forward_only=True, counts64=counts)
+    except (_lib.HcgError, RuntimeError):        # (memory, an unsupported launch)
+        return None
+
+
+_EPOCH_WINDOWS = _LoaderWindows("_hcg_epoch_window", _epoch_window_key, EpochWindow.build, EpochWindow.launch_epoch,
+                                EpochWindow.draw_order)
+_EVAL_WINDOWS = _LoaderWindows("_hcg_eval_window", _eval_window_key, _build_eval_window, lambda win, _: win.replay())
+# (model, loader, build=False) -> the `EpochWindow` train_network / the forward-only `StepWindow` eval_network replays, or None
+epoch_window_of, eval_window_of = _EPOCH_WINDOWS.of, _EVAL_WINDOWS.of
 
 
 def eval_network(model, loader, device):
     """reference utils/utils_model.py:72-79 (forward + sqrt(MSE) per batch; no parameter update)."""
     model.eval()
     fused = _fused_of(model)
-    total = _eval_window(model, loader, fused)
-    if total is not None:
-        return total
+    got = _EVAL_WINDOWS.launch(model, loader)
+    if got is not None:
+        return got[0].value() / len(loader.dataset)
     total = _EpochSum()
     with torch.no_grad():
         for batch in loader:
@@ -1334,27 +1326,25 @@ def eval_network(model, loader, device):
     return total.value(len(loader.dataset))
 
 
-def _fused_of(model):
-    fused = getattr(model, "_hcg_train_step", None)
-    if fused is None:
-        fused = FusedTrainStep(model)
+def _kept_on(model, attr, make):
+    """`model.attr`, made on first use (a model that refuses attributes gets a new one every time)."""
+    v = getattr(model, attr, None)
+    if v is None:
+        v = make()
         try:
-            model._hcg_train_step = fused
+            setattr(model, attr, v)
         except Exception:
             pass
-    return fused
+    return v
+
+
+def _fused_of(model):
+    return _kept_on(model, "_hcg_train_step", lambda: FusedTrainStep(model))
 
 
 def _run_stream(model, device):
-    """The HIP stream of an independent run (one per model, made on first use)."""
-    st = getattr(model, "_hcg_run_stream", None)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        try:
-            model._hcg_run_stream = st
-        except Exception:
-            pass
-    return st
+    """The HIP stream of an independent run (one per model)."""
+    return _kept_on(model, "_hcg_run_stream", lambda: torch.cuda.Stream(device=device))
 
 
 def train_networks(models, train_loaders, device, active=None):
@@ -1369,59 +1359,72 @@ def train_networks(models, train_loaders, device, active=None):
     flight.  Each run's arithmetic is untouched: bitwise what `train_network` gives that run alone
     (tests/test_gpu_train_step.py::test_concurrent_runs_equal_the_runs_one_by_one).  A run whose epoch does not fit the
     one-graph form (a host loader, a layer on the dense row-streaming kernels) is trained by `train_network` in turn."""
-    K = len(models)
-    if len(train_loaders) != K or (active is not None and len(active) != K):
-        raise ValueError("train_networks: one loader (and one `active` flag) per model")
-    on = [bool(a) for a in active] if active is not None else [True] * K
-    out, flying = [None] * K, []
-    cur = torch.cuda.current_stream(device)
-    for k, (m, ld) in enumerate(zip(models, train_loaders)):
-        if not on[k]:
-            continue
-        m.train()
-        _fused_of(m)
-        st = _run_stream(m, device)
-        st.wait_stream(cur)                         # (whatever the caller did to this run's model on its own stream)
-        with torch.cuda.stream(st):
-            got = _epoch_window_launch(m, ld)
-        if got is None:
-            out[k] = train_network(m, ld, device)
-        else:
-            flying.append((k, st, got))
-    for k, st, (win, losses) in flying:
-        with torch.cuda.stream(st):
-            out[k] = win.finish_epoch(losses)
-        cur.wait_stream(st)
-    return out
+    return _run_networks("train_networks", models, train_loaders, device, active, lambda m: m.train(), _EPOCH_WINDOWS.launch,
+                         lambda got, ld: got[0].finish_epoch(got[1]), train_network)
 
 
 def eval_networks(models, loaders, device, active=None):
     """`eval_network` of several independent runs at once (see `train_networks`): every run's evaluation epoch -- one
     forward-only hipGraph over its fixed loader -- on the run's own stream.  -> [eval_network(model_k, loader_k, device)]."""
+    return _run_networks("eval_networks", models, loaders, device, active, lambda m: m.eval(), _EVAL_WINDOWS.launch,
+                         lambda got, ld: got[0].value() / len(ld.dataset), eval_network)
+
+
+def _run_networks(name, models, loaders, device, active, set_mode, launch, finish, single):
+    """One epoch of every active run on the run's own stream: `launch(model, loader)` issues it as one graph -> what
+    `finish(got, loader)` turns into its value (synchronises), or None: `single(model, loader, device)` runs it in turn."""
     K = len(models)
     if len(loaders) != K or (active is not None and len(active) != K):
-        raise ValueError("eval_networks: one loader (and one `active` flag) per model")
-    on = [bool(a) for a in active] if active is not None else [True] * K
+        raise ValueError(f"{name}: one loader (and one `active` flag) per model")
     out, flying = [None] * K, []
     cur = torch.cuda.current_stream(device)
     for k, (m, ld) in enumerate(zip(models, loaders)):
-        if not on[k]:
+        if active is not None and not active[k]:
             continue
-        m.eval()
-        fused = _fused_of(m)
+        set_mode(m)
+        _fused_of(m)
         st = _run_stream(m, device)
-        st.wait_stream(cur)
+        st.wait_stream(cur)                         # (whatever the caller did to this run's model on its own stream)
         with torch.cuda.stream(st):
-            got = _eval_window(m, ld, fused, launch_only=True)
+            got = launch(m, ld)
         if got is None:
-            out[k] = eval_network(m, ld, device)
+            out[k] = single(m, ld, device)
         else:
-            flying.append((k, st, got, len(ld.dataset)))
-    for k, st, win, n in flying:
+            flying.append((k, st, got, ld))
+    for k, st, got, ld in flying:
         with torch.cuda.stream(st):
-            out[k] = win.value() / n
+            out[k] = finish(got, ld)
         cur.wait_stream(st)
     return out
+
+
+class _Predictions:
+    """What the predict loops collect for M models over one loader, and the reference's result tuples made of it."""
+
+    def __init__(self):
+        self.y_pred, self.y_true, self.idx, self.embs = [], [], [], []
+
+    def add(self, batch, out, emb=None):
+        """`out` [M, graphs of the batch], `emb` [M, graphs, 2D] or None."""
+        self.y_pred.append(out)
+        self.y_true.append(batch.y.reshape(-1))
+        self.idx.append(batch.idx.reshape(-1) if batch.idx is not None else torch.full((batch.num_graphs,), -1, device=out.device))
+        if emb is not None:
+            self.embs.append(emb)
+
+    def results(self, return_emb: bool) -> list:
+        """-> [(y_pred, y_true, idx[, embeddings DataFrame])], one per model."""
+        y_pred = torch.cat(self.y_pred, 1).cpu().numpy()
+        y_true = torch.cat(self.y_true).cpu().numpy().ravel()
+        idx = torch.cat(self.idx).cpu().numpy().ravel()
+        res = [(row.ravel(), y_true, idx) for row in y_pred]
+        if return_emb:
+            import pandas as pd
+            for k, emb in enumerate(torch.cat(self.embs, 1).cpu().numpy()):
+                frame = pd.DataFrame(emb)
+                frame["ddG_exp"], frame["ddG_pred"], frame["index"] = y_true, res[k][0], idx
+                res[k] += (frame,)
+        return res
 
 
 def predict_network(model, loader, return_emb: bool = False, device=None):
@@ -1429,31 +1432,16 @@ def predict_network(model, loader, return_emb: bool = False, device=None):
     The reference moves the model to the CPU for this; here it stays on the GPU (`device` defaults to the
     model's) and only the results come back.  The embeddings frame has the reference's columns: `0..2D-1`
     (graph_emb = [max, mean]), `ddG_exp`, `ddG_pred`, `index`."""
-    import numpy as np
     model.eval()
     if device is None:
         device = next(model.parameters()).device
-    y_pred, y_true, idx, embs = [], [], [], []
+    got = _Predictions()
     with torch.no_grad():
         for batch in loader:
             batch = batch.to(device)
             out, emb = model(batch, True)
-            y_pred.append(out.reshape(-1))
-            y_true.append(batch.y.reshape(-1))
-            idx.append(batch.idx.reshape(-1) if batch.idx is not None else torch.full((batch.num_graphs,), -1, device=out.device))
-            if return_emb:
-                embs.append(emb)
-    y_pred = torch.cat(y_pred).cpu().numpy().ravel()
-    y_true = torch.cat(y_true).cpu().numpy().ravel()
-    idx = torch.cat(idx).cpu().numpy().ravel()
-    if not return_emb:
-        return y_pred, y_true, idx
-    import pandas as pd
-    frame = pd.DataFrame(torch.cat(embs).cpu().numpy())
-    frame["ddG_exp"] = y_true
-    frame["ddG_pred"] = y_pred
-    frame["index"] = idx
-    return y_pred, y_true, idx, frame
+            got.add(batch, out.reshape(1, -1), emb[None] if return_emb else None)
+    return got.results(return_emb)[0]
 
 
 def predict_networks(models, loader, return_emb: bool = False, device=None):
@@ -1470,28 +1458,10 @@ def predict_networks(models, loader, return_emb: bool = False, device=None):
         device = next(models[0].parameters()).device
     ens = EnsemblePredict(models)
     M = len(models)
-    y_pred, embs, y_true, idx = [], [], [], []
+    got = _Predictions()
     with torch.no_grad():
         for batch in loader:
             batch = batch.to(device)
             r = ens(batch, return_emb=return_emb, stats=False)
-            y_pred.append(r.out.reshape(M, -1).clone())
-            y_true.append(batch.y.reshape(-1))
-            idx.append(batch.idx.reshape(-1) if batch.idx is not None else torch.full((batch.num_graphs,), -1, device=r.out.device))
-            if return_emb:
-                embs.append(r.emb.clone())
-    y_pred = torch.cat(y_pred, 1).cpu().numpy()
-    y_true = torch.cat(y_true).cpu().numpy().ravel()
-    idx = torch.cat(idx).cpu().numpy().ravel()
-    if not return_emb:
-        return [(y_pred[k].ravel(), y_true, idx) for k in range(M)]
-    import pandas as pd
-    emb = torch.cat(embs, 1).cpu().numpy()
-    res = []
-    for k in range(M):
-        frame = pd.DataFrame(emb[k])
-        frame["ddG_exp"] = y_true
-        frame["ddG_pred"] = y_pred[k].ravel()
-        frame["index"] = idx
-        res.append((y_pred[k].ravel(), y_true, idx, frame))
-    return res
+            got.add(batch, r.out.reshape(M, -1).clone(), r.emb.clone() if return_emb else None)
+    return got.results(return_emb)

@@ -147,9 +147,8 @@ def test_epoch_window_equals_the_per_batch_loop(H):
     a, b = _cls_model(H, 25, 3, seed=6), _cls_model(H, 25, 3, seed=6)
     la = H.DeviceLoader(store, batch_size=40, shuffle=True, seed=11)
     lb = H.DeviceLoader(store, batch_size=40, shuffle=True, seed=11)
-    win = train.EpochWindow.build(a, la)
+    win = train.epoch_window_of(a, la, build=True)
     assert win is not None
-    la._hcg_epoch_window = ((id(a), la.batch_size, la.drop_last, len(la.store)), win)
     assert a.optimizer.steps_done() == 0
     va = [train.train_network(a, la, "cuda") for _ in range(2)]
     train.EPOCH_WINDOW = False
@@ -165,7 +164,7 @@ def test_epoch_window_equals_the_per_batch_loop(H):
 
 
 def test_eval_window_equals_the_batch_loop(H):
-    from hcatgnet_amd.train import FusedTrainStep, eval_network
+    from hcatgnet_amd.train import FusedTrainStep, eval_network, eval_window_of
     store = H.DeviceGraphStore(_cls_synth("REAL", 130, 3, seed=3).as_graph_list(), device="cuda")
     val = H.DeviceLoader(store, batch_size=40)
     m = _cls_model(H, 25, 3, R=4, seed=8)
@@ -175,7 +174,7 @@ def test_eval_window_equals_the_batch_loop(H):
         tot += float(st.evaluate(b)) * b.num_graphs
     want = tot / len(store)
     got = eval_network(m, val, "cuda")
-    assert getattr(val, "_hcg_eval_window", None) is not None
+    assert eval_window_of(m, val) is not None
     assert abs(got - want) <= 1e-6 * abs(want), (got, want)
 
 

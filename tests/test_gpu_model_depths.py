@@ -124,7 +124,7 @@ def test_real_batch_with_seven_conv_layers_keeps_the_autograd_loop(H):
     assert "jobs" in FusedTrainStep(m).reason(next(iter(loader)))
     losses = [train.train_network(m, loader, "cuda") for _ in range(2)]
     assert all(v == v and v > 0 for v in losses)
-    assert getattr(loader, "_hcg_epoch_window", (None, None))[1] is None
+    assert train.epoch_window_of(m, loader) is None
 
 
 def _torch_twin(rule, m):
@@ -217,9 +217,8 @@ def test_epoch_window_equals_the_per_batch_loop(H, R, n_conv):
     a, b = _model(H, 25, R=R, n_conv=n_conv, seed=6), _model(H, 25, R=R, n_conv=n_conv, seed=6)
     la = H.DeviceLoader(store, batch_size=40, shuffle=True, seed=11)
     lb = H.DeviceLoader(store, batch_size=40, shuffle=True, seed=11)
-    win = train.EpochWindow.build(a, la)
+    win = train.epoch_window_of(a, la, build=True)
     assert win is not None
-    la._hcg_epoch_window = ((id(a), la.batch_size, la.drop_last, len(la.store)), win)
     assert a.optimizer.steps_done() == 0
     va = [train.train_network(a, la, "cuda") for _ in range(3)]
     train.EPOCH_WINDOW = False
@@ -251,7 +250,7 @@ def test_train_networks_over_mixed_depths_equals_the_runs_one_by_one(H):
 
 
 def test_eval_window_equals_the_batch_loop(H):
-    from hcatgnet_amd.train import FusedTrainStep, eval_network
+    from hcatgnet_amd.train import FusedTrainStep, eval_network, eval_window_of
     store = H.DeviceGraphStore(_synth("REAL", 130, seed=3).as_graph_list(), device="cuda")
     val = H.DeviceLoader(store, batch_size=40)
     m = _model(H, 25, R=4, n_conv=4, seed=8)
@@ -261,7 +260,7 @@ def test_eval_window_equals_the_batch_loop(H):
         tot += float(st.evaluate(b)) * b.num_graphs
     want = tot / len(store)
     got = eval_network(m, val, "cuda")
-    assert getattr(val, "_hcg_eval_window", None) is not None
+    assert eval_window_of(m, val) is not None
     assert abs(got - want) <= 1e-6 * abs(want), (got, want)
 
 

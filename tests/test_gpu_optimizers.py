@@ -322,15 +322,14 @@ def test_epoch_window_equals_the_per_batch_loop_on_the_same_permutations(H, rule
     fl = a.optimizer._flat[0]
     before = [t.clone() for t in [fl["p"]] + a.optimizer.flat_state(fl)]
     assert len(before) == (2 if rule == "rmsprop" else 1)
-    win = train.EpochWindow.build(a, la)
+    win = train.epoch_window_of(a, la, build=True)
     assert win is not None, "the epoch window must apply to SGD / RMSprop"
-    la._hcg_epoch_window = ((id(a), la.batch_size, la.drop_last, len(la.store)), win)
     fl = a.optimizer._flat[0]
     for x, y in zip([fl["p"]] + a.optimizer.flat_state(fl), before):
         assert torch.equal(x, y)                               # the capture's warm-up epoch was undone
     assert a.optimizer.steps_done() == len(la)
     va = [train.train_network(a, la, "cuda") for _ in range(4)]
-    assert la._hcg_epoch_window[1] is not None
+    assert train.epoch_window_of(a, la) is win
     train.EPOCH_WINDOW = False
     try:
         vb = [train.train_network(b, lb, "cuda") for _ in range(4)]
@@ -360,7 +359,7 @@ def test_concurrent_runs_of_mixed_rules_equal_the_runs_one_by_one(H):
     """train_networks over Adam, SGD and RMSprop runs: every run's epoch is its own one-graph epoch, and each run is bitwise
     what train_network gives it alone."""
     from hcatgnet_amd import synth
-    from hcatgnet_amd.train import train_network, train_networks
+    from hcatgnet_amd.train import epoch_window_of, train_network, train_networks
     rules = ["Adam", "SGD", "rmsprop"]
     sizes = [135, 100, 121]
 
@@ -379,7 +378,7 @@ def test_concurrent_runs_of_mixed_rules_equal_the_runs_one_by_one(H):
         for k, (m, trn) in enumerate(alone):
             assert tv[k] == train_network(m, trn, "cuda"), (rules[k], tv[k])
     for k, ((ma, ta), (mb, tb)) in enumerate(zip(together, alone)):
-        assert getattr(ta, "_hcg_epoch_window", (None, None))[1] is not None, rules[k]     # the one-graph form ran
+        assert epoch_window_of(ma, ta) is not None, rules[k]     # the one-graph form ran
         for q, r in zip(ma.parameters(), mb.parameters()):
             assert torch.equal(q, r), rules[k]
 

@@ -755,6 +755,36 @@ def test_device_collate_equals_host_collate_and_feeds_the_model(H):
             assert sorted(seen) == [1000 + i for i in range(37)]
 
 
+def test_plans_built_three_ways_set_every_slot(H):
+    """`BatchPlan.build`, `DeviceGraphStore.collate` and a slot of an `EpochWindow` all leave a plan with EVERY slot set;
+    the two trusted ones (`BatchPlan.from_pointers`) are blocked, pointers only, on the shared status word."""
+    from hcatgnet_amd import train
+    g = torch.Generator().manual_seed(3)
+    graphs = [H.Data(x=torch.randn(n, 5, generator=g), edge_index=torch.randint(0, n, (2, 2 * n), generator=g),
+                     y=torch.randn(1, generator=g), idx=i) for i, n in enumerate([3, 9, 4, 7, 5, 6])]
+    store = H.DeviceGraphStore(graphs, "cuda")
+    cb = store.collate(range(6))
+    built = H.BatchPlan.build(cb.edge_index, cb.batch, cb.x.shape[0], num_graphs=6, mode="blocked", validate=False)
+    m = H.make_network("GCN", H.default_options(), 5).cuda()
+    win = train.EpochWindow(m, H.DeviceLoader(store, batch_size=4))
+    plans = {"build": built, "collate": cb._hcg_plan, "epoch": win.batches[0]._hcg_plan}
+    for name, plan in plans.items():
+        for slot in H.BatchPlan.__slots__:
+            getattr(plan, slot)                              # (an unset slot raises AttributeError)
+    assert torch.equal(plans["collate"].graph_ptr, built.graph_ptr) and torch.equal(plans["collate"].edge_ptr, built.edge_ptr)
+    assert built.graph_ptr.cpu().tolist() == [0, 3, 12, 16, 23, 28, 34]
+    unset = ("edge_weight", "rowptr", "col", "eid", "rowptr_t", "col_t", "eid_t", "dinv", "ew_csr", "ew_csc", "dinv_unw")
+    for name in ("collate", "epoch"):
+        plan = plans[name]
+        assert (plan.fill, plan.mode, plan.validated, plan.has_csr) == (1.0, "blocked", True, False), name
+        assert plan.shared_status is True and plan.want_eid is False and plan.status is built.status, name
+        assert all(getattr(plan, slot) is None for slot in unset), name
+    assert (plans["collate"].N, plans["collate"].E, plans["collate"].B) == (34, 68, 6)
+    assert (plans["collate"].max_nodes, plans["collate"].max_edges) == (9, 18)
+    first = plans["epoch"]                                   # capacity shape: the 4 largest graphs of the dataset
+    assert (first.N, first.E, first.B, first.max_nodes, first.max_edges) == (9 + 7 + 6 + 5, 18 + 14 + 12 + 10, 4, 9, 18)
+
+
 @pytest.mark.parametrize("apply_sigmoid", [True, False])
 def test_explain_masks_forward_and_mask_gradients(H, oracle, apply_sigmoid):
     """explain-mode hooks.  Edge mask multiplied into every message of every conv layer (PyG Explainer

@@ -207,7 +207,7 @@ def test_eval_network_window_equals_the_batch_loop(H):
     after the optimiser has re-based the parameters (the window is rebuilt), and after further epochs (the graph reads the
     live weights); a shuffling loader keeps the loop."""
     from hcatgnet_amd import synth
-    from hcatgnet_amd.train import FusedTrainStep, eval_network, train_network
+    from hcatgnet_amd.train import FusedTrainStep, eval_network, eval_window_of, train_network
     sb = synth.make_config("REAL", num_graphs=130)
     store = H.DeviceGraphStore(sb.as_graph_list(), device="cuda")
     val = H.DeviceLoader(store, batch_size=40)
@@ -223,11 +223,11 @@ def test_eval_network_window_equals_the_batch_loop(H):
     for phase in range(3):
         got, want = eval_network(m, val, "cuda"), loop_value()
         assert abs(got - want) <= 1e-6 * abs(want), (phase, got, want)
-        assert getattr(val, "_hcg_eval_window", None) is not None
+        assert eval_window_of(m, val) is not None
         train_network(m, trn, "cuda")
-    assert getattr(trn, "_hcg_eval_window", None) is None
+    assert eval_window_of(m, trn) is None
     v = eval_network(m, trn, "cuda")                      # shuffling loader: the loop, no window
-    assert getattr(trn, "_hcg_eval_window", None) is None and v > 0
+    assert eval_window_of(m, trn) is None and v > 0
 
 
 @pytest.mark.parametrize("cfg,feat,G,bs", [("REAL", 25, 135, 40), ("C2", 64, 100, 32)])
@@ -245,9 +245,8 @@ def test_epoch_window_equals_the_per_batch_loop_on_the_same_permutations(H, cfg,
     b.load_state_dict(a.state_dict())
     la, lb = H.DeviceLoader(store, batch_size=bs, shuffle=True, seed=11), H.DeviceLoader(store, batch_size=bs, shuffle=True, seed=11)
     before = [q.detach().clone() for q in a.parameters()]
-    win = train.EpochWindow.build(a, la)
+    win = train.epoch_window_of(a, la, build=True)
     assert win is not None, "the epoch window must apply to the reference's own regime"
-    la._hcg_epoch_window = ((id(a), la.batch_size, la.drop_last, len(la.store)), win)
     assert all(torch.equal(q, r) for q, r in zip(a.parameters(), before))          # the capture's warm-up epoch was undone
     assert a.optimizer.steps_done() == 0
     va = [train.train_network(a, la, "cuda") for _ in range(4)]
@@ -282,7 +281,7 @@ def test_concurrent_runs_equal_the_runs_one_by_one(H):
     weights after three epochs -- with different datasets, sizes and seeds per run, one run switched off for an epoch (early
     stopping) and one run over a host loader (no window: trained in turn)."""
     from hcatgnet_amd import synth
-    from hcatgnet_amd.train import eval_network, eval_networks, train_network, train_networks
+    from hcatgnet_amd.train import epoch_window_of, eval_network, eval_networks, train_network, train_networks
     K = 4
     sizes = [135, 100, 121, 90]
 
@@ -313,7 +312,7 @@ def test_concurrent_runs_equal_the_runs_one_by_one(H):
     for (ma, _, _), (mb, _, _) in zip(together, alone):
         for q, r in zip(ma.parameters(), mb.parameters()):
             assert torch.equal(q, r)
-    assert getattr(together[0][1], "_hcg_epoch_window", (None, None))[1] is not None     # the one-graph form did run
+    assert epoch_window_of(together[0][0], together[0][1]) is not None     # the one-graph form did run
     with pytest.raises(ValueError):
         train_networks([together[0][0]], [], "cuda")
 

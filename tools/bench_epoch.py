@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import hcatgnet_amd as H
 from hcatgnet_amd import synth
+from hcatgnet_amd import train as _train
 from hcatgnet_amd.train import train_network, eval_network
 from oracle import gcn_oracle
 ap = argparse.ArgumentParser()
@@ -51,8 +52,7 @@ for _ in range(EP):
     loss = train_network(model, loader, "cuda")
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / EP
 print(f"MI355X  train_network: {dt * 1e3:8.2f} ms/epoch ({len(loader)} batches of {BS}; {G / dt:10.0f} graphs/s), last epoch loss {loss:.4f}"
-      f"  [whole epochs as one hipGraph: {getattr(loader, '_hcg_epoch_window', (None, None))[1] is not None}]")
-from hcatgnet_amd import train as _train
+      f"  [whole epochs as one hipGraph: {_train.epoch_window_of(model, loader) is not None}]")
 _train.EPOCH_WINDOW = False
 loader_b = H.DeviceLoader(store, batch_size=BS, shuffle=True, seed=0)
 model_b = H.make_network("GCN", H.default_options(optimizer=OPT, **DEPTH), 25).cuda()      # (its own model: the window's 14 trainers stay out of the way)

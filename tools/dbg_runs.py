@@ -17,7 +17,7 @@ for k in range(K):
 ms, lds = [r[0] for r in runs], [r[1] for r in runs]
 for _ in range(3):
     train.train_networks(ms, lds, "cuda")
-wins = [ld._hcg_epoch_window[1] for ld in lds]
+wins = [train.epoch_window_of(m, ld) for m, ld in runs]
 streams = [m._hcg_run_stream for m in ms]
 gc.collect(); gc.freeze()
 EP = 20
