@@ -38,6 +38,7 @@
 #include "split_mfma.h"
 #include "head_tile.h"
 #include "pair_query.h"
+#include "launch.h"
 
 // Diagnostic builds only (tools/probe_fused.hip defines HCG_STAMP): s_memtime stamps of a few waves go to
 // a buffer of their own; the product build compiles STAMP() to nothing and executes no stamp.
@@ -1243,16 +1244,43 @@ __global__ __launch_bounds__(WAVES * 64, 2) void k_fused_bwd_pair(const BwdPairA
                                                           nullptr, partials0, a.status);
 }
 
-int pick_grid(int num_tiles) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  int grid = (num_tiles + WAVES - 1) / WAVES;
-  if (grid > cus) grid = cus;
-  return grid < 1 ? 1 : grid;
+int pick_grid(int num_tiles) { return hcg_grid((num_tiles + WAVES - 1) / WAVES, hcg_cu_count()); }
+
+// The launch geometry of the tiles, derived HERE and nowhere else: what a workspace is sized by is what a launch indexes
+// by.  Valid for graphs_per_tile >= 1 (every caller refuses anything else first).
+struct TilesGeo {
+  int kpad;                 // K padding of the F input columns
+  int tiles, grid;          // 32-row tiles of the batch; workgroups of a launch
+  int slabs;                // slabs a backward leaves: one per workgroup, none for an empty batch
+  int slab_floats;          // dW [64][kpad] | db [64]
+  bool vec;                 // x rows are whole, aligned float4
+  bool deal;                // a partial last round is dealt evenly over the workgroups (TileSeq); whole rounds keep the plain form
+  size_t head_ws_bytes;     // the head in the forward's tail: one slab (gradient partial sums + SSE partial) per workgroup
+};
+TilesGeo tiles_geo(int64_t N, int64_t B, int64_t F, int graphs_per_tile, const void* x) {
+  TilesGeo g{};
+  g.kpad = hcg_kpad(F);
+  g.tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
+  g.grid = pick_grid(g.tiles);
+  g.slabs = (N > 0 && B > 0) ? g.grid : 0;
+  g.slab_floats = hcg_dw_db_slab_floats(DD, g.kpad);
+  g.vec = (F == 64 || F == 32) && ((uintptr_t)x % 16 == 0);
+  g.deal = g.tiles % (g.grid * WAVES) != 0 && g.tiles > g.grid * WAVES;
+  g.head_ws_bytes = B > 0 ? hcg_align_up((size_t)g.grid * (hcg_head::HC<DD>::SLAB + 1) * sizeof(float), 256) + 256 : 0;
+  return g;
 }
+
+// The forward's forms: one or two stacked conv layers, [max, mean] pooling of the last one, the training form of the pooled
+// layer (activations stay on chip, 2 bits per element leave), the readout head in the launch's tail (1: forward, 2: + backward)
+struct TilesFwdForm { bool pool, stack2, bits; int head; };
+constexpr TilesFwdForm TILES_FWD_FORMS[8] = {
+    {false, false, false, 0}, {true, false, false, 0}, {false, true, false, 0}, {true, true, false, 0},   // 2 stack2 + pooled
+    {true, false, true, 0},   {true, true, true, 0},                                                      // 4 + stack2
+    {true, true, true, 1},    {true, true, true, 2}};                                                     // 6 + head backward
+// The backward's forms of the upstream gradient: per node, pooled, pooled from the forward's bit form
+struct TilesBwdForm { bool poolg, bits; };
+constexpr TilesBwdForm TILES_BWD_FORMS[3] = {{false, false}, {true, false}, {true, true}};
+int tiles_bwd_form(bool poolg, bool bits) { return bits ? 2 : (poolg ? 1 : 0); }
 
 }  // namespace
 
@@ -1264,25 +1292,17 @@ extern "C" int hcg_fused_graphs_per_tile(int64_t F, int64_t D, int64_t max_nodes
 
 extern "C" size_t hcg_fused_workspace_bytes(int64_t B, int64_t F, int64_t D, int graphs_per_tile) {
   if (graphs_per_tile <= 0) return 0;
-  const int kpad = F <= 32 ? 32 : 64;
-  const int tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
-  return (size_t)pick_grid(tiles) * (DD * kpad + DD) * sizeof(float) + 256;
-}
-
-// workspace of the head in the forward's tail: one slab (gradient partial sums + SSE partial) per workgroup of the launch
-static size_t fused_head_workspace_bytes(int64_t B, int graphs_per_tile) {
-  if (graphs_per_tile <= 0 || B <= 0) return 0;
-  const int tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
-  return hcg_align_up((size_t)pick_grid(tiles) * (hcg_head::HC<DD>::SLAB + 1) * sizeof(float), 256) + 256;
+  const TilesGeo g = tiles_geo(1, B, F, graphs_per_tile, nullptr);
+  return (size_t)g.grid * g.slab_floats * sizeof(float) + 256;
 }
 
 extern "C" int hcg_fused_head_reduce_job(const void* workspace, size_t workspace_bytes, int64_t B, int graphs_per_tile, int64_t C,
                                          float* dW0, float* db0, float* dW1, float* db1, hcg_reduce_job* job) {
   if (B <= 0 || graphs_per_tile < 1 || C < 1 || C > hcg_head::RCMAX || !job || !workspace) return HCG_ERR_INVALID_ARG;
   if (dW0 && (!db0 || !dW1 || !db1)) return HCG_ERR_INVALID_ARG;
-  if (workspace_bytes < fused_head_workspace_bytes(B, graphs_per_tile)) return HCG_ERR_WORKSPACE;
-  const int tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
-  hcg_head::head_fill_job<DD>((const float*)workspace, pick_grid(tiles), (int)C, dW0, db0, dW1, db1, job);
+  const TilesGeo g = tiles_geo(1, B, DD, graphs_per_tile, nullptr);
+  if (workspace_bytes < g.head_ws_bytes) return HCG_ERR_WORKSPACE;
+  hcg_head::head_fill_job<DD>((const float*)workspace, g.grid, (int)C, dW0, db0, dW1, db1, job);
   return HCG_OK;
 }
 
@@ -1307,7 +1327,7 @@ extern "C" int hcg_fused_forward(const hcg_fused_fwd_args* a, hcg_stream_t strea
   const bool bits = poolbits != nullptr;   // the pooled layer's activations stay on chip (training form)
   const bool head = a->head_W0 != nullptr;
   if (D != DD || F < 1 || F > 64 || graphs_per_tile < 1) return HCG_ERR_UNSUPPORTED;
-  if (a->apply_act && !(a->slope >= 0.f && a->slope <= 1.f)) return HCG_ERR_UNSUPPORTED;  // LeakyReLU is evaluated as max(v, slope*v)
+  if (!hcg_slope_ok(a->apply_act, a->slope)) return HCG_ERR_UNSUPPORTED;
   if (N < 0 || B < 0 || E < 0) return HCG_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return head ? HCG_ERR_INVALID_ARG : HCG_OK;
   if (!x || !W || !b || !a->graph_ptr || !a->edge_ptr || !a->status || (E > 0 && !edge_index)) return HCG_ERR_INVALID_ARG;
@@ -1317,6 +1337,7 @@ extern "C" int hcg_fused_forward(const hcg_fused_fwd_args* a, hcg_stream_t strea
   } else {
     if (out2 || (!out && !bits)) return HCG_ERR_INVALID_ARG;
   }
+  const TilesGeo g = tiles_geo(N, B, F, graphs_per_tile, x);
   const bool head_bwd = head && !(a->head_flags & HCG_HEAD_FORWARD_ONLY);
   FwdHead H{};
   if (head) {
@@ -1325,46 +1346,30 @@ extern "C" int hcg_fused_forward(const hcg_fused_fwd_args* a, hcg_stream_t strea
     if (a->C < 1 || a->C > hcg_head::RCMAX) return HCG_ERR_UNSUPPORTED;
     if (!a->y || !a->head_b0 || !a->head_W1 || !a->head_b1 || !a->z || !a->out || (head_bwd && !a->demb) || !a->head_workspace)
       return HCG_ERR_INVALID_ARG;
-    if (a->head_workspace_bytes < fused_head_workspace_bytes(B, graphs_per_tile)) return HCG_ERR_WORKSPACE;
+    if (a->head_workspace_bytes < g.head_ws_bytes) return HCG_ERR_WORKSPACE;
     H = FwdHead{a->y, a->head_W0, a->head_b0, a->head_W1, a->head_b1, (int)a->C, a->z, a->out, a->demb, (float*)a->head_workspace,
                 (int*)a->step_counter};
   }
-  const int tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
-  const int grid = pick_grid(tiles);
-  const bool vec = (F == 64 || F == 32) && ((uintptr_t)x % 16 == 0);
-  const dim3 g(grid), blk(WAVES * 64);
-  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(a->graph_ptr); E = 1; }  // readable dummy; no tile has edges
-  // a partial last round is dealt evenly over the workgroups (TileSeq); whole rounds keep the plain form
-  const bool deal = tiles % (grid * WAVES) != 0 && tiles > grid * WAVES;
-#define LAUNCH_FWD_D(KP, VC, PL, ST, BT, HD, DL)                                                                           \
-  hipLaunchKernelGGL((k_fused_layer_fwd<KP, VC, PL, ST, BT, HD, DL>), g, blk, 0, stream, x, (int)F, W, b, W2, b2, edge_index, \
-                     E, a->graph_ptr, a->edge_ptr, N, graphs_per_tile, (int)B, tiles, a->slope, a->apply_act, out, out2, \
-                     emb, poolbits, a->status, H)
-#define LAUNCH_FWD(KP, VC, PL, ST, BT, HD)                                                                               \
-  do { if (deal) LAUNCH_FWD_D(KP, VC, PL, ST, BT, HD, true); else LAUNCH_FWD_D(KP, VC, PL, ST, BT, HD, false); } while (0)
-#define DISPATCH_FWD(KP, VC)                                                                                     \
-  do {                                                                                                           \
-    if (head)        { if (head_bwd) LAUNCH_FWD(KP, VC, true, true, true, 2); else LAUNCH_FWD(KP, VC, true, true, true, 1); } \
-    else if (bits)   { if (stack2) LAUNCH_FWD(KP, VC, true, true, true, 0); else LAUNCH_FWD(KP, VC, true, false, true, 0); } \
-    else if (stack2) { if (emb) LAUNCH_FWD(KP, VC, true, true, false, 0); else LAUNCH_FWD(KP, VC, false, true, false, 0); }  \
-    else             { if (emb) LAUNCH_FWD(KP, VC, true, false, false, 0); else LAUNCH_FWD(KP, VC, false, false, false, 0); } \
-  } while (0)
-  if (F <= 32) { if (vec) DISPATCH_FWD(32, true); else DISPATCH_FWD(32, false); }
-  else         { if (vec) DISPATCH_FWD(64, true); else DISPATCH_FWD(64, false); }
-#undef DISPATCH_FWD
-#undef LAUNCH_FWD
-#undef LAUNCH_FWD_D
-  HCG_CHECK_LAUNCH();
-  return HCG_OK;
+  hcg_edge_dummy(edge_index, E, a->graph_ptr);
+  const int form = head ? 6 + head_bwd : (bits ? 4 + stack2 : 2 * stack2 + (emb != nullptr));
+  return hcg_with_index<8>(form, [&](auto I) {
+    constexpr TilesFwdForm f = TILES_FWD_FORMS[decltype(I)::value];
+    return hcg_with_bools([&](auto K64, auto VEC, auto DEAL) {
+      return hcg_launch<k_fused_layer_fwd<(K64 ? 64 : 32), VEC, f.pool, f.stack2, f.bits, f.head, DEAL>>(
+          dim3(g.grid), dim3(WAVES * 64), 0, 0, stream, x, (int)F, W, b, W2, b2, edge_index, E, a->graph_ptr, a->edge_ptr, N,
+          graphs_per_tile, (int)B, g.tiles, a->slope, a->apply_act, out, out2, emb, poolbits, a->status, H);
+    }, g.kpad == 64, g.vec, g.deal);
+  });
 }
 
 // kind HCG_FUSED_POOLBITS: 2 bits per element of the pooled layer (training forms, see k_fused_layer_fwd<BITS>);
 // kind HCG_FUSED_HEAD_WS: the head-in-the-forward's slabs + SSE partials
 extern "C" size_t hcg_fused_aux_bytes(int kind, int64_t B, int graphs_per_tile) {
   if (graphs_per_tile <= 0 || B <= 0) return 0;
-  if (kind == HCG_FUSED_HEAD_WS) return fused_head_workspace_bytes(B, graphs_per_tile);
+  const TilesGeo g = tiles_geo(1, B, DD, graphs_per_tile, nullptr);
+  if (kind == HCG_FUSED_HEAD_WS) return g.head_ws_bytes;
   if (kind != HCG_FUSED_POOLBITS) return 0;
-  return (size_t)((B + graphs_per_tile - 1) / graphs_per_tile) * 128 * sizeof(uint32_t);
+  return (size_t)g.tiles * 128 * sizeof(uint32_t);
 }
 
 static int launch_fused_bwd(const float* dout, const float* demb, const float* emb, const float* out,
@@ -1381,45 +1386,21 @@ static int launch_fused_bwd(const float* dout, const float* demb, const float* e
     out = x;    // (never read; keeps the pointer checks below uniform)
     emb = demb;
   }
-  if (poolg && (!demb || !emb)) return HCG_ERR_INVALID_ARG;
-  if (apply_act & ~3) return HCG_ERR_INVALID_ARG;
-  if ((apply_act & 2) && !dx) return HCG_ERR_INVALID_ARG;
-  // `out` is only read for the activation derivative and the pooled-gradient routing
-  if (N > 0 && B > 0 && (((poolg || (apply_act & 1)) && !out) || !x || !graph_ptr || !edge_ptr || !status || (E > 0 && !edge_index)))
-    return HCG_ERR_INVALID_ARG;
-  if (!poolg && !(apply_act & 1)) out = nullptr;
-  const int kpad = F <= 32 ? 32 : 64;
-  const int tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
-  const int grid = (N > 0 && B > 0) ? pick_grid(tiles) : 0;
-  const size_t slab = (size_t)(DD * kpad + DD);
-  if (workspace_bytes < (size_t)grid * slab * sizeof(float)) return HCG_ERR_WORKSPACE;
-  float* partials = (float*)workspace;
-  if (grid > 0) {
-    const bool vec = (F == 64 || F == 32) && ((uintptr_t)x % 16 == 0);
-    const bool ndx = dx != nullptr;
-    const dim3 g(grid), blk(WAVES * 64);
-    if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(graph_ptr); E = 1; }  // readable dummy
-    const bool deal = tiles % (grid * WAVES) != 0 && tiles > grid * WAVES;     // (as the forward: TileSeq)
-#define LAUNCH_BWD_D(KP, VC, DX, PG, BT, DL)                                                                          \
-  hipLaunchKernelGGL((k_fused_layer_bwd<KP, VC, DX, PG, BT, DL>), g, blk, 0, stream, dout, demb, emb, out, poolbits, x, \
-                     (int)F, W, edge_index, E, graph_ptr, edge_ptr, N, graphs_per_tile, (int)B, tiles, slope, apply_act, \
-                     dx, partials, status)
-#define LAUNCH_BWD(KP, VC, DX, PG, BT)                                                                                \
-  do { if (deal) LAUNCH_BWD_D(KP, VC, DX, PG, BT, true); else LAUNCH_BWD_D(KP, VC, DX, PG, BT, false); } while (0)
-#define DISPATCH_BWD(KP, VC)                                                                                   \
-  do {                                                                                                         \
-    if (bits)     { if (ndx) LAUNCH_BWD(KP, VC, true, true, true); else LAUNCH_BWD(KP, VC, false, true, true); }   \
-    else if (ndx) { if (poolg) LAUNCH_BWD(KP, VC, true, true, false); else LAUNCH_BWD(KP, VC, true, false, false); } \
-    else          { if (poolg) LAUNCH_BWD(KP, VC, false, true, false); else LAUNCH_BWD(KP, VC, false, false, false); } \
-  } while (0)
-    if (kpad == 32) { if (vec) DISPATCH_BWD(32, true); else DISPATCH_BWD(32, false); }
-    else            { if (vec) DISPATCH_BWD(64, true); else DISPATCH_BWD(64, false); }
-#undef DISPATCH_BWD
-#undef LAUNCH_BWD
-#undef LAUNCH_BWD_D
-    HCG_CHECK_LAUNCH();
-  }
-  return HCG_OK;
+  const TilesGeo g = tiles_geo(N, B, F, graphs_per_tile, x);
+  HCG_TRY(hcg_bwd_form_check(poolg, demb, emb, apply_act, dx, out || g.slabs == 0));
+  if (g.slabs > 0 && (!x || !graph_ptr || !edge_ptr || !status || (E > 0 && !edge_index))) return HCG_ERR_INVALID_ARG;
+  if (!hcg_bwd_reads_out(poolg, apply_act)) out = nullptr;
+  if (workspace_bytes < (size_t)g.slabs * g.slab_floats * sizeof(float)) return HCG_ERR_WORKSPACE;
+  if (g.slabs == 0) return HCG_OK;
+  hcg_edge_dummy(edge_index, E, graph_ptr);
+  return hcg_with_index<3>(tiles_bwd_form(poolg, bits), [&](auto I) {
+    constexpr TilesBwdForm f = TILES_BWD_FORMS[decltype(I)::value];
+    return hcg_with_bools([&](auto K64, auto VEC, auto DX, auto DEAL) {
+      return hcg_launch<k_fused_layer_bwd<(K64 ? 64 : 32), VEC, DX, f.poolg, f.bits, DEAL>>(
+          dim3(g.grid), dim3(WAVES * 64), 0, 0, stream, dout, demb, emb, out, poolbits, x, (int)F, W, edge_index, E, graph_ptr,
+          edge_ptr, N, graphs_per_tile, (int)B, g.tiles, slope, apply_act, dx, (float*)workspace, status);
+    }, g.kpad == 64, g.vec, dx != nullptr, g.deal);
+  });
 }
 
 // `poolbits` != NULL: pooled backward of a layer whose forward ran in the training form (poolbits stand in for out / emb;
@@ -1438,8 +1419,6 @@ extern "C" int hcg_fused_layer_bwd(const float* dout, const float* demb, const f
 // x, W1, output out1) and D -> D (upper: input out1, W2), in ONE launch (k_fused_bwd_pair).  The block's fields keep their
 // forward meaning; the upper layer takes the three forms of hcg_fused_layer_bwd.
 static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream) {
-  const int64_t N = a->N, B = a->B, F = a->F;
-  const int gpt = a->graphs_per_tile;
   // ALL validation of the block -- flags, shapes, alignment, every pointer the kernel dereferences except the two workspaces
   // checked below -- is hcg_bwd_pair_applies (pair_query.h); a -DHCG_NO_BWD_PAIR build answers unsupported there
   const int rc = hcg_bwd_pair_applies(a, DD);
@@ -1448,21 +1427,19 @@ static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream
   const bool poolg = bits || a->pair_dout == nullptr;
   if (a->pair_flags & HCG_FUSED_PAIR_QUERY) return HCG_OK;
   if (!a->pair_ws_upper || !a->pair_ws_lower) return HCG_ERR_INVALID_ARG;
-  const int kpad0 = F <= 32 ? 32 : 64;
-  const int tiles = (int)((B + gpt - 1) / gpt);
-  const int grid = (N > 0 && B > 0) ? pick_grid(tiles) : 0;
-  if (a->pair_ws_upper_bytes < (size_t)grid * (DD * DD + DD) * sizeof(float) ||
-      a->pair_ws_lower_bytes < (size_t)grid * (DD * kpad0 + DD) * sizeof(float))
+  const TilesGeo g = tiles_geo(a->N, a->B, a->F, a->graphs_per_tile, a->x);     // (the lower layer's; both walk the same tiles)
+  if (a->pair_ws_upper_bytes < (size_t)g.slabs * hcg_dw_db_slab_floats(DD, DD) * sizeof(float) ||
+      a->pair_ws_lower_bytes < (size_t)g.slabs * g.slab_floats * sizeof(float))
     return HCG_ERR_WORKSPACE;
-  if (grid == 0) return HCG_OK;
+  if (g.slabs == 0) return HCG_OK;
   const int64_t* edge_index = a->edge_index;
   int64_t E = a->E;
-  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(a->graph_ptr); E = 1; }  // readable dummy
+  hcg_edge_dummy(edge_index, E, a->graph_ptr);
   BwdPairArgs k{};
   k.dout = poolg ? nullptr : a->pair_dout;
   k.demb = a->demb;
   k.emb = bits ? a->demb : a->emb;                    // (bits: never read)
-  k.a_out = (poolg || (a->pair_act_upper & 1)) ? (bits ? a->out1 : a->out2) : nullptr;
+  k.a_out = hcg_bwd_reads_out(poolg, a->pair_act_upper) ? (bits ? a->out1 : a->out2) : nullptr;
   k.poolbits = a->poolbits;
   k.x = a->out1;
   k.W = a->W2;
@@ -1470,10 +1447,10 @@ static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream
   k.E = E;
   k.graph_ptr = a->graph_ptr;
   k.edge_ptr = a->edge_ptr;
-  k.N = N;
-  k.gpt = gpt;
-  k.B = (int)B;
-  k.num_tiles = tiles;
+  k.N = a->N;
+  k.gpt = a->graphs_per_tile;
+  k.B = (int)a->B;
+  k.num_tiles = g.tiles;
   k.slope = a->slope;
   k.apply_act = a->pair_act_upper;
   k.dx = a->pair_dx;
@@ -1481,44 +1458,21 @@ static int launch_fused_bwd_pair(const hcg_fused_fwd_args* a, hipStream_t stream
   k.status = a->status;
   k.x0 = a->x;
   k.partials0 = (float*)a->pair_ws_lower;
-  k.F0 = (int)F;
-  const bool vec0 = (F == 64 || F == 32) && ((uintptr_t)a->x % 16 == 0);
-  const bool deal = tiles % (grid * WAVES) != 0 && tiles > grid * WAVES;     // (as the single launches: TileSeq)
-  const dim3 g(grid), blk(WAVES * 64);
-#define LAUNCH_PAIR_D(PG, BT, KP, VC, DL) hipLaunchKernelGGL((k_fused_bwd_pair<PG, BT, KP, VC, DL>), g, blk, 0, stream, k)
-#define LAUNCH_PAIR(PG, BT, KP, VC) \
-  do { if (deal) LAUNCH_PAIR_D(PG, BT, KP, VC, true); else LAUNCH_PAIR_D(PG, BT, KP, VC, false); } while (0)
-#define DISPATCH_PAIR(KP, VC)                                                  \
-  do {                                                                         \
-    if (bits) LAUNCH_PAIR(true, true, KP, VC);                                 \
-    else if (poolg) LAUNCH_PAIR(true, false, KP, VC);                          \
-    else LAUNCH_PAIR(false, false, KP, VC);                                    \
-  } while (0)
-  if (kpad0 == 32) { if (vec0) DISPATCH_PAIR(32, true); else DISPATCH_PAIR(32, false); }
-  else             { if (vec0) DISPATCH_PAIR(64, true); else DISPATCH_PAIR(64, false); }
-#undef DISPATCH_PAIR
-#undef LAUNCH_PAIR
-#undef LAUNCH_PAIR_D
-  HCG_CHECK_LAUNCH();
-  return HCG_OK;
+  k.F0 = (int)a->F;
+  return hcg_with_index<3>(tiles_bwd_form(poolg, bits), [&](auto I) {
+    constexpr TilesBwdForm f = TILES_BWD_FORMS[decltype(I)::value];
+    return hcg_with_bools([&](auto K64, auto VEC, auto DEAL) {
+      return hcg_launch<k_fused_bwd_pair<f.poolg, f.bits, (K64 ? 64 : 32), VEC, DEAL>>(dim3(g.grid), dim3(WAVES * 64), 0, 0, stream, k);
+    }, g.kpad == 64, g.vec, g.deal);
+  });
 }
 
 // host-side description of this layer's slab set for hcg_step_tail (no launch)
 extern "C" int hcg_fused_reduce_job(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F, int64_t D,
                                     int graphs_per_tile, float* dW, float* db, hcg_reduce_job* job) {
   if (D != DD || F < 1 || F > 64 || graphs_per_tile < 1 || !dW || !db || !job || !workspace) return HCG_ERR_INVALID_ARG;
-  const int kpad = F <= 32 ? 32 : 64;
-  const int tiles = (int)((B + graphs_per_tile - 1) / graphs_per_tile);
-  const int grid = (N > 0 && B > 0) ? pick_grid(tiles) : 0;
-  const int slab_floats = DD * kpad + DD;
-  if (workspace_bytes < (size_t)grid * slab_floats * sizeof(float)) return HCG_ERR_WORKSPACE;
-  job->slabs = (const float*)workspace;
-  job->nslabs = grid;
-  job->slab_floats = slab_floats;
-  job->nseg = 2;
-  job->sse_part = nullptr;
-  job->reserved = 0;
-  job->seg[0] = hcg_reduce_seg{0, DD * kpad, kpad, (int32_t)F, dW};
-  job->seg[1] = hcg_reduce_seg{DD * kpad, DD, 1, 1, db};
+  const TilesGeo g = tiles_geo(N, B, F, graphs_per_tile, nullptr);
+  if (workspace_bytes < (size_t)g.slabs * g.slab_floats * sizeof(float)) return HCG_ERR_WORKSPACE;
+  hcg_fill_job_dw_db(job, (const float*)workspace, g.slabs, DD, g.kpad, F, dW, db);
   return HCG_OK;
 }

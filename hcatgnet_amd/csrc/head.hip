@@ -7,6 +7,7 @@
 // (head_tile.h: the loss scale is deferred to the step's last launch), so the grid is simply min(tiles, CUs).
 #include "common.h"
 #include "head_tile.h"
+#include "launch.h"
 
 namespace {
 using namespace hcg_head;
@@ -61,18 +62,7 @@ __global__ __launch_bounds__(hcg_head16::NT, 1) void k_head16(const float* __res
 }
 
 // min(tiles of rt graphs, CUs)
-int head_grid_rt(int64_t B, int rt) {
-  static int cus = 0;       // queried once per process (also keeps the query out of a stream capture)
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  int grid = (int)((B + rt - 1) / rt);
-  if (grid > cus) grid = cus;
-  return grid < 1 ? 1 : grid;
-}
+int head_grid_rt(int64_t B, int rt) { return hcg_grid((B + rt - 1) / rt, hcg_cu_count()); }
 int head_grid(int64_t B, int64_t D = 128) { return head_grid_rt(B, D == 64 ? hcg_head16::RT : RT); }
 size_t head_slab(int64_t D) { return D == 128 ? (size_t)HC<128>::SLAB : (size_t)HC<64>::SLAB; }
 

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "split_mfma.h"
 #include "graph_csr.h"
+#include "launch.h"
 
 namespace {
 
@@ -1248,16 +1249,7 @@ __global__ __launch_bounds__(MT, 2) void k_mid_layer_bwd(
   }
 }
 
-int mid_grid(int64_t B, int wgs_per_cu) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  int64_t grid = (int64_t)cus * wgs_per_cu;
-  if (grid > B) grid = B;
-  return grid < 1 ? 1 : (int)grid;
-}
+int mid_grid(int64_t B, int wgs_per_cu) { return hcg_grid(B, (int64_t)hcg_cu_count() * wgs_per_cu); }
 
 // workgroups of 8 waves that fit a CU: 160 KB of LDS, at most 2 (16 waves: the kernels use up to 256 VGPRs per lane)
 int wgs_per_cu(size_t lds) { return lds * 2 <= 160 * 1024 ? 2 : 1; }
@@ -1265,11 +1257,29 @@ int wgs_per_cu(size_t lds) { return lds * 2 <= 160 * 1024 ? 2 : 1; }
 int pad32(int64_t v) { return (int)((v + 31) / 32 * 32); }
 int pad8(int64_t v) { return (int)((v + 7) / 8 * 8 > 8 ? (v + 7) / 8 * 8 : 8); }
 
-// dynamic LDS above 64 KB has to be allowed per kernel: once per process (not per launch: the step may be under capture)
-template <auto KFN>
-hipError_t allow_big_lds() {   // (the kernel is a template VALUE parameter: one static per instantiation, not per signature)
-  static hipError_t st = hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  return st;
+constexpr size_t MID_LDS_LIMIT = 160 * 1024;
+
+// How the backward of one layer runs -- the ONE place that says so; the workspace query, the launcher and the reduction
+// job read it.  Slab of one 64-column half: dW [64][fpad] | db [64].
+struct MidBwdGeo {
+  bool wave;                // one graph per wave (wave.hip) instead of one per workgroup
+  int npad, emax, kpad, fpad;
+  int grid;                 // workgroups = slabs per half
+  int slab_floats;
+  size_t lds;               // of the workgroup kernel, for this `needs_dx`
+  size_t workspace_bytes;   // every half's slabs
+};
+MidBwdGeo mid_bwd_geo(int64_t B, int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges, bool needs_dx) {
+  MidBwdGeo g{};
+  g.wave = hcg_w64_applicable(F, D, max_nodes, max_edges) != 0;
+  g.npad = pad32(max_nodes), g.emax = pad8(max_edges);
+  g.fpad = hcg_fpad(F), g.kpad = hcg_kpad(F);
+  g.slab_floats = hcg_dw_db_slab_floats(DD, g.fpad);
+  g.lds = mid_lds_bytes(g.npad, g.emax, needs_dx ? g.kpad : 0, DD, true);
+  // one grid size for both variants of a step (with / without dx) keeps the slab count a function of the batch only
+  g.grid = g.wave ? hcg_w64_bwd_grid(B) : mid_grid(B, wgs_per_cu(mid_lds_bytes(g.npad, g.emax, g.kpad, DD, true)));
+  g.workspace_bytes = (size_t)(D / DD) * g.grid * g.slab_floats * sizeof(float) + 256;
+  return g;
 }
 
 }  // namespace
@@ -1287,77 +1297,50 @@ extern "C" int hcg_mid_layer_fwd(const float* x, const float* W, const float* b,
                                  uint8_t* poolbits, float* xagg, uint8_t* signbits, int32_t* status, hcg_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!hcg_mid_supported(F, D, max_nodes, max_edges)) return HCG_ERR_UNSUPPORTED;
+  const bool wave = hcg_w64_applicable(F, D, max_nodes, max_edges) != 0;
   // Ahat x + sign pieces (training form of a first, not pooled, 64-wide layer over graphs of more than 64 nodes)
   if ((xagg == nullptr) != (signbits == nullptr)) return HCG_ERR_INVALID_ARG;
-  if (xagg && (emb || poolbits || D != DD || F > 64 || !out || hcg_w64_applicable(F, D, max_nodes, max_edges))) return HCG_ERR_UNSUPPORTED;
-  if (apply_act && !(slope >= 0.f && slope <= 1.f)) return HCG_ERR_UNSUPPORTED;   // LeakyReLU is evaluated as max(v, slope*v)
+  if (xagg && (emb || poolbits || D != DD || F > 64 || !out || wave)) return HCG_ERR_UNSUPPORTED;
+  if (!hcg_slope_ok(apply_act, slope)) return HCG_ERR_UNSUPPORTED;
   if (N < 0 || B < 0 || E < 0) return HCG_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return HCG_OK;
   if (!x || !W || !b || !graph_ptr || !edge_ptr || (!out && !poolbits) || !status || (E > 0 && !edge_index)) return HCG_ERR_INVALID_ARG;
   // the bit form (training, pooled layer: `out` is not written) exists for F <= 64 on graphs of more than 64 nodes
-  if (poolbits && (!emb || F > 64 || hcg_w64_applicable(F, D, max_nodes, max_edges))) return HCG_ERR_UNSUPPORTED;
-  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(graph_ptr); E = 1; }  // readable dummy; no graph has edges
+  if (poolbits && (!emb || F > 64 || wave)) return HCG_ERR_UNSUPPORTED;
+  hcg_edge_dummy(edge_index, E, graph_ptr);
   // graphs up to 64 nodes: one graph per WAVE (wave.hip).  (Round 3 measured this kernel's rebuilt forward on them instead:
   // equal at 4096 graphs of 37-63 atoms -- 49.5 / 47.2 against 49.5 / 48.0 us -- and 18.1 / 17.6 against 19.2 / 19.2 us on the
   // 1 270 graphs of 33-36 atoms of the ragged batch, whose launches are one graph chain long either way.)
-  if (hcg_w64_applicable(F, D, max_nodes, max_edges))
+  if (wave)
     return hcg_w64_fwd_launch(x, W, b, edge_index, E, graph_ptr, edge_ptr, B, F, slope, apply_act, out, emb, status, stream);
   const int npad = pad32(max_nodes), emax = pad8(max_edges);
-  const int kpad = F <= 32 ? 32 : 64;
+  const int kpad = hcg_kpad(F);
   const int nimg = F > 64 ? (int)((F + 63) / 64) : 1;                 // K-chunk weight images kept resident (MULTIK)
   const size_t lds = mid_lds_bytes(npad, emax, DD * nimg, kpad, false);
   const dim3 grid(mid_grid(B, wgs_per_cu(lds))), blk(MT);
-#define LAUNCH_MID_FWD(KP, PL, MK, VC, NRC, BT, ZSV)                                                                       \
-  do {                                                                                                                     \
-    auto kfn = k_mid_layer_fwd<KP, PL, MK, VC, NRC, BT, ZSV>;                                                              \
-    hipError_t e = allow_big_lds<k_mid_layer_fwd<KP, PL, MK, VC, NRC, BT, ZSV>>();                                         \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                            \
-    hipLaunchKernelGGL(kfn, grid, blk, lds, stream, x, (int)F, Wh, bh, edge_index, E, graph_ptr, edge_ptr, (int)B, npad,    \
-                       emax, slope, apply_act, out, (int)D, coff, emb, status, poolbits, xagg,                             \
-                       reinterpret_cast<unsigned short*>(signbits));                                                       \
-  } while (0)
-#define LAUNCH_MID_FWD_V(KP, PL, NRC, BT, ZSV)                                                                             \
-  do { if (vec) LAUNCH_MID_FWD(KP, PL, false, true, NRC, BT, ZSV); else LAUNCH_MID_FWD(KP, PL, false, false, NRC, BT, ZSV); } while (0)
-#define LAUNCH_MID_FWD_X(KP, PL)                                                                                           \
-  do {                                                                                                                     \
-    if (PL && poolbits) { if (npad <= 128) LAUNCH_MID_FWD_V(KP, true, 128, true, false); else LAUNCH_MID_FWD_V(KP, true, MID_MAX_NODES, true, false); } \
-    else if (!PL && xagg) { if (npad <= 128) LAUNCH_MID_FWD_V(KP, false, 128, false, true); else LAUNCH_MID_FWD_V(KP, false, MID_MAX_NODES, false, true); } \
-    else { if (npad <= 128) LAUNCH_MID_FWD_V(KP, PL, 128, false, false); else LAUNCH_MID_FWD_V(KP, PL, MID_MAX_NODES, false, false); } \
-  } while (0)
   const bool vec = F == kpad && ((uintptr_t)x % 16 == 0);     // whole float4 rows in the x prefetch
   for (int half = 0; half < (int)(D / DD); ++half) {     // 64 output columns per launch
     const float* Wh = W + (size_t)half * DD * F;
     const float* bh = b + half * DD;
     const int coff = half * DD;
-    if (kpad == 32)   { if (emb) LAUNCH_MID_FWD_X(32, true); else LAUNCH_MID_FWD_X(32, false); }
-    else if (F <= 64) { if (emb) LAUNCH_MID_FWD_X(64, true); else LAUNCH_MID_FWD_X(64, false); }
-    else              { if (emb) LAUNCH_MID_FWD(64, true, true, false, 32, false, false); else LAUNCH_MID_FWD(64, false, true, false, 32, false, false); }
-    HCG_CHECK_LAUNCH();
+    HCG_TRY(hcg_with_index<4>(hcg_fwd_form(emb, poolbits, xagg), [&](auto I) {
+      constexpr hcg_fwd_form_t f = HCG_FWD_FORMS[decltype(I)::value];
+      return hcg_with_bools([&](auto MULTIK, auto K64, auto VEC, auto BIG) {
+        // F > 64 (MULTIK) is ONE shape -- K = 64 in resident chunks, scalar x rows, 32-row blocks -- in the plain and the
+        // pooled form only (the others were refused above): every other choice collapses onto it
+        constexpr int KP = (MULTIK || K64) ? 64 : 32, NR = MULTIK ? 32 : (BIG ? MID_MAX_NODES : 128);
+        return hcg_launch<k_mid_layer_fwd<KP, f.pool, MULTIK, (VEC && !MULTIK), NR, (f.bits && !MULTIK), (f.zs && !MULTIK)>>(
+            grid, blk, lds, MID_LDS_LIMIT, stream, x, (int)F, Wh, bh, edge_index, E, graph_ptr, edge_ptr, (int)B, npad, emax, slope,
+            apply_act, out, (int)D, coff, emb, status, poolbits, xagg, reinterpret_cast<unsigned short*>(signbits));
+      }, F > 64, kpad == 64, vec, npad > 128);
+    }));
   }
-#undef LAUNCH_MID_FWD_X
-#undef LAUNCH_MID_FWD_V
-#undef LAUNCH_MID_FWD
   return HCG_OK;
-}
-
-// slab geometry of one column half: dW [64][fpad] | db [64]
-static int mid_fpad(int64_t F) { return F <= 32 ? 32 : (F <= 64 ? 64 : 128); }
-
-static int mid_bwd_grid(int64_t B, int64_t F, int64_t max_nodes, int64_t max_edges, size_t* lds_out, bool needs_dx) {
-  const int kpad = F <= 32 ? 32 : 64;
-  const size_t lds = mid_lds_bytes(pad32(max_nodes), pad8(max_edges), needs_dx ? kpad : 0, DD, true);
-  if (lds_out) *lds_out = lds;
-  // one grid size for both variants of a step (with / without dx) keeps the slab count a function of the batch only
-  const size_t lds_worst = mid_lds_bytes(pad32(max_nodes), pad8(max_edges), kpad, DD, true);
-  return mid_grid(B, wgs_per_cu(lds_worst));
 }
 
 extern "C" size_t hcg_mid_workspace_bytes(int64_t B, int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges) {
   if (!hcg_mid_supported(F, D, max_nodes, max_edges)) return 0;
-  if (hcg_w64_applicable(F, D, max_nodes, max_edges))
-    return (size_t)hcg_w64_bwd_grid(B) * (DD * mid_fpad(F) + DD) * sizeof(float) + 256;
-  const size_t half = (size_t)mid_bwd_grid(B, F, max_nodes, max_edges, nullptr, true) * (DD * mid_fpad(F) + DD) * sizeof(float);
-  return (size_t)(D / DD) * half + 256;
+  return mid_bwd_geo(B, F, D, max_nodes, max_edges, true).workspace_bytes;
 }
 
 // backward, stage 1 (one launch per 64-column half).  dout == NULL selects the pooled form (upstream gradient = demb
@@ -1372,45 +1355,28 @@ extern "C" int hcg_mid_layer_bwd(const float* dout, const float* demb, const flo
   if (!hcg_mid_supported(F, D, max_nodes, max_edges)) return HCG_ERR_UNSUPPORTED;
   if (N <= 0 || B <= 0 || E < 0 || !W || !workspace || !x || !graph_ptr || !edge_ptr || !status || (E > 0 && !edge_index))
     return HCG_ERR_INVALID_ARG;
-  const bool poolg = (dout == nullptr);
-  if (poolg && (!demb || !emb)) return HCG_ERR_INVALID_ARG;
-  if ((apply_act & ~3) || ((apply_act & 2) && !dx)) return HCG_ERR_INVALID_ARG;
-  if ((poolg || (apply_act & 1)) && !out) return HCG_ERR_INVALID_ARG;   // `out` is only read for leaky' and the pooled routing
-  if (workspace_bytes < hcg_mid_workspace_bytes(B, F, D, max_nodes, max_edges)) return HCG_ERR_WORKSPACE;
-  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(graph_ptr); E = 1; }
-  if (hcg_w64_applicable(F, D, max_nodes, max_edges))
+  const bool poolg = (dout == nullptr), ndx = dx != nullptr;
+  HCG_TRY(hcg_bwd_form_check(poolg, demb, emb, apply_act, ndx, out));
+  const MidBwdGeo g = mid_bwd_geo(B, F, D, max_nodes, max_edges, ndx);
+  if (workspace_bytes < g.workspace_bytes) return HCG_ERR_WORKSPACE;
+  hcg_edge_dummy(edge_index, E, graph_ptr);
+  if (g.wave)
     return hcg_w64_bwd_launch(dout, demb, emb, out, x, W, edge_index, E, graph_ptr, edge_ptr, B, F, slope, apply_act, dx,
                               (float*)workspace, status, stream);
-  const int npad = pad32(max_nodes), emax = pad8(max_edges), fpad = mid_fpad(F);
-  const bool ndx = dx != nullptr;
-  size_t lds = 0;
-  const int gsz = mid_bwd_grid(B, F, max_nodes, max_edges, &lds, ndx);
-  const dim3 grid(gsz), blk(MT);
-  const size_t slab_half = (size_t)gsz * (DD * fpad + DD);
-#define LAUNCH_MID_BWD(KP, NF, DX, PG)                                                                                      \
-  do {                                                                                                                      \
-    auto kfn = k_mid_layer_bwd<KP, NF, DX, PG>;                                                                             \
-    hipError_t e = allow_big_lds<k_mid_layer_bwd<KP, NF, DX, PG>>();                                                        \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                             \
-    hipLaunchKernelGGL(kfn, grid, blk, lds, stream, dout, demb, emb, out, (int)D, coff, x, (int)F, Wh, edge_index, E,        \
-                       graph_ptr, edge_ptr, (int)B, npad, emax, slope, apply_act, dx, half > 0 ? 1 : 0, partials, status);   \
-  } while (0)
-#define DISPATCH_MID_BWD(KP, NF)                                                                              \
-  do {                                                                                                        \
-    if (ndx) { if (poolg) LAUNCH_MID_BWD(KP, NF, true, true); else LAUNCH_MID_BWD(KP, NF, true, false); }     \
-    else     { if (poolg) LAUNCH_MID_BWD(KP, NF, false, true); else LAUNCH_MID_BWD(KP, NF, false, false); }   \
-  } while (0)
+  const dim3 grid(g.grid), blk(MT);
   for (int half = 0; half < (int)(D / DD); ++half) {
     const float* Wh = W + (size_t)half * DD * F;
     const int coff = half * DD;
-    float* partials = (float*)workspace + (size_t)half * slab_half;
-    if (fpad == 32) DISPATCH_MID_BWD(32, 1);
-    else if (fpad == 64) DISPATCH_MID_BWD(64, 1);
-    else DISPATCH_MID_BWD(64, 2);
-    HCG_CHECK_LAUNCH();
+    float* partials = (float*)workspace + (size_t)half * g.grid * g.slab_floats;
+    HCG_TRY(hcg_with_index<3>(g.fpad / 64, [&](auto I) {      // fpad 32, 64, 128: K padding 32, 64, 64 in one or two chunks
+      constexpr int KP = I == 0 ? 32 : 64, NFC = I == 2 ? 2 : 1;
+      return hcg_with_bools([&](auto DX, auto POOLG) {
+        return hcg_launch<k_mid_layer_bwd<KP, NFC, DX, POOLG>>(grid, blk, g.lds, MID_LDS_LIMIT, stream, dout, demb, emb, out, (int)D, coff,
+                                                              x, (int)F, Wh, edge_index, E, graph_ptr, edge_ptr, (int)B, g.npad,
+                                                              g.emax, slope, apply_act, dx, half > 0 ? 1 : 0, partials, status);
+      }, ndx, poolg);
+    }));
   }
-#undef DISPATCH_MID_BWD
-#undef LAUNCH_MID_BWD
   return HCG_OK;
 }
 
@@ -1419,16 +1385,9 @@ extern "C" int hcg_mid_reduce_job(const void* workspace, size_t workspace_bytes,
                                   int64_t max_nodes, int64_t max_edges, int half, float* dW, float* db, hcg_reduce_job* job) {
   if (!hcg_mid_supported(F, D, max_nodes, max_edges) || !dW || !db || !job || !workspace || B <= 0 || half < 0 || half >= D / DD)
     return HCG_ERR_INVALID_ARG;
-  if (workspace_bytes < hcg_mid_workspace_bytes(B, F, D, max_nodes, max_edges)) return HCG_ERR_WORKSPACE;
-  const int fpad = mid_fpad(F);
-  const int gsz = hcg_w64_applicable(F, D, max_nodes, max_edges) ? hcg_w64_bwd_grid(B) : mid_bwd_grid(B, F, max_nodes, max_edges, nullptr, true);
-  job->slabs = (const float*)workspace + (size_t)half * gsz * (DD * fpad + DD);
-  job->nslabs = gsz;
-  job->slab_floats = DD * fpad + DD;
-  job->nseg = 2;
-  job->sse_part = nullptr;
-  job->reserved = 0;
-  job->seg[0] = hcg_reduce_seg{0, DD * fpad, fpad, (int32_t)F, dW + (size_t)half * DD * F};
-  job->seg[1] = hcg_reduce_seg{DD * fpad, DD, 1, 1, db + half * DD};
+  const MidBwdGeo g = mid_bwd_geo(B, F, D, max_nodes, max_edges, true);
+  if (workspace_bytes < g.workspace_bytes) return HCG_ERR_WORKSPACE;
+  hcg_fill_job_dw_db(job, (const float*)workspace + (size_t)half * g.grid * g.slab_floats, g.grid, DD, g.fpad, F,
+                     dW + (size_t)half * DD * F, db + half * DD);
   return HCG_OK;
 }

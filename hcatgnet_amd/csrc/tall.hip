@@ -26,6 +26,7 @@
 #include "common.h"
 #include "split_mfma.h"
 #include "graph_csr.h"
+#include "launch.h"
 
 namespace {
 
@@ -999,53 +1000,27 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 2) void k_gseg_bwd(
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-int cu_count() {
-  static int cus = 0;
-  if (cus > 0) return cus;
-  int dev = 0, v = 0;
-  cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-    cus = v;
-  return cus;
-}
-int seg_grid(int64_t B) {            // one workgroup of 16 waves per CU
-  int64_t g = (int64_t)cu_count();
-  if (g > B) g = B;
-  return g < 1 ? 1 : (int)g;
-}
-int mm_grid(int64_t N) {
-  int64_t g = hcg_cdiv(hcg_cdiv(N, 32), TW / 2);
-  if (g > cu_count()) g = cu_count();
-  return g < 1 ? 1 : (int)g;
-}
+int seg_grid(int64_t B) { return hcg_grid(B, hcg_cu_count()); }     // one workgroup of 16 waves per CU
+int mm_grid(int64_t N) { return hcg_grid(hcg_cdiv(hcg_cdiv(N, 32), TW / 2), hcg_cu_count()); }
 constexpr int DW_TILE = 64;
-int dw_grid(int64_t N, int64_t D = 128) {   // one workgroup per CU (110 KB of operand images; D = 64: two); every workgroup leaves a slab
-  int64_t g = hcg_cdiv(N, DW_TILE);
-  const int64_t cap = (int64_t)cu_count() * (D == 64 ? 2 : 1);
-  if (g > cap) g = cap;
-  return g < 1 ? 1 : (int)g;
-}
-int seg_grid64(int64_t B) {          // 64-wide layers: up to four 4-wave workgroups per CU (two 8-wave ones for graphs > 128 nodes)
-  int64_t g = (int64_t)cu_count() * 4;
-  if (g > B) g = B;
-  return g < 1 ? 1 : (int)g;
-}
+// one workgroup per CU (110 KB of operand images; D = 64: two); every workgroup leaves a slab
+int dw_grid(int64_t N, int64_t D = 128) { return hcg_grid(hcg_cdiv(N, DW_TILE), (int64_t)hcg_cu_count() * (D == 64 ? 2 : 1)); }
+// 64-wide layers: up to four 4-wave workgroups per CU (two 8-wave ones for graphs > 128 nodes)
+int seg_grid64(int64_t B) { return hcg_grid(B, (int64_t)hcg_cu_count() * 4); }
 int seg_npad(int64_t max_nodes) { return (int)((max_nodes + 3) / 4 * 4); }
 size_t seg_tile_bytes(int npad) { return (size_t)npad * SEG_TS * sizeof(float); }
-int tall_fpad(int64_t F) { return F <= 32 ? 32 : (F <= 64 ? 64 : 128); }
 
-template <auto KFN>
-hipError_t allow_lds(size_t bytes) {
-  static hipError_t st = hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return st;
-}
-
-struct TallWs { float* inter; float* dw_slabs; float* db_slabs; size_t total; };
+// the workspace and the grids it was sized for: the launches and the reduction jobs read both from here
+struct TallWs {
+  float* inter; float* dw_slabs; float* db_slabs; size_t total;
+  int fpad, dw_grid, seg_grid64;     // dW slabs: [dw_grid][D][fpad]; db slabs [D] each: seg_grid64, or dw_grid in the first-layer form
+};
 TallWs tall_carve(void* ws, int64_t N, int64_t B, int64_t F, int64_t D) {
   TallWs t;
+  t.fpad = hcg_fpad(F), t.dw_grid = dw_grid(N, D), t.seg_grid64 = seg_grid64(B);
   const size_t o1 = hcg_align_up((size_t)N * D * sizeof(float), 256);
-  const size_t o2 = o1 + hcg_align_up((size_t)dw_grid(N, D) * D * tall_fpad(F) * sizeof(float), 256);
-  const int dbs = seg_grid64(B) > dw_grid(N, D) ? seg_grid64(B) : dw_grid(N, D);      // (first-layer form: one db slab per dW slab)
+  const size_t o2 = o1 + hcg_align_up((size_t)t.dw_grid * D * t.fpad * sizeof(float), 256);
+  const int dbs = t.seg_grid64 > t.dw_grid ? t.seg_grid64 : t.dw_grid;      // (first-layer form: one db slab per dW slab)
   const size_t o3 = o2 + hcg_align_up((size_t)dbs * D * sizeof(float), 256);
   char* p = (char*)ws;
   t.inter = (float*)p;
@@ -1054,6 +1029,16 @@ TallWs tall_carve(void* ws, int64_t N, int64_t B, int64_t F, int64_t D) {
   t.total = o3 + 256;
   return t;
 }
+
+// the dense kernels' shapes: `db` blocks of 32 output columns (D = 64, 128), `nbf` blocks of 32 input columns (fpad / 32)
+struct TallDense { int db, nbf; };
+constexpr TallDense TALL_DENSE[5] = {{2, 1}, {2, 2}, {4, 1}, {4, 2}, {4, 4}};
+int tall_dense_form(int64_t D, int fpad) { return (D == 64 ? 0 : 2) + fpad / 64; }
+constexpr size_t tall_dw_lds(TallDense f) { return (size_t)3 * (f.db * 32 + f.nbf * 32) * (DW_TILE + 8) * sizeof(short); }
+
+// the upstream gradient's forms of k_gseg_bwd: plain, times leaky'(out), pooled (routed with out / emb), pooled from the bit form
+struct GsegForm { bool poolg, two, bits; };
+constexpr GsegForm GSEG_FORMS[4] = {{false, false, false}, {false, true, false}, {true, false, false}, {true, false, true}};
 
 }  // namespace
 
@@ -1088,46 +1073,28 @@ extern "C" int hcg_tall_layer_fwd(const float* x, const float* W, const float* b
   if ((xagg == nullptr) != (signbits == nullptr)) return HCG_ERR_INVALID_ARG;
   if (xagg && (emb || poolbits || !out)) return HCG_ERR_UNSUPPORTED;     // (first-layer form: a layer that is not pooled)
   if (poolbits && !emb) return HCG_ERR_INVALID_ARG;
-  if (apply_act && !(slope >= 0.f && slope <= 1.f)) return HCG_ERR_UNSUPPORTED;   // LeakyReLU is evaluated as max(v, slope*v)
+  if (!hcg_slope_ok(apply_act, slope)) return HCG_ERR_UNSUPPORTED;
   if (N < 0 || B < 0 || E < 0) return HCG_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return HCG_OK;
   if (!x || !W || !b || !graph_ptr || !edge_ptr || (!out && !poolbits) || !status || !workspace || (E > 0 && !edge_index)) return HCG_ERR_INVALID_ARG;
-  if (workspace_bytes < hcg_tall_workspace_bytes(N, B, F, D)) return HCG_ERR_WORKSPACE;
-  if (N > (int64_t)INT32_MAX / 2) return HCG_ERR_UNSUPPORTED;
-  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(graph_ptr); E = 1; }
   const TallWs ws = tall_carve(workspace, N, B, F, D);
-  const dim3 sgrid(seg_grid(B)), sblk(SN);
+  if (workspace_bytes < ws.total) return HCG_ERR_WORKSPACE;
+  if (N > (int64_t)INT32_MAX / 2) return HCG_ERR_UNSUPPORTED;
+  hcg_edge_dummy(edge_index, E, graph_ptr);
   const int npad = seg_npad(max_nodes);
-  const size_t slds = seg_tile_bytes(npad);
-  const size_t wbuf = (size_t)2 * WCH * sizeof(short);
   // x -> (MFMA) -> H tile in LDS -> sums: the tile (<= 224 rows), two weight chunks and the CSR fit 160 KB of LDS
-  {
-    const int KP = (int)((F + 15) / 16 * 16);
-    short* img = reinterpret_cast<short*>(ws.inter);                 // 3 x 128 x KP bf16
-    hipLaunchKernelGGL(k_split_weight, dim3((128 * KP + 255) / 256), dim3(256), 0, stream, W, (int)D, (int)F, KP, img);
-    HCG_CHECK_LAUNCH();
-    const size_t lds = slds + wbuf, lds_max = 160 * 1024 - 512 - sizeof(SegLdsT<false>);
-    if (lds > lds_max) return HCG_ERR_UNSUPPORTED;
-    hipError_t e = xagg ? allow_lds<k_seg_fwd<false, false, true>>(lds_max)
-                        : (poolbits ? allow_lds<k_seg_fwd<true, true>>(lds_max)
-                                    : (emb ? allow_lds<k_seg_fwd<true>>(lds_max) : allow_lds<k_seg_fwd<false>>(lds_max)));
-    if (e != hipSuccess) return hcg_hip_err(e);
-    if (xagg)
-      hipLaunchKernelGGL((k_seg_fwd<false, false, true>), sgrid, sblk, lds, stream, x, (int)F, KP, (const short*)img, b, edge_index,
-                         E, graph_ptr, edge_ptr, (int)B, npad, slope, apply_act, out, emb, status, (unsigned char*)nullptr, xagg,
-                         tall_fpad(F), reinterpret_cast<uint32_t*>(signbits));
-    else if (poolbits)
-      hipLaunchKernelGGL((k_seg_fwd<true, true>), sgrid, sblk, lds, stream, x, (int)F, KP, (const short*)img, b, edge_index, E,
-                         graph_ptr, edge_ptr, (int)B, npad, slope, apply_act, out, emb, status, poolbits);
-    else if (emb)
-      hipLaunchKernelGGL((k_seg_fwd<true>), sgrid, sblk, lds, stream, x, (int)F, KP, (const short*)img, b, edge_index, E,
-                         graph_ptr, edge_ptr, (int)B, npad, slope, apply_act, out, emb, status);
-    else
-      hipLaunchKernelGGL((k_seg_fwd<false>), sgrid, sblk, lds, stream, x, (int)F, KP, (const short*)img, b, edge_index, E,
-                         graph_ptr, edge_ptr, (int)B, npad, slope, apply_act, out, emb, status);
-    HCG_CHECK_LAUNCH();
-  }
-  return HCG_OK;
+  const int KP = (int)((F + 15) / 16 * 16);
+  short* img = reinterpret_cast<short*>(ws.inter);                 // 3 x 128 x KP bf16
+  hipLaunchKernelGGL(k_split_weight, dim3((128 * KP + 255) / 256), dim3(256), 0, stream, W, (int)D, (int)F, KP, img);
+  HCG_CHECK_LAUNCH();
+  const size_t lds = seg_tile_bytes(npad) + (size_t)2 * WCH * sizeof(short), lds_max = 160 * 1024 - 512 - sizeof(SegLdsT<false>);
+  if (lds > lds_max) return HCG_ERR_UNSUPPORTED;
+  return hcg_with_index<4>(hcg_fwd_form(emb, poolbits, xagg), [&](auto I) {
+    constexpr hcg_fwd_form_t f = HCG_FWD_FORMS[decltype(I)::value];
+    return hcg_launch<k_seg_fwd<f.pool, f.bits, f.zs>>(dim3(seg_grid(B)), dim3(SN), lds, lds_max, stream, x, (int)F, KP, (const short*)img, b,
+                                                      edge_index, E, graph_ptr, edge_ptr, (int)B, npad, slope, apply_act, out, emb,
+                                                      status, poolbits, xagg, xagg ? ws.fpad : 0, reinterpret_cast<uint32_t*>(signbits));
+  });
 }
 
 // dout == NULL selects the pooled form (upstream gradient = demb [B, 2D], expanded on chip with `emb` and `out`).
@@ -1149,152 +1116,70 @@ extern "C" int hcg_tall_layer_bwd(const float* dout, const float* demb, const fl
   const bool bits = poolbits != nullptr;      // the forward's bit form stands in for `out` and `emb`
   if (bits && !poolg) return HCG_ERR_INVALID_ARG;
   if ((xagg == nullptr) != (signbits == nullptr)) return HCG_ERR_INVALID_ARG;
+  const TallWs ws = tall_carve(workspace, N, B, F, D);
+  const int dense = tall_dense_form(D, ws.fpad);
   if (xagg) {
     // ---- first-layer form: dW = (dout (.) leaky'(out))^T (Ahat x) and db = its column sums, ONE dense launch (k_tall_dw<FIRST>)
     if (dx || poolg || (D == 64 && F > 64)) return HCG_ERR_UNSUPPORTED;
-    if (workspace_bytes < hcg_tall_workspace_bytes(N, B, F, D)) return HCG_ERR_WORKSPACE;
-    const TallWs ws = tall_carve(workspace, N, B, F, D);
-    const int fp = tall_fpad(F);
-    const dim3 grid(dw_grid(N, D)), blk(DWT);
+    if (workspace_bytes < ws.total) return HCG_ERR_WORKSPACE;
     const float slope_eff = (apply_act & 1) ? slope : 1.f;
-#define LAUNCH_DW_FIRST(DBV, NBF)                                                                                        \
-  do {                                                                                                                   \
-    const size_t lds = (size_t)3 * (DBV * 32 + NBF * 32) * (DW_TILE + 8) * sizeof(short);                                \
-    hipError_t e = allow_lds<k_tall_dw<DBV, NBF, true, true>>(lds);                                                      \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                          \
-    hipLaunchKernelGGL((k_tall_dw<DBV, NBF, true, true>), grid, blk, lds, stream, dout, xagg, fp, ws.dw_slabs, (int)N,   \
-                       reinterpret_cast<const unsigned short*>(signbits), slope_eff, ws.db_slabs, n_dev);                \
-  } while (0)
-    if (D == 64) { if (fp == 32) LAUNCH_DW_FIRST(2, 1); else LAUNCH_DW_FIRST(2, 2); }
-    else         { if (fp == 32) LAUNCH_DW_FIRST(4, 1); else if (fp == 64) LAUNCH_DW_FIRST(4, 2); else LAUNCH_DW_FIRST(4, 4); }
-#undef LAUNCH_DW_FIRST
-    HCG_CHECK_LAUNCH();
-    return HCG_OK;
+    return hcg_with_index<5>(dense, [&](auto I) {
+      constexpr TallDense f = TALL_DENSE[decltype(I)::value];
+      return hcg_launch<k_tall_dw<f.db, f.nbf, true, true>>(dim3(ws.dw_grid), dim3(DWT), tall_dw_lds(f), tall_dw_lds(f), stream, dout, xagg,
+                                                           ws.fpad, ws.dw_slabs, (int)N, reinterpret_cast<const unsigned short*>(signbits),
+                                                           slope_eff, ws.db_slabs, n_dev);
+    });
   }
-  if (poolg && (!demb || (!emb && !bits))) return HCG_ERR_INVALID_ARG;
-  if ((apply_act & ~3) || ((apply_act & 2) && !dx)) return HCG_ERR_INVALID_ARG;
-  if ((poolg || (apply_act & 1)) && !out && !bits) return HCG_ERR_INVALID_ARG;
-  if (workspace_bytes < hcg_tall_workspace_bytes(N, B, F, D)) return HCG_ERR_WORKSPACE;
-  if (E == 0) { edge_index = reinterpret_cast<const int64_t*>(graph_ptr); E = 1; }
-  const TallWs ws = tall_carve(workspace, N, B, F, D);
+  HCG_TRY(hcg_bwd_form_check(poolg, demb, emb || bits, apply_act, dx, out || bits));
+  if (workspace_bytes < ws.total) return HCG_ERR_WORKSPACE;
+  hcg_edge_dummy(edge_index, E, graph_ptr);
   const int act_here = apply_act & 1;
   {   // ---- dH = Ahat^T (dA . leaky'), db slabs: 64-column groups (one for D = 64, two for D = 128: blockIdx.y)
     const int npad = seg_npad(max_nodes);
-    const dim3 sgrid(seg_grid64(B), (unsigned)(D / 64));
+    const dim3 sgrid(ws.seg_grid64, (unsigned)(D / 64));
     const size_t slds = (size_t)npad * (64 + 4) * sizeof(float);
-#define LAUNCH_GSEG(NTV, NMAXV, PG, TW2, AOUT, BT)                                                                         \
-  do {                                                                                                                     \
-    hipError_t e = allow_lds<k_gseg_bwd<64, NTV, NMAXV, PG, TW2, BT>>((size_t)NMAXV * 68 * sizeof(float));                \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                            \
-    hipLaunchKernelGGL((k_gseg_bwd<64, NTV, NMAXV, PG, TW2, BT>), sgrid, dim3(NTV), slds, stream, dout, demb, emb, AOUT,   \
-                       edge_index, E, graph_ptr, edge_ptr, (int)B, npad, slope, act_here, ws.inter, ws.db_slabs, status,   \
-                       (int)D, poolbits);                                                                                  \
-  } while (0)
-#define DISPATCH_GSEG(NTV, NMAXV)                                                                                          \
-  do {                                                                                                                     \
-    if (bits) LAUNCH_GSEG(NTV, NMAXV, true, false, (const float*)nullptr, true);                                           \
-    else if (poolg) LAUNCH_GSEG(NTV, NMAXV, true, false, out, false);                                                      \
-    else if (act_here) LAUNCH_GSEG(NTV, NMAXV, false, true, out, false);                                                   \
-    else LAUNCH_GSEG(NTV, NMAXV, false, false, (const float*)nullptr, false);                                              \
-  } while (0)
-    if (npad <= 128) DISPATCH_GSEG(256, 128); else DISPATCH_GSEG(512, 224);
-#undef DISPATCH_GSEG
-#undef LAUNCH_GSEG
-    HCG_CHECK_LAUNCH();
+    const int form = bits ? 3 : (poolg ? 2 : act_here);
+    const float* aout = (form == 1 || form == 2) ? out : nullptr;
+    HCG_TRY(hcg_with_index<4>(form, [&](auto I) {
+      constexpr GsegForm f = GSEG_FORMS[decltype(I)::value];
+      return hcg_with_bools([&](auto BIG) {
+        constexpr int NT = BIG ? 512 : 256, NMAX = BIG ? 224 : 128;
+        return hcg_launch<k_gseg_bwd<64, NT, NMAX, f.poolg, f.two, f.bits>>(sgrid, dim3(NT), slds, (size_t)NMAX * 68 * sizeof(float), stream, dout,
+                                                                           demb, emb, aout, edge_index, E, graph_ptr, edge_ptr, (int)B,
+                                                                           npad, slope, act_here, ws.inter, ws.db_slabs, status, (int)D,
+                                                                           poolbits);
+      }, npad > 128);
+    }));
   }
-  if (D == 64) {
-    const int fp = tall_fpad(F);
-    {   // dW slabs = dH^T x
-      const dim3 grid(dw_grid(N, 64)), blk(DWT);
-      const bool xvec = (F % 4) == 0 && ((uintptr_t)x % 16) == 0;
-#define LAUNCH_DW64(NBF, XV)                                                                                          \
-  do {                                                                                                               \
-    const size_t lds = (size_t)3 * (64 + NBF * 32) * (DW_TILE + 8) * sizeof(short);                                  \
-    hipError_t e = allow_lds<k_tall_dw<2, NBF, XV>>(lds);                                                            \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                      \
-    hipLaunchKernelGGL((k_tall_dw<2, NBF, XV>), grid, blk, lds, stream, ws.inter, x, (int)F, ws.dw_slabs, (int)N);   \
-  } while (0)
-      if (fp == 32) { if (xvec) LAUNCH_DW64(1, true); else LAUNCH_DW64(1, false); }
-      else          { if (xvec) LAUNCH_DW64(2, true); else LAUNCH_DW64(2, false); }
-#undef LAUNCH_DW64
-      HCG_CHECK_LAUNCH();
-    }
-    if (dx) {   // dx = dH W
-      const dim3 grid(mm_grid(N)), blk(TT);
-      const size_t lds = (size_t)3 * fp * (64 + WPAD) * 2;
-      const bool pm = (apply_act & 2) != 0;
-#define LAUNCH_MM64(NOB, PM)                                                                                               \
-  do {                                                                                                                     \
-    hipError_t e = allow_lds<k_tall_mm<64, NOB, true, PM>>(lds);                                                           \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                            \
-    hipLaunchKernelGGL((k_tall_mm<64, NOB, true, PM>), grid, blk, lds, stream, ws.inter, (int)D, W, (int)D, (int)F, dx,    \
-                       (int)F, x, slope, (int)N);                                                                          \
-  } while (0)
-      if (fp == 32) { if (pm) LAUNCH_MM64(1, true); else LAUNCH_MM64(1, false); }
-      else          { if (pm) LAUNCH_MM64(2, true); else LAUNCH_MM64(2, false); }
-#undef LAUNCH_MM64
-      HCG_CHECK_LAUNCH();
-    }
-    return HCG_OK;
-  }
-  const int fp = tall_fpad(F);
-  // dW slabs = dH^T x
-  {
-    const dim3 grid(dw_grid(N)), blk(DWT);
-#define LAUNCH_DW(NBF)                                                                                               \
-  do {                                                                                                               \
-    const size_t lds = (size_t)3 * (128 + NBF * 32) * (DW_TILE + 8) * sizeof(short);                                 \
-    hipError_t e = allow_lds<k_tall_dw<4, NBF>>(lds);                                                                \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                      \
-    hipLaunchKernelGGL((k_tall_dw<4, NBF>), grid, blk, lds, stream, ws.inter, x, (int)F, ws.dw_slabs, (int)N);       \
-  } while (0)
-    if (fp == 32) LAUNCH_DW(1); else if (fp == 64) LAUNCH_DW(2); else LAUNCH_DW(4);
-#undef LAUNCH_DW
-    HCG_CHECK_LAUNCH();
-  }
+  // dW slabs = dH^T x (x rows as whole float4 where they can be: always at D = 128, whose F is a multiple of 4)
+  const bool xvec = (F % 4) == 0 && ((uintptr_t)x % 16) == 0;
+  HCG_TRY(hcg_with_index<5>(dense, [&](auto I) {
+    constexpr TallDense f = TALL_DENSE[decltype(I)::value];
+    return hcg_with_bools([&](auto XV) {
+      return hcg_launch<k_tall_dw<f.db, f.nbf, (f.db == 4 || XV)>>(dim3(ws.dw_grid), dim3(DWT), tall_dw_lds(f), tall_dw_lds(f), stream, ws.inter, x,
+                                                                  (int)F, ws.dw_slabs, (int)N, nullptr, 1.f, nullptr, nullptr);
+    }, xvec);
+  }));
+  if (!dx) return HCG_OK;
   // dx = dH W
-  if (dx) {
-    const dim3 grid(mm_grid(N)), blk(TT);
-    const size_t lds = (size_t)3 * fp * (128 + WPAD) * 2;
-    const bool pm = (apply_act & 2) != 0;
-#define LAUNCH_MM_BWD(NOB, PM)                                                                                             \
-  do {                                                                                                                     \
-    hipError_t e = allow_lds<k_tall_mm<128, NOB, true, PM>>(lds);                                                          \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                            \
-    hipLaunchKernelGGL((k_tall_mm<128, NOB, true, PM>), grid, blk, lds, stream, ws.inter, (int)D, W, (int)D, (int)F, dx,   \
-                       (int)F, x, slope, (int)N);                                                                          \
-  } while (0)
-    if (fp == 32)      { if (pm) LAUNCH_MM_BWD(1, true); else LAUNCH_MM_BWD(1, false); }
-    else if (fp == 64) { if (pm) LAUNCH_MM_BWD(2, true); else LAUNCH_MM_BWD(2, false); }
-    else               { if (pm) LAUNCH_MM_BWD(4, true); else LAUNCH_MM_BWD(4, false); }
-#undef LAUNCH_MM_BWD
-    HCG_CHECK_LAUNCH();
-  }
-  return HCG_OK;
+  const size_t lds = (size_t)3 * ws.fpad * (D + WPAD) * 2;
+  return hcg_with_index<5>(dense, [&](auto I) {
+    constexpr TallDense f = TALL_DENSE[decltype(I)::value];
+    return hcg_with_bools([&](auto PM) {
+      return hcg_launch<k_tall_mm<f.db * 32, f.nbf, true, PM>>(dim3(mm_grid(N)), dim3(TT), lds, lds, stream, ws.inter, (int)D, W, (int)D, (int)F, dx,
+                                                              (int)F, x, slope, (int)N);
+    }, (apply_act & 2) != 0);
+  });
 }
 
 // two jobs: job_host[0] = dW [D, F] from the k_tall_dw slabs, job_host[1] = db [D] from the k_seg_bwd slabs
 extern "C" int hcg_tall_reduce_jobs(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F, int64_t D,
                                     int first_layer_form, float* dW, float* db, hcg_reduce_job* job_host) {
   if ((D != 128 && D != 64) || F < 1 || F > 128 || N <= 0 || B <= 0 || !dW || !db || !job_host || !workspace) return HCG_ERR_INVALID_ARG;
-  if (workspace_bytes < hcg_tall_workspace_bytes(N, B, F, D)) return HCG_ERR_WORKSPACE;
   const TallWs ws = tall_carve(const_cast<void*>(workspace), N, B, F, D);
-  const int fp = tall_fpad(F);
-  hcg_reduce_job* j = job_host;
-  j->slabs = ws.dw_slabs;
-  j->nslabs = dw_grid(N, D);
-  j->slab_floats = (int32_t)(D * fp);
-  j->nseg = 1;
-  j->sse_part = nullptr;
-  j->reserved = 0;
-  j->seg[0] = hcg_reduce_seg{0, (int32_t)(D * fp), fp, (int32_t)F, dW};
-  j = job_host + 1;
-  j->slabs = ws.db_slabs;
-  j->nslabs = first_layer_form ? dw_grid(N, D) : seg_grid64(B);      // (first-layer form: k_tall_dw<FIRST> leaves the db slabs)
-  j->slab_floats = (int32_t)D;
-  j->nseg = 1;
-  j->sse_part = nullptr;
-  j->reserved = 0;
-  j->seg[0] = hcg_reduce_seg{0, (int32_t)D, 1, 1, db};
+  if (workspace_bytes < ws.total) return HCG_ERR_WORKSPACE;
+  hcg_fill_job(job_host, ws.dw_slabs, ws.dw_grid, (int32_t)(D * ws.fpad), ws.fpad, (int32_t)F, dW);
+  // (first-layer form: k_tall_dw<FIRST> leaves the db slabs)
+  hcg_fill_job(job_host + 1, ws.db_slabs, first_layer_form ? ws.dw_grid : ws.seg_grid64, (int32_t)D, 1, 1, db);
   return HCG_OK;
 }

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "split_mfma.h"
 #include "graph_csr.h"
+#include "launch.h"
 
 namespace {
 
@@ -656,29 +657,10 @@ __global__ __launch_bounds__(NW * 64) void k_w64_layer_bwd(
   }
 }
 
-int w_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return cus;
-}
-
-int w_grid(int64_t B, int nw) {
-  int64_t grid = (B + nw - 1) / nw;
-  const int cus = w_cus();
-  if (grid > cus) grid = cus;
-  return grid < 1 ? 1 : (int)grid;
-}
-
-template <auto KFN>
-hipError_t w_allow_big_lds() {
-  static hipError_t st = hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  return st;
-}
+int w_grid(int64_t B, int nw) { return hcg_grid((B + nw - 1) / nw, hcg_cu_count()); }
 
 constexpr int NW_FWD = 7, NW_BWD = 8, NW_BWD_DX = 7;   // waves per workgroup: 160 KB of LDS / (one tile per wave + the weight image)
+constexpr size_t W_LDS_LIMIT = 160 * 1024;
 
 }  // namespace
 
@@ -693,46 +675,25 @@ int hcg_w64_bwd_grid(int64_t B) { return w_grid(B, NW_BWD_DX); }
 int hcg_w64_fwd_launch(const float* x, const float* W, const float* b, const int64_t* edge_index, int64_t E,
                        const int32_t* graph_ptr, const int32_t* edge_ptr, int64_t B, int64_t F, float slope, int apply_act,
                        float* out, float* emb, int32_t* status, hipStream_t stream) {
-  const size_t lds = (size_t)NW_FWD * w_wave_bytes(1) + (size_t)3 * DD * ((F <= 32 ? 32 : 64) + WPAD) * 2;
+  const int kpad = hcg_kpad(F);
+  const size_t lds = (size_t)NW_FWD * w_wave_bytes(1) + (size_t)3 * DD * (kpad + WPAD) * 2;
   const dim3 grid(w_grid(B, NW_FWD)), blk(NW_FWD * 64);
-#define LAUNCH_W_FWD(KP, PL)                                                                                       \
-  do {                                                                                                             \
-    hipError_t e = w_allow_big_lds<k_w64_layer_fwd<KP, PL, NW_FWD>>();                                             \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                    \
-    hipLaunchKernelGGL((k_w64_layer_fwd<KP, PL, NW_FWD>), grid, blk, lds, stream, x, (int)F, W, b, edge_index, E,  \
-                       graph_ptr, edge_ptr, (int)B, slope, apply_act, out, emb, status);                           \
-  } while (0)
-  if (F <= 32) { if (emb) LAUNCH_W_FWD(32, true); else LAUNCH_W_FWD(32, false); }
-  else         { if (emb) LAUNCH_W_FWD(64, true); else LAUNCH_W_FWD(64, false); }
-#undef LAUNCH_W_FWD
-  HCG_CHECK_LAUNCH();
-  return HCG_OK;
+  return hcg_with_bools([&](auto K64, auto POOL) {
+    return hcg_launch<k_w64_layer_fwd<(K64 ? 64 : 32), POOL, NW_FWD>>(grid, blk, lds, W_LDS_LIMIT, stream, x, (int)F, W, b, edge_index, E,
+                                                                    graph_ptr, edge_ptr, (int)B, slope, apply_act, out, emb, status);
+  }, kpad == 64, emb != nullptr);
 }
 
 int hcg_w64_bwd_launch(const float* dout, const float* demb, const float* emb, const float* out, const float* x,
                        const float* W, const int64_t* edge_index, int64_t E, const int32_t* graph_ptr,
                        const int32_t* edge_ptr, int64_t B, int64_t F, float slope, int apply_act, float* dx,
                        float* partials, int32_t* status, hipStream_t stream) {
-  const bool poolg = dout == nullptr, ndx = dx != nullptr;
-  const int kpad = F <= 32 ? 32 : 64;
-  const int gsz = hcg_w64_bwd_grid(B);
-  const dim3 grid(gsz);
-#define LAUNCH_W_BWD(KP, DX, PG, NWV)                                                                                   \
-  do {                                                                                                                  \
-    const size_t lds = (size_t)NWV * w_wave_bytes(1) + (DX ? (size_t)3 * KP * (DD + WPAD) * 2 : 0);                     \
-    hipError_t e = w_allow_big_lds<k_w64_layer_bwd<KP, DX, PG, NWV>>();                                                 \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                         \
-    hipLaunchKernelGGL((k_w64_layer_bwd<KP, DX, PG, NWV>), grid, dim3(NWV * 64), lds, stream, dout, demb, emb, out, x,  \
-                       (int)F, W, edge_index, E, graph_ptr, edge_ptr, (int)B, slope, apply_act, dx, partials, status);  \
-  } while (0)
-#define DISPATCH_W_BWD(KP)                                                                                        \
-  do {                                                                                                            \
-    if (ndx) { if (poolg) LAUNCH_W_BWD(KP, true, true, NW_BWD_DX); else LAUNCH_W_BWD(KP, true, false, NW_BWD_DX); } \
-    else     { if (poolg) LAUNCH_W_BWD(KP, false, true, NW_BWD); else LAUNCH_W_BWD(KP, false, false, NW_BWD); }   \
-  } while (0)
-  if (kpad == 32) DISPATCH_W_BWD(32); else DISPATCH_W_BWD(64);
-#undef DISPATCH_W_BWD
-#undef LAUNCH_W_BWD
-  HCG_CHECK_LAUNCH();
-  return HCG_OK;
+  const dim3 grid(hcg_w64_bwd_grid(B));
+  return hcg_with_bools([&](auto K64, auto DX, auto POOLG) {
+    constexpr int KP = K64 ? 64 : 32, NWV = DX ? NW_BWD_DX : NW_BWD;
+    const size_t lds = (size_t)NWV * w_wave_bytes(1) + (DX ? (size_t)3 * KP * (DD + WPAD) * 2 : 0);
+    return hcg_launch<k_w64_layer_bwd<KP, DX, POOLG, NWV>>(grid, dim3(NWV * 64), lds, W_LDS_LIMIT, stream, dout, demb, emb, out, x, (int)F, W,
+                                                          edge_index, E, graph_ptr, edge_ptr, (int)B, slope, apply_act, dx, partials,
+                                                          status);
+  }, hcg_kpad(F) == 64, dx != nullptr, dout == nullptr);
 }

@@ -7,7 +7,9 @@
 import ast, cProfile, pstats, sys, os, io, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hcatgnet_amd as H
-from hcatgnet_amd import synth
+from hcatgnet_amd import synth, _lib
+if os.environ.get("HCG_LIB"):          # a library variant (A/B runs on one box)
+    _lib.LIB_PATH = os.path.abspath(os.environ["HCG_LIB"])
 cfg, kw = (sys.argv[1:2] or ["C2"])[0], {k: ast.literal_eval(v) for k, v in (a.split("=", 1) for a in sys.argv[2:])}
 sb = synth.make_config(cfg, **kw); m = H.make_network("GCN", H.default_options(), sb.x.shape[1]).cuda()
 print(f"config {cfg} {kw}: {sb.num_graphs} graphs, {sb.x.shape[0]} nodes, largest {sb.max_nodes}, n_small {sb.n_small}")

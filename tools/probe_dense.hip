@@ -322,24 +322,12 @@ static int launch_dense_fwd(const float* x, const float* W, const float* b, cons
   const size_t lds = dense_lds_bytes(npad, kpad);
   const dim3 grid(mid_grid(B, wgs_per_cu(lds))), blk(MT);
   const int coff = 0;
-#define LAUNCH_DENSE_FWD(KP, PL, VC)                                                                                       \
-  do {                                                                                                                     \
-    auto kfn = k_mid_dense_fwd<KP, PL, VC>;                                                                                \
-    hipError_t e = allow_big_lds<k_mid_dense_fwd<KP, PL, VC>>();                                                           \
-    if (e != hipSuccess) return hcg_hip_err(e);                                                                            \
-    hipLaunchKernelGGL(kfn, grid, blk, lds, stream, x, (int)F, W, b, edge_index, E, graph_ptr, edge_ptr, (int)B, npad,      \
-                       emax, slope, apply_act, out, (int)D, coff, emb, status);                                            \
-  } while (0)
   const bool vec = F == kpad && ((uintptr_t)x % 16 == 0);
-  if (kpad == 32) {
-    if (vec) { if (emb) LAUNCH_DENSE_FWD(32, true, true); else LAUNCH_DENSE_FWD(32, false, true); }
-    else     { if (emb) LAUNCH_DENSE_FWD(32, true, false); else LAUNCH_DENSE_FWD(32, false, false); }
-  } else {
-    if (vec) { if (emb) LAUNCH_DENSE_FWD(64, true, true); else LAUNCH_DENSE_FWD(64, false, true); }
-    else     { if (emb) LAUNCH_DENSE_FWD(64, true, false); else LAUNCH_DENSE_FWD(64, false, false); }
-  }
-#undef LAUNCH_DENSE_FWD
-  return hcg_hip_err(hipGetLastError());
+  return hcg_with_bools([&](auto K64, auto POOL, auto VEC) {
+    return hcg_launch<k_mid_dense_fwd<(K64 ? 64 : 32), POOL, VEC>>(grid, blk, lds, MID_LDS_LIMIT, stream, x, (int)F, W, b, edge_index, E,
+                                                                  graph_ptr, edge_ptr, (int)B, npad, emax, slope, apply_act, out, (int)D,
+                                                                  coff, emb, status);
+  }, kpad == 64, emb != nullptr, vec);
 }
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
