@@ -33,6 +33,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--early-stopping", type=int, default=6)
     ap.add_argument("--out", default=None, help="where to write embeddings.csv")
+    ap.add_argument("--fit", action="store_true", help="run the loop as ONE call of hcatgnet_amd.fit_network: schedule, early "
+                    "stopping and best weights kept on the device, the same lines printed from its log afterwards")
     args = ap.parse_args(argv)
     device = torch.device("cuda")
     opt = H.default_options()
@@ -51,6 +53,8 @@ def main(argv=None):
     test_loader = H.DeviceLoader(stores["test"], batch_size=opt.batch_size)
 
     model = H.make_network("GCN", opt, F).to(device)
+    if args.fit:
+        return fit_main(args, model, stores, train_loader, val_loader, test_loader, device, opt)
     val_best, best_epoch, stall, best_params = float("inf"), 0, 0, deepcopy(model.state_dict())
     # an epoch here is ~2 ms of host work; a full cyclic-GC pass over a process that imported torch is ~85 ms: keep what
     # exists now (torch, the datasets, the model) out of the collector's sight
@@ -77,6 +81,10 @@ def main(argv=None):
     print(f"training time: {time.time() - t0:.2f} s, best validation loss {val_best:.4f} at epoch {best_epoch}")
 
     model.load_state_dict(best_params)
+    return finish(args, model, stores, val_loader, test_loader, opt, val_best)
+
+
+def finish(args, model, stores, val_loader, test_loader, opt, val_best):
     y_pred, y_true, idx = predict_network(model, test_loader)
     print(f"test RMSE {float(np.sqrt(np.mean((y_pred - y_true) ** 2))):.4f} over {len(idx)} graphs")
     if args.out:
@@ -84,6 +92,20 @@ def main(argv=None):
                                                  "val": val_loader, "test": test_loader}, args.out)
         print(f"wrote {args.out}: {frame.shape[0]} rows x {frame.shape[1]} columns")
     return val_best
+
+
+def fit_main(args, model, stores, train_loader, val_loader, test_loader, device, opt):
+    """The same loop as one `fit_network` call (the best weights come back loaded into the model)."""
+    t0 = time.time()
+    res = H.fit_network(model, train_loader, val_loader, test_loader, device, epochs=args.epochs,
+                        early_stopping=args.early_stopping, control_every=5)
+    for epoch, (train_loss, val_loss, test_loss, _) in enumerate(res.log):
+        print(f"Epoch {epoch:03d} | Train loss: {train_loss:.3f} | Validation loss: {val_loss:.3f} | Test loss: {test_loss:.3f}")
+    if res.stopped_early and res.epochs_run < args.epochs:
+        print("Early stopping limit reached")
+    print(f"training time: {time.time() - t0:.2f} s, best validation loss {res.best_val:.4f} at epoch {res.best_epoch} "
+          f"({res.form} form, {res.epochs_enqueued} epochs enqueued for {res.epochs_run} counted)")
+    return finish(args, model, stores, val_loader, test_loader, opt, res.best_val)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,8 @@ Public surface (mirrors the reference's names for this path):
                                                 the reference's loops (utils/utils_model.py:55-111); the step as 6 launches
     io.load_processed_dir / write_embeddings_csv the reference's on-disk formats (reaction_N.pt in, embeddings.csv out)
     explain.set_masks / clear_masks             explain-mode edge masks (PyG Explainer hooks)
+    fit_network, fit_networks, FitResult        the reference's whole epoch loop (train_GNN.py:73-111) enqueued ahead of the GPU:
+                                                scheduler, early stopping, best weights and loss log kept on the device
     ExplainFit                                  GNNExplainer's whole mask optimisation of a batch of graphs in one launch
                                                 (the reference's first explain algorithm, explain_gnn.py)
     EnsemblePredict, stack_weights              M trained models predict one batch in one launch (the reference's
@@ -25,6 +27,7 @@ from .batch import Batch, Data, DataLoader, collate  # noqa: F401
 from .call_methods import default_options, make_network  # noqa: F401
 from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F401
 from .explain import ExplainFit, ExplainFitResult, ExplainFitState  # noqa: F401
+from .fit import FitControl, FitResult, fit_network, fit_networks  # noqa: F401
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
 from .networks import BaseNetwork  # noqa: F401
 from .plan import BatchPlan  # noqa: F401
@@ -34,4 +37,4 @@ from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
            "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "ExplainFit", "ExplainFitResult",
-           "ExplainFitState"]
+           "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl"]

@@ -23,6 +23,7 @@ HCG_WS_PLAN, HCG_WS_LINEAR, HCG_WS_GCN_LAYER_BWD, HCG_WS_READOUT2, HCG_WS_HEAD_D
 HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                          # hcg_fused_aux_bytes kinds
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
 HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS, HCG_STRUCT_EXPLAIN_ARGS = 5, 6, 7
+HCG_STRUCT_FIT_CONTROL_ARGS, HCG_STRUCT_FIT_STATE = 8, 9
 HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY, HCG_EXPLAIN_FIT = 0, 1, 2, 3, 4   # modes of hcg_explain
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
@@ -39,6 +40,7 @@ STATUS_BITS = {1: "edge_index entry outside [0, N)", 2: "batch vector not sorted
 STATUS_EDGE_UNGROUPED = 8
 
 P, I64, SZ, F32, INT = c_void_p, c_int64, c_size_t, c_float, c_int
+F64 = ctypes.c_double
 I32 = ctypes.c_int32
 
 
@@ -61,10 +63,26 @@ class TailArgs(ctypes.Structure):
                 ("peers_host", P), ("rank", I32), ("world", I32), ("xchg_mode", I32), ("update_rule", I32), ("xchg_err", P)]
 
 
+class FitState(ctypes.Structure):
+    """hcg_fit_state: the fit controller's DEVICE state (scheduler, early stopping, counters); the host initialises it and
+    reads it back."""
+    _fields_ = [("lr", F64), ("sched_best", F64), ("val_best", F64), ("epoch", I32), ("num_bad_epochs", I32),
+                ("cooldown_counter", I32), ("last_epoch", I32), ("best_epoch", I32), ("stall", I32), ("stopped", I32),
+                ("epochs_counted", I32)]
+
+
+class FitControlArgs(ctypes.Structure):
+    """hcg_fit_control_args: one launch of the fit controller behind an epoch's train / validation / test graphs."""
+    _fields_ = [("sums", P * 3), ("denom", F64 * 3), ("state", P), ("lr_dev", P), ("param", P), ("best", P), ("n", I64),
+                ("log", P), ("factor", F64), ("rel_epsilon", F64), ("min_lr", F64), ("eps", F64), ("patience", I32),
+                ("cooldown", I32), ("control_every", I32), ("early_stopping", I32), ("max_epochs", I32), ("reserved", I32)]
+
+
 class UpdateArgs(ctypes.Structure):
-    """hcg_update_args: every rule's capturable update, plain or in the data-parallel SSE form."""
+    """hcg_update_args: every rule's capturable update, plain or in the data-parallel SSE form; or, with `fit_control`
+    (the host address of a `FitControlArgs`), the fit controller's launch."""
     _fields_ = [("param", P), ("grad", P), ("exp_avg", P), ("exp_avg_sq", P), ("n", I64), ("lr_dev", P), ("step_dev", P),
-                ("loss", P), ("beta1", F32), ("beta2", F32), ("eps", F32), ("update_rule", I32)]
+                ("loss", P), ("beta1", F32), ("beta2", F32), ("eps", F32), ("update_rule", I32), ("fit_control", P)]
 
 
 class FusedFwdArgs(ctypes.Structure):
@@ -323,6 +341,14 @@ def update_dev(grad, *, rule: int = HCG_UPDATE_ADAM, param=None, exp_avg=None, e
     a.n, a.lr_dev, a.step_dev, a.loss = n, ptr(lr_dev), ptr(step_dev), ptr(loss)
     a.beta1, a.beta2, a.eps, a.update_rule = beta1, beta2, eps, rule
     check(load().hcg_update_dev(ctypes.addressof(a), stream_ptr()), "hcg_update_dev")
+
+
+def fit_control(args: FitControlArgs, stream=None):
+    """The fit controller (csrc/fit.hip: k_fit_control) on `stream` (default: the current one): hcg_update_dev with its
+    `fit_control` set -- the ABI's symbol count is capped, so the controller has no symbol of its own."""
+    a = UpdateArgs()
+    a.fit_control = ctypes.addressof(args)
+    check(load().hcg_update_dev(ctypes.addressof(a), stream_ptr() if stream is None else stream), "hcg_update_dev (fit control)")
 
 
 def layer_edge_grad(dout, out, h, rowptr, col, dinv, slope: float, apply_act: int, dew_csr, N: int, E: int, D: int):

@@ -127,6 +127,9 @@ int hcg_ensemble_launch(hcg_explain_args* p, hipStream_t stream);
 // ---- Shapley value sampling (shapley.hip), reached through hcg_explain, mode HCG_EXPLAIN_SHAPLEY -------------------------
 int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream);
 
+// ---- the fit controller (fit.hip), reached through hcg_update_dev (optim.hip): `fit_control` of hcg_update_args ----------
+int hcg_fit_control_launch(const hcg_fit_control_args* a, hipStream_t stream);
+
 // ---- one-graph-per-wave kernels (wave.hip), selected inside the hcg_mid_* entry points (mid.hip) ----------
 int hcg_w64_applicable(int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges);
 int hcg_w64_bwd_grid(int64_t B);

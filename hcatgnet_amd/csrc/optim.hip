@@ -126,6 +126,7 @@ extern "C" int hcg_adam_step_dev_sse(float* param, float* flat, float* exp_avg, 
 }
 
 extern "C" int hcg_update_dev(const hcg_update_args* a, hcg_stream_t stream_) {
+  if (a && a->fit_control) return hcg_fit_control_launch(a->fit_control, (hipStream_t)stream_);      // (fit.hip)
   if (!a || a->n <= 0 || !a->grad) return HCG_ERR_INVALID_ARG;
   const hipStream_t stream = (hipStream_t)stream_;
   if (!a->param) {                                     // the SSE form's scale and loss alone

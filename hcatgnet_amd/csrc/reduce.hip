@@ -308,6 +308,8 @@ extern "C" size_t hcg_struct_bytes(int which) {
     case HCG_STRUCT_UPDATE_ARGS: return sizeof(hcg_update_args);
     case HCG_STRUCT_HEAD_ARGS: return sizeof(hcg_head_args);
     case HCG_STRUCT_EXPLAIN_ARGS: return sizeof(hcg_explain_args);
+    case HCG_STRUCT_FIT_CONTROL_ARGS: return sizeof(hcg_fit_control_args);
+    case HCG_STRUCT_FIT_STATE: return sizeof(hcg_fit_state);
     default: return 0;
   }
 }

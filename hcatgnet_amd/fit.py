@@ -1,0 +1,393 @@
+"""A whole fit -- the reference's epoch loop (scripts_experiments/train_GNN.py:73-111, restated in
+examples/train_like_reference.py) -- without a host sync per epoch.
+
+  reference loop, per epoch                              here (`fit_network`, device form)
+  ---------------------------------------------------    ------------------------------------------------------------
+  train_network / eval_network x 2: three blocking       draw the permutation, upload the index arrays through a ring of
+      reads of a host float                                  pinned rows, replay the three hipGraphs (`train.EpochWindow`,
+                                                             the two forward-only `train.StepWindow`s)
+  every 5th epoch: model.scheduler.step(val_loss)        ONE launch of ONE workgroup behind them (csrc/fit.hip): the three
+      (ReduceLROnPlateau), stall counting,                   losses from the graphs' float64 sums, the scheduler, the
+      deepcopy(model.state_dict()) of the best epoch         early-stopping counters, the copy of the best weights and the
+                                                             loss log, all in device memory
+  `if stall > early_stopping: break`                     the host reads ONE flag per control interval, `lookahead`
+                                                             intervals behind what it has enqueued
+
+`FitControl` is that launch's state machine in plain Python: the host form of a fit (any loader / scheduler the device form
+does not take) runs on it, and the tests hold the kernel against it bit for bit.
+"""
+from __future__ import annotations
+
+import ctypes
+import time
+from collections import OrderedDict
+from copy import deepcopy
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import train as T
+from .optim import FusedFlatOptimizer
+
+
+class FitResult(NamedTuple):
+    log: np.ndarray             # [epochs_run, 4] float64: train, validation, test loss and the lr after the epoch
+    epochs_run: int             # epochs the loop counted (the reference's loop would have run exactly these)
+    stopped_early: bool         # the early-stopping limit was reached
+    best_epoch: int             # control epoch with the lowest validation loss
+    best_val: float
+    best_state: dict            # state-dict of clones: the weights after `best_epoch` (the initial ones if none was better)
+    epochs_enqueued: int        # epochs issued to the GPU: epochs_run <= ... <= epochs_run + lookahead * control_every
+    form: str = "device"        # "device" or "host"
+    enqueue_s: float = 0.0      # host seconds until the last epoch was issued (before the final synchronisation)
+
+
+def _plateau_of(model):
+    """The model's scheduler if the fit controller restates it: ReduceLROnPlateau, mode "min", threshold_mode "rel", one
+    parameter group (one min_lr)."""
+    sched = getattr(model, "scheduler", None)
+    if (isinstance(sched, torch.optim.lr_scheduler.ReduceLROnPlateau) and sched.mode == "min"
+            and sched.threshold_mode == "rel" and len(sched.optimizer.param_groups) == 1 and len(sched.min_lrs) == 1):
+        return sched
+    return None
+
+
+class FitControl:
+    """csrc/fit.hip's state machine on Python floats: per epoch `step(train, val, test)`; on a control epoch (`epoch %
+    control_every == 0`) torch's `ReduceLROnPlateau.step(val)` (mode "min", threshold_mode "rel") and then the example
+    loop's bookkeeping (best validation loss, stall count, `stopped = stall > early_stopping`).  `schedule=False`: the
+    caller steps a scheduler of its own and sets `lr`; only the bookkeeping and the log happen here."""
+
+    STATE = ("lr", "sched_best", "val_best", "epoch", "num_bad_epochs", "cooldown_counter", "last_epoch", "best_epoch",
+             "stall", "stopped", "epochs_counted")
+
+    def __init__(self, lr, factor=0.1, patience=10, threshold=1e-4, cooldown=0, min_lr=0.0, eps=1e-8, control_every=5,
+                 early_stopping=6, max_epochs=250, sched_best=float("inf"), num_bad_epochs=0, cooldown_counter=0,
+                 last_epoch=0, schedule=True):
+        self.factor, self.patience, self.rel_epsilon = float(factor), int(patience), 1.0 - threshold
+        self.cooldown, self.min_lr, self.eps = int(cooldown), float(min_lr), float(eps)
+        self.control_every, self.early_stopping, self.max_epochs = int(control_every), int(early_stopping), int(max_epochs)
+        self.schedule = bool(schedule)
+        self.lr, self.sched_best, self.val_best = float(lr), float(sched_best), float("inf")
+        self.epoch, self.num_bad_epochs, self.cooldown_counter, self.last_epoch = 0, int(num_bad_epochs), int(cooldown_counter), int(last_epoch)
+        self.best_epoch, self.stall, self.stopped, self.epochs_counted = 0, 0, 0, 0
+        self.log = []
+
+    @classmethod
+    def for_model(cls, model, control_every, early_stopping, max_epochs):
+        """Continue the model's scheduler where it stands (a fresh one: best = inf, counters 0)."""
+        lr, sched = float(model.optimizer.param_groups[0]["lr"]), _plateau_of(model)
+        if sched is None:
+            return cls(lr, control_every=control_every, early_stopping=early_stopping, max_epochs=max_epochs, schedule=False)
+        return cls(lr, sched.factor, sched.patience, sched.threshold, sched.cooldown, sched.min_lrs[0], sched.eps, control_every,
+                   early_stopping, max_epochs, sched.best, sched.num_bad_epochs, sched.cooldown_counter, sched.last_epoch)
+
+    def control_epoch(self) -> bool:
+        return self.epoch % self.control_every == 0
+
+    def live(self) -> bool:
+        return not self.stopped and self.epoch < self.max_epochs
+
+    def step(self, train, val, test) -> Optional[bool]:
+        """One epoch's losses -> whether the weights after it are the best so far (a snapshot is due); None = ignored (the
+        fit has stopped, or `max_epochs` rows are written)."""
+        if not self.live():
+            return None
+        train, val, test, snapshot = float(train), float(val), float(test), False
+        if self.control_epoch():
+            if self.schedule:
+                self.last_epoch += 1
+                if val < self.sched_best * self.rel_epsilon:
+                    self.sched_best, self.num_bad_epochs = val, 0
+                else:
+                    self.num_bad_epochs += 1
+                if self.cooldown_counter > 0:
+                    self.cooldown_counter -= 1
+                    self.num_bad_epochs = 0
+                if self.num_bad_epochs > self.patience:
+                    new = max(self.lr * self.factor, self.min_lr)
+                    if self.lr - new > self.eps:
+                        self.lr = new
+                    self.cooldown_counter, self.num_bad_epochs = self.cooldown, 0
+            if val < self.val_best:
+                self.val_best, self.best_epoch, self.stall, snapshot = val, self.epoch, 0, True
+            else:
+                self.stall += 1
+            self.stopped = int(self.stall > self.early_stopping)
+        self.log.append((train, val, test, self.lr))
+        self.epoch += 1
+        self.epochs_counted += 1
+        return snapshot
+
+    def state(self) -> dict:
+        return {k: getattr(self, k) for k in self.STATE}
+
+
+def _write_back(model, st: dict):
+    """The controller's state -> the host objects a caller goes on with: the group's lr, the optimiser's record of what its
+    device word holds (so `sync_lr()` pushes nothing stale), the scheduler's attributes."""
+    opt, sched = model.optimizer, _plateau_of(model)
+    opt.param_groups[0]["lr"] = st["lr"]
+    fl = getattr(opt, "_flat", {}).get(0)
+    if fl is not None and "lr_dev" in fl:
+        if fl["lr_host"] != st["lr"]:
+            fl["lr_dev"].fill_(st["lr"])
+        fl["lr_host"] = st["lr"]
+    if sched is not None:
+        sched.best, sched.num_bad_epochs = st["sched_best"], st["num_bad_epochs"]
+        sched.cooldown_counter, sched.last_epoch, sched._last_lr = st["cooldown_counter"], st["last_epoch"], [st["lr"]]
+
+
+def _result(model, fc_state, log, stopped, best_state, enqueued, form, enqueue_s, load_best):
+    if load_best:
+        model.load_state_dict(best_state)
+    return FitResult(np.asarray(log, dtype=np.float64).reshape(-1, 4), int(fc_state["epochs_counted"]), bool(stopped),
+                     int(fc_state["best_epoch"]), float(fc_state["val_best"]), best_state, int(enqueued), form, enqueue_s)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# host form: the example's loop
+# ---------------------------------------------------------------------------------------------------------------
+def _host_fit(model, train_loader, val_loader, test_loader, device, epochs, early_stopping, control_every, load_best):
+    fc = FitControl.for_model(model, control_every, early_stopping, epochs)
+    sched, group = getattr(model, "scheduler", None), model.optimizer.param_groups[0]
+    best_state = deepcopy(model.state_dict())
+    t0 = time.perf_counter()
+    for _ in range(epochs):
+        if fc.stopped:
+            break
+        train_loss = T.train_network(model, train_loader, device)
+        val_loss = T.eval_network(model, val_loader, device)
+        test_loss = T.eval_network(model, test_loader, device)
+        control = fc.control_epoch()
+        if control and not fc.schedule and sched is not None:
+            sched.step(val_loss)
+            fc.lr = float(group["lr"])
+        snapshot = fc.step(train_loss, val_loss, test_loss)
+        if control and fc.schedule:
+            _write_back(model, fc.state())
+        if snapshot:
+            best_state = deepcopy(model.state_dict())
+    st = fc.state()
+    return _result(model, st, fc.log, st["stopped"], best_state, st["epochs_counted"], "host", time.perf_counter() - t0, load_best)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# device form
+# ---------------------------------------------------------------------------------------------------------------
+class _HostForm(Exception):
+    """The device form does not take this fit (the reason is the message): the host form runs it."""
+
+
+class _DeviceFit:
+    """One fit in its device form, issued chunk by chunk on the stream that is current at each call: chunk 0 is epoch 0,
+    chunk c the epochs up to and including control epoch c * control_every; `check()` after each chunk is the look-ahead's
+    one read of the stop flag."""
+
+    def __init__(self, model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead):
+        self.model, self.loaders = model, (train_loader, val_loader, test_loader)
+        self.epochs, self.every, self.lookahead = epochs, control_every, lookahead
+        opt = model.optimizer
+        self.sched = _plateau_of(model)
+        if self.sched is None:
+            raise _HostForm("the scheduler is not a ReduceLROnPlateau with mode 'min', threshold_mode 'rel' and one group")
+        if not isinstance(opt, FusedFlatOptimizer) or len(opt.param_groups) != 1:
+            raise _HostForm("the optimiser is not one of the fused ones with one parameter group")
+        self.args = a = _lib.FitControlArgs()
+        self._resolve()                        # (the windows, built on first use: not a device form without all three)
+        dev, n = self.fl["p"].device, self.fl["n"]
+        s = self.sched
+        init = _lib.FitState()
+        init.lr, init.sched_best, init.val_best = float(opt.param_groups[0]["lr"]), float(s.best), float("inf")
+        init.num_bad_epochs, init.cooldown_counter, init.last_epoch = int(s.num_bad_epochs), int(s.cooldown_counter), int(s.last_epoch)
+        self.nstate = ctypes.sizeof(_lib.FitState)
+        self.state_dev = torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8).to(dev)
+        self.log_dev = torch.full((epochs, 4), float("nan"), dtype=torch.float64, device=dev)
+        self.best = self.fl["p"].clone()       # the reference keeps the initial state-dict until an epoch is better
+        a.state, a.best, a.n, a.log = self.state_dev.data_ptr(), self.best.data_ptr(), n, self.log_dev.data_ptr()
+        a.denom[0], a.denom[1], a.denom[2] = float(self.tw.G), float(len(val_loader.dataset)), float(len(test_loader.dataset))
+        a.factor, a.rel_epsilon, a.min_lr, a.eps = float(s.factor), 1.0 - s.threshold, float(s.min_lrs[0]), float(s.eps)
+        a.patience, a.cooldown, a.control_every = int(s.patience), int(s.cooldown), control_every
+        a.early_stopping, a.max_epochs = early_stopping, epochs
+        # pinned staging: one row of index arrays per epoch that can be in flight, one state row per unread control epoch
+        nrows = (lookahead + 1) * control_every + 1
+        self.rows = [torch.zeros_like(self.tw.host).pin_memory() for _ in range(nrows)]
+        self.row_events = [None] * nrows
+        self.state_pin = torch.zeros(lookahead + 1, self.nstate, dtype=torch.uint8).pin_memory()
+        self.state_events = [torch.cuda.Event() for _ in range(lookahead + 1)]
+        self.issued, self.controls, self.done, self.stop_seen = 0, 0, False, False
+        self.rng_states = []
+        self.t0, self.enqueue_s = time.perf_counter(), 0.0
+
+    def _resolve(self):
+        """The three windows and the optimiser's flat storages as they are NOW -> the launch's pointers.  A window whose
+        baked-in addresses were replaced since its capture (`load_state_dict` of the optimiser, a larger eager batch) is
+        dropped and built again, once, as `train._LoaderWindows.launch` does: nothing is written through an old pointer."""
+        model, opt = self.model, self.model.optimizer
+        kinds = (T._EPOCH_WINDOWS, T._EVAL_WINDOWS, T._EVAL_WINDOWS)
+        for attempt in range(2):
+            wins = [kind.of(model, ld, build=True) for kind, ld in zip(kinds, self.loaders)]
+            if any(w is None for w in wins):
+                raise _HostForm("a loader has no captured window (a host loader, a layer on the row-streaming kernels, a live "
+                                "multi-rank process group)")
+            steps = [wins[0].window, wins[1], wins[2]]
+            live = opt.capture_state()         # (flat storages and device words; a re-base here shows as a stale window)
+            stale = [not T._replayable(w.steps, w._fp, False) for w in steps]
+            if not any(stale):
+                break
+            if attempt:
+                raise _lib.HcgError("fit_network: a window went stale again right after it was rebuilt")
+            for ld, kind, bad in zip(self.loaders, kinds, stale):
+                if bad:
+                    setattr(ld, kind.attr, None)
+        fl = opt._flat[0]
+        if not opt.on_storages(live) or fl["params"][0].data_ptr() != fl["p"].data_ptr():
+            raise _lib.HcgError("fit_network: the optimiser's flat storages are not the model's parameters")
+        opt.sync_lr()
+        self.tw, self.vw, self.tew, self.fl = wins[0], wins[1], wins[2], fl
+        a = self.args
+        a.sums[0], a.sums[1], a.sums[2] = (w.value_dev.data_ptr() for w in steps)
+        a.lr_dev, a.param = fl["lr_dev"].data_ptr(), fl["p"].data_ptr()
+
+    def issue_chunk(self):
+        """Enqueue the epochs up to and including the next control epoch (or the last epoch) on the current stream."""
+        self._resolve()
+        tw, nrows = self.tw, len(self.rows)
+        rng = self.loaders[0].rng
+        while self.issued < self.epochs:
+            e = self.issued
+            order = tw.draw_order()
+            self.rng_states.append(rng.bit_generator.state)
+            r = e % nrows
+            if self.row_events[r] is None:
+                self.row_events[r] = torch.cuda.Event()
+            else:
+                self.row_events[r].synchronize()        # (the upload that read this row has long run)
+            tw.launch_epoch(order, staging=self.rows[r])
+            self.row_events[r].record()
+            self.vw.replay()
+            self.tew.replay()
+            _lib.fit_control(self.args)
+            self.issued += 1
+            if e % self.every == 0:
+                slot = self.controls % (self.lookahead + 1)
+                self.state_pin[slot].copy_(self.state_dev, non_blocking=True)
+                self.state_events[slot].record()
+                self.controls += 1
+                break
+        self.enqueue_s = time.perf_counter() - self.t0
+
+    def check(self) -> bool:
+        """After a chunk: wait for the control epoch `lookahead` chunks back, read its stop flag -> nothing more to issue."""
+        c = self.controls - 1 - self.lookahead
+        if c >= 0 and not self.stop_seen:
+            slot = c % (self.lookahead + 1)
+            self.state_events[slot].synchronize()
+            st = _lib.FitState.from_buffer_copy(self.state_pin[slot].numpy().tobytes())
+            self.stop_seen = bool(st.stopped)
+        self.done = self.stop_seen or self.issued >= self.epochs
+        return self.done
+
+    def finish(self, load_best) -> FitResult:
+        torch.cuda.current_stream().synchronize()
+        raw = _lib.FitState.from_buffer_copy(self.state_dev.cpu().numpy().tobytes())
+        st = {k: getattr(raw, k) for k in FitControl.STATE}
+        counted = st["epochs_counted"]
+        log = self.log_dev[:counted].cpu().numpy()
+        # the loader goes on as after the host loop: the epochs issued past the stop drew permutations it never would have
+        if counted < self.issued:
+            self.loaders[0].rng.bit_generator.state = self.rng_states[counted - 1]
+        _write_back(self.model, st)
+        self.model.eval()                      # (the loop's last call is an eval_network)
+        fl, off, offs = self.fl, 0, {}
+        for q in fl["params"]:
+            offs[id(q)] = off
+            off += q.numel()
+        best_state = OrderedDict()
+        for k, v in self.model.state_dict(keep_vars=True).items():
+            o = offs.get(id(v))
+            best_state[k] = (self.best[o:o + v.numel()].view(v.shape).clone() if o is not None else v.detach().clone())
+        return _result(self.model, st, log, st["stopped"], best_state, self.issued, "device", self.enqueue_s, load_best)
+
+
+def _check_args(epochs, early_stopping, control_every, lookahead):
+    if int(epochs) < 1:
+        raise ValueError(f"epochs must be at least 1, got {epochs}")
+    if int(control_every) < 1:
+        raise ValueError(f"control_every must be at least 1, got {control_every}")
+    if int(lookahead) < 0:
+        raise ValueError(f"lookahead must not be negative, got {lookahead}")
+    if int(early_stopping) < 0:
+        raise ValueError(f"early_stopping must not be negative, got {early_stopping}")
+    return int(epochs), int(early_stopping), int(control_every), int(lookahead)
+
+
+def fit_network(model, train_loader, val_loader, test_loader, device, epochs=250, early_stopping=6, control_every=5,
+                lookahead=1, load_best=True) -> FitResult:
+    """The reference's whole epoch loop for one model (scripts_experiments/train_GNN.py:73-111): per epoch train, validate,
+    test; on every `control_every`-th epoch (0, control_every, ...) `model.scheduler.step(val_loss)`, the best validation
+    loss with a copy of its weights, and the stall count that ends the fit once it exceeds `early_stopping`.
+
+    Device form (loaders are `DeviceLoader`s whose epochs are captured windows, a fused optimiser, a ReduceLROnPlateau
+    with mode "min" / threshold_mode "rel" and one group): every epoch is enqueued without a blocking read -- the
+    permutation from the loader's own generator, the index upload, three graph replays, one controller launch
+    (csrc/fit.hip) that keeps schedule, stop decision, best weights and log on the device.  The host reads the stop flag of
+    the control epoch `lookahead` intervals behind the one it has just enqueued:
+      lookahead = 0   waits on every control epoch: exact in every respect, one sync per `control_every` epochs;
+      lookahead > 0   up to lookahead * control_every epochs past the stop have been issued.  The controller ignores them
+                      (no log row, no snapshot, no lr change) and the loader's generator is put back, but they DO move the
+                      live weights, the optimiser's moments and its step count.
+    `load_best=True` (what the reference does next, utils/utils_model.py:170) loads `best_state` into the model, so the
+    model handed back does not depend on `lookahead`.  Log, best state, scheduler and lr are bitwise the host loop's.
+    Any other case runs the host form in the same call: the example's loop over `train_network` / `eval_network`."""
+    epochs, early_stopping, control_every, lookahead = _check_args(epochs, early_stopping, control_every, lookahead)
+    try:
+        run = _DeviceFit(model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead)
+    except _HostForm:
+        return _host_fit(model, train_loader, val_loader, test_loader, device, epochs, early_stopping, control_every, load_best)
+    while not run.done:
+        run.issue_chunk()
+        run.check()
+    return run.finish(load_best)
+
+
+def fit_networks(models, train_loaders, val_loaders, test_loaders, device, epochs=250, early_stopping=6, control_every=5,
+                 lookahead=1, load_best=True, active=None) -> list:
+    """`fit_network` of several independent runs at once (see `train.train_networks`) -> [FitResult] (None where
+    `active[k]` is false).  Every run in the device form goes on its own stream with its own controller; each round issues
+    one chunk of every live run before any stop flag is waited for, and a run that stops drops out.  Each run is bitwise the
+    run alone.  Runs in the host form are fitted in turn."""
+    models = list(models)
+    K = len(models)
+    if any(len(x) != K for x in (train_loaders, val_loaders, test_loaders)) or (active is not None and len(active) != K):
+        raise ValueError("fit_networks: one train, validation and test loader (and one `active` flag) per model")
+    epochs, early_stopping, control_every, lookahead = _check_args(epochs, early_stopping, control_every, lookahead)
+    out, runs, host = [None] * K, [], []
+    cur = torch.cuda.current_stream(device)
+    for k, m in enumerate(models):
+        if active is not None and not active[k]:
+            continue
+        st = T._run_stream(m, device)
+        st.wait_stream(cur)
+        with torch.cuda.stream(st):
+            try:
+                runs.append((k, st, _DeviceFit(m, train_loaders[k], val_loaders[k], test_loaders[k], epochs, early_stopping,
+                                               control_every, lookahead)))
+            except _HostForm:
+                host.append(k)
+    live = list(runs)
+    while live:
+        for _, st, run in live:
+            with torch.cuda.stream(st):
+                run.issue_chunk()
+        live = [(k, st, run) for k, st, run in live if not run.check()]
+    for k, st, run in runs:
+        with torch.cuda.stream(st):
+            out[k] = run.finish(load_best)
+        cur.wait_stream(st)
+    for k in host:
+        out[k] = _host_fit(models[k], train_loaders[k], val_loaders[k], test_loaders[k], device, epochs, early_stopping,
+                           control_every, load_best)
+    return out

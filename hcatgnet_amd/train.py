@@ -1118,12 +1118,13 @@ class EpochWindow:
         if not opt.on_storages(live):
             raise _lib.HcgError("EpochWindow: the optimiser re-based its state during the capture")
 
-    def _layout(self, order):
-        """The epoch's index arrays (`store.epoch_layout`) for the graphs in this order -> device."""
+    def _layout(self, order, staging=None):
+        """The epoch's index arrays (`store.epoch_layout`) for the graphs in this order -> device, through the window's pinned
+        buffer or `staging` (a pinned int64 row like `self.host`, the caller's to keep intact until the copy has run)."""
         from .store import epoch_layout
-        st = self.loader.store
-        epoch_layout(st.n_host, st.e_host, *self.batching, order, out=self.host.numpy())
-        self.dbuf.copy_(self.host, non_blocking=True)
+        st, host = self.loader.store, (self.host if staging is None else staging)
+        epoch_layout(st.n_host, st.e_host, *self.batching, order, out=host.numpy())
+        self.dbuf.copy_(host, non_blocking=True)
 
     def draw_order(self):
         """The next permutation of the loader's generator (what iterating the loader would have drawn)."""
@@ -1131,12 +1132,13 @@ class EpochWindow:
         ld = self.loader
         return ld.rng.permutation(self.G) if ld.shuffle else np.arange(self.G)
 
-    def launch_epoch(self, order=None):
+    def launch_epoch(self, order=None, staging=None):
         """Issue the epoch on the current stream (index upload + ONE graph launch), no synchronisation; `finish_epoch` reads
-        its value.  One epoch in flight per window (the pinned index buffer is rewritten by the next launch)."""
+        its value.  One epoch in flight per window (the pinned index buffer is rewritten by the next launch) -- unless every
+        epoch in flight has a `staging` row of its own (`_layout`; fit.py keeps a ring of them)."""
         if order is None:
             order = self.draw_order()
-        self._layout(order)
+        self._layout(order, staging)
         return self.window.replay()
 
     def finish_epoch(self, losses) -> float:

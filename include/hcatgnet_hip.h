@@ -608,6 +608,8 @@ typedef struct hcg_reduce_job {
 #define HCG_STRUCT_UPDATE_ARGS 5
 #define HCG_STRUCT_HEAD_ARGS 6
 #define HCG_STRUCT_EXPLAIN_ARGS 7
+#define HCG_STRUCT_FIT_CONTROL_ARGS 8
+#define HCG_STRUCT_FIT_STATE 9   /* (a DEVICE struct the host reads back: hcg_fit_state) */
 size_t hcg_struct_bytes(int which);
 int hcg_fused_reduce_job(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F,
                          int64_t D, int graphs_per_tile, float* dW, float* db, hcg_reduce_job* job_host);
@@ -705,8 +707,45 @@ int hcg_adam_step_dev_sse(float* param, float* flat, float* exp_avg, float* exp_
                           const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_dev, float* loss,
                           hcg_stream_t stream);
 
+/* ---- fit control: what the reference's epoch loop does on the host between two epochs (scripts_experiments/
+ * train_GNN.py:73-111: ReduceLROnPlateau, early stopping, the copy of the best weights, the loss log), as ONE launch of ONE
+ * workgroup behind an epoch's train / validation / test graphs on the same stream, so that a whole fit is enqueued without
+ * the host reading a loss.  Reached through hcg_update_dev (`fit_control` of hcg_update_args: the exported symbols are
+ * capped, tests/test_host_cpu.py); enqueue-only, owns no memory.
+ * Thread 0, in float64 with every product, quotient and comparison the one Python's floats make on the host:
+ *   stopped, or epoch >= max_epochs: nothing at all is written;
+ *   loss_k = *sums[k] / denom[k] (k = train, validation, test); log[epoch] = {train, validation, test, lr after the epoch};
+ *   epoch % control_every == 0: torch's ReduceLROnPlateau.step(validation) for mode "min", threshold_mode "rel" (better:
+ *     a < best * rel_epsilon, rel_epsilon = 1 - threshold formed by the host; cooldown; num_bad_epochs > patience:
+ *     new = max(lr * factor, min_lr), taken when lr - new > eps, then *lr_dev = (float)lr), then the loop's bookkeeping:
+ *     validation < val_best: val_best, best_epoch = epoch, stall = 0, snapshot; else ++stall; stopped = stall > early_stopping;
+ *   ++epoch, ++epochs_counted.
+ * A NaN loss is never better (IEEE comparisons, as on the host).  On a snapshot the whole workgroup copies param [n] into
+ * best [n] (16-byte accesses where both are 16-byte aligned, a scalar tail); thread 0 stores the state last. */
+typedef struct hcg_fit_state {   /* DEVICE struct, caller-initialised */
+  double lr;                   /* the learning rate (param_groups[0]["lr"]) */
+  double sched_best;           /* ReduceLROnPlateau.best (+inf at the start) */
+  double val_best;             /* best validation loss seen on a control epoch (+inf at the start) */
+  int32_t epoch;               /* epochs seen = row of the log the next launch writes */
+  int32_t num_bad_epochs, cooldown_counter, last_epoch;   /* ReduceLROnPlateau's */
+  int32_t best_epoch, stall, stopped, epochs_counted;
+} hcg_fit_state;
+typedef struct hcg_fit_control_args {   /* HOST struct; zero it first */
+  const double* sums[3];       /* device scalars: dot(losses, counts) of the train, validation and test epoch */
+  double denom[3];             /* their denominators (graphs of each dataset), > 0 */
+  hcg_fit_state* state;
+  float* lr_dev;               /* the optimiser's learning-rate word */
+  const float* param;          /* [n] the flat parameters (read) */
+  float* best;                 /* [n] the best slot (written on a snapshot) */
+  int64_t n;
+  double* log;                 /* [max_epochs, 4] */
+  double factor, rel_epsilon, min_lr, eps;
+  int32_t patience, cooldown, control_every, early_stopping, max_epochs, reserved;
+} hcg_fit_control_args;
+
 /* Every rule's capturable update (HCG_UPDATE_*) with hcg_adam_step_dev's step-word contract (step_dev = [count, stamp,
  * ticket, pad]: count advanced by one, stamp untouched, ticket zero between launches), plain or in the SSE form.
+ *   fit_control != NULL: the launch is the fit controller above and nothing else of this struct is read;
  *   loss == NULL: `grad` = [n] gradients;
  *   loss != NULL: `grad` = [n summed SSE/2-gradients | SSE | count], scaled in place by 1 / (count * L), L = sqrt(SSE /
  *                 count); loss[0] = L, loss[1] = SSE / count;
@@ -724,6 +763,7 @@ typedef struct hcg_update_args {
   float* loss;                 /* NULL = plain form */
   float beta1, beta2, eps;
   int32_t update_rule;         /* HCG_UPDATE_* */
+  const hcg_fit_control_args* fit_control;   /* HOST pointer; NULL = an update */
 } hcg_update_args;
 int hcg_update_dev(const hcg_update_args* args_host, hcg_stream_t stream);
 
