@@ -35,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="where to write embeddings.csv")
     ap.add_argument("--fit", action="store_true", help="run the loop as ONE call of hcatgnet_amd.fit_network: schedule, early "
                     "stopping and best weights kept on the device, the same lines printed from its log afterwards")
+    ap.add_argument("--form", choices=("epoch", "chunk"), default="epoch", help="with --fit: 'chunk' draws the shuffle on the "
+                    "device and issues a control interval of epochs as one graph launch (same results)")
     args = ap.parse_args(argv)
     device = torch.device("cuda")
     opt = H.default_options()
@@ -98,13 +100,14 @@ def fit_main(args, model, stores, train_loader, val_loader, test_loader, device,
     """The same loop as one `fit_network` call (the best weights come back loaded into the model)."""
     t0 = time.time()
     res = H.fit_network(model, train_loader, val_loader, test_loader, device, epochs=args.epochs,
-                        early_stopping=args.early_stopping, control_every=5)
+                        early_stopping=args.early_stopping, control_every=5, form=args.form)
     for epoch, (train_loss, val_loss, test_loss, _) in enumerate(res.log):
         print(f"Epoch {epoch:03d} | Train loss: {train_loss:.3f} | Validation loss: {val_loss:.3f} | Test loss: {test_loss:.3f}")
     if res.stopped_early and res.epochs_run < args.epochs:
         print("Early stopping limit reached")
     print(f"training time: {time.time() - t0:.2f} s, best validation loss {res.best_val:.4f} at epoch {res.best_epoch} "
-          f"({res.form} form, {res.epochs_enqueued} epochs enqueued for {res.epochs_run} counted)")
+          f"({res.form} form, {res.epochs_enqueued} epochs enqueued for {res.epochs_run} counted, {res.graph_launches} graph "
+          f"launches)")
     return finish(args, model, stores, val_loader, test_loader, opt, res.best_val)
 
 

@@ -24,6 +24,8 @@ HCG_FUSED_POOLBITS, HCG_FUSED_HEAD_WS = 0, 1                                    
 HCG_STRUCT_REDUCE_JOB, HCG_STRUCT_TAIL_ARGS, HCG_STRUCT_FUSED_FWD_ARGS, HCG_STRUCT_COLLATE_ARGS, HCG_STRUCT_COLLATE_SLOT = 0, 1, 2, 3, 4   # hcg_struct_bytes
 HCG_STRUCT_UPDATE_ARGS, HCG_STRUCT_HEAD_ARGS, HCG_STRUCT_EXPLAIN_ARGS = 5, 6, 7
 HCG_STRUCT_FIT_CONTROL_ARGS, HCG_STRUCT_FIT_STATE = 8, 9
+HCG_STRUCT_EPOCH_DRAW_ARGS, HCG_STRUCT_PCG64 = 10, 11
+HCG_EPOCH_DRAW_MAX_GRAPHS = 8192                         # graphs one hcg_collate draw launch takes (its workgroup's LDS)
 HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY, HCG_EXPLAIN_FIT = 0, 1, 2, 3, 4   # modes of hcg_explain
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
@@ -132,11 +134,24 @@ class CollateSlot(ctypes.Structure):
                 ("y_out", P), ("idx_out", P), ("B", I64), ("N_out", I64), ("E_out", I64)]
 
 
+class Pcg64(ctypes.Structure):
+    """hcg_pcg64: numpy's PCG64 state in DEVICE memory (`np.random.PCG64().state`, the 128-bit integers as two words)."""
+    _fields_ = [("state_lo", ctypes.c_uint64), ("state_hi", ctypes.c_uint64), ("inc_lo", ctypes.c_uint64),
+                ("inc_hi", ctypes.c_uint64), ("has_uint32", ctypes.c_uint32), ("uinteger", ctypes.c_uint32)]
+
+
+class EpochDrawArgs(ctypes.Structure):
+    """hcg_epoch_draw_args: one epoch's permutation and index arrays drawn on the device (csrc/shuffle.hip)."""
+    _fields_ = [("rng", P), ("layout", P), ("gate", P), ("G", I64), ("batch_size", I32), ("drop_last", I32),
+                ("gate_max_epochs", I32), ("reserved", I32)]
+
+
 class CollateArgs(ctypes.Structure):
-    """hcg_collate_args: the dataset + one slot (host values) or a device array of slots."""
+    """hcg_collate_args: the dataset + one slot (host values) or a device array of slots; or, with `epoch_draw` (the host
+    address of an `EpochDrawArgs`), the draw launch."""
     _fields_ = [("x_all", P), ("src_all", P), ("dst_all", P), ("node_ptr_all", P), ("edge_ptr_all", P), ("y_all", P),
                 ("idx_all", P), ("F", I64), ("nslots", I32), ("reserved", I32), ("slot", CollateSlot), ("slots_dev", P),
-                ("max_B", I64)]
+                ("max_B", I64), ("epoch_draw", P)]
 
 
 # name -> (restype, argtypes); must list every symbol of include/hcatgnet_hip.h
@@ -349,6 +364,15 @@ def fit_control(args: FitControlArgs, stream=None):
     a = UpdateArgs()
     a.fit_control = ctypes.addressof(args)
     check(load().hcg_update_dev(ctypes.addressof(a), stream_ptr() if stream is None else stream), "hcg_update_dev (fit control)")
+
+
+def epoch_draw(dataset: CollateArgs, draw: EpochDrawArgs, stream=None):
+    """One epoch's shuffle and index arrays (csrc/shuffle.hip: k_epoch_draw) on `stream` (default: the current one):
+    hcg_collate with its `epoch_draw` set, `dataset` lending node_ptr_all / edge_ptr_all -- like the fit controller the
+    launch has no symbol of its own."""
+    a = CollateArgs.from_buffer_copy(dataset)
+    a.epoch_draw = ctypes.addressof(draw)
+    check(load().hcg_collate(ctypes.byref(a), stream_ptr() if stream is None else stream), "hcg_collate (epoch draw)")
 
 
 def layer_edge_grad(dout, out, h, rowptr, col, dinv, slope: float, apply_act: int, dew_csr, N: int, E: int, D: int):

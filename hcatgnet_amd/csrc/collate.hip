@@ -76,6 +76,7 @@ __global__ __launch_bounds__(256) void k_collate(Dataset ds, hcg_collate_slot on
 }  // namespace
 
 extern "C" int hcg_collate(const hcg_collate_args* a, hcg_stream_t stream) {
+  if (a && a->epoch_draw) return hcg_epoch_draw_launch(a, (hipStream_t)stream);      // (shuffle.hip)
   if (!a || a->nslots < 1 || a->F <= 0 || a->F >= (1 << 20)) return HCG_ERR_INVALID_ARG;
   if (!a->x_all || !a->node_ptr_all || !a->edge_ptr_all) return HCG_ERR_INVALID_ARG;
   const Dataset ds{a->x_all, a->src_all, a->dst_all, a->node_ptr_all, a->edge_ptr_all, a->y_all, a->idx_all, (int)a->F};

@@ -130,6 +130,10 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream);
 // ---- the fit controller (fit.hip), reached through hcg_update_dev (optim.hip): `fit_control` of hcg_update_args ----------
 int hcg_fit_control_launch(const hcg_fit_control_args* a, hipStream_t stream);
 
+// ---- an epoch's shuffle and index arrays (shuffle.hip), reached through hcg_collate (collate.hip): `epoch_draw` of
+//      hcg_collate_args, not NULL ----------
+int hcg_epoch_draw_launch(const hcg_collate_args* c, hipStream_t stream);
+
 // ---- one-graph-per-wave kernels (wave.hip), selected inside the hcg_mid_* entry points (mid.hip) ----------
 int hcg_w64_applicable(int64_t F, int64_t D, int64_t max_nodes, int64_t max_edges);
 int hcg_w64_bwd_grid(int64_t B);

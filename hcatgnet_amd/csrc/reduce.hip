@@ -310,6 +310,8 @@ extern "C" size_t hcg_struct_bytes(int which) {
     case HCG_STRUCT_EXPLAIN_ARGS: return sizeof(hcg_explain_args);
     case HCG_STRUCT_FIT_CONTROL_ARGS: return sizeof(hcg_fit_control_args);
     case HCG_STRUCT_FIT_STATE: return sizeof(hcg_fit_state);
+    case HCG_STRUCT_EPOCH_DRAW_ARGS: return sizeof(hcg_epoch_draw_args);
+    case HCG_STRUCT_PCG64: return sizeof(hcg_pcg64);
     default: return 0;
   }
 }

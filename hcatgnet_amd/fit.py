@@ -13,6 +13,10 @@ examples/train_like_reference.py) -- without a host sync per epoch.
   `if stall > early_stopping: break`                     the host reads ONE flag per control interval, `lookahead`
                                                              intervals behind what it has enqueued
 
+`form="chunk"` takes the first row's host work away too: the permutation and the index arrays are made on the device
+(csrc/shuffle.hip, `store.DeviceGenerator`), and a control interval of epochs -- draw, three epochs' steps, controller,
+`control_every` times over -- is ONE hipGraph (`ChunkWindow`), bitwise the form above.
+
 `FitControl` is that launch's state machine in plain Python: the host form of a fit (any loader / scheduler the device form
 does not take) runs on it, and the tests hold the kernel against it bit for bit.
 """
@@ -40,8 +44,9 @@ class FitResult(NamedTuple):
     best_val: float
     best_state: dict            # state-dict of clones: the weights after `best_epoch` (the initial ones if none was better)
     epochs_enqueued: int        # epochs issued to the GPU: epochs_run <= ... <= epochs_run + lookahead * control_every
-    form: str = "device"        # "device" or "host"
+    form: str = "device"        # "device", "device-chunk" or "host"
     enqueue_s: float = 0.0      # host seconds until the last epoch was issued (before the final synchronisation)
+    graph_launches: int = 0     # hipGraph launches issued: three per epoch in the device form, one per chunk in the chunk form
 
 
 def _plateau_of(model):
@@ -140,11 +145,12 @@ def _write_back(model, st: dict):
         sched.cooldown_counter, sched.last_epoch, sched._last_lr = st["cooldown_counter"], st["last_epoch"], [st["lr"]]
 
 
-def _result(model, fc_state, log, stopped, best_state, enqueued, form, enqueue_s, load_best):
+def _result(model, fc_state, log, stopped, best_state, enqueued, form, enqueue_s, load_best, graph_launches=0):
     if load_best:
         model.load_state_dict(best_state)
     return FitResult(np.asarray(log, dtype=np.float64).reshape(-1, 4), int(fc_state["epochs_counted"]), bool(stopped),
-                     int(fc_state["best_epoch"]), float(fc_state["val_best"]), best_state, int(enqueued), form, enqueue_s)
+                     int(fc_state["best_epoch"]), float(fc_state["val_best"]), best_state, int(enqueued), form, enqueue_s,
+                     int(graph_launches))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -296,9 +302,7 @@ class _DeviceFit:
         st = {k: getattr(raw, k) for k in FitControl.STATE}
         counted = st["epochs_counted"]
         log = self.log_dev[:counted].cpu().numpy()
-        # the loader goes on as after the host loop: the epochs issued past the stop drew permutations it never would have
-        if counted < self.issued:
-            self.loaders[0].rng.bit_generator.state = self.rng_states[counted - 1]
+        self._settle_generator(counted)
         _write_back(self.model, st)
         self.model.eval()                      # (the loop's last call is an eval_network)
         fl, off, offs = self.fl, 0, {}
@@ -309,10 +313,283 @@ class _DeviceFit:
         for k, v in self.model.state_dict(keep_vars=True).items():
             o = offs.get(id(v))
             best_state[k] = (self.best[o:o + v.numel()].view(v.shape).clone() if o is not None else v.detach().clone())
-        return _result(self.model, st, log, st["stopped"], best_state, self.issued, "device", self.enqueue_s, load_best)
+        return _result(self.model, st, log, st["stopped"], best_state, self.issued, self.form, self.enqueue_s, load_best,
+                       self._graph_launches())
+
+    form = "device"
+
+    def _settle_generator(self, counted):
+        """The loader goes on as after the host loop: the epochs issued past the stop drew permutations it never would have."""
+        if counted < self.issued:
+            self.loaders[0].rng.bit_generator.state = self.rng_states[counted - 1]
+
+    def _graph_launches(self) -> int:
+        return 3 * self.issued
 
 
-def _check_args(epochs, early_stopping, control_every, lookahead):
+# ---------------------------------------------------------------------------------------------------------------
+# chunk form: a control interval of epochs as ONE graph, the shuffle drawn on the device
+# ---------------------------------------------------------------------------------------------------------------
+class _EpochForm(Exception):
+    """The chunk form does not take this fit (the reason is the message): the device form runs it, epoch by epoch."""
+
+
+class ChunkWindow:
+    """`L` consecutive epochs of a fit as ONE hipGraph, recorded per epoch in the order the device form issues them:
+      the draw and layout launch (csrc/shuffle.hip) into the `EpochWindow`'s index buffer, gated on the fit state;
+      the train epoch -- the `EpochWindow`'s own `FusedTrainStep`s, slot batches and collate launch -- and its float64 sum;
+      the validation and the test steps of the two forward-only windows with their sums;
+      the controller launch (csrc/fit.hip), `sums` pointing at this graph's own three sum tensors of that epoch.
+    Nothing comes from the host between two epochs, so a replay is one launch whatever `L`.  The capture's warm-up runs all of
+    it once; `ChunkWindows.build` takes that back (weights, optimiser, controller, generator, index buffer)."""
+
+    def __init__(self, cs, L: int):
+        self.cs, self.L = cs, int(L)
+        tw, vw, tew = cs.wins
+        self.parts = (tw.window, vw, tew)
+        self.steps = [st for w in self.parts for st in w.steps]
+        self.sums = None
+
+        def run():
+            a, sums = cs.args, []
+            for _ in range(self.L):
+                if cs.shuffle:
+                    cs.gen.draw(tw.dbuf, gate=cs.state_dev, max_epochs=cs.epochs)
+                three = []
+                for w in self.parts:
+                    losses = [st(b() if callable(b) else b, _forward_only=w.forward_only) for st, b in zip(w.steps, w.batches)]
+                    three.append(T._weighted_loss_dev(losses, w.counts64))
+                a.sums[0], a.sums[1], a.sums[2] = (s.data_ptr() for s in three)
+                _lib.fit_control(a)
+                sums.append(three)
+            return sums
+        cap = T._Capture(cs.model.optimizer, True, run)
+        self.graph = cap.graph
+        with cap.recording():
+            self.sums = run()                   # (kept alive: the graph's controller launches read them)
+        self._fp = [st._graph_fingerprint() for st in self.steps]
+
+    def replayable(self) -> bool:
+        return T._replayable(self.steps, self._fp, True)
+
+    def replay(self):
+        if not self.replayable():
+            raise _lib.HcgError("ChunkWindow.replay(): parameter / optimiser / step buffers changed since the capture: build it again")
+        self.graph.replay()
+
+
+class ChunkWindows:
+    """What a fit in the chunk form replays, kept on the train loader for the next fit of the same model and settings: the
+    one-epoch graph (epoch 0 and a tail) and the `control_every`-epoch graph, and the device memory they have baked in -- the
+    controller's state, log and best slot, the loader's generator (`store.DeviceGenerator`).  `max_epochs`, the scheduler's
+    constants and the stop limit are launch arguments of the recorded controller, so they are part of `key`."""
+
+    ATTR = "_hcg_chunk_windows"
+
+    @staticmethod
+    def key_of(sched, loaders, epochs, early_stopping, control_every):
+        return (epochs, early_stopping, control_every, float(sched.factor), float(sched.threshold), int(sched.patience),
+                int(sched.cooldown), float(sched.min_lrs[0]), float(sched.eps), bool(loaders[0].shuffle))
+
+    @classmethod
+    def of(cls, model, loaders, wins, fl, epochs, early_stopping, control_every, build=True):
+        """The train loader's windows for this model, loaders and settings (`wins`: the three loaders' captured windows as
+        they are now, `fl`: the optimiser's flat storages), built on first use; a set whose baked-in addresses were replaced
+        since is dropped and built again.  None: the capture failed (kept: not tried again for the same key)."""
+        sched, trn = _plateau_of(model), loaders[0]
+        key = cls.key_of(sched, loaders, epochs, early_stopping, control_every)
+        ent = getattr(trn, cls.ATTR, None)
+        if ent is not None and ent[0] is model and ent[1] == key and all(a is b for a, b in zip(ent[2], loaders)):
+            cs = ent[3]
+            if cs is None or (all(a is b for a, b in zip(cs.wins, wins)) and cs.fl is fl
+                              and all(g.replayable() for g in cs.graphs.values())):
+                return cs
+        if not build:
+            return None
+        try:
+            cs = cls(model, loaders, wins, fl, epochs, early_stopping, control_every)
+        except (_lib.HcgError, RuntimeError):       # refused, or the capture failed (memory, an unsupported launch)
+            cs = None
+        try:
+            setattr(trn, cls.ATTR, (model, key, tuple(loaders), cs))
+        except Exception:
+            pass
+        return cs
+
+    def __init__(self, model, loaders, wins, fl, epochs, early_stopping, control_every):
+        from .store import DeviceGenerator
+        self.model, self.loaders, self.wins, self.fl = model, tuple(loaders), tuple(wins), fl
+        self.epochs, self.every, self.shuffle = epochs, control_every, bool(loaders[0].shuffle)
+        tw, s, dev = wins[0], _plateau_of(model), fl["p"].device
+        self.gen = DeviceGenerator(loaders[0])
+        self.nstate = ctypes.sizeof(_lib.FitState)
+        self.state_dev = torch.zeros(self.nstate, dtype=torch.uint8, device=dev)
+        self.log_dev = torch.full((epochs, 4), float("nan"), dtype=torch.float64, device=dev)
+        self.best = fl["p"].clone()
+        self.pins = {}
+        self.args = a = _lib.FitControlArgs()
+        a.state, a.best, a.n, a.log = self.state_dev.data_ptr(), self.best.data_ptr(), fl["n"], self.log_dev.data_ptr()
+        a.lr_dev, a.param = fl["lr_dev"].data_ptr(), fl["p"].data_ptr()
+        a.denom[0], a.denom[1], a.denom[2] = float(tw.G), float(len(loaders[1].dataset)), float(len(loaders[2].dataset))
+        a.factor, a.rel_epsilon, a.min_lr, a.eps = float(s.factor), 1.0 - s.threshold, float(s.min_lrs[0]), float(s.eps)
+        a.patience, a.cooldown, a.control_every = int(s.patience), int(s.cooldown), control_every
+        a.early_stopping, a.max_epochs = early_stopping, epochs
+        self.reset()                            # (the warm-ups run on a fit's first state, not on zeros)
+        # every capture's warm-up is L hidden epochs: taken back in place, as `train.EpochWindow` does -- also when a capture
+        # fails, since the caller then fits on in the device form
+        opt = model.optimizer
+        live = opt.capture_state()
+        if not opt.on_storages([fl["p"]]):
+            raise _lib.HcgError("ChunkWindows: the optimiser re-based its state before the capture")
+        held = list(live) + [fl["lr_dev"], self.state_dev, self.log_dev, self.best, self.gen.state_dev, tw.dbuf]
+        saved = [t.clone() for t in held]
+        self.graphs = {}
+        try:
+            for L in sorted({1, control_every}):
+                self.graphs[L] = ChunkWindow(self, L)
+                torch.cuda.synchronize()
+                with torch.no_grad():           # (each graph's warm-up starts where a fit would)
+                    for t, u in zip(held, saved):
+                        t.copy_(u)
+        finally:
+            torch.cuda.synchronize()
+            with torch.no_grad():
+                for t, u in zip(held, saved):
+                    t.copy_(u)
+            torch.cuda.synchronize()
+        if not opt.on_storages(live):
+            raise _lib.HcgError("ChunkWindows: the optimiser re-based its state during the capture")
+
+    def reset(self):
+        """A fit's start on the current stream: the controller's first state from the model's scheduler, an empty log, the
+        best slot = the weights as they are, the loader's generator moved up; a loader that does not shuffle gets its
+        (identity) index arrays once."""
+        opt, s = self.model.optimizer, _plateau_of(self.model)
+        init = _lib.FitState()
+        init.lr, init.sched_best, init.val_best = float(opt.param_groups[0]["lr"]), float(s.best), float("inf")
+        init.num_bad_epochs, init.cooldown_counter, init.last_epoch = int(s.num_bad_epochs), int(s.cooldown_counter), int(s.last_epoch)
+        self.state_dev.copy_(torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8))
+        self.log_dev.fill_(float("nan"))
+        self.best.copy_(self.fl["p"])
+        self.gen.to_device()
+        if not self.shuffle:
+            self.wins[0]._layout(np.arange(self.wins[0].G))
+
+    def pinned(self, lookahead):
+        """Pinned rows and events for the state copies of a fit with this look-ahead (one fit at a time uses a set)."""
+        got = self.pins.get(lookahead)
+        if got is None:
+            got = self.pins[lookahead] = (torch.zeros(lookahead + 1, self.nstate, dtype=torch.uint8).pin_memory(),
+                                          [torch.cuda.Event() for _ in range(lookahead + 1)])
+        return got
+
+
+class _ChunkFit(_DeviceFit):
+    """One fit in its chunk form: chunk 0 is the one-epoch graph (epoch 0 is a control epoch), every further chunk ONE replay
+    of the `control_every`-epoch graph, a tail shorter than that one-epoch graphs; behind each chunk that ends in a control
+    epoch the state struct's asynchronous copy, read by `check()` as in the device form."""
+
+    form = "device-chunk"
+
+    def __init__(self, model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead):
+        from .store import DeviceGenerator, DeviceLoader
+        self.model, self.loaders = model, (train_loader, val_loader, test_loader)
+        self.epochs, self.every, self.lookahead = epochs, control_every, lookahead
+        opt = model.optimizer
+        self.sched = _plateau_of(model)
+        if self.sched is None:
+            raise _HostForm("the scheduler is not a ReduceLROnPlateau with mode 'min', threshold_mode 'rel' and one group")
+        if not isinstance(opt, FusedFlatOptimizer) or len(opt.param_groups) != 1:
+            raise _HostForm("the optimiser is not one of the fused ones with one parameter group")
+        if not isinstance(train_loader, DeviceLoader):
+            raise _HostForm("the train loader is a host loader")
+        why = DeviceGenerator.reason(train_loader)
+        if why is not None:
+            raise _EpochForm(why)
+        self.args = _lib.FitControlArgs()       # (`_resolve` fills the device form's pointers in: not used here)
+        for attempt in range(2):
+            self._resolve()
+            self.cs = ChunkWindows.of(model, self.loaders, (self.tw, self.vw, self.tew), self.fl, epochs, early_stopping,
+                                      control_every)
+            if self.cs is None:
+                raise _EpochForm("the chunk graphs could not be captured")
+            # (building them ran the steps: the loaders' windows must still stand, else once more from the top)
+            if all(T._replayable(w.steps, w._fp, False) for w in (self.tw.window, self.vw, self.tew)):
+                break
+            if attempt:
+                raise _lib.HcgError("fit_network: a window went stale again right after the chunk graphs were built")
+        cs = self.cs
+        opt.sync_lr()
+        cs.reset()
+        self.state_dev, self.log_dev, self.best, self.nstate = cs.state_dev, cs.log_dev, cs.best, cs.nstate
+        self.state_pin, self.state_events = cs.pinned(lookahead)
+        self.issued, self.controls, self.done, self.stop_seen, self.launches = 0, 0, False, False, 0
+        self.t0, self.enqueue_s = time.perf_counter(), 0.0
+
+    def issue_chunk(self):
+        """Enqueue the next chunk on the current stream."""
+        cs, e, left = self.cs, self.issued, self.epochs - self.issued
+        if left <= 0:
+            return
+        if e == 0 or left < self.every:
+            L, n = 1, (1 if e == 0 else left)   # (epoch 0 alone; a tail: the rest, epoch by epoch)
+        else:
+            L, n = self.every, 1
+        for _ in range(n):
+            cs.graphs[L].replay()
+        self.issued += L * n
+        self.launches += n
+        if (self.issued - 1) % self.every == 0:
+            slot = self.controls % (self.lookahead + 1)
+            self.state_pin[slot].copy_(self.state_dev, non_blocking=True)
+            self.state_events[slot].record()
+            self.controls += 1
+        self.enqueue_s = time.perf_counter() - self.t0
+
+    def _settle_generator(self, counted):
+        """Epochs issued past the stop drew nothing (the gate): the device generator IS where the host loop's would be."""
+        if self.cs.shuffle:
+            self.cs.gen.to_host()
+
+    def _graph_launches(self) -> int:
+        return self.launches
+
+
+FORMS = ("epoch", "chunk")
+
+
+def chunk_launches(epochs: int, control_every: int) -> int:
+    """Graph launches of a chunk-form fit that runs all `epochs`: epoch 0, the full control intervals, the tail's epochs."""
+    return 1 + (epochs - 1) // control_every + (epochs - 1) % control_every
+
+
+def build_chunk_windows(model, train_loader, val_loader, test_loader, epochs=250, early_stopping=6, control_every=5):
+    """Capture, ahead of the first `fit_network(..., form="chunk")` with these settings, what it replays -> the
+    `ChunkWindows` kept on the train loader, or None where the fit would not take the chunk form.  Launches nothing that
+    stays: weights, optimiser, scheduler and the loader's generator are bitwise what they were."""
+    epochs, early_stopping, control_every, _ = _check_args(epochs, early_stopping, control_every, 0)
+    try:
+        return _ChunkFit(model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, 0).cs
+    except (_HostForm, _EpochForm):
+        return None
+
+
+def _make_run(form, model, loaders, epochs, early_stopping, control_every, lookahead):
+    """The fit's run object in the form asked for, else the next one down: chunk -> device (epoch by epoch) -> None = host."""
+    try:
+        if form == "chunk":
+            try:
+                return _ChunkFit(model, *loaders, epochs, early_stopping, control_every, lookahead)
+            except _EpochForm:
+                pass
+        return _DeviceFit(model, *loaders, epochs, early_stopping, control_every, lookahead)
+    except _HostForm:
+        return None
+
+
+def _check_args(epochs, early_stopping, control_every, lookahead, form="epoch"):
+    if form not in FORMS:
+        raise ValueError(f"form must be one of {FORMS}, got {form!r}")
     if int(epochs) < 1:
         raise ValueError(f"epochs must be at least 1, got {epochs}")
     if int(control_every) < 1:
@@ -325,7 +602,7 @@ def _check_args(epochs, early_stopping, control_every, lookahead):
 
 
 def fit_network(model, train_loader, val_loader, test_loader, device, epochs=250, early_stopping=6, control_every=5,
-                lookahead=1, load_best=True) -> FitResult:
+                lookahead=1, load_best=True, form="epoch") -> FitResult:
     """The reference's whole epoch loop for one model (scripts_experiments/train_GNN.py:73-111): per epoch train, validate,
     test; on every `control_every`-th epoch (0, control_every, ...) `model.scheduler.step(val_loss)`, the best validation
     loss with a copy of its weights, and the stall count that ends the fit once it exceeds `early_stopping`.
@@ -341,11 +618,20 @@ def fit_network(model, train_loader, val_loader, test_loader, device, epochs=250
                       live weights, the optimiser's moments and its step count.
     `load_best=True` (what the reference does next, utils/utils_model.py:170) loads `best_state` into the model, so the
     model handed back does not depend on `lookahead`.  Log, best state, scheduler and lr are bitwise the host loop's.
-    Any other case runs the host form in the same call: the example's loop over `train_network` / `eval_network`."""
-    epochs, early_stopping, control_every, lookahead = _check_args(epochs, early_stopping, control_every, lookahead)
-    try:
-        run = _DeviceFit(model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead)
-    except _HostForm:
+    Any other case runs the host form in the same call: the example's loop over `train_network` / `eval_network`.
+
+    `form="chunk"` (opt-in; `FitResult.form == "device-chunk"`): the shuffle is drawn ON the device (csrc/shuffle.hip: numpy's
+    own PCG64 permutation bit for bit, and the epoch's index arrays made of it), so nothing an epoch needs comes from the
+    host and a control interval is ONE graph (`ChunkWindow`): chunk 0 a one-epoch graph, every further chunk one replay of
+    the `control_every`-epoch graph, a shorter tail one-epoch graphs -- about epochs / control_every launches
+    (`FitResult.graph_launches`) instead of four per epoch and an upload.  `lookahead` as above; the epochs issued past the
+    stop draw nothing (the launch is gated on the fit state) and train on the last order, so the loader's generator ends
+    where the host loop's would with nothing to put back.  Everything a fit leaves is bitwise the device form's.  Needs the
+    device form's conditions, a loader generator that is numpy's PCG64 (the default) and a train store of at most
+    `_lib.HCG_EPOCH_DRAW_MAX_GRAPHS` graphs; else the device form runs, and failing that the host form."""
+    epochs, early_stopping, control_every, lookahead = _check_args(epochs, early_stopping, control_every, lookahead, form)
+    run = _make_run(form, model, (train_loader, val_loader, test_loader), epochs, early_stopping, control_every, lookahead)
+    if run is None:
         return _host_fit(model, train_loader, val_loader, test_loader, device, epochs, early_stopping, control_every, load_best)
     while not run.done:
         run.issue_chunk()
@@ -354,16 +640,16 @@ def fit_network(model, train_loader, val_loader, test_loader, device, epochs=250
 
 
 def fit_networks(models, train_loaders, val_loaders, test_loaders, device, epochs=250, early_stopping=6, control_every=5,
-                 lookahead=1, load_best=True, active=None) -> list:
+                 lookahead=1, load_best=True, active=None, form="epoch") -> list:
     """`fit_network` of several independent runs at once (see `train.train_networks`) -> [FitResult] (None where
     `active[k]` is false).  Every run in the device form goes on its own stream with its own controller; each round issues
     one chunk of every live run before any stop flag is waited for, and a run that stops drops out.  Each run is bitwise the
-    run alone.  Runs in the host form are fitted in turn."""
+    run alone.  Runs in the host form are fitted in turn.  `form`: as `fit_network`'s, decided run by run."""
     models = list(models)
     K = len(models)
     if any(len(x) != K for x in (train_loaders, val_loaders, test_loaders)) or (active is not None and len(active) != K):
         raise ValueError("fit_networks: one train, validation and test loader (and one `active` flag) per model")
-    epochs, early_stopping, control_every, lookahead = _check_args(epochs, early_stopping, control_every, lookahead)
+    epochs, early_stopping, control_every, lookahead = _check_args(epochs, early_stopping, control_every, lookahead, form)
     out, runs, host = [None] * K, [], []
     cur = torch.cuda.current_stream(device)
     for k, m in enumerate(models):
@@ -372,11 +658,12 @@ def fit_networks(models, train_loaders, val_loaders, test_loaders, device, epoch
         st = T._run_stream(m, device)
         st.wait_stream(cur)
         with torch.cuda.stream(st):
-            try:
-                runs.append((k, st, _DeviceFit(m, train_loaders[k], val_loaders[k], test_loaders[k], epochs, early_stopping,
-                                               control_every, lookahead)))
-            except _HostForm:
+            run = _make_run(form, m, (train_loaders[k], val_loaders[k], test_loaders[k]), epochs, early_stopping, control_every,
+                            lookahead)
+            if run is None:
                 host.append(k)
+            else:
+                runs.append((k, st, run))
     live = list(runs)
     while live:
         for _, st, run in live:

@@ -41,6 +41,118 @@ def epoch_layout(n_host, e_host, batch_size, drop_last, order, out=None):
     return buf, spans, tot
 
 
+_PCG_MULT, _M128, _M64 = 0x2360ED051FC65DA44385DF649FCCF645, (1 << 128) - 1, (1 << 64) - 1
+
+
+def pcg64_permutation(state: dict, n: int):
+    """`np.random.Generator(PCG64).permutation(n)` in plain Python integers: `state` = the generator's
+    `bit_generator.state` dict -> (the permutation as a list, the state dict after the draw; `state` is not modified).
+    csrc/shuffle.hip's draw restated (include/hcatgnet_hip.h: hcg_epoch_draw_args) and its CPU oracle: a Fisher-Yates shuffle
+    from the top, every index `random_interval(i)` = masked rejection over 32-bit halves of pcg64's XSL-RR output, the high
+    half of a 64-bit word kept for the next call."""
+    if state.get("bit_generator") != "PCG64":
+        raise ValueError(f"pcg64_permutation restates numpy's PCG64, not {state.get('bit_generator')!r}")
+    s, inc = int(state["state"]["state"]), int(state["state"]["inc"])
+    has, held = int(state["has_uint32"]), int(state["uinteger"])
+    a = list(range(int(n)))
+    for i in range(len(a) - 1, 0, -1):
+        mask = (1 << i.bit_length()) - 1
+        while True:
+            if has:
+                has, v = 0, held
+            else:
+                s = (s * _PCG_MULT + inc) & _M128
+                x, rot = ((s >> 64) ^ s) & _M64, s >> 122
+                w = ((x >> rot) | (x << ((64 - rot) & 63))) & _M64
+                has, held, v = 1, w >> 32, w & 0xFFFFFFFF
+            v &= mask
+            if v <= i:
+                break
+        a[i], a[v] = a[v], a[i]
+    return a, {"bit_generator": "PCG64", "state": {"state": s, "inc": inc}, "has_uint32": has, "uinteger": held}
+
+
+def pcg64_to_struct(state: dict) -> "_lib.Pcg64":
+    """numpy's PCG64 state dict -> the device struct's host mirror (hcg_pcg64)."""
+    if state.get("bit_generator") != "PCG64":
+        raise ValueError(f"the device generator is numpy's PCG64, not {state.get('bit_generator')!r}")
+    s, inc, g = int(state["state"]["state"]), int(state["state"]["inc"]), _lib.Pcg64()
+    g.state_lo, g.state_hi, g.inc_lo, g.inc_hi = s & _M64, s >> 64, inc & _M64, inc >> 64
+    g.has_uint32, g.uinteger = int(state["has_uint32"]), int(state["uinteger"])
+    return g
+
+
+def pcg64_from_struct(g: "_lib.Pcg64") -> dict:
+    """... and back: what `bit_generator.state = ` takes."""
+    return {"bit_generator": "PCG64", "state": {"state": (int(g.state_hi) << 64) | int(g.state_lo),
+                                                "inc": (int(g.inc_hi) << 64) | int(g.inc_lo)},
+            "has_uint32": int(g.has_uint32), "uinteger": int(g.uinteger)}
+
+
+class DeviceGenerator:
+    """A `DeviceLoader`'s shuffle generator in device memory: `to_device()` moves `loader.rng`'s PCG64 state up, `draw(layout)`
+    issues ONE launch (csrc/shuffle.hip) that draws the next permutation -- bit for bit `loader.rng.permutation(G)` -- and
+    fills `layout` as `epoch_layout` would, `to_host()` brings the state back: `loader.rng.bit_generator.state` is then what
+    numpy would hold after the same draws.  `reason(loader)`: why a loader has none (its generator is not numpy's PCG64, its
+    store exceeds what one draw launch takes), else None."""
+
+    @staticmethod
+    def reason(loader) -> Optional[str]:
+        rng = getattr(loader, "rng", None)
+        if not isinstance(rng, np.random.Generator) or type(rng.bit_generator) is not np.random.PCG64:
+            return "the loader's generator is not numpy's PCG64"
+        if len(loader.store) > _lib.HCG_EPOCH_DRAW_MAX_GRAPHS:
+            return f"more than {_lib.HCG_EPOCH_DRAW_MAX_GRAPHS} graphs (what one draw launch keeps in LDS)"
+        return None
+
+    def __init__(self, loader):
+        why = self.reason(loader)
+        if why is not None:
+            raise _lib.HcgError(f"DeviceGenerator: {why}")
+        self.loader, self.G = loader, len(loader.store)
+        self.nbytes, self._words = ctypes.sizeof(_lib.Pcg64), None
+        self.state_dev = torch.zeros(self.nbytes, dtype=torch.uint8, device=loader.store.device)
+        self.args = a = _lib.EpochDrawArgs()
+        a.rng, a.G, a.batch_size, a.drop_last = self.state_dev.data_ptr(), self.G, loader.batch_size, int(bool(loader.drop_last))
+
+    def layout_words(self) -> int:
+        """int64 words of the layout buffer a draw fills (`epoch_layout`'s)."""
+        if self._words is None:
+            self._words = epoch_layout(self.loader.store.n_host, self.loader.store.e_host, self.args.batch_size,
+                                       bool(self.args.drop_last), np.arange(self.G))[0].size
+        return self._words
+
+    def to_device(self):
+        """`loader.rng`'s state -> the device struct (a copy on the current stream)."""
+        host = torch.frombuffer(bytearray(bytes(pcg64_to_struct(self.loader.rng.bit_generator.state))), dtype=torch.uint8)
+        self.state_dev.copy_(host)
+        return self
+
+    def state(self) -> dict:
+        """The device struct as numpy's state dict (synchronises)."""
+        return pcg64_from_struct(_lib.Pcg64.from_buffer_copy(self.state_dev.cpu().numpy().tobytes()))
+
+    def to_host(self):
+        """The device struct -> `loader.rng` (synchronises)."""
+        self.loader.rng.bit_generator.state = self.state()
+        return self
+
+    def draw(self, layout, gate=None, max_epochs: int = 0):
+        """Enqueue one draw on the current stream: the next permutation and its index arrays into `layout` (int64 device
+        buffer of `layout_words()`).  `gate`: the device tensor of a fit's `_lib.FitState` -- a stopped fit, or one whose
+        epoch has reached `max_epochs`, draws nothing and leaves generator and layout as they are."""
+        if layout.dtype != torch.int64 or layout.numel() < self.layout_words() or not layout.is_contiguous():
+            raise ValueError("DeviceGenerator.draw: the layout buffer is int64, contiguous and at least layout_words() long")
+        _lib.require_gpu(layout, self.state_dev, gate)
+        a = self.args
+        a.layout, a.gate, a.gate_max_epochs = layout.data_ptr(), _lib.ptr(gate), int(max_epochs)
+        _lib.epoch_draw(self.loader.store.collate_args(), a)
+
+    def order(self, layout):
+        """The drawn order a layout buffer holds (synchronises)."""
+        return layout[:self.G].cpu().numpy()
+
+
 def fill_collate_slot(sl, ids, gp, ep, x, ei, bvec, y, idx, B, N, E):
     """Point a `_lib.CollateSlot` at one batch: the index views its gather reads, the tensors it writes."""
     p = _lib.ptr

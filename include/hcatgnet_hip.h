@@ -610,6 +610,8 @@ typedef struct hcg_reduce_job {
 #define HCG_STRUCT_EXPLAIN_ARGS 7
 #define HCG_STRUCT_FIT_CONTROL_ARGS 8
 #define HCG_STRUCT_FIT_STATE 9   /* (a DEVICE struct the host reads back: hcg_fit_state) */
+#define HCG_STRUCT_EPOCH_DRAW_ARGS 10
+#define HCG_STRUCT_PCG64 11      /* (a DEVICE struct the host reads back: hcg_pcg64) */
 size_t hcg_struct_bytes(int which);
 int hcg_fused_reduce_job(const void* workspace, size_t workspace_bytes, int64_t N, int64_t B, int64_t F,
                          int64_t D, int graphs_per_tile, float* dW, float* db, hcg_reduce_job* job_host);
@@ -806,6 +808,36 @@ int hcg_xchg_ipc_close(void* ptr);
  * nslots == 1: the batch is `slot` (host values).  nslots > 1: `slots_dev` is a DEVICE array of nslots descriptors (every
  * batch of a shuffled epoch: train.EpochWindow collates an epoch in one launch in front of its steps), max_B the largest
  * slot.B; the caller has validated them.  Replaces reference data/datasets.py:74-78 + PyG collate (call_methods.py:41-46). */
+/* ---- an epoch's shuffle and index arrays drawn on the device: ONE launch of ONE workgroup (csrc/shuffle.hip), reached
+ * through hcg_collate (`epoch_draw` of hcg_collate_args: the exported symbols are capped, tests/test_host_cpu.py), so that
+ * an epoch of a fit needs no host data and a control interval of epochs can be one captured graph (fit.py).
+ * The generator is numpy's PCG64 in device memory, its fields those of `np.random.PCG64().state` (the 128-bit integers as a
+ * low and a high word); the draw is bit for bit `np.random.Generator(PCG64).permutation(G)`:
+ *   a = arange(G); for i = G-1 .. 1: j = random_interval(i), swap a[i], a[j]     (G == 1 draws nothing)
+ *   random_interval(max): mask = the smallest 2^k - 1 >= max; repeat v = next_uint32() & mask until v <= max
+ *   next_uint32(): the buffered high half if has_uint32 (cleared), else w = next_uint64(), the high half kept, the low returned
+ *   next_uint64(): state = state * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128); rotr64(hi ^ lo, state >> 122)
+ * One lane walks the swap chain with the array in LDS.  The workgroup then fills `layout` exactly as the host's
+ * `store.epoch_layout` does: int64 ids [G] | per batch an int32 block graph_ptr | per batch an int32 block edge_ptr, every
+ * block (B + 2) / 2 int64 words holding the B + 1 prefix sums of the permuted graphs' node / edge counts (from node_ptr_all /
+ * edge_ptr_all of hcg_collate_args, the only other fields read) behind a zero, a padding int32 zero where B is even; batches
+ * of `batch_size` graphs, the last one shorter (dropped with `drop_last`): G + 2 * tot words, tot = the blocks' words.
+ * `gate` != NULL and the fit stopped, or its epoch outside [0, gate_max_epochs): NOTHING is written, generator and layout
+ * stay as they are -- epochs enqueued past a fit's stop draw nothing, the generator ends where the host loop's would.
+ * G <= HCG_EPOCH_DRAW_MAX_GRAPHS (what one workgroup keeps in LDS; any number of batches), else HCG_ERR_UNSUPPORTED. */
+#define HCG_EPOCH_DRAW_MAX_GRAPHS 8192
+typedef struct hcg_pcg64 {     /* DEVICE struct, caller-initialised */
+  uint64_t state_lo, state_hi, inc_lo, inc_hi;
+  uint32_t has_uint32, uinteger;
+} hcg_pcg64;
+typedef struct hcg_epoch_draw_args {   /* HOST struct; zero it first */
+  hcg_pcg64* rng;                    /* device */
+  int64_t* layout;                   /* device [G + 2 * tot] */
+  const hcg_fit_state* gate;         /* device, nullable */
+  int64_t G;
+  int32_t batch_size, drop_last, gate_max_epochs, reserved;
+} hcg_epoch_draw_args;
+
 typedef struct hcg_collate_slot {
   const int64_t* ids;
   const int32_t* graph_ptr;
@@ -831,6 +863,7 @@ typedef struct hcg_collate_args {
   hcg_collate_slot slot;                 /* nslots == 1 */
   const hcg_collate_slot* slots_dev;     /* nslots > 1 */
   int64_t max_B;                         /* nslots > 1 */
+  const hcg_epoch_draw_args* epoch_draw; /* HOST pointer; NULL = a collate */
 } hcg_collate_args;
 int hcg_collate(const hcg_collate_args* args_host, hcg_stream_t stream);
 

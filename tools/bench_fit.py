@@ -75,6 +75,27 @@ def host_loops(runs, epochs, every):
                 hc.control(v)
 
 
+def time_draw(loader, reps=200, windows=5):
+    """The draw launch alone (csrc/shuffle.hip) on the loader's store: us per launch, `reps` back to back between two events."""
+    from hcatgnet_amd.store import DeviceGenerator
+    state = loader.rng.bit_generator.state
+    gen = DeviceGenerator(loader).to_device()
+    layout = torch.zeros(gen.layout_words(), dtype=torch.int64, device="cuda")
+    for _ in range(20):
+        gen.draw(layout)
+    out = []
+    for _ in range(windows):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(reps):
+            gen.draw(layout)
+        t1.record()
+        t1.synchronize()
+        out.append(t0.elapsed_time(t1) / reps)
+    loader.rng.bit_generator.state = state
+    return dict(graphs=len(loader.store), **stats(out, 1e3))
+
+
 def stats(xs, scale):
     xs = np.asarray(xs) * scale
     return dict(median=round(float(np.median(xs)), 4), p10=round(float(np.percentile(xs, 10)), 4), p90=round(float(np.percentile(xs, 90)), 4))
@@ -88,28 +109,42 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--runs", type=int, default=12)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "fit_bench.json"))
+    ap.add_argument("--form", choices=("epoch", "chunk"), default="epoch", help="chunk: two more legs beside a..e, the fits of c "
+                    "and e with form='chunk' (f, g), the draw kernel alone, and the record goes to profiles/fit_chunk_bench.json")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_fit.py measures on an MI355X: no GPU visible"
+    chunk = a.form == "chunk"
+    if chunk and a.out.endswith(os.path.join("profiles", "fit_bench.json")):
+        a.out = a.out[:-len("fit_bench.json")] + "fit_chunk_bench.json"
     runs = [make_run(k) for k in range(a.runs)]
     one = runs[0]
     kw = dict(epochs=a.epochs, early_stopping=NEVER, control_every=a.every, load_best=False)
     enq = {"b_fit_lookahead0": [], "c_fit_lookahead1": [], "e_fit_networks": []}
+    launches = {}
 
-    def fit(name, lookahead):
+    def fit(name, lookahead, form="epoch"):
         def leg():
-            r = H.fit_network(*one, "cuda", lookahead=lookahead, **kw)
-            assert r.form == "device" and r.epochs_run == a.epochs
+            r = H.fit_network(*one, "cuda", lookahead=lookahead, form=form, **kw)
+            assert r.form == ("device" if form == "epoch" else "device-chunk") and r.epochs_run == a.epochs
             enq[name].append(r.enqueue_s)
+            launches[name] = r.graph_launches
         return leg
 
-    def fits():
-        rs = H.fit_networks(*[[r[i] for r in runs] for i in range(4)], "cuda", lookahead=1, **kw)
-        assert all(r.form == "device" and r.epochs_run == a.epochs for r in rs)
-        enq["e_fit_networks"].append(max(r.enqueue_s for r in rs))
+    def fits(name="e_fit_networks", form="epoch"):
+        def leg():
+            rs = H.fit_networks(*[[r[i] for r in runs] for i in range(4)], "cuda", lookahead=1, form=form, **kw)
+            assert all(r.form == ("device" if form == "epoch" else "device-chunk") and r.epochs_run == a.epochs for r in rs)
+            enq[name].append(max(r.enqueue_s for r in rs))
+            launches[name] = rs[0].graph_launches
+        return leg
 
     legs = {"a_host_loop": lambda: host_loop(one, a.epochs, a.every), "b_fit_lookahead0": fit("b_fit_lookahead0", 0),
             "c_fit_lookahead1": fit("c_fit_lookahead1", 1), "d_train_eval_networks": lambda: host_loops(runs, a.epochs, a.every),
-            "e_fit_networks": fits}
+            "e_fit_networks": fits()}
+    if chunk:
+        enq.update(f_chunk_lookahead1=[], g_chunk_fit_networks=[])
+        legs.update(f_chunk_lookahead1=fit("f_chunk_lookahead1", 1, "chunk"),
+                    g_chunk_fit_networks=fits("g_chunk_fit_networks", "chunk"))
     for fn in legs.values():                  # warm-up: every window captured, every kernel loaded
         fn()
     torch.cuda.synchronize()
@@ -133,6 +168,14 @@ def main():
     rec["c_median_above_a_p90"] = rec["c_fit_lookahead1"]["median"] > rec["a_host_loop"]["p90"]
     rec["a_over_c_median"] = round(rec["a_host_loop"]["median"] / rec["c_fit_lookahead1"]["median"], 3)
     rec["d_over_e_median"] = round(rec["d_train_eval_networks"]["median"] / rec["e_fit_networks"]["median"], 3)
+    if chunk:
+        rec["graph_launches_per_fit"] = launches
+        for single, many, key in (("c_fit_lookahead1", "f_chunk_lookahead1", "one_fit"), ("e_fit_networks", "g_chunk_fit_networks", "runs")):
+            # faster only where the chunk form's p90 is below the epoch form's p10 of the same run; slower likewise
+            rec[f"chunk_faster_{key}"] = rec[many]["p90"] < rec[single]["p10"]
+            rec[f"chunk_slower_{key}"] = rec[many]["p10"] > rec[single]["p90"]
+            rec[f"epoch_over_chunk_median_{key}"] = round(rec[single]["median"] / rec[many]["median"], 3)
+        rec["draw_kernel_us"] = time_draw(one[1])
     rec["note"] = ("every window ends in a device synchronise; enqueue = host time from a fit's set-up to the return of its enqueue "
                    "loop (b waits on every control epoch inside it), e: the longest of the K runs")
     line = json.dumps(rec)
