@@ -17,6 +17,10 @@ examples/train_like_reference.py) -- without a host sync per epoch.
 (csrc/shuffle.hip, `store.DeviceGenerator`), and a control interval of epochs -- draw, three epochs' steps, controller,
 `control_every` times over -- is ONE hipGraph (`ChunkWindow`), bitwise the form above.
 
+Both device forms are one skeleton: `_ControlBlock` is the controller's device memory and launch arguments, `chunk_end` says
+where a chunk ends, `_DeviceFit` issues chunks, posts the state copy behind each control epoch, reads the stop flag and gathers
+the result; `_EpochFit` and `_ChunkFit` only say how a chunk's epochs are enqueued.
+
 `FitControl` is that launch's state machine in plain Python: the host form of a fit (any loader / scheduler the device form
 does not take) runs on it, and the tests hold the kernel against it bit for bit.
 """
@@ -181,56 +185,117 @@ def _host_fit(model, train_loader, val_loader, test_loader, device, epochs, earl
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# device form
+# device forms: the controller's block, the chunk schedule, the run skeleton
 # ---------------------------------------------------------------------------------------------------------------
 class _HostForm(Exception):
     """The device form does not take this fit (the reason is the message): the host form runs it."""
 
 
-class _DeviceFit:
-    """One fit in its device form, issued chunk by chunk on the stream that is current at each call: chunk 0 is epoch 0,
-    chunk c the epochs up to and including control epoch c * control_every; `check()` after each chunk is the look-ahead's
-    one read of the stop flag."""
+class _EpochForm(Exception):
+    """The chunk form does not take this fit (the reason is the message): the device form runs it, epoch by epoch."""
 
-    def __init__(self, model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead):
-        self.model, self.loaders = model, (train_loader, val_loader, test_loader)
-        self.epochs, self.every, self.lookahead = epochs, control_every, lookahead
-        opt = model.optimizer
-        self.sched = _plateau_of(model)
-        if self.sched is None:
-            raise _HostForm("the scheduler is not a ReduceLROnPlateau with mode 'min', threshold_mode 'rel' and one group")
-        if not isinstance(opt, FusedFlatOptimizer) or len(opt.param_groups) != 1:
-            raise _HostForm("the optimiser is not one of the fused ones with one parameter group")
+
+def _first_state(model) -> _lib.FitState:
+    """The controller's state before a fit's first epoch, as the struct the kernel reads: the group's lr, the model's scheduler
+    continued where it stands, nothing counted yet -- `FitControl.for_model(model, ...).state()`.  Needs no device."""
+    s, init = _plateau_of(model), _lib.FitState()
+    init.lr, init.sched_best, init.val_best = float(model.optimizer.param_groups[0]["lr"]), float(s.best), float("inf")
+    init.num_bad_epochs, init.cooldown_counter, init.last_epoch = int(s.num_bad_epochs), int(s.cooldown_counter), int(s.last_epoch)
+    return init
+
+
+class _ControlBlock:
+    """The controller launch's device memory for one fit at a time -- `FitState` bytes, loss log, best-weights slot -- and its
+    arguments, constants and pointers filled once; `args.sums` is left to whoever issues or records the launch."""
+
+    def __init__(self, model, fl, denominators, epochs, early_stopping, control_every):
+        s, dev = _plateau_of(model), fl["p"].device
+        self.model, self.fl, self.pins = model, fl, {}
+        self.state_dev = torch.zeros(ctypes.sizeof(_lib.FitState), dtype=torch.uint8, device=dev)
+        self.log_dev = torch.empty((epochs, 4), dtype=torch.float64, device=dev)
+        self.best = torch.empty_like(fl["p"])
         self.args = a = _lib.FitControlArgs()
-        self._resolve()                        # (the windows, built on first use: not a device form without all three)
-        dev, n = self.fl["p"].device, self.fl["n"]
-        s = self.sched
-        init = _lib.FitState()
-        init.lr, init.sched_best, init.val_best = float(opt.param_groups[0]["lr"]), float(s.best), float("inf")
-        init.num_bad_epochs, init.cooldown_counter, init.last_epoch = int(s.num_bad_epochs), int(s.cooldown_counter), int(s.last_epoch)
-        self.nstate = ctypes.sizeof(_lib.FitState)
-        self.state_dev = torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8).to(dev)
-        self.log_dev = torch.full((epochs, 4), float("nan"), dtype=torch.float64, device=dev)
-        self.best = self.fl["p"].clone()       # the reference keeps the initial state-dict until an epoch is better
-        a.state, a.best, a.n, a.log = self.state_dev.data_ptr(), self.best.data_ptr(), n, self.log_dev.data_ptr()
-        a.denom[0], a.denom[1], a.denom[2] = float(self.tw.G), float(len(val_loader.dataset)), float(len(test_loader.dataset))
+        a.state, a.best, a.n, a.log = self.state_dev.data_ptr(), self.best.data_ptr(), fl["n"], self.log_dev.data_ptr()
+        a.lr_dev, a.param = fl["lr_dev"].data_ptr(), fl["p"].data_ptr()
+        a.denom[0], a.denom[1], a.denom[2] = (float(d) for d in denominators)
         a.factor, a.rel_epsilon, a.min_lr, a.eps = float(s.factor), 1.0 - s.threshold, float(s.min_lrs[0]), float(s.eps)
         a.patience, a.cooldown, a.control_every = int(s.patience), int(s.cooldown), control_every
         a.early_stopping, a.max_epochs = early_stopping, epochs
-        # pinned staging: one row of index arrays per epoch that can be in flight, one state row per unread control epoch
-        nrows = (lookahead + 1) * control_every + 1
-        self.rows = [torch.zeros_like(self.tw.host).pin_memory() for _ in range(nrows)]
-        self.row_events = [None] * nrows
-        self.state_pin = torch.zeros(lookahead + 1, self.nstate, dtype=torch.uint8).pin_memory()
-        self.state_events = [torch.cuda.Event() for _ in range(lookahead + 1)]
-        self.issued, self.controls, self.done, self.stop_seen = 0, 0, False, False
-        self.rng_states = []
+
+    def reset(self):
+        """A fit's start on the current stream: the first state, an empty log, the best slot = the weights as they are."""
+        self.state_dev.copy_(torch.frombuffer(bytearray(bytes(_first_state(self.model))), dtype=torch.uint8))
+        self.log_dev.fill_(float("nan"))
+        self.best.copy_(self.fl["p"])          # (the reference keeps the initial state-dict until an epoch is better)
+
+    def read(self) -> dict:
+        """The state as `FitControl.state()` gives it (waits for the current stream)."""
+        torch.cuda.current_stream().synchronize()
+        raw = _lib.FitState.from_buffer_copy(self.state_dev.cpu().numpy().tobytes())
+        return {k: getattr(raw, k) for k in FitControl.STATE}
+
+    def log(self, n):
+        return self.log_dev[:n].cpu().numpy()
+
+    def best_state_dict(self) -> OrderedDict:
+        """The best slot as a state-dict of clones (entries outside the flat storage: as they are in the model)."""
+        off, offs = 0, {}
+        for q in self.fl["params"]:
+            offs[id(q)] = off
+            off += q.numel()
+        best_state = OrderedDict()
+        for k, v in self.model.state_dict(keep_vars=True).items():
+            o = offs.get(id(v))
+            best_state[k] = (self.best[o:o + v.numel()].view(v.shape).clone() if o is not None else v.detach().clone())
+        return best_state
+
+    def pinned(self, lookahead):
+        """Pinned rows and events for the state copies of a fit with this look-ahead: one per unread control epoch."""
+        got = self.pins.get(lookahead)
+        if got is None:
+            got = self.pins[lookahead] = (torch.zeros(lookahead + 1, self.state_dev.numel(), dtype=torch.uint8).pin_memory(),
+                                          [torch.cuda.Event() for _ in range(lookahead + 1)])
+        return got
+
+
+def chunk_end(issued: int, epochs: int, control_every: int) -> int:
+    """The exclusive end of the chunk that starts at `issued`: epoch 0 alone, then up to and including the next control epoch."""
+    return min(epochs, issued + control_every if issued else 1)
+
+
+def chunk_launches(epochs: int, control_every: int) -> int:
+    """Graph launches of a chunk-form fit that runs all `epochs`: epoch 0, the full control intervals, the tail's epochs."""
+    return 1 + (epochs - 1) // control_every + (epochs - 1) % control_every
+
+
+class _DeviceFit:
+    """One fit in a device form, issued chunk by chunk (`chunk_end`) on the stream that is current at each call; behind a
+    chunk that ends in a control epoch the state struct's asynchronous copy, and `check()` after each chunk is the
+    look-ahead's one read of the stop flag.  A form says what it needs on top of this (`_eligible`), what it launches
+    (`_bind`: once the windows stand; `_issue`: a chunk's epochs) and where the loader's generator ends (`_settle_generator`)."""
+
+    def __init__(self, model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead):
+        self.model, self.loaders = model, (train_loader, val_loader, test_loader)
+        self.epochs, self.early_stopping, self.every, self.lookahead = epochs, early_stopping, control_every, lookahead
+        if _plateau_of(model) is None:
+            raise _HostForm("the scheduler is not a ReduceLROnPlateau with mode 'min', threshold_mode 'rel' and one group")
+        if not isinstance(model.optimizer, FusedFlatOptimizer) or len(model.optimizer.param_groups) != 1:
+            raise _HostForm("the optimiser is not one of the fused ones with one parameter group")
+        self._eligible()
+        self.block = None
+        self._resolve()                        # (the windows, built on first use: not a device form without all three)
+        self.state_pin, self.state_events = self.block.pinned(lookahead)
+        self.issued, self.controls, self.graph_launches, self.done, self.stop_seen = 0, 0, 0, False, False
         self.t0, self.enqueue_s = time.perf_counter(), 0.0
 
+    def _eligible(self):
+        pass
+
     def _resolve(self):
-        """The three windows and the optimiser's flat storages as they are NOW -> the launch's pointers.  A window whose
-        baked-in addresses were replaced since its capture (`load_state_dict` of the optimiser, a larger eager batch) is
-        dropped and built again, once, as `train._LoaderWindows.launch` does: nothing is written through an old pointer."""
+        """The three windows and the optimiser's flat storages as they are NOW -> `_bind`.  A window whose baked-in addresses
+        were replaced since its capture (`load_state_dict` of the optimiser, a larger eager batch) is dropped and built
+        again, once, as `train._LoaderWindows.launch` does: nothing is written through an old pointer.  The same pass covers
+        what a form captures on top of the windows: where `_bind` ran their steps (it says so), they are looked at again."""
         model, opt = self.model, self.model.optimizer
         kinds = (T._EPOCH_WINDOWS, T._EVAL_WINDOWS, T._EVAL_WINDOWS)
         for attempt in range(2):
@@ -238,51 +303,35 @@ class _DeviceFit:
             if any(w is None for w in wins):
                 raise _HostForm("a loader has no captured window (a host loader, a layer on the row-streaming kernels, a live "
                                 "multi-rank process group)")
-            steps = [wins[0].window, wins[1], wins[2]]
+            steps = (wins[0].window, wins[1], wins[2])
             live = opt.capture_state()         # (flat storages and device words; a re-base here shows as a stale window)
-            stale = [not T._replayable(w.steps, w._fp, False) for w in steps]
+            look = lambda: [not T._replayable(w.steps, w._fp, False) for w in steps]
+            stale = look()
             if not any(stale):
-                break
+                fl = opt._flat[0]
+                if not opt.on_storages(live) or fl["params"][0].data_ptr() != fl["p"].data_ptr():
+                    raise _lib.HcgError("fit_network: the optimiser's flat storages are not the model's parameters")
+                opt.sync_lr()
+                stale = look() if self._bind(wins, fl) else stale
+                if not any(stale):
+                    return
             if attempt:
                 raise _lib.HcgError("fit_network: a window went stale again right after it was rebuilt")
             for ld, kind, bad in zip(self.loaders, kinds, stale):
                 if bad:
                     setattr(ld, kind.attr, None)
-        fl = opt._flat[0]
-        if not opt.on_storages(live) or fl["params"][0].data_ptr() != fl["p"].data_ptr():
-            raise _lib.HcgError("fit_network: the optimiser's flat storages are not the model's parameters")
-        opt.sync_lr()
-        self.tw, self.vw, self.tew, self.fl = wins[0], wins[1], wins[2], fl
-        a = self.args
-        a.sums[0], a.sums[1], a.sums[2] = (w.value_dev.data_ptr() for w in steps)
-        a.lr_dev, a.param = fl["lr_dev"].data_ptr(), fl["p"].data_ptr()
 
     def issue_chunk(self):
-        """Enqueue the epochs up to and including the next control epoch (or the last epoch) on the current stream."""
-        self._resolve()
-        tw, nrows = self.tw, len(self.rows)
-        rng = self.loaders[0].rng
-        while self.issued < self.epochs:
-            e = self.issued
-            order = tw.draw_order()
-            self.rng_states.append(rng.bit_generator.state)
-            r = e % nrows
-            if self.row_events[r] is None:
-                self.row_events[r] = torch.cuda.Event()
-            else:
-                self.row_events[r].synchronize()        # (the upload that read this row has long run)
-            tw.launch_epoch(order, staging=self.rows[r])
-            self.row_events[r].record()
-            self.vw.replay()
-            self.tew.replay()
-            _lib.fit_control(self.args)
-            self.issued += 1
-            if e % self.every == 0:
+        """Enqueue the next chunk on the current stream."""
+        first, end = self.issued, chunk_end(self.issued, self.epochs, self.every)
+        if end > first:
+            self.graph_launches += self._issue(first, end)
+            self.issued = end
+            if (end - 1) % self.every == 0:
                 slot = self.controls % (self.lookahead + 1)
-                self.state_pin[slot].copy_(self.state_dev, non_blocking=True)
+                self.state_pin[slot].copy_(self.block.state_dev, non_blocking=True)
                 self.state_events[slot].record()
                 self.controls += 1
-                break
         self.enqueue_s = time.perf_counter() - self.t0
 
     def check(self) -> bool:
@@ -291,49 +340,66 @@ class _DeviceFit:
         if c >= 0 and not self.stop_seen:
             slot = c % (self.lookahead + 1)
             self.state_events[slot].synchronize()
-            st = _lib.FitState.from_buffer_copy(self.state_pin[slot].numpy().tobytes())
-            self.stop_seen = bool(st.stopped)
+            self.stop_seen = bool(_lib.FitState.from_buffer_copy(self.state_pin[slot].numpy().tobytes()).stopped)
         self.done = self.stop_seen or self.issued >= self.epochs
         return self.done
 
     def finish(self, load_best) -> FitResult:
-        torch.cuda.current_stream().synchronize()
-        raw = _lib.FitState.from_buffer_copy(self.state_dev.cpu().numpy().tobytes())
-        st = {k: getattr(raw, k) for k in FitControl.STATE}
-        counted = st["epochs_counted"]
-        log = self.log_dev[:counted].cpu().numpy()
-        self._settle_generator(counted)
+        st = self.block.read()
+        self._settle_generator(st["epochs_counted"])
         _write_back(self.model, st)
         self.model.eval()                      # (the loop's last call is an eval_network)
-        fl, off, offs = self.fl, 0, {}
-        for q in fl["params"]:
-            offs[id(q)] = off
-            off += q.numel()
-        best_state = OrderedDict()
-        for k, v in self.model.state_dict(keep_vars=True).items():
-            o = offs.get(id(v))
-            best_state[k] = (self.best[o:o + v.numel()].view(v.shape).clone() if o is not None else v.detach().clone())
-        return _result(self.model, st, log, st["stopped"], best_state, self.issued, self.form, self.enqueue_s, load_best,
-                       self._graph_launches())
+        return _result(self.model, st, self.block.log(st["epochs_counted"]), st["stopped"], self.block.best_state_dict(),
+                       self.issued, self.form, self.enqueue_s, load_best, self.graph_launches)
+
+
+class _EpochFit(_DeviceFit):
+    """The device form: every epoch enqueued on its own -- the permutation from the loader's generator, the index upload
+    through a ring of pinned rows, three graph replays, the controller launch."""
 
     form = "device"
+
+    def _bind(self, wins, fl):
+        """The fit's block and staging on first use; the controller reads the sums of the windows as they are now."""
+        if self.block is None:
+            self.block = _ControlBlock(self.model, fl, (wins[0].G, len(self.loaders[1].dataset), len(self.loaders[2].dataset)),
+                                       self.epochs, self.early_stopping, self.every)
+            self.block.reset()
+            nrows = (self.lookahead + 1) * self.every + 1       # (one row of index arrays per epoch that can be in flight)
+            self.rows = [torch.zeros_like(wins[0].host).pin_memory() for _ in range(nrows)]
+            self.row_events, self.rng_states = [torch.cuda.Event() for _ in range(nrows)], []
+        elif fl is not self.block.fl:
+            raise _lib.HcgError("fit_network: the optimiser re-based its flat storages during the fit")
+        self.wins, a = wins, self.block.args
+        a.sums[0], a.sums[1], a.sums[2] = (w.value_dev.data_ptr() for w in (wins[0].window, wins[1], wins[2]))
+        return False
+
+    def _issue(self, first, end):
+        self._resolve()
+        (tw, vw, tew), args = self.wins, self.block.args
+        rows, events, nrows = self.rows, self.row_events, len(self.rows)
+        rng, states = self.loaders[0].rng, self.rng_states
+        for e in range(first, end):
+            order = tw.draw_order()
+            states.append(rng.bit_generator.state)
+            r = e % nrows
+            events[r].synchronize()                     # (the upload that read this row has long run; none yet: no wait)
+            tw.launch_epoch(order, staging=rows[r])
+            events[r].record()
+            vw.replay()
+            tew.replay()
+            _lib.fit_control(args)
+        return 3 * (end - first)
 
     def _settle_generator(self, counted):
         """The loader goes on as after the host loop: the epochs issued past the stop drew permutations it never would have."""
         if counted < self.issued:
             self.loaders[0].rng.bit_generator.state = self.rng_states[counted - 1]
 
-    def _graph_launches(self) -> int:
-        return 3 * self.issued
-
 
 # ---------------------------------------------------------------------------------------------------------------
 # chunk form: a control interval of epochs as ONE graph, the shuffle drawn on the device
 # ---------------------------------------------------------------------------------------------------------------
-class _EpochForm(Exception):
-    """The chunk form does not take this fit (the reason is the message): the device form runs it, epoch by epoch."""
-
-
 class ChunkWindow:
     """`L` consecutive epochs of a fit as ONE hipGraph, recorded per epoch in the order the device form issues them:
       the draw and layout launch (csrc/shuffle.hip) into the `EpochWindow`'s index buffer, gated on the fit state;
@@ -341,24 +407,20 @@ class ChunkWindow:
       the validation and the test steps of the two forward-only windows with their sums;
       the controller launch (csrc/fit.hip), `sums` pointing at this graph's own three sum tensors of that epoch.
     Nothing comes from the host between two epochs, so a replay is one launch whatever `L`.  The capture's warm-up runs all of
-    it once; `ChunkWindows.build` takes that back (weights, optimiser, controller, generator, index buffer)."""
+    it once; `ChunkWindows` takes that back (weights, optimiser, controller, generator, index buffer)."""
 
     def __init__(self, cs, L: int):
         self.cs, self.L = cs, int(L)
         tw, vw, tew = cs.wins
         self.parts = (tw.window, vw, tew)
         self.steps = [st for w in self.parts for st in w.steps]
-        self.sums = None
 
         def run():
-            a, sums = cs.args, []
+            a, sums = cs.block.args, []
             for _ in range(self.L):
                 if cs.shuffle:
-                    cs.gen.draw(tw.dbuf, gate=cs.state_dev, max_epochs=cs.epochs)
-                three = []
-                for w in self.parts:
-                    losses = [st(b() if callable(b) else b, _forward_only=w.forward_only) for st, b in zip(w.steps, w.batches)]
-                    three.append(T._weighted_loss_dev(losses, w.counts64))
+                    cs.gen.draw(tw.dbuf, gate=cs.block.state_dev, max_epochs=cs.epochs)
+                three = [w.run()[1] for w in self.parts]
                 a.sums[0], a.sums[1], a.sums[2] = (s.data_ptr() for s in three)
                 _lib.fit_control(a)
                 sums.append(three)
@@ -381,15 +443,10 @@ class ChunkWindow:
 class ChunkWindows:
     """What a fit in the chunk form replays, kept on the train loader for the next fit of the same model and settings: the
     one-epoch graph (epoch 0 and a tail) and the `control_every`-epoch graph, and the device memory they have baked in -- the
-    controller's state, log and best slot, the loader's generator (`store.DeviceGenerator`).  `max_epochs`, the scheduler's
-    constants and the stop limit are launch arguments of the recorded controller, so they are part of `key`."""
+    controller's `block` (state, log, best slot), the loader's generator (`store.DeviceGenerator`).  `max_epochs`, the
+    scheduler's constants and the stop limit are launch arguments of the recorded controller, so they are part of `key`."""
 
     ATTR = "_hcg_chunk_windows"
-
-    @staticmethod
-    def key_of(sched, loaders, epochs, early_stopping, control_every):
-        return (epochs, early_stopping, control_every, float(sched.factor), float(sched.threshold), int(sched.patience),
-                int(sched.cooldown), float(sched.min_lrs[0]), float(sched.eps), bool(loaders[0].shuffle))
 
     @classmethod
     def of(cls, model, loaders, wins, fl, epochs, early_stopping, control_every, build=True):
@@ -397,7 +454,8 @@ class ChunkWindows:
         they are now, `fl`: the optimiser's flat storages), built on first use; a set whose baked-in addresses were replaced
         since is dropped and built again.  None: the capture failed (kept: not tried again for the same key)."""
         sched, trn = _plateau_of(model), loaders[0]
-        key = cls.key_of(sched, loaders, epochs, early_stopping, control_every)
+        key = (epochs, early_stopping, control_every, float(sched.factor), float(sched.threshold), int(sched.patience),
+               int(sched.cooldown), float(sched.min_lrs[0]), float(sched.eps), bool(trn.shuffle))
         ent = getattr(trn, cls.ATTR, None)
         if ent is not None and ent[0] is model and ent[1] == key and all(a is b for a, b in zip(ent[2], loaders)):
             cs = ent[3]
@@ -420,147 +478,68 @@ class ChunkWindows:
         from .store import DeviceGenerator
         self.model, self.loaders, self.wins, self.fl = model, tuple(loaders), tuple(wins), fl
         self.epochs, self.every, self.shuffle = epochs, control_every, bool(loaders[0].shuffle)
-        tw, s, dev = wins[0], _plateau_of(model), fl["p"].device
         self.gen = DeviceGenerator(loaders[0])
-        self.nstate = ctypes.sizeof(_lib.FitState)
-        self.state_dev = torch.zeros(self.nstate, dtype=torch.uint8, device=dev)
-        self.log_dev = torch.full((epochs, 4), float("nan"), dtype=torch.float64, device=dev)
-        self.best = fl["p"].clone()
-        self.pins = {}
-        self.args = a = _lib.FitControlArgs()
-        a.state, a.best, a.n, a.log = self.state_dev.data_ptr(), self.best.data_ptr(), fl["n"], self.log_dev.data_ptr()
-        a.lr_dev, a.param = fl["lr_dev"].data_ptr(), fl["p"].data_ptr()
-        a.denom[0], a.denom[1], a.denom[2] = float(tw.G), float(len(loaders[1].dataset)), float(len(loaders[2].dataset))
-        a.factor, a.rel_epsilon, a.min_lr, a.eps = float(s.factor), 1.0 - s.threshold, float(s.min_lrs[0]), float(s.eps)
-        a.patience, a.cooldown, a.control_every = int(s.patience), int(s.cooldown), control_every
-        a.early_stopping, a.max_epochs = early_stopping, epochs
+        self.block = b = _ControlBlock(model, fl, (wins[0].G, len(loaders[1].dataset), len(loaders[2].dataset)), epochs,
+                                       early_stopping, control_every)
         self.reset()                            # (the warm-ups run on a fit's first state, not on zeros)
-        # every capture's warm-up is L hidden epochs: taken back in place, as `train.EpochWindow` does -- also when a capture
-        # fails, since the caller then fits on in the device form
-        opt = model.optimizer
-        live = opt.capture_state()
-        if not opt.on_storages([fl["p"]]):
-            raise _lib.HcgError("ChunkWindows: the optimiser re-based its state before the capture")
-        held = list(live) + [fl["lr_dev"], self.state_dev, self.log_dev, self.best, self.gen.state_dev, tw.dbuf]
-        saved = [t.clone() for t in held]
-        self.graphs = {}
-        try:
+        # every capture's warm-up is L hidden epochs: taken back in place, each graph's starting where a fit would
+        opt, self.graphs = model.optimizer, {}
+        held = [fl["lr_dev"], b.state_dev, b.log_dev, b.best, self.gen.state_dev, wins[0].dbuf]
+        with T._taken_back(opt, held, "ChunkWindows") as restore:
+            if not opt.on_storages([fl["p"]]):
+                raise _lib.HcgError("ChunkWindows: the optimiser re-based its state before the capture")
             for L in sorted({1, control_every}):
+                if self.graphs:
+                    restore()
                 self.graphs[L] = ChunkWindow(self, L)
-                torch.cuda.synchronize()
-                with torch.no_grad():           # (each graph's warm-up starts where a fit would)
-                    for t, u in zip(held, saved):
-                        t.copy_(u)
-        finally:
-            torch.cuda.synchronize()
-            with torch.no_grad():
-                for t, u in zip(held, saved):
-                    t.copy_(u)
-            torch.cuda.synchronize()
-        if not opt.on_storages(live):
-            raise _lib.HcgError("ChunkWindows: the optimiser re-based its state during the capture")
 
     def reset(self):
-        """A fit's start on the current stream: the controller's first state from the model's scheduler, an empty log, the
-        best slot = the weights as they are, the loader's generator moved up; a loader that does not shuffle gets its
-        (identity) index arrays once."""
-        opt, s = self.model.optimizer, _plateau_of(self.model)
-        init = _lib.FitState()
-        init.lr, init.sched_best, init.val_best = float(opt.param_groups[0]["lr"]), float(s.best), float("inf")
-        init.num_bad_epochs, init.cooldown_counter, init.last_epoch = int(s.num_bad_epochs), int(s.cooldown_counter), int(s.last_epoch)
-        self.state_dev.copy_(torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8))
-        self.log_dev.fill_(float("nan"))
-        self.best.copy_(self.fl["p"])
+        """A fit's start on the current stream: the controller's block, the loader's generator moved up; a loader that does
+        not shuffle gets its (identity) index arrays once."""
+        self.block.reset()
         self.gen.to_device()
         if not self.shuffle:
             self.wins[0]._layout(np.arange(self.wins[0].G))
 
-    def pinned(self, lookahead):
-        """Pinned rows and events for the state copies of a fit with this look-ahead (one fit at a time uses a set)."""
-        got = self.pins.get(lookahead)
-        if got is None:
-            got = self.pins[lookahead] = (torch.zeros(lookahead + 1, self.nstate, dtype=torch.uint8).pin_memory(),
-                                          [torch.cuda.Event() for _ in range(lookahead + 1)])
-        return got
-
 
 class _ChunkFit(_DeviceFit):
-    """One fit in its chunk form: chunk 0 is the one-epoch graph (epoch 0 is a control epoch), every further chunk ONE replay
-    of the `control_every`-epoch graph, a tail shorter than that one-epoch graphs; behind each chunk that ends in a control
-    epoch the state struct's asynchronous copy, read by `check()` as in the device form."""
+    """The chunk form: a chunk of `control_every` epochs is ONE replay of the `control_every`-epoch graph, any other (epoch 0,
+    a tail shorter than an interval) one-epoch graphs."""
 
     form = "device-chunk"
 
-    def __init__(self, model, train_loader, val_loader, test_loader, epochs, early_stopping, control_every, lookahead):
+    def _eligible(self):
         from .store import DeviceGenerator, DeviceLoader
-        self.model, self.loaders = model, (train_loader, val_loader, test_loader)
-        self.epochs, self.every, self.lookahead = epochs, control_every, lookahead
-        opt = model.optimizer
-        self.sched = _plateau_of(model)
-        if self.sched is None:
-            raise _HostForm("the scheduler is not a ReduceLROnPlateau with mode 'min', threshold_mode 'rel' and one group")
-        if not isinstance(opt, FusedFlatOptimizer) or len(opt.param_groups) != 1:
-            raise _HostForm("the optimiser is not one of the fused ones with one parameter group")
-        if not isinstance(train_loader, DeviceLoader):
+        if not isinstance(self.loaders[0], DeviceLoader):
             raise _HostForm("the train loader is a host loader")
-        why = DeviceGenerator.reason(train_loader)
+        why = DeviceGenerator.reason(self.loaders[0])
         if why is not None:
             raise _EpochForm(why)
-        self.args = _lib.FitControlArgs()       # (`_resolve` fills the device form's pointers in: not used here)
-        for attempt in range(2):
-            self._resolve()
-            self.cs = ChunkWindows.of(model, self.loaders, (self.tw, self.vw, self.tew), self.fl, epochs, early_stopping,
-                                      control_every)
-            if self.cs is None:
-                raise _EpochForm("the chunk graphs could not be captured")
-            # (building them ran the steps: the loaders' windows must still stand, else once more from the top)
-            if all(T._replayable(w.steps, w._fp, False) for w in (self.tw.window, self.vw, self.tew)):
-                break
-            if attempt:
-                raise _lib.HcgError("fit_network: a window went stale again right after the chunk graphs were built")
-        cs = self.cs
-        opt.sync_lr()
-        cs.reset()
-        self.state_dev, self.log_dev, self.best, self.nstate = cs.state_dev, cs.log_dev, cs.best, cs.nstate
-        self.state_pin, self.state_events = cs.pinned(lookahead)
-        self.issued, self.controls, self.done, self.stop_seen, self.launches = 0, 0, False, False, 0
-        self.t0, self.enqueue_s = time.perf_counter(), 0.0
 
-    def issue_chunk(self):
-        """Enqueue the next chunk on the current stream."""
-        cs, e, left = self.cs, self.issued, self.epochs - self.issued
-        if left <= 0:
-            return
-        if e == 0 or left < self.every:
-            L, n = 1, (1 if e == 0 else left)   # (epoch 0 alone; a tail: the rest, epoch by epoch)
-        else:
-            L, n = self.every, 1
+    def _bind(self, wins, fl):
+        """The kept graphs for the windows as they are now (building them runs the windows' steps), at a fit's start."""
+        self.cs = ChunkWindows.of(self.model, self.loaders, wins, fl, self.epochs, self.early_stopping, self.every)
+        if self.cs is None:
+            raise _EpochForm("the chunk graphs could not be captured")
+        self.block = self.cs.block
+        self.cs.reset()
+        return True
+
+    def _issue(self, first, end):
+        n = end - first
+        L, n = (n, 1) if n == self.every else (1, n)
+        graph = self.cs.graphs[L]
         for _ in range(n):
-            cs.graphs[L].replay()
-        self.issued += L * n
-        self.launches += n
-        if (self.issued - 1) % self.every == 0:
-            slot = self.controls % (self.lookahead + 1)
-            self.state_pin[slot].copy_(self.state_dev, non_blocking=True)
-            self.state_events[slot].record()
-            self.controls += 1
-        self.enqueue_s = time.perf_counter() - self.t0
+            graph.replay()
+        return n
 
     def _settle_generator(self, counted):
         """Epochs issued past the stop drew nothing (the gate): the device generator IS where the host loop's would be."""
         if self.cs.shuffle:
             self.cs.gen.to_host()
 
-    def _graph_launches(self) -> int:
-        return self.launches
-
 
 FORMS = ("epoch", "chunk")
-
-
-def chunk_launches(epochs: int, control_every: int) -> int:
-    """Graph launches of a chunk-form fit that runs all `epochs`: epoch 0, the full control intervals, the tail's epochs."""
-    return 1 + (epochs - 1) // control_every + (epochs - 1) % control_every
 
 
 def build_chunk_windows(model, train_loader, val_loader, test_loader, epochs=250, early_stopping=6, control_every=5):
@@ -582,7 +561,7 @@ def _make_run(form, model, loaders, epochs, early_stopping, control_every, looka
                 return _ChunkFit(model, *loaders, epochs, early_stopping, control_every, lookahead)
             except _EpochForm:
                 pass
-        return _DeviceFit(model, *loaders, epochs, early_stopping, control_every, lookahead)
+        return _EpochFit(model, *loaders, epochs, early_stopping, control_every, lookahead)
     except _HostForm:
         return None
 

@@ -23,6 +23,7 @@ the autograd path with the same arithmetic contract.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import NamedTuple, Optional
 
@@ -958,6 +959,30 @@ def _replayable(steps, fingerprints, updates) -> bool:
     return True
 
 
+@contextlib.contextmanager
+def _taken_back(opt, extra=(), what="capture"):
+    """A capture's warm-up runs every step once: hidden extra epochs.  They are undone: parameters, moments and the step count
+    (re-based onto the optimiser's flat storages BEFORE the snapshot) and the `extra` tensors go back to what they were, in
+    place (same storages, so the captured addresses stay valid) -- also when the capture fails, since the caller then trains
+    on in another form.  The exchange stamp is never taken back.  Yields `restore()`, for the caller of several captures."""
+    live = opt.capture_state()
+    held = live + list(extra)
+    saved = [t.clone() for t in held]
+
+    def restore():
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for t, u in zip(held, saved):
+                t.copy_(u)
+        torch.cuda.synchronize()
+    try:
+        yield restore
+    finally:
+        restore()
+    if not opt.on_storages(live):
+        raise _lib.HcgError(f"{what}: the optimiser re-based its state during the capture")
+
+
 class StepWindow:
     """Several consecutive training steps as ONE hipGraph: `steps[i]` (a `FusedTrainStep`, all on the same model) run on
     `batches[i]` (a Batch, or a callable returning one), in order, the weights carried from step to step exactly as
@@ -989,22 +1014,25 @@ class StepWindow:
         self.steps, self.model, self.forward_only = steps, model, bool(forward_only)
         self.updates = steps[0].optimizer_step and not self.forward_only
         self.batches, self.counts64 = batches, counts64      # (kept alive: the graph reads their storages)
-        run = lambda: [st(b() if callable(b) else b, _forward_only=self.forward_only) for st, b in zip(steps, batches)]
-        # warm-up (every step once): every buffer allocated, optimiser state re-based
-        cap = _Capture(model.optimizer if any(st.optimizer_step for st in steps) else None, self.updates, run)
+        # warm-up (every step once): every buffer allocated, optimiser state re-based, the sum's kernels loaded
+        cap = _Capture(model.optimizer if any(st.optimizer_step for st in steps) else None, self.updates, self.run)
         self.value_host = None
         if counts64 is not None:
             self.value_host = torch.zeros(1, dtype=torch.float64).pin_memory()
-            _weighted_loss_dev([counts64.new_zeros((), dtype=torch.float32) for _ in steps], counts64)   # (its kernels loaded before the capture)
-            self.value_host.copy_(counts64[:1], non_blocking=True)
+            self.value_host.copy_(counts64[:1], non_blocking=True)       # (the copy's path taken before the capture)
             torch.cuda.synchronize()
         self.graph = cap.graph
         with cap.recording():
-            self.losses = run()
+            self.losses, self.value_dev = self.run()
             if counts64 is not None:
-                self.value_dev = _weighted_loss_dev(self.losses, counts64)
                 self.value_host.copy_(self.value_dev.reshape(1), non_blocking=True)
         self._fp = [st._graph_fingerprint() for st in steps]
+
+    def run(self):
+        """The steps once, in order, on the current stream (eager, or into a graph that is being recorded) -> their losses and
+        dot(losses, counts64), a float64 device scalar (None without `counts64`)."""
+        losses = [st(b() if callable(b) else b, _forward_only=self.forward_only) for st, b in zip(self.steps, self.batches)]
+        return losses, (None if self.counts64 is None else _weighted_loss_dev(losses, self.counts64))
 
     def value(self) -> float:
         """dot(losses, counts64) of the last replay (needs `counts64`): waits for the current stream, reads the pinned scalar."""
@@ -1099,24 +1127,11 @@ class EpochWindow:
         if why is not None:
             raise _lib.HcgError(f"EpochWindow: {why}")
         self.counts = torch.tensor([float(B) for B in self.Bs], dtype=torch.float64, device=dev)
-        # the capture's warm-up runs every step once: a hidden extra epoch.  It is undone: parameters, moments and the step
-        # count go back to what they were, in place (same storages, so the captured addresses stay valid) -- also when the
-        # capture fails, since the caller then trains on in its per-batch loop.  The exchange stamp is never taken back
         self._layout(np.arange(G))
         for q in model.parameters():
             _lib.require_gpu(q)
-        opt = model.optimizer
-        live = opt.capture_state()          # (re-based onto the optimiser's flat storages BEFORE the snapshot)
-        saved = [t.clone() for t in live]
-        try:
+        with _taken_back(model.optimizer, what="EpochWindow"):      # (the warm-up is a hidden extra epoch)
             self.window = StepWindow(self.steps, fns, counts64=self.counts)
-        finally:
-            torch.cuda.synchronize()
-            with torch.no_grad():
-                for t, u in zip(live, saved):
-                    t.copy_(u)
-        if not opt.on_storages(live):
-            raise _lib.HcgError("EpochWindow: the optimiser re-based its state during the capture")
 
     def _layout(self, order, staging=None):
         """The epoch's index arrays (`store.epoch_layout`) for the graphs in this order -> device, through the window's pinned
