@@ -21,8 +21,13 @@ Public surface (mirrors the reference's names for this path):
                                                 predict_test.py loop); train.predict_networks is its loader form
     ShapleySampling, draw_permutations          Shapley value sampling of a batch of graphs, the permutation walk on chip
                                                 (the reference's second explain algorithm, explain_gnn.py)
+    IntegratedGradients, quadrature             integrated gradients (Captum's IntegratedGradients through the same
+                                                CaptumExplainer entry point) of a batch of graphs, the whole path of every
+                                                graph in one launch; method="gradient" / saliency=True are its one-step
+                                                relatives InputXGradient and Saliency
 Compute lives in csrc/libhcatgnet_hip.so (hand-written HIP for gfx950) behind include/hcatgnet_hip.h.
 """
+from .attribution import IntegratedGradients, IntegratedGradientsResult, quadrature  # noqa: F401
 from .batch import Batch, Data, DataLoader, collate  # noqa: F401
 from .call_methods import default_options, make_network  # noqa: F401
 from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F401
@@ -37,4 +42,5 @@ from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
            "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "ExplainFit", "ExplainFitResult",
-           "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl"]
+           "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
+           "quadrature"]

@@ -1,4 +1,4 @@
-"""The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`: one
+"""The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`, `IntegratedGradients`: one
 graph per workgroup, all through `hcg_explain`): what a model must look like, the batch checks and their reason strings, the
 library's shape query, and the argument block's graph and weight pointers.  Private: the classes are the interface.
 """
@@ -18,7 +18,8 @@ SLOPE = 0.01                       # nn.LeakyReLU() default (reference model/gcn
 _MODES = {_lib.HCG_EXPLAIN_GRAPHS: ("one-launch explain", 224, "hcg_explain (query)"),
           _lib.HCG_EXPLAIN_ENSEMBLE: ("one-launch ensemble", 224, "hcg_explain (ensemble query)"),
           _lib.HCG_EXPLAIN_SHAPLEY: ("on-chip Shapley", 184, "hcg_explain (shapley query)"),
-          _lib.HCG_EXPLAIN_FIT: ("one-launch explainer fit", 224, "hcg_explain (fit query)")}
+          _lib.HCG_EXPLAIN_FIT: ("one-launch explainer fit", 224, "hcg_explain (fit query)"),
+          _lib.HCG_EXPLAIN_INTEGRATED: ("one-launch integrated gradients", 224, "hcg_explain (integrated query)")}
 
 
 def model_shape(model):

@@ -27,6 +27,7 @@ HCG_STRUCT_FIT_CONTROL_ARGS, HCG_STRUCT_FIT_STATE = 8, 9
 HCG_STRUCT_EPOCH_DRAW_ARGS, HCG_STRUCT_PCG64 = 10, 11
 HCG_EPOCH_DRAW_MAX_GRAPHS = 8192                         # graphs one hcg_collate draw launch takes (its workgroup's LDS)
 HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY, HCG_EXPLAIN_FIT = 0, 1, 2, 3, 4   # modes of hcg_explain
+HCG_EXPLAIN_INTEGRATED = 5
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
 HCG_ERR_UNSUPPORTED = -3
@@ -109,8 +110,10 @@ class HeadArgs(ctypes.Structure):
 
 class ExplainArgs(ctypes.Structure):
     """hcg_explain_args: a batch of graphs explained in one launch, one any-shape layer's edge-multiplier gradient, an
-    ensemble of models predicting one batch in one launch, Shapley value sampling of a batch of graphs, or the whole
-    GNNExplainer mask fit of a batch of graphs."""
+    ensemble of models predicting one batch in one launch, Shapley value sampling of a batch of graphs, the whole
+    GNNExplainer mask fit of a batch of graphs, or its integrated gradients.  The header's `path_` fields
+    (HCG_EXPLAIN_INTEGRATED) share the storage of the `fit_` block through a union; here they are the `_Overlay` attributes
+    attached below (`PATH_FIELDS`), so `_fields_`, the size and every offset stay what they were."""
     _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
                 ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
                 ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
@@ -126,6 +129,39 @@ class ExplainArgs(ctypes.Structure):
                 ("fit_hard_count", P), ("fit_loss_hist", P), ("fit_edge_mask_out", P), ("fit_node_mask_out", P),
                 ("step_first", I32), ("epoch_count", I32), ("fit_lr", F32), ("fit_beta1", F32), ("fit_beta2", F32),
                 ("fit_eps", F32), ("fit_coeffs", F32 * 4)]
+
+
+class _Overlay:
+    """A member of a union in the header that the ctypes mirror does not list in `_fields_`: a value of `ctype` at a fixed
+    byte `offset` of the structure, read and written like a field (None / int for a pointer)."""
+
+    def __init__(self, ctype, offset: int):
+        self.ctype, self.offset, self.size = ctype, int(offset), ctypes.sizeof(ctype)
+
+    def __get__(self, obj, owner=None):
+        return self if obj is None else self.ctype.from_address(ctypes.addressof(obj) + self.offset).value
+
+    def __set__(self, obj, value):
+        self.ctype.from_address(ctypes.addressof(obj) + self.offset).value = value
+
+
+# hcg_explain_args' HCG_EXPLAIN_INTEGRATED members, in the header's order, from the offset of `fit_edge_logit` on
+PATH_FIELDS = (("path_alpha", P), ("path_weight", P), ("path_node_attr", P), ("path_edge_attr", P), ("path_out_full", P),
+               ("path_out_base", P), ("path_steps", I32), ("path_step_first", I32), ("path_step_count", I32),
+               ("path_class_index", I32))
+
+
+def _attach_path_fields():
+    off = ExplainArgs.fit_edge_logit.offset
+    for name, ctype in PATH_FIELDS:
+        align = ctypes.alignment(ctype)
+        off = (off + align - 1) // align * align
+        setattr(ExplainArgs, name, _Overlay(ctype, off))
+        off += ctypes.sizeof(ctype)
+    assert off <= ctypes.sizeof(ExplainArgs)
+
+
+_attach_path_fields()
 
 
 class CollateSlot(ctypes.Structure):

@@ -1,0 +1,293 @@
+"""Gradient attributions for a batch of graphs: integrated gradients, input x gradient, saliency.
+
+The reference's explain stage reaches Captum through `torch_geometric.explain.Explainer(CaptumExplainer(name), ...,
+node_mask_type='attributes', edge_mask_type='object')` (scripts_experiments/explain_gnn.py); `ShapleySampling` serves the
+name it uses, `'ShapleyValueSampling'`.  The same entry point takes `'IntegratedGradients'`: attributions of the same kind
+(the same features, baseline 0, one value per node-feature entry and per edge) for `n_steps` forward and backward passes
+per graph instead of one forward per feature per permutation.  `IntegratedGradients` runs the whole path of every graph
+of a batch in ONE launch (csrc/explain.hip: `ExplainStep`'s kernel with a loop over the quadrature points inside).  No
+artefact of the reference pins these values: parity is against an fp64 restatement on the oracle
+(tests/integrated_ref.py).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _frozen, _lib
+from .explain import ExplainStep
+from .shapley import CUS, LAUNCH_SECONDS
+
+METHODS = ("gausslegendre", "riemann_middle", "gradient")
+ENDPOINT_METHODS = ("riemann_left", "riemann_right", "riemann_trapezoid")
+STEP_SECONDS = 400e-6              # one forward + backward of a workgroup at the shape limits: an estimate (default_steps_per_launch)
+
+
+class IntegratedGradientsResult(NamedTuple):
+    node_attr: torch.Tensor      # [N, F]
+    edge_attr: torch.Tensor      # [E], the batch's edge order
+    out_full: torch.Tensor       # [B, C] the model's output at masks of 1 (= the plain forward)
+    out_base: torch.Tensor       # [B, C] at masks of 0
+
+
+def quadrature(method: str, n_steps: int):
+    """-> (alpha [n_steps], weight [n_steps]) float32 CPU tensors: the points in (0, 1) and their weights, computed in
+    float64 and rounded once.  These float32 values are what every path uses.
+        gausslegendre    numpy.polynomial.legendre.leggauss(n) mapped to [0, 1], weights halved
+        riemann_middle   alpha_k = (k + 1/2) / n, w_k = 1 / n
+        gradient         one point: alpha = 1, w = 1 (`n_steps` must be 1)
+    Captum's methods with a point at 0 or 1 (riemann_left / _right / _trapezoid) are refused: at alpha = 0 every node row
+    of a graph is identical, the max-pool is one large exact tie and the gradient there is a convention, not a value."""
+    n = int(n_steps)
+    if method in ENDPOINT_METHODS:
+        raise ValueError(f"method {method!r} has a quadrature point at alpha = 0 or 1; at alpha = 0 every node row of a graph is "
+                         f"identical and the max-pool is one exact tie, so the gradient there is not defined by the model: use "
+                         f"'gausslegendre' or 'riemann_middle'")
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}; got {method!r}")
+    if n < 1:
+        raise ValueError(f"n_steps must be at least 1; got {n_steps}")
+    if method == "gausslegendre":
+        t, w = np.polynomial.legendre.leggauss(n)
+        alpha, weight = (t + 1.0) / 2.0, w / 2.0
+    elif method == "riemann_middle":
+        alpha, weight = (np.arange(n, dtype=np.float64) + 0.5) / n, np.full(n, 1.0 / n, dtype=np.float64)
+    else:
+        if n != 1:
+            raise ValueError(f"method 'gradient' is one step; got n_steps = {n_steps}")
+        alpha, weight = np.ones(1), np.ones(1)
+    return torch.from_numpy(np.ascontiguousarray(alpha)).to(torch.float32), torch.from_numpy(np.ascontiguousarray(weight)).to(torch.float32)
+
+
+class IntegratedGradients:
+    """Integrated gradients of a frozen model for a whole batch of graphs, one launch per call.
+
+        ig = IntegratedGradients(model, n_steps=50, method="gausslegendre")
+        r = ig(batch, class_index=0, n_steps=None, steps_per_launch=None)
+        # IntegratedGradientsResult(node_attr [N, F], edge_attr [E], out_full [B, C], out_base [B, C])
+        ig.convergence_delta(batch, r)      # [B] float64
+
+    Definition: Captum's `IntegratedGradients` as torch_geometric's `CaptumExplainer` calls it.  The inputs are a node
+    mask of ones [N, F] and an edge mask of ones [E], the baselines are 0.  The masks mean what they mean in
+    `ExplainStep(apply_sigmoid=False)`: `x * node_mask` goes into the first layer; the edge mask multiplies every message
+    of every conv layer after gcn_norm; dinv comes from the unmasked in-degree; self loops keep 1, and an explicit (i, i)
+    edge is part of the unit self loop.  For graph g, output column c = `class_index` and quadrature points alpha_k in
+    (0, 1) with weights w_k (`quadrature(method, n_steps)`), G_k is the gradient of out[g, c] with respect to (node mask,
+    edge mask) evaluated with every node-mask and every edge-mask entry of the graph equal to alpha_k; the attribution is
+    sum_k w_k G_k, summed in float32 in the order k = 0, 1, ... (the factor input - baseline is 1).  An entry of x that is
+    exactly 0 and an explicit (i, i) edge get exactly 0.  `out_full` / `out_base` are the outputs at masks of 1 and of 0.
+
+    `convergence_delta(batch, r)` = sum of graph g's attributions - (out_full - out_base)[g, c], in float64: a diagnostic.
+    The path of a LeakyReLU / max-pool model is piecewise polynomial with thousands of kinks, so the quadrature does not
+    close this gap at any practical `n_steps`; nothing here asserts that it does.
+
+    `method="gradient"` is the one-step case alpha = 1, w = 1: `CaptumExplainer`'s `InputXGradient` on the masks (the
+    gradient at masks of ones); with `saliency=True` its absolute value (`Saliency`).
+
+    The steps are split into launches of `steps_per_launch` (None: `default_steps_per_launch`); the result is bitwise
+    independent of that split, of the run and of the rest of the batch.  The weights are read, never written; no
+    parameter's `.grad` is touched and no mask stays attached to the model.  `batch` needs the collate metadata
+    `ExplainStep` needs.  Buffers are allocated for the largest call seen and reused (in steady state a call allocates
+    nothing); the returned tensors are views of them, overwritten by the next call.
+
+    When `reason(batch)` is not None (shape outside the kernel, `embedding_dim != 64`, CPU tensors, `use_fused` off) the same
+    call runs `loop`: one `ExplainStep(apply_sigmoid=False)` call per step with `dout` = the one-hot column on GPU tensors,
+    plain torch autograd on CPU tensors, accumulated in float32 in step order.  `last_path` says which one ran ("fused" /
+    "loop")."""
+
+    def __init__(self, model: torch.nn.Module, n_steps: int = 50, method: str = "gausslegendre", saliency: bool = False):
+        if saliency and method != "gradient":
+            raise ValueError(f"saliency=True is the absolute value of method='gradient'; got method {method!r}")
+        if method == "gradient":
+            n_steps = 1
+        quadrature(method, n_steps)                         # (refuses the method or the step count)
+        self.model, self.n_steps, self.method, self.saliency = model, int(n_steps), method, bool(saliency)
+        self.last_path: Optional[str] = None
+        self.last_class_index: Optional[int] = None
+        self._cap = None            # (N, E, B, workspace bytes) capacity of the buffers
+        self._bufs = None
+        self._points = {}           # (n_steps, device) -> (alpha, weight) on the device
+        self._args = _lib.ExplainArgs()
+        self._step = ExplainStep(model, apply_sigmoid=False)
+
+    # ------------------------------------------------------------------ support check (host only, no sync)
+    def _shape_args(self, a, batch) -> Optional[str]:
+        m = self.model
+        why = _frozen.model_reason(m)
+        if why is None and batch is not None:
+            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, int(m.n_node_features), "model")
+        return why or _frozen.query(a, _lib.HCG_EXPLAIN_INTEGRATED, _frozen.model_shape(m), batch, edge_mask=None, node_mask=None,
+                                    target=None, dout=None, dx=None)
+
+    def reason(self, batch=None) -> Optional[str]:
+        """None when this model (and `batch`) takes the one-launch kernel, else why not.  Host metadata only."""
+        return self._shape_args(_lib.ExplainArgs(), batch)
+
+    def lds_bytes(self, batch) -> Optional[int]:
+        """Dynamic LDS of one workgroup of the kernel for this batch, as the library's query reports it; None when the
+        batch does not take the kernel."""
+        a = _lib.ExplainArgs()
+        return int(a.lds_bytes) if self._shape_args(a, batch) is None else None
+
+    @staticmethod
+    def default_steps_per_launch(n_steps: int, num_graphs: int) -> int:
+        """Steps of one launch: as many as keep its run time near `shapley.LAUNCH_SECONDS`, at least 1.  The device runs
+        the graphs in ceil(num_graphs / CUS) rounds of one workgroup per compute unit (the occupancy at the shape limits'
+        LDS), each step of a round taking `STEP_SECONDS`.  `STEP_SECONDS` is an ESTIMATE: `ExplainFit` -- the same forward
+        and backward per epoch -- takes about 90 us per epoch and workgroup on real-size graphs and two conv layers (README:
+        144.8 ms for 100 epochs of 4096 graphs), extrapolated to 224 nodes and four layers; nobody has timed a launch at the
+        limit shapes."""
+        rounds = max(1, -(-int(num_graphs) // CUS))
+        return max(1, min(int(n_steps), int(LAUNCH_SECONDS / (rounds * STEP_SECONDS))))
+
+    # ------------------------------------------------------------------ arguments
+    def _steps(self, n_steps) -> int:
+        n = self.n_steps if n_steps is None else int(n_steps)
+        if self.method == "gradient" and n != 1:
+            raise ValueError(f"method 'gradient' is one step; got n_steps = {n_steps}")
+        if n < 1:
+            raise ValueError(f"n_steps must be at least 1; got {n_steps}")
+        return n
+
+    def _class(self, class_index) -> int:
+        C = int(self.model._n_classes)
+        if not 0 <= int(class_index) < C:
+            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
+        return int(class_index)
+
+    def _quadrature(self, n: int, dev):
+        key = (n, str(dev))
+        if key not in self._points:
+            alpha, weight = quadrature(self.method, n)
+            self._points[key] = (alpha.to(dev), weight.to(dev))
+        return self._points[key]
+
+    # ------------------------------------------------------------------ buffers
+    def _buffers(self, N, E, B, F, C, ws_bytes, dev):
+        cap = self._cap
+        need = (N, E, B, ws_bytes)
+        if cap is None or any(n > c for n, c in zip(need, cap)) or self._bufs["full"].device != dev:
+            cap = tuple(max(n, c) for n, c in zip(need, cap or (0,) * 4))
+            f32 = dict(dtype=torch.float32, device=dev)
+            self._bufs = dict(node=torch.zeros(max(cap[0], 1), F, **f32), edge=torch.zeros(max(cap[1], 1), **f32),
+                              full=torch.zeros(max(cap[2], 1), C, **f32), base=torch.zeros(max(cap[2], 1), C, **f32),
+                              ws=torch.empty(max(cap[3], 256), dtype=torch.uint8, device=dev))
+            self._cap = cap
+        return self._bufs
+
+    # ------------------------------------------------------------------ the call
+    def __call__(self, batch, class_index: int = 0, n_steps: Optional[int] = None,
+                 steps_per_launch: Optional[int] = None) -> IntegratedGradientsResult:
+        n = self._steps(n_steps)
+        cls = self._class(class_index)
+        if steps_per_launch is not None and int(steps_per_launch) < 1:
+            raise ValueError(f"steps_per_launch must be at least 1; got {steps_per_launch}")
+        a = self._args
+        why = self._shape_args(a, batch)
+        if why is not None:
+            return self.loop(batch, cls, n)
+        m = self.model
+        x = _frozen.batch_x(batch)
+        N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
+        per = self.default_steps_per_launch(n, B) if steps_per_launch is None else min(int(steps_per_launch), n)
+        alpha, weight = self._quadrature(n, x.device)
+        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
+        bufs = self._buffers(N, E, B, F, C, int(a.workspace_bytes_needed), x.device)
+        p = _lib.ptr
+        a.flags = 0
+        _frozen.fill_graph(a, x, plan)
+        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "IntegratedGradients"))
+        a.out = None
+        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
+        a.slope = _frozen.SLOPE
+        a.path_alpha, a.path_weight = p(alpha), p(weight)
+        a.path_node_attr, a.path_edge_attr = p(bufs["node"]), p(bufs["edge"])
+        a.path_out_full, a.path_out_base = p(bufs["full"]), p(bufs["base"])
+        a.path_steps, a.path_class_index = n, cls
+        lib, stream = _lib.load(), _lib.stream_ptr()
+        for first in range(0, n, per):
+            a.path_step_first, a.path_step_count = first, min(per, n - first)
+            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (integrated)")
+        if self.saliency:
+            bufs["node"].abs_()
+            bufs["edge"].abs_()
+        self.last_path, self.last_class_index = "fused", cls
+        return IntegratedGradientsResult(bufs["node"][:N], bufs["edge"][:E], bufs["full"][:B], bufs["base"][:B])
+
+    # ------------------------------------------------------------------ the loop path (any shape, CPU tensors)
+    def _grads(self, batch, alpha: float, onehot):
+        """-> (d out[:, c] / d node mask [N, F], d out[:, c] / d edge mask [E]) with every mask entry = alpha"""
+        (N, F), E, B = batch.x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
+        dev = batch.x.device
+        if batch.x.is_cuda:
+            em = torch.full((E,), alpha, dtype=torch.float32, device=dev)
+            nm = torch.full((N, F), alpha, dtype=torch.float32, device=dev)
+            r = self._step(batch, em, nm, dout=onehot)
+            return r.d_node_mask, r.d_edge_mask
+        from .shapley import _torch_forward                 # (the package's layers take GPU tensors only)
+        em = torch.full((E,), alpha, dtype=torch.float32).requires_grad_(True)
+        nm = torch.full((N, F), alpha, dtype=torch.float32).requires_grad_(True)
+        with torch.enable_grad():
+            out = _torch_forward(self.model, batch.x.detach() * nm, batch.edge_index, batch.batch, B, em).reshape(B, -1)
+            d_n, d_e = torch.autograd.grad((out * onehot).sum(), [nm, em])     # (no parameter's .grad is touched)
+        return d_n, d_e
+
+    def _forward(self, batch, value: float):
+        (N, F), E, B = batch.x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
+        dev = batch.x.device
+        em = torch.full((E,), value, dtype=torch.float32, device=dev)
+        nm = torch.full((N, F), value, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            if batch.x.is_cuda:
+                return self._step(batch, em, nm).out.reshape(B, -1).clone()
+            from .shapley import _torch_forward
+            return _torch_forward(self.model, batch.x * nm, batch.edge_index, batch.batch, B, em).reshape(B, -1)
+
+    def loop(self, batch, class_index: int = 0, n_steps: Optional[int] = None) -> IntegratedGradientsResult:
+        """One `ExplainStep` call per quadrature point (see the class docstring), whatever `reason(batch)` says."""
+        n = self._steps(n_steps)
+        cls = self._class(class_index)
+        (N, F), E, B = batch.x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
+        dev = batch.x.device
+        alpha, weight = quadrature(self.method, n)
+        onehot = torch.zeros(B, int(self.model._n_classes), dtype=torch.float32, device=dev)
+        onehot[:, cls] = 1.0
+        node = torch.zeros(N, F, dtype=torch.float32, device=dev)
+        edge = torch.zeros(E, dtype=torch.float32, device=dev)
+        for k in range(n):
+            d_n, d_e = self._grads(batch, float(alpha[k]), onehot)
+            node.add_(d_n, alpha=float(weight[k]))
+            edge.add_(d_e, alpha=float(weight[k]))
+        if self.saliency:
+            node.abs_()
+            edge.abs_()
+        out_full, out_base = self._forward(batch, 1.0), self._forward(batch, 0.0)
+        self.last_path, self.last_class_index = "loop", cls
+        return IntegratedGradientsResult(node, edge, out_full, out_base)
+
+    # ------------------------------------------------------------------ the diagnostic
+    def convergence_delta(self, batch, result: IntegratedGradientsResult, class_index: Optional[int] = None) -> torch.Tensor:
+        """[B] float64: sum of graph g's node and edge attributions - (out_full - out_base)[g, c]; c = `class_index`
+        (None: the last call's)."""
+        if class_index is None:
+            class_index = self.last_class_index
+        if class_index is None:
+            raise ValueError("class_index is needed before the first call")
+        return convergence_delta(batch, result, self._class(class_index))
+
+
+def convergence_delta(batch, result, class_index: int) -> torch.Tensor:
+    """The formula of `IntegratedGradients.convergence_delta` on any (node_attr, edge_attr, out_full, out_base), in float64."""
+    B = int(batch.num_graphs)
+    node_attr, edge_attr, out_full, out_base = result[:4]
+    dev = node_attr.device
+    owner_n = batch.batch.to(dev)
+    owner_e = owner_n[batch.edge_index[1].to(dev)]
+    total = torch.zeros(B, dtype=torch.float64, device=dev)
+    total.index_add_(0, owner_n, node_attr.double().sum(dim=1))
+    total.index_add_(0, owner_e, edge_attr.double())
+    return total - (out_full.double()[:, class_index] - out_base.double()[:, class_index])
+

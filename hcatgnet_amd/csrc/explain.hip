@@ -35,6 +35,15 @@
 // state is read and written by ONE thread of the graph's workgroup (the same in every epoch); the counts are integers.  So a
 // fit split into several launches repeats the single launch bit for bit.  FIT = false compiles to what the kernel was
 // before the template existed (same VGPRs, no scratch, same LDS): every FIT branch is `if constexpr`.
+//
+// HCG_EXPLAIN_INTEGRATED is the third instantiation (k_explain_graphs<false, true>): integrated gradients of one output column
+// along the straight path from masks of 0 to masks of 1.  The graph is built once; then for every quadrature point of the
+// launch: mask values and the masked input tile from alpha_k (no sigmoid), the forward, the upstream gradient 1 at the
+// column, the backward above, and -- instead of storing the two mask gradients -- acc = fmaf(w_k, g, acc) on the caller's
+// attribution arrays.  Every accumulator entry belongs to ONE thread of the graph's workgroup (the index maps of the
+// outputs below), the same in every step, and step 0 starts from 0 whatever the arrays hold: a path split into several
+// launches repeats the single launch bit for bit.  The launch that holds step 0 first runs two forward-only passes (t = -2:
+// masks of 1, t = -1: masks of 0) for out_full / out_base.  The other two instantiations compile to what they were.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -71,10 +80,22 @@ struct XFit {      // what HCG_EXPLAIN_FIT adds (FIT = true only)
 
 struct XFitArgs { XArgs a; XFit f; };
 
-template <bool FIT> struct XKernelArgs { using type = XArgs; };
-template <> struct XKernelArgs<true> { using type = XFitArgs; };
+struct XPath {     // what HCG_EXPLAIN_INTEGRATED adds (PATH = true only); a.out is out_full
+  const float* alpha; const float* weight;                           // [n_steps] quadrature points and weights
+  float* node_attr;                                                  // [N][F]  IN/OUT accumulators
+  float* edge_attr;                                                  // [E]
+  float* out_base;                                                   // [B][C]
+  int step_first, steps, cls;
+};
+
+struct XPathArgs { XArgs a; XPath f; };
+
+template <bool FIT, bool PATH = false> struct XKernelArgs { using type = XArgs; };
+template <> struct XKernelArgs<true, false> { using type = XFitArgs; };
+template <> struct XKernelArgs<false, true> { using type = XPathArgs; };
 __device__ __forceinline__ const XArgs& x_base(const XArgs& a) { return a; }
 __device__ __forceinline__ const XArgs& x_base(const XFitArgs& a) { return a.a; }
+__device__ __forceinline__ const XArgs& x_base(const XPathArgs& a) { return a.a; }
 
 struct XLds {
   float* t0;            // [npad][XS]
@@ -127,8 +148,9 @@ __device__ __forceinline__ float x_dent(float m) {
   return (logf(b) + (1.f - m) / b) - (logf(a) + m / a);
 }
 
-template <bool FIT>
-__global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArgs<FIT>::type args) {
+template <bool FIT, bool PATH = false>
+__global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArgs<FIT, PATH>::type args) {
+  static_assert(!(FIT && PATH), "one loop or the other");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const XArgs& a = x_base(args);
   const XCommon& cm = a.c;
@@ -137,9 +159,9 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   const int g = blockIdx.x;
   const int F = cm.F, C = cm.C, n_conv = cm.n_conv;
   const float slope = cm.slope;
-  const bool bwd = FIT || a.target != nullptr || a.dout != nullptr || a.target_class != nullptr;
-  const bool need_dx = FIT || a.d_node_mask != nullptr || a.dx != nullptr;
-  const bool sig = FIT || a.sigmoid;
+  const bool bwd = FIT || PATH || a.target != nullptr || a.dout != nullptr || a.target_class != nullptr;
+  const bool need_dx = FIT || PATH || a.d_node_mask != nullptr || a.dx != nullptr;
+  const bool sig = !PATH && (FIT || a.sigmoid);
 
   XSpan sp;
   if (x_refused(sp, cm, g, tid)) {
@@ -153,6 +175,10 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
       d_e = args.f.edge_out;
       d_n = args.f.node_out;
       for (int t = tid; t < args.f.epochs; t += XT) args.f.loss_hist[(size_t)t * args.f.B + g] = 0.f;
+    } else if constexpr (PATH) {
+      d_e = args.f.edge_attr;
+      d_n = args.f.node_attr;
+      for (int k = tid; k < C; k += XT) args.f.out_base[(size_t)g * C + k] = 0.f;
     } else {
       if (a.loss && tid == 0) a.loss[g] = 0.f;
     }
@@ -198,7 +224,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
       L.t0[r * XS + k] = v;
     }
   };
-  if constexpr (!FIT) stage_masks(a.edge_mask, a.node_mask);
+  if constexpr (!FIT && !PATH) stage_masks(a.edge_mask, a.node_mask);
   XEdges q;
   x_edge_pass(q, er, sp, tid, cm.status);
   const XMasked fmt{L.mval};
@@ -215,13 +241,31 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
     epochs = args.f.epochs;
     if (tid < 2) hc[tid] = args.f.step_first > 0 ? args.f.hard_count[2 * g + tid] : 0;
   }
+  int t = 0;
+  if constexpr (PATH) {
+    epochs = args.f.steps;
+    t = args.f.step_first == 0 ? -2 : 0;                  // (the two forward-only passes come first)
+  }
 
 #pragma nounroll
-  for (int t = 0; t < epochs; ++t) {
+  for (; t < epochs; ++t) {
   float* loss_out = a.loss;
   if constexpr (FIT) {
     loss_out = args.f.loss_hist + (size_t)t * args.f.B;
     stage_masks(args.f.e_logit, args.f.n_logit);
+    __syncthreads();
+  }
+  if constexpr (PATH) {
+    // every mask entry of the graph = alpha_k (t = -2: 1, t = -1: 0), x~ = x alpha_k, zero-padded to 64 columns
+    const float al = t < 0 ? (t == -2 ? 1.f : 0.f) : args.f.alpha[args.f.step_first + t];
+    for (int e = tid; e < ne; e += XT) {
+      L.mval[e] = al;
+      L.eg[e] = 0.f;
+    }
+    for (int idx = tid; idx < n * XD; idx += XT) {
+      const int r = idx >> 6, k = idx & 63;
+      L.t0[r * XS + k] = k < F ? cm.x[(size_t)(nbase + r) * F + k] * al : 0.f;
+    }
     __syncthreads();
   }
 
@@ -252,6 +296,12 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   // off = position of the output row in hv / hg
   if (tid < C) {
     const float o = L.hv[off + tid];
+    if constexpr (PATH) {
+      // out_full / out_base from the forward-only passes; upstream: 1 at the column (compared, never an address)
+      if (t == -2) a.out[(size_t)g * C + tid] = o;
+      if (t == -1) args.f.out_base[(size_t)g * C + tid] = o;
+      L.hg[off + tid] = tid == args.f.cls ? 1.f : 0.f;
+    } else {
     a.out[(size_t)g * C + tid] = o;
     if (a.target_class) {
       // cross-entropy against class y (uniform per launch): every thread below C restates the row from hv.  y is compared,
@@ -277,8 +327,12 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
       L.red[tid] = d * d;
       L.hg[off + tid] = a.target ? 2.f * d / (float)C : (a.dout ? a.dout[(size_t)g * C + tid] : 0.f);
     }
+    }
   }
   __syncthreads();
+  if constexpr (PATH) {
+    if (t < 0) continue;                                  // (uniform; nothing reads the tiles behind this barrier)
+  }
   if (loss_out && tid == 0) {
     if (a.target_class) {
       loss_out[g] = L.red[0];
@@ -391,7 +445,26 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   }
   __syncthreads();
 
-  if constexpr (!FIT) {
+  if constexpr (PATH) {
+  // ---------------------------------------------------------------------------------------------- PATH: acc = fmaf(w_k, g, acc)
+  // Entry p of the accumulators belongs to the thread that reads it here (the index maps of the outputs below), in every step.
+  const XPath& f = args.f;
+  const int step = f.step_first + t;
+  const float wk = f.weight[step];
+  const bool fresh = step == 0;                           // the path starts from 0 whatever the arrays hold
+  for (int e = tid; e < ne; e += XT) {
+    const size_t p = (size_t)ebase + e;
+    f.edge_attr[p] = fmaf(wk, L.eg[e], fresh ? 0.f : f.edge_attr[p]);
+  }
+  for (int idx = tid; idx < n * XD; idx += XT) {
+    const int r = idx >> 6, k = idx & 63;
+    if (k < F) {
+      const size_t p = (size_t)(nbase + r) * F + k;
+      f.node_attr[p] = fmaf(wk, L.t0[r * XS + k] * cm.x[p], fresh ? 0.f : f.node_attr[p]);
+    }
+  }
+  __syncthreads();                                        // (the next step stages over t0 and eg)
+  } else if constexpr (!FIT) {
   // ---------------------------------------------------------------------------------------------- outputs
   for (int e = tid; e < ne; e += XT) {
     const float m = L.mval[e];
@@ -524,13 +597,52 @@ int x_fit_launch(hcg_explain_args* p, hipStream_t stream) {
   return x_launch<k_explain_graphs<true>>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax) + X_FIT_LDS_EXTRA, stream, k);
 }
 
+// hcg_explain, mode HCG_EXPLAIN_INTEGRATED, behind the shape check, the flag / NULL checks and the query
+int x_path_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->path_steps < 1 || p->path_step_first < 0 || p->path_step_count < 0 ||
+      (long long)p->path_step_first + p->path_step_count > p->path_steps)
+    return HCG_ERR_INVALID_ARG;
+  if (p->path_class_index < 0 || p->path_class_index >= p->C) return HCG_ERR_INVALID_ARG;
+  if (p->B == 0 || p->path_step_count == 0) return HCG_OK;
+  if (!p->path_out_full || !p->path_out_base || !p->path_alpha || !p->path_weight) return HCG_ERR_INVALID_ARG;
+  if (!p->graph_ptr || !p->edge_ptr || !p->status || (p->N > 0 && !p->x) || (p->E > 0 && !p->edge_index)) return HCG_ERR_INVALID_ARG;
+  for (int l = 0; l < p->n_conv; ++l)
+    if (!p->conv_W[l] || !p->conv_b[l]) return HCG_ERR_INVALID_ARG;
+  for (int i = 0; i < p->R; ++i)
+    if (!p->head_W[i] || !p->head_b[i]) return HCG_ERR_INVALID_ARG;
+  if ((p->E > 0 && !p->path_edge_attr) || (p->N > 0 && !p->path_node_attr)) return HCG_ERR_INVALID_ARG;
+  if (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed) return HCG_ERR_WORKSPACE;
+
+  XPathArgs k;
+  XArgs& a = k.a;
+  x_fill_common(a.c, p);
+  a.edge_mask = a.node_mask = a.target = a.dout = nullptr;
+  a.target_class = nullptr;
+  a.out = p->path_out_full;
+  a.loss = a.d_edge_mask = a.d_node_mask = a.dx = nullptr;
+  a.ws = (float*)p->workspace;
+  a.N = (int)p->N;
+  a.sigmoid = 0;
+  XPath& f = k.f;
+  f.alpha = p->path_alpha;
+  f.weight = p->path_weight;
+  f.node_attr = p->path_node_attr;
+  f.edge_attr = p->path_edge_attr;
+  f.out_base = p->path_out_base;
+  f.step_first = p->path_step_first;
+  f.steps = p->path_step_count;
+  f.cls = p->path_class_index;
+  return x_launch<k_explain_graphs<false, true>>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax), stream, k);
+}
+
 }  // namespace
 
 extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (!p) return HCG_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   // the class-index form of the upstream gradient belongs to HCG_EXPLAIN_GRAPHS and HCG_EXPLAIN_FIT alone
-  if ((p->flags & HCG_EXPLAIN_TARGET_CLASS) && (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD || p->mode == HCG_EXPLAIN_ENSEMBLE || p->mode == HCG_EXPLAIN_SHAPLEY))
+  if ((p->flags & HCG_EXPLAIN_TARGET_CLASS) && (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD || p->mode == HCG_EXPLAIN_ENSEMBLE ||
+                                                p->mode == HCG_EXPLAIN_SHAPLEY || p->mode == HCG_EXPLAIN_INTEGRATED))
     return HCG_ERR_INVALID_ARG;
   if (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD) {
     if (p->flags & HCG_EXPLAIN_QUERY) { p->workspace_bytes_needed = 0; return HCG_OK; }
@@ -540,16 +652,21 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (p->mode == HCG_EXPLAIN_ENSEMBLE) return hcg_ensemble_launch(p, stream);
   if (p->mode == HCG_EXPLAIN_SHAPLEY) return hcg_shapley_launch(p, stream);
   const bool fit = p->mode == HCG_EXPLAIN_FIT;
-  if (p->mode != HCG_EXPLAIN_GRAPHS && !fit) return HCG_ERR_INVALID_ARG;
+  const bool path = p->mode == HCG_EXPLAIN_INTEGRATED;
+  if (p->mode != HCG_EXPLAIN_GRAPHS && !fit && !path) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p)) return HCG_ERR_UNSUPPORTED;
+  // (PATH: the masks and the upstream gradient are the algorithm's own)
+  if (path && ((p->flags & HCG_EXPLAIN_SIGMOID) || p->target || p->dout || p->edge_mask || p->node_mask || p->dx)) return HCG_ERR_INVALID_ARG;
   const bool cls = (p->flags & HCG_EXPLAIN_TARGET_CLASS) != 0;
   if (cls && p->C < 2) return HCG_ERR_UNSUPPORTED;          // a cross-entropy needs two classes or more
   // (FIT: the tiles and lists of HCG_EXPLAIN_GRAPHS and two hard counts behind them)
   if (fit) p->lds_bytes = (int32_t)(x_lds_bytes(x_round4(p->max_nodes, 4), x_round4(p->max_edges, 4)) + X_FIT_LDS_EXTRA);
+  if (path) p->lds_bytes = (int32_t)x_lds_bytes(x_round4(p->max_nodes, 4), x_round4(p->max_edges, 4));
   // H_l and A_l of every layer, [N][64] f32 each: the backward reads them again
   p->workspace_bytes_needed = hcg_align_up((size_t)2 * p->n_conv * (size_t)(p->N > 0 ? p->N : 1) * XD * sizeof(float), 256);
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (fit) return x_fit_launch(p, stream);
+  if (path) return x_path_launch(p, stream);
   if (p->B == 0) return HCG_OK;
   const bool bwd = p->target || p->dout;                       // (target: the slot in either reading)
   if ((p->target && p->dout) || (cls && !p->target_class)) return HCG_ERR_INVALID_ARG;

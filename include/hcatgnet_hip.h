@@ -132,7 +132,7 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
                       int64_t N, int64_t E, int64_t F, int64_t D,
                       void* workspace, size_t workspace_bytes, hcg_stream_t stream);
 
-/* ---- explain mode (f4): ONE entry point, five jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
+/* ---- explain mode (f4): ONE entry point, six jobs (`mode`).  HOST struct; zero it first, unused parts stay NULL.
  * PyG's Explainer multiplies every message by an edge mask inside each MessagePassing layer, AFTER gcn_norm, self loops keep 1
  * (reference scripts_experiments/explain_gnn.py:39-50: edge_mask_type='object'); the node mask multiplies x.
  *
@@ -214,18 +214,37 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   fit_edge_mask_out / fit_node_mask_out = sigmoid(logit) of the hard entries, 0 elsewhere.  edge_mask, node_mask, dout and dx
  *   must be NULL.  Shapes, workspace and refusals as HCG_EXPLAIN_GRAPHS (a refused graph: its rows of out, fit_loss_hist and
  *   the two mask outputs zero, its state untouched).  No float atomics, no exchange between workgroups.
- *   HCG_EXPLAIN_QUERY as above; this mode also writes lds_bytes. */
+ *   HCG_EXPLAIN_QUERY as above; this mode also writes lds_bytes.
+ * HCG_EXPLAIN_INTEGRATED: integrated gradients (Captum's IntegratedGradients as torch_geometric's CaptumExplainer calls it:
+ *   inputs a node mask of ones [N, F] and an edge mask of ones [E], baselines 0) of output column path_class_index for a batch
+ *   of graphs in ONE launch: the kernel of HCG_EXPLAIN_GRAPHS without sigmoid with a loop over the quadrature points around
+ *   forward and backward, one workgroup per graph, the graph built once.  For k = path_step_first .. path_step_first +
+ *   path_step_count - 1, ascending: every node-mask and edge-mask entry of the graph is path_alpha[k]; the upstream gradient
+ *   is 1 at column path_class_index and 0 elsewhere (the index is compared, never used as an address); and the two mask
+ *   gradients g are accumulated, acc = fmaf(path_weight[k], g, acc), into path_node_attr [N, F] / path_edge_attr [E] (an
+ *   explicit (i, i) edge and an entry whose x is 0: exactly 0).  Every accumulator entry is read and written by ONE thread
+ *   of the graph's workgroup, the same in every step; the launch with path_step_first = 0 starts from 0 whatever the arrays
+ *   hold, a later one continues from them: a path split into several launches is bitwise the single launch.  The launch
+ *   with path_step_first = 0 also runs two forward-only passes, masks of 1 and of 0, into path_out_full / path_out_base
+ *   [B, C].  path_alpha / path_weight: float32 device arrays [path_steps].  HCG_EXPLAIN_SIGMOID and HCG_EXPLAIN_TARGET_CLASS
+ *   must be clear; target, dout, edge_mask, node_mask and dx must be NULL; path_steps >= 1, 0 <= path_step_first,
+ *   path_step_first + path_step_count <= path_steps, 0 <= path_class_index < C (each: HCG_ERR_INVALID_ARG).  `out` is not
+ *   used.  The path_ fields share the storage of the fit_ fields (a union: the two modes never meet in one call), so the
+ *   struct's size and every earlier offset are what they were.  Shapes, workspace, LDS and refusals as HCG_EXPLAIN_GRAPHS
+ *   (a refused graph: its rows of path_out_full / path_out_base and its entries of both attribution arrays zero, the other
+ *   graphs untouched).  HCG_EXPLAIN_QUERY as above (checks the flags and the NULL pointers too); also writes lds_bytes. */
 #define HCG_EXPLAIN_GRAPHS 0
 #define HCG_EXPLAIN_LAYER_EDGE_GRAD 1
 #define HCG_EXPLAIN_ENSEMBLE 2
 #define HCG_EXPLAIN_SHAPLEY 3
 #define HCG_EXPLAIN_FIT 4
+#define HCG_EXPLAIN_INTEGRATED 5
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -275,7 +294,9 @@ typedef struct hcg_explain_args {
   int32_t class_index;                   /* the explained output column, 0 .. C - 1 */
   int32_t lds_bytes;                     /* OUT: dynamic LDS of one workgroup for max_nodes / max_edges (also by a query) */
   int32_t reserved;
-  float* fit_edge_logit;                 /* HCG_EXPLAIN_FIT from here on.  IN/OUT state of the edge mask, [E] each */
+  union {                                /* ONE block of storage, read by `mode` (the struct's size and every offset stay): */
+  struct {                               /*   HCG_EXPLAIN_FIT */
+  float* fit_edge_logit;                 /* IN/OUT state of the edge mask, [E] each */
   float* fit_edge_exp_avg;
   float* fit_edge_exp_avg_sq;
   uint8_t* fit_edge_hard;                /* 1: the entry's first gradient was not 0 (written by the step-0 epoch) */
@@ -291,6 +312,20 @@ typedef struct hcg_explain_args {
   int32_t epoch_count;                   /* epochs of this launch, >= 1 */
   float fit_lr, fit_beta1, fit_beta2, fit_eps;
   float fit_coeffs[4];                   /* edge_size (on a sum), edge_ent, node_feat_size (on a mean), node_feat_ent */
+  };
+  struct {                               /*   HCG_EXPLAIN_INTEGRATED */
+  const float* path_alpha;               /* [path_steps] quadrature points in (0, 1), device memory */
+  const float* path_weight;              /* [path_steps] their weights */
+  float* path_node_attr;                 /* IN/OUT [N, F]: sum_k w_k d out[g, c] / d node mask at alpha_k (read when path_step_first > 0) */
+  float* path_edge_attr;                 /* IN/OUT [E], the caller's edge order */
+  float* path_out_full;                  /* OUT [B, C]: the outputs at masks of 1 (written by the launch with path_step_first = 0) */
+  float* path_out_base;                  /* OUT [B, C]: at masks of 0 */
+  int32_t path_steps;                    /* n_steps of the whole path, >= 1 */
+  int32_t path_step_first;               /* first quadrature point of this launch */
+  int32_t path_step_count;               /* points of this launch; path_step_first + path_step_count <= path_steps */
+  int32_t path_class_index;              /* the attributed output column c, 0 .. C - 1 */
+  };
+  };
 } hcg_explain_args;
 int hcg_explain(hcg_explain_args* args_host, hcg_stream_t stream);
 
