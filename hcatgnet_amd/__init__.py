@@ -25,9 +25,11 @@ Public surface (mirrors the reference's names for this path):
                                                 CaptumExplainer entry point) of a batch of graphs, the whole path of every
                                                 graph in one launch; method="gradient" / saliency=True are its one-step
                                                 relatives InputXGradient and Saliency
+    EnsembleAttribution                         the same attributions of M models in one launch (one workgroup per graph
+                                                and model), with their mean and standard deviation over the models
 Compute lives in csrc/libhcatgnet_hip.so (hand-written HIP for gfx950) behind include/hcatgnet_hip.h.
 """
-from .attribution import IntegratedGradients, IntegratedGradientsResult, quadrature  # noqa: F401
+from .attribution import EnsembleAttribution, EnsembleAttributionResult, IntegratedGradients, IntegratedGradientsResult, quadrature  # noqa: F401
 from .batch import Batch, Data, DataLoader, collate  # noqa: F401
 from .call_methods import default_options, make_network  # noqa: F401
 from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F401
@@ -43,4 +45,4 @@ __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
            "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "ExplainFit", "ExplainFitResult",
            "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
-           "quadrature"]
+           "quadrature", "EnsembleAttribution", "EnsembleAttributionResult"]

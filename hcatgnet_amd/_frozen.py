@@ -1,5 +1,5 @@
-"""The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`, `IntegratedGradients`: one
-graph per workgroup, all through `hcg_explain`): what a model must look like, the batch checks and their reason strings, the
+"""The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`, `IntegratedGradients`,
+`EnsembleAttribution`: one graph per workgroup, all through `hcg_explain`): what a model must look like, the batch checks and their reason strings, the
 library's shape query, and the argument block's graph and weight pointers.  Private: the classes are the interface.
 """
 from __future__ import annotations

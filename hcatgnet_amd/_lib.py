@@ -28,6 +28,7 @@ HCG_STRUCT_EPOCH_DRAW_ARGS, HCG_STRUCT_PCG64 = 10, 11
 HCG_EPOCH_DRAW_MAX_GRAPHS = 8192                         # graphs one hcg_collate draw launch takes (its workgroup's LDS)
 HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLAIN_SHAPLEY, HCG_EXPLAIN_FIT = 0, 1, 2, 3, 4   # modes of hcg_explain
 HCG_EXPLAIN_INTEGRATED = 5
+HCG_EXPLAIN_MOMENTS = 6          # mean / std over the model axis of HCG_EXPLAIN_INTEGRATED's outputs with n_models > 1
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
 HCG_ERR_UNSUPPORTED = -3
@@ -113,7 +114,8 @@ class ExplainArgs(ctypes.Structure):
     ensemble of models predicting one batch in one launch, Shapley value sampling of a batch of graphs, the whole
     GNNExplainer mask fit of a batch of graphs, or its integrated gradients.  The header's `path_` fields
     (HCG_EXPLAIN_INTEGRATED) share the storage of the `fit_` block through a union; here they are the `_Overlay` attributes
-    attached below (`PATH_FIELDS`), so `_fields_`, the size and every offset stay what they were."""
+    attached below (`PATH_FIELDS`), so `_fields_`, the size and every offset stay what they were.  The `mom_` fields
+    (HCG_EXPLAIN_MOMENTS, `MOMENT_FIELDS`) are the union's third block, attached the same way."""
     _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
                 ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
                 ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
@@ -151,9 +153,16 @@ PATH_FIELDS = (("path_alpha", P), ("path_weight", P), ("path_node_attr", P), ("p
                ("path_class_index", I32))
 
 
-def _attach_path_fields():
+# hcg_explain_args' HCG_EXPLAIN_MOMENTS members (the union's third block), in the header's order from the same offset; the
+# header's two-element arrays are one attribute per element here (`mom_values0`, `mom_values1`, ...)
+MOMENT_FIELDS = tuple((f"{name}{s}", ctype) for name, ctype in (("mom_values", P), ("mom_mean", P), ("mom_m2", P), ("mom_std", P),
+                                                                 ("mom_len", I64)) for s in (0, 1)) + \
+    (("mom_total", I32), ("mom_first", I32), ("mom_count", I32), ("mom_reserved", I32))
+
+
+def _attach_union_fields(fields):
     off = ExplainArgs.fit_edge_logit.offset
-    for name, ctype in PATH_FIELDS:
+    for name, ctype in fields:
         align = ctypes.alignment(ctype)
         off = (off + align - 1) // align * align
         setattr(ExplainArgs, name, _Overlay(ctype, off))
@@ -161,7 +170,8 @@ def _attach_path_fields():
     assert off <= ctypes.sizeof(ExplainArgs)
 
 
-_attach_path_fields()
+_attach_union_fields(PATH_FIELDS)
+_attach_union_fields(MOMENT_FIELDS)
 
 
 class CollateSlot(ctypes.Structure):

@@ -1,4 +1,6 @@
-"""Gradient attributions for a batch of graphs: integrated gradients, input x gradient, saliency.
+"""Gradient attributions for a batch of graphs: integrated gradients, input x gradient, saliency -- of one model
+(`IntegratedGradients`) or of an ensemble of models in one launch with the mean and the standard deviation over the models
+(`EnsembleAttribution`).
 
 The reference's explain stage reaches Captum through `torch_geometric.explain.Explainer(CaptumExplainer(name), ...,
 node_mask_type='attributes', edge_mask_type='object')` (scripts_experiments/explain_gnn.py); `ShapleySampling` serves the
@@ -12,17 +14,19 @@ artefact of the reference pins these values: parity is against an fp64 restateme
 from __future__ import annotations
 
 import ctypes
-from typing import NamedTuple, Optional
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _frozen, _lib
+from .ensemble import stack_weights, weight_names
 from .explain import ExplainStep
 from .shapley import CUS, LAUNCH_SECONDS
 
 METHODS = ("gausslegendre", "riemann_middle", "gradient")
 ENDPOINT_METHODS = ("riemann_left", "riemann_right", "riemann_trapezoid")
+LAUNCH_BUDGET_BYTES = 1 << 30      # workspace + per-model attribution arrays of one `EnsembleAttribution` launch (default chunking)
 STEP_SECONDS = 400e-6              # one forward + backward of a workgroup at the shape limits: an estimate (default_steps_per_launch)
 
 
@@ -291,3 +295,211 @@ def convergence_delta(batch, result, class_index: int) -> torch.Tensor:
     total.index_add_(0, owner_e, edge_attr.double())
     return total - (out_full.double()[:, class_index] - out_base.double()[:, class_index])
 
+
+
+class EnsembleAttributionResult(NamedTuple):
+    node_mean: torch.Tensor             # [N, F]  mean over the models of their node attributions
+    node_std: torch.Tensor              # [N, F]  population standard deviation over the models
+    edge_mean: torch.Tensor             # [E], the batch's edge order
+    edge_std: torch.Tensor              # [E]
+    out_full: torch.Tensor              # [M, B, C] every model's output at masks of 1
+    out_base: torch.Tensor              # [M, B, C] at masks of 0
+    node_attr: Optional[torch.Tensor]   # [M, N, F] the per-model attributions; None unless asked for
+    edge_attr: Optional[torch.Tensor]   # [M, E]
+
+
+class EnsembleAttribution:
+    """Integrated gradients of M frozen models of one architecture for a whole batch of graphs: every (graph, model) pair is
+    one workgroup of ONE launch, and the mean and the standard deviation over the models are taken on the device.
+
+        ea = EnsembleAttribution(models, n_steps=50, method="gausslegendre", saliency=False)
+        r = ea(batch, class_index=0, per_model=False, models_per_launch=None, steps_per_launch=None)
+        # EnsembleAttributionResult(node_mean [N, F], node_std [N, F], edge_mean [E], edge_std [E],
+        #                           out_full [M, B, C], out_base [M, B, C], node_attr [M, N, F] | None, edge_attr [M, E] | None)
+        ea.refresh(); ea.reason(batch); ea.last_path
+
+    `models` are checked and snapshotted as `EnsemblePredict` does it: the same (node features, embedding_dim, classes,
+    conv layers, readout layers) for every model (`ValueError` otherwise), weights stacked once into contiguous [M, ...]
+    buffers; later changes of a model do not show until `refresh()` re-stacks them in place.  Methods, step-count rules
+    and `saliency` are `IntegratedGradients`': `node_attr[m]` / `edge_attr[m]` / `out_full[m]` / `out_base[m]` are bit for bit
+    what `IntegratedGradients(models[m], ...)(batch)` returns, whatever the other models are.
+
+    Integrated gradients are linear in the model output, so `node_mean` / `edge_mean` ARE the integrated gradients of the
+    ensemble's mean prediction (`EnsemblePredict.mean`); `node_std` / `edge_std` (population form, ddof = 0, as
+    `EnsemblePredict.std`) say where the models disagree.  With `saliency=True` the per-model values are absolute values
+    and the mean is THEIR mean -- not the saliency of the mean output, which is `abs(node_mean)` of `method="gradient"`.
+    The moments are Welford's recurrence in float32 over the models in ascending order (csrc/explain.hip k_model_moments):
+    an entry that is 0 in every model (an `x` entry equal to 0, an explicit (i, i) edge) has mean and std exactly 0, and a
+    one-model ensemble has the model's attributions as mean and std exactly 0.
+
+    The models run in chunks of `models_per_launch` (None: `default_models_per_launch`), inside a chunk the steps in chunks
+    of `steps_per_launch` (None: `IntegratedGradients.default_steps_per_launch` with graphs x models of the chunk as the
+    workgroup count); one moments launch follows each chunk of models.  Every returned value is bitwise independent of
+    both splits, of the run and of the rest of the batch.  With `per_model=False` only one chunk's [models_per_launch, ...]
+    attribution arrays exist (at 90 models x 535 graphs the full arrays are about 0.4 GB).  Buffers grow to the largest
+    call and are reused (a warm call allocates nothing); the returned tensors are views of them, overwritten by the next
+    call.  No parameter's `.grad` is touched and no mask stays on a model.
+
+    When `reason(batch)` is not None (shape outside the kernel, `embedding_dim != 64`, CPU tensors, `use_fused` off on any
+    model) the same call runs `IntegratedGradients(model_k).loop` per model -- on the models' CURRENT weights -- and takes
+    the moments with torch ops (`mean(0)`, `std(0, unbiased=False)`); `last_path` says which one ran ("fused" / "loop")."""
+
+    def __init__(self, models: Sequence[torch.nn.Module], n_steps: int = 50, method: str = "gausslegendre", saliency: bool = False):
+        self.models: List[torch.nn.Module] = list(models)
+        if not self.models:
+            raise ValueError("EnsembleAttribution needs at least one model")
+        for k, m in enumerate(self.models):
+            if any(not hasattr(m, a) for a in _frozen.MODEL_ATTRS):
+                raise ValueError(f"model {k} is not a hcatgnet_amd GCN model")
+        sig = [_frozen.model_shape(m) for m in self.models]
+        for k, s in enumerate(sig):
+            if s != sig[0]:
+                raise ValueError(f"model {k} has (features, embedding_dim, classes, conv layers, readout layers) = {s}, "
+                                 f"model 0 has {sig[0]}")
+        self.F, self.D, self.C, self.n_conv, self.R = sig[0]
+        # (method, step count and saliency: `IntegratedGradients`' own checks; these are also the loop path's workers)
+        self._singles = [IntegratedGradients(m, n_steps, method, saliency) for m in self.models]
+        self.n_steps, self.method, self.saliency = self._singles[0].n_steps, method, bool(saliency)
+        self.stacked = stack_weights([m.state_dict() for m in self.models])
+        self.last_path: Optional[str] = None
+        self.last_class_index: Optional[int] = None
+        self._bufs = {}
+        self._points = {}
+        self._args = _lib.ExplainArgs()
+        self._mom = _lib.ExplainArgs()
+
+    @property
+    def n_models(self) -> int:
+        return len(self.models)
+
+    def refresh(self):
+        """Re-stack the models' current weights into the same buffers (in place: pointers stay valid)."""
+        with torch.no_grad():
+            for k, m in enumerate(self.models):
+                for name, t in m.state_dict().items():
+                    if name in self.stacked:
+                        self.stacked[name][k].copy_(t.detach())
+        return self
+
+    # ------------------------------------------------------------------ support check (host only, no sync)
+    def _shape_args(self, a, batch) -> Optional[str]:
+        """None when the kernel takes these models and `batch`; `a` then holds the shapes and the ONE-model workspace bytes"""
+        if not all(bool(getattr(m, "use_fused", True)) for m in self.models):
+            return "fused kernels disabled on a model"
+        if batch is not None:
+            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, self.F, "models")
+            if why is not None:
+                return why
+        return _frozen.query(a, _lib.HCG_EXPLAIN_INTEGRATED, (self.F, self.D, self.C, self.n_conv, self.R), batch, edge_mask=None,
+                             node_mask=None, target=None, dout=None, dx=None, n_models=1)
+
+    def reason(self, batch=None) -> Optional[str]:
+        """None when these models (and `batch`) take the one-launch kernel, else why not.  Host metadata only."""
+        return self._shape_args(_lib.ExplainArgs(), batch)
+
+    @staticmethod
+    def default_models_per_launch(n_models: int, workspace_bytes: int, entries: int, budget: int = LAUNCH_BUDGET_BYTES) -> int:
+        """Models of one launch: all of them, unless their workspace slices (`workspace_bytes` each, the library's
+        one-model figure) plus their attribution rows (`entries` = N F + E float32 each) exceed `budget` bytes
+        (`LAUNCH_BUDGET_BYTES`); then as many as fit, at least 1."""
+        per = int(workspace_bytes) + 4 * int(entries)
+        return max(1, min(int(n_models), int(budget) // max(per, 1)))
+
+    # ------------------------------------------------------------------ buffers
+    def _buffer(self, name: str, numel: int, dev, dtype=torch.float32):
+        """A flat buffer of at least `numel` elements, grown to the largest request and kept"""
+        t = self._bufs.get(name)
+        if t is None or t.numel() < numel or t.device != dev:
+            t = torch.zeros(max(numel, 1), dtype=dtype, device=dev)
+            self._bufs[name] = t
+        return t
+
+    def _quadrature(self, n: int, dev):
+        key = (n, str(dev))
+        if key not in self._points:
+            alpha, weight = quadrature(self.method, n)
+            self._points[key] = (alpha.to(dev), weight.to(dev))
+        return self._points[key]
+
+    # ------------------------------------------------------------------ the call
+    def __call__(self, batch, class_index: int = 0, per_model: bool = False, models_per_launch: Optional[int] = None,
+                 steps_per_launch: Optional[int] = None, n_steps: Optional[int] = None) -> EnsembleAttributionResult:
+        one = self._singles[0]
+        n = one._steps(n_steps)
+        cls = one._class(class_index)
+        for name, v in (("models_per_launch", models_per_launch), ("steps_per_launch", steps_per_launch)):
+            if v is not None and int(v) < 1:
+                raise ValueError(f"{name} must be at least 1; got {v}")
+        a = self._args
+        why = self._shape_args(a, batch)
+        if why is not None:
+            return self.loop(batch, cls, per_model, n)
+        x = _frozen.batch_x(batch)
+        dev = x.device
+        M = len(self.models)
+        N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
+        ws_one = int(a.workspace_bytes_needed)
+        S = self.stacked
+        _frozen.check_weights(S.values(), dev, "EnsembleAttribution: the stacked weights must be on the batch's device "
+                              "(construct the ensemble from models on that device)")
+        Ml = self.default_models_per_launch(M, ws_one, N * F + E) if models_per_launch is None else min(int(models_per_launch), M)
+        alpha, weight = self._quadrature(n, dev)
+        plan = self.models[0]._plan_for(batch, x, batch.edge_index, batch.batch, None)
+        rows = M if per_model else Ml
+        node = self._buffer("node", rows * N * F, dev)
+        edge = self._buffer("edge", rows * E, dev)
+        full, base = self._buffer("full", M * B * C, dev), self._buffer("base", M * B * C, dev)
+        ws = self._buffer("ws", Ml * ws_one, dev, torch.uint8)
+        mom = {k: self._buffer(k, N * F if k.startswith("node") else E, dev)
+               for k in ("node_mean", "node_m2", "node_std", "edge_mean", "edge_m2", "edge_std")}
+        p = _lib.ptr
+        a.flags = 0
+        _frozen.fill_graph(a, x, plan)
+        a.out = None
+        a.workspace, a.workspace_bytes = p(ws), ws.numel()
+        a.slope = _frozen.SLOPE
+        a.path_alpha, a.path_weight = p(alpha), p(weight)
+        a.path_steps, a.path_class_index = n, cls
+        q = self._mom
+        q.mode, q.flags = _lib.HCG_EXPLAIN_MOMENTS, 0
+        q.mom_mean0, q.mom_m20, q.mom_std0, q.mom_len0 = p(mom["node_mean"]), p(mom["node_m2"]), p(mom["node_std"]), N * F
+        q.mom_mean1, q.mom_m21, q.mom_std1, q.mom_len1 = p(mom["edge_mean"]), p(mom["edge_m2"]), p(mom["edge_std"]), E
+        q.mom_total = M
+        names = weight_names(self.n_conv, self.R)
+        lib, stream = _lib.load(), _lib.stream_ptr()
+        for m0 in range(0, M, Ml):
+            count = min(Ml, M - m0)
+            row0 = m0 if per_model else 0               # (per_model=False: every chunk reuses the one chunk's rows)
+            # pointers already offset to the chunk's first model: the library has no "first model" field
+            for slots, group in zip((a.conv_W, a.conv_b, a.head_W, a.head_b), names):
+                for i in range(len(slots)):
+                    slots[i] = S[group[i]].data_ptr() + 4 * m0 * S[group[i]].stride(0) if i < len(group) else None
+            a.n_models = count
+            a.path_node_attr = node.data_ptr() + 4 * row0 * N * F
+            a.path_edge_attr = edge.data_ptr() + 4 * row0 * E
+            a.path_out_full, a.path_out_base = full.data_ptr() + 4 * m0 * B * C, base.data_ptr() + 4 * m0 * B * C
+            per = one.default_steps_per_launch(n, B * count) if steps_per_launch is None else min(int(steps_per_launch), n)
+            for first in range(0, n, per):
+                a.path_step_first, a.path_step_count = first, min(per, n - first)
+                _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (integrated, ensemble)")
+            if self.saliency:
+                node[row0 * N * F:(row0 + count) * N * F].abs_()
+                edge[row0 * E:(row0 + count) * E].abs_()
+            q.mom_values0, q.mom_values1 = a.path_node_attr, a.path_edge_attr
+            q.mom_first, q.mom_count = m0, count
+            _lib.check(lib.hcg_explain(ctypes.addressof(q), stream), "hcg_explain (moments)")
+        self.last_path, self.last_class_index = "fused", cls
+        return EnsembleAttributionResult(
+            mom["node_mean"][:N * F].view(N, F), mom["node_std"][:N * F].view(N, F), mom["edge_mean"][:E], mom["edge_std"][:E],
+            full[:M * B * C].view(M, B, C), base[:M * B * C].view(M, B, C),
+            node[:M * N * F].view(M, N, F) if per_model else None, edge[:M * E].view(M, E) if per_model else None)
+
+    # ------------------------------------------------------------------ the loop path (any shape, CPU tensors)
+    def loop(self, batch, class_index: int = 0, per_model: bool = False, n_steps: Optional[int] = None) -> EnsembleAttributionResult:
+        """`IntegratedGradients(model_k).loop` per model on the models' current weights, the moments with torch ops."""
+        rs = [ig.loop(batch, class_index, n_steps) for ig in self._singles]
+        node, edge = torch.stack([r.node_attr for r in rs]), torch.stack([r.edge_attr for r in rs])
+        self.last_path, self.last_class_index = "loop", int(class_index)
+        return EnsembleAttributionResult(node.mean(0), node.std(0, unbiased=False), edge.mean(0), edge.std(0, unbiased=False),
+                                         torch.stack([r.out_full for r in rs]), torch.stack([r.out_base for r in rs]),
+                                         node if per_model else None, edge if per_model else None)

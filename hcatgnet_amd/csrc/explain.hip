@@ -44,6 +44,11 @@
 // outputs below), the same in every step, and step 0 starts from 0 whatever the arrays hold: a path split into several
 // launches repeats the single launch bit for bit.  The launch that holds step 0 first runs two forward-only passes (t = -2:
 // masks of 1, t = -1: masks of 0) for out_full / out_base.  The other two instantiations compile to what they were.
+// With n_models = M the launch is dim3(B, M): workgroup (g, m) runs graph g's path with model m of weights stacked along a
+// leading model axis (ensemble.hip's layout) into slice m of the workspace, of the accumulators ([M][N][F], [M][E]) and of
+// out_full / out_base ([M][B][C]).  The model index is uniform: scalar offsets only, 148 VGPRs with and without it.
+//
+// HCG_EXPLAIN_MOMENTS (k_model_moments, at the end of this file): mean and standard deviation over that model axis.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -86,6 +91,8 @@ struct XPath {     // what HCG_EXPLAIN_INTEGRATED adds (PATH = true only); a.out
   float* edge_attr;                                                  // [E]
   float* out_base;                                                   // [B][C]
   int step_first, steps, cls;
+  int B;                                                             // graphs: the model stride of out_full / out_base is B C
+  unsigned long long ws_model;                                       // floats of one model's workspace slice
 };
 
 struct XPathArgs { XArgs a; XPath f; };
@@ -159,6 +166,9 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   const int g = blockIdx.x;
   const int F = cm.F, C = cm.C, n_conv = cm.n_conv;
   const float slope = cm.slope;
+  // PATH: the model of this workgroup (grid y) of weights stacked [M][...]; uniform, so every offset below is scalar.  The
+  // other instantiations have one model: mdl is the constant 0 and every product with it folds away.
+  const unsigned mdl = PATH ? blockIdx.y : 0u;
   const bool bwd = FIT || PATH || a.target != nullptr || a.dout != nullptr || a.target_class != nullptr;
   const bool need_dx = FIT || PATH || a.d_node_mask != nullptr || a.dx != nullptr;
   const bool sig = !PATH && (FIT || a.sigmoid);
@@ -167,8 +177,10 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   if (x_refused(sp, cm, g, tid)) {
     // the graph's outputs are zero -- over whatever part of its ranges lies inside the arrays
     const int nbase = sp.nbase, ebase = sp.ebase, n_raw = sp.n_raw, ne_raw = sp.ne_raw;
-    for (int k = tid; k < C; k += XT) a.out[(size_t)g * C + k] = 0.f;
-    // (FIT: the masks and the loss history; the graph's state is left as it came)
+    float* out0 = a.out;
+    if constexpr (PATH) out0 += (size_t)mdl * args.f.B * C;
+    for (int k = tid; k < C; k += XT) out0[(size_t)g * C + k] = 0.f;
+    // (FIT: the masks and the loss history; the graph's state is left as it came.  PATH: model mdl's slices)
     float* d_e = a.d_edge_mask;
     float* d_n = a.d_node_mask;
     if constexpr (FIT) {
@@ -176,9 +188,9 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
       d_n = args.f.node_out;
       for (int t = tid; t < args.f.epochs; t += XT) args.f.loss_hist[(size_t)t * args.f.B + g] = 0.f;
     } else if constexpr (PATH) {
-      d_e = args.f.edge_attr;
-      d_n = args.f.node_attr;
-      for (int k = tid; k < C; k += XT) args.f.out_base[(size_t)g * C + k] = 0.f;
+      d_e = args.f.edge_attr + (size_t)mdl * (size_t)cm.E;
+      d_n = args.f.node_attr + (size_t)mdl * (size_t)a.N * F;
+      for (int k = tid; k < C; k += XT) args.f.out_base[((size_t)mdl * args.f.B + g) * C + k] = 0.f;
     } else {
       if (a.loss && tid == 0) a.loss[g] = 0.f;
     }
@@ -232,7 +244,19 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   __syncthreads();
 
   const size_t plane = (size_t)a.N * XD;                  // one [N][64] tensor of the workspace
-  float* const wsg = a.ws + (size_t)nbase * XD;           // this graph's rows of plane 0
+  float* wsg = a.ws + (size_t)nbase * XD;                 // this graph's rows of plane 0
+  // PATH: model mdl's slices of the workspace, the accumulators and the two output arrays
+  [[maybe_unused]] float* p_node = nullptr;
+  [[maybe_unused]] float* p_edge = nullptr;
+  [[maybe_unused]] float* p_full = nullptr;
+  [[maybe_unused]] float* p_base = nullptr;
+  if constexpr (PATH) {
+    wsg += (size_t)mdl * args.f.ws_model;
+    p_node = args.f.node_attr + (size_t)mdl * (size_t)a.N * F;
+    p_edge = args.f.edge_attr + (size_t)mdl * (size_t)cm.E;           // (E = 0: nothing is addressed)
+    p_full = a.out + (size_t)mdl * args.f.B * C;
+    p_base = args.f.out_base + (size_t)mdl * args.f.B * C;
+  }
 
   // FIT: the hard counts (behind the tiles and lists in LDS), from the state unless this launch holds the step-0 epoch
   [[maybe_unused]] int* const hc = reinterpret_cast<int*>(smem + x_lds_bytes(cm.npad, cm.emax));
@@ -275,7 +299,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
     const int K = __builtin_amdgcn_readfirstlane(l == 0 ? F : XD);   // (uniform: keeps the weight addressing scalar)
     {
       float w[XD];
-      x_weight_row(w, reinterpret_cast<const char*>(x_pick(cm.cW, l)), lane, K);
+      x_weight_row(w, reinterpret_cast<const char*>(x_pick(cm.cW, l) + (size_t)mdl * XD * K), lane, K);
       float* hws = wsg + (size_t)(2 * l) * plane;
       x_gemm(L.t0, w, n, wave, [&](int r, float v) {
         L.t1[r * XS + lane] = v;
@@ -284,7 +308,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
     }
     __syncthreads();
     float* aws = wsg + (size_t)(2 * l + 1) * plane;
-    x_conv_out(L.t1, L.t0, L.ent_d, L.rowptr_d, fmt, L.dinv, x_pick(cm.cb, l), n, tid, slope, [&](int row, int c4, float4 y) {
+    x_conv_out(L.t1, L.t0, L.ent_d, L.rowptr_d, fmt, L.dinv, x_pick(cm.cb, l) + (size_t)mdl * XD, n, tid, slope, [&](int row, int c4, float4 y) {
       if (bwd && l + 1 < n_conv) *reinterpret_cast<float4*>(aws + (size_t)row * XD + 4 * c4) = y;
     });
     __syncthreads();
@@ -292,14 +316,14 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
 
   // ---------------------------------------------------------------------------------------------- pooling (t0 = A of the last layer), readout
   x_pool(L.t0, L.red, L.hv, n, tid);
-  int off = x_readout(L.hv, cm, 0, tid);
+  int off = x_readout(L.hv, cm, (int)mdl, tid);
   // off = position of the output row in hv / hg
   if (tid < C) {
     const float o = L.hv[off + tid];
     if constexpr (PATH) {
       // out_full / out_base from the forward-only passes; upstream: 1 at the column (compared, never an address)
-      if (t == -2) a.out[(size_t)g * C + tid] = o;
-      if (t == -1) args.f.out_base[(size_t)g * C + tid] = o;
+      if (t == -2) p_full[(size_t)g * C + tid] = o;
+      if (t == -1) p_base[(size_t)g * C + tid] = o;
       L.hg[off + tid] = tid == args.f.cls ? 1.f : 0.f;
     } else {
     a.out[(size_t)g * C + tid] = o;
@@ -349,7 +373,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
     const int in_i = (2 * XD) >> i, out_i = i == cm.R - 1 ? C : in_i / 2;
     off -= in_i;                                        // layer i's input vector; its output sits at off + in_i
     if (tid < in_i) {
-      const float* W = x_pick(cm.hW, i) + tid;
+      const float* W = x_pick(cm.hW, i) + (size_t)mdl * out_i * in_i + tid;
       float s = 0.f;
       for (int o = 0; o < out_i; ++o) s = fmaf(W[(size_t)o * in_i], L.hg[off + in_i + o], s);
       if (i > 0) s *= hcg_leaky_grad(L.hv[off + tid], slope);
@@ -425,7 +449,7 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
     // dA_prev = dH W (lane = input column k), times leaky'(A_prev) for a hidden layer
     {
       float w[XD];
-      const char* Wb = reinterpret_cast<const char*>(x_pick(cm.cW, l));
+      const char* Wb = reinterpret_cast<const char*>(x_pick(cm.cW, l) + (size_t)mdl * XD * K);
       const unsigned col = (unsigned)(lane < K ? lane : K - 1);
       unsigned Kv = (unsigned)K;
       asm volatile("" : "+v"(Kv));          // (opaque: the row offsets stay 32-bit vector offsets on the one uniform base)
@@ -454,13 +478,13 @@ __global__ __launch_bounds__(XT) void k_explain_graphs(const typename XKernelArg
   const bool fresh = step == 0;                           // the path starts from 0 whatever the arrays hold
   for (int e = tid; e < ne; e += XT) {
     const size_t p = (size_t)ebase + e;
-    f.edge_attr[p] = fmaf(wk, L.eg[e], fresh ? 0.f : f.edge_attr[p]);
+    p_edge[p] = fmaf(wk, L.eg[e], fresh ? 0.f : p_edge[p]);
   }
   for (int idx = tid; idx < n * XD; idx += XT) {
     const int r = idx >> 6, k = idx & 63;
     if (k < F) {
       const size_t p = (size_t)(nbase + r) * F + k;
-      f.node_attr[p] = fmaf(wk, L.t0[r * XS + k] * cm.x[p], fresh ? 0.f : f.node_attr[p]);
+      p_node[p] = fmaf(wk, L.t0[r * XS + k] * cm.x[p], fresh ? 0.f : p_node[p]);
     }
   }
   __syncthreads();                                        // (the next step stages over t0 and eg)
@@ -597,7 +621,10 @@ int x_fit_launch(hcg_explain_args* p, hipStream_t stream) {
   return x_launch<k_explain_graphs<true>>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax) + X_FIT_LDS_EXTRA, stream, k);
 }
 
-// hcg_explain, mode HCG_EXPLAIN_INTEGRATED, behind the shape check, the flag / NULL checks and the query
+// the model axis of HCG_EXPLAIN_INTEGRATED: n_models, 0 (what a caller of the one-model form leaves there) meaning 1
+inline int x_path_models(const hcg_explain_args* p) { return p->n_models == 0 ? 1 : p->n_models; }
+
+// hcg_explain, mode HCG_EXPLAIN_INTEGRATED, behind the shape check, the flag / NULL checks, the model count and the query
 int x_path_launch(hcg_explain_args* p, hipStream_t stream) {
   if (p->path_steps < 1 || p->path_step_first < 0 || p->path_step_count < 0 ||
       (long long)p->path_step_first + p->path_step_count > p->path_steps)
@@ -632,7 +659,76 @@ int x_path_launch(hcg_explain_args* p, hipStream_t stream) {
   f.step_first = p->path_step_first;
   f.steps = p->path_step_count;
   f.cls = p->path_class_index;
-  return x_launch<k_explain_graphs<false, true>>(dim3((unsigned)p->B), x_lds_bytes(a.c.npad, a.c.emax), stream, k);
+  f.B = (int)p->B;
+  const int M = x_path_models(p);                         // (checked by the caller: 1 .. 65535)
+  f.ws_model = p->workspace_bytes_needed / (size_t)M / sizeof(float);
+  return x_launch<k_explain_graphs<false, true>>(dim3((unsigned)p->B, (unsigned)M), x_lds_bytes(a.c.npad, a.c.emax), stream, k);
+}
+
+// ---- HCG_EXPLAIN_MOMENTS: running mean / sum of squared deviations over a model axis ---------------------------------------
+// One thread per entry of the (up to two) [count][len] arrays of a call walks the models in ascending order: Welford's
+// recurrence in float32, never contracted, k = the 1-based count over the WHOLE ensemble.  The state lives in the caller's
+// arrays and each entry has one owner, so the moments are bitwise independent of how the models are split into calls.
+// Consecutive threads read consecutive floats of a model's row.
+constexpr int XM_T = 256;
+
+struct XMom {
+  const float* v0; const float* v1;     // [count][len0], [count][len1]
+  float* mean0; float* mean1;
+  float* m20; float* m21;
+  float* sd0; float* sd1;
+  long long len0, len1;
+  int total, first, count;
+};
+
+__global__ __launch_bounds__(XM_T) void k_model_moments(const XMom a) {
+#pragma clang fp contract(off)
+  long long i = (long long)blockIdx.x * XM_T + threadIdx.x;
+  const bool second = i >= a.len0;
+  if (second) i -= a.len0;
+  const long long len = second ? a.len1 : a.len0;
+  if (i >= len) return;
+  const float* v = (second ? a.v1 : a.v0) + i;
+  float* const mean_p = (second ? a.mean1 : a.mean0) + i;
+  float* const m2_p = (second ? a.m21 : a.m20) + i;
+  float mean = 0.f, m2 = 0.f;                             // the call that starts at model 0 starts from 0
+  if (a.first > 0) { mean = *mean_p; m2 = *m2_p; }
+  for (int j = 0; j < a.count; ++j) {
+    const float x = v[(size_t)j * (size_t)len];
+    const float k = (float)(a.first + j + 1);
+    const float d = x - mean;
+    mean += d / k;
+    m2 += d * (x - mean);
+  }
+  *mean_p = mean;
+  *m2_p = m2;
+  if (a.first + a.count == a.total) (second ? a.sd1 : a.sd0)[i] = sqrtf(m2 / (float)a.total);
+}
+
+int x_moments_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->mom_total < 1 || p->mom_first < 0 || p->mom_count < 0 || (long long)p->mom_first + p->mom_count > p->mom_total)
+    return HCG_ERR_INVALID_ARG;
+  long long blocks = 0;
+  for (int s = 0; s < 2; ++s) {
+    if (p->mom_len[s] < 0 || p->mom_len[s] >= (1ll << 31)) return HCG_ERR_INVALID_ARG;
+    blocks += p->mom_len[s];
+  }
+  blocks = hcg_cdiv(blocks, (long long)XM_T);
+  p->workspace_bytes_needed = 0;
+  if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
+  if (p->mom_count == 0 || blocks == 0) return HCG_OK;
+  for (int s = 0; s < 2; ++s)
+    if (p->mom_len[s] > 0 && (!p->mom_values[s] || !p->mom_mean[s] || !p->mom_m2[s] || !p->mom_std[s])) return HCG_ERR_INVALID_ARG;
+  XMom a;
+  a.v0 = p->mom_values[0]; a.v1 = p->mom_values[1];
+  a.mean0 = p->mom_mean[0]; a.mean1 = p->mom_mean[1];
+  a.m20 = p->mom_m2[0]; a.m21 = p->mom_m2[1];
+  a.sd0 = p->mom_std[0]; a.sd1 = p->mom_std[1];
+  a.len0 = p->mom_len[0]; a.len1 = p->mom_len[1];
+  a.total = p->mom_total; a.first = p->mom_first; a.count = p->mom_count;
+  hipLaunchKernelGGL(k_model_moments, dim3((unsigned)blocks), dim3(XM_T), 0, stream, a);
+  HCG_CHECK_LAUNCH();
+  return HCG_OK;
 }
 
 }  // namespace
@@ -642,7 +738,8 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   // the class-index form of the upstream gradient belongs to HCG_EXPLAIN_GRAPHS and HCG_EXPLAIN_FIT alone
   if ((p->flags & HCG_EXPLAIN_TARGET_CLASS) && (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD || p->mode == HCG_EXPLAIN_ENSEMBLE ||
-                                                p->mode == HCG_EXPLAIN_SHAPLEY || p->mode == HCG_EXPLAIN_INTEGRATED))
+                                                p->mode == HCG_EXPLAIN_SHAPLEY || p->mode == HCG_EXPLAIN_INTEGRATED ||
+                                                p->mode == HCG_EXPLAIN_MOMENTS))
     return HCG_ERR_INVALID_ARG;
   if (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD) {
     if (p->flags & HCG_EXPLAIN_QUERY) { p->workspace_bytes_needed = 0; return HCG_OK; }
@@ -651,6 +748,7 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   }
   if (p->mode == HCG_EXPLAIN_ENSEMBLE) return hcg_ensemble_launch(p, stream);
   if (p->mode == HCG_EXPLAIN_SHAPLEY) return hcg_shapley_launch(p, stream);
+  if (p->mode == HCG_EXPLAIN_MOMENTS) return x_moments_launch(p, stream);
   const bool fit = p->mode == HCG_EXPLAIN_FIT;
   const bool path = p->mode == HCG_EXPLAIN_INTEGRATED;
   if (p->mode != HCG_EXPLAIN_GRAPHS && !fit && !path) return HCG_ERR_INVALID_ARG;
@@ -664,6 +762,12 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (path) p->lds_bytes = (int32_t)x_lds_bytes(x_round4(p->max_nodes, 4), x_round4(p->max_edges, 4));
   // H_l and A_l of every layer, [N][64] f32 each: the backward reads them again
   p->workspace_bytes_needed = hcg_align_up((size_t)2 * p->n_conv * (size_t)(p->N > 0 ? p->N : 1) * XD * sizeof(float), 256);
+  if (path) {
+    // one workspace slice per model of the launch (grid y)
+    const int M = x_path_models(p);
+    if (M < 1 || M > 65535) return HCG_ERR_INVALID_ARG;
+    p->workspace_bytes_needed *= (size_t)M;
+  }
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (fit) return x_fit_launch(p, stream);
   if (path) return x_path_launch(p, stream);

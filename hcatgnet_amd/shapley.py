@@ -85,7 +85,9 @@ def _torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):
     for c in convs:
         t = Fn.linear(h, c.lin.weight)
         y = (dinv * dinv).unsqueeze(1) * t
-        y = y.index_add(0, d, coef * t[s])
+        # (index_select, not t[s]: the same values forward; its backward adds the rows serially in index order, where
+        # the backward of t[s] adds them with atomics from several threads -- a gradient that differs in its last bits run to run)
+        y = y.index_add(0, d, coef * t.index_select(0, s))
         h = Fn.leaky_relu(y + c.bias, SLOPE)
     idx = batch_vec.unsqueeze(1).expand_as(h)
     mx = h.new_zeros(B, h.shape[1]).scatter_reduce(0, idx, h, reduce="amax", include_self=False)

@@ -232,19 +232,40 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   used.  The path_ fields share the storage of the fit_ fields (a union: the two modes never meet in one call), so the
  *   struct's size and every earlier offset are what they were.  Shapes, workspace, LDS and refusals as HCG_EXPLAIN_GRAPHS
  *   (a refused graph: its rows of path_out_full / path_out_base and its entries of both attribution arrays zero, the other
- *   graphs untouched).  HCG_EXPLAIN_QUERY as above (checks the flags and the NULL pointers too); also writes lds_bytes. */
+ *   graphs untouched).  HCG_EXPLAIN_QUERY as above (checks the flags and the NULL pointers too); also writes lds_bytes.
+ *   A model axis: `n_models` = M frozen models of one architecture (0, what a caller of the one-model form leaves there,
+ *   means 1; 1 .. 65535, otherwise HCG_ERR_INVALID_ARG) run the same path in ONE launch, one workgroup per (graph, model).
+ *   conv_W[l] / conv_b[l] / head_W[i] / head_b[i] then point at tensors stacked along a leading model axis, the layout of
+ *   HCG_EXPLAIN_ENSEMBLE; path_node_attr is [M, N, F], path_edge_attr [M, E], path_out_full / path_out_base [M, B, C], and
+ *   the workspace M times the one-model workspace (workspace_bytes_needed, the query too, accounts for M; model m uses
+ *   slice m).  Entry [m] of every output is bitwise what the one-model call with model m's weights writes, whatever M and
+ *   the other models are; a refused graph's rows are zero in every model's outputs.  To run a sub-range of an ensemble the
+ *   caller passes pointers already offset to its first model.  `models_per_group` is not read.
+ * HCG_EXPLAIN_MOMENTS: mean and standard deviation over a model axis, for the outputs of HCG_EXPLAIN_INTEGRATED with
+ *   n_models > 1.  Up to two arrays per call (s = 0, 1; mom_len[s] = 0 leaves one out): mom_values[s] is [mom_count, mom_len[s]]
+ *   float32, row j = model mom_first + j of an ensemble of mom_total models.  One thread per entry walks the rows in
+ *   ascending order with Welford's recurrence in float32, no operation contracted:  d = v - mean;  mean += d / k;
+ *   m2 += d * (v - mean),  k = the 1-based count over the WHOLE ensemble (mom_first + j + 1).  The state is the caller's
+ *   mom_mean[s] / mom_m2[s] [mom_len[s]]: the call with mom_first = 0 starts from 0 whatever they hold, a later call
+ *   continues from them, and the call with mom_first + mom_count = mom_total also writes mom_std[s] = sqrtf(m2 / mom_total)
+ *   (the population form).  Every entry has one owner and a fixed order: the moments are bitwise independent of how the
+ *   models are split into calls; an entry that is 0 in every model has mean and std exactly 0.  No atomics; consecutive
+ *   threads read consecutive floats.  mom_total >= 1, 0 <= mom_first, mom_first + mom_count <= mom_total, 0 <= mom_len[s] <
+ *   2^31 (each: HCG_ERR_INVALID_ARG); HCG_EXPLAIN_TARGET_CLASS must be clear.  No other field is read; no workspace
+ *   (workspace_bytes_needed = 0).  The mom_ fields are a third member of the union of the fit_ and path_ fields. */
 #define HCG_EXPLAIN_GRAPHS 0
 #define HCG_EXPLAIN_LAYER_EDGE_GRAD 1
 #define HCG_EXPLAIN_ENSEMBLE 2
 #define HCG_EXPLAIN_SHAPLEY 3
 #define HCG_EXPLAIN_FIT 4
 #define HCG_EXPLAIN_INTEGRATED 5
+#define HCG_EXPLAIN_MOMENTS 6
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -283,7 +304,7 @@ typedef struct hcg_explain_args {
   const float* dinv;
   float* dew_csr;
   float* emb;                            /* HCG_EXPLAIN_ENSEMBLE from here on: [M, B, 2D], nullable */
-  int32_t n_models;                      /* M */
+  int32_t n_models;                      /* M (also read by HCG_EXPLAIN_INTEGRATED: 0 means 1) */
   int32_t models_per_group;              /* models one workgroup runs on its graph, 1 .. M */
   const int32_t* perm;                   /* HCG_EXPLAIN_SHAPLEY from here on: [n_perm][N F + E] */
   float* out_base;                       /* [B, C] */
@@ -324,6 +345,17 @@ typedef struct hcg_explain_args {
   int32_t path_step_first;               /* first quadrature point of this launch */
   int32_t path_step_count;               /* points of this launch; path_step_first + path_step_count <= path_steps */
   int32_t path_class_index;              /* the attributed output column c, 0 .. C - 1 */
+  };
+  struct {                               /*   HCG_EXPLAIN_MOMENTS */
+  const float* mom_values[2];            /* [mom_count, mom_len[s]]: row j = model mom_first + j */
+  float* mom_mean[2];                    /* IN/OUT [mom_len[s]]: running mean (read when mom_first > 0) */
+  float* mom_m2[2];                      /* IN/OUT [mom_len[s]]: running sum of squared deviations */
+  float* mom_std[2];                     /* OUT [mom_len[s]]: sqrtf(m2 / mom_total), by the call that ends at mom_total */
+  int64_t mom_len[2];                    /* entries per model of array s; 0: the array is not used */
+  int32_t mom_total;                     /* models of the whole ensemble, >= 1 */
+  int32_t mom_first;                     /* first model of this call */
+  int32_t mom_count;                     /* models of this call; mom_first + mom_count <= mom_total */
+  int32_t mom_reserved;
   };
   };
 } hcg_explain_args;
