@@ -21,6 +21,8 @@ Public surface (mirrors the reference's names for this path):
                                                 predict_test.py loop); train.predict_networks is its loader form
     ShapleySampling, draw_permutations          Shapley value sampling of a batch of graphs, the permutation walk on chip
                                                 (the reference's second explain algorithm, explain_gnn.py)
+    atom_groups, bond_groups, draw_group_permutations, all_group_permutations
+                                                the same walk with atoms, bonds or fragments as the players
     IntegratedGradients, quadrature             integrated gradients (Captum's IntegratedGradients through the same
                                                 CaptumExplainer entry point) of a batch of graphs, the whole path of every
                                                 graph in one launch; method="gradient" / saliency=True are its one-step
@@ -38,11 +40,13 @@ from .fit import FitControl, FitResult, fit_network, fit_networks  # noqa: F401
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
 from .networks import BaseNetwork  # noqa: F401
 from .plan import BatchPlan  # noqa: F401
-from .shapley import ShapleyResult, ShapleySampling, draw_permutations  # noqa: F401
+from .shapley import (GroupedShapleyResult, ShapleyResult, ShapleySampling, all_group_permutations, atom_groups,  # noqa: F401
+                      bond_groups, draw_group_permutations, draw_permutations)
 from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
 
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
-           "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "ExplainFit", "ExplainFitResult",
+           "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "GroupedShapleyResult", "atom_groups",
+           "bond_groups", "draw_group_permutations", "all_group_permutations", "ExplainFit", "ExplainFitResult",
            "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
            "quadrature", "EnsembleAttribution", "EnsembleAttributionResult"]

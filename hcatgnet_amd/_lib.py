@@ -31,6 +31,7 @@ HCG_EXPLAIN_INTEGRATED = 5
 HCG_EXPLAIN_MOMENTS = 6          # mean / std over the model axis of HCG_EXPLAIN_INTEGRATED's outputs with n_models > 1
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
+HCG_EXPLAIN_GROUPED = 8          # flag of HCG_EXPLAIN_SHAPLEY: groups of features are the players (`SHAPLEY_GROUP_FIELDS`)
 HCG_ERR_UNSUPPORTED = -3
 HCG_FUSED_FORWARD, HCG_FUSED_BWD_PAIR, HCG_FUSED_PAIR_QUERY = 0, 1, 1      # modes of hcg_fused_forward's block; the pair's flag
 HCG_HEAD_MAX_LAYERS = 4
@@ -115,7 +116,8 @@ class ExplainArgs(ctypes.Structure):
     GNNExplainer mask fit of a batch of graphs, or its integrated gradients.  The header's `path_` fields
     (HCG_EXPLAIN_INTEGRATED) share the storage of the `fit_` block through a union; here they are the `_Overlay` attributes
     attached below (`PATH_FIELDS`), so `_fields_`, the size and every offset stay what they were.  The `mom_` fields
-    (HCG_EXPLAIN_MOMENTS, `MOMENT_FIELDS`) are the union's third block, attached the same way."""
+    (HCG_EXPLAIN_MOMENTS, `MOMENT_FIELDS`) are the union's third block and the `shap_` fields (HCG_EXPLAIN_SHAPLEY with
+    HCG_EXPLAIN_GROUPED, `SHAPLEY_GROUP_FIELDS`) its fourth, attached the same way."""
     _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
                 ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
                 ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
@@ -170,8 +172,14 @@ def _attach_union_fields(fields):
     assert off <= ctypes.sizeof(ExplainArgs)
 
 
+# hcg_explain_args' members of HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED (the union's fourth block), from the same offset
+SHAPLEY_GROUP_FIELDS = (("shap_group_ptr", P), ("shap_member_ptr", P), ("shap_members", P), ("shap_bg_ptr", P),
+                        ("shap_bg_members", P), ("shap_n_groups", I64))
+
+
 _attach_union_fields(PATH_FIELDS)
 _attach_union_fields(MOMENT_FIELDS)
+_attach_union_fields(SHAPLEY_GROUP_FIELDS)
 
 
 class CollateSlot(ctypes.Structure):

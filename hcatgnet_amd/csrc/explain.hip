@@ -741,6 +741,8 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
                                                 p->mode == HCG_EXPLAIN_SHAPLEY || p->mode == HCG_EXPLAIN_INTEGRATED ||
                                                 p->mode == HCG_EXPLAIN_MOMENTS))
     return HCG_ERR_INVALID_ARG;
+  // groups of features as players belong to HCG_EXPLAIN_SHAPLEY alone
+  if ((p->flags & HCG_EXPLAIN_GROUPED) && p->mode != HCG_EXPLAIN_SHAPLEY) return HCG_ERR_INVALID_ARG;
   if (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD) {
     if (p->flags & HCG_EXPLAIN_QUERY) { p->workspace_bytes_needed = 0; return HCG_OK; }
     return hcg_edge_weight_grad_launch(p->layer_dout, p->layer_out, p->layer_h, p->rowptr, p->col, p->dinv, p->slope,

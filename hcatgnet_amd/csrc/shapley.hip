@@ -33,6 +33,13 @@
 // The differences go to the caller's workspace, one row per permutation of the launch; k_shapley_reduce then adds the rows onto
 // the accumulator, p ascending, continuing from what earlier launches left: the mean over all permutations is one fixed-order
 // sum however the permutations are split into launches.
+// HCG_EXPLAIN_GROUPED (k_shapley_walk<true>): the players are groups of features -- an atom, a bond, a fragment (Captum's
+// feature_mask) -- and a background is always on.  The walk is the same: "apply the step to the state" becomes "apply every
+// live member of the group" (s_apply: the host lists them, ascending, in global memory), "evaluate" stays one evaluation, and
+// the base evaluation follows the background's application.  The chunk classification reads one group id per thread; an empty
+// member range is a group that cannot change the output (0 at once, no evaluation); pj / pv carry the queued group ids and
+// their first member positions.  Permutation rows, workspace rows and the accumulator have one entry per group.  No LDS is
+// added: the members are staged through t1, which is idle between two evaluations.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -49,8 +56,16 @@ struct SArgs {     // the kernel's argument block (device pointers by value)
   float* out;                               // [B][C] everything on
   float* out_base;                          // [B][C] everything off
   float* ws;                                // [count][row] the differences of this launch's permutations
-  long long NF, Etot, row;                  // N F, E, N F + E
+  long long NF, Etot, row;                  // N F, E, N F + E (GROUPED: row = G, the groups of the batch)
   int first, cls;
+};
+
+struct SGArgs : SArgs {   // what HCG_EXPLAIN_GROUPED adds (GROUPED = true only): perm is [P][G], ws [count][G]
+  const int32_t* group_ptr;                 // [B + 1] graph g's groups: group_ptr[g] .. group_ptr[g + 1] - 1 of a row
+  const int32_t* member_ptr;                // [G + 1] into `members`
+  const int32_t* members;                   // live members, local feature indices, ascending within a group
+  const int32_t* bg_ptr;                    // [B + 1] into `bg_members`
+  const int32_t* bg_members;                // the live background of every graph, ascending
 };
 
 struct SLds {
@@ -63,8 +78,8 @@ struct SLds {
   int* cnt;             // [npad]  in-degree, then the fill cursor
   float* dinv;          // [npad]
   float* hv;            // [X_HEAD] readout activations: emb | v1 | v2 | ... | out
-  int* pj;              // [S_CHUNK] the chunk's steps: local feature index, -1 = nothing to evaluate
-  float* pv;            // [S_CHUNK] the x value of a node entry
+  int* pj;              // [S_CHUNK] the chunk's steps: local feature index (GROUPED: local group id), -1 = nothing to evaluate
+  float* pv;            // [S_CHUNK] the x value of a node entry (GROUPED: the bits of the group's first position in `members`)
 };
 
 __host__ __device__ inline unsigned s_lds_bytes(int npad, int emax) {
@@ -91,7 +106,58 @@ __device__ __forceinline__ SLds s_carve(char* base, int npad, int emax) {
 
 __device__ __forceinline__ float s_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
-__global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
+// GROUPED: switch the members mem[mb .. me) on (mb, me uniform; all 8 waves).  XT members at a time are staged in t1 (free
+// between two evaluations): the thread that loads a member stores an edge's mval = 1 itself and leaves a node entry as
+// (node << 6 | f, x) for the node's owner -- wave (node mod 8) -- which applies its entries in list order with the ungrouped
+// walk's rank-1 update.  So every element of h1 has one owner and takes its updates in ascending member order, whatever the
+// group's size.  An index outside [0, K) is skipped.  The caller places the barrier between this and the evaluation.
+__device__ __forceinline__ void s_apply(const SLds& L, const XCommon& cm, const int32_t* mem, int mb, int me, int nbase, int nF,
+                                        int K, int tid) {
+  const int lane = tid & 63, wave = tid >> 6, F = cm.F;
+  int* const code = reinterpret_cast<int*>(L.t1);        // [XT]
+  float* const val = L.t1 + XT;                          // [XT]  (npad >= 16: the tile has 16 * XS >= 2 XT floats)
+#pragma nounroll
+  for (int c0 = mb; c0 < me; c0 += XT) {
+    if (c0 != mb) __syncthreads();                       // (the members staged before have been applied)
+    int cd = -1;
+    float xv = 0.f;
+    if (tid < me - c0) {
+      const int jj = mem[c0 + tid];
+      if (jj >= 0 && jj < nF) {
+        const int i = jj / F;
+        cd = (i << 6) | (jj - i * F);
+        xv = cm.x[(size_t)nbase * F + jj];
+      } else if (jj >= nF && jj < K) {
+        L.mval[jj - nF] = 1.f;
+      }
+    }
+    code[tid] = cd;
+    val[tid] = xv;
+    __syncthreads();
+    const int cnt = min(XT, me - c0);
+#pragma nounroll
+    for (int s = 0; s < cnt; s += 64) {
+      const int cdl = code[s + lane];
+      const float xl = val[s + lane];
+      unsigned long long mine = __ballot(cdl >= 0 && ((cdl >> 6) & (XW - 1)) == wave);
+#pragma nounroll
+      while (mine) {
+        const int b = __builtin_ctzll(mine);
+        mine &= mine - 1;
+        const int cu = __builtin_amdgcn_readlane(cdl, b);
+        const float xs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xl), b));
+        const int i = cu >> 6, f = cu & 63;
+        L.h1[i * XS + lane] = fmaf(xs, cm.cW[0][lane * F + f], L.h1[i * XS + lane]);
+      }
+    }
+  }
+}
+
+// GROUPED = false: one feature per step (Args = SArgs).  GROUPED = true: HCG_EXPLAIN_GROUPED (Args = SGArgs) -- the players are
+// the graph's groups, a step switches on every live member of one group and is evaluated once, and the live background is on
+// from the base evaluation on.  The ungrouped instantiation is the kernel as it was before the template.
+template <bool GROUPED, class Args>
+__global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const XCommon& cm = a.c;
   const SLds L = s_carve(smem, cm.npad, cm.emax);
@@ -107,6 +173,12 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
     const int nbase = sp.nbase, ebase = sp.ebase, n_raw = sp.n_raw, ne_raw = sp.ne_raw;
     if (p0)
       for (int k = tid; k < C; k += XT) { a.out[(size_t)g * C + k] = 0.f; a.out_base[(size_t)g * C + k] = 0.f; }
+    if constexpr (GROUPED) {
+      const long long ge = a.group_ptr[g + 1];
+      for (long long k = (long long)a.group_ptr[g] + tid; k < ge; k += XT)
+        if (k >= 0 && k < a.row) wsrow[k] = 0.f;
+      return;
+    }
     for (long long e = tid; e < ne_raw; e += XT) {
       const long long p = (long long)ebase + e;
       if (p >= 0 && p < a.Etot) wsrow[a.NF + p] = 0.f;
@@ -149,7 +221,12 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
   }
 
   const int nF = n * F, K = nF + ne;                      // the graph's features
-  const long long seg = (long long)nbase * F + ebase;     // its segment of a permutation row
+  int gp = 0, steps = K;                                  // GROUPED: the graph's first group and its number of groups
+  if constexpr (GROUPED) {
+    gp = __builtin_amdgcn_readfirstlane(a.group_ptr[g]);
+    steps = __builtin_amdgcn_readfirstlane(a.group_ptr[g + 1]) - gp;
+  }
+  const long long seg = GROUPED ? (long long)gp : (long long)nbase * F + ebase;     // its segment of a permutation row
   const int32_t* const prow = a.perm + (size_t)(a.first + (int)blockIdx.y) * (size_t)a.row;
   int knext = 0, nq = 0, qi = 0;
   bool base = true;
@@ -164,8 +241,8 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
       bool found = false;
       while (!found) {
         if (qi == nq) {
-          if (knext >= K) break;
-          const int cnt = min(S_CHUNK, K - knext);
+          if (knext >= steps) break;
+          const int cnt = min(S_CHUNK, steps - knext);
           __syncthreads();                                 // (the chunk before has been walked)
           if (tid < cnt) {
             long long at = seg + knext + tid;
@@ -173,7 +250,14 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
             const int jj = prow[at];
             int code = -1;
             float xv = 0.f;
-            if (jj >= 0 && jj < nF) {
+            if constexpr (GROUPED) {
+              // a group without a live member: its difference is 0 by definition, written at once
+              if (jj >= 0 && jj < steps && (long long)gp + jj < a.row) {
+                const int mb = a.member_ptr[gp + jj];
+                if (a.member_ptr[gp + jj + 1] > mb) code = jj; else wsrow[gp + jj] = 0.f;
+                xv = __int_as_float(mb);
+              }
+            } else if (jj >= 0 && jj < nF) {
               const size_t p = (size_t)nbase * F + jj;
               xv = cm.x[p];
               if (xv != 0.f) code = jj; else wsrow[p] = 0.f;
@@ -194,7 +278,11 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
         ++qi;
       }
       if (!found) break;
-      if (j < nF) {
+      if constexpr (GROUPED) {
+        const int mb = __builtin_amdgcn_readfirstlane(__float_as_int(L.pv[qi - 1]));
+        const int me = __builtin_amdgcn_readfirstlane(a.member_ptr[gp + j + 1]);
+        s_apply(L, cm, a.members, mb, me, nbase, nF, K, tid);
+      } else if (j < nF) {
         if (wave == 0) {
           const float xv = s_uniform(L.pv[qi - 1]);
           const int i = j / F, f = j - i * F;
@@ -203,6 +291,11 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
       } else if (tid == 0) {
         L.mval[j - nF] = 1.f;
       }
+      __syncthreads();
+    } else if constexpr (GROUPED) {
+      // the background is on in every evaluation, the base included
+      s_apply(L, cm, a.bg_members, __builtin_amdgcn_readfirstlane(a.bg_ptr[g]), __builtin_amdgcn_readfirstlane(a.bg_ptr[g + 1]),
+              nbase, nF, K, tid);
       __syncthreads();
     }
 
@@ -246,13 +339,14 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const SArgs a) {
     if (base) {
       if (p0 && tid < C) a.out_base[(size_t)g * C + tid] = L.hv[off + tid];
     } else if (tid == 0) {
-      wsrow[j < nF ? (size_t)nbase * F + j : (size_t)(a.NF + ebase + (j - nF))] = v - vprev;
+      wsrow[GROUPED ? (size_t)(gp + j) : j < nF ? (size_t)nbase * F + j : (size_t)(a.NF + ebase + (j - nF))] = v - vprev;
     }
     vprev = v;
     base = false;
     // (hv is next written behind the barriers of the next evaluation's conv stack)
   }
-  // hv still holds the last evaluation: everything on (features that were skipped change nothing)
+  // hv still holds the last evaluation: everything on (features that were skipped change nothing; GROUPED: every live
+  // feature is in the background or in a group)
   if (p0 && tid < C) a.out[(size_t)g * C + tid] = L.hv[off + tid];
 }
 
@@ -272,7 +366,11 @@ __global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict_
 int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   if (p->edge_mask || p->node_mask || p->target || p->dout) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
-  const long long NF = (long long)p->N * p->F, row = NF + p->E;
+  const bool grouped = (p->flags & HCG_EXPLAIN_GROUPED) != 0;
+  const long long NF = (long long)p->N * p->F;
+  // (every group has a member, so G <= N F + E)
+  if (grouped && (p->shap_n_groups < 0 || p->shap_n_groups > NF + p->E)) return HCG_ERR_INVALID_ARG;
+  const long long row = grouped ? (long long)p->shap_n_groups : NF + p->E;   // entries of a permutation and of a workspace row
   const int count = p->perm_count > 0 ? p->perm_count : 1;
   if (row >= (1ll << 31) || count > 65535) return HCG_ERR_UNSUPPORTED;
   const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
@@ -286,9 +384,11 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
     return HCG_ERR_INVALID_ARG;
   if (p->B == 0) return HCG_OK;
   if (!x_common_ok(p) || !p->out_base || (row > 0 && (!p->perm || !p->shap_acc))) return HCG_ERR_INVALID_ARG;
+  if (grouped && (!p->shap_group_ptr || !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members))
+    return HCG_ERR_INVALID_ARG;
   if (row > 0 && (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed)) return HCG_ERR_WORKSPACE;
 
-  SArgs a;
+  SGArgs a;
   x_fill_common(a.c, p, S_NPAD_MIN);
   a.perm = p->perm;
   a.out = p->out;
@@ -299,7 +399,14 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   a.row = row;
   a.first = p->perm_first;
   a.cls = p->class_index;
-  const int rc = x_launch<k_shapley_walk>(dim3((unsigned)p->B, (unsigned)p->perm_count), lds, stream, a);
+  a.group_ptr = grouped ? p->shap_group_ptr : nullptr;      // (the union holds these in a grouped call only)
+  a.member_ptr = grouped ? p->shap_member_ptr : nullptr;
+  a.members = grouped ? p->shap_members : nullptr;
+  a.bg_ptr = grouped ? p->shap_bg_ptr : nullptr;
+  a.bg_members = grouped ? p->shap_bg_members : nullptr;
+  const dim3 grid((unsigned)p->B, (unsigned)p->perm_count);
+  const int rc = grouped ? x_launch<k_shapley_walk<true, SGArgs>>(grid, lds, stream, a)
+                         : x_launch<k_shapley_walk<false, SArgs>>(grid, lds, stream, static_cast<const SArgs&>(a));
   if (rc != HCG_OK) return rc;
   if (row > 0) {
     hipLaunchKernelGGL(k_shapley_reduce, dim3((unsigned)hcg_cdiv(row, 256)), dim3(256), 0, stream, (const float*)p->workspace,

@@ -11,10 +11,17 @@ chosen output column at its step.  The attribution is the mean over the permutat
 `ShapleySampling` runs that walk on chip (csrc/shapley.hip): one workgroup per (graph, permutation) keeps its graph in LDS
 and evaluates the model after every step, with no launch in between.  No reference artefact pins Shapley values: parity
 is against the fp64 oracle only.
+
+Groups as players (Captum's `feature_mask`, PyG's mask type None): with `node_group` / `edge_group` the features of a graph
+are partitioned into groups -- an atom, a bond, a fragment -- that are switched on together and share one attribution, plus
+a background that is always on.  The same kernel walks them (`HCG_EXPLAIN_GROUPED`): a step applies every live member of
+its group and is evaluated once.  `atom_groups`, `bond_groups`, `draw_group_permutations` and `all_group_permutations`
+build the usual arguments.
 """
 from __future__ import annotations
 
 import ctypes
+import itertools
 from typing import NamedTuple, Optional
 
 import torch
@@ -29,6 +36,7 @@ CUS = 256                          # compute units of an MI355X
 LAUNCH_SECONDS = 1.0               # what one launch should stay near (the machines are shared)
 EVAL_SECONDS = 60e-6               # one evaluation at the shape limits: an estimate (default_samples_per_launch)
 MAX_WORKGROUPS_PER_CU = 4
+GROUPED_WORKGROUPS_PER_CU = 64     # a grouped walk is short (its steps are the groups): more of them queue on a CU per launch
 
 
 class ShapleyResult(NamedTuple):
@@ -36,6 +44,15 @@ class ShapleyResult(NamedTuple):
     edge_attr: torch.Tensor      # [E], the batch's edge order
     out_full: torch.Tensor       # [B, C] the model's output with every feature on (= the plain forward)
     out_base: torch.Tensor       # [B, C] with every feature off
+
+
+class GroupedShapleyResult(NamedTuple):
+    group_attr: torch.Tensor     # [G] graph g's groups at group_ptr[g] .. group_ptr[g + 1] - 1
+    group_ptr: torch.Tensor      # [B + 1] int64
+    node_attr: torch.Tensor      # [N, F] every member carries its group's value, the background 0 (a gather of group_attr)
+    edge_attr: torch.Tensor      # [E]
+    out_full: torch.Tensor       # [B, C] the model's output with everything on (= the plain forward)
+    out_base: torch.Tensor       # [B, C] with the background only
 
 
 def _layout(batch, F: int):
@@ -68,6 +85,141 @@ def draw_permutations(batch, F: int, n_samples: int, generator: Optional[torch.G
         order = torch.argsort(gid.to(torch.float64) + key)
         out[p] = (order - start).to(torch.int32)
     return out
+
+
+class _Groups(NamedTuple):
+    """The group layout of one call (`_group_layout`); every tensor on the batch's device."""
+    G: int                       # groups of the batch
+    max_groups: int              # the largest G_g
+    count: torch.Tensor          # [B] int64 G_g
+    group_ptr: torch.Tensor      # [B + 1] int64
+    slot: torch.Tensor           # [N * F + E] int64: the feature's global group (group_ptr[graph] + id), G for the background
+    live_group: torch.Tensor     # [G] bool: the group has a live member
+    member_ptr: torch.Tensor     # [G + 1] int32 into `members`
+    bg_ptr: torch.Tensor         # [B + 1] int32 into `members`
+    members: torch.Tensor        # [N * F + E] int32 local feature indices: the groups' live members, group by group,
+    #                              then the graphs' live background, then the dead features
+
+
+def _group_layout(batch, F: int, node_group, edge_group) -> _Groups:
+    """Check `node_group` / `edge_group` and build the lists the kernel reads, with torch ops on the batch's device: one
+    stable sort of all features by (group | graph of the background | dead) -- features are numbered graph by graph, node
+    entries before edges, so equal keys stay in ascending local index -- and ONE read of three scalars (G, the largest G_g,
+    whether the ids are valid) beside what `_layout` costs."""
+    x, ei = batch.x, batch.edge_index
+    N, E, B, dev = int(x.shape[0]), int(ei.shape[1]), int(batch.num_graphs), x.device
+
+    def ids_of(t, name, shapes):
+        if t is None:
+            return None
+        if not torch.is_tensor(t) or t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64) or tuple(t.shape) not in shapes:
+            raise ValueError(f"{name} must be an integer tensor of shape {' or '.join(str(list(q)) for q in shapes)}; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, the batch on {dev}")
+        return t.to(torch.int64)
+    ng = ids_of(node_group, "node_group", ((N,), (N, F)))
+    eg = ids_of(edge_group, "edge_group", ((E,),))
+    if ng is None and eg is None:
+        raise ValueError("give node_group, edge_group or both")
+    ng = torch.full((N * F,), -1, dtype=torch.int64, device=dev) if ng is None else \
+        (ng.unsqueeze(1).expand(N, F) if ng.dim() == 1 else ng).reshape(-1)
+    eg = torch.full((E,), -1, dtype=torch.int64, device=dev) if eg is None else eg
+    n, e, gptr, eptr, _ = _layout(batch, F)
+    src, dst = ei[0], ei[1]
+    egraph = batch.batch[dst]
+    ids = torch.cat([ng, eg])
+    graph = torch.cat([batch.batch.repeat_interleave(F), egraph])
+    count = torch.zeros(B, dtype=torch.int64, device=dev).scatter_reduce(0, graph, ids + 1, reduce="amax", include_self=True)
+    group_ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    group_ptr[1:] = count.cumsum(0)
+    grouped = ids >= 0
+    # (every group has a member, so valid ids have G <= N F + E: the used-slot table needs no size from the device, and a
+    # slot beyond it -- ids with a gap -- lands on the spare entry and leaves the count short)
+    used = torch.zeros(N * F + E + 1, dtype=torch.int64, device=dev)
+    at = group_ptr[graph] + ids
+    used[torch.where(grouped & (at < N * F + E), at, N * F + E)] = 1
+    bad = (used[:-1].sum() != group_ptr[-1]) | (ids < -1).any()
+    G, max_groups, bad = torch.stack([group_ptr[-1], count.max() if B > 0 else group_ptr[-1], bad.to(torch.int64)]).tolist()
+    if bad:
+        raise ValueError("the group ids of a graph, over node_group and edge_group, must be exactly 0 .. G_g - 1, each used "
+                         "at least once, and -1 for the background")
+    slot = torch.where(grouped, group_ptr[graph] + ids, G)
+    local = torch.cat([((torch.arange(N, device=dev) - gptr[batch.batch]) * F).repeat_interleave(F) + torch.arange(F, device=dev).repeat(N),
+                       n[egraph] * F + torch.arange(E, device=dev) - eptr[egraph]])
+    live = torch.cat([(x != 0).reshape(-1), src != dst])
+    key = torch.where(live, torch.where(grouped, slot, G + graph), G + B)
+    order = torch.sort(key, stable=True).indices
+    ptr = torch.zeros(G + B + 2, dtype=torch.int64, device=dev)
+    ptr[1:] = torch.bincount(key, minlength=G + B + 1).cumsum(0)
+    live_group = ptr[1:G + 1] > ptr[:G]
+    return _Groups(int(G), int(max_groups), count, group_ptr, slot, live_group, ptr[:G + 1].to(torch.int32).contiguous(),
+                   ptr[G:G + B + 1].to(torch.int32).contiguous(), local[order].to(torch.int32).contiguous())
+
+
+def atom_groups(batch) -> torch.Tensor:
+    """`node_group` [N] int64 with one player per atom: the node's index inside its graph."""
+    B = int(batch.num_graphs)
+    gptr = torch.zeros(B + 1, dtype=torch.int64, device=batch.batch.device)
+    gptr[1:] = torch.bincount(batch.batch, minlength=B).cumsum(0)
+    return torch.arange(batch.batch.numel(), device=batch.batch.device) - gptr[batch.batch]
+
+
+def bond_groups(batch, first=0) -> torch.Tensor:
+    """`edge_group` [E] int64 that pairs (i, j) with (j, i) inside a graph: ids ascend by first occurrence in the batch's
+    edge order and start at `first` in every graph (`first` may be a [B] tensor: bonds numbered after atoms).  An unpaired
+    directed edge is a group of its own, every duplicate of a directed edge joins its pair's group, an explicit (i, i) gets
+    a group that is simply dead."""
+    ei, dev = batch.edge_index, batch.edge_index.device
+    E, B, N = int(ei.shape[1]), int(batch.num_graphs), int(batch.batch.numel())
+    first = torch.as_tensor(first, dtype=torch.int64, device=dev)
+    if first.dim() > 1 or (first.dim() == 1 and first.numel() != B):
+        raise ValueError(f"first must be an integer or a [B = {B}] tensor; got shape {tuple(first.shape)}")
+    if E == 0:
+        return torch.zeros(0, dtype=torch.int64, device=dev)
+    lo, hi = torch.minimum(ei[0], ei[1]), torch.maximum(ei[0], ei[1])
+    graph = batch.batch[ei[1]]
+    _, inv = torch.unique(lo * max(N, 1) + hi, return_inverse=True)              # one id per undirected bond
+    U = int(inv.max()) + 1
+    pos = torch.full((U,), E, dtype=torch.int64, device=dev).scatter_reduce(0, inv, torch.arange(E, device=dev), reduce="amin")
+    bond_graph = torch.zeros(U, dtype=torch.int64, device=dev).scatter(0, inv, graph)
+    rank = torch.empty(U, dtype=torch.int64, device=dev)
+    rank[torch.argsort(bond_graph * E + pos)] = torch.arange(U, device=dev)      # graph by graph, by first occurrence
+    start = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    start[1:] = torch.bincount(bond_graph, minlength=B).cumsum(0)
+    return rank[inv] - start[graph] + (first[graph] if first.dim() == 1 else first)
+
+
+def draw_group_permutations(batch, node_group=None, edge_group=None, n_samples: int = 25,
+                            generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """int32 [n_samples, G] on the batch's device: in every row, graph g's segment (start group_ptr[g], length G_g) is a
+    uniformly random permutation of 0 .. G_g - 1, drawn as `draw_permutations` draws: the argsort of (graph id, key)."""
+    return _draw_group_permutations(_group_layout(batch, int(batch.x.shape[1]), node_group, edge_group), batch.x.device,
+                                    n_samples, generator)
+
+
+def _draw_group_permutations(gr: _Groups, dev, n_samples: int, generator) -> torch.Tensor:
+    gid = torch.repeat_interleave(torch.arange(gr.count.numel(), device=dev), gr.count)
+    start = gr.group_ptr[gid]
+    gdev = generator.device if generator is not None else dev
+    out = torch.empty(int(n_samples), gr.G, dtype=torch.int32, device=dev)
+    for p in range(int(n_samples)):
+        key = torch.rand(gr.G, generator=generator, device=gdev, dtype=torch.float64).to(dev)
+        order = torch.argsort(gid.to(torch.float64) + key)
+        out[p] = (order - start).to(torch.int32)
+    return out
+
+
+def all_group_permutations(batch, node_group=None, edge_group=None) -> torch.Tensor:
+    """int32 [G_g!, G]: every order of the groups, for a batch whose graphs all have the same G_g <= 6 (ValueError
+    otherwise).  The mean over these rows is the exact Shapley value of the groups."""
+    gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
+    counts = set(gr.count.tolist())
+    if len(counts) > 1 or (counts and max(counts) > 6):
+        raise ValueError(f"all_group_permutations needs the same number of groups <= 6 in every graph; got {sorted(counts)}")
+    g0 = counts.pop() if counts else 0
+    rows = torch.tensor(list(itertools.permutations(range(g0))), dtype=torch.int32).reshape(-1, g0)
+    return rows.repeat(1, gr.count.numel()).to(batch.x.device).contiguous()
 
 
 def _torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):
@@ -125,7 +277,24 @@ class ShapleySampling:
     batch-synchronous loop `loop`: step k switches on the k-th feature of every graph's permutation at once and runs one
     masked forward of the whole batch -- forward-only `ExplainStep` on GPU tensors (its one-launch kernel where that
     applies, else `set_masks` + the model under `no_grad`), plain torch ops on CPU tensors.  `last_path` says which one
-    ran ("fused" / "loop")."""
+    ran ("fused" / "loop").
+
+    Groups as players (Captum's `feature_mask`, baselines 0):
+
+        r = sv(batch, n_samples=25, node_group=atom_groups(batch), edge_group=None, group_permutations=None, ...)
+        # GroupedShapleyResult(group_attr [G], group_ptr [B + 1], node_attr [N, F], edge_attr [E], out_full, out_base)
+
+    `node_group`: integer tensor [N] (all F entries of a node share the id) or [N, F]; `edge_group`: integer tensor [E].
+    Ids are local to the graph: over both arrays a graph uses exactly 0 .. G_g - 1, each at least once (else ValueError),
+    and -1 for the background, which is never a player: it is on in every evaluation, the base included.  Giving one
+    array puts the other kind wholly in the background.  For permutation pi of graph g's groups, v_0 is the output with
+    the background only, v_k with the groups pi_1 .. pi_k on as well, and group pi_k gets v_k[c] - v_(k-1)[c]; the mean
+    over the permutations, p ascending, is `group_attr`.  A group without a live member (a node entry with x != 0, an
+    edge that is no explicit (i, i)) gets exactly 0 and costs no evaluation.  `node_attr` / `edge_attr` follow Captum:
+    every member carries its group's value, the background 0.  `group_permutations`: int32 [P, G], graph g's segment at
+    group_ptr[g] (`draw_group_permutations`, `all_group_permutations`); None: `n_samples` rows from `generator`.
+    `permutations` belongs to the ungrouped call.  With neither array given the call is the ungrouped one, unchanged.
+    The host checks the ids and lists the members with torch ops: one stable sort and one read of three scalars."""
 
     def __init__(self, model: torch.nn.Module):
         self.model = model
@@ -136,13 +305,15 @@ class ShapleySampling:
         self._step = ExplainStep(model, apply_sigmoid=False)
 
     # ------------------------------------------------------------------ support check (host only, no sync)
-    def _shape_args(self, a, batch, perm_count: int = 1) -> Optional[str]:
+    def _shape_args(self, a, batch, perm_count: int = 1, n_groups: Optional[int] = None) -> Optional[str]:
+        """`n_groups`: the query of a grouped call (rows of G entries)."""
         m = self.model
         why = _frozen.model_reason(m)
         if why is None and batch is not None:
             why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, int(m.n_node_features), "model")
+        more = {} if n_groups is None else dict(flags=_lib.HCG_EXPLAIN_QUERY | _lib.HCG_EXPLAIN_GROUPED, shap_n_groups=int(n_groups))
         return why or _frozen.query(a, _lib.HCG_EXPLAIN_SHAPLEY, _frozen.model_shape(m), batch, perm_count=int(perm_count),
-                                    edge_mask=None, node_mask=None, target=None, dout=None)
+                                    edge_mask=None, node_mask=None, target=None, dout=None, **more)
 
     def reason(self, batch=None) -> Optional[str]:
         """None when this model (and `batch`) takes the on-chip kernel, else why not.  Host metadata only."""
@@ -155,16 +326,18 @@ class ShapleySampling:
         return int(a.lds_bytes) if self._shape_args(a, batch) is None else None
 
     @staticmethod
-    def default_samples_per_launch(n_perm: int, num_graphs: int, row: int, max_steps: int = 0) -> int:
+    def default_samples_per_launch(n_perm: int, num_graphs: int, row: int, max_steps: int = 0,
+                                   max_per_cu: int = MAX_WORKGROUPS_PER_CU) -> int:
         """Permutations of one launch: as many as keep its workspace (4 * row bytes each) under `WORKSPACE_CAP_BYTES` and
-        its run time near `LAUNCH_SECONDS`, at least 1.  `max_steps` = max_nodes * F + max_edges bounds the evaluations of
-        one workgroup (every step evaluated: dense features); at `EVAL_SECONDS` each, a CU gets as many workgroups as fit
+        its run time near `LAUNCH_SECONDS`, at least 1.  `max_steps` = max_nodes * F + max_edges (a grouped call: the
+        largest G_g) bounds the evaluations of one workgroup (every step evaluated: dense features); at `EVAL_SECONDS` each, a CU gets as many workgroups as fit
         the time, at least one.  `EVAL_SECONDS` is an ESTIMATE: profiles/shapley_bench.json has about 15-20 us per
         evaluation at two conv layers and 122-node graphs (36 ms per launch of 535 workgroups of about 860 evaluations),
-        extrapolated to the 184-node, four-layer limit; nobody has timed a launch at the limit shapes."""
+        extrapolated to the 184-node, four-layer limit; nobody has timed a launch at the limit shapes.  `max_per_cu` caps
+        the workgroups a CU gets in one launch (a grouped call: `GROUPED_WORKGROUPS_PER_CU`)."""
         by_ws = WORKSPACE_CAP_BYTES // max(4 * int(row), 1)
         per_cu = max(1, int(LAUNCH_SECONDS / (max(int(max_steps), 1) * EVAL_SECONDS)))
-        by_wg = min(per_cu, MAX_WORKGROUPS_PER_CU) * CUS // max(int(num_graphs), 1)
+        by_wg = min(per_cu, int(max_per_cu)) * CUS // max(int(num_graphs), 1)
         return max(1, min(int(n_perm), by_ws, by_wg, 65535))
 
     # ------------------------------------------------------------------ buffers
@@ -194,8 +367,75 @@ class ShapleySampling:
         return t.contiguous()
 
     # ------------------------------------------------------------------ the call
+    # ------------------------------------------------------------------ groups as players
+    def _group_permutations(self, batch, gr, n_samples, group_permutations, generator):
+        if group_permutations is None:
+            if int(n_samples) < 1:
+                raise ValueError(f"n_samples must be at least 1; got {n_samples}")
+            return _draw_group_permutations(gr, batch.x.device, int(n_samples), generator)
+        t = group_permutations
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != gr.G:
+            raise ValueError(f"group_permutations must be an int32 tensor of shape [P >= 1, G = {gr.G}]; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != batch.x.device:
+            raise ValueError(f"group_permutations are on {t.device}, the batch on {batch.x.device}")
+        return t.contiguous()
+
+    @staticmethod
+    def _grouped_result(gr, acc, N, F, out_full, out_base) -> GroupedShapleyResult:
+        flat = torch.cat([acc[:gr.G], acc.new_zeros(1)])[gr.slot]          # (the background reads the appended 0)
+        return GroupedShapleyResult(acc[:gr.G], gr.group_ptr, flat[:N * F].view(N, F), flat[N * F:], out_full, out_base)
+
+    def _call_grouped(self, batch, n_samples, generator, class_index, samples_per_launch, node_group, edge_group,
+                      group_permutations) -> GroupedShapleyResult:
+        a = self._args
+        F = int(batch.x.shape[1])
+        gr = _group_layout(batch, F, node_group, edge_group)
+        perm = self._group_permutations(batch, gr, n_samples, group_permutations, generator)
+        if self._shape_args(a, batch, 1, gr.G) is not None:
+            return self._loop_grouped(batch, gr, perm, class_index)
+        m = self.model
+        x = _frozen.batch_x(batch)
+        N, B, C = a.N, a.B, a.C
+        if not 0 <= int(class_index) < C:
+            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
+        P, G = int(perm.shape[0]), gr.G
+        spl = self.default_samples_per_launch(P, B, G, gr.max_groups, GROUPED_WORKGROUPS_PER_CU) if samples_per_launch is None \
+            else int(samples_per_launch)
+        if not 1 <= spl <= 65535:
+            raise ValueError(f"samples_per_launch must lie in 1 .. 65535; got {samples_per_launch}")
+        spl = min(spl, P)
+        self._shape_args(a, batch, spl, G)                  # the workspace of a launch of `spl` permutations
+        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
+        bufs = self._buffers(G, B, C, int(a.workspace_bytes_needed), x.device)
+        p = _lib.ptr
+        group_ptr = gr.group_ptr.to(torch.int32)
+        a.flags = _lib.HCG_EXPLAIN_GROUPED
+        _frozen.fill_graph(a, x, plan)
+        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ShapleySampling"))
+        a.out, a.out_base, a.shap_acc, a.perm = p(bufs["out"]), p(bufs["base"]), p(bufs["acc"]), p(perm)
+        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
+        a.slope, a.n_perm, a.class_index = SLOPE, P, int(class_index)
+        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr), p(gr.member_ptr), p(gr.bg_ptr)
+        # one array holds the groups' members and, behind them, the background (a batch without features: never read)
+        a.shap_members = a.shap_bg_members = p(gr.members) if gr.members.numel() else p(group_ptr)
+        a.shap_n_groups = G
+        lib, stream = _lib.load(), _lib.stream_ptr()
+        for first in range(0, P, spl):
+            a.perm_first, a.perm_count = first, min(spl, P - first)
+            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (grouped shapley)")
+        self.last_path = "fused"
+        return self._grouped_result(gr, bufs["acc"], N, F, bufs["out"][:B], bufs["base"][:B])
+
     def __call__(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0,
-                 samples_per_launch: Optional[int] = None) -> ShapleyResult:
+                 samples_per_launch: Optional[int] = None, node_group=None, edge_group=None, group_permutations=None):
+        if node_group is not None or edge_group is not None:
+            if permutations is not None:
+                raise ValueError("a grouped call takes group_permutations, not permutations")
+            return self._call_grouped(batch, n_samples, generator, class_index, samples_per_launch, node_group, edge_group,
+                                      group_permutations)
+        if group_permutations is not None:
+            raise ValueError("group_permutations need node_group or edge_group")
         a = self._args
         why = self._shape_args(a, batch)
         if why is not None:
@@ -235,8 +475,54 @@ class ShapleySampling:
             return _torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
         return self._step(batch, edge_mask, node_mask).out
 
-    def loop(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0) -> ShapleyResult:
+    def _loop_grouped(self, batch, gr, perm, class_index) -> GroupedShapleyResult:
+        """The loop with groups as players: the background is on from the base on, step k switches on every member of the
+        k-th group of every graph's permutation."""
+        x = batch.x
+        (N, F), B, G = x.shape, int(batch.num_graphs), gr.G
+        perm = perm.to(torch.int64)
+        P, dev = int(perm.shape[0]), x.device
+        garange = torch.arange(B, device=dev)
+        background = (gr.slot == G).to(torch.float32)
+        acc = torch.zeros(G, dtype=torch.float32, device=dev)
+        out_full = out_base = None
+        with torch.no_grad():
+            for p in range(P):
+                on = background.clone()
+                phi = torch.zeros(G, dtype=torch.float32, device=dev)
+                out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
+                if p == 0:
+                    out_base = out
+                vprev = out[:, class_index].clone()
+                for k in range(gr.max_groups):
+                    act = garange[gr.count > k]                            # graphs whose walk is not finished
+                    slot = gr.group_ptr[act] + perm[p, gr.group_ptr[act] + k]
+                    step = torch.zeros(G + 1, dtype=torch.bool, device=dev)
+                    step[slot] = True
+                    on = torch.where(step[gr.slot], torch.ones_like(on), on)
+                    out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
+                    v = out[:, class_index]
+                    # a group without a live member cannot change the output: its difference is exactly 0 by definition
+                    phi[slot] = torch.where(gr.live_group[slot], v[act] - vprev[act], torch.zeros_like(v[act]))
+                    vprev = v.clone()
+                if p == 0:
+                    out_full = out
+                acc = acc + phi
+        acc = acc / float(P)
+        self.last_path = "loop"
+        return self._grouped_result(gr, acc, N, F, out_full, out_base)
+
+    def loop(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0, node_group=None,
+             edge_group=None, group_permutations=None):
         """The batch-synchronous loop (see the class docstring), whatever `reason(batch)` says."""
+        if node_group is not None or edge_group is not None:
+            if permutations is not None:
+                raise ValueError("a grouped call takes group_permutations, not permutations")
+            gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
+            perm = self._group_permutations(batch, gr, n_samples, group_permutations, generator)
+            return self._loop_grouped(batch, gr, perm, class_index)
+        if group_permutations is not None:
+            raise ValueError("group_permutations need node_group or edge_group")
         x = batch.x
         (N, F), E, B = x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
         perm = self._permutations(batch, F, n_samples, permutations, generator).to(torch.int64)

@@ -195,6 +195,25 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   target_class and dout must be NULL (HCG_ERR_INVALID_ARG).  Shapes: as HCG_EXPLAIN_GRAPHS but graphs of <= 184 nodes (three [n][64] tiles are kept
  *   in LDS) and perm_count <= 65535; refusals as there (HCG_STATUS_SHAPE_LIMIT: the graph's rows of every output zero).
  *   HCG_EXPLAIN_QUERY as above (reads perm_count too).
+ *   HCG_EXPLAIN_GROUPED in `flags` (this mode only; in every other mode HCG_ERR_INVALID_ARG): the players are GROUPS of
+ *   features (Captum's ShapleyValueSampling with feature_mask, baselines 0).  Graph g's K features, indexed as above, are
+ *   partitioned into G_g groups with local ids 0 .. G_g - 1 and a background that is never a player: it is on in every
+ *   evaluation, the base included.  G = shap_n_groups is the batch's number of groups, shap_group_ptr [B + 1] int32 their
+ *   prefix sum (graph g's groups are shap_group_ptr[g] .. shap_group_ptr[g + 1] - 1 of every array of length G).  Only the
+ *   LIVE members are listed (a node entry with x != 0, an edge that is not an explicit (i, i)): group shap_group_ptr[g] + y
+ *   has the members shap_members[shap_member_ptr[..] .. shap_member_ptr[.. + 1]), local feature indices, ascending;
+ *   shap_member_ptr is [G + 1] int32; graph g's live background is shap_bg_members[shap_bg_ptr[g] .. shap_bg_ptr[g + 1]),
+ *   ascending, shap_bg_ptr [B + 1] int32 (both lists may lie in one array).  `perm` is [n_perm][G] int32: row p holds, for
+ *   every graph at offset shap_group_ptr[g], a permutation of 0 .. G_g - 1.  v_0 = out[class_index] with the background on,
+ *   v_k with the groups perm_1 .. perm_k on as well, phi_p[perm_k] = v_k - v_(k-1): a step switches every member of the group
+ *   on (every element of the first layer's product has one owner, which adds the members' terms in ascending member order)
+ *   and is evaluated ONCE.  A group without a live member -- an empty range -- gets exactly 0 and costs no evaluation.  The
+ *   workspace rows and shap_acc have length G (workspace_bytes_needed = perm_count * max(G, 1) * 4 rounded up to 256, by a
+ *   query too); out_base [B, C] = the output with the background only, out = with everything on.  Contents are trusted; a
+ *   member outside [0, K_g) and a group id outside [0, G_g) are skipped, never used as an address.  0 <= shap_n_groups <=
+ *   N F + E and, for a launch, the five arrays non-NULL (HCG_ERR_INVALID_ARG).  A refused graph: its G_g entries zero.  LDS,
+ *   shapes and the order of the sum over the permutations as without the flag.  The shap_ fields are the fourth member of
+ *   the union of the fit_, path_ and mom_ fields.
  * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
  *   node_mask_type 'attributes', edge_mask_type 'object'; regression, or multiclass classification on raw outputs) for a
  *   batch of graphs in ONE launch: the kernel of
@@ -263,10 +282,11 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
+#define HCG_EXPLAIN_GROUPED 8  /* flags: HCG_EXPLAIN_SHAPLEY walks groups of features (the shap_ fields) */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
   int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS */
-  int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS */
+  int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS | HCG_EXPLAIN_GROUPED */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
   const int32_t* graph_ptr;              /* [B + 1] */
@@ -356,6 +376,14 @@ typedef struct hcg_explain_args {
   int32_t mom_first;                     /* first model of this call */
   int32_t mom_count;                     /* models of this call; mom_first + mom_count <= mom_total */
   int32_t mom_reserved;
+  };
+  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED */
+  const int32_t* shap_group_ptr;         /* [B + 1] prefix sum of the graphs' group counts */
+  const int32_t* shap_member_ptr;        /* [G + 1] group -> its range of shap_members */
+  const int32_t* shap_members;           /* live members only: local feature indices, ascending within a group */
+  const int32_t* shap_bg_ptr;            /* [B + 1] graph -> its range of shap_bg_members */
+  const int32_t* shap_bg_members;        /* the live background, ascending within a graph */
+  int64_t shap_n_groups;                 /* G */
   };
   };
 } hcg_explain_args;
