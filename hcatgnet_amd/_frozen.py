@@ -1,18 +1,35 @@
 """The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`, `IntegratedGradients`,
-`EnsembleAttribution`: one graph per workgroup, all through `hcg_explain`): what a model must look like, the batch checks and their reason strings, the
-library's shape query, and the argument block's graph and weight pointers.  Private: the classes are the interface.
+`EnsembleAttribution`: one graph per workgroup, all through `hcg_explain`).
+
+    Frozen           what every class is: `last_path`, the argument block `_args`, the buffer pool `_bufs`, the support check
+                     (`_shape_args`, `reason`, `lds_bytes`), the class-index check and `_fill`, which sets what every launch sets
+    FrozenModel      one model: what it must look like, its weights checked for a launch (the ensembles' counterpart,
+                     `FrozenEnsemble`, lives beside `stack_weights` in ensemble.py)
+    Pool             name -> flat tensor, grow-only; a request returns the buffer's front in the shape asked for
+    query            clears the WHOLE argument block, fills the shapes and asks the library; a class then sets every member
+                     its launch reads, so nothing of an earlier launch (the `fit_` / `path_` / `mom_` / `shap_` members overlay
+                     one union) can reach the next one
+    torch_forward    the model's masked forward in plain torch ops: what every loop path runs on CPU tensors
+    CUS, LAUNCH_SECONDS   what the launch-size estimates of shapley.py and attribution.py share
+
+The order of a fused call: `_shape_args` (clears and queries; not None: the class's loop path), the class's own argument checks,
+`_bufs.take` / `_bufs.workspace`, `_fill`, the class's own members, the launches.  Private: the classes are the interface.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
+import torch.nn.functional as Fn
 
 from . import _lib
 
 MODEL_ATTRS = ("embedding_dim", "n_node_features", "n_convolutions", "readout_layers", "_n_classes", "conv1", "readout")
 SLOPE = 0.01                       # nn.LeakyReLU() default (reference model/gcn.py:21, :63)
+CUS = 256                          # compute units of an MI355X
+LAUNCH_SECONDS = 1.0               # what one launch should stay near (the machines are shared)
 
 # mode -> (the kernel's name in a reason, its node limit, the label of a failed query)
 _MODES = {_lib.HCG_EXPLAIN_GRAPHS: ("one-launch explain", 224, "hcg_explain (query)"),
@@ -47,14 +64,6 @@ def check_weights(tensors, device, message: str):
             raise _lib.HcgError(message)
 
 
-def model_weights(model, device, who: str):
-    """-> (conv weights, conv biases, readout weights, readout biases) of one model, checked for a launch on `device`"""
-    convs, lins = model_layers(model)
-    w = [c.lin.weight for c in convs], [c.bias for c in convs], [li.weight for li in lins], [li.bias for li in lins]
-    check_weights([t for ts in w for t in ts], device, f"{who}: the model's weights must be contiguous float32 on the batch's device")
-    return w
-
-
 def batch_reason(batch, F: int, what: str) -> Optional[str]:
     """Why `batch` cannot take a kernel of this family, from its host metadata; `what`: "model" or "models"."""
     if None in (getattr(batch, "max_nodes", None), getattr(batch, "max_edges", None)) or not getattr(batch, "edges_grouped", False):
@@ -67,11 +76,11 @@ def batch_reason(batch, F: int, what: str) -> Optional[str]:
 
 
 def query(a, mode: int, shape, batch, **extra) -> Optional[str]:
-    """Fill the shape fields of `a` from `shape` (`model_shape`) and `batch` (checked by `batch_reason`, or None) plus
+    """Clear `a`, fill its shape fields from `shape` (`model_shape`) and `batch` (checked by `batch_reason`, or None) plus
     `extra`, and ask the library: None when the kernel takes them (`a.workspace_bytes_needed` is set), else the limits."""
+    ctypes.memset(ctypes.addressof(a), 0, ctypes.sizeof(a))
     a.mode, a.flags = mode, _lib.HCG_EXPLAIN_QUERY
     a.F, a.D, a.C, a.n_conv, a.R = shape
-    a.N = a.E = a.B = a.max_nodes = a.max_edges = 0
     if batch is not None:
         a.N, a.E, a.B = int(batch.x.shape[0]), int(batch.edge_index.shape[1]), int(batch.num_graphs)
         a.max_nodes, a.max_edges = int(batch.max_nodes), int(batch.max_edges)
@@ -94,14 +103,148 @@ def batch_x(batch, *more):
     return batch.x
 
 
-def fill_graph(a, x, plan):
-    p = _lib.ptr
-    a.x, a.edge_index, a.graph_ptr, a.edge_ptr = p(x), p(plan.edge_index), p(plan.graph_ptr), p(plan.edge_ptr)
-    a.status = p(plan.status)
+class Pool(dict):
+    """name -> flat tensor.  A buffer is as large as the largest request seen for its name (at least 1 element) and is
+    replaced only by a larger request or another device; new storage is zero."""
+
+    def __init__(self):
+        super().__init__()
+        self._last = {}             # name -> (shape, device, view) of the last request: a warm call builds no tensor at all
+
+    def take(self, name: str, shape: tuple, dev, dtype=torch.float32) -> torch.Tensor:
+        """The front of buffer `name` as a contiguous tensor of `shape`"""
+        last = self._last.get(name)
+        if last is not None and last[0] == shape and last[1] == dev:
+            return last[2]
+        numel = math.prod(shape)
+        t = self.get(name)
+        if t is None or t.numel() < numel or t.device != dev:
+            t = self[name] = torch.zeros(max(numel, 1), dtype=dtype, device=dev)
+        view = t[:numel].view(shape)
+        self._last[name] = (shape, dev, view)
+        return view
+
+    def workspace(self, nbytes: int, dev) -> torch.Tensor:
+        """The whole byte buffer "ws", at least `nbytes` and 256 bytes large; its contents are not defined"""
+        t = self.get("ws")
+        if t is None or t.numel() < nbytes or t.device != dev:
+            t = self["ws"] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        return t
 
 
-def fill_weights(a, cW, cb, hW, hb):
-    """Lists of tensors in layer order (one model's, or the ensemble's stacked [M, ...] ones)."""
-    for slots, tensors in ((a.conv_W, cW), (a.conv_b, cb), (a.head_W, hW), (a.head_b, hb)):
+def fill_weights(a, weights, first: int = 0):
+    """`weights`: (conv weights, conv biases, readout weights, readout biases), lists of tensors in layer order: one model's,
+    or an ensemble's stacked [M, ...] ones, then read from model `first` on (the library has no "first model" field)."""
+    for slots, tensors in zip((a.conv_W, a.conv_b, a.head_W, a.head_b), weights):
         for i in range(len(slots)):
-            slots[i] = _lib.ptr(tensors[i]) if i < len(tensors) else None
+            slots[i] = tensors[i].data_ptr() + (4 * first * tensors[i].stride(0) if first else 0) if i < len(tensors) else None
+
+
+def front(view) -> Optional[int]:
+    """Device address of the pool buffer that `view` (`Pool.take`) is the front of; None for None.  An empty view has no
+    address of its own: the library still gets its buffer's, never NULL."""
+    return None if view is None else view.data_ptr() or view.untyped_storage().data_ptr()
+
+
+class Frozen:
+    """What the six classes share.  A subclass names its kernel (`KERNEL`), itself (`NAME`, for messages), says "model" or
+    "models" in a reason (`WHAT`) and whether a CPU batch is refused before anything else of it is read (`REFUSES_CPU`), and
+    provides `_model_reason()`, `_shape()` (`model_shape`'s tuple) and `_planner()` (the model whose plan cache serves the batch)."""
+    KERNEL: int = -1
+    NAME = ""
+    WHAT = "model"
+    REFUSES_CPU = True
+
+    def __init__(self):
+        self.last_path: Optional[str] = None
+        self._args = _lib.ExplainArgs()
+        self._bufs = Pool()
+
+    # ------------------------------------------------------------------ support check (host only, no sync)
+    def _shape_args(self, a, batch, **extra) -> Optional[str]:
+        why = self._model_reason()
+        shape = None if why else self._shape()
+        if why is None and batch is not None:
+            why = "the batch is on the CPU" if self.REFUSES_CPU and not batch.x.is_cuda else batch_reason(batch, shape[0], self.WHAT)
+        return why or query(a, self.KERNEL, shape, batch, **extra)
+
+    def reason(self, batch=None) -> Optional[str]:
+        """None when the model(s) (and `batch`) take the kernel, else why not.  Host metadata only."""
+        return self._shape_args(_lib.ExplainArgs(), batch)
+
+    def lds_bytes(self, batch) -> Optional[int]:
+        """Dynamic LDS of one workgroup of the kernel for this batch, as the library's query reports it (the fit, the
+        integrated-gradients and the Shapley kernel do); None when the batch does not take the kernel."""
+        a = _lib.ExplainArgs()
+        return int(a.lds_bytes) if self._shape_args(a, batch) is None else None
+
+    def _class(self, class_index) -> int:
+        C = self._shape()[2]
+        if not 0 <= int(class_index) < C:
+            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
+        return int(class_index)
+
+    # ------------------------------------------------------------------ what every launch sets
+    def _fill(self, a, flags: int, batch, x, weights, ws=None):
+        """The launch's flags, the graph, the slope, the weights (`fill_weights`; None: the caller fills them, chunk by
+        chunk) and the workspace `ws`, if it has one."""
+        p = _lib.ptr
+        plan = self._planner()._plan_for(batch, x, batch.edge_index, batch.batch, None)
+        a.flags, a.slope = flags, SLOPE
+        a.x, a.edge_index, a.graph_ptr, a.edge_ptr = p(x), p(plan.edge_index), p(plan.graph_ptr), p(plan.edge_ptr)
+        a.status = p(plan.status)
+        if weights is not None:
+            fill_weights(a, weights)
+        if ws is not None:
+            a.workspace, a.workspace_bytes = p(ws), ws.numel()
+
+
+class FrozenModel(Frozen):
+    def __init__(self, model: torch.nn.Module):
+        super().__init__()
+        self.model = model
+
+    def _model_reason(self):
+        return model_reason(self.model)
+
+    def _shape(self):
+        return model_shape(self.model)
+
+    def _planner(self):
+        return self.model
+
+    def _weights(self, device):
+        """-> (conv weights, conv biases, readout weights, readout biases), checked for a launch on `device`"""
+        convs, lins = model_layers(self.model)
+        w = [c.lin.weight for c in convs], [c.bias for c in convs], [li.weight for li in lins], [li.bias for li in lins]
+        check_weights([t for ts in w for t in ts], device, f"{self.NAME}: the model's weights must be contiguous float32 on the batch's device")
+        return w
+
+
+def torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):
+    """The model's masked forward in plain torch ops, for CPU tensors (the package's layers are HIP kernels and take GPU
+    tensors only).  The loop paths use it when the batch lives on the CPU; nothing on a GPU ever runs it."""
+    convs, lins = model_layers(model)
+    N = x.shape[0]
+    src, dst = edge_index[0], edge_index[1]
+    keep = src != dst                                   # an explicit (i, i) edge is part of the unit self loop
+    deg = torch.ones(N, dtype=x.dtype).scatter_add_(0, dst[keep], torch.ones(int(keep.sum()), dtype=x.dtype))
+    dinv = deg.pow(-0.5)
+    coef = (dinv[src] * dinv[dst] * edge_mask)[keep].unsqueeze(1)
+    s, d = src[keep], dst[keep]
+    h = x
+    for c in convs:
+        t = Fn.linear(h, c.lin.weight)
+        y = (dinv * dinv).unsqueeze(1) * t
+        # (index_select, not t[s]: the same values forward; its backward adds the rows serially in index order, where
+        # the backward of t[s] adds them with atomics from several threads -- a gradient that differs in its last bits run to run)
+        y = y.index_add(0, d, coef * t.index_select(0, s))
+        h = Fn.leaky_relu(y + c.bias, SLOPE)
+    idx = batch_vec.unsqueeze(1).expand_as(h)
+    mx = h.new_zeros(B, h.shape[1]).scatter_reduce(0, idx, h, reduce="amax", include_self=False)
+    cnt = torch.bincount(batch_vec, minlength=B).clamp_min(1).to(h.dtype).unsqueeze(1)
+    z = torch.cat([mx, h.new_zeros(B, h.shape[1]).index_add(0, batch_vec, h) / cnt], 1)
+    for li in lins[:-1]:
+        z = Fn.leaky_relu(Fn.linear(z, li.weight, li.bias), SLOPE)
+    z = Fn.linear(z, lins[-1].weight, lins[-1].bias)
+    return z

@@ -14,15 +14,15 @@ artefact of the reference pins these values: parity is against an fp64 restateme
 from __future__ import annotations
 
 import ctypes
-from typing import List, NamedTuple, Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _frozen, _lib
-from .ensemble import stack_weights, weight_names
+from ._frozen import CUS, LAUNCH_SECONDS
+from .ensemble import FrozenEnsemble
 from .explain import ExplainStep
-from .shapley import CUS, LAUNCH_SECONDS
 
 METHODS = ("gausslegendre", "riemann_middle", "gradient")
 ENDPOINT_METHODS = ("riemann_left", "riemann_right", "riemann_trapezoid")
@@ -66,7 +66,50 @@ def quadrature(method: str, n_steps: int):
     return torch.from_numpy(np.ascontiguousarray(alpha)).to(torch.float32), torch.from_numpy(np.ascontiguousarray(weight)).to(torch.float32)
 
 
-class IntegratedGradients:
+class _Path:
+    """The path of `IntegratedGradients` and `EnsembleAttribution`: method, step count and `saliency` with their checks, the
+    quadrature points on the device, the default split of the steps into launches, and the launch's `path_` members."""
+
+    def _init_path(self, n_steps: int, method: str, saliency: bool):
+        if saliency and method != "gradient":
+            raise ValueError(f"saliency=True is the absolute value of method='gradient'; got method {method!r}")
+        if method == "gradient":
+            n_steps = 1
+        quadrature(method, n_steps)                         # (refuses the method or the step count)
+        self.n_steps, self.method, self.saliency = int(n_steps), method, bool(saliency)
+        self.last_class_index: Optional[int] = None
+        self._points = {}           # (n_steps, device) -> (alpha, weight) on the device
+
+    @staticmethod
+    def default_steps_per_launch(n_steps: int, num_graphs: int) -> int:
+        """Steps of one launch: as many as keep its run time near `LAUNCH_SECONDS`, at least 1.  The device runs
+        the graphs in ceil(num_graphs / CUS) rounds of one workgroup per compute unit (the occupancy at the shape limits'
+        LDS), each step of a round taking `STEP_SECONDS`.  `STEP_SECONDS` is an ESTIMATE: `ExplainFit` -- the same forward
+        and backward per epoch -- takes about 90 us per epoch and workgroup on real-size graphs and two conv layers (README:
+        144.8 ms for 100 epochs of 4096 graphs), extrapolated to 224 nodes and four layers; nobody has timed a launch at the
+        limit shapes."""
+        rounds = max(1, -(-int(num_graphs) // CUS))
+        return max(1, min(int(n_steps), int(LAUNCH_SECONDS / (rounds * STEP_SECONDS))))
+
+    def _steps(self, n_steps) -> int:
+        n = self.n_steps if n_steps is None else int(n_steps)
+        if self.method == "gradient" and n != 1:
+            raise ValueError(f"method 'gradient' is one step; got n_steps = {n_steps}")
+        if n < 1:
+            raise ValueError(f"n_steps must be at least 1; got {n_steps}")
+        return n
+
+    def _fill_path(self, a, n: int, cls: int, dev):
+        key = (n, str(dev))
+        if key not in self._points:
+            alpha, weight = quadrature(self.method, n)
+            self._points[key] = (alpha.to(dev), weight.to(dev))
+        alpha, weight = self._points[key]
+        a.path_alpha, a.path_weight = _lib.ptr(alpha), _lib.ptr(weight)
+        a.path_steps, a.path_class_index = n, cls
+
+
+class IntegratedGradients(_Path, _frozen.FrozenModel):
     """Integrated gradients of a frozen model for a whole batch of graphs, one launch per call.
 
         ig = IntegratedGradients(model, n_steps=50, method="gausslegendre")
@@ -102,85 +145,12 @@ class IntegratedGradients:
     plain torch autograd on CPU tensors, accumulated in float32 in step order.  `last_path` says which one ran ("fused" /
     "loop")."""
 
+    KERNEL, NAME = _lib.HCG_EXPLAIN_INTEGRATED, "IntegratedGradients"
+
     def __init__(self, model: torch.nn.Module, n_steps: int = 50, method: str = "gausslegendre", saliency: bool = False):
-        if saliency and method != "gradient":
-            raise ValueError(f"saliency=True is the absolute value of method='gradient'; got method {method!r}")
-        if method == "gradient":
-            n_steps = 1
-        quadrature(method, n_steps)                         # (refuses the method or the step count)
-        self.model, self.n_steps, self.method, self.saliency = model, int(n_steps), method, bool(saliency)
-        self.last_path: Optional[str] = None
-        self.last_class_index: Optional[int] = None
-        self._cap = None            # (N, E, B, workspace bytes) capacity of the buffers
-        self._bufs = None
-        self._points = {}           # (n_steps, device) -> (alpha, weight) on the device
-        self._args = _lib.ExplainArgs()
+        _frozen.FrozenModel.__init__(self, model)
+        self._init_path(n_steps, method, saliency)
         self._step = ExplainStep(model, apply_sigmoid=False)
-
-    # ------------------------------------------------------------------ support check (host only, no sync)
-    def _shape_args(self, a, batch) -> Optional[str]:
-        m = self.model
-        why = _frozen.model_reason(m)
-        if why is None and batch is not None:
-            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, int(m.n_node_features), "model")
-        return why or _frozen.query(a, _lib.HCG_EXPLAIN_INTEGRATED, _frozen.model_shape(m), batch, edge_mask=None, node_mask=None,
-                                    target=None, dout=None, dx=None)
-
-    def reason(self, batch=None) -> Optional[str]:
-        """None when this model (and `batch`) takes the one-launch kernel, else why not.  Host metadata only."""
-        return self._shape_args(_lib.ExplainArgs(), batch)
-
-    def lds_bytes(self, batch) -> Optional[int]:
-        """Dynamic LDS of one workgroup of the kernel for this batch, as the library's query reports it; None when the
-        batch does not take the kernel."""
-        a = _lib.ExplainArgs()
-        return int(a.lds_bytes) if self._shape_args(a, batch) is None else None
-
-    @staticmethod
-    def default_steps_per_launch(n_steps: int, num_graphs: int) -> int:
-        """Steps of one launch: as many as keep its run time near `shapley.LAUNCH_SECONDS`, at least 1.  The device runs
-        the graphs in ceil(num_graphs / CUS) rounds of one workgroup per compute unit (the occupancy at the shape limits'
-        LDS), each step of a round taking `STEP_SECONDS`.  `STEP_SECONDS` is an ESTIMATE: `ExplainFit` -- the same forward
-        and backward per epoch -- takes about 90 us per epoch and workgroup on real-size graphs and two conv layers (README:
-        144.8 ms for 100 epochs of 4096 graphs), extrapolated to 224 nodes and four layers; nobody has timed a launch at the
-        limit shapes."""
-        rounds = max(1, -(-int(num_graphs) // CUS))
-        return max(1, min(int(n_steps), int(LAUNCH_SECONDS / (rounds * STEP_SECONDS))))
-
-    # ------------------------------------------------------------------ arguments
-    def _steps(self, n_steps) -> int:
-        n = self.n_steps if n_steps is None else int(n_steps)
-        if self.method == "gradient" and n != 1:
-            raise ValueError(f"method 'gradient' is one step; got n_steps = {n_steps}")
-        if n < 1:
-            raise ValueError(f"n_steps must be at least 1; got {n_steps}")
-        return n
-
-    def _class(self, class_index) -> int:
-        C = int(self.model._n_classes)
-        if not 0 <= int(class_index) < C:
-            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
-        return int(class_index)
-
-    def _quadrature(self, n: int, dev):
-        key = (n, str(dev))
-        if key not in self._points:
-            alpha, weight = quadrature(self.method, n)
-            self._points[key] = (alpha.to(dev), weight.to(dev))
-        return self._points[key]
-
-    # ------------------------------------------------------------------ buffers
-    def _buffers(self, N, E, B, F, C, ws_bytes, dev):
-        cap = self._cap
-        need = (N, E, B, ws_bytes)
-        if cap is None or any(n > c for n, c in zip(need, cap)) or self._bufs["full"].device != dev:
-            cap = tuple(max(n, c) for n, c in zip(need, cap or (0,) * 4))
-            f32 = dict(dtype=torch.float32, device=dev)
-            self._bufs = dict(node=torch.zeros(max(cap[0], 1), F, **f32), edge=torch.zeros(max(cap[1], 1), **f32),
-                              full=torch.zeros(max(cap[2], 1), C, **f32), base=torch.zeros(max(cap[2], 1), C, **f32),
-                              ws=torch.empty(max(cap[3], 256), dtype=torch.uint8, device=dev))
-            self._cap = cap
-        return self._bufs
 
     # ------------------------------------------------------------------ the call
     def __call__(self, batch, class_index: int = 0, n_steps: Optional[int] = None,
@@ -193,33 +163,24 @@ class IntegratedGradients:
         why = self._shape_args(a, batch)
         if why is not None:
             return self.loop(batch, cls, n)
-        m = self.model
         x = _frozen.batch_x(batch)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         per = self.default_steps_per_launch(n, B) if steps_per_launch is None else min(int(steps_per_launch), n)
-        alpha, weight = self._quadrature(n, x.device)
-        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        bufs = self._buffers(N, E, B, F, C, int(a.workspace_bytes_needed), x.device)
-        p = _lib.ptr
-        a.flags = 0
-        _frozen.fill_graph(a, x, plan)
-        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "IntegratedGradients"))
-        a.out = None
-        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
-        a.slope = _frozen.SLOPE
-        a.path_alpha, a.path_weight = p(alpha), p(weight)
-        a.path_node_attr, a.path_edge_attr = p(bufs["node"]), p(bufs["edge"])
-        a.path_out_full, a.path_out_base = p(bufs["full"]), p(bufs["base"])
-        a.path_steps, a.path_class_index = n, cls
+        take, front, dev = self._bufs.take, _frozen.front, x.device
+        node, edge = take("node", (N, F), dev), take("edge", (E,), dev)
+        full, base = take("full", (B, C), dev), take("base", (B, C), dev)
+        self._fill(a, 0, batch, x, self._weights(dev), self._bufs.workspace(int(a.workspace_bytes_needed), dev))
+        self._fill_path(a, n, cls, dev)
+        a.path_node_attr, a.path_edge_attr, a.path_out_full, a.path_out_base = front(node), front(edge), front(full), front(base)
         lib, stream = _lib.load(), _lib.stream_ptr()
         for first in range(0, n, per):
             a.path_step_first, a.path_step_count = first, min(per, n - first)
             _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (integrated)")
         if self.saliency:
-            bufs["node"].abs_()
-            bufs["edge"].abs_()
+            node.abs_()
+            edge.abs_()
         self.last_path, self.last_class_index = "fused", cls
-        return IntegratedGradientsResult(bufs["node"][:N], bufs["edge"][:E], bufs["full"][:B], bufs["base"][:B])
+        return IntegratedGradientsResult(node, edge, full, base)
 
     # ------------------------------------------------------------------ the loop path (any shape, CPU tensors)
     def _grads(self, batch, alpha: float, onehot):
@@ -231,11 +192,10 @@ class IntegratedGradients:
             nm = torch.full((N, F), alpha, dtype=torch.float32, device=dev)
             r = self._step(batch, em, nm, dout=onehot)
             return r.d_node_mask, r.d_edge_mask
-        from .shapley import _torch_forward                 # (the package's layers take GPU tensors only)
         em = torch.full((E,), alpha, dtype=torch.float32).requires_grad_(True)
         nm = torch.full((N, F), alpha, dtype=torch.float32).requires_grad_(True)
         with torch.enable_grad():
-            out = _torch_forward(self.model, batch.x.detach() * nm, batch.edge_index, batch.batch, B, em).reshape(B, -1)
+            out = _frozen.torch_forward(self.model, batch.x.detach() * nm, batch.edge_index, batch.batch, B, em).reshape(B, -1)
             d_n, d_e = torch.autograd.grad((out * onehot).sum(), [nm, em])     # (no parameter's .grad is touched)
         return d_n, d_e
 
@@ -247,8 +207,7 @@ class IntegratedGradients:
         with torch.no_grad():
             if batch.x.is_cuda:
                 return self._step(batch, em, nm).out.reshape(B, -1).clone()
-            from .shapley import _torch_forward
-            return _torch_forward(self.model, batch.x * nm, batch.edge_index, batch.batch, B, em).reshape(B, -1)
+            return _frozen.torch_forward(self.model, batch.x * nm, batch.edge_index, batch.batch, B, em).reshape(B, -1)
 
     def loop(self, batch, class_index: int = 0, n_steps: Optional[int] = None) -> IntegratedGradientsResult:
         """One `ExplainStep` call per quadrature point (see the class docstring), whatever `reason(batch)` says."""
@@ -308,7 +267,7 @@ class EnsembleAttributionResult(NamedTuple):
     edge_attr: Optional[torch.Tensor]   # [M, E]
 
 
-class EnsembleAttribution:
+class EnsembleAttribution(_Path, FrozenEnsemble):
     """Integrated gradients of M frozen models of one architecture for a whole batch of graphs: every (graph, model) pair is
     one workgroup of ONE launch, and the mean and the standard deviation over the models are taken on the device.
 
@@ -344,58 +303,16 @@ class EnsembleAttribution:
     model) the same call runs `IntegratedGradients(model_k).loop` per model -- on the models' CURRENT weights -- and takes
     the moments with torch ops (`mean(0)`, `std(0, unbiased=False)`); `last_path` says which one ran ("fused" / "loop")."""
 
+    KERNEL, NAME = _lib.HCG_EXPLAIN_INTEGRATED, "EnsembleAttribution"
+
     def __init__(self, models: Sequence[torch.nn.Module], n_steps: int = 50, method: str = "gausslegendre", saliency: bool = False):
-        self.models: List[torch.nn.Module] = list(models)
-        if not self.models:
-            raise ValueError("EnsembleAttribution needs at least one model")
-        for k, m in enumerate(self.models):
-            if any(not hasattr(m, a) for a in _frozen.MODEL_ATTRS):
-                raise ValueError(f"model {k} is not a hcatgnet_amd GCN model")
-        sig = [_frozen.model_shape(m) for m in self.models]
-        for k, s in enumerate(sig):
-            if s != sig[0]:
-                raise ValueError(f"model {k} has (features, embedding_dim, classes, conv layers, readout layers) = {s}, "
-                                 f"model 0 has {sig[0]}")
-        self.F, self.D, self.C, self.n_conv, self.R = sig[0]
-        # (method, step count and saliency: `IntegratedGradients`' own checks; these are also the loop path's workers)
-        self._singles = [IntegratedGradients(m, n_steps, method, saliency) for m in self.models]
-        self.n_steps, self.method, self.saliency = self._singles[0].n_steps, method, bool(saliency)
-        self.stacked = stack_weights([m.state_dict() for m in self.models])
-        self.last_path: Optional[str] = None
-        self.last_class_index: Optional[int] = None
-        self._bufs = {}
-        self._points = {}
-        self._args = _lib.ExplainArgs()
-        self._mom = _lib.ExplainArgs()
+        FrozenEnsemble.__init__(self, models)
+        self._init_path(n_steps, method, saliency)
+        self._singles = [IntegratedGradients(m, n_steps, method, saliency) for m in self.models]       # the loop path's workers
 
-    @property
-    def n_models(self) -> int:
-        return len(self.models)
-
-    def refresh(self):
-        """Re-stack the models' current weights into the same buffers (in place: pointers stay valid)."""
-        with torch.no_grad():
-            for k, m in enumerate(self.models):
-                for name, t in m.state_dict().items():
-                    if name in self.stacked:
-                        self.stacked[name][k].copy_(t.detach())
-        return self
-
-    # ------------------------------------------------------------------ support check (host only, no sync)
     def _shape_args(self, a, batch) -> Optional[str]:
         """None when the kernel takes these models and `batch`; `a` then holds the shapes and the ONE-model workspace bytes"""
-        if not all(bool(getattr(m, "use_fused", True)) for m in self.models):
-            return "fused kernels disabled on a model"
-        if batch is not None:
-            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, self.F, "models")
-            if why is not None:
-                return why
-        return _frozen.query(a, _lib.HCG_EXPLAIN_INTEGRATED, (self.F, self.D, self.C, self.n_conv, self.R), batch, edge_mask=None,
-                             node_mask=None, target=None, dout=None, dx=None, n_models=1)
-
-    def reason(self, batch=None) -> Optional[str]:
-        """None when these models (and `batch`) take the one-launch kernel, else why not.  Host metadata only."""
-        return self._shape_args(_lib.ExplainArgs(), batch)
+        return super()._shape_args(a, batch, n_models=1)
 
     @staticmethod
     def default_models_per_launch(n_models: int, workspace_bytes: int, entries: int, budget: int = LAUNCH_BUDGET_BYTES) -> int:
@@ -405,28 +322,11 @@ class EnsembleAttribution:
         per = int(workspace_bytes) + 4 * int(entries)
         return max(1, min(int(n_models), int(budget) // max(per, 1)))
 
-    # ------------------------------------------------------------------ buffers
-    def _buffer(self, name: str, numel: int, dev, dtype=torch.float32):
-        """A flat buffer of at least `numel` elements, grown to the largest request and kept"""
-        t = self._bufs.get(name)
-        if t is None or t.numel() < numel or t.device != dev:
-            t = torch.zeros(max(numel, 1), dtype=dtype, device=dev)
-            self._bufs[name] = t
-        return t
-
-    def _quadrature(self, n: int, dev):
-        key = (n, str(dev))
-        if key not in self._points:
-            alpha, weight = quadrature(self.method, n)
-            self._points[key] = (alpha.to(dev), weight.to(dev))
-        return self._points[key]
-
     # ------------------------------------------------------------------ the call
     def __call__(self, batch, class_index: int = 0, per_model: bool = False, models_per_launch: Optional[int] = None,
                  steps_per_launch: Optional[int] = None, n_steps: Optional[int] = None) -> EnsembleAttributionResult:
-        one = self._singles[0]
-        n = one._steps(n_steps)
-        cls = one._class(class_index)
+        n = self._steps(n_steps)
+        cls = self._class(class_index)
         for name, v in (("models_per_launch", models_per_launch), ("steps_per_launch", steps_per_launch)):
             if v is not None and int(v) < 1:
                 raise ValueError(f"{name} must be at least 1; got {v}")
@@ -439,60 +339,44 @@ class EnsembleAttribution:
         M = len(self.models)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         ws_one = int(a.workspace_bytes_needed)
-        S = self.stacked
-        _frozen.check_weights(S.values(), dev, "EnsembleAttribution: the stacked weights must be on the batch's device "
-                              "(construct the ensemble from models on that device)")
+        weights = self._weights(dev)
         Ml = self.default_models_per_launch(M, ws_one, N * F + E) if models_per_launch is None else min(int(models_per_launch), M)
-        alpha, weight = self._quadrature(n, dev)
-        plan = self.models[0]._plan_for(batch, x, batch.edge_index, batch.batch, None)
         rows = M if per_model else Ml
-        node = self._buffer("node", rows * N * F, dev)
-        edge = self._buffer("edge", rows * E, dev)
-        full, base = self._buffer("full", M * B * C, dev), self._buffer("base", M * B * C, dev)
-        ws = self._buffer("ws", Ml * ws_one, dev, torch.uint8)
-        mom = {k: self._buffer(k, N * F if k.startswith("node") else E, dev)
+        take, front = self._bufs.take, _frozen.front
+        node, edge = take("node", (rows, N, F), dev), take("edge", (rows, E), dev)
+        full, base = take("full", (M, B, C), dev), take("base", (M, B, C), dev)
+        mom = {k: take(k, (N, F) if k.startswith("node") else (E,), dev)
                for k in ("node_mean", "node_m2", "node_std", "edge_mean", "edge_m2", "edge_std")}
-        p = _lib.ptr
-        a.flags = 0
-        _frozen.fill_graph(a, x, plan)
-        a.out = None
-        a.workspace, a.workspace_bytes = p(ws), ws.numel()
-        a.slope = _frozen.SLOPE
-        a.path_alpha, a.path_weight = p(alpha), p(weight)
-        a.path_steps, a.path_class_index = n, cls
-        q = self._mom
-        q.mode, q.flags = _lib.HCG_EXPLAIN_MOMENTS, 0
-        q.mom_mean0, q.mom_m20, q.mom_std0, q.mom_len0 = p(mom["node_mean"]), p(mom["node_m2"]), p(mom["node_std"]), N * F
-        q.mom_mean1, q.mom_m21, q.mom_std1, q.mom_len1 = p(mom["edge_mean"]), p(mom["edge_m2"]), p(mom["edge_std"]), E
+        self._fill(a, 0, batch, x, None, self._bufs.workspace(Ml * ws_one, dev))
+        self._fill_path(a, n, cls, dev)
+        q = _lib.ExplainArgs()                          # the moments launches' block
+        q.mode = _lib.HCG_EXPLAIN_MOMENTS
+        q.mom_mean0, q.mom_m20, q.mom_std0, q.mom_len0 = front(mom["node_mean"]), front(mom["node_m2"]), front(mom["node_std"]), N * F
+        q.mom_mean1, q.mom_m21, q.mom_std1, q.mom_len1 = front(mom["edge_mean"]), front(mom["edge_m2"]), front(mom["edge_std"]), E
         q.mom_total = M
-        names = weight_names(self.n_conv, self.R)
         lib, stream = _lib.load(), _lib.stream_ptr()
         for m0 in range(0, M, Ml):
             count = min(Ml, M - m0)
             row0 = m0 if per_model else 0               # (per_model=False: every chunk reuses the one chunk's rows)
-            # pointers already offset to the chunk's first model: the library has no "first model" field
-            for slots, group in zip((a.conv_W, a.conv_b, a.head_W, a.head_b), names):
-                for i in range(len(slots)):
-                    slots[i] = S[group[i]].data_ptr() + 4 * m0 * S[group[i]].stride(0) if i < len(group) else None
+            _frozen.fill_weights(a, weights, m0)
             a.n_models = count
-            a.path_node_attr = node.data_ptr() + 4 * row0 * N * F
-            a.path_edge_attr = edge.data_ptr() + 4 * row0 * E
-            a.path_out_full, a.path_out_base = full.data_ptr() + 4 * m0 * B * C, base.data_ptr() + 4 * m0 * B * C
-            per = one.default_steps_per_launch(n, B * count) if steps_per_launch is None else min(int(steps_per_launch), n)
+            a.path_node_attr = front(node) + 4 * row0 * N * F
+            a.path_edge_attr = front(edge) + 4 * row0 * E
+            a.path_out_full, a.path_out_base = front(full) + 4 * m0 * B * C, front(base) + 4 * m0 * B * C
+            per = self.default_steps_per_launch(n, B * count) if steps_per_launch is None else min(int(steps_per_launch), n)
             for first in range(0, n, per):
                 a.path_step_first, a.path_step_count = first, min(per, n - first)
                 _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (integrated, ensemble)")
             if self.saliency:
-                node[row0 * N * F:(row0 + count) * N * F].abs_()
-                edge[row0 * E:(row0 + count) * E].abs_()
+                node[row0:row0 + count].abs_()
+                edge[row0:row0 + count].abs_()
             q.mom_values0, q.mom_values1 = a.path_node_attr, a.path_edge_attr
             q.mom_first, q.mom_count = m0, count
             _lib.check(lib.hcg_explain(ctypes.addressof(q), stream), "hcg_explain (moments)")
         self.last_path, self.last_class_index = "fused", cls
         return EnsembleAttributionResult(
-            mom["node_mean"][:N * F].view(N, F), mom["node_std"][:N * F].view(N, F), mom["edge_mean"][:E], mom["edge_std"][:E],
-            full[:M * B * C].view(M, B, C), base[:M * B * C].view(M, B, C),
-            node[:M * N * F].view(M, N, F) if per_model else None, edge[:M * E].view(M, E) if per_model else None)
+            mom["node_mean"], mom["node_std"], mom["edge_mean"], mom["edge_std"], full, base,
+            node if per_model else None, edge if per_model else None)
 
     # ------------------------------------------------------------------ the loop path (any shape, CPU tensors)
     def loop(self, batch, class_index: int = 0, per_model: bool = False, n_steps: Optional[int] = None) -> EnsembleAttributionResult:

@@ -60,6 +60,57 @@ def weight_names(n_conv: int, n_read: int):
     return cw, cb, hw, hb
 
 
+class FrozenEnsemble(_frozen.Frozen):
+    """M models of one architecture, their weights stacked once into contiguous [M, ...] buffers (`stacked`: a snapshot):
+    what `EnsemblePredict` and `attribution.EnsembleAttribution` share."""
+    WHAT = "models"
+
+    def __init__(self, models: Sequence[torch.nn.Module]):
+        super().__init__()
+        self.models: List[torch.nn.Module] = list(models)
+        if not self.models:
+            raise ValueError(f"{self.NAME} needs at least one model")
+        for k, m in enumerate(self.models):
+            if any(not hasattr(m, a) for a in _frozen.MODEL_ATTRS):
+                raise ValueError(f"model {k} is not a hcatgnet_amd GCN model")
+        sig = [_frozen.model_shape(m) for m in self.models]
+        for k, s in enumerate(sig):
+            if s != sig[0]:
+                raise ValueError(f"model {k} has (features, embedding_dim, classes, conv layers, readout layers) = {s}, "
+                                 f"model 0 has {sig[0]}")
+        self.F, self.D, self.C, self.n_conv, self.R = sig[0]
+        self.stacked = stack_weights([m.state_dict() for m in self.models])
+
+    @property
+    def n_models(self) -> int:
+        return len(self.models)
+
+    def refresh(self):
+        """Re-stack the models' current weights into the same buffers (in place: pointers, and captured calls, stay valid)."""
+        with torch.no_grad():
+            for k, m in enumerate(self.models):
+                for name, t in m.state_dict().items():
+                    if name in self.stacked:
+                        self.stacked[name][k].copy_(t.detach())
+        return self
+
+    def _model_reason(self):
+        return None if all(bool(getattr(m, "use_fused", True)) for m in self.models) else "fused kernels disabled on a model"
+
+    def _shape(self):
+        return self.F, self.D, self.C, self.n_conv, self.R
+
+    def _planner(self):
+        return self.models[0]
+
+    def _weights(self, device):
+        """-> the stacked (conv weights, conv biases, readout weights, readout biases), checked for a launch on `device`"""
+        S = self.stacked
+        _frozen.check_weights(S.values(), device, f"{self.NAME}: the stacked weights must be on the batch's device "
+                              "(construct the ensemble from models on that device)")
+        return [[S[n] for n in names] for names in weight_names(self.n_conv, self.R)]
+
+
 class EnsembleResult(NamedTuple):
     out: torch.Tensor                 # [M, B, C]
     emb: Optional[torch.Tensor]       # [M, B, 2D] ([max, mean] pooling, max first); None unless asked for
@@ -67,7 +118,7 @@ class EnsembleResult(NamedTuple):
     std: Optional[torch.Tensor]       # [B, C] = out.std(0, unbiased=False)
 
 
-class EnsemblePredict:
+class EnsemblePredict(FrozenEnsemble):
     """Predictions of M frozen models for a whole batch of graphs, one launch per call.
 
         ens = EnsemblePredict(models, models_per_group=None)
@@ -89,71 +140,18 @@ class EnsemblePredict:
     outlive it).  When `reason(batch)` is not None the call runs `model_k(batch, True)` for every k -- on the models'
     CURRENT weights -- and returns the same fields; `last_path` says which one ran ("fused" / "loop")."""
 
+    KERNEL, NAME, REFUSES_CPU = _lib.HCG_EXPLAIN_ENSEMBLE, "EnsemblePredict", False
+
     def __init__(self, models: Sequence[torch.nn.Module], models_per_group: Optional[int] = None):
-        self.models: List[torch.nn.Module] = list(models)
-        if not self.models:
-            raise ValueError("EnsemblePredict needs at least one model")
-        for k, m in enumerate(self.models):
-            if any(not hasattr(m, a) for a in _frozen.MODEL_ATTRS):
-                raise ValueError(f"model {k} is not a hcatgnet_amd GCN model")
-        sig = [_frozen.model_shape(m) for m in self.models]
-        for k, s in enumerate(sig):
-            if s != sig[0]:
-                raise ValueError(f"model {k} has (features, embedding_dim, classes, conv layers, readout layers) = {s}, "
-                                 f"model 0 has {sig[0]}")
-        self.F, self.D, self.C, self.n_conv, self.R = sig[0]
+        super().__init__(models)
         if models_per_group is not None and not 1 <= int(models_per_group) <= len(self.models):
             raise ValueError(f"models_per_group must lie in 1 .. {len(self.models)}; got {models_per_group}")
         self.models_per_group = None if models_per_group is None else int(models_per_group)
-        self.stacked = stack_weights([m.state_dict() for m in self.models])
-        self.last_path: Optional[str] = None
-        self._cap = None            # (B,) capacity of the buffers
-        self._bufs = None
-        self._args = _lib.ExplainArgs()
 
-    @property
-    def n_models(self) -> int:
-        return len(self.models)
-
-    def refresh(self):
-        """Re-stack the models' current weights into the same buffers (in place: pointers, and captured calls, stay valid)."""
-        with torch.no_grad():
-            for k, m in enumerate(self.models):
-                for name, t in m.state_dict().items():
-                    if name in self.stacked:
-                        self.stacked[name][k].copy_(t.detach())
-        return self
-
-    # ------------------------------------------------------------------ support check (host only, no sync)
     def _shape_args(self, a, batch) -> Optional[str]:
-        if not all(bool(getattr(m, "use_fused", True)) for m in self.models):
-            return "fused kernels disabled on a model"
-        why = _frozen.batch_reason(batch, self.F, "models") if batch is not None else None
-        if why is not None:
-            return why
         M = len(self.models)
         mpg = self.models_per_group or (default_models_per_group(M, int(batch.num_graphs)) if batch is not None else 1)
-        return _frozen.query(a, _lib.HCG_EXPLAIN_ENSEMBLE, (self.F, self.D, self.C, self.n_conv, self.R), batch,
-                             n_models=M, models_per_group=mpg)
-
-    def reason(self, batch=None) -> Optional[str]:
-        """None when these models (and `batch`) take the one-launch kernel, else why not.  Host metadata only."""
-        return self._shape_args(_lib.ExplainArgs(), batch)
-
-    # ------------------------------------------------------------------ buffers
-    def _buffers(self, B, dev):
-        """Flat buffers of the largest batch seen; a call's [M, B, ...] results are contiguous views of their fronts."""
-        if self._cap is None or B > self._cap or self._bufs["out"].device != dev:
-            cap = max(B, self._cap or 0, 1)
-            M = len(self.models)
-            f32 = dict(dtype=torch.float32, device=dev)
-            self._bufs = dict(out=torch.zeros(M * cap * self.C, **f32), emb=torch.zeros(M * cap * 2 * self.D, **f32),
-                              mean=torch.zeros(cap * self.C, **f32), std=torch.zeros(cap * self.C, **f32))
-            self._cap = cap
-        M, C, D2 = len(self.models), self.C, 2 * self.D
-        b = self._bufs
-        return (b["out"][:M * B * C].view(M, B, C), b["emb"][:M * B * D2].view(M, B, D2), b["mean"][:B * C].view(B, C),
-                b["std"][:B * C].view(B, C))
+        return super()._shape_args(a, batch, n_models=M, models_per_group=mpg)
 
     # ------------------------------------------------------------------ the call
     def __call__(self, batch, return_emb: bool = False, stats: bool = True) -> EnsembleResult:
@@ -162,25 +160,20 @@ class EnsemblePredict:
         if why is not None:
             return self._loop(batch, return_emb, stats)
         x = _frozen.batch_x(batch)
-        B = a.B
-        S = self.stacked
-        _frozen.check_weights(S.values(), x.device, "EnsemblePredict: the stacked weights must be on the batch's device "
-                              "(construct the ensemble from models on that device)")
-        plan = self.models[0]._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        out, emb, mean, std = self._buffers(B, x.device)
-        p = _lib.ptr
-        a.flags = 0
-        _frozen.fill_graph(a, x, plan)
-        _frozen.fill_weights(a, *([S[n] for n in names] for names in weight_names(self.n_conv, self.R)))
-        a.edge_mask = a.node_mask = a.target = a.dout = None
-        a.out, a.emb = p(out), (p(emb) if return_emb else None)
-        a.slope = _frozen.SLOPE
+        M, B, C, D2 = len(self.models), a.B, self.C, 2 * self.D
+        take, dev = self._bufs.take, x.device
+        out = take("out", (M, B, C), dev)
+        emb = take("emb", (M, B, D2), dev) if return_emb else None
+        self._fill(a, 0, batch, x, self._weights(dev))
+        a.out, a.emb = _frozen.front(out), _frozen.front(emb)
         _lib.check(_lib.load().hcg_explain(ctypes.addressof(a), _lib.stream_ptr()), "hcg_explain (ensemble)")
         self.last_path = "fused"
+        mean = std = None
         if stats:
+            mean, std = take("mean", (B, C), dev), take("std", (B, C), dev)
             torch.mean(out, dim=0, out=mean)
             torch.std(out, dim=0, unbiased=False, out=std)
-        return EnsembleResult(out, emb if return_emb else None, mean if stats else None, std if stats else None)
+        return EnsembleResult(out, emb, mean, std)
 
     # ------------------------------------------------------------------ the existing path (any shape), model by model
     def _loop(self, batch, return_emb, stats) -> EnsembleResult:

@@ -59,7 +59,7 @@ class ExplainResult(NamedTuple):
     dx: Optional[torch.Tensor]              # [N, F] = dJ/dx; None unless asked for
 
 
-class ExplainStep:
+class ExplainStep(_frozen.FrozenModel):
     """Outputs and mask gradients of a frozen model for a whole batch of graphs, one launch per call.
 
         step = ExplainStep(model, apply_sigmoid=True)
@@ -87,38 +87,11 @@ class ExplainStep:
     `torch.autograd.grad` with respect to the masks and x only, `clear_masks`) and returns the same fields;
     `last_path` says which one ran ("fused" / "autograd")."""
 
+    KERNEL, NAME, REFUSES_CPU = _lib.HCG_EXPLAIN_GRAPHS, "ExplainStep", False
+
     def __init__(self, model: torch.nn.Module, apply_sigmoid: bool = True):
-        self.model, self.apply_sigmoid = model, bool(apply_sigmoid)
-        self.last_path: Optional[str] = None
-        self._cap = None            # (N, E, B) capacity of the buffers
-        self._bufs = None
-        self._args = _lib.ExplainArgs()
-
-    # ------------------------------------------------------------------ support check (host only, no sync)
-    def _shape_args(self, a, batch) -> Optional[str]:
-        m = self.model
-        why = _frozen.model_reason(m)
-        if why is None and batch is not None:
-            why = _frozen.batch_reason(batch, int(m.n_node_features), "model")
-        return why or _frozen.query(a, _lib.HCG_EXPLAIN_GRAPHS, _frozen.model_shape(m), batch)
-
-    def reason(self, batch=None) -> Optional[str]:
-        """None when this model (and `batch`) takes the one-launch kernel, else why not.  Host metadata only."""
-        return self._shape_args(_lib.ExplainArgs(), batch)
-
-    # ------------------------------------------------------------------ buffers
-    def _buffers(self, N, E, B, F, C, ws_bytes, dev):
-        cap = self._cap
-        if cap is None or N > cap[0] or E > cap[1] or B > cap[2] or ws_bytes > cap[3] or self._bufs["out"].device != dev:
-            cap = (max(N, cap[0] if cap else 0), max(E, cap[1] if cap else 0), max(B, cap[2] if cap else 0),
-                   max(ws_bytes, cap[3] if cap else 0))
-            f32 = dict(dtype=torch.float32, device=dev)
-            self._bufs = dict(out=torch.zeros(cap[2], C, **f32), loss=torch.zeros(cap[2], **f32),
-                              d_edge=torch.zeros(max(cap[1], 1), **f32), d_node=torch.zeros(max(cap[0], 1), F, **f32),
-                              dx=torch.zeros(max(cap[0], 1), F, **f32),
-                              ws=torch.empty(max(cap[3], 256), dtype=torch.uint8, device=dev))
-            self._cap = cap
-        return self._bufs
+        super().__init__(model)
+        self.apply_sigmoid = bool(apply_sigmoid)
 
     @staticmethod
     def _mask(t, shape, what):
@@ -145,7 +118,6 @@ class ExplainStep:
         why = self._shape_args(a, batch)
         if why is not None:
             return self._autograd(batch, edge_mask, node_mask, target, dout, want_dx, target_class)
-        m = self.model
         x = _frozen.batch_x(batch, edge_mask, node_mask, target, dout, target_class)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         em = self._mask(edge_mask, (E,), "edge_mask")
@@ -153,26 +125,21 @@ class ExplainStep:
         tg = self._mask(target, (B, C), "target") if target is not None else None
         do = self._mask(dout, (B, C), "dout") if dout is not None else None
         tc = target_class.detach() if target_class is not None else None
-        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
         bwd = tg is not None or do is not None or tc is not None
-        bufs = self._buffers(N, E, B, F, C, int(a.workspace_bytes_needed), x.device)
+        take, dev = self._bufs.take, x.device
+        out, loss, d_edge = take("out", (B, C), dev), take("loss", (B,), dev), take("d_edge", (E,), dev)
+        d_node = take("d_node", (N, F), dev) if nm is not None else None
+        dx = take("dx", (N, F), dev) if want_dx else None
         p = _lib.ptr
-        a.flags = (_lib.HCG_EXPLAIN_SIGMOID if self.apply_sigmoid else 0) | (_lib.HCG_EXPLAIN_TARGET_CLASS if tc is not None else 0)
-        _frozen.fill_graph(a, x, plan)
-        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ExplainStep"))
+        self._fill(a, (_lib.HCG_EXPLAIN_SIGMOID if self.apply_sigmoid else 0) | (_lib.HCG_EXPLAIN_TARGET_CLASS if tc is not None else 0),
+                   batch, x, self._weights(dev), self._bufs.workspace(int(a.workspace_bytes_needed), dev))
         a.edge_mask, a.node_mask, a.dout = p(em), p(nm), p(do)
         a.target = p(tc) if tc is not None else p(tg)        # (one slot of the argument block, read by the flag)
-        a.out, a.loss, a.d_edge_mask = p(bufs["out"]), p(bufs["loss"]), p(bufs["d_edge"])
-        a.d_node_mask = p(bufs["d_node"]) if nm is not None else None
-        a.dx = p(bufs["dx"]) if want_dx else None
-        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
-        a.slope = _frozen.SLOPE
+        a.out, a.loss, a.d_edge_mask, a.d_node_mask, a.dx = (_frozen.front(t) for t in (out, loss, d_edge, d_node, dx))
         _lib.check(_lib.load().hcg_explain(ctypes.addressof(a), _lib.stream_ptr()), "hcg_explain")
         self.last_path = "fused"
-        return ExplainResult(bufs["out"][:B], bufs["loss"][:B] if tg is not None or tc is not None else None,
-                             bufs["d_edge"][:E] if bwd else None,
-                             bufs["d_node"][:N] if bwd and nm is not None else None,
-                             bufs["dx"][:N] if bwd and want_dx else None)
+        return ExplainResult(out, loss if tg is not None or tc is not None else None, d_edge if bwd else None,
+                             d_node if bwd else None, dx if bwd else None)
 
     # ------------------------------------------------------------------ the existing path (any shape), under autograd
     def _autograd(self, batch, edge_mask, node_mask, target, dout, want_dx, target_class=None) -> ExplainResult:
@@ -255,7 +222,7 @@ def _entropy_grad(m):
     return (torch.log(b) + (1 - m) / b) - (torch.log(a) + m / a)
 
 
-class ExplainFit:
+class ExplainFit(_frozen.FrozenModel):
     """GNNExplainer for a whole batch of graphs: every graph's mask optimisation, all epochs, in ONE launch.
 
         fit = ExplainFit(model, epochs=100, lr=0.01, coeffs=None, mode="regression")
@@ -292,6 +259,7 @@ class ExplainFit:
     tensors) and torch ops for the regularisers and Adam.  `last_path` says which one ran ("fused" / "loop")."""
 
     MODES = ("regression", "multiclass_classification")
+    KERNEL, NAME = _lib.HCG_EXPLAIN_FIT, "ExplainFit"
 
     def __init__(self, model: torch.nn.Module, epochs: int = 100, lr: float = 0.01, coeffs: Optional[dict] = None,
                  mode: str = "regression"):
@@ -303,36 +271,14 @@ class ExplainFit:
         self._ce = mode == "multiclass_classification"
         if self._ce and int(getattr(model, "_n_classes", 2)) < 2:
             raise ValueError(f"mode {mode!r} needs a model of two classes or more (n_classes >= 2); this one has {int(model._n_classes)}")
-        self.model, self.epochs, self.lr = model, int(epochs), float(lr)
+        super().__init__(model)
+        self.epochs, self.lr = int(epochs), float(lr)
         self.coeffs = dict(DEFAULT_COEFFS)
         for k, v in (coeffs or {}).items():
             if k not in DEFAULT_COEFFS:
                 raise ValueError(f"unknown coefficient {k!r}; known: {sorted(DEFAULT_COEFFS)}")
             self.coeffs[k] = float(v)
-        self.last_path: Optional[str] = None
-        self._cap = None            # (N, E, B, T * B, workspace bytes) capacity of the buffers
-        self._bufs = None
-        self._args = _lib.ExplainArgs()
         self._step = ExplainStep(model, apply_sigmoid=True)
-
-    # ------------------------------------------------------------------ support check (host only, no sync)
-    def _shape_args(self, a, batch) -> Optional[str]:
-        m = self.model
-        why = _frozen.model_reason(m)
-        if why is None and batch is not None:
-            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, int(m.n_node_features), "model")
-        return why or _frozen.query(a, _lib.HCG_EXPLAIN_FIT, _frozen.model_shape(m), batch, edge_mask=None, node_mask=None,
-                                    target=None, dout=None, dx=None)
-
-    def reason(self, batch=None) -> Optional[str]:
-        """None when this model (and `batch`) takes the one-launch kernel, else why not.  Host metadata only."""
-        return self._shape_args(_lib.ExplainArgs(), batch)
-
-    def lds_bytes(self, batch) -> Optional[int]:
-        """Dynamic LDS of one workgroup of the kernel for this batch, as the library's query reports it; None when the
-        batch does not take the kernel."""
-        a = _lib.ExplainArgs()
-        return int(a.lds_bytes) if self._shape_args(a, batch) is None else None
 
     # ------------------------------------------------------------------ state
     @staticmethod
@@ -383,9 +329,8 @@ class ExplainFit:
                 if batch.x.is_cuda:
                     target = self.model(batch).reshape(B, C).clone()
                 else:
-                    from .shapley import _torch_forward
                     ones = torch.ones(batch.edge_index.shape[1], dtype=batch.x.dtype)
-                    target = _torch_forward(self.model, batch.x, batch.edge_index, batch.batch, B, ones).reshape(B, C)
+                    target = _frozen.torch_forward(self.model, batch.x, batch.edge_index, batch.batch, B, ones).reshape(B, C)
                 if self._ce:
                     target = target.argmax(dim=1)           # (on the batch's device, no sync; a tie: the first maximal index)
         if self._ce:
@@ -398,19 +343,6 @@ class ExplainFit:
         if target.dtype != torch.float32 or tuple(target.shape) != (B, C) or not target.is_contiguous():
             raise ValueError(f"target must be a contiguous float32 tensor of shape {(B, C)}; got {target.dtype} {tuple(target.shape)}")
         return target.detach()
-
-    # ------------------------------------------------------------------ buffers
-    def _buffers(self, N, E, B, F, C, TB, ws_bytes, dev):
-        cap = self._cap
-        need = (N, E, B, TB, ws_bytes)
-        if cap is None or any(n > c for n, c in zip(need, cap)) or self._bufs["out"].device != dev:
-            cap = tuple(max(n, c) for n, c in zip(need, cap or (0,) * 5))
-            f32 = dict(dtype=torch.float32, device=dev)
-            self._bufs = dict(out=torch.zeros(max(cap[2], 1), C, **f32), hist=torch.zeros(max(cap[3], 1), **f32),
-                              edge=torch.zeros(max(cap[1], 1), **f32), node=torch.zeros(max(cap[0], 1), F, **f32),
-                              ws=torch.empty(max(cap[4], 256), dtype=torch.uint8, device=dev))
-            self._cap = cap
-        return self._bufs
 
     # ------------------------------------------------------------------ the call
     def __call__(self, batch, target=None, state: Optional[ExplainFitState] = None, epochs: Optional[int] = None,
@@ -425,37 +357,34 @@ class ExplainFit:
         why = self._shape_args(a, batch)
         if why is not None:
             return self.loop(batch, target, state, T, generator)
-        m = self.model
         x = _frozen.batch_x(batch, target)
         N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
         if state is None:
             state = self.init_state(batch, generator)
         self._check_state(state, batch)
         tg = self._target(batch, target)
-        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        bufs = self._buffers(N, E, B, F, C, T * B, int(a.workspace_bytes_needed), x.device)
+        take, dev = self._bufs.take, x.device
+        out, hist = take("out", (B, C), dev), take("hist", (T, B), dev)
+        edge, node = take("edge", (E,), dev), take("node", (N, F), dev)
         p = _lib.ptr
-        a.flags = _lib.HCG_EXPLAIN_TARGET_CLASS if self._ce else 0      # (how the library reads the target slot)
-        _frozen.fill_graph(a, x, plan)
-        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ExplainFit"))
-        a.target, a.out = p(tg), p(bufs["out"])
-        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
-        a.slope = _frozen.SLOPE
+        self._fill(a, _lib.HCG_EXPLAIN_TARGET_CLASS if self._ce else 0,        # (how the library reads the target slot)
+                   batch, x, self._weights(dev), self._bufs.workspace(int(a.workspace_bytes_needed), dev))
+        a.target, a.out = p(tg), _frozen.front(out)
         s = state
         a.fit_edge_logit, a.fit_edge_exp_avg, a.fit_edge_exp_avg_sq, a.fit_edge_hard = p(s.edge_logit), p(s.edge_exp_avg), p(s.edge_exp_avg_sq), p(s.edge_hard)
         a.fit_node_logit, a.fit_node_exp_avg, a.fit_node_exp_avg_sq, a.fit_node_hard = p(s.node_logit), p(s.node_exp_avg), p(s.node_exp_avg_sq), p(s.node_hard)
-        a.fit_hard_count, a.fit_edge_mask_out, a.fit_node_mask_out = p(s.hard_count), p(bufs["edge"]), p(bufs["node"])
+        a.fit_hard_count, a.fit_edge_mask_out, a.fit_node_mask_out = p(s.hard_count), _frozen.front(edge), _frozen.front(node)
         a.fit_lr, a.fit_beta1, a.fit_beta2, a.fit_eps = self.lr, BETA1, BETA2, ADAM_EPS
         for i, k in enumerate(("edge_size", "edge_ent", "node_feat_size", "node_feat_ent")):
             a.fit_coeffs[i] = self.coeffs[k]
-        lib, stream, hist = _lib.load(), _lib.stream_ptr(), bufs["hist"]
+        lib, stream = _lib.load(), _lib.stream_ptr()
         for first in range(0, T, per):
             a.step_first, a.epoch_count = int(s.step), min(per, T - first)
-            a.fit_loss_hist = hist.data_ptr() + 4 * first * B
+            a.fit_loss_hist = _frozen.front(hist) + 4 * first * B
             _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (fit)")
             s.step = int(s.step) + int(a.epoch_count)
         self.last_path = "fused"
-        return ExplainFitResult(bufs["edge"][:E], bufs["node"][:N], bufs["out"][:B], hist[:T * B].view(T, B), s)
+        return ExplainFitResult(edge, node, out, hist, s)
 
     # ------------------------------------------------------------------ the loop path (any shape, CPU tensors)
     def _grads(self, batch, s, target):
@@ -463,12 +392,11 @@ class ExplainFit:
         if batch.x.is_cuda:
             r = self._step(batch, s.edge_logit, s.node_logit, **{"target_class" if self._ce else "target": target})
             return r.out, r.loss, r.d_edge_mask, r.d_node_mask
-        from .shapley import _torch_forward                 # (the package's layers take GPU tensors only)
         em = s.edge_logit.detach().clone().requires_grad_(True)
         nm = s.node_logit.detach().clone().requires_grad_(True)
         B = int(batch.num_graphs)
         with torch.enable_grad():
-            out = _torch_forward(self.model, batch.x * nm.sigmoid(), batch.edge_index, batch.batch, B, em.sigmoid()).reshape(B, -1)
+            out = _frozen.torch_forward(self.model, batch.x * nm.sigmoid(), batch.edge_index, batch.batch, B, em.sigmoid()).reshape(B, -1)
             loss = F_.cross_entropy(out, target, reduction="none") if self._ce else ((out - target) ** 2).mean(dim=1)
             d_e, d_n = torch.autograd.grad(loss.sum(), [em, nm])           # (no parameter's .grad is touched)
         return out.detach(), loss.detach(), d_e, d_n

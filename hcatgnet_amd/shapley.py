@@ -25,15 +25,12 @@ import itertools
 from typing import NamedTuple, Optional
 
 import torch
-import torch.nn.functional as Fn
 
 from . import _frozen, _lib
-from ._frozen import SLOPE
+from ._frozen import CUS, LAUNCH_SECONDS  # noqa: F401  (their home; importable from here as before)
 from .explain import ExplainStep
 
 WORKSPACE_CAP_BYTES = 256 << 20    # the per-permutation rows of one launch
-CUS = 256                          # compute units of an MI355X
-LAUNCH_SECONDS = 1.0               # what one launch should stay near (the machines are shared)
 EVAL_SECONDS = 60e-6               # one evaluation at the shape limits: an estimate (default_samples_per_launch)
 MAX_WORKGROUPS_PER_CU = 4
 GROUPED_WORKGROUPS_PER_CU = 64     # a grouped walk is short (its steps are the groups): more of them queue on a CU per launch
@@ -68,23 +65,28 @@ def _layout(batch, F: int):
     return n, e, gptr, eptr, gptr[:-1] * F + eptr[:-1]
 
 
-def draw_permutations(batch, F: int, n_samples: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """int32 [n_samples, N * F + E] on the batch's device: in every row, graph g's segment (start graph_ptr[g] * F +
-    edge_ptr[g], length K_g = n_g * F + e_g) is a uniformly random permutation of 0 .. K_g - 1, drawn from `generator`
-    (on the generator's device; None: the default generator of the batch's device) as the argsort of (graph id, key)."""
-    n, e, _, _, seg = _layout(batch, F)
-    dev = batch.x.device
-    K = n * F + e
-    total = int(K.sum())
-    gid = torch.repeat_interleave(torch.arange(K.numel(), device=dev), K)
-    start = seg[gid]
+def _draw_segments(count, start, total: int, n_samples: int, generator, dev) -> torch.Tensor:
+    """int32 [n_samples, total]: in every row, segment g (start[g], length count[g]; the segments tile the row in order) is
+    a uniformly random permutation of 0 .. count[g] - 1: the argsort of (segment id, key), one float64 key per entry and
+    one `torch.rand` per row, on the generator's device (None: the default generator of `dev`)."""
+    gid = torch.repeat_interleave(torch.arange(count.numel(), device=dev), count)
+    first = start[gid]
     gdev = generator.device if generator is not None else dev
     out = torch.empty(int(n_samples), total, dtype=torch.int32, device=dev)
     for p in range(int(n_samples)):
         key = torch.rand(total, generator=generator, device=gdev, dtype=torch.float64).to(dev)
         order = torch.argsort(gid.to(torch.float64) + key)
-        out[p] = (order - start).to(torch.int32)
+        out[p] = (order - first).to(torch.int32)
     return out
+
+
+def draw_permutations(batch, F: int, n_samples: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """int32 [n_samples, N * F + E] on the batch's device: in every row, graph g's segment (start graph_ptr[g] * F +
+    edge_ptr[g], length K_g = n_g * F + e_g) is a uniformly random permutation of 0 .. K_g - 1, drawn from `generator`
+    (on the generator's device; None: the default generator of the batch's device) as the argsort of (graph id, key)."""
+    n, e, _, _, seg = _layout(batch, F)
+    return _draw_segments(n * F + e, seg, int(batch.batch.numel()) * F + int(batch.edge_index.shape[1]), n_samples, generator,
+                          batch.x.device)
 
 
 class _Groups(NamedTuple):
@@ -194,20 +196,8 @@ def draw_group_permutations(batch, node_group=None, edge_group=None, n_samples: 
                             generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """int32 [n_samples, G] on the batch's device: in every row, graph g's segment (start group_ptr[g], length G_g) is a
     uniformly random permutation of 0 .. G_g - 1, drawn as `draw_permutations` draws: the argsort of (graph id, key)."""
-    return _draw_group_permutations(_group_layout(batch, int(batch.x.shape[1]), node_group, edge_group), batch.x.device,
-                                    n_samples, generator)
-
-
-def _draw_group_permutations(gr: _Groups, dev, n_samples: int, generator) -> torch.Tensor:
-    gid = torch.repeat_interleave(torch.arange(gr.count.numel(), device=dev), gr.count)
-    start = gr.group_ptr[gid]
-    gdev = generator.device if generator is not None else dev
-    out = torch.empty(int(n_samples), gr.G, dtype=torch.int32, device=dev)
-    for p in range(int(n_samples)):
-        key = torch.rand(gr.G, generator=generator, device=gdev, dtype=torch.float64).to(dev)
-        order = torch.argsort(gid.to(torch.float64) + key)
-        out[p] = (order - start).to(torch.int32)
-    return out
+    gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
+    return _draw_segments(gr.count, gr.group_ptr, gr.G, n_samples, generator, batch.x.device)
 
 
 def all_group_permutations(batch, node_group=None, edge_group=None) -> torch.Tensor:
@@ -222,36 +212,127 @@ def all_group_permutations(batch, node_group=None, edge_group=None) -> torch.Ten
     return rows.repeat(1, gr.count.numel()).to(batch.x.device).contiguous()
 
 
-def _torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):
-    """The model's masked forward in plain torch ops, for CPU tensors (the package's layers are HIP kernels and take GPU
-    tensors only).  The loop path uses it when the batch lives on the CPU; nothing on a GPU ever runs it."""
-    convs, lins = _frozen.model_layers(model)
-    N = x.shape[0]
-    src, dst = edge_index[0], edge_index[1]
-    keep = src != dst                                   # an explicit (i, i) edge is part of the unit self loop
-    deg = torch.ones(N, dtype=x.dtype).scatter_add_(0, dst[keep], torch.ones(int(keep.sum()), dtype=x.dtype))
-    dinv = deg.pow(-0.5)
-    coef = (dinv[src] * dinv[dst] * edge_mask)[keep].unsqueeze(1)
-    s, d = src[keep], dst[keep]
-    h = x
-    for c in convs:
-        t = Fn.linear(h, c.lin.weight)
-        y = (dinv * dinv).unsqueeze(1) * t
-        # (index_select, not t[s]: the same values forward; its backward adds the rows serially in index order, where
-        # the backward of t[s] adds them with atomics from several threads -- a gradient that differs in its last bits run to run)
-        y = y.index_add(0, d, coef * t.index_select(0, s))
-        h = Fn.leaky_relu(y + c.bias, SLOPE)
-    idx = batch_vec.unsqueeze(1).expand_as(h)
-    mx = h.new_zeros(B, h.shape[1]).scatter_reduce(0, idx, h, reduce="amax", include_self=False)
-    cnt = torch.bincount(batch_vec, minlength=B).clamp_min(1).to(h.dtype).unsqueeze(1)
-    z = torch.cat([mx, h.new_zeros(B, h.shape[1]).index_add(0, batch_vec, h) / cnt], 1)
-    for li in lins[:-1]:
-        z = Fn.leaky_relu(Fn.linear(z, li.weight, li.bias), SLOPE)
-    z = Fn.linear(z, lins[-1].weight, lins[-1].bias)
-    return z
+class _Walk(NamedTuple):
+    """What the loop path needs of the players (`_Players.walk`); every tensor on the batch's device."""
+    count: torch.Tensor          # [B] int64 players of every graph
+    start: torch.Tensor          # [B] int64 where graph g's segment of a permutation row starts
+    steps: int                   # the largest count
+    place: object                # (graphs [A], their local players [A]) -> the players' indices in the accumulator
+    owner: torch.Tensor          # [N * F + E] int64: the player that switches the feature on, `row` for one that is always on
+    live: torch.Tensor           # [row] bool: the player can change the output
 
 
-class ShapleySampling:
+class _Players:
+    """The players of one call: the features themselves (`_Features`) or groups of them (`_GroupPlayers`).  `row` players in
+    the batch: the width of a permutation row and of the accumulator."""
+    arg = width = label = ""     # the permutation argument, its width in a message, the launch's label in an error
+    flags = 0                    # of the launch
+    per_cu = MAX_WORKGROUPS_PER_CU
+    query: dict = {}             # what the shape query takes beside the permutation count
+
+    def __init__(self, batch):
+        self.batch = batch
+        (self.N, self.F), self.E, self.B = batch.x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
+
+    def permutations(self, n_samples, given, generator) -> torch.Tensor:
+        """`given`, checked, or `n_samples` rows drawn from `generator`"""
+        dev = self.batch.x.device
+        if given is None:
+            if int(n_samples) < 1:
+                raise ValueError(f"n_samples must be at least 1; got {n_samples}")
+            return _draw_segments(*self.segments(), self.row, n_samples, generator, dev)
+        t = given
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != self.row:
+            raise ValueError(f"{self.arg} must be an int32 tensor of shape [P >= 1, {self.width} = {self.row}]; got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != dev:
+            raise ValueError(f"{self.arg} are on {t.device}, the batch on {dev}")
+        return t.contiguous()
+
+
+class _Features(_Players):
+    arg, width, label = "permutations", "N * F + E", "hcg_explain (shapley)"
+
+    def __init__(self, batch):
+        super().__init__(batch)
+        self.row = self.N * self.F + self.E
+
+    def segments(self):
+        n, e, _, _, seg = _layout(self.batch, self.F)
+        return n * self.F + e, seg
+
+    def max_steps(self, a) -> int:
+        return a.max_nodes * self.F + a.max_edges
+
+    def fill(self, a):
+        pass
+
+    def walk(self) -> _Walk:
+        N, F, x, ei = self.N, self.F, self.batch.x, self.batch.edge_index
+        n, e, gptr, eptr, seg = _layout(self.batch, F)
+        nF, K = n * F, n * F + e
+
+        def place(act, j):       # a node entry before the batch's edges, as `ShapleyResult` splits the accumulator
+            return torch.where(j < nF[act], gptr[act] * F + j, N * F + eptr[act] + j - nF[act])
+        # what cannot change the output: its difference is exactly 0 by definition
+        live = torch.cat([(x != 0).reshape(-1), ei[0] != ei[1]])
+        return _Walk(K, seg, int(K.max()) if self.B > 0 else 0, place, torch.arange(self.row, device=x.device), live)
+
+    def result(self, acc, out_full, out_base) -> ShapleyResult:
+        NF = self.N * self.F
+        return ShapleyResult(acc[:NF].view(self.N, self.F), acc[NF:self.row], out_full, out_base)
+
+
+class _GroupPlayers(_Players):
+    arg, width, label = "group_permutations", "G", "hcg_explain (grouped shapley)"
+    flags, per_cu = _lib.HCG_EXPLAIN_GROUPED, GROUPED_WORKGROUPS_PER_CU
+
+    def __init__(self, batch, node_group, edge_group):
+        super().__init__(batch)
+        self.groups = gr = _group_layout(batch, self.F, node_group, edge_group)
+        self.row = gr.G
+        self.query = dict(flags=_lib.HCG_EXPLAIN_QUERY | _lib.HCG_EXPLAIN_GROUPED, shap_n_groups=gr.G)
+
+    def segments(self):
+        return self.groups.count, self.groups.group_ptr
+
+    def max_steps(self, a) -> int:
+        return self.groups.max_groups
+
+    def fill(self, a):
+        gr, p = self.groups, _lib.ptr
+        self.group_ptr32 = group_ptr = gr.group_ptr.to(torch.int32)         # (lives as long as the call's players)
+        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr), p(gr.member_ptr), p(gr.bg_ptr)
+        # one array holds the groups' members and, behind them, the background (a batch without features: never read)
+        a.shap_members = a.shap_bg_members = p(gr.members) if gr.members.numel() else p(group_ptr)
+        a.shap_n_groups = gr.G
+
+    def walk(self) -> _Walk:
+        gr = self.groups
+
+        def place(act, j):
+            return gr.group_ptr[act] + j
+        # a group without a live member cannot change the output: its difference is exactly 0 by definition
+        return _Walk(gr.count, gr.group_ptr, gr.max_groups, place, gr.slot, gr.live_group)
+
+    def result(self, acc, out_full, out_base) -> GroupedShapleyResult:
+        gr, NF = self.groups, self.N * self.F
+        flat = torch.cat([acc[:gr.G], acc.new_zeros(1)])[gr.slot]          # (the background reads the appended 0)
+        return GroupedShapleyResult(acc[:gr.G], gr.group_ptr, flat[:NF].view(self.N, self.F), flat[NF:], out_full, out_base)
+
+
+def _players(batch, permutations, node_group, edge_group, group_permutations):
+    """-> (the players of a call with these arguments, the permutations it was given or None)"""
+    if node_group is not None or edge_group is not None:
+        if permutations is not None:
+            raise ValueError("a grouped call takes group_permutations, not permutations")
+        return _GroupPlayers(batch, node_group, edge_group), group_permutations
+    if group_permutations is not None:
+        raise ValueError("group_permutations need node_group or edge_group")
+    return _Features(batch), permutations
+
+
+class ShapleySampling(_frozen.FrozenModel):
     """Shapley value sampling of a frozen model for a whole batch of graphs.
 
         sv = ShapleySampling(model)
@@ -296,34 +377,11 @@ class ShapleySampling:
     `permutations` belongs to the ungrouped call.  With neither array given the call is the ungrouped one, unchanged.
     The host checks the ids and lists the members with torch ops: one stable sort and one read of three scalars."""
 
+    KERNEL, NAME = _lib.HCG_EXPLAIN_SHAPLEY, "ShapleySampling"
+
     def __init__(self, model: torch.nn.Module):
-        self.model = model
-        self.last_path: Optional[str] = None
-        self._cap = None            # (N * F + E, B, workspace bytes) capacity of the buffers
-        self._bufs = None
-        self._args = _lib.ExplainArgs()
+        super().__init__(model)
         self._step = ExplainStep(model, apply_sigmoid=False)
-
-    # ------------------------------------------------------------------ support check (host only, no sync)
-    def _shape_args(self, a, batch, perm_count: int = 1, n_groups: Optional[int] = None) -> Optional[str]:
-        """`n_groups`: the query of a grouped call (rows of G entries)."""
-        m = self.model
-        why = _frozen.model_reason(m)
-        if why is None and batch is not None:
-            why = "the batch is on the CPU" if not batch.x.is_cuda else _frozen.batch_reason(batch, int(m.n_node_features), "model")
-        more = {} if n_groups is None else dict(flags=_lib.HCG_EXPLAIN_QUERY | _lib.HCG_EXPLAIN_GROUPED, shap_n_groups=int(n_groups))
-        return why or _frozen.query(a, _lib.HCG_EXPLAIN_SHAPLEY, _frozen.model_shape(m), batch, perm_count=int(perm_count),
-                                    edge_mask=None, node_mask=None, target=None, dout=None, **more)
-
-    def reason(self, batch=None) -> Optional[str]:
-        """None when this model (and `batch`) takes the on-chip kernel, else why not.  Host metadata only."""
-        return self._shape_args(_lib.ExplainArgs(), batch)
-
-    def lds_bytes(self, batch) -> Optional[int]:
-        """Dynamic LDS of one workgroup of the kernel for this batch, as the library's query reports it; None when the
-        batch does not take the kernel."""
-        a = _lib.ExplainArgs()
-        return int(a.lds_bytes) if self._shape_args(a, batch) is None else None
 
     @staticmethod
     def default_samples_per_launch(n_perm: int, num_graphs: int, row: int, max_steps: int = 0,
@@ -340,225 +398,82 @@ class ShapleySampling:
         by_wg = min(per_cu, int(max_per_cu)) * CUS // max(int(num_graphs), 1)
         return max(1, min(int(n_perm), by_ws, by_wg, 65535))
 
-    # ------------------------------------------------------------------ buffers
-    def _buffers(self, row, B, C, ws_bytes, dev):
-        cap = self._cap
-        if cap is None or row > cap[0] or B > cap[1] or ws_bytes > cap[2] or self._bufs["out"].device != dev:
-            cap = (max(row, cap[0] if cap else 0), max(B, cap[1] if cap else 0), max(ws_bytes, cap[2] if cap else 0))
-            f32 = dict(dtype=torch.float32, device=dev)
-            self._bufs = dict(acc=torch.zeros(max(cap[0], 1), **f32), out=torch.zeros(max(cap[1], 1), C, **f32),
-                              base=torch.zeros(max(cap[1], 1), C, **f32),
-                              ws=torch.empty(max(cap[2], 256), dtype=torch.uint8, device=dev))
-            self._cap = cap
-        return self._bufs
-
-    def _permutations(self, batch, F, n_samples, permutations, generator):
-        row = int(batch.x.shape[0]) * F + int(batch.edge_index.shape[1])
-        if permutations is None:
-            if int(n_samples) < 1:
-                raise ValueError(f"n_samples must be at least 1; got {n_samples}")
-            return draw_permutations(batch, F, int(n_samples), generator)
-        t = permutations
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != row:
-            raise ValueError(f"permutations must be an int32 tensor of shape [P >= 1, N * F + E = {row}]; got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != batch.x.device:
-            raise ValueError(f"permutations are on {t.device}, the batch on {batch.x.device}")
-        return t.contiguous()
-
     # ------------------------------------------------------------------ the call
-    # ------------------------------------------------------------------ groups as players
-    def _group_permutations(self, batch, gr, n_samples, group_permutations, generator):
-        if group_permutations is None:
-            if int(n_samples) < 1:
-                raise ValueError(f"n_samples must be at least 1; got {n_samples}")
-            return _draw_group_permutations(gr, batch.x.device, int(n_samples), generator)
-        t = group_permutations
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != gr.G:
-            raise ValueError(f"group_permutations must be an int32 tensor of shape [P >= 1, G = {gr.G}]; got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != batch.x.device:
-            raise ValueError(f"group_permutations are on {t.device}, the batch on {batch.x.device}")
-        return t.contiguous()
-
-    @staticmethod
-    def _grouped_result(gr, acc, N, F, out_full, out_base) -> GroupedShapleyResult:
-        flat = torch.cat([acc[:gr.G], acc.new_zeros(1)])[gr.slot]          # (the background reads the appended 0)
-        return GroupedShapleyResult(acc[:gr.G], gr.group_ptr, flat[:N * F].view(N, F), flat[N * F:], out_full, out_base)
-
-    def _call_grouped(self, batch, n_samples, generator, class_index, samples_per_launch, node_group, edge_group,
-                      group_permutations) -> GroupedShapleyResult:
+    def __call__(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0,
+                 samples_per_launch: Optional[int] = None, node_group=None, edge_group=None, group_permutations=None):
+        pl, given = _players(batch, permutations, node_group, edge_group, group_permutations)
         a = self._args
-        F = int(batch.x.shape[1])
-        gr = _group_layout(batch, F, node_group, edge_group)
-        perm = self._group_permutations(batch, gr, n_samples, group_permutations, generator)
-        if self._shape_args(a, batch, 1, gr.G) is not None:
-            return self._loop_grouped(batch, gr, perm, class_index)
-        m = self.model
+        if self._shape_args(a, batch, perm_count=1, **pl.query) is not None:
+            return self._walk(pl, pl.permutations(n_samples, given, generator), class_index)
         x = _frozen.batch_x(batch)
-        N, B, C = a.N, a.B, a.C
-        if not 0 <= int(class_index) < C:
-            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
-        P, G = int(perm.shape[0]), gr.G
-        spl = self.default_samples_per_launch(P, B, G, gr.max_groups, GROUPED_WORKGROUPS_PER_CU) if samples_per_launch is None \
+        B, C, dev = a.B, a.C, x.device
+        cls = self._class(class_index)
+        perm = pl.permutations(n_samples, given, generator)
+        P = int(perm.shape[0])
+        spl = self.default_samples_per_launch(P, B, pl.row, pl.max_steps(a), pl.per_cu) if samples_per_launch is None \
             else int(samples_per_launch)
         if not 1 <= spl <= 65535:
             raise ValueError(f"samples_per_launch must lie in 1 .. 65535; got {samples_per_launch}")
         spl = min(spl, P)
-        self._shape_args(a, batch, spl, G)                  # the workspace of a launch of `spl` permutations
-        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        bufs = self._buffers(G, B, C, int(a.workspace_bytes_needed), x.device)
-        p = _lib.ptr
-        group_ptr = gr.group_ptr.to(torch.int32)
-        a.flags = _lib.HCG_EXPLAIN_GROUPED
-        _frozen.fill_graph(a, x, plan)
-        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ShapleySampling"))
-        a.out, a.out_base, a.shap_acc, a.perm = p(bufs["out"]), p(bufs["base"]), p(bufs["acc"]), p(perm)
-        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
-        a.slope, a.n_perm, a.class_index = SLOPE, P, int(class_index)
-        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr), p(gr.member_ptr), p(gr.bg_ptr)
-        # one array holds the groups' members and, behind them, the background (a batch without features: never read)
-        a.shap_members = a.shap_bg_members = p(gr.members) if gr.members.numel() else p(group_ptr)
-        a.shap_n_groups = G
+        # the workspace of a launch of `spl` permutations (model and batch are checked: the library's query alone)
+        _frozen.query(a, self.KERNEL, self._shape(), batch, perm_count=spl, **pl.query)
+        take, front = self._bufs.take, _frozen.front
+        acc, out, base = take("acc", (pl.row,), dev), take("out", (B, C), dev), take("base", (B, C), dev)
+        self._fill(a, pl.flags, batch, x, self._weights(dev), self._bufs.workspace(int(a.workspace_bytes_needed), dev))
+        a.out, a.out_base, a.shap_acc, a.perm = front(out), front(base), front(acc), _lib.ptr(perm)
+        a.n_perm, a.class_index = P, cls
+        pl.fill(a)
         lib, stream = _lib.load(), _lib.stream_ptr()
         for first in range(0, P, spl):
             a.perm_first, a.perm_count = first, min(spl, P - first)
-            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (grouped shapley)")
+            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), pl.label)
         self.last_path = "fused"
-        return self._grouped_result(gr, bufs["acc"], N, F, bufs["out"][:B], bufs["base"][:B])
-
-    def __call__(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0,
-                 samples_per_launch: Optional[int] = None, node_group=None, edge_group=None, group_permutations=None):
-        if node_group is not None or edge_group is not None:
-            if permutations is not None:
-                raise ValueError("a grouped call takes group_permutations, not permutations")
-            return self._call_grouped(batch, n_samples, generator, class_index, samples_per_launch, node_group, edge_group,
-                                      group_permutations)
-        if group_permutations is not None:
-            raise ValueError("group_permutations need node_group or edge_group")
-        a = self._args
-        why = self._shape_args(a, batch)
-        if why is not None:
-            return self.loop(batch, n_samples, permutations, generator, class_index)
-        m = self.model
-        x = _frozen.batch_x(batch)
-        N, F, E, B, C = a.N, a.F, a.E, a.B, a.C
-        if not 0 <= int(class_index) < C:
-            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
-        perm = self._permutations(batch, F, n_samples, permutations, generator)
-        P, row = int(perm.shape[0]), N * F + E
-        spl = self.default_samples_per_launch(P, B, row, a.max_nodes * F + a.max_edges) if samples_per_launch is None else int(samples_per_launch)
-        if not 1 <= spl <= 65535:
-            raise ValueError(f"samples_per_launch must lie in 1 .. 65535; got {samples_per_launch}")
-        spl = min(spl, P)
-        self._shape_args(a, batch, spl)                     # the workspace of a launch of `spl` permutations
-        plan = m._plan_for(batch, x, batch.edge_index, batch.batch, None)
-        bufs = self._buffers(row, B, C, int(a.workspace_bytes_needed), x.device)
-        p = _lib.ptr
-        a.flags = 0
-        _frozen.fill_graph(a, x, plan)
-        _frozen.fill_weights(a, *_frozen.model_weights(m, x.device, "ShapleySampling"))
-        a.out, a.out_base, a.shap_acc, a.perm = p(bufs["out"]), p(bufs["base"]), p(bufs["acc"]), p(perm)
-        a.workspace, a.workspace_bytes = p(bufs["ws"]), bufs["ws"].numel()
-        a.slope, a.n_perm, a.class_index = SLOPE, P, int(class_index)
-        lib, stream = _lib.load(), _lib.stream_ptr()
-        for first in range(0, P, spl):
-            a.perm_first, a.perm_count = first, min(spl, P - first)
-            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (shapley)")
-        self.last_path = "fused"
-        acc = bufs["acc"]
-        return ShapleyResult(acc[:N * F].view(N, F), acc[N * F:row], bufs["out"][:B], bufs["base"][:B])
+        return pl.result(acc, out, base)
 
     # ------------------------------------------------------------------ the existing path (any shape): one forward per step
     def _forward(self, batch, node_mask, edge_mask):
         if not batch.x.is_cuda:
-            return _torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
+            return _frozen.torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
         return self._step(batch, edge_mask, node_mask).out
-
-    def _loop_grouped(self, batch, gr, perm, class_index) -> GroupedShapleyResult:
-        """The loop with groups as players: the background is on from the base on, step k switches on every member of the
-        k-th group of every graph's permutation."""
-        x = batch.x
-        (N, F), B, G = x.shape, int(batch.num_graphs), gr.G
-        perm = perm.to(torch.int64)
-        P, dev = int(perm.shape[0]), x.device
-        garange = torch.arange(B, device=dev)
-        background = (gr.slot == G).to(torch.float32)
-        acc = torch.zeros(G, dtype=torch.float32, device=dev)
-        out_full = out_base = None
-        with torch.no_grad():
-            for p in range(P):
-                on = background.clone()
-                phi = torch.zeros(G, dtype=torch.float32, device=dev)
-                out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
-                if p == 0:
-                    out_base = out
-                vprev = out[:, class_index].clone()
-                for k in range(gr.max_groups):
-                    act = garange[gr.count > k]                            # graphs whose walk is not finished
-                    slot = gr.group_ptr[act] + perm[p, gr.group_ptr[act] + k]
-                    step = torch.zeros(G + 1, dtype=torch.bool, device=dev)
-                    step[slot] = True
-                    on = torch.where(step[gr.slot], torch.ones_like(on), on)
-                    out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
-                    v = out[:, class_index]
-                    # a group without a live member cannot change the output: its difference is exactly 0 by definition
-                    phi[slot] = torch.where(gr.live_group[slot], v[act] - vprev[act], torch.zeros_like(v[act]))
-                    vprev = v.clone()
-                if p == 0:
-                    out_full = out
-                acc = acc + phi
-        acc = acc / float(P)
-        self.last_path = "loop"
-        return self._grouped_result(gr, acc, N, F, out_full, out_base)
 
     def loop(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0, node_group=None,
              edge_group=None, group_permutations=None):
         """The batch-synchronous loop (see the class docstring), whatever `reason(batch)` says."""
-        if node_group is not None or edge_group is not None:
-            if permutations is not None:
-                raise ValueError("a grouped call takes group_permutations, not permutations")
-            gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
-            perm = self._group_permutations(batch, gr, n_samples, group_permutations, generator)
-            return self._loop_grouped(batch, gr, perm, class_index)
-        if group_permutations is not None:
-            raise ValueError("group_permutations need node_group or edge_group")
-        x = batch.x
-        (N, F), E, B = x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
-        perm = self._permutations(batch, F, n_samples, permutations, generator).to(torch.int64)
-        P, dev = int(perm.shape[0]), x.device
-        n, e, gptr, eptr, seg = _layout(batch, F)
-        nF, K = n * F, n * F + e
-        kmax = int(K.max()) if B > 0 else 0
-        src, dst = batch.edge_index[0], batch.edge_index[1]
-        # what cannot change the output: its difference is exactly 0 by definition
-        dead = torch.cat([(x == 0).reshape(-1), src == dst])
+        pl, given = _players(batch, permutations, node_group, edge_group, group_permutations)
+        return self._walk(pl, pl.permutations(n_samples, given, generator), class_index)
+
+    def _walk(self, pl: _Players, perm, class_index):
+        """Step k switches on the k-th player of every graph's permutation: a feature, or every member of a group (what no
+        group holds, the background, is on from the base on)."""
+        batch, N, F, B, row = pl.batch, pl.N, pl.F, pl.B, pl.row
+        w = pl.walk()
+        perm = perm.to(torch.int64)
+        P, dev = int(perm.shape[0]), batch.x.device
         garange = torch.arange(B, device=dev)
-        acc = torch.zeros(N * F + E, dtype=torch.float32, device=dev)
+        background = (w.owner == row).to(torch.float32)
+        acc = torch.zeros(row, dtype=torch.float32, device=dev)
         out_full = out_base = None
         with torch.no_grad():
             for p in range(P):
-                nm = torch.zeros(N, F, dtype=torch.float32, device=dev)
-                em = torch.zeros(E, dtype=torch.float32, device=dev)
-                phi = torch.zeros(N * F + E, dtype=torch.float32, device=dev)
-                out = self._forward(batch, nm, em).reshape(B, -1).clone()
+                on = background.clone()
+                phi = torch.zeros(row, dtype=torch.float32, device=dev)
+                out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
                 if p == 0:
                     out_base = out
                 vprev = out[:, class_index].clone()
-                for k in range(kmax):
-                    act = garange[K > k]                                  # graphs whose walk is not finished
-                    j = perm[p, seg[act] + k]
-                    is_node = j < nF[act]
-                    slot = torch.where(is_node, gptr[act] * F + j, N * F + eptr[act] + j - nF[act])
-                    nm.view(-1)[slot[is_node]] = 1.0
-                    em[slot[~is_node] - N * F] = 1.0
-                    out = self._forward(batch, nm, em).reshape(B, -1).clone()
+                for k in range(w.steps):
+                    act = garange[w.count > k]                            # graphs whose walk is not finished
+                    slot = w.place(act, perm[p, w.start[act] + k])
+                    step = torch.zeros(row + 1, dtype=torch.bool, device=dev)
+                    step[slot] = True
+                    on = torch.where(step[w.owner], torch.ones_like(on), on)
+                    out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
                     v = out[:, class_index]
-                    phi[slot] = torch.where(dead[slot], torch.zeros_like(v[act]), v[act] - vprev[act])
+                    phi[slot] = torch.where(w.live[slot], v[act] - vprev[act], torch.zeros_like(v[act]))
                     vprev = v.clone()
                 if p == 0:
                     out_full = out
                 acc = acc + phi
         acc = acc / float(P)
         self.last_path = "loop"
-        return ShapleyResult(acc[:N * F].view(N, F), acc[N * F:], out_full, out_base)
+        return pl.result(acc, out_full, out_base)

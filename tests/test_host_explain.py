@@ -107,33 +107,38 @@ def test_explain_step_support_check_is_host_only():
 
 
 _LIMITS = "embedding_dim 64, <= 64 node features, <= 4 conv layers, readout depth <= 4, <= 8 classes, graphs of <= {} nodes and <= 1024 directed edges)"
+_ONE = dict(off="fused kernels disabled on the model", weight="explicit edge weights cannot be combined with masks",
+            feat="batch has 32 node features, the model takes 25")
+_MANY = dict(off="fused kernels disabled on a model", weight="explicit edge weights are outside the ensemble kernel",
+             feat="batch has 32 node features, the models take 25")
 _FROZEN = {
-    "explain": dict(make=lambda m: ExplainStep(m), nodes=224, off="fused kernels disabled on the model",
-                    weight="explicit edge weights cannot be combined with masks",
-                    feat="batch has 32 node features, the model takes 25",
+    "explain": dict(make=lambda m: ExplainStep(m), nodes=224, cpu=False, **_ONE,
                     limit="model / graph shape outside the one-launch explain kernel (" + _LIMITS.format(224)),
-    "ensemble": dict(make=lambda m: H.ensemble.EnsemblePredict([m]), nodes=224, off="fused kernels disabled on a model",
-                     weight="explicit edge weights are outside the ensemble kernel",
-                     feat="batch has 32 node features, the models take 25",
+    "ensemble": dict(make=lambda m: H.ensemble.EnsemblePredict([m]), nodes=224, cpu=False, **_MANY,
                      limit="model / graph shape outside the one-launch ensemble kernel (" + _LIMITS.format(224)),
-    "shapley": dict(make=lambda m: H.shapley.ShapleySampling(m), nodes=184, off="fused kernels disabled on the model",
-                    weight="explicit edge weights cannot be combined with masks",
-                    feat="batch has 32 node features, the model takes 25",
+    "shapley": dict(make=lambda m: H.shapley.ShapleySampling(m), nodes=184, cpu=True, **_ONE,
                     limit="model / graph shape outside the on-chip Shapley kernel (" + _LIMITS.format(184)),
+    "fit": dict(make=lambda m: H.explain.ExplainFit(m), nodes=224, cpu=True, **_ONE,
+                limit="model / graph shape outside the one-launch explainer fit kernel (" + _LIMITS.format(224)),
+    "integrated": dict(make=lambda m: H.attribution.IntegratedGradients(m), nodes=224, cpu=True, **_ONE,
+                       limit="model / graph shape outside the one-launch integrated gradients kernel (" + _LIMITS.format(224)),
+    "ensemble_attribution": dict(make=lambda m: H.attribution.EnsembleAttribution([m]), nodes=224, cpu=True, **_MANY,
+                                 limit="model / graph shape outside the one-launch integrated gradients kernel (" + _LIMITS.format(224)),
 }
+
+
+def _stand_in(F=25, is_cuda=True, N=4, E=0, **kw):
+    """`reason` and `_shape_args` read host metadata only, so a stand-in batch serves."""
+    from types import SimpleNamespace as NS
+    return NS(x=NS(is_cuda=is_cuda, shape=(N, F)), edge_index=NS(shape=(2, E)), num_graphs=1, **kw)
 
 
 @pytest.mark.parametrize("name", sorted(_FROZEN))
 def test_frozen_classes_keep_their_own_reason_strings(name):
-    """The three frozen-model classes share one support check (hcatgnet_amd/_frozen.py); each still answers in its own
-    words.  `reason` reads host metadata only, so a stand-in batch serves (its x claims to be on a GPU: ShapleySampling
-    asks that first)."""
-    from types import SimpleNamespace as NS
-    import hcatgnet_amd.ensemble, hcatgnet_amd.shapley  # noqa: F401
-
-    def mk(F=25, **kw):
-        return NS(x=NS(is_cuda=True, shape=(4, F)), edge_index=NS(shape=(2, 0)), num_graphs=1, **kw)
-
+    """The six frozen-model classes share one support check (hcatgnet_amd/_frozen.py); each still answers in its own
+    words.  The stand-in's x claims to be on a GPU: four of the six ask that first, and say so when it is not."""
+    import hcatgnet_amd.attribution, hcatgnet_amd.ensemble, hcatgnet_amd.shapley  # noqa: F401
+    mk = _stand_in
     w = _FROZEN[name]
     meta = dict(max_nodes=30, max_edges=64, edges_grouped=True)
     obj = w["make"](H.make_network("GCN", H.default_options(), 25))
@@ -144,4 +149,88 @@ def test_frozen_classes_keep_their_own_reason_strings(name):
     assert obj.reason(mk(F=32, **meta)) == w["feat"]
     assert obj.reason(mk(max_nodes=w["nodes"] + 1, max_edges=64, edges_grouped=True)) == w["limit"]
     assert w["make"](H.make_network("GCN", H.default_options(use_fused=False), 25)).reason() == w["off"]
+    if w["cpu"]:
+        assert obj.reason(mk(is_cuda=False, **meta)) == "the batch is on the CPU"
     assert obj.last_path is None
+
+
+def test_buffer_pool_grows_one_name_at_a_time():
+    """The frozen-model classes' buffers (`obj._bufs`): name -> flat tensor, as large as the largest request seen for the
+    name, at least 1 element; a request returns the buffer's front in the shape asked for."""
+    from hcatgnet_amd._frozen import Pool
+    pool, cpu = Pool(), torch.device("cpu")
+    a, b = pool.take("a", (2, 3), cpu), pool.take("b", (4,), cpu)
+    assert a.shape == (2, 3) and a.is_contiguous() and a.dtype == torch.float32 and not a.any() and not b.any()      # fresh storage is zero
+    assert pool["a"].shape == (6,) and pool["b"].shape == (4,) and sorted(pool) == ["a", "b"]
+    a.fill_(3.0)
+    pa, pb = pool["a"].data_ptr(), pool["b"].data_ptr()
+    for shape in ((5,), (2, 3), (1, 2, 3)):                                       # requests that fit: the same storage
+        fit = pool.take("a", shape, cpu)
+        assert fit.data_ptr() == pa and pool["a"].data_ptr() == pa and fit.shape == shape and bool((fit == 3.0).all())
+    grown = pool.take("a", (3, 3), cpu)                                           # a larger one: this name alone regrows, to the request
+    assert pool["a"].shape == (9,) and grown.shape == (3, 3) and not grown.any() and grown.data_ptr() == pool["a"].data_ptr()
+    assert pool["b"].data_ptr() == pb and pool["b"].numel() == 4
+    assert pool.take("a", (2, 3), cpu).data_ptr() == pool["a"].data_ptr() and pool["a"].numel() == 9      # never shrinks
+    none = pool.take("c", (0, 25), cpu)
+    assert none.shape == (0, 25) and pool["c"].numel() == 1 and pool.take("i", (3,), cpu, torch.int32).dtype == torch.int32
+    meta = pool.take("b", (2,), torch.device("meta"))                             # another device: reallocated, to the request
+    assert meta.device.type == "meta" and pool["b"].device.type == "meta" and pool["b"].numel() == 2
+    back = pool.take("b", (2,), cpu)
+    assert back.device.type == "cpu" and pool["b"].device.type == "cpu" and not back.any()
+    ws = pool.workspace(10, cpu)
+    assert ws.dtype == torch.uint8 and ws.numel() == 256 and pool["ws"] is ws and pool.workspace(200, cpu) is ws
+    assert pool.workspace(1000, cpu).numel() == 1000 and pool.workspace(10, cpu).numel() == 1000
+
+
+def _set_by_query(extra=()):
+    return {"mode", "flags", "F", "D", "C", "n_conv", "R", "N", "E", "B", "max_nodes", "max_edges",
+            "workspace_bytes_needed", "lds_bytes", *extra}
+
+
+_SHAPE_ARGS = {
+    "explain": (lambda m: ExplainStep(m), {}, _set_by_query()),
+    "fit": (lambda m: H.explain.ExplainFit(m), {}, _set_by_query()),
+    "ensemble": (lambda m: H.ensemble.EnsemblePredict([m]), {}, _set_by_query(("n_models", "models_per_group"))),
+    "shapley": (lambda m: H.shapley.ShapleySampling(m), dict(perm_count=3), _set_by_query(("perm_count",))),
+    "shapley_grouped": (lambda m: H.shapley.ShapleySampling(m),
+                        dict(perm_count=3, flags=_lib.HCG_EXPLAIN_QUERY | _lib.HCG_EXPLAIN_GROUPED, shap_n_groups=7),
+                        _set_by_query(("perm_count", "shap_n_groups"))),
+    "integrated": (lambda m: H.attribution.IntegratedGradients(m), {}, _set_by_query()),
+    "ensemble_attribution": (lambda m: H.attribution.EnsembleAttribution([m]), {}, _set_by_query(("n_models",))),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_SHAPE_ARGS))
+def test_shape_query_leaves_nothing_of_an_earlier_launch(name):
+    """A class reuses one argument block, whose `fit_` / `path_` / `mom_` / `shap_` members overlay one union: whatever an
+    earlier launch left there must not reach the next one.  Every byte of a block is set to 0xFF; after the class's
+    `_shape_args` every byte outside the members the query itself sets (shapes, mode, flags, its counts and the library's
+    two answers) is 0, so a launch reads only what the class sets after the query.  Before `_frozen.query` cleared the
+    block this failed for every class: each nulled a hand-kept list of pointers and left the rest."""
+    import hcatgnet_amd.attribution, hcatgnet_amd.ensemble, hcatgnet_amd.shapley  # noqa: F401
+    make, extra, set_here = _SHAPE_ARGS[name]
+    obj = make(H.make_network("GCN", H.default_options(), 25))
+    a = _lib.ExplainArgs()
+    size = ctypes.sizeof(a)
+    ctypes.memset(ctypes.addressof(a), 0xFF, size)
+    batch = _stand_in(N=30, E=64, max_nodes=30, max_edges=64, edges_grouped=True)
+    assert obj._shape_args(a, batch, **extra) is None
+    assert (a.N, a.E, a.B, a.F, a.max_nodes, a.max_edges) == (30, 64, 1, 25, 30, 64)
+    assert a.workspace_bytes_needed > 0 or name == "ensemble"                  # (the ensemble kernel needs no workspace)
+    left = bytearray(ctypes.string_at(ctypes.addressof(a), size))
+    span = lambda f: range(getattr(_lib.ExplainArgs, f).offset, getattr(_lib.ExplainArgs, f).offset + getattr(_lib.ExplainArgs, f).size)
+    written = set()
+    for field in set_here:
+        written.update(span(field))
+    for i in written:
+        left[i] = 0
+    stale = [i for i, v in enumerate(left) if v]
+    assert not stale, f"{len(stale)} stale bytes, the first at offset {stale[0]}"
+    # the same, member by member: the structure's own fields and the three blocks that overlay its `fit_` members
+    names = [f[0] for f in _lib.ExplainArgs._fields_] + [f[0] for f in _lib.PATH_FIELDS + _lib.MOMENT_FIELDS + _lib.SHAPLEY_GROUP_FIELDS]
+    assert len(names) > 100
+    for field in names:
+        if field in set_here or written.intersection(span(field)):
+            continue
+        v = getattr(a, field)
+        assert v is None or v == 0 or (not isinstance(v, (int, float)) and not any(v)), field       # (pointer, number, array)
