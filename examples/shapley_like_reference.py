@@ -12,10 +12,12 @@ Captum draws them its own way), and neither captum nor torch_geometric is a depe
 `--players` chooses who is credited (Captum's `feature_mask`): `entries` (every node-feature entry and every directed edge,
 the reference's setting), `atoms` (one player per atom, the bonds always present), `atoms+bonds` (atoms and undirected
 bonds) or `fragments` (the synthetic graphs get three contiguous node ranges as fragments; all 3! orders are walked, which
-is the exact Shapley value for 4 evaluations per order).
+is the exact Shapley value for 4 evaluations per order).  With `--coalitions` the fragments go through `CoalitionValues`
+instead: every subset of them evaluated once, exact Shapley values and the pairwise interaction matrix from that table.
 
     python examples/shapley_like_reference.py --graphs 64 --samples 25
     python examples/shapley_like_reference.py --graphs 64 --players fragments
+    python examples/shapley_like_reference.py --graphs 64 --players fragments --coalitions
 """
 from __future__ import annotations
 
@@ -56,6 +58,21 @@ def grouped(a, sv, batch):
           [round(v, 5) for v in g0[torch.argsort(g0.abs(), descending=True)[:5]].tolist()])
 
 
+def coalitions(model, batch):
+    """Three fragments per graph through the table of all 2^3 subsets: exact Shapley values and who matters together."""
+    n = torch.bincount(batch.batch, minlength=batch.num_graphs)
+    frag = H.atom_groups(batch) * 3 // n[batch.batch]
+    cv = H.CoalitionValues(model)
+    r = cv(batch, node_group=frag, class_index=0)
+    print(f"path {cv.last_path}: {batch.num_graphs} graphs, {r.values.shape[0]} subsets of 3 fragments evaluated")
+    G = int(r.group_ptr[1])
+    print("graph 0, output per subset (bit y = fragment y on):", [round(v, 5) for v in r.values[:int(r.table_ptr[1]), 0].tolist()])
+    print("graph 0, exact Shapley values:", [round(v, 5) for v in r.group_attr[:G].tolist()])
+    print("graph 0, Shapley interaction indices:")
+    for row in r.interaction[:int(r.pair_ptr[1])].view(G, G).tolist():
+        print("   ", [round(v, 5) for v in row])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=64)
@@ -63,13 +80,18 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--nonzero-share", type=float, default=0.2, help="share of the node-feature entries kept non-zero (one-hot-like)")
     ap.add_argument("--players", choices=("entries", "atoms", "atoms+bonds", "fragments"), default="entries")
+    ap.add_argument("--coalitions", action="store_true", help="with --players fragments: every subset through CoalitionValues")
     a = ap.parse_args()
+    if a.coalitions and a.players != "fragments":
+        ap.error("--coalitions goes with --players fragments")
     model = H.make_network("GCN", H.default_options(), 25).cuda()
     sb = synth.make_batch(num_graphs=a.graphs, nodes=87, nodes_jitter=30, extra_bonds=4, max_degree=4, feat=25)
     keep = torch.rand(sb.x.shape, generator=torch.Generator().manual_seed(a.seed)) < a.nonzero_share
     sb.x = (sb.x * keep).contiguous()
     batch = sb.as_batch("cuda")
 
+    if a.coalitions:
+        return coalitions(model, batch)
     sv = H.ShapleySampling(model)
     if a.players != "entries":
         return grouped(a, sv, batch)

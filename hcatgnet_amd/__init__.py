@@ -23,6 +23,9 @@ Public surface (mirrors the reference's names for this path):
                                                 (the reference's second explain algorithm, explain_gnn.py)
     atom_groups, bond_groups, draw_group_permutations, all_group_permutations
                                                 the same walk with atoms, bonds or fragments as the players
+    CoalitionValues, shapley_from_coalitions, interactions_from_coalitions
+                                                the model's output for every subset of a graph's groups (up to 16), evaluated
+                                                on chip; exact Shapley values and pairwise interaction indices from that table
     IntegratedGradients, quadrature             integrated gradients (Captum's IntegratedGradients through the same
                                                 CaptumExplainer entry point) of a batch of graphs, the whole path of every
                                                 graph in one launch; method="gradient" / saliency=True are its one-step
@@ -40,8 +43,9 @@ from .fit import FitControl, FitResult, fit_network, fit_networks  # noqa: F401
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
 from .networks import BaseNetwork  # noqa: F401
 from .plan import BatchPlan  # noqa: F401
-from .shapley import (GroupedShapleyResult, ShapleyResult, ShapleySampling, all_group_permutations, atom_groups,  # noqa: F401
-                      bond_groups, draw_group_permutations, draw_permutations)
+from .shapley import (CoalitionResult, CoalitionValues, GroupedShapleyResult, ShapleyResult, ShapleySampling,  # noqa: F401
+                      all_group_permutations, atom_groups, bond_groups, draw_group_permutations, draw_permutations,
+                      interactions_from_coalitions, shapley_from_coalitions)
 from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
 
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
@@ -49,4 +53,5 @@ __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "
            "stack_weights", "ShapleySampling", "ShapleyResult", "draw_permutations", "GroupedShapleyResult", "atom_groups",
            "bond_groups", "draw_group_permutations", "all_group_permutations", "ExplainFit", "ExplainFitResult",
            "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
-           "quadrature", "EnsembleAttribution", "EnsembleAttributionResult"]
+           "quadrature", "EnsembleAttribution", "EnsembleAttributionResult", "CoalitionValues", "CoalitionResult",
+           "shapley_from_coalitions", "interactions_from_coalitions"]

@@ -126,6 +126,8 @@ int hcg_edge_weight_grad_launch(const float* dout, const float* out, const float
 int hcg_ensemble_launch(hcg_explain_args* p, hipStream_t stream);
 // ---- Shapley value sampling (shapley.hip), reached through hcg_explain, mode HCG_EXPLAIN_SHAPLEY -------------------------
 int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream);
+// mode HCG_EXPLAIN_COALITIONS: the table over every subset of a graph's live groups
+int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream);
 
 // ---- the fit controller (fit.hip), reached through hcg_update_dev (optim.hip): `fit_control` of hcg_update_args ----------
 int hcg_fit_control_launch(const hcg_fit_control_args* a, hipStream_t stream);

@@ -283,9 +283,10 @@ inline int x_shapes_ok(const hcg_explain_args* p) {
 }
 
 
-// the pointers every mode needs for a launch (the per-mode ones are checked in the mode's file)
-inline bool x_common_ok(const hcg_explain_args* p) {
-  if (!p->graph_ptr || !p->edge_ptr || !p->out || !p->status || (p->N > 0 && !p->x) || (p->E > 0 && !p->edge_index)) return false;
+// the pointers every mode needs for a launch (the per-mode ones are checked in the mode's file; HCG_EXPLAIN_COALITIONS writes
+// its table and no `out`)
+inline bool x_common_ok(const hcg_explain_args* p, bool with_out = true) {
+  if (!p->graph_ptr || !p->edge_ptr || (with_out && !p->out) || !p->status || (p->N > 0 && !p->x) || (p->E > 0 && !p->edge_index)) return false;
   for (int l = 0; l < p->n_conv; ++l)
     if (!p->conv_W[l] || !p->conv_b[l]) return false;
   for (int i = 0; i < p->R; ++i)

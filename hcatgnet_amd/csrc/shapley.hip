@@ -40,6 +40,9 @@
 // member range is a group that cannot change the output (0 at once, no evaluation); pj / pv carry the queued group ids and
 // their first member positions.  Permutation rows, workspace rows and the accumulator have one entry per group.  No LDS is
 // added: the members are staged through t1, which is idle between two evaluations.
+// HCG_EXPLAIN_COALITIONS (k_coalition_values, below the walk): every subset of a graph's live groups evaluated once, the state
+// rebuilt from zero per subset.  Build (s_build), weights in registers (s_load_weights), application (s_apply) and evaluation
+// (s_eval) are the walk's: both kernels call the same four functions.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -153,6 +156,83 @@ __device__ __forceinline__ void s_apply(const SLds& L, const XCommon& cm, const 
   }
 }
 
+// One evaluation of the state in LDS (h1, mval): conv stack, pooling, readout -> the position of the output row in hv.  `w` is
+// the lane's weight row of conv layer 2 (models of two conv layers: loaded once by the caller; deeper stacks reload it here),
+// rw0 the thread's 16 weights of readout layer 0 (W[ro][rsub + 8 k], zero for a thread without an output).  Opens on the
+// caller's barrier behind the last change of the state, ends behind a barrier; k_shapley_walk and k_coalition_values both
+// evaluate through this and nothing else.
+__device__ __forceinline__ int s_eval(const SLds& L, const XCommon& cm, const XMasked fmt, float (&w)[XD], const float (&rw0)[16],
+                                      int n, int tid) {
+  const int lane = tid & 63, wave = tid >> 6, ro = tid >> 3, rsub = tid & 7;
+  const int C = cm.C, R = cm.R, n_conv = cm.n_conv;
+#pragma nounroll
+  for (int l = 0; l < n_conv; ++l) {
+    if (l > 0) {
+      if (n_conv > 2) x_weight_row(w, reinterpret_cast<const char*>(x_pick(cm.cW, l)), lane, XD);
+      x_gemm(L.t0, w, n, wave, [&](int r, float v) { L.t1[r * XS + lane] = v; });
+      __syncthreads();
+    }
+    x_conv_out(l == 0 ? L.h1 : L.t1, L.t0, L.ent, L.rowptr, fmt, L.dinv, x_pick(cm.cb, l), n, tid, cm.slope,
+               [](int, int, float4) {});
+    __syncthreads();
+  }
+  // pooling (t0 = A of the last layer; the partials alias t1), readout
+  x_pool(L.t0, L.t1, L.hv, n, tid);
+  int off = 0;
+  for (int i = 0; i < R; ++i) {
+    const int in_i = (2 * XD) >> i, out_i = i == R - 1 ? C : in_i / 2;
+    float p = 0.f;
+    if (i == 0) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) p = fmaf(rw0[k], L.hv[rsub + 8 * k], p);
+    } else if (ro < out_i) {
+      const float* W = x_pick(cm.hW, i) + (size_t)ro * in_i;
+      for (int k = rsub; k < in_i; k += 8) p = fmaf(W[k], L.hv[off + k], p);
+    }
+    p += __shfl_xor(p, 1, 8);
+    p += __shfl_xor(p, 2, 8);
+    p += __shfl_xor(p, 4, 8);
+    if (ro < out_i && rsub == 0) {
+      const float y = p + x_pick(cm.hb, i)[ro];
+      L.hv[off + in_i + ro] = i == R - 1 ? y : hcg_leaky(y, cm.slope);
+    }
+    off += in_i;
+    __syncthreads();
+  }
+  return off;
+}
+
+// The weights every evaluation of a workgroup reuses, loaded once: the lane's row of conv layer 2 (two conv layers) and the
+// thread's share of readout layer 0.
+__device__ __forceinline__ void s_load_weights(float (&w)[XD], float (&rw0)[16], const XCommon& cm, int tid) {
+  const int lane = tid & 63, ro = tid >> 3, rsub = tid & 7;
+  if (cm.n_conv == 2) x_weight_row(w, reinterpret_cast<const char*>(cm.cW[1]), lane, XD);
+  const int out0 = cm.R == 1 ? cm.C : XD;
+  const float* W = cm.hW[0] + (size_t)(ro < out0 ? ro : 0) * (2 * XD) + rsub;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const float v = W[8 * k];
+    rw0[k] = ro < out0 ? v : 0.f;
+  }
+}
+
+// The graph, once per workgroup (both kernels): the by-destination entry list, dinv, h1 = 0 and mval = 0 for an edge with an
+// entry, -1 for one without.  Ends behind a barrier.
+__device__ __forceinline__ void s_build(const SLds& L, const XCommon& cm, const XSpan& sp, int tid) {
+  const int n = sp.n, ne = sp.ne;
+  EdgeRegs<X_EPT, XT> er;
+  er.load(XGraph{sp.ebase, sp.ne}, cm.ei, cm.E, tid);
+  for (int i = tid; i < cm.npad; i += XT) L.cnt[i] = 0;
+  for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;       // everything off
+  XEdges q;
+  x_edge_pass(q, er, sp, tid, cm.status);
+  x_build_rows<XMasked, false>(q, {L.ent, L.rowptr, L.cnt}, {}, L.dinv, n, tid);
+#pragma unroll
+  for (int j = 0; j < X_EPT; ++j)
+    if (tid + j * XT < ne) L.mval[tid + j * XT] = q.live[j] ? 0.f : -1.f;
+  __syncthreads();
+}
+
 // GROUPED = false: one feature per step (Args = SArgs).  GROUPED = true: HCG_EXPLAIN_GROUPED (Args = SGArgs) -- the players are
 // the graph's groups, a step switches on every live member of one group and is evaluated once, and the live background is on
 // from the base evaluation on.  The ungrouped instantiation is the kernel as it was before the template.
@@ -163,7 +243,7 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
   const SLds L = s_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x;
-  const int F = cm.F, C = cm.C, R = cm.R, n_conv = cm.n_conv;
+  const int F = cm.F, C = cm.C;
   const bool p0 = a.first + (int)blockIdx.y == 0;          // permutation 0 of the whole call writes out / out_base
   float* const wsrow = a.ws + (size_t)blockIdx.y * (size_t)a.row;
 
@@ -192,33 +272,13 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
 
   // ---------------------------------------------------------------------------------------------- build (once per workgroup)
   const int nbase = sp.nbase, ebase = sp.ebase, n = sp.n, ne = sp.ne;
-  EdgeRegs<X_EPT, XT> er;
-  er.load(XGraph{sp.ebase, sp.ne}, cm.ei, cm.E, tid);
-  for (int i = tid; i < cm.npad; i += XT) L.cnt[i] = 0;
-  for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;       // everything off
-  XEdges q;
-  x_edge_pass(q, er, sp, tid, cm.status);
+  s_build(L, cm, sp, tid);
   const XMasked fmt{L.mval};
-  x_build_rows<XMasked, false>(q, {L.ent, L.rowptr, L.cnt}, {}, L.dinv, n, tid);
-#pragma unroll
-  for (int j = 0; j < X_EPT; ++j)
-    if (tid + j * XT < ne) L.mval[tid + j * XT] = q.live[j] ? 0.f : -1.f;
-  __syncthreads();
 
   // ---------------------------------------------------------------------------------------------- what every evaluation reuses
-  const int ro = tid >> 3, rsub = tid & 7;                // readout: 8 lanes per output
   float w[XD];                                            // the lane's weight row of a conv layer >= 2
-  if (n_conv == 2) x_weight_row(w, reinterpret_cast<const char*>(cm.cW[1]), lane, XD);
   float rw0[16];                                          // readout layer 0: W[ro][rsub + 8 k]
-  {
-    const int out0 = R == 1 ? C : XD;
-    const float* W = cm.hW[0] + (size_t)(ro < out0 ? ro : 0) * (2 * XD) + rsub;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const float v = W[8 * k];
-      rw0[k] = ro < out0 ? v : 0.f;
-    }
-  }
+  s_load_weights(w, rw0, cm, tid);
 
   const int nF = n * F, K = nF + ne;                      // the graph's features
   int gp = 0, steps = K;                                  // GROUPED: the graph's first group and its number of groups
@@ -299,42 +359,7 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
       __syncthreads();
     }
 
-    // -------------------------------------------------------------------------------------------- evaluate: conv stack
-#pragma nounroll
-    for (int l = 0; l < n_conv; ++l) {
-      if (l > 0) {
-        if (n_conv > 2) x_weight_row(w, reinterpret_cast<const char*>(x_pick(cm.cW, l)), lane, XD);
-        x_gemm(L.t0, w, n, wave, [&](int r, float v) { L.t1[r * XS + lane] = v; });
-        __syncthreads();
-      }
-      x_conv_out(l == 0 ? L.h1 : L.t1, L.t0, L.ent, L.rowptr, fmt, L.dinv, x_pick(cm.cb, l), n, tid, cm.slope,
-                 [](int, int, float4) {});
-      __syncthreads();
-    }
-
-    // -------------------------------------------------------------------------------------------- pooling (t0 = A of the last layer; the partials alias t1), readout
-    x_pool(L.t0, L.t1, L.hv, n, tid);
-    off = 0;
-    for (int i = 0; i < R; ++i) {
-      const int in_i = (2 * XD) >> i, out_i = i == R - 1 ? C : in_i / 2;
-      float p = 0.f;
-      if (i == 0) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) p = fmaf(rw0[k], L.hv[rsub + 8 * k], p);
-      } else if (ro < out_i) {
-        const float* W = x_pick(cm.hW, i) + (size_t)ro * in_i;
-        for (int k = rsub; k < in_i; k += 8) p = fmaf(W[k], L.hv[off + k], p);
-      }
-      p += __shfl_xor(p, 1, 8);
-      p += __shfl_xor(p, 2, 8);
-      p += __shfl_xor(p, 4, 8);
-      if (ro < out_i && rsub == 0) {
-        const float y = p + x_pick(cm.hb, i)[ro];
-        L.hv[off + in_i + ro] = i == R - 1 ? y : hcg_leaky(y, cm.slope);
-      }
-      off += in_i;
-      __syncthreads();
-    }
+    off = s_eval(L, cm, fmt, w, rw0, n, tid);
     const float v = L.hv[off + a.cls];
     if (base) {
       if (p0 && tid < C) a.out_base[(size_t)g * C + tid] = L.hv[off + tid];
@@ -348,6 +373,86 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
   // hv still holds the last evaluation: everything on (features that were skipped change nothing; GROUPED: every live
   // feature is in the background or in a group)
   if (p0 && tid < C) a.out[(size_t)g * C + tid] = L.hv[off + tid];
+}
+
+// HCG_EXPLAIN_COALITIONS: the table v(S) over every subset S of a graph's LIVE groups.  One workgroup per job (graph, run of
+// consecutive subset masks), the LDS layout and the build of k_shapley_walk<true>.  For every mask m of the run the state is
+// rebuilt from zero -- h1 = 0, mval = 0 for every edge with an entry, the live background applied, then the k-th live group for
+// every set bit k of m, ascending, all through s_apply -- and evaluated once (s_eval); thread c < C writes output c to row
+// live_ptr[g] + m.  Nothing is carried from one mask to the next, so a row is bitwise independent of the run it sits in, of
+// the launch and of the rest of the batch; every row has one writer, there is no workspace, no reduce and no atomics.  The
+// state of mask 2^(y + 1) - 1 takes the updates the walk's state takes in the identity order up to group y, in that order.
+struct CArgs {
+  XCommon c;
+  float* table;                             // [rows][C]
+  const int32_t* jobs;                      // [.][3] graph, first mask, masks
+  const long long* live_ptr;                // [B + 1] graph g's rows: live_ptr[g] + mask
+  const int32_t* group_ptr;                 // [B + 1] the LIVE groups of graph g (the grouped block's arrays)
+  const int32_t* member_ptr;                // [G + 1]
+  const int32_t* members;
+  const int32_t* bg_ptr;                    // [B + 1]
+  const int32_t* bg_members;
+  long long rows, G, B;
+  int first;                                // first job of this launch
+};
+
+constexpr int C_MAX_GROUPS = 16;
+
+__global__ __launch_bounds__(XT) void k_coalition_values(const CArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const XCommon& cm = a.c;
+  const SLds L = s_carve(smem, cm.npad, cm.emax);
+  const int tid = threadIdx.x;
+  const int C = cm.C;
+  const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
+  const int g = __builtin_amdgcn_readfirstlane(job[0]);
+  const int m0 = __builtin_amdgcn_readfirstlane(job[1]);
+  const int mcount = __builtin_amdgcn_readfirstlane(job[2]);
+  if (g < 0 || g >= a.B) return;
+  const int gp = __builtin_amdgcn_readfirstlane(a.group_ptr[g]);
+  const int ng = __builtin_amdgcn_readfirstlane(a.group_ptr[g + 1]) - gp;
+  if (ng < 0 || ng > C_MAX_GROUPS || gp < 0 || (long long)gp + ng > a.G) return;
+  // the masks of the run that exist and whose rows lie inside the table
+  const long long lp = a.live_ptr[g];
+  const long long mlo = max(0ll, max((long long)m0, -lp));
+  const long long mhi = min(min((long long)m0 + mcount, 1ll << ng), a.rows - lp);
+
+  XSpan sp;
+  if (x_refused(sp, cm, g, tid)) {
+    for (long long k = mlo * C + tid; k < mhi * C; k += XT) a.table[lp * C + k] = 0.f;
+    return;
+  }
+  const int nbase = sp.nbase, n = sp.n, ne = sp.ne;
+  s_build(L, cm, sp, tid);
+  const XMasked fmt{L.mval};
+  float w[XD];
+  float rw0[16];
+  s_load_weights(w, rw0, cm, tid);
+  const int nF = n * cm.F, K = nF + ne;
+  const int bb = __builtin_amdgcn_readfirstlane(a.bg_ptr[g]), be = __builtin_amdgcn_readfirstlane(a.bg_ptr[g + 1]);
+
+#pragma nounroll
+  for (long long mm = mlo; mm < mhi; ++mm) {
+    const int m = (int)mm;
+    // everything off (the evaluation before ended behind a barrier: h1, mval and t1 are idle)
+    for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
+#pragma unroll
+    for (int j = 0; j < X_EPT; ++j)
+      if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
+    __syncthreads();
+    s_apply(L, cm, a.bg_members, bb, be, nbase, nF, K, tid);
+#pragma nounroll
+    for (int k = 0; k < ng; ++k)
+      if ((m >> k) & 1) {
+        __syncthreads();                                   // (the staging of the list before has been read)
+        s_apply(L, cm, a.members, __builtin_amdgcn_readfirstlane(a.member_ptr[gp + k]),
+                __builtin_amdgcn_readfirstlane(a.member_ptr[gp + k + 1]), nbase, nF, K, tid);
+      }
+    __syncthreads();
+    const int off = s_eval(L, cm, fmt, w, rw0, n, tid);
+    if (tid < C) a.table[(lp + mm) * C + tid] = L.hv[off + tid];
+    // (hv is next written behind the barriers of the next evaluation's conv stack)
+  }
 }
 
 // acc[i] (+)= sum_p ws[p][i], p ascending; the call that ends at the last permutation divides by their number
@@ -415,4 +520,38 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
     HCG_CHECK_LAUNCH();
   }
   return HCG_OK;
+}
+
+// hcg_explain, mode HCG_EXPLAIN_COALITIONS (explain.hip dispatches here)
+int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  if (p->coal_max_live > C_MAX_GROUPS || p->coal_rows >= (1ll << 31)) return HCG_ERR_UNSUPPORTED;
+  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
+  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
+  p->lds_bytes = (int32_t)lds;
+  p->workspace_bytes_needed = 0;
+  if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
+  if (p->coal_max_live < 0 || p->coal_rows < 0 || p->shap_n_groups < 0 || p->coal_job_first < 0 || p->coal_job_count < 0)
+    return HCG_ERR_INVALID_ARG;
+  if (p->B == 0 || p->coal_job_count == 0) return HCG_OK;
+  if (!x_common_ok(p, false) || !p->coal_values || !p->coal_jobs || !p->coal_live_ptr || !p->shap_group_ptr ||
+      !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members)
+    return HCG_ERR_INVALID_ARG;
+
+  CArgs a;
+  x_fill_common(a.c, p, S_NPAD_MIN);
+  a.table = p->coal_values;
+  a.jobs = p->coal_jobs;
+  a.live_ptr = reinterpret_cast<const long long*>(p->coal_live_ptr);
+  a.group_ptr = p->shap_group_ptr;
+  a.member_ptr = p->shap_member_ptr;
+  a.members = p->shap_members;
+  a.bg_ptr = p->shap_bg_ptr;
+  a.bg_members = p->shap_bg_members;
+  a.rows = p->coal_rows;
+  a.G = p->shap_n_groups;
+  a.B = p->B;
+  a.first = p->coal_job_first;
+  return x_launch<k_coalition_values>(dim3((unsigned)p->coal_job_count), lds, stream, a);
 }

@@ -17,11 +17,17 @@ are partitioned into groups -- an atom, a bond, a fragment -- that are switched 
 a background that is always on.  The same kernel walks them (`HCG_EXPLAIN_GROUPED`): a step applies every live member of
 its group and is evaluated once.  `atom_groups`, `bond_groups`, `draw_group_permutations` and `all_group_permutations`
 build the usual arguments.
+
+Coalition values: `CoalitionValues` evaluates EVERY subset of a graph's groups once (2^G states where all G! orders cost
+G G! evaluations; up to 16 groups) with a second kernel of csrc/shapley.hip that shares the walk's build, application and
+evaluation (`HCG_EXPLAIN_COALITIONS`).  Exact Shapley values and pairwise Shapley interaction indices are fixed linear forms
+of that table: `shapley_from_coalitions`, `interactions_from_coalitions`.
 """
 from __future__ import annotations
 
 import ctypes
 import itertools
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -202,7 +208,9 @@ def draw_group_permutations(batch, node_group=None, edge_group=None, n_samples: 
 
 def all_group_permutations(batch, node_group=None, edge_group=None) -> torch.Tensor:
     """int32 [G_g!, G]: every order of the groups, for a batch whose graphs all have the same G_g <= 6 (ValueError
-    otherwise).  The mean over these rows is the exact Shapley value of the groups."""
+    otherwise).  The mean over these rows is the exact Shapley value of the groups, at G_g * G_g! evaluations per graph;
+    `CoalitionValues` gives the same values from the 2^G_g distinct states, for up to 16 groups, with the pairwise
+    interaction indices."""
     gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
     counts = set(gr.count.tolist())
     if len(counts) > 1 or (counts and max(counts) > 6):
@@ -477,3 +485,315 @@ class ShapleySampling(_frozen.FrozenModel):
         acc = acc / float(P)
         self.last_path = "loop"
         return pl.result(acc, out_full, out_base)
+
+
+# ====================================================================== coalition values: every subset of a graph's groups
+MAX_COALITION_GROUPS = 16          # groups of one graph: 2^16 rows
+SUBSETS_PER_WORKGROUP = 16         # the longest run of masks one workgroup evaluates (`default_subsets_per_workgroup`)
+
+
+class CoalitionResult(NamedTuple):
+    values: torch.Tensor         # [T, C]: values[table_ptr[g] + s] = the output with the background and the groups {y : bit y of s} on
+    table_ptr: torch.Tensor      # [B + 1] int64, T = sum_g 2^G_g
+    group_ptr: torch.Tensor      # [B + 1] int64
+    group_attr: torch.Tensor     # [G] the exact Shapley value of every group for `class_index`
+    interaction: torch.Tensor    # [Q] graph g's G_g x G_g Shapley interaction indices, row-major at pair_ptr[g]
+    pair_ptr: torch.Tensor       # [B + 1] int64, Q = sum_g G_g^2
+    out_full: torch.Tensor       # [B, C] everything on: row 2^G_g - 1 of the graph
+    out_base: torch.Tensor       # [B, C] the background only: row 0
+
+
+def _popcount(t: torch.Tensor, bits: int) -> torch.Tensor:
+    size = torch.zeros_like(t)
+    for y in range(bits):
+        size += (t >> y) & 1
+    return size
+
+
+def _spread(t: torch.Tensor, at: int) -> torch.Tensor:
+    """`t` with a 0 bit inserted at position `at`"""
+    return ((t >> at) << (at + 1)) | (t & ((1 << at) - 1))
+
+
+def _counts(ptr) -> list:
+    """Host list of the per-graph counts of a [B + 1] prefix sum (one read)."""
+    p = ptr.tolist()
+    return [b - a for a, b in zip(p[:-1], p[1:])]
+
+
+def _by_count(counts: list):
+    """distinct G_g > 0 -> the graphs that have it, ascending"""
+    by = {}
+    for g, c in enumerate(counts):
+        if c > 0:
+            by.setdefault(c, []).append(g)
+    return sorted(by.items())
+
+
+def _tables(values, table_ptr, graphs: list, Gv: int, class_index: int) -> torch.Tensor:
+    """float64 [len(graphs), 2^Gv]: column `class_index` of the tables of `graphs`, which all have Gv groups"""
+    dev = values.device
+    first = table_ptr[torch.tensor(graphs, dtype=torch.int64, device=dev)]
+    return values[:, class_index][first.unsqueeze(1) + torch.arange(1 << Gv, device=dev)].to(torch.float64)
+
+
+def _check_table(values, table_ptr, group_ptr, class_index):
+    if values.dim() != 2 or not 0 <= int(class_index) < values.shape[1]:
+        raise ValueError(f"values must be [T, C] and class_index lie in 0 .. C - 1; got {tuple(values.shape)}, {class_index}")
+    if table_ptr.numel() != group_ptr.numel():
+        raise ValueError("table_ptr and group_ptr must both be [B + 1]")
+
+
+def _shapley_of(values, table_ptr, counts: list, class_index: int) -> torch.Tensor:
+    dev = values.device
+    gptr = [0]
+    for c in counts:
+        gptr.append(gptr[-1] + c)
+    phi = torch.zeros(gptr[-1], dtype=torch.float64, device=dev)
+    for Gv, graphs in _by_count(counts):
+        V = _tables(values, table_ptr, graphs, Gv, class_index)
+        rest = torch.arange(1 << (Gv - 1), device=dev)                     # the subsets of the other groups, packed
+        size = _popcount(rest, Gv - 1)
+        fact = [math.factorial(k) for k in range(Gv + 1)]
+        w = torch.tensor([fact[k] * fact[Gv - k - 1] / fact[Gv] for k in range(Gv)], dtype=torch.float64, device=dev)[size]
+        at = torch.tensor([gptr[g] for g in graphs], dtype=torch.int64, device=dev)
+        for y in range(Gv):
+            S = _spread(rest, y)
+            # (the difference first: a group whose rows repeat the rows without it gets exactly 0)
+            phi[at + y] = ((V[:, S | (1 << y)] - V[:, S]) * w).sum(1)
+    return phi.to(torch.float32)
+
+
+def _interactions_of(values, table_ptr, counts: list, class_index: int):
+    dev = values.device
+    pptr = [0]
+    for c in counts:
+        pptr.append(pptr[-1] + c * c)
+    out = torch.zeros(pptr[-1], dtype=torch.float64, device=dev)
+    for Gv, graphs in _by_count(counts):
+        if Gv < 2:
+            continue
+        V = _tables(values, table_ptr, graphs, Gv, class_index)
+        rest = torch.arange(1 << (Gv - 2), device=dev)
+        size = _popcount(rest, Gv - 2)
+        fact = [math.factorial(k) for k in range(Gv + 1)]
+        w = torch.tensor([fact[k] * fact[Gv - k - 2] / fact[Gv - 1] for k in range(Gv - 1)], dtype=torch.float64, device=dev)[size]
+        at = torch.tensor([pptr[g] for g in graphs], dtype=torch.int64, device=dev)
+        for i in range(Gv):
+            for j in range(i + 1, Gv):
+                S = _spread(_spread(rest, i), j)                           # (i < j: the lower bit goes in first)
+                bi, bj = 1 << i, 1 << j
+                # (the differences of rows that repeat each other first: a dead group's row and column are exactly 0)
+                d = (V[:, S | bi | bj] - V[:, S | bj]) - (V[:, S | bi] - V[:, S])
+                val = (d * w).sum(1)
+                out[at + i * Gv + j] = val
+                out[at + j * Gv + i] = val
+    return out.to(torch.float32), torch.tensor(pptr, dtype=torch.int64, device=dev)
+
+
+def shapley_from_coalitions(values, table_ptr, group_ptr, class_index: int = 0) -> torch.Tensor:
+    """float32 [G]: the exact Shapley value of every group for output column `class_index`, from a table of coalition
+    values (`CoalitionResult.values`, `.table_ptr`, `.group_ptr`):
+        phi_y = sum over S not containing y of |S|! (G - |S| - 1)! / G! (v(S + y) - v(S)).
+    Formed in float64 on the table's device, vectorised over the graphs that share a G_g (a loop over the groups, none
+    over the subsets), rounded to float32.  One host read: `group_ptr`."""
+    _check_table(values, table_ptr, group_ptr, class_index)
+    return _shapley_of(values, table_ptr, _counts(group_ptr), int(class_index))
+
+
+def interactions_from_coalitions(values, table_ptr, group_ptr, class_index: int = 0):
+    """-> (float32 [Q], pair_ptr [B + 1] int64): graph g's G_g x G_g matrix of Shapley interaction indices (Grabisch and
+    Roubens), row-major at pair_ptr[g], symmetric, 0 on the diagonal:
+        I_ij = sum over S within the others of |S|! (G - |S| - 2)! / (G - 1)! (v(S+i+j) - v(S+i) - v(S+j) + v(S)).
+    Formed as `shapley_from_coalitions` forms its values (a loop over the pairs of groups, none over the subsets)."""
+    _check_table(values, table_ptr, group_ptr, class_index)
+    return _interactions_of(values, table_ptr, _counts(group_ptr), int(class_index))
+
+
+class CoalitionValues(_frozen.FrozenModel):
+    """The model's output for EVERY subset of each graph's groups, and what follows from that table.
+
+        cv = CoalitionValues(model)
+        r = cv(batch, node_group=None, edge_group=None, class_index=0, subsets_per_workgroup=None)
+        # CoalitionResult(values [T, C], table_ptr [B + 1], group_ptr [B + 1], group_attr [G], interaction [Q],
+        #                 pair_ptr [B + 1], out_full [B, C], out_base [B, C])
+
+    `node_group` / `edge_group` are `ShapleySampling`'s: local ids 0 .. G_g - 1, -1 for the background, the same checks and
+    errors.  A graph may have up to `MAX_COALITION_GROUPS` = 16 groups (ValueError before any launch otherwise), and the
+    table must fit `attribution.LAUNCH_BUDGET_BYTES` (ValueError: split the batch).  `values[table_ptr[g] + s]` is the
+    output [C] with the background and the groups {y : bit y of s} on, T = sum_g 2^G_g; row 0 is `out_base[g]`, row
+    2^G_g - 1 `out_full[g]`; a graph without groups has one row.  That is 2^G evaluations where all G! orders cost G G!,
+    and exact for up to 16 groups where `all_group_permutations` stops at 6.
+
+    `group_attr` is the exact Shapley value of every group for `class_index` and `interaction` the pairwise Shapley
+    interaction index (`shapley_from_coalitions`, `interactions_from_coalitions`: fixed linear forms of the table, formed
+    in float64 by torch ops; call them on `values` for another class without a second launch).
+
+    One workgroup evaluates a run of up to `subsets_per_workgroup` consecutive masks of one graph on chip
+    (csrc/shapley.hip, k_coalition_values): it builds the graph once and rebuilds the state from zero for every mask, so
+    every row is bitwise independent of the run length, of the launch split, of the run and of the rest of the batch, and
+    row 2^(y + 1) - 1 is bitwise what `ShapleySampling` evaluates after group y in the identity order.  A group without a
+    live member is not sent to the kernel: the kernel runs over the 2^L_g masks of the graph's live groups and the host
+    expands to [T, C] with one gather, so rows that differ only in dead groups are the same row, and a dead group's
+    Shapley value and interactions are exactly 0.  None for `subsets_per_workgroup`: `default_subsets_per_workgroup`.  Jobs
+    are split into launches by the estimate `ShapleySampling.default_samples_per_launch` uses (`jobs_per_launch`; set the
+    attribute to force a split).
+
+    Host reads, once per call each: what `_group_layout` reads (three scalars), and the per-graph group counts and live
+    counts, which give T, T_live and the job list.  `shapley_from_coalitions` called on its own reads `group_ptr`.
+
+    When `reason(batch)` is not None (shape outside the kernel, CPU tensors, `use_fused` off) the same call runs `loop`:
+    mask index s ascends, every graph with s < 2^G_g is switched to subset s and one masked forward of the whole batch
+    follows (forward-only `ExplainStep` on GPU tensors, plain torch ops on CPU tensors).  `last_path` says which one ran.
+    The returned tensors are new on the loop path; on the fused path `values`, `out_full` and `out_base` are new and the
+    kernel's own live table is a pool buffer."""
+
+    KERNEL, NAME = _lib.HCG_EXPLAIN_COALITIONS, "CoalitionValues"
+    jobs_per_launch: Optional[int] = None          # None: `default_jobs_per_launch`
+
+    def __init__(self, model: torch.nn.Module):
+        super().__init__(model)
+        self._step = ExplainStep(model, apply_sigmoid=False)
+
+    @staticmethod
+    def default_subsets_per_workgroup(live_rows: int) -> int:
+        """Masks per workgroup: up to `SUBSETS_PER_WORKGROUP` = 16, which spreads the graph's build (about the cost of one
+        evaluation) over 16 of them, but no more than leaves four workgroups for every CU -- a single graph of 10 groups
+        runs one mask per workgroup, 535 graphs of 6 groups run 16."""
+        return max(1, min(SUBSETS_PER_WORKGROUP, int(live_rows) // (4 * CUS)))
+
+    @staticmethod
+    def default_jobs_per_launch(subsets_per_workgroup: int) -> int:
+        """Workgroups of one launch by `default_samples_per_launch`'s estimate: a CU gets as many as fit `LAUNCH_SECONDS` at
+        `EVAL_SECONDS` per mask (the rebuild is counted as part of the evaluation: nobody has timed it apart), at most
+        `GROUPED_WORKGROUPS_PER_CU`."""
+        per_cu = max(1, int(LAUNCH_SECONDS / (max(int(subsets_per_workgroup), 1) * EVAL_SECONDS)))
+        return min(per_cu, GROUPED_WORKGROUPS_PER_CU) * CUS
+
+    # ------------------------------------------------------------------ what both paths share
+    def _layout(self, batch, node_group, edge_group):
+        """-> (the group layout, per-graph counts, per-graph live counts, live_group's rank inside its graph [G]); the
+        limits checked.  One host read beside `_group_layout`'s."""
+        F, B, dev = int(batch.x.shape[1]), int(batch.num_graphs), batch.x.device
+        gr = _group_layout(batch, F, node_group, edge_group)
+        if gr.max_groups > MAX_COALITION_GROUPS:
+            raise ValueError(f"a graph has {gr.max_groups} groups; CoalitionValues takes at most {MAX_COALITION_GROUPS} "
+                             f"(2^{MAX_COALITION_GROUPS} rows per graph)")
+        ggraph = torch.repeat_interleave(torch.arange(B, device=dev), gr.count, output_size=gr.G)
+        live = gr.live_group.to(torch.int64)
+        nlive = torch.zeros(B, dtype=torch.int64, device=dev).index_add_(0, ggraph, live)
+        lptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        lptr[1:] = nlive.cumsum(0)
+        rank = live.cumsum(0) - live - lptr[ggraph]                         # a live group's index among its graph's live groups
+        counts, lives = torch.stack([gr.count, nlive]).tolist() if B > 0 else ([], [])
+        C = int(self.model._n_classes)
+        T = sum(1 << c for c in counts)
+        from . import attribution
+        if T * C * 4 > attribution.LAUNCH_BUDGET_BYTES:
+            raise ValueError(f"the table of this batch has {T} rows of {C} outputs, {T * C * 4} bytes, above "
+                             f"LAUNCH_BUDGET_BYTES = {attribution.LAUNCH_BUDGET_BYTES}: split the batch")
+        return gr, counts, lives, (ggraph, lptr, rank)
+
+    @staticmethod
+    def _expand(gr, counts, lives, aux, dev):
+        """-> (table_ptr [B + 1], live_ptr [B + 1], index [T] int64): row table_ptr[g] + s of the full table is row
+        index[.] = live_ptr[g] + (the live bits of s, packed) of the live table."""
+        ggraph, lptr, rank = aux
+        B = len(counts)
+        rows = torch.tensor([1 << c for c in counts], dtype=torch.int64, device=dev)
+        tptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        tptr[1:] = rows.cumsum(0)
+        vptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        vptr[1:] = torch.tensor([1 << c for c in lives], dtype=torch.int64, device=dev).cumsum(0)
+        T = sum(1 << c for c in counts)
+        g = torch.repeat_interleave(torch.arange(B, device=dev), rows, output_size=T)
+        s = torch.arange(T, device=dev) - tptr[g]
+        packed = torch.zeros(T, dtype=torch.int64, device=dev)
+        if gr.G > 0:
+            for y in range(max(counts)):
+                has = (gr.count[g] > y) & (((s >> y) & 1) == 1)
+                at = torch.where(has, gr.group_ptr[g] + y, torch.zeros_like(s))
+                packed += torch.where(has & gr.live_group[at], torch.ones_like(s) << rank[at], torch.zeros_like(s))
+        return tptr, vptr, vptr[g] + packed
+
+    def _result(self, values, tptr, gr, counts, cls) -> CoalitionResult:
+        attr = _shapley_of(values, tptr, counts, cls)
+        inter, pptr = _interactions_of(values, tptr, counts, cls)
+        return CoalitionResult(values, tptr, gr.group_ptr, attr, inter, pptr, values[tptr[1:] - 1], values[tptr[:-1]])
+
+    # ------------------------------------------------------------------ the call
+    def __call__(self, batch, node_group=None, edge_group=None, class_index: int = 0, subsets_per_workgroup: Optional[int] = None):
+        a = self._args
+        if self._shape_args(a, batch) is not None:
+            return self.loop(batch, node_group, edge_group, class_index)
+        x = _frozen.batch_x(batch)
+        B, C, dev = a.B, a.C, x.device
+        cls = self._class(class_index)
+        gr, counts, lives, aux = self._layout(batch, node_group, edge_group)
+        tptr, vptr, index = self._expand(gr, counts, lives, aux, dev)
+        T_live = sum(1 << c for c in lives)
+        spw = self.default_subsets_per_workgroup(T_live) if subsets_per_workgroup is None else int(subsets_per_workgroup)
+        if spw < 1:
+            raise ValueError(f"subsets_per_workgroup must be at least 1; got {subsets_per_workgroup}")
+        spw = min(spw, 1 << MAX_COALITION_GROUPS)
+        # the jobs (graph, first mask, masks), built on the host from the live counts
+        jobs = [(g, m, min(spw, (1 << c) - m)) for g, c in enumerate(lives) for m in range(0, 1 << c, spw)]
+        J = len(jobs)
+        jobs_t = torch.tensor(jobs, dtype=torch.int32).reshape(J, 3).to(dev)
+        # the live groups' lists: a dead group's member range is empty, so dropping its pointer keeps the others' ranges
+        keep = torch.cat([gr.live_group, torch.ones(1, dtype=torch.bool, device=dev)])
+        member_ptr = gr.member_ptr[keep].contiguous()
+        live_ptr32 = aux[1].to(torch.int32)
+        table = self._bufs.take("table", (T_live, C), dev)
+        self.last_path = "fused"
+        if J == 0:                                                          # (no graph: nothing to launch)
+            return self._result(table[index], tptr, gr, counts, cls)
+        _frozen.query(a, self.KERNEL, self._shape(), batch, coal_rows=T_live, coal_max_live=max(lives))
+        self._fill(a, 0, batch, x, self._weights(dev))
+        p = _lib.ptr
+        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(live_ptr32), p(member_ptr), p(gr.bg_ptr)
+        a.shap_members = a.shap_bg_members = p(gr.members) if gr.members.numel() else p(live_ptr32)
+        a.shap_n_groups = int(member_ptr.numel()) - 1
+        a.coal_values, a.coal_jobs, a.coal_live_ptr = _frozen.front(table), p(jobs_t), p(vptr)
+        a.coal_rows, a.coal_max_live = T_live, max(lives)
+        jpl = self.default_jobs_per_launch(spw) if self.jobs_per_launch is None else int(self.jobs_per_launch)
+        if jpl < 1:
+            raise ValueError(f"jobs_per_launch must be at least 1; got {self.jobs_per_launch}")
+        lib, stream = _lib.load(), _lib.stream_ptr()
+        for first in range(0, J, jpl):
+            a.coal_job_first, a.coal_job_count = first, min(jpl, J - first)
+            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (coalitions)")
+        return self._result(table[index], tptr, gr, counts, cls)
+
+    # ------------------------------------------------------------------ the existing path (any shape): one forward per mask index
+    def _forward(self, batch, node_mask, edge_mask):
+        if not batch.x.is_cuda:
+            return _frozen.torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
+        return self._step(batch, edge_mask, node_mask).out
+
+    def loop(self, batch, node_group=None, edge_group=None, class_index: int = 0):
+        """The batch-synchronous loop (see the class docstring), whatever `reason(batch)` says."""
+        (N, F), B, dev = batch.x.shape, int(batch.num_graphs), batch.x.device
+        gr, counts, lives, aux = self._layout(batch, node_group, edge_group)
+        C = int(self.model._n_classes)
+        if not 0 <= int(class_index) < C:
+            raise ValueError(f"class_index must lie in 0 .. {C - 1}; got {class_index}")
+        tptr, vptr, index = self._expand(gr, counts, lives, aux, dev)
+        ggraph = aux[0]
+        # the feature's bit: its group's local id (the background: always on)
+        local = torch.cat([torch.arange(gr.G, device=dev) - gr.group_ptr[ggraph], torch.zeros(1, dtype=torch.int64, device=dev)])[gr.slot]
+        background = gr.slot == gr.G
+        T = sum(1 << c for c in counts)
+        raw = torch.zeros(T, C, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for s in range(1 << max(counts)) if B > 0 else ():
+                on = (background | (((torch.full_like(local, s) >> local) & 1) == 1)).to(torch.float32)
+                out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1)
+                act = (torch.ones_like(gr.count) << gr.count) > s
+                raw[tptr[:-1][act] + s] = out[act].to(torch.float32)
+        # the rows of the live table, read back through the same gather as the fused path's: a row stands for every row
+        # that differs from it in dead groups only (its own dead bits cleared)
+        canon = torch.zeros(sum(1 << c for c in lives), dtype=torch.int64, device=dev)
+        canon.scatter_reduce_(0, index, torch.arange(T, device=dev), reduce="amin", include_self=False)
+        self.last_path = "loop"
+        return self._result(raw[canon[index]], tptr, gr, counts, int(class_index))

@@ -214,6 +214,27 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   N F + E and, for a launch, the five arrays non-NULL (HCG_ERR_INVALID_ARG).  A refused graph: its G_g entries zero.  LDS,
  *   shapes and the order of the sum over the permutations as without the flag.  The shap_ fields are the fourth member of
  *   the union of the fit_, path_ and mom_ fields.
+ * HCG_EXPLAIN_COALITIONS: the coalition values of ONE frozen model for a batch of graphs (csrc/shapley.hip,
+ *   k_coalition_values): the model's output for EVERY subset of each graph's groups, the table every exact quantity of a few
+ *   players is a fixed linear form of (Shapley values, Shapley interaction indices, any single what-if).  Players, background,
+ *   features and their indexing are those of HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED, and the shap_ fields are read as
+ *   there, with one rule more: the caller lists the LIVE groups only (a group without a live member changes no output), so
+ *   shap_group_ptr [B + 1] is the prefix sum of the graphs' live counts L_g and shap_n_groups their total.  Graph g has 2^L_g
+ *   rows in coal_values [coal_rows, C] float32, from row coal_live_ptr[g] (int64 [B + 1]): row coal_live_ptr[g] + m holds
+ *   all C outputs with the background and the live groups {k : bit k of m} on.  coal_jobs is an int32 array of triples
+ *   (graph, first mask, masks); a call runs the jobs coal_job_first .. coal_job_first + coal_job_count - 1, one workgroup
+ *   each, which builds its graph once and then, for every mask of its run, REBUILDS the state from zero -- nothing on, the
+ *   live background applied, then the set groups in ascending order, each as the grouped walk applies a group -- and
+ *   evaluates it once with the walk's evaluation.  So a row is bitwise independent of the run it sits in, of how the jobs
+ *   are split into calls and of the rest of the batch, and row 2^(y + 1) - 1 is bitwise the grouped walk's v_(y + 1) in the
+ *   identity order.  Every row has one writer; no workspace (workspace_bytes_needed = 0), no reduction, no atomics; `out`,
+ *   out_base and shap_acc are not used.  Contents are trusted, but a graph outside [0, B), a member outside [0, K_g), a
+ *   mask outside [0, 2^L_g) and a row outside [0, coal_rows) are skipped, never used as an address.  edge_mask, node_mask,
+ *   target / target_class, dout and perm must be NULL and HCG_EXPLAIN_TARGET_CLASS / HCG_EXPLAIN_GROUPED clear
+ *   (HCG_ERR_INVALID_ARG); coal_max_live = the largest L_g must be <= 16 and coal_rows < 2^31 (HCG_ERR_UNSUPPORTED); for a
+ *   launch the five shap_ arrays, coal_values, coal_jobs and coal_live_ptr non-NULL.  Shapes, LDS and refusals as
+ *   HCG_EXPLAIN_SHAPLEY (184 nodes; a refused graph: its rows zero, HCG_STATUS_SHAPE_LIMIT).  HCG_EXPLAIN_QUERY as above;
+ *   also writes lds_bytes.  The coal_ fields follow the shap_ fields in the union's fourth member.
  * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
  *   node_mask_type 'attributes', edge_mask_type 'object'; regression, or multiclass classification on raw outputs) for a
  *   batch of graphs in ONE launch: the kernel of
@@ -279,13 +300,14 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
 #define HCG_EXPLAIN_FIT 4
 #define HCG_EXPLAIN_INTEGRATED 5
 #define HCG_EXPLAIN_MOMENTS 6
+#define HCG_EXPLAIN_COALITIONS 7
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
 #define HCG_EXPLAIN_GROUPED 8  /* flags: HCG_EXPLAIN_SHAPLEY walks groups of features (the shap_ fields) */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS / _COALITIONS */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS | HCG_EXPLAIN_GROUPED */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -377,13 +399,21 @@ typedef struct hcg_explain_args {
   int32_t mom_count;                     /* models of this call; mom_first + mom_count <= mom_total */
   int32_t mom_reserved;
   };
-  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED */
+  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED, and HCG_EXPLAIN_COALITIONS */
   const int32_t* shap_group_ptr;         /* [B + 1] prefix sum of the graphs' group counts */
   const int32_t* shap_member_ptr;        /* [G + 1] group -> its range of shap_members */
   const int32_t* shap_members;           /* live members only: local feature indices, ascending within a group */
   const int32_t* shap_bg_ptr;            /* [B + 1] graph -> its range of shap_bg_members */
   const int32_t* shap_bg_members;        /* the live background, ascending within a graph */
   int64_t shap_n_groups;                 /* G */
+  float* coal_values;                    /* HCG_EXPLAIN_COALITIONS from here on: OUT [coal_rows, C] */
+  const int32_t* coal_jobs;              /* [.][3]: graph, first mask, masks */
+  const int64_t* coal_live_ptr;          /* [B + 1] graph g's rows: coal_live_ptr[g] + mask */
+  int64_t coal_rows;                     /* T_live = sum_g 2^L_g */
+  int32_t coal_job_first;                /* first job of this call */
+  int32_t coal_job_count;                /* jobs of this call (the grid) */
+  int32_t coal_max_live;                 /* the largest L_g, <= 16 */
+  int32_t coal_reserved;
   };
   };
 } hcg_explain_args;
