@@ -14,10 +14,14 @@ the reference's setting), `atoms` (one player per atom, the bonds always present
 bonds) or `fragments` (the synthetic graphs get three contiguous node ranges as fragments; all 3! orders are walked, which
 is the exact Shapley value for 4 evaluations per order).  With `--coalitions` the fragments go through `CoalitionValues`
 instead: every subset of them evaluated once, exact Shapley values and the pairwise interaction matrix from that table.
+With `--curves` (`--players atoms`) the atoms are ranked by the call's own attribution and `AttributionCurves` asks the model
+how good that ranking is: the mean area under the insertion curve (high is good) and under the deletion curve (low is good),
+beside the same two figures for a random order drawn from `--seed`.
 
     python examples/shapley_like_reference.py --graphs 64 --samples 25
     python examples/shapley_like_reference.py --graphs 64 --players fragments
     python examples/shapley_like_reference.py --graphs 64 --players fragments --coalitions
+    python examples/shapley_like_reference.py --graphs 64 --players atoms --curves
 """
 from __future__ import annotations
 
@@ -56,6 +60,22 @@ def grouped(a, sv, batch):
     g0 = r.group_attr[:int(r.group_ptr[1])]
     print("graph 0, groups by |attribution|:", torch.argsort(g0.abs(), descending=True)[:5].tolist(),
           [round(v, 5) for v in g0[torch.argsort(g0.abs(), descending=True)[:5]].tolist()])
+    if a.curves:
+        curves(a, sv.model, batch, atoms, r)
+
+
+def curves(a, model, batch, atoms, r):
+    """Deletion and insertion curves of the atoms ranked by the attribution just computed, and of a random order."""
+    ac = H.AttributionCurves(model)
+    mine = ac(batch, H.ranking(r.group_attr, r.group_ptr), node_group=atoms, class_index=0)
+    path = ac.last_path
+    ins, dele = float(mine.insertion_auc.mean()), float(mine.deletion_auc.mean())
+    drawn = H.draw_group_permutations(batch, atoms, None, n_samples=1, generator=torch.Generator().manual_seed(a.seed))
+    rand = ac(batch, drawn, node_group=atoms, class_index=0)
+    print(f"curves, path {path}: {mine.k.numel()} points on {batch.num_graphs} graphs, two evaluations per interior point")
+    print("mean insertion AUC / deletion AUC, atoms ranked by their attribution: %.5f / %.5f" % (ins, dele))
+    print("mean insertion AUC / deletion AUC, a random order:                    %.5f / %.5f"
+          % (float(rand.insertion_auc.mean()), float(rand.deletion_auc.mean())))
 
 
 def coalitions(model, batch):
@@ -81,9 +101,12 @@ def main():
     ap.add_argument("--nonzero-share", type=float, default=0.2, help="share of the node-feature entries kept non-zero (one-hot-like)")
     ap.add_argument("--players", choices=("entries", "atoms", "atoms+bonds", "fragments"), default="entries")
     ap.add_argument("--coalitions", action="store_true", help="with --players fragments: every subset through CoalitionValues")
+    ap.add_argument("--curves", action="store_true", help="with --players atoms: deletion / insertion curves of the atoms' ranking")
     a = ap.parse_args()
     if a.coalitions and a.players != "fragments":
         ap.error("--coalitions goes with --players fragments")
+    if a.curves and a.players != "atoms":
+        ap.error("--curves goes with --players atoms")
     model = H.make_network("GCN", H.default_options(), 25).cuda()
     sb = synth.make_batch(num_graphs=a.graphs, nodes=87, nodes_jitter=30, extra_bonds=4, max_degree=4, feat=25)
     keep = torch.rand(sb.x.shape, generator=torch.Generator().manual_seed(a.seed)) < a.nonzero_share

@@ -26,6 +26,10 @@ Public surface (mirrors the reference's names for this path):
     CoalitionValues, shapley_from_coalitions, interactions_from_coalitions
                                                 the model's output for every subset of a graph's groups (up to 16), evaluated
                                                 on chip; exact Shapley values and pairwise interaction indices from that table
+    SubsetValues, AttributionCurves, pack_subsets, ranking, group_scores
+                                                the model's output for a LIST of subsets of a graph's groups (any number
+                                                of groups) evaluated on chip; deletion / insertion curves and their AUCs
+                                                for a ranking of the groups, whichever attribution it came from
     IntegratedGradients, quadrature             integrated gradients (Captum's IntegratedGradients through the same
                                                 CaptumExplainer entry point) of a batch of graphs, the whole path of every
                                                 graph in one launch; method="gradient" / saliency=True are its one-step
@@ -47,6 +51,7 @@ from .shapley import (CoalitionResult, CoalitionValues, GroupedShapleyResult, Sh
                       all_group_permutations, atom_groups, bond_groups, draw_group_permutations, draw_permutations,
                       interactions_from_coalitions, shapley_from_coalitions)
 from .store import DeviceGraphStore, DeviceLoader  # noqa: F401
+from .subsets import AttributionCurves, CurveResult, SubsetResult, SubsetValues, group_scores, pack_subsets, ranking  # noqa: F401
 
 __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "BaseNetwork", "Data", "Batch",
            "collate", "DataLoader", "BatchPlan", "DeviceGraphStore", "DeviceLoader", "EnsemblePredict", "EnsembleResult",
@@ -54,4 +59,5 @@ __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "
            "bond_groups", "draw_group_permutations", "all_group_permutations", "ExplainFit", "ExplainFitResult",
            "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
            "quadrature", "EnsembleAttribution", "EnsembleAttributionResult", "CoalitionValues", "CoalitionResult",
-           "shapley_from_coalitions", "interactions_from_coalitions"]
+           "shapley_from_coalitions", "interactions_from_coalitions", "SubsetValues", "SubsetResult", "AttributionCurves",
+           "CurveResult", "pack_subsets", "ranking", "group_scores"]

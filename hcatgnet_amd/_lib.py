@@ -30,6 +30,7 @@ HCG_EXPLAIN_GRAPHS, HCG_EXPLAIN_LAYER_EDGE_GRAD, HCG_EXPLAIN_ENSEMBLE, HCG_EXPLA
 HCG_EXPLAIN_INTEGRATED = 5
 HCG_EXPLAIN_MOMENTS = 6          # mean / std over the model axis of HCG_EXPLAIN_INTEGRATED's outputs with n_models > 1
 HCG_EXPLAIN_COALITIONS = 7      # every subset of a graph's live groups evaluated (`COALITION_FIELDS` behind the `shap_` fields)
+HCG_EXPLAIN_SUBSETS = 8         # a list of subsets of a graph's groups evaluated (`SUBSET_FIELDS` behind the `coal_` fields)
 HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
 HCG_EXPLAIN_GROUPED = 8          # flag of HCG_EXPLAIN_SHAPLEY: groups of features are the players (`SHAPLEY_GROUP_FIELDS`)
@@ -119,7 +120,8 @@ class ExplainArgs(ctypes.Structure):
     attached below (`PATH_FIELDS`), so `_fields_`, the size and every offset stay what they were.  The `mom_` fields
     (HCG_EXPLAIN_MOMENTS, `MOMENT_FIELDS`) are the union's third block and the `shap_` fields (HCG_EXPLAIN_SHAPLEY with
     HCG_EXPLAIN_GROUPED, `SHAPLEY_GROUP_FIELDS`) its fourth, attached the same way; the `coal_` fields (HCG_EXPLAIN_COALITIONS,
-    `COALITION_FIELDS`) follow the `shap_` fields in that fourth block."""
+    `COALITION_FIELDS`) follow the `shap_` fields in that fourth block and the `sub_` fields (HCG_EXPLAIN_SUBSETS,
+    `SUBSET_FIELDS`) the `coal_` fields."""
     _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
                 ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
                 ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
@@ -182,10 +184,13 @@ SHAPLEY_GROUP_FIELDS = (("shap_group_ptr", P), ("shap_member_ptr", P), ("shap_me
 COALITION_FIELDS = (("coal_values", P), ("coal_jobs", P), ("coal_live_ptr", P), ("coal_rows", I64), ("coal_job_first", I32),
                     ("coal_job_count", I32), ("coal_max_live", I32), ("coal_reserved", I32))
 
+# what HCG_EXPLAIN_SUBSETS adds behind those (it reads coal_values / coal_jobs / coal_rows / coal_job_first / coal_job_count too)
+SUBSET_FIELDS = (("sub_bits", P), ("sub_word_ptr", P), ("sub_member_group", P), ("sub_max_groups", I32), ("sub_reserved", I32))
+
 
 _attach_union_fields(PATH_FIELDS)
 _attach_union_fields(MOMENT_FIELDS)
-_attach_union_fields(SHAPLEY_GROUP_FIELDS + COALITION_FIELDS)
+_attach_union_fields(SHAPLEY_GROUP_FIELDS + COALITION_FIELDS + SUBSET_FIELDS)
 
 
 class CollateSlot(ctypes.Structure):

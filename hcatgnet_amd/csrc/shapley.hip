@@ -43,6 +43,9 @@
 // HCG_EXPLAIN_COALITIONS (k_coalition_values, below the walk): every subset of a graph's live groups evaluated once, the state
 // rebuilt from zero per subset.  Build (s_build), weights in registers (s_load_weights), application (s_apply) and evaluation
 // (s_eval) are the walk's: both kernels call the same four functions.
+// HCG_EXPLAIN_SUBSETS (k_subset_values, below the coalition kernel): a caller's LIST of subsets of a graph's groups, any number
+// of groups, evaluated the same way -- but the set groups are applied in ONE filtered pass over the graph's member list
+// (s_apply_subset), the row's bit words staged in pj / pv, where the coalition kernel pays one s_apply per set group.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -114,8 +117,11 @@ __device__ __forceinline__ float s_uniform(float v) { return __int_as_float(__bu
 // (node << 6 | f, x) for the node's owner -- wave (node mod 8) -- which applies its entries in list order with the ungrouped
 // walk's rank-1 update.  So every element of h1 has one owner and takes its updates in ascending member order, whatever the
 // group's size.  An index outside [0, K) is skipped.  The caller places the barrier between this and the evaluation.
-__device__ __forceinline__ void s_apply(const SLds& L, const XCommon& cm, const int32_t* mem, int mb, int me, int nbase, int nF,
-                                        int K, int tid) {
+// `on(position in mem)` filters the list (s_apply: everything; s_apply_subset: the members of the row's groups): a member that
+// is off is staged as nothing (code -1), which skips without reordering.
+template <class On>
+__device__ __forceinline__ void s_apply_if(const SLds& L, const XCommon& cm, const int32_t* mem, int mb, int me, int nbase, int nF,
+                                           int K, int tid, On on) {
   const int lane = tid & 63, wave = tid >> 6, F = cm.F;
   int* const code = reinterpret_cast<int*>(L.t1);        // [XT]
   float* const val = L.t1 + XT;                          // [XT]  (npad >= 16: the tile has 16 * XS >= 2 XT floats)
@@ -124,7 +130,7 @@ __device__ __forceinline__ void s_apply(const SLds& L, const XCommon& cm, const 
     if (c0 != mb) __syncthreads();                       // (the members staged before have been applied)
     int cd = -1;
     float xv = 0.f;
-    if (tid < me - c0) {
+    if (tid < me - c0 && on(c0 + tid)) {
       const int jj = mem[c0 + tid];
       if (jj >= 0 && jj < nF) {
         const int i = jj / F;
@@ -154,6 +160,23 @@ __device__ __forceinline__ void s_apply(const SLds& L, const XCommon& cm, const 
       }
     }
   }
+}
+
+__device__ __forceinline__ void s_apply(const SLds& L, const XCommon& cm, const int32_t* mem, int mb, int me, int nbase, int nF,
+                                        int K, int tid) {
+  s_apply_if(L, cm, mem, mb, me, nbase, nF, K, tid, [](int) { return true; });
+}
+
+// HCG_EXPLAIN_SUBSETS: the members mem[mb .. me) -- ALL groups of the graph, group by group -- whose group is set in the row's
+// bit words `bits` (LDS, staged by the caller behind a barrier), in one pass.  grp[p] is the local group id of mem[p]; an id
+// outside [0, ng) is off.  The list is ordered by group, then by local index, and an off member is skipped in place, so every
+// element of h1 takes the updates it takes when the set groups are applied one s_apply each, in the same order.
+__device__ __forceinline__ void s_apply_subset(const SLds& L, const XCommon& cm, const int32_t* mem, const int32_t* grp,
+                                               const unsigned* bits, int ng, int mb, int me, int nbase, int nF, int K, int tid) {
+  s_apply_if(L, cm, mem, mb, me, nbase, nF, K, tid, [&](int p) {
+    const int y = grp[p];
+    return y >= 0 && y < ng && ((bits[y >> 5] >> (y & 31)) & 1u) != 0;
+  });
 }
 
 // One evaluation of the state in LDS (h1, mval): conv stack, pooling, readout -> the position of the output row in hv.  `w` is
@@ -455,6 +478,90 @@ __global__ __launch_bounds__(XT) void k_coalition_values(const CArgs a) {
   }
 }
 
+// HCG_EXPLAIN_SUBSETS: v(S) for a caller's list of subsets S of a graph's groups (ALL of them listed: a dead group has an
+// empty member range, so bit y is the caller's group y), any number of groups up to V_MAX_GROUPS.  One workgroup per job
+// (graph, first row, rows), the LDS layout and the build of the two kernels above.  Per row: the graph's bit words of the
+// row are staged in pj / pv (512 words, idle here), the state is rebuilt from zero -- h1 = 0, mval = 0 for every edge with an
+// entry, the live background through s_apply, the set groups through s_apply_subset: one filtered pass over the graph's
+// member list, no global load per group -- and evaluated once (s_eval); thread c < C writes output c to row (s, g) of the
+// [S][B][C] table.  Nothing is carried from row to row: a row depends on its bits and its graph alone.  For the same subset
+// the state takes the updates k_coalition_values applies, in the same order, so the rows are bitwise that kernel's.
+struct VArgs {
+  XCommon c;
+  float* table;                             // [S][B][C]
+  const int32_t* jobs;                      // [.][3] graph, first row, rows
+  const unsigned* bits;                     // [S][W]
+  const int32_t* word_ptr;                  // [B + 1] graph g's words of a row: word_ptr[g] .., W = word_ptr[B]
+  const int32_t* group_ptr;                 // [B + 1] ALL groups of graph g
+  const int32_t* member_ptr;                // [G + 1]
+  const int32_t* members;
+  const int32_t* member_group;              // parallel to `members`: the member's local group id
+  const int32_t* bg_ptr;                    // [B + 1]
+  const int32_t* bg_members;
+  long long S, G, B;
+  int first;                                // first job of this launch
+};
+
+constexpr int V_MAX_GROUPS = 2 * S_CHUNK * 32;     // the bits pj / pv hold: 16384 (a graph inside the limits has <= 12800 features)
+
+__global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const XCommon& cm = a.c;
+  const SLds L = s_carve(smem, cm.npad, cm.emax);
+  const int tid = threadIdx.x;
+  const int C = cm.C;
+  const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
+  const int g = __builtin_amdgcn_readfirstlane(job[0]);
+  const int s0 = __builtin_amdgcn_readfirstlane(job[1]);
+  const int scount = __builtin_amdgcn_readfirstlane(job[2]);
+  if (g < 0 || g >= a.B) return;
+  const int gp = __builtin_amdgcn_readfirstlane(a.group_ptr[g]);
+  const int ng = __builtin_amdgcn_readfirstlane(a.group_ptr[g + 1]) - gp;
+  if (ng < 0 || ng > V_MAX_GROUPS || gp < 0 || (long long)gp + ng > a.G) return;
+  const int nw = (ng + 31) >> 5;                           // <= 512 = XT: one word per thread
+  const int wp = __builtin_amdgcn_readfirstlane(a.word_ptr[g]);
+  const int W = __builtin_amdgcn_readfirstlane(a.word_ptr[a.B]);
+  if (wp < 0 || (long long)wp + nw > W) return;
+  // the rows of the run that exist
+  const long long slo = max(0ll, (long long)s0);
+  const long long shi = min((long long)s0 + scount, a.S);
+
+  XSpan sp;
+  if (x_refused(sp, cm, g, tid)) {
+    for (long long s = slo; s < shi; ++s)
+      if (tid < C) a.table[((size_t)s * (size_t)a.B + g) * C + tid] = 0.f;
+    return;
+  }
+  const int nbase = sp.nbase, n = sp.n, ne = sp.ne;
+  s_build(L, cm, sp, tid);
+  const XMasked fmt{L.mval};
+  float w[XD];
+  float rw0[16];
+  s_load_weights(w, rw0, cm, tid);
+  const int nF = n * cm.F, K = nF + ne;
+  const int bb = __builtin_amdgcn_readfirstlane(a.bg_ptr[g]), be = __builtin_amdgcn_readfirstlane(a.bg_ptr[g + 1]);
+  const int mb = __builtin_amdgcn_readfirstlane(a.member_ptr[gp]), me = __builtin_amdgcn_readfirstlane(a.member_ptr[gp + ng]);
+  unsigned* const bits = reinterpret_cast<unsigned*>(L.pj);     // [2 S_CHUNK]: pj and pv lie side by side
+
+#pragma nounroll
+  for (long long s = slo; s < shi; ++s) {
+    // the row's words, and everything off (the evaluation before ended behind a barrier: h1, mval, t1 and pj / pv are idle)
+    if (tid < nw) bits[tid] = a.bits[(size_t)s * (size_t)W + wp + tid];
+    for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
+#pragma unroll
+    for (int j = 0; j < X_EPT; ++j)
+      if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
+    __syncthreads();
+    s_apply(L, cm, a.bg_members, bb, be, nbase, nF, K, tid);
+    __syncthreads();                                       // (the staging of the list before has been read)
+    s_apply_subset(L, cm, a.members, a.member_group, bits, ng, mb, me, nbase, nF, K, tid);
+    __syncthreads();
+    const int off = s_eval(L, cm, fmt, w, rw0, n, tid);
+    if (tid < C) a.table[((size_t)s * (size_t)a.B + g) * C + tid] = L.hv[off + tid];
+    // (hv is next written behind the barriers of the next evaluation's conv stack)
+  }
+}
+
 // acc[i] (+)= sum_p ws[p][i], p ascending; the call that ends at the last permutation divides by their number
 __global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict__ ws, float* __restrict__ acc, long long row,
                                                         int count, int fresh, int last, float n_perm) {
@@ -554,4 +661,40 @@ int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream) {
   a.B = p->B;
   a.first = p->coal_job_first;
   return x_launch<k_coalition_values>(dim3((unsigned)p->coal_job_count), lds, stream, a);
+}
+
+// hcg_explain, mode HCG_EXPLAIN_SUBSETS (explain.hip dispatches here)
+int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  if (p->sub_max_groups > V_MAX_GROUPS || p->coal_rows >= (1ll << 31)) return HCG_ERR_UNSUPPORTED;
+  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
+  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
+  p->lds_bytes = (int32_t)lds;
+  p->workspace_bytes_needed = 0;
+  if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
+  if (p->sub_max_groups < 0 || p->coal_rows < 0 || p->shap_n_groups < 0 || p->coal_job_first < 0 || p->coal_job_count < 0)
+    return HCG_ERR_INVALID_ARG;
+  if (p->B == 0 || p->coal_job_count == 0) return HCG_OK;
+  if (!x_common_ok(p, false) || !p->coal_values || !p->coal_jobs || !p->sub_bits || !p->sub_word_ptr || !p->sub_member_group ||
+      !p->shap_group_ptr || !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members)
+    return HCG_ERR_INVALID_ARG;
+
+  VArgs a;
+  x_fill_common(a.c, p, S_NPAD_MIN);
+  a.table = p->coal_values;
+  a.jobs = p->coal_jobs;
+  a.bits = p->sub_bits;
+  a.word_ptr = p->sub_word_ptr;
+  a.group_ptr = p->shap_group_ptr;
+  a.member_ptr = p->shap_member_ptr;
+  a.members = p->shap_members;
+  a.member_group = p->sub_member_group;
+  a.bg_ptr = p->shap_bg_ptr;
+  a.bg_members = p->shap_bg_members;
+  a.S = p->coal_rows;
+  a.G = p->shap_n_groups;
+  a.B = p->B;
+  a.first = p->coal_job_first;
+  return x_launch<k_subset_values>(dim3((unsigned)p->coal_job_count), lds, stream, a);
 }

@@ -235,6 +235,32 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   launch the five shap_ arrays, coal_values, coal_jobs and coal_live_ptr non-NULL.  Shapes, LDS and refusals as
  *   HCG_EXPLAIN_SHAPLEY (184 nodes; a refused graph: its rows zero, HCG_STATUS_SHAPE_LIMIT).  HCG_EXPLAIN_QUERY as above;
  *   also writes lds_bytes.  The coal_ fields follow the shap_ fields in the union's fourth member.
+ * HCG_EXPLAIN_SUBSETS: the values of a caller's LIST of subsets of each graph's groups, for ONE frozen model and a batch of
+ *   graphs (csrc/shapley.hip, k_subset_values): the primitive under deletion / insertion curves and any sampled estimator
+ *   over groups, for ANY number of groups per graph (atoms as players: 57 - 184).  Players, background, features and their
+ *   indexing are those of HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED and the shap_ fields are read as there: ALL groups of
+ *   every graph are listed (a dead group has an empty member range), so a bit position is the caller's group id.  The
+ *   subsets are bit words: sub_bits [coal_rows][W] uint32, sub_word_ptr [B + 1] int32 the prefix sum of ceil(G_g / 32),
+ *   W = sub_word_ptr[B]; group y of graph g is on in row s iff bit (y & 31) of sub_bits[s W + sub_word_ptr[g] + (y >> 5)] is
+ *   set (bits at or above G_g in a graph's last word are ignored).  sub_member_group, int32, parallel to shap_members, gives
+ *   the local group id of every listed member.  The mode reuses the coal_ slots whose meaning carries over: coal_values is
+ *   the table [S][B][C] float32 (row s of graph g at (s B + g) C), coal_rows = S, coal_jobs the int32 triples (graph, first
+ *   row, rows), coal_job_first / coal_job_count the jobs of this call, one workgroup each; coal_live_ptr and coal_max_live
+ *   are not read.  A workgroup builds its graph once and, for every row of its run, stages the graph's words of the row in
+ *   LDS, REBUILDS the state from zero -- nothing on, the live background applied, then ONE filtered pass over the graph's
+ *   whole member range that applies the members whose group's bit is set, in list order (no global load per group) -- and
+ *   evaluates it once with the walk's evaluation.  The list is ordered by group, then by local index, and skipping does not
+ *   reorder: for the same subset every element of the state takes the updates HCG_EXPLAIN_COALITIONS applies, in the same
+ *   order, so the rows are bitwise that mode's, and a row depends on its bits and its graph alone -- not on the run, the
+ *   call split, the other rows or the rest of the batch.  Every row has one writer; no workspace (workspace_bytes_needed =
+ *   0), no reduction, no atomics; a row no job names is not written.  Contents are trusted, but a graph outside [0, B), a
+ *   row outside [0, S), a member outside [0, K_g) and a group id outside [0, G_g) are skipped, never used as an address.
+ *   edge_mask, node_mask, target / target_class, dout and perm must be NULL and HCG_EXPLAIN_TARGET_CLASS /
+ *   HCG_EXPLAIN_GROUPED clear (HCG_ERR_INVALID_ARG); sub_max_groups = the largest G_g must be <= 16384 (the bits the staging
+ *   holds; a graph inside the shape limits has at most 12800 features) and coal_rows < 2^31 (HCG_ERR_UNSUPPORTED); for a
+ *   launch the five shap_ arrays, coal_values, coal_jobs, sub_bits, sub_word_ptr and sub_member_group non-NULL.  Shapes, LDS
+ *   and refusals as HCG_EXPLAIN_SHAPLEY (184 nodes; a refused graph: the rows of its jobs zero, HCG_STATUS_SHAPE_LIMIT).
+ *   HCG_EXPLAIN_QUERY as above; also writes lds_bytes.  The sub_ fields follow the coal_ fields in the union's fourth member.
  * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
  *   node_mask_type 'attributes', edge_mask_type 'object'; regression, or multiclass classification on raw outputs) for a
  *   batch of graphs in ONE launch: the kernel of
@@ -301,13 +327,14 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
 #define HCG_EXPLAIN_INTEGRATED 5
 #define HCG_EXPLAIN_MOMENTS 6
 #define HCG_EXPLAIN_COALITIONS 7
+#define HCG_EXPLAIN_SUBSETS 8
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
 #define HCG_EXPLAIN_GROUPED 8  /* flags: HCG_EXPLAIN_SHAPLEY walks groups of features (the shap_ fields) */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS / _COALITIONS */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS / _COALITIONS / _SUBSETS */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS | HCG_EXPLAIN_GROUPED */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -399,7 +426,7 @@ typedef struct hcg_explain_args {
   int32_t mom_count;                     /* models of this call; mom_first + mom_count <= mom_total */
   int32_t mom_reserved;
   };
-  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED, and HCG_EXPLAIN_COALITIONS */
+  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED, HCG_EXPLAIN_COALITIONS and HCG_EXPLAIN_SUBSETS */
   const int32_t* shap_group_ptr;         /* [B + 1] prefix sum of the graphs' group counts */
   const int32_t* shap_member_ptr;        /* [G + 1] group -> its range of shap_members */
   const int32_t* shap_members;           /* live members only: local feature indices, ascending within a group */
@@ -414,6 +441,11 @@ typedef struct hcg_explain_args {
   int32_t coal_job_count;                /* jobs of this call (the grid) */
   int32_t coal_max_live;                 /* the largest L_g, <= 16 */
   int32_t coal_reserved;
+  const uint32_t* sub_bits;              /* HCG_EXPLAIN_SUBSETS from here on (it reads coal_values / _jobs / _rows / _job_first / _job_count too): [coal_rows][W] */
+  const int32_t* sub_word_ptr;           /* [B + 1] prefix sum of ceil(G_g / 32); W = sub_word_ptr[B] */
+  const int32_t* sub_member_group;       /* parallel to shap_members: the member's local group id */
+  int32_t sub_max_groups;                /* the largest G_g, <= 16384 */
+  int32_t sub_reserved;
   };
   };
 } hcg_explain_args;
