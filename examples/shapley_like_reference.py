@@ -17,11 +17,15 @@ instead: every subset of them evaluated once, exact Shapley values and the pairw
 With `--curves` (`--players atoms`) the atoms are ranked by the call's own attribution and `AttributionCurves` asks the model
 how good that ranking is: the mean area under the insertion curve (high is good) and under the deletion curve (low is good),
 beside the same two figures for a random order drawn from `--seed`.
+With `--greedy` (`--players atoms`) `GreedySelection` finds the model's own greedy insertion and deletion orders of the atoms
+(high insertion AUC / low deletion AUC by construction: the practical envelope) and prints, per mode, the mean AUC of the
+greedy order beside the sampled-Shapley ranking's and the random order's, all three through `AttributionCurves`.
 
     python examples/shapley_like_reference.py --graphs 64 --samples 25
     python examples/shapley_like_reference.py --graphs 64 --players fragments
     python examples/shapley_like_reference.py --graphs 64 --players fragments --coalitions
     python examples/shapley_like_reference.py --graphs 64 --players atoms --curves
+    python examples/shapley_like_reference.py --graphs 64 --players atoms --greedy
 """
 from __future__ import annotations
 
@@ -62,6 +66,24 @@ def grouped(a, sv, batch):
           [round(v, 5) for v in g0[torch.argsort(g0.abs(), descending=True)[:5]].tolist()])
     if a.curves:
         curves(a, sv.model, batch, atoms, r)
+    if a.greedy:
+        greedy(a, sv.model, batch, atoms, r)
+
+
+def greedy(a, model, batch, atoms, r):
+    """How far is the sampled-Shapley ranking from what the model allows?  The greedy insertion order (always add the atom
+    that raises the output most) and the greedy deletion order (always remove the atom that lowers it most) beside the
+    ranking and a random order, all three through `AttributionCurves`."""
+    gs, ac = H.GreedySelection(model), H.AttributionCurves(model)
+    drawn = H.draw_group_permutations(batch, atoms, None, n_samples=1, generator=torch.Generator().manual_seed(a.seed))
+    orders = {"atoms ranked by their attribution": H.ranking(r.group_attr, r.group_ptr), "a random order": drawn}
+    for mode in ("insertion", "deletion"):
+        g = gs(batch, node_group=atoms, class_index=0, mode=mode)
+        print(f"greedy {mode}, path {gs.last_path}: {int(g.steps.sum())} picks on {batch.num_graphs} graphs in {gs.launches} launches; "
+              f"graph 0's first five: {g.order[0, :5].tolist()}")
+        for name, order in {f"the greedy {mode} order": g.order, **orders}.items():
+            c = ac(batch, order, node_group=atoms, class_index=0)
+            print("  mean %s AUC, %-34s %.5f" % (mode, name + ":", float((c.insertion_auc if mode == "insertion" else c.deletion_auc).mean())))
 
 
 def curves(a, model, batch, atoms, r):
@@ -102,7 +124,10 @@ def main():
     ap.add_argument("--players", choices=("entries", "atoms", "atoms+bonds", "fragments"), default="entries")
     ap.add_argument("--coalitions", action="store_true", help="with --players fragments: every subset through CoalitionValues")
     ap.add_argument("--curves", action="store_true", help="with --players atoms: deletion / insertion curves of the atoms' ranking")
+    ap.add_argument("--greedy", action="store_true", help="with --players atoms: the greedy insertion / deletion orders beside the ranking's AUCs")
     a = ap.parse_args()
+    if a.greedy and a.players != "atoms":
+        ap.error("--greedy goes with --players atoms")
     if a.coalitions and a.players != "fragments":
         ap.error("--coalitions goes with --players fragments")
     if a.curves and a.players != "atoms":

@@ -30,6 +30,9 @@ Public surface (mirrors the reference's names for this path):
                                                 the model's output for a LIST of subsets of a graph's groups (any number
                                                 of groups) evaluated on chip; deletion / insertion curves and their AUCs
                                                 for a ranking of the groups, whichever attribution it came from
+    GreedySelection, GreedyResult               the model-driven greedy insertion / deletion order of a graph's groups, one
+                                                launch per round and the winner picked on chip: the envelope the curves
+                                                are read against, and the top-k sufficient / necessary set of groups
     IntegratedGradients, quadrature             integrated gradients (Captum's IntegratedGradients through the same
                                                 CaptumExplainer entry point) of a batch of graphs, the whole path of every
                                                 graph in one launch; method="gradient" / saliency=True are its one-step
@@ -45,6 +48,7 @@ from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F4
 from .explain import ExplainFit, ExplainFitResult, ExplainFitState  # noqa: F401
 from .fit import FitControl, FitResult, fit_network, fit_networks  # noqa: F401
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
+from .greedy import GreedyResult, GreedySelection  # noqa: F401
 from .networks import BaseNetwork  # noqa: F401
 from .plan import BatchPlan  # noqa: F401
 from .shapley import (CoalitionResult, CoalitionValues, GroupedShapleyResult, ShapleyResult, ShapleySampling,  # noqa: F401
@@ -60,4 +64,4 @@ __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "
            "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
            "quadrature", "EnsembleAttribution", "EnsembleAttributionResult", "CoalitionValues", "CoalitionResult",
            "shapley_from_coalitions", "interactions_from_coalitions", "SubsetValues", "SubsetResult", "AttributionCurves",
-           "CurveResult", "pack_subsets", "ranking", "group_scores"]
+           "CurveResult", "pack_subsets", "ranking", "group_scores", "GreedySelection", "GreedyResult"]

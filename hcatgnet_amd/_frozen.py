@@ -38,7 +38,8 @@ _MODES = {_lib.HCG_EXPLAIN_GRAPHS: ("one-launch explain", 224, "hcg_explain (que
           _lib.HCG_EXPLAIN_FIT: ("one-launch explainer fit", 224, "hcg_explain (fit query)"),
           _lib.HCG_EXPLAIN_INTEGRATED: ("one-launch integrated gradients", 224, "hcg_explain (integrated query)"),
           _lib.HCG_EXPLAIN_COALITIONS: ("on-chip coalition", 184, "hcg_explain (coalitions query)"),
-          _lib.HCG_EXPLAIN_SUBSETS: ("on-chip subset", 184, "hcg_explain (subsets query)")}
+          _lib.HCG_EXPLAIN_SUBSETS: ("on-chip subset", 184, "hcg_explain (subsets query)"),
+          _lib.HCG_EXPLAIN_GREEDY: ("on-chip greedy selection", 184, "hcg_explain (greedy query)")}
 
 
 def model_shape(model):

@@ -31,7 +31,9 @@ HCG_EXPLAIN_INTEGRATED = 5
 HCG_EXPLAIN_MOMENTS = 6          # mean / std over the model axis of HCG_EXPLAIN_INTEGRATED's outputs with n_models > 1
 HCG_EXPLAIN_COALITIONS = 7      # every subset of a graph's live groups evaluated (`COALITION_FIELDS` behind the `shap_` fields)
 HCG_EXPLAIN_SUBSETS = 8         # a list of subsets of a graph's groups evaluated (`SUBSET_FIELDS` behind the `coal_` fields)
-HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4   # its flags; conv layers of the one-launch kernel
+HCG_EXPLAIN_GREEDY = 9          # one round of the greedy insertion / deletion order of a graph's groups (`GREEDY_FIELDS`, `GREEDY_SLOTS`)
+HCG_GREEDY_DELETION, HCG_GREEDY_NEGATE = 1, 2     # its `greedy_flags`
+HCG_EXPLAIN_QUERY, HCG_EXPLAIN_SIGMOID, HCG_EXPLAIN_MAX_CONVS = 1, 2, 4  # its flags; conv layers of the one-launch kernel
 HCG_EXPLAIN_TARGET_CLASS = 4     # flag: the `target` slot holds int64 class indices [B] (the header's `target_class`)
 HCG_EXPLAIN_GROUPED = 8          # flag of HCG_EXPLAIN_SHAPLEY: groups of features are the players (`SHAPLEY_GROUP_FIELDS`)
 HCG_ERR_UNSUPPORTED = -3
@@ -121,7 +123,8 @@ class ExplainArgs(ctypes.Structure):
     (HCG_EXPLAIN_MOMENTS, `MOMENT_FIELDS`) are the union's third block and the `shap_` fields (HCG_EXPLAIN_SHAPLEY with
     HCG_EXPLAIN_GROUPED, `SHAPLEY_GROUP_FIELDS`) its fourth, attached the same way; the `coal_` fields (HCG_EXPLAIN_COALITIONS,
     `COALITION_FIELDS`) follow the `shap_` fields in that fourth block and the `sub_` fields (HCG_EXPLAIN_SUBSETS,
-    `SUBSET_FIELDS`) the `coal_` fields."""
+    `SUBSET_FIELDS`) the `coal_` fields; `greedy_round` / `greedy_flags` (HCG_EXPLAIN_GREEDY, `GREEDY_FIELDS`) follow the `sub_`
+    fields and fill the block, and that mode's two pointers take slots it does not read otherwise (`GREEDY_SLOTS`)."""
     _fields_ = [("mode", I32), ("flags", I32), ("x", P), ("edge_index", P), ("graph_ptr", P), ("edge_ptr", P), ("edge_mask", P),
                 ("node_mask", P), ("target", P), ("dout", P), ("conv_W", P * HCG_EXPLAIN_MAX_CONVS),
                 ("conv_b", P * HCG_EXPLAIN_MAX_CONVS), ("head_W", P * HCG_HEAD_MAX_LAYERS), ("head_b", P * HCG_HEAD_MAX_LAYERS),
@@ -187,10 +190,19 @@ COALITION_FIELDS = (("coal_values", P), ("coal_jobs", P), ("coal_live_ptr", P), 
 # what HCG_EXPLAIN_SUBSETS adds behind those (it reads coal_values / coal_jobs / coal_rows / coal_job_first / coal_job_count too)
 SUBSET_FIELDS = (("sub_bits", P), ("sub_word_ptr", P), ("sub_member_group", P), ("sub_max_groups", I32), ("sub_reserved", I32))
 
+# what HCG_EXPLAIN_GREEDY adds behind those (it reads the shap_ fields, coal_values / coal_jobs / coal_job_first /
+# coal_job_count and sub_member_group / sub_max_groups too); the block is full with them
+GREEDY_FIELDS = (("greedy_round", I32), ("greedy_flags", I32))
+
+# ... and its two pointers, which the header declares in a union with a field the mode does not read: name -> that field
+GREEDY_SLOTS = (("greedy_order", "coal_live_ptr"), ("greedy_cand", "sub_bits"))
+
 
 _attach_union_fields(PATH_FIELDS)
 _attach_union_fields(MOMENT_FIELDS)
-_attach_union_fields(SHAPLEY_GROUP_FIELDS + COALITION_FIELDS + SUBSET_FIELDS)
+_attach_union_fields(SHAPLEY_GROUP_FIELDS +COALITION_FIELDS + SUBSET_FIELDS + GREEDY_FIELDS)
+for _name, _slot in GREEDY_SLOTS:
+    setattr(ExplainArgs, _name, _Overlay(P, getattr(ExplainArgs, _slot).offset))
 
 
 class CollateSlot(ctypes.Structure):

@@ -130,6 +130,8 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream);
 int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream);
 // mode HCG_EXPLAIN_SUBSETS: the values of a list of subsets of a graph's groups
 int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream);
+// mode HCG_EXPLAIN_GREEDY: one round of the greedy insertion / deletion order of a graph's groups
+int hcg_greedy_launch(hcg_explain_args* p, hipStream_t stream);
 
 // ---- the fit controller (fit.hip), reached through hcg_update_dev (optim.hip): `fit_control` of hcg_update_args ----------
 int hcg_fit_control_launch(const hcg_fit_control_args* a, hipStream_t stream);

@@ -740,7 +740,7 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if ((p->flags & HCG_EXPLAIN_TARGET_CLASS) && (p->mode == HCG_EXPLAIN_LAYER_EDGE_GRAD || p->mode == HCG_EXPLAIN_ENSEMBLE ||
                                                 p->mode == HCG_EXPLAIN_SHAPLEY || p->mode == HCG_EXPLAIN_INTEGRATED ||
                                                 p->mode == HCG_EXPLAIN_MOMENTS || p->mode == HCG_EXPLAIN_COALITIONS ||
-                                                p->mode == HCG_EXPLAIN_SUBSETS))
+                                                p->mode == HCG_EXPLAIN_SUBSETS || p->mode == HCG_EXPLAIN_GREEDY))
     return HCG_ERR_INVALID_ARG;
   // groups of features as players belong to HCG_EXPLAIN_SHAPLEY alone
   if ((p->flags & HCG_EXPLAIN_GROUPED) && p->mode != HCG_EXPLAIN_SHAPLEY) return HCG_ERR_INVALID_ARG;
@@ -753,6 +753,7 @@ extern "C" int hcg_explain(hcg_explain_args* p, hcg_stream_t stream_) {
   if (p->mode == HCG_EXPLAIN_SHAPLEY) return hcg_shapley_launch(p, stream);
   if (p->mode == HCG_EXPLAIN_COALITIONS) return hcg_coalitions_launch(p, stream);
   if (p->mode == HCG_EXPLAIN_SUBSETS) return hcg_subsets_launch(p, stream);
+  if (p->mode == HCG_EXPLAIN_GREEDY) return hcg_greedy_launch(p, stream);
   if (p->mode == HCG_EXPLAIN_MOMENTS) return x_moments_launch(p, stream);
   const bool fit = p->mode == HCG_EXPLAIN_FIT;
   const bool path = p->mode == HCG_EXPLAIN_INTEGRATED;

@@ -46,6 +46,8 @@
 // HCG_EXPLAIN_SUBSETS (k_subset_values, below the coalition kernel): a caller's LIST of subsets of a graph's groups, any number
 // of groups, evaluated the same way -- but the set groups are applied in ONE filtered pass over the graph's member list
 // (s_apply_subset), the row's bit words staged in pj / pv, where the coalition kernel pays one s_apply per set group.
+// HCG_EXPLAIN_GREEDY (k_greedy_round, below the subset kernel): one round of the greedy insertion / deletion order per launch,
+// the previous round's winner picked on chip by every workgroup of the graph, the candidates evaluated as k_subset_values rows.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -562,6 +564,182 @@ __global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
   }
 }
 
+// HCG_EXPLAIN_GREEDY: one ROUND of the greedy insertion / deletion order of every graph's groups; launch k = a.round of a
+// sequence the host enqueues on one stream without reading anything in between.  One workgroup per job (graph, first id, ids),
+// the LDS layout, the build and the per-row sequence of k_subset_values.  The graph's on-set lives in pj / pv as bit words:
+// the start state (empty, or full for a deletion run) with the picks 0 .. k - 2 flipped, read from the `order` prefix that
+// the owners of earlier launches wrote.  For k >= 1 EVERY workgroup of the graph computes pick k - 1 itself from round
+// k - 1's candidate values (half (k - 1) & 1 of `cand`, written by launch k - 1; this launch writes the other half): the live
+// groups not yet picked, scanned with the total order (greater key, then lower id; NaN = -inf), so the pick does not depend
+// on how the scan is split over threads, and no workgroup reads what a sibling writes in the same launch.  Only the owner
+// (first id 0) records it: order[gp + k - 1] and the pick's C values.  The owner of launch 0 evaluates the all-on and the
+// background-only rows.  Then the job's candidates: flip the bit in LDS, rebuild from zero and evaluate exactly as a
+// k_subset_values row, write the C outputs to `cand`, flip the bit back -- bitwise that kernel's row for the same bits.
+struct GArgs {
+  XCommon c;
+  float* values;                            // [G][C] row gp + k: the outputs after pick k
+  float* cand;                              // [2][G][C]
+  int32_t* order;                           // [G]
+  float* out;                               // [B][C] everything on
+  float* out_base;                          // [B][C] the background only
+  const int32_t* jobs;                      // [.][3] graph, first id, ids
+  const int32_t* group_ptr;                 // [B + 1] ALL groups of graph g
+  const int32_t* member_ptr;                // [G + 1]
+  const int32_t* members;
+  const int32_t* member_group;              // parallel to `members`: the member's local group id
+  const int32_t* bg_ptr;                    // [B + 1]
+  const int32_t* bg_members;
+  long long G, B;
+  int first;                                // first job of this launch
+  int round, cls;
+  int deletion;                             // the on-set starts full; a picked group's bit is clear
+  float sgn;                                // key = sgn * value[cls]
+};
+
+// (key, id) of lane a against lane b's: the greater key, then the lower id
+__device__ __forceinline__ void g_better(float& bk, int& by, float ok, int oy) {
+  if (ok > bk || (ok == bk && oy < by)) { bk = ok; by = oy; }
+}
+
+__global__ __launch_bounds__(XT) void k_greedy_round(const GArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const XCommon& cm = a.c;
+  const SLds L = s_carve(smem, cm.npad, cm.emax);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int C = cm.C;
+  const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
+  const int g = __builtin_amdgcn_readfirstlane(job[0]);
+  const int y0 = __builtin_amdgcn_readfirstlane(job[1]);
+  const int ycount = __builtin_amdgcn_readfirstlane(job[2]);
+  if (g < 0 || g >= a.B) return;
+  const int gp = __builtin_amdgcn_readfirstlane(a.group_ptr[g]);
+  const int ng = __builtin_amdgcn_readfirstlane(a.group_ptr[g + 1]) - gp;
+  if (ng < 0 || ng > V_MAX_GROUPS || gp < 0 || (long long)gp + ng > a.G) return;
+  const int nw = (ng + 31) >> 5;                           // <= 512 = XT: one word per thread
+  const int k = a.round;
+  const bool owner = y0 == 0;
+  // the ids of the job that exist
+  const int ylo = max(0, y0);
+  const int yhi = (int)min((long long)y0 + ycount, (long long)ng);
+  float* const cw = a.cand + ((size_t)(k & 1) * (size_t)a.G + gp) * C;                  // this round's candidates
+  const float* const cr = a.cand + ((size_t)((k + 1) & 1) * (size_t)a.G + gp) * C;      // the round before's
+  const bool record = owner && k >= 1 && k - 1 < ng;       // the owner's row of `values` and entry of `order`
+  float* const vrow = a.values + (size_t)(gp + (record ? k - 1 : 0)) * C;
+
+  XSpan sp;
+  if (x_refused(sp, cm, g, tid)) {
+    for (long long i = (long long)ylo * C + tid; i < (long long)yhi * C; i += XT) cw[i] = 0.f;
+    if (owner && k == 0 && tid < C) { a.out[(size_t)g * C + tid] = 0.f; a.out_base[(size_t)g * C + tid] = 0.f; }
+    if (record && tid < C) vrow[tid] = 0.f;
+    return;
+  }
+  const bool evaluates = yhi > ylo || (owner && k == 0);   // (a job that only picks needs no graph)
+  const int nbase = sp.nbase, n = sp.n, ne = sp.ne;
+  float w[XD];
+  float rw0[16];
+  if (evaluates) {
+    s_build(L, cm, sp, tid);
+    s_load_weights(w, rw0, cm, tid);
+  }
+  const XMasked fmt{L.mval};
+  const int nF = n * cm.F, K = nF + ne;
+  const int bb = __builtin_amdgcn_readfirstlane(a.bg_ptr[g]), be = __builtin_amdgcn_readfirstlane(a.bg_ptr[g + 1]);
+  const int mb = __builtin_amdgcn_readfirstlane(a.member_ptr[gp]), me = __builtin_amdgcn_readfirstlane(a.member_ptr[gp + ng]);
+  unsigned* const bits = reinterpret_cast<unsigned*>(L.pj);     // [2 S_CHUNK]: pj and pv lie side by side
+
+  // the row in `bits`: everything off, the live background, the set groups in one filtered pass, one evaluation -- the
+  // sequence of a k_subset_values row.  Opens behind a barrier (bits written, the evaluation before done), ends behind one.
+  auto row = [&]() {
+    for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
+#pragma unroll
+    for (int j = 0; j < X_EPT; ++j)
+      if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
+    __syncthreads();
+    s_apply(L, cm, a.bg_members, bb, be, nbase, nF, K, tid);
+    __syncthreads();                                       // (the staging of the list before has been read)
+    s_apply_subset(L, cm, a.members, a.member_group, bits, ng, mb, me, nbase, nF, K, tid);
+    __syncthreads();
+    return s_eval(L, cm, fmt, w, rw0, n, tid);
+  };
+  // a word of the state in which every group of the graph is on
+  auto full_word = [&](int t) { return t == nw - 1 && (ng & 31) ? (1u << (ng & 31)) - 1u : 0xffffffffu; };
+
+  if (owner && k == 0) {
+    // ---------------------------------------------------------------------------------------------- launch 0: both ends
+    if (tid < nw) bits[tid] = full_word(tid);
+    __syncthreads();
+    int off = row();
+    if (tid < C) a.out[(size_t)g * C + tid] = L.hv[off + tid];
+    if (tid < nw) bits[tid] = 0u;
+    __syncthreads();
+    off = row();
+    if (tid < C) a.out_base[(size_t)g * C + tid] = L.hv[off + tid];
+    __syncthreads();                                       // (the filtered pass has read the words)
+  }
+
+  // ------------------------------------------------------------------------------------------------ the on-set after picks 0 .. k - 2
+  if (tid < nw) bits[tid] = a.deletion ? full_word(tid) : 0u;
+  __syncthreads();
+  for (int i = tid; i < min(k - 1, ng); i += XT) {
+    const int y = a.order[gp + i];
+    if (y >= 0 && y < ng) atomicXor(&bits[y >> 5], 1u << (y & 31));        // (integer: the picks are distinct, any order)
+  }
+  __syncthreads();
+
+  if (k >= 1) {
+    // ---------------------------------------------------------------------------------------------- pick k - 1
+    float bk = -INFINITY;
+    int by = 0x7fffffff;                                   // (no candidate: loses against every candidate, -inf keys included)
+    for (int y = tid; y < ng; y += XT) {
+      const bool picked = (((bits[y >> 5] >> (y & 31)) & 1u) != 0u) != (a.deletion != 0);
+      if (!picked && a.member_ptr[gp + y + 1] > a.member_ptr[gp + y]) {
+        float key = a.sgn * cr[(size_t)y * C + a.cls];
+        if (!(key == key)) key = -INFINITY;
+        g_better(bk, by, key, y);
+      }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float ok = __shfl_xor(bk, d);
+      const int oy = __shfl_xor(by, d);
+      g_better(bk, by, ok, oy);
+    }
+    float* const rk = L.t1;                                // [XW] (idle between two evaluations)
+    int* const ry = reinterpret_cast<int*>(L.t1) + XW;     // [XW]
+    if (lane == 0) { rk[wave] = bk; ry[wave] = by; }
+    __syncthreads();
+    bk = rk[0];
+    by = ry[0];
+#pragma unroll
+    for (int q = 1; q < XW; ++q) g_better(bk, by, rk[q], ry[q]);
+    const int pick = __builtin_amdgcn_readfirstlane(by);
+    if (pick < ng) {
+      if (tid == 0) bits[pick >> 5] ^= 1u << (pick & 31);
+      if (record) {
+        if (tid == 0) a.order[gp + k - 1] = pick;
+        if (tid < C) vrow[tid] = cr[(size_t)pick * C + tid];
+      }
+    }
+    __syncthreads();
+  }
+
+  // -------------------------------------------------------------------------------------------------- the job's candidates
+#pragma nounroll
+  for (int y = ylo; y < yhi; ++y) {
+    const unsigned m = 1u << (y & 31);
+    const bool picked = ((__builtin_amdgcn_readfirstlane(bits[y >> 5]) & m) != 0u) != (a.deletion != 0);
+    const bool live = __builtin_amdgcn_readfirstlane(a.member_ptr[gp + y + 1]) > __builtin_amdgcn_readfirstlane(a.member_ptr[gp + y]);
+    if (picked || !live) continue;                         // (uniform: the words are the same for every thread)
+    __syncthreads();                                       // (every thread has read the word)
+    if (tid == 0) bits[y >> 5] ^= m;
+    const int off = row();                                 // (its first barrier stands between the flip and the filtered pass)
+    if (tid < C) cw[(size_t)y * C + tid] = L.hv[off + tid];
+    if (tid == 0) bits[y >> 5] ^= m;
+    __syncthreads();
+    // (hv is next written behind the barriers of the next evaluation's conv stack)
+  }
+}
+
 // acc[i] (+)= sum_p ws[p][i], p ascending; the call that ends at the last permutation divides by their number
 __global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict__ ws, float* __restrict__ acc, long long row,
                                                         int count, int fresh, int last, float n_perm) {
@@ -697,4 +875,50 @@ int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
   a.B = p->B;
   a.first = p->coal_job_first;
   return x_launch<k_subset_values>(dim3((unsigned)p->coal_job_count), lds, stream, a);
+}
+
+// hcg_explain, mode HCG_EXPLAIN_GREEDY (explain.hip dispatches here)
+int hcg_greedy_launch(hcg_explain_args* p, hipStream_t stream) {
+  if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  // (what is wrong whatever the shapes are, by a query too: the column, the round, the flags)
+  if (p->class_index < 0 || p->class_index >= p->C || p->greedy_round < 0 ||
+      (p->greedy_flags & ~(HCG_GREEDY_DELETION | HCG_GREEDY_NEGATE)))
+    return HCG_ERR_INVALID_ARG;
+  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  if (p->sub_max_groups > V_MAX_GROUPS) return HCG_ERR_UNSUPPORTED;
+  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
+  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
+  p->lds_bytes = (int32_t)lds;
+  p->workspace_bytes_needed = 0;
+  if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
+  if (p->sub_max_groups < 0 || p->shap_n_groups < 0 || p->shap_n_groups >= (1ll << 31) || p->coal_job_first < 0 ||
+      p->coal_job_count < 0)
+    return HCG_ERR_INVALID_ARG;
+  if (p->B == 0 || p->coal_job_count == 0) return HCG_OK;
+  if (!x_common_ok(p) || !p->out_base || !p->coal_values || !p->coal_jobs || !p->greedy_order || !p->greedy_cand ||
+      !p->sub_member_group || !p->shap_group_ptr || !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members)
+    return HCG_ERR_INVALID_ARG;
+
+  GArgs a;
+  x_fill_common(a.c, p, S_NPAD_MIN);
+  a.values = p->coal_values;
+  a.cand = p->greedy_cand;
+  a.order = p->greedy_order;
+  a.out = p->out;
+  a.out_base = p->out_base;
+  a.jobs = p->coal_jobs;
+  a.group_ptr = p->shap_group_ptr;
+  a.member_ptr = p->shap_member_ptr;
+  a.members = p->shap_members;
+  a.member_group = p->sub_member_group;
+  a.bg_ptr = p->shap_bg_ptr;
+  a.bg_members = p->shap_bg_members;
+  a.G = p->shap_n_groups;
+  a.B = p->B;
+  a.first = p->coal_job_first;
+  a.round = p->greedy_round;
+  a.cls = p->class_index;
+  a.deletion = (p->greedy_flags & HCG_GREEDY_DELETION) ? 1 : 0;
+  a.sgn = (p->greedy_flags & HCG_GREEDY_NEGATE) ? -1.f : 1.f;
+  return x_launch<k_greedy_round>(dim3((unsigned)p->coal_job_count), lds, stream, a);
 }

@@ -261,6 +261,43 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   launch the five shap_ arrays, coal_values, coal_jobs, sub_bits, sub_word_ptr and sub_member_group non-NULL.  Shapes, LDS
  *   and refusals as HCG_EXPLAIN_SHAPLEY (184 nodes; a refused graph: the rows of its jobs zero, HCG_STATUS_SHAPE_LIMIT).
  *   HCG_EXPLAIN_QUERY as above; also writes lds_bytes.  The sub_ fields follow the coal_ fields in the union's fourth member.
+ * HCG_EXPLAIN_GREEDY: ONE ROUND of the model-driven greedy insertion or deletion order of each graph's groups, for ONE frozen
+ *   model and a batch of graphs (csrc/shapley.hip, k_greedy_round): the order every attribution's deletion / insertion curve
+ *   is read against, and the top-k sufficient / necessary set.  Players, background, features, their indexing and the shap_
+ *   fields are those of HCG_EXPLAIN_SUBSETS (ALL groups listed; a dead group has an empty member range and is never a
+ *   candidate), sub_member_group as there.  The on-set of graph g starts empty (insertion) or full (HCG_GREEDY_DELETION in
+ *   greedy_flags).  In round k the candidates are the live groups not yet picked; candidate y's value is the output [C] with
+ *   the background and (the on-set with y flipped) on; its key is sgn value[class_index], sgn = -1 with HCG_GREEDY_NEGATE
+ *   and +1 without; the pick is the candidate with the greatest key, equal keys go to the lower group id and a NaN key
+ *   counts as -inf -- a total order on (key, id), so the pick does not depend on the shape of the reduction -- and its bit
+ *   is flipped for good.  A call is launch k = greedy_round of a sequence the caller enqueues on one stream, k = 0, 1, ...,
+ *   with no host read in between: coal_jobs holds int32 triples (graph, first id, ids), the call runs the jobs
+ *   coal_job_first .. coal_job_first + coal_job_count - 1, one workgroup each; launch k's jobs of a graph tile its ids
+ *   0 .. G_g - 1, the job whose first id is 0 is the graph's OWNER (exactly one per graph and launch), and a graph whose
+ *   rounds have all run gets one job (g, 0, 0) in the next launch and none afterwards.  A workgroup of launch k stages the
+ *   graph's on-set after the picks 0 .. k - 2 as bit words in LDS from greedy_order[shap_group_ptr[g] ..] (integer
+ *   operations only), and for k >= 1 computes pick k - 1 ITSELF from round k - 1's candidate values -- greedy_cand
+ *   [2][G][C] float32, half (k - 1) & 1, written by launch k - 1; this launch writes the other half, so no workgroup reads
+ *   what a sibling writes in the same launch, and no workgroup waits for another.  Only the owner writes
+ *   greedy_order[shap_group_ptr[g] + k - 1] = the pick (int32 [G], the caller presets it to -1) and the pick's C values to
+ *   row shap_group_ptr[g] + k - 1 of coal_values [G][C] (the caller presets 0); the owner of launch 0 evaluates the all-on
+ *   and the background-only rows into `out` / out_base [B, C].  Then the workgroup evaluates its job's candidates: for each,
+ *   the bit is flipped in LDS, the state REBUILT from zero and evaluated exactly as HCG_EXPLAIN_SUBSETS does for a row with
+ *   those bits, the C outputs written to greedy_cand, and the bit flipped back -- so a candidate's value is bitwise that
+ *   mode's row, a pick is a function of those values alone, and the result is bitwise independent of the tiling, of the
+ *   rest of the batch and of the call.  No workspace (workspace_bytes_needed = 0), no reduction across workgroups, no
+ *   atomics on floats.  Contents are trusted, but a graph outside [0, B), an id outside [0, G_g), an entry of greedy_order
+ *   outside [0, G_g) and a member outside [0, K_g) are skipped, never used as an address.  edge_mask, node_mask, target /
+ *   target_class, dout and perm must be NULL and HCG_EXPLAIN_TARGET_CLASS / HCG_EXPLAIN_GROUPED clear, greedy_round >= 0,
+ *   greedy_flags within its two bits, 0 <= class_index < C (HCG_ERR_INVALID_ARG, checked before the shapes and by a query
+ *   too); sub_max_groups = the largest G_g must be
+ *   <= 16384 (HCG_ERR_UNSUPPORTED); for a launch the five shap_ arrays, sub_member_group, coal_values, coal_jobs,
+ *   greedy_order, greedy_cand, `out` and out_base non-NULL.  coal_rows, coal_max_live and sub_word_ptr are not read.
+ *   Shapes, LDS and refusals as HCG_EXPLAIN_SHAPLEY (184 nodes, 1024 directed edges, 160 KB; a refused graph: what its
+ *   workgroups own is zero -- their candidate rows, the owner's row of coal_values, `out` / out_base -- its greedy_order
+ *   entries are left alone, HCG_STATUS_SHAPE_LIMIT).  HCG_EXPLAIN_QUERY as above; also writes lds_bytes.  greedy_round and
+ *   greedy_flags follow the sub_ fields in the union's fourth member, which they fill; greedy_order and greedy_cand take
+ *   the slots of coal_live_ptr and sub_bits, which this mode does not read.
  * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
  *   node_mask_type 'attributes', edge_mask_type 'object'; regression, or multiclass classification on raw outputs) for a
  *   batch of graphs in ONE launch: the kernel of
@@ -328,13 +365,16 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
 #define HCG_EXPLAIN_MOMENTS 6
 #define HCG_EXPLAIN_COALITIONS 7
 #define HCG_EXPLAIN_SUBSETS 8
+#define HCG_EXPLAIN_GREEDY 9
+#define HCG_GREEDY_DELETION 1  /* greedy_flags: the on-set starts full and a pick removes a group */
+#define HCG_GREEDY_NEGATE 2    /* greedy_flags: the key is -value[class_index] */
 #define HCG_EXPLAIN_QUERY 1    /* flags */
 #define HCG_EXPLAIN_SIGMOID 2  /* flags */
 #define HCG_EXPLAIN_TARGET_CLASS 4  /* flags: the target slot holds int64 class indices [B] (target_class), not float [B, C] */
 #define HCG_EXPLAIN_GROUPED 8  /* flags: HCG_EXPLAIN_SHAPLEY walks groups of features (the shap_ fields) */
 #define HCG_EXPLAIN_MAX_CONVS 4
 typedef struct hcg_explain_args {
-  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS / _COALITIONS / _SUBSETS */
+  int32_t mode;                          /* HCG_EXPLAIN_GRAPHS / _LAYER_EDGE_GRAD / _ENSEMBLE / _SHAPLEY / _FIT / _INTEGRATED / _MOMENTS / _COALITIONS / _SUBSETS / _GREEDY */
   int32_t flags;                         /* HCG_EXPLAIN_QUERY | HCG_EXPLAIN_SIGMOID | HCG_EXPLAIN_TARGET_CLASS | HCG_EXPLAIN_GROUPED */
   const float* x;                        /* [N, F] */
   const int64_t* edge_index;             /* [2, E], grouped by graph */
@@ -426,7 +466,7 @@ typedef struct hcg_explain_args {
   int32_t mom_count;                     /* models of this call; mom_first + mom_count <= mom_total */
   int32_t mom_reserved;
   };
-  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED, HCG_EXPLAIN_COALITIONS and HCG_EXPLAIN_SUBSETS */
+  struct {                               /*   HCG_EXPLAIN_SHAPLEY with HCG_EXPLAIN_GROUPED, HCG_EXPLAIN_COALITIONS, HCG_EXPLAIN_SUBSETS and HCG_EXPLAIN_GREEDY */
   const int32_t* shap_group_ptr;         /* [B + 1] prefix sum of the graphs' group counts */
   const int32_t* shap_member_ptr;        /* [G + 1] group -> its range of shap_members */
   const int32_t* shap_members;           /* live members only: local feature indices, ascending within a group */
@@ -435,17 +475,25 @@ typedef struct hcg_explain_args {
   int64_t shap_n_groups;                 /* G */
   float* coal_values;                    /* HCG_EXPLAIN_COALITIONS from here on: OUT [coal_rows, C] */
   const int32_t* coal_jobs;              /* [.][3]: graph, first mask, masks */
+  union {                                /* one slot: */
   const int64_t* coal_live_ptr;          /* [B + 1] graph g's rows: coal_live_ptr[g] + mask */
+  int32_t* greedy_order;                 /* HCG_EXPLAIN_GREEDY: IN/OUT [G] the picks, graph g's from shap_group_ptr[g]; preset to -1 */
+  };
   int64_t coal_rows;                     /* T_live = sum_g 2^L_g */
   int32_t coal_job_first;                /* first job of this call */
   int32_t coal_job_count;                /* jobs of this call (the grid) */
   int32_t coal_max_live;                 /* the largest L_g, <= 16 */
   int32_t coal_reserved;
+  union {                                /* one slot: */
   const uint32_t* sub_bits;              /* HCG_EXPLAIN_SUBSETS from here on (it reads coal_values / _jobs / _rows / _job_first / _job_count too): [coal_rows][W] */
+  float* greedy_cand;                    /* HCG_EXPLAIN_GREEDY: IN/OUT [2][G][C] the candidates' values of the last two rounds */
+  };
   const int32_t* sub_word_ptr;           /* [B + 1] prefix sum of ceil(G_g / 32); W = sub_word_ptr[B] */
   const int32_t* sub_member_group;       /* parallel to shap_members: the member's local group id */
   int32_t sub_max_groups;                /* the largest G_g, <= 16384 */
   int32_t sub_reserved;
+  int32_t greedy_round;                  /* HCG_EXPLAIN_GREEDY (it reads the shap_ fields, coal_values / _jobs / _job_first / _job_count, sub_member_group / _max_groups too): k */
+  int32_t greedy_flags;                  /* HCG_GREEDY_DELETION | HCG_GREEDY_NEGATE */
   };
   };
 } hcg_explain_args;
