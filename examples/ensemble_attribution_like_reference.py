@@ -14,6 +14,13 @@ This is an EXAMPLE, not a parity claim: neither captum nor torch_geometric is a 
 of the reference pins these values.
 
     python examples/ensemble_attribution_like_reference.py --models 9 --graphs 52 --steps 50
+
+`--method shapley --players atoms|fragments` explains the same joint prediction with the reference's other algorithm, Shapley
+value sampling (`EnsembleShapley`: one set of permutations for all models); `--curves` asks the ensemble itself which ranking
+to believe: deletion / insertion AUCs of its MEAN output (`EnsembleCurves`) for the Shapley ranking, the integrated-gradients
+ranking (`group_scores` of `EnsembleAttribution`'s means) and a random order.
+
+    python examples/ensemble_attribution_like_reference.py --models 9 --graphs 52 --method shapley --players atoms --curves
 """
 from __future__ import annotations
 
@@ -35,7 +42,12 @@ def main():
     ap.add_argument("--models", type=int, default=9)
     ap.add_argument("--graphs", type=int, default=52)
     ap.add_argument("--steps", type=int, default=50, help="quadrature points of the path")
-    ap.add_argument("--method", default="gausslegendre", choices=["gausslegendre", "riemann_middle", "gradient"])
+    ap.add_argument("--method", default="gausslegendre", choices=["gausslegendre", "riemann_middle", "gradient", "shapley"],
+                    help="a quadrature of the integrated-gradients path, or 'shapley': Shapley value sampling of the ensemble (`EnsembleShapley`)")
+    ap.add_argument("--players", default="atoms", choices=["atoms", "fragments"], help="--method shapley / --curves: the players (fragments: 3 per graph)")
+    ap.add_argument("--permutations", type=int, default=25, help="--method shapley: sampled orders of the players")
+    ap.add_argument("--curves", action="store_true", help="deletion / insertion AUCs of the ensemble's MEAN output for the Shapley ranking, "
+                                                          "the integrated-gradients ranking and a random order (`EnsembleCurves`)")
     ap.add_argument("--weights", nargs="*", default=None, help="saved state dicts, one per model; default: train on the synthetic labels")
     ap.add_argument("--train-steps", type=int, default=30)
     ap.add_argument("--top", type=int, default=3, help="atoms printed per graph")
@@ -65,6 +77,34 @@ def main():
             if losses:
                 print(f"model {k}: trained {a.train_steps} steps on the synthetic labels: loss {losses[0]:.4f} -> {losses[-1]:.4f}")
 
+    ag = H.atom_groups(batch)
+    sizes = torch.bincount(batch.batch, minlength=batch.num_graphs)
+    players = ag if a.players == "atoms" else ag * 3 // sizes[batch.batch]
+    if a.method == "shapley" or a.curves:
+        # Shapley values are linear in the output: the mean over the models IS the sampled Shapley value of the mean prediction
+        es = H.EnsembleShapley(models)
+        rs = es(batch, n_samples=a.permutations, generator=torch.Generator().manual_seed(a.seed), node_group=players)
+        gp = rs.group_ptr.cpu().tolist()
+        print(f"path {es.last_path}: Shapley value sampling of {len(models)} models x {batch.num_graphs} graphs, {a.permutations} shared "
+              f"permutations of {gp[-1]} {a.players}")
+        for g in range(min(a.show, batch.num_graphs)):
+            mean_g, std_g = rs.group_mean[gp[g]:gp[g + 1]].cpu(), rs.group_std[gp[g]:gp[g + 1]].cpu()
+            idx = torch.topk(mean_g.abs(), min(a.top, mean_g.numel())).indices
+            print(f"graph {g}: " + ", ".join(f"{a.players[:-1]} {int(i)} ({float(mean_g[i]):+.3e} +- {float(std_g[i]):.1e})" for i in idx))
+    if a.curves:
+        ig = H.EnsembleAttribution(models, n_steps=a.steps, method="gausslegendre" if a.method == "shapley" else a.method)
+        ri = ig(batch, class_index=0)
+        scores, _ = H.group_scores(ri.node_mean, ri.edge_mean, players, None, batch)
+        rand = torch.rand(int(rs.group_mean.numel()), generator=torch.Generator().manual_seed(a.seed + 7)).to(scores.device)
+        ec = H.EnsembleCurves(models)
+        print(f"mean AUC over the graphs of the ensemble's mean output (insertion: higher is better for a positive prediction; path {ig.last_path}):")
+        for label, sc in (("ensemble Shapley", rs.group_mean), ("ensemble integrated gradients", scores), ("random order", rand)):
+            rc = ec(batch, H.ranking(sc, rs.group_ptr), node_group=players)
+            print(f"  {label:32s} insertion {float(rc.insertion_auc.mean()):+.4f}  deletion {float(rc.deletion_auc.mean()):+.4f}  "
+                  f"largest std over the models on a curve {float(torch.maximum(rc.insertion_std.max(), rc.deletion_std.max())):.3e}")
+        print(f"path {ec.last_path}: every subset of both curves evaluated by every model in one call per ranking")
+    if a.method == "shapley":
+        return
     ea = H.EnsembleAttribution(models, n_steps=a.steps, method=a.method)
     r = ea(batch, class_index=0)
     print(f"path {ea.last_path}: {len(models)} models x {batch.num_graphs} graphs, {ea.n_steps} point(s) of {a.method} each, one call")

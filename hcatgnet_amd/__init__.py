@@ -39,12 +39,18 @@ Public surface (mirrors the reference's names for this path):
                                                 relatives InputXGradient and Saliency
     EnsembleAttribution                         the same attributions of M models in one launch (one workgroup per graph
                                                 and model), with their mean and standard deviation over the models
+    EnsembleShapley, EnsembleSubsetValues, EnsembleCurves
+                                                Shapley value sampling, subset values and deletion / insertion curves of M
+                                                models, the model a grid axis of the single-model kernels: the moments over
+                                                the models on the device, entry [m] bitwise the single-model class's
 Compute lives in csrc/libhcatgnet_hip.so (hand-written HIP for gfx950) behind include/hcatgnet_hip.h.
 """
 from .attribution import EnsembleAttribution, EnsembleAttributionResult, IntegratedGradients, IntegratedGradientsResult, quadrature  # noqa: F401
 from .batch import Batch, Data, DataLoader, collate  # noqa: F401
 from .call_methods import default_options, make_network  # noqa: F401
 from .ensemble import EnsemblePredict, EnsembleResult, stack_weights  # noqa: F401
+from .ensemble_shapley import (EnsembleCurveResult, EnsembleCurves, EnsembleFeatureShapleyResult, EnsembleShapley,  # noqa: F401
+                               EnsembleShapleyResult, EnsembleSubsetResult, EnsembleSubsetValues)
 from .explain import ExplainFit, ExplainFitResult, ExplainFitState  # noqa: F401
 from .fit import FitControl, FitResult, fit_network, fit_networks  # noqa: F401
 from .gcn import GCN, GCN_explain, GCNConv  # noqa: F401
@@ -64,4 +70,6 @@ __all__ = ["make_network", "default_options", "GCN", "GCN_explain", "GCNConv", "
            "ExplainFitState", "fit_network", "fit_networks", "FitResult", "FitControl", "IntegratedGradients", "IntegratedGradientsResult",
            "quadrature", "EnsembleAttribution", "EnsembleAttributionResult", "CoalitionValues", "CoalitionResult",
            "shapley_from_coalitions", "interactions_from_coalitions", "SubsetValues", "SubsetResult", "AttributionCurves",
-           "CurveResult", "pack_subsets", "ranking", "group_scores", "GreedySelection", "GreedyResult"]
+           "CurveResult", "pack_subsets", "ranking", "group_scores", "GreedySelection", "GreedyResult",
+           "EnsembleShapley", "EnsembleShapleyResult", "EnsembleFeatureShapleyResult", "EnsembleSubsetValues", "EnsembleSubsetResult",
+           "EnsembleCurves", "EnsembleCurveResult"]

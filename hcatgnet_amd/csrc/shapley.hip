@@ -48,6 +48,13 @@
 // (s_apply_subset), the row's bit words staged in pj / pv, where the coalition kernel pays one s_apply per set group.
 // HCG_EXPLAIN_GREEDY (k_greedy_round, below the subset kernel): one round of the greedy insertion / deletion order per launch,
 // the previous round's winner picked on chip by every workgroup of the graph, the candidates evaluated as k_subset_values rows.
+// A model axis (k_shapley_walk, both instantiations, and k_subset_values): n_models = M frozen models of one architecture,
+// weights stacked [M, ...], one more grid axis -- walk dim3(B, perm_count, M), subsets dim3(jobs, M).  The model index is
+// uniform: s_model shifts the weight pointers of a LOCAL XCommon by m times the layer's size once, at the top of the kernel,
+// and s_apply*, s_load_weights and s_eval run on it unchanged.  Every output takes a leading model axis (out / out_base
+// [M][B][C], workspace [M][count][row], shap_acc [M][row], table [M][S][B][C]); with M = 1 every offset is zero.  The
+// coalition and the greedy kernel take one model (n_models > 1: HCG_ERR_UNSUPPORTED); a loop over a group of models INSIDE
+// a workgroup, which would build the graph once per group as ensemble.hip does, is not done.
 #include "common.h"
 #include "graph_csr.h"
 #include "explain_tile.h"
@@ -113,6 +120,26 @@ __device__ __forceinline__ SLds s_carve(char* base, int npad, int emax) {
 }
 
 __device__ __forceinline__ float s_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+// The launch's XCommon with the weight pointers of model m (uniform) of weights stacked [M, ...]: layer sizes 64 F, then
+// 64 * 64 (conv), 64 (conv bias), out_i in_i and out_i (readout; in_i = 128 >> i, out_i = C on the last layer).  m = 0
+// changes nothing.  A layer the model does not have keeps a pointer nobody reads.
+__device__ __forceinline__ XCommon s_model(const XCommon& c, unsigned m) {
+  XCommon r = c;
+  const size_t mm = m;
+#pragma unroll
+  for (int l = 0; l < HCG_EXPLAIN_MAX_CONVS; ++l) {
+    r.cW[l] = c.cW[l] + mm * (size_t)(XD * (l == 0 ? c.F : XD));
+    r.cb[l] = c.cb[l] + mm * XD;
+  }
+#pragma unroll
+  for (int i = 0; i < HCG_HEAD_MAX_LAYERS; ++i) {
+    const int in_i = (2 * XD) >> i, out_i = i == c.R - 1 ? c.C : in_i / 2;
+    r.hW[i] = c.hW[i] + mm * (size_t)(out_i * in_i);
+    r.hb[i] = c.hb[i] + mm * (size_t)out_i;
+  }
+  return r;
+}
 
 // GROUPED: switch the members mem[mb .. me) on (mb, me uniform; all 8 waves).  XT members at a time are staged in t1 (free
 // between two evaluations): the thread that loads a member stores an edge's mval = 1 itself and leaves a node entry as
@@ -264,20 +291,23 @@ __device__ __forceinline__ void s_build(const SLds& L, const XCommon& cm, const 
 template <bool GROUPED, class Args>
 __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const XCommon& cm = a.c;
+  const XCommon cm = s_model(a.c, blockIdx.z);             // grid z: the model
   const SLds L = s_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x;
   const int F = cm.F, C = cm.C;
   const bool p0 = a.first + (int)blockIdx.y == 0;          // permutation 0 of the whole call writes out / out_base
-  float* const wsrow = a.ws + (size_t)blockIdx.y * (size_t)a.row;
+  // the model's slices: ws [M][count][row], out / out_base [M][B][C]
+  float* const wsrow = a.ws + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * (size_t)a.row;
+  float* const out = a.out + (size_t)blockIdx.z * gridDim.x * C;
+  float* const out_base = a.out_base + (size_t)blockIdx.z * gridDim.x * C;
 
   XSpan sp;
   if (x_refused(sp, cm, g, tid)) {
     // the graph's rows are zero -- over whatever part of its ranges lies inside the arrays
     const int nbase = sp.nbase, ebase = sp.ebase, n_raw = sp.n_raw, ne_raw = sp.ne_raw;
     if (p0)
-      for (int k = tid; k < C; k += XT) { a.out[(size_t)g * C + k] = 0.f; a.out_base[(size_t)g * C + k] = 0.f; }
+      for (int k = tid; k < C; k += XT) { out[(size_t)g * C + k] = 0.f; out_base[(size_t)g * C + k] = 0.f; }
     if constexpr (GROUPED) {
       const long long ge = a.group_ptr[g + 1];
       for (long long k = (long long)a.group_ptr[g] + tid; k < ge; k += XT)
@@ -387,7 +417,7 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
     off = s_eval(L, cm, fmt, w, rw0, n, tid);
     const float v = L.hv[off + a.cls];
     if (base) {
-      if (p0 && tid < C) a.out_base[(size_t)g * C + tid] = L.hv[off + tid];
+      if (p0 && tid < C) out_base[(size_t)g * C + tid] = L.hv[off + tid];
     } else if (tid == 0) {
       wsrow[GROUPED ? (size_t)(gp + j) : j < nF ? (size_t)nbase * F + j : (size_t)(a.NF + ebase + (j - nF))] = v - vprev;
     }
@@ -397,7 +427,7 @@ __global__ __launch_bounds__(XT) void k_shapley_walk(const Args a) {
   }
   // hv still holds the last evaluation: everything on (features that were skipped change nothing; GROUPED: every live
   // feature is in the background or in a group)
-  if (p0 && tid < C) a.out[(size_t)g * C + tid] = L.hv[off + tid];
+  if (p0 && tid < C) out[(size_t)g * C + tid] = L.hv[off + tid];
 }
 
 // HCG_EXPLAIN_COALITIONS: the table v(S) over every subset S of a graph's LIVE groups.  One workgroup per job (graph, run of
@@ -508,10 +538,11 @@ constexpr int V_MAX_GROUPS = 2 * S_CHUNK * 32;     // the bits pj / pv hold: 163
 
 __global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const XCommon& cm = a.c;
+  const XCommon cm = s_model(a.c, blockIdx.y);             // grid y: the model
   const SLds L = s_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x;
   const int C = cm.C;
+  float* const table = a.table + (size_t)blockIdx.y * (size_t)a.S * (size_t)a.B * C;      // [M][S][B][C]: the model's slice
   const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
   const int g = __builtin_amdgcn_readfirstlane(job[0]);
   const int s0 = __builtin_amdgcn_readfirstlane(job[1]);
@@ -531,7 +562,7 @@ __global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
   XSpan sp;
   if (x_refused(sp, cm, g, tid)) {
     for (long long s = slo; s < shi; ++s)
-      if (tid < C) a.table[((size_t)s * (size_t)a.B + g) * C + tid] = 0.f;
+      if (tid < C) table[((size_t)s * (size_t)a.B + g) * C + tid] = 0.f;
     return;
   }
   const int nbase = sp.nbase, n = sp.n, ne = sp.ne;
@@ -559,7 +590,7 @@ __global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
     s_apply_subset(L, cm, a.members, a.member_group, bits, ng, mb, me, nbase, nF, K, tid);
     __syncthreads();
     const int off = s_eval(L, cm, fmt, w, rw0, n, tid);
-    if (tid < C) a.table[((size_t)s * (size_t)a.B + g) * C + tid] = L.hv[off + tid];
+    if (tid < C) table[((size_t)s * (size_t)a.B + g) * C + tid] = L.hv[off + tid];
     // (hv is next written behind the barriers of the next evaluation's conv stack)
   }
 }
@@ -740,21 +771,30 @@ __global__ __launch_bounds__(XT) void k_greedy_round(const GArgs a) {
   }
 }
 
-// acc[i] (+)= sum_p ws[p][i], p ascending; the call that ends at the last permutation divides by their number
+// acc[i] (+)= sum_p ws[p][i], p ascending; the call that ends at the last permutation divides by their number.  Grid y: the
+// model -- its [count][row] slice of the workspace, its row of the accumulator, the same sum.
 __global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict__ ws, float* __restrict__ acc, long long row,
                                                         int count, int fresh, int last, float n_perm) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= row) return;
+  ws += (size_t)blockIdx.y * (size_t)count * (size_t)row;
+  acc += (size_t)blockIdx.y * (size_t)row;
   float s = fresh ? 0.f : acc[i];
   for (int p = 0; p < count; ++p) s += ws[(size_t)p * (size_t)row + i];
   acc[i] = last ? s / n_perm : s;
 }
+
+// the model axis of HCG_EXPLAIN_SHAPLEY and HCG_EXPLAIN_SUBSETS: n_models, 0 (what a caller of the one-model form leaves
+// there) meaning 1, as HCG_EXPLAIN_INTEGRATED reads it
+inline int s_models(const hcg_explain_args* p) { return p->n_models == 0 ? 1 : p->n_models; }
 
 }  // namespace
 
 // hcg_explain, mode HCG_EXPLAIN_SHAPLEY (explain.hip dispatches here)
 int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   if (p->edge_mask || p->node_mask || p->target || p->dout) return HCG_ERR_INVALID_ARG;
+  const int M = s_models(p);
+  if (M < 1 || M > 65535) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
   const bool grouped = (p->flags & HCG_EXPLAIN_GROUPED) != 0;
   const long long NF = (long long)p->N * p->F;
@@ -766,8 +806,8 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
   if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
   p->lds_bytes = (int32_t)lds;
-  // one row of differences per permutation of this call
-  p->workspace_bytes_needed = hcg_align_up((size_t)count * (size_t)(row > 0 ? row : 1) * sizeof(float), 256);
+  // one row of differences per permutation of this call and model: M times the one-model figure ([M][count][row], packed)
+  p->workspace_bytes_needed = (size_t)M * hcg_align_up((size_t)count * (size_t)(row > 0 ? row : 1) * sizeof(float), 256);
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (p->n_perm < 1 || p->perm_count < 1 || p->perm_first < 0 || (long long)p->perm_first + p->perm_count > p->n_perm ||
       p->class_index < 0 || p->class_index >= p->C)
@@ -794,12 +834,12 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   a.members = grouped ? p->shap_members : nullptr;
   a.bg_ptr = grouped ? p->shap_bg_ptr : nullptr;
   a.bg_members = grouped ? p->shap_bg_members : nullptr;
-  const dim3 grid((unsigned)p->B, (unsigned)p->perm_count);
+  const dim3 grid((unsigned)p->B, (unsigned)p->perm_count, (unsigned)M);
   const int rc = grouped ? x_launch<k_shapley_walk<true, SGArgs>>(grid, lds, stream, a)
                          : x_launch<k_shapley_walk<false, SArgs>>(grid, lds, stream, static_cast<const SArgs&>(a));
   if (rc != HCG_OK) return rc;
   if (row > 0) {
-    hipLaunchKernelGGL(k_shapley_reduce, dim3((unsigned)hcg_cdiv(row, 256)), dim3(256), 0, stream, (const float*)p->workspace,
+    hipLaunchKernelGGL(k_shapley_reduce, dim3((unsigned)hcg_cdiv(row, 256), (unsigned)M), dim3(256), 0, stream, (const float*)p->workspace,
                        p->shap_acc, row, p->perm_count, p->perm_first == 0 ? 1 : 0,
                        p->perm_first + p->perm_count == p->n_perm ? 1 : 0, (float)p->n_perm);
     HCG_CHECK_LAUNCH();
@@ -810,6 +850,7 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
 // hcg_explain, mode HCG_EXPLAIN_COALITIONS (explain.hip dispatches here)
 int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream) {
   if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  if (p->n_models > 1) return HCG_ERR_UNSUPPORTED;          // (the kernel has no model axis: never one model silently)
   if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
   if (p->coal_max_live > C_MAX_GROUPS || p->coal_rows >= (1ll << 31)) return HCG_ERR_UNSUPPORTED;
   const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
@@ -844,6 +885,8 @@ int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream) {
 // hcg_explain, mode HCG_EXPLAIN_SUBSETS (explain.hip dispatches here)
 int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
   if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  const int M = s_models(p);
+  if (M < 1 || M > 65535) return HCG_ERR_INVALID_ARG;
   if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
   if (p->sub_max_groups > V_MAX_GROUPS || p->coal_rows >= (1ll << 31)) return HCG_ERR_UNSUPPORTED;
   const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
@@ -874,7 +917,7 @@ int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
   a.G = p->shap_n_groups;
   a.B = p->B;
   a.first = p->coal_job_first;
-  return x_launch<k_subset_values>(dim3((unsigned)p->coal_job_count), lds, stream, a);
+  return x_launch<k_subset_values>(dim3((unsigned)p->coal_job_count, (unsigned)M), lds, stream, a);
 }
 
 // hcg_explain, mode HCG_EXPLAIN_GREEDY (explain.hip dispatches here)
@@ -884,6 +927,7 @@ int hcg_greedy_launch(hcg_explain_args* p, hipStream_t stream) {
   if (p->class_index < 0 || p->class_index >= p->C || p->greedy_round < 0 ||
       (p->greedy_flags & ~(HCG_GREEDY_DELETION | HCG_GREEDY_NEGATE)))
     return HCG_ERR_INVALID_ARG;
+  if (p->n_models > 1) return HCG_ERR_UNSUPPORTED;          // (the pick would need a reduction over the models inside a round)
   if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
   if (p->sub_max_groups > V_MAX_GROUPS) return HCG_ERR_UNSUPPORTED;
   const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));

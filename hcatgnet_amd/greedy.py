@@ -21,7 +21,7 @@ import torch
 
 from . import _frozen, _lib
 from .shapley import SUBSETS_PER_WORKGROUP, _group_layout
-from .subsets import MAX_SUBSET_GROUPS, SubsetValues, _group_graph
+from .subsets import MAX_SUBSET_GROUPS, SubsetValues, _group_graph, _member_group
 
 MODES = ("insertion", "deletion")
 
@@ -197,11 +197,8 @@ class GreedySelection(_frozen.FrozenModel):
         values.zero_()
         self.last_path, self.launches = "fused", len(lptr) - 1
         if B > 0:
-            # the local group id of every listed member (behind the groups' members: the background and the dead, never read)
             L = int(gr.members.numel())
-            glob = torch.bucketize(torch.arange(L, device=dev), gr.member_ptr[1:].to(torch.int64), right=True)
-            local = glob - gr.group_ptr[ggraph[glob.clamp(max=G - 1)]] if G > 0 else glob
-            member_group = torch.where(glob < G, local, torch.full_like(glob, -1)).to(torch.int32).contiguous()
+            member_group = _member_group(gr, ggraph)
             jobs_t = jobs.to(dev)
             group_ptr32 = gr.group_ptr.to(torch.int32)
             _frozen.query(a, self.KERNEL, self._shape(), batch, sub_max_groups=gr.max_groups)

@@ -50,10 +50,38 @@ class CurveResult(NamedTuple):
     out_base: torch.Tensor       # [B, C]
 
 
+class _CurvePlan(NamedTuple):
+    """The points of both curves of an order and the rows that hold them (`AttributionCurves._plan`); tensors on the batch's device."""
+    rows: torch.Tensor           # [S, G] bool: row 2 i = the first k groups of a graph's pair i, 2 i + 1 = everything else
+    rows_per_graph: list         # [B] host: the rows graph g uses
+    S: int
+    ins_row: torch.Tensor        # [Pn] int64: the row of the [S + 2, B, C] table that is the point's insertion value
+    del_row: torch.Tensor        # [Pn]
+    graph: torch.Tensor          # [Pn] int64: the point's graph
+    k: torch.Tensor              # [Pn] int64
+    curve_ptr: torch.Tensor      # [B + 1] int64
+    groups: torch.Tensor         # [Pn] int64: G_g of the point's graph
+    points: torch.Tensor         # [B] int64: points per graph
+    count: torch.Tensor          # [B] int64: G_g
+
+
 # ====================================================================== the bit layout
 def _group_graph(count: torch.Tensor, G: int) -> torch.Tensor:
     """[G] int64: the graph of every group"""
     return torch.repeat_interleave(torch.arange(count.numel(), device=count.device), count, output_size=G)
+
+
+def _member_group(gr, ggraph: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [len(gr.members)]: the local group id of every listed member of a `_group_layout`, -1 behind the groups' members
+    (the background and the dead, which the kernels never read as group members).  `ggraph`: `_group_graph(gr.count, gr.G)`
+    when the caller has it.  What `SubsetValues`, `GreedySelection` and `EnsembleSubsetValues` hand the library as
+    `sub_member_group`."""
+    L, G, dev = int(gr.members.numel()), gr.G, gr.members.device
+    if ggraph is None:
+        ggraph = _group_graph(gr.count, G)
+    glob = torch.bucketize(torch.arange(L, device=dev), gr.member_ptr[1:].to(torch.int64), right=True)
+    local = glob - gr.group_ptr[ggraph[glob.clamp(max=G - 1)]] if G > 0 else glob
+    return torch.where(glob < G, local, torch.full_like(glob, -1)).to(torch.int32).contiguous()
 
 
 def _pack(subsets: torch.Tensor, group_ptr: torch.Tensor, W: int):
@@ -278,12 +306,8 @@ class SubsetValues(_frozen.FrozenModel):
         rows = torch.cat([subsets, torch.ones(1, G, dtype=torch.bool, device=dev), torch.zeros(1, G, dtype=torch.bool, device=dev)])
         W = sum((c + 31) // 32 for c in counts)
         bits, word_ptr = _pack(rows, gr.group_ptr, W)
-        # the local group id of every listed member (behind the groups' members: the background and the dead, never read)
         L = int(gr.members.numel())
-        ggraph = _group_graph(gr.count, G)
-        glob = torch.bucketize(torch.arange(L, device=dev), gr.member_ptr[1:].to(torch.int64), right=True)
-        local = glob - gr.group_ptr[ggraph[glob.clamp(max=G - 1)]] if G > 0 else glob
-        member_group = torch.where(glob < G, local, torch.full_like(glob, -1)).to(torch.int32).contiguous()
+        member_group = _member_group(gr)
         jobs_t = jobs.to(dev)
         group_ptr32 = gr.group_ptr.to(torch.int32)
         _frozen.query(a, self.KERNEL, self._shape(), batch, coal_rows=S2, sub_max_groups=gr.max_groups)
@@ -390,7 +414,19 @@ class AttributionCurves:
         cls = sv._class(class_index)
         fr = self._fractions(fractions)
         gr, counts = sv._layout(batch, node_group, edge_group)
-        B, G, dev = len(counts), gr.G, batch.x.device
+        plan = self._plan(gr, counts, order, fr, batch.x.device)
+        table = sv._table(batch, gr, counts, plan.rows, plan.rows_per_graph, rows_per_workgroup, why)
+        insertion, deletion = self._gather(table, plan)
+        ins_auc, del_auc = self._areas(insertion, deletion, plan, cls)
+        # (rows S and S + 1: everything on, the background only)
+        return CurveResult(insertion, deletion, plan.k, plan.curve_ptr, gr.group_ptr, ins_auc, del_auc,
+                           table[plan.S].clone(), table[plan.S + 1].clone())
+
+    # ------------------------------------------------------------------ the rows and points of an order (`EnsembleCurves` too)
+    @staticmethod
+    def _plan(gr, counts, order, fr, dev) -> _CurvePlan:
+        """`order` checked; the points of both curves and the bool rows [S, G] of the one `SubsetValues` call that holds them"""
+        B, G = len(counts), gr.G
         if not torch.is_tensor(order) or order.dtype != torch.int32 or tuple(order.shape) not in ((G,), (1, G)):
             raise ValueError(f"order must be an int32 tensor of shape [G = {G}] or [1, {G}]; got "
                              f"{getattr(order, 'dtype', type(order))} {tuple(getattr(order, 'shape', ()))}")
@@ -435,18 +471,25 @@ class AttributionCurves:
         kk = kpair.to(dev)[r >> 1][:, ggraph]                               # [S, G]
         first = pos.to(torch.int16).unsqueeze(0) < kk
         rows = torch.where(((r & 1) == 1).unsqueeze(1), ~first, first) & (r.unsqueeze(1) < (2 * pairs).to(dev)[ggraph].unsqueeze(0))
-        table = sv._table(batch, gr, counts, rows, (2 * pairs).tolist(), rows_per_workgroup, why)
-
-        # ---- gather (S: everything on, S + 1: the background only)
+        # ---- which row of the [S + 2, B, C] table holds each point (S: everything on, S + 1: the background only)
         full, base = torch.full_like(k, S), torch.full_like(k, S + 1)
         ins_row = torch.where(k == 0, base, torch.where(k == Gp, full, 2 * pair))
         del_row = torch.where(k == 0, full, torch.where(k == Gp, base, 2 * pair + 1))
-        pg_d, k_d, cptr_d = pg.to(dev), k.to(dev), cptr.to(dev)
-        insertion, deletion = table[ins_row.to(dev), pg_d], table[del_row.to(dev), pg_d]
-        out_full, out_base = table[S].clone(), table[S + 1].clone()
+        return _CurvePlan(rows, (2 * pairs).tolist(), S, ins_row.to(dev), del_row.to(dev), pg.to(dev), k.to(dev), cptr.to(dev),
+                          Gp.to(dev), npts.to(dev), cnt.to(dev))
 
-        # ---- areas: the trapezoid rule over x = k / G_g, every graph's sum by one owner in point order
-        Gd = Gp.to(dev).to(torch.float64)
+    @staticmethod
+    def _gather(table, plan: _CurvePlan):
+        """-> (insertion [Pn, ...], deletion [Pn, ...]): the points' rows of a [S + 2, B, ...] table"""
+        return table[plan.ins_row, plan.graph], table[plan.del_row, plan.graph]
+
+    @staticmethod
+    def _areas(insertion, deletion, plan: _CurvePlan, cls: int):
+        """-> (insertion_auc [B], deletion_auc [B]): the trapezoid rule over x = k / G_g on column `cls`, every graph's sum
+        by one owner in point order"""
+        pg_d, k_d, cptr_d, cnt, npts, dev = plan.graph, plan.k, plan.curve_ptr, plan.count, plan.points, plan.k.device
+        B, Pn = int(cnt.numel()), int(k_d.numel())
+        Gd = plan.groups.to(torch.float64)
         xq = torch.where(Gd > 0, k_d.to(torch.float64) / Gd.clamp(min=1.0), torch.zeros_like(Gd))
         aucs = []
         for curve in (insertion, deletion):
@@ -455,8 +498,8 @@ class AttributionCurves:
             if Pn > 1:
                 same = pg_d[1:] == pg_d[:-1]
                 area[:-1] = torch.where(same, (xq[1:] - xq[:-1]) * (v[1:] + v[:-1]) * 0.5, torch.zeros_like(v[1:]))
-            auc = _segment_sums(area, npts.to(dev))
+            auc = _segment_sums(area, npts)
             if B > 0:
-                auc = torch.where(cnt.to(dev) == 0, v[cptr_d[:-1]], auc)
+                auc = torch.where(cnt == 0, v[cptr_d[:-1]], auc)
             aucs.append(auc.to(torch.float32))
-        return CurveResult(insertion, deletion, k_d, cptr_d, gr.group_ptr, aucs[0], aucs[1], out_full, out_base)
+        return aucs[0], aucs[1]

@@ -214,6 +214,16 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   N F + E and, for a launch, the five arrays non-NULL (HCG_ERR_INVALID_ARG).  A refused graph: its G_g entries zero.  LDS,
  *   shapes and the order of the sum over the permutations as without the flag.  The shap_ fields are the fourth member of
  *   the union of the fit_, path_ and mom_ fields.
+ *   A model axis (with and without HCG_EXPLAIN_GROUPED): `n_models` = M frozen models of one architecture (0, what a caller
+ *   of the one-model form leaves there, means 1; 1 <= M <= 65535, else HCG_ERR_INVALID_ARG, by a query too).  The weight
+ *   pointers name model 0 of tensors stacked along a leading model axis ([M, 64, F], [M, 64, 64], [M, 64], [M, out_i, in_i],
+ *   [M, out_i]); the launch is dim3(B, perm_count, M) and workgroup (g, p, m) walks permutation p of graph g with model m:
+ *   the model index shifts the weight pointers once, nothing else of the walk changes.  Every output takes a leading model
+ *   axis: out / out_base [M][B][C], the workspace [M][perm_count][row] (workspace_bytes_needed = M times the one-model
+ *   figure), shap_acc [M][row], each model's rows summed p ascending as above.  The permutations are shared by the models.
+ *   Entry [m] is bitwise what a one-model call with model m's weights writes, whatever M and the other models are; a
+ *   refused graph's entries are zero in every model's slice.  HCG_EXPLAIN_MOMENTS takes the mean and the standard deviation
+ *   over the model axis of shap_acc.
  * HCG_EXPLAIN_COALITIONS: the coalition values of ONE frozen model for a batch of graphs (csrc/shapley.hip,
  *   k_coalition_values): the model's output for EVERY subset of each graph's groups, the table every exact quantity of a few
  *   players is a fixed linear form of (Shapley values, Shapley interaction indices, any single what-if).  Players, background,
@@ -234,7 +244,8 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   (HCG_ERR_INVALID_ARG); coal_max_live = the largest L_g must be <= 16 and coal_rows < 2^31 (HCG_ERR_UNSUPPORTED); for a
  *   launch the five shap_ arrays, coal_values, coal_jobs and coal_live_ptr non-NULL.  Shapes, LDS and refusals as
  *   HCG_EXPLAIN_SHAPLEY (184 nodes; a refused graph: its rows zero, HCG_STATUS_SHAPE_LIMIT).  HCG_EXPLAIN_QUERY as above;
- *   also writes lds_bytes.  The coal_ fields follow the shap_ fields in the union's fourth member.
+ *   also writes lds_bytes.  The coal_ fields follow the shap_ fields in the union's fourth member.  ONE model: n_models > 1
+ *   is HCG_ERR_UNSUPPORTED (by a query too), never a silent run of model 0.
  * HCG_EXPLAIN_SUBSETS: the values of a caller's LIST of subsets of each graph's groups, for ONE frozen model and a batch of
  *   graphs (csrc/shapley.hip, k_subset_values): the primitive under deletion / insertion curves and any sampled estimator
  *   over groups, for ANY number of groups per graph (atoms as players: 57 - 184).  Players, background, features and their
@@ -261,6 +272,10 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   launch the five shap_ arrays, coal_values, coal_jobs, sub_bits, sub_word_ptr and sub_member_group non-NULL.  Shapes, LDS
  *   and refusals as HCG_EXPLAIN_SHAPLEY (184 nodes; a refused graph: the rows of its jobs zero, HCG_STATUS_SHAPE_LIMIT).
  *   HCG_EXPLAIN_QUERY as above; also writes lds_bytes.  The sub_ fields follow the coal_ fields in the union's fourth member.
+ *   A model axis: `n_models` = M as in HCG_EXPLAIN_SHAPLEY (0 means 1; 1 <= M <= 65535, else HCG_ERR_INVALID_ARG; weights
+ *   stacked [M, ...], the pointers naming model 0).  The launch is dim3(jobs, M): workgroup (j, m) runs job j with model m.
+ *   coal_values is [M][S][B][C]; slice m is bitwise the one-model call's table for model m's weights; a refused graph's rows
+ *   are zero in every slice.  Jobs, bit words and the member lists are shared by the models.
  * HCG_EXPLAIN_GREEDY: ONE ROUND of the model-driven greedy insertion or deletion order of each graph's groups, for ONE frozen
  *   model and a batch of graphs (csrc/shapley.hip, k_greedy_round): the order every attribution's deletion / insertion curve
  *   is read against, and the top-k sufficient / necessary set.  Players, background, features, their indexing and the shap_
@@ -297,7 +312,8 @@ int hcg_gcn_layer_bwd(const float* dout, const float* out, const float* x, const
  *   workgroups own is zero -- their candidate rows, the owner's row of coal_values, `out` / out_base -- its greedy_order
  *   entries are left alone, HCG_STATUS_SHAPE_LIMIT).  HCG_EXPLAIN_QUERY as above; also writes lds_bytes.  greedy_round and
  *   greedy_flags follow the sub_ fields in the union's fourth member, which they fill; greedy_order and greedy_cand take
- *   the slots of coal_live_ptr and sub_bits, which this mode does not read.
+ *   the slots of coal_live_ptr and sub_bits, which this mode does not read.  ONE model: n_models > 1 is HCG_ERR_UNSUPPORTED
+ *   (by a query too) -- an ensemble's pick needs a reduction over the models inside a round, which this kernel does not have.
  * HCG_EXPLAIN_FIT: GNNExplainer's whole mask optimisation (published torch_geometric 2.3 / 2.4 GNNExplainer, model explanation,
  *   node_mask_type 'attributes', edge_mask_type 'object'; regression, or multiclass classification on raw outputs) for a
  *   batch of graphs in ONE launch: the kernel of
@@ -413,7 +429,7 @@ typedef struct hcg_explain_args {
   const float* dinv;
   float* dew_csr;
   float* emb;                            /* HCG_EXPLAIN_ENSEMBLE from here on: [M, B, 2D], nullable */
-  int32_t n_models;                      /* M (also read by HCG_EXPLAIN_INTEGRATED: 0 means 1) */
+  int32_t n_models;                      /* M (also read by HCG_EXPLAIN_INTEGRATED, _SHAPLEY and _SUBSETS: 0 means 1; _COALITIONS and _GREEDY refuse M > 1) */
   int32_t models_per_group;              /* models one workgroup runs on its graph, 1 .. M */
   const int32_t* perm;                   /* HCG_EXPLAIN_SHAPLEY from here on: [n_perm][N F + E] */
   float* out_base;                       /* [B, C] */
