@@ -1,19 +1,24 @@
-"""The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`, `IntegratedGradients`,
-`EnsembleAttribution`: one graph per workgroup, all through `hcg_explain`).
+"""The host path the frozen-model classes share (`ExplainStep`, `ExplainFit`, `EnsemblePredict`, `ShapleySampling`, `CoalitionValues`,
+`SubsetValues`, `GreedySelection`, `IntegratedGradients`, `EnsembleAttribution` and the ensemble classes of ensemble_shapley.py: one
+graph per workgroup, all through `hcg_explain`).
 
     Frozen           what every class is: `last_path`, the argument block `_args`, the buffer pool `_bufs`, the support check
                      (`_shape_args`, `reason`, `lds_bytes`), the class-index check and `_fill`, which sets what every launch sets
-    FrozenModel      one model: what it must look like, its weights checked for a launch (the ensembles' counterpart,
-                     `FrozenEnsemble`, lives beside `stack_weights` in ensemble.py)
+    FrozenModel      one model: what it must look like, its weights checked for a launch, and `_masked_forward`, the masked
+                     forward every loop path of the Shapley family runs (the ensembles' counterpart, `FrozenEnsemble`, lives
+                     beside `stack_weights` in ensemble.py and holds the model-chunk loop and the moments block)
     Pool             name -> flat tensor, grow-only; a request returns the buffer's front in the shape asked for
     query            clears the WHOLE argument block, fills the shapes and asks the library; a class then sets every member
                      its launch reads, so nothing of an earlier launch (the `fit_` / `path_` / `mom_` / `shap_` members overlay
                      one union) can reach the next one
+    positive         the check of every `*_per_launch` / `*_per_workgroup` / `*_per_job` argument
+    launch_jobs      the jobs of a filled block in launches of `jobs_per_launch` (coalitions, subsets, a greedy round)
     torch_forward    the model's masked forward in plain torch ops: what every loop path runs on CPU tensors
     CUS, LAUNCH_SECONDS   what the launch-size estimates of shapley.py and attribution.py share
 
 The order of a fused call: `_shape_args` (clears and queries; not None: the class's loop path), the class's own argument checks,
 `_bufs.take` / `_bufs.workspace`, `_fill`, the class's own members, the launches.  Private: the classes are the interface.
+What describes a batch's players -- group layout, group lists, permutations, subsets -- is _groups.py.
 """
 from __future__ import annotations
 
@@ -143,6 +148,26 @@ def fill_weights(a, weights, first: int = 0):
             slots[i] = tensors[i].data_ptr() + (4 * first * tensors[i].stride(0) if first else 0) if i < len(tensors) else None
 
 
+def positive(name: str, value) -> Optional[int]:
+    """None for None, else `value` as an int of at least 1 (ValueError otherwise): the check of every `*_per_launch`,
+    `*_per_workgroup` and `*_per_job` argument; the caller supplies its default (`positive(...) or default`)."""
+    if value is None:
+        return None
+    if int(value) < 1:
+        raise ValueError(f"{name} must be at least 1; got {value}")
+    return int(value)
+
+
+def launch_jobs(a, first: int, count: int, per_launch: int, label: str, stream=None):
+    """Run the jobs first .. first + count - 1 of the filled block `a` (`coal_jobs`) in launches of at most `per_launch` on
+    `stream` (None: the current one); `label` names the launch in an error."""
+    lib, addr = _lib.load(), ctypes.addressof(a)
+    stream = _lib.stream_ptr() if stream is None else stream
+    for at in range(first, first + count, per_launch):
+        a.coal_job_first, a.coal_job_count = at, min(per_launch, first + count - at)
+        _lib.check(lib.hcg_explain(addr, stream), label)
+
+
 def front(view) -> Optional[int]:
     """Device address of the pool buffer that `view` (`Pool.take`) is the front of; None for None.  An empty view has no
     address of its own: the library still gets its buffer's, never NULL."""
@@ -222,6 +247,19 @@ class FrozenModel(Frozen):
         w = [c.lin.weight for c in convs], [c.bias for c in convs], [li.weight for li in lins], [li.bias for li in lins]
         check_weights([t for ts in w for t in ts], device, f"{self.NAME}: the model's weights must be contiguous float32 on the batch's device")
         return w
+
+    _masked_step = None             # forward-only `ExplainStep(model, apply_sigmoid=False)`, made on first use
+
+    def _masked_forward(self, batch, node_mask, edge_mask):
+        """The model's output [B, C] for `batch.x * node_mask` and `edge_mask` (mask semantics of `ExplainStep` without
+        sigmoid): what every loop path of the Shapley family runs -- forward-only `ExplainStep` on GPU tensors, `torch_forward`
+        on CPU tensors.  The caller holds `no_grad`; the result is overwritten by the next call on GPU tensors."""
+        if not batch.x.is_cuda:
+            return torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
+        if self._masked_step is None:
+            from .explain import ExplainStep        # (explain.py imports this module)
+            self._masked_step = ExplainStep(self.model, apply_sigmoid=False)
+        return self._masked_step(batch, edge_mask, node_mask).out
 
 
 def torch_forward(model, x, edge_index, batch_vec, B: int, edge_mask):

@@ -349,19 +349,12 @@ class EnsembleAttribution(_Path, FrozenEnsemble):
                for k in ("node_mean", "node_m2", "node_std", "edge_mean", "edge_m2", "edge_std")}
         self._fill(a, 0, batch, x, None, self._bufs.workspace(Ml * ws_one, dev))
         self._fill_path(a, n, cls, dev)
-        q = _lib.ExplainArgs()                          # the moments launches' block
-        q.mode = _lib.HCG_EXPLAIN_MOMENTS
-        q.mom_mean0, q.mom_m20, q.mom_std0, q.mom_len0 = front(mom["node_mean"]), front(mom["node_m2"]), front(mom["node_std"]), N * F
-        q.mom_mean1, q.mom_m21, q.mom_std1, q.mom_len1 = front(mom["edge_mean"]), front(mom["edge_m2"]), front(mom["edge_std"]), E
-        q.mom_total = M
+        q = self._moments_block((mom["node_mean"], mom["node_m2"], mom["node_std"], N * F),
+                                (mom["edge_mean"], mom["edge_m2"], mom["edge_std"], E))
         lib, stream = _lib.load(), _lib.stream_ptr()
-        for m0 in range(0, M, Ml):
-            count = min(Ml, M - m0)
-            row0 = m0 if per_model else 0               # (per_model=False: every chunk reuses the one chunk's rows)
-            _frozen.fill_weights(a, weights, m0)
-            a.n_models = count
-            a.path_node_attr = front(node) + 4 * row0 * N * F
-            a.path_edge_attr = front(edge) + 4 * row0 * E
+        for m0, count, row0 in self._model_chunks(a, weights, Ml, per_model, q):
+            q.mom_values0 = a.path_node_attr = front(node) + 4 * row0 * N * F
+            q.mom_values1 = a.path_edge_attr = front(edge) + 4 * row0 * E
             a.path_out_full, a.path_out_base = front(full) + 4 * m0 * B * C, front(base) + 4 * m0 * B * C
             per = self.default_steps_per_launch(n, B * count) if steps_per_launch is None else min(int(steps_per_launch), n)
             for first in range(0, n, per):
@@ -370,9 +363,6 @@ class EnsembleAttribution(_Path, FrozenEnsemble):
             if self.saliency:
                 node[row0:row0 + count].abs_()
                 edge[row0:row0 + count].abs_()
-            q.mom_values0, q.mom_values1 = a.path_node_attr, a.path_edge_attr
-            q.mom_first, q.mom_count = m0, count
-            _lib.check(lib.hcg_explain(ctypes.addressof(q), stream), "hcg_explain (moments)")
         self.last_path, self.last_class_index = "fused", cls
         return EnsembleAttributionResult(
             mom["node_mean"], mom["node_std"], mom["edge_mean"], mom["edge_std"], full, base,

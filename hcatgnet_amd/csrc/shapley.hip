@@ -285,6 +285,51 @@ __device__ __forceinline__ void s_build(const SLds& L, const XCommon& cm, const 
   __syncthreads();
 }
 
+// Everything off: h1 = 0 and mval = 0 for every edge with an entry.  Opens behind a barrier (the evaluation before is done: h1,
+// mval and t1 are idle), ends behind one.
+__device__ __forceinline__ void s_reset(const SLds& L, int n, int ne, int tid) {
+  for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
+#pragma unroll
+  for (int j = 0; j < X_EPT; ++j)
+    if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
+  __syncthreads();
+}
+
+// One row of k_subset_values, which k_greedy_round evaluates its candidates with: everything off, the live background
+// bgm[bb .. be), the members mem[mb .. me) whose group is set in `bits` in one filtered pass, one evaluation -> the position of
+// the output row in hv.  Opens behind a barrier (or on `bits` written by the thread that reads them: s_reset's barrier stands
+// before the filtered pass), ends behind one.
+__device__ __forceinline__ int s_row_subset(const SLds& L, const XCommon& cm, const XMasked fmt, float (&w)[XD], const float (&rw0)[16],
+                                            const int32_t* bgm, int bb, int be, const int32_t* mem, const int32_t* grp,
+                                            const unsigned* bits, int ng, int mb, int me, int nbase, int n, int ne, int tid) {
+  const int nF = n * cm.F, K = nF + ne;
+  s_reset(L, n, ne, tid);
+  s_apply(L, cm, bgm, bb, be, nbase, nF, K, tid);
+  __syncthreads();                                         // (the staging of the list before has been read)
+  s_apply_subset(L, cm, mem, grp, bits, ng, mb, me, nbase, nF, K, tid);
+  __syncthreads();
+  return s_eval(L, cm, fmt, w, rw0, n, tid);
+}
+
+// The job of a workgroup of the three job kernels, a triple of a.jobs, and its graph's groups; all uniform.
+struct SJob {
+  int g, first, count;                      // the graph, the first mask / row / id of the run, their number
+  int gp, ng;                               // the graph's first group and its number of groups
+};
+
+// false: the triple or the graph's group range is outside the arrays (at most `max_groups` groups) -- nothing to do
+template <class Args>
+__device__ __forceinline__ bool s_job(SJob& j, const Args& a, int max_groups) {
+  const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
+  j.g = __builtin_amdgcn_readfirstlane(job[0]);
+  j.first = __builtin_amdgcn_readfirstlane(job[1]);
+  j.count = __builtin_amdgcn_readfirstlane(job[2]);
+  if (j.g < 0 || j.g >= a.B) return false;
+  j.gp = __builtin_amdgcn_readfirstlane(a.group_ptr[j.g]);
+  j.ng = __builtin_amdgcn_readfirstlane(a.group_ptr[j.g + 1]) - j.gp;
+  return !(j.ng < 0 || j.ng > max_groups || j.gp < 0 || (long long)j.gp + j.ng > a.G);
+}
+
 // GROUPED = false: one feature per step (Args = SArgs).  GROUPED = true: HCG_EXPLAIN_GROUPED (Args = SGArgs) -- the players are
 // the graph's groups, a step switches on every live member of one group and is evaluated once, and the live background is on
 // from the base evaluation on.  The ungrouped instantiation is the kernel as it was before the template.
@@ -459,14 +504,9 @@ __global__ __launch_bounds__(XT) void k_coalition_values(const CArgs a) {
   const SLds L = s_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x;
   const int C = cm.C;
-  const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
-  const int g = __builtin_amdgcn_readfirstlane(job[0]);
-  const int m0 = __builtin_amdgcn_readfirstlane(job[1]);
-  const int mcount = __builtin_amdgcn_readfirstlane(job[2]);
-  if (g < 0 || g >= a.B) return;
-  const int gp = __builtin_amdgcn_readfirstlane(a.group_ptr[g]);
-  const int ng = __builtin_amdgcn_readfirstlane(a.group_ptr[g + 1]) - gp;
-  if (ng < 0 || ng > C_MAX_GROUPS || gp < 0 || (long long)gp + ng > a.G) return;
+  SJob jb;
+  if (!s_job(jb, a, C_MAX_GROUPS)) return;
+  const int g = jb.g, m0 = jb.first, mcount = jb.count, gp = jb.gp, ng = jb.ng;
   // the masks of the run that exist and whose rows lie inside the table
   const long long lp = a.live_ptr[g];
   const long long mlo = max(0ll, max((long long)m0, -lp));
@@ -489,12 +529,7 @@ __global__ __launch_bounds__(XT) void k_coalition_values(const CArgs a) {
 #pragma nounroll
   for (long long mm = mlo; mm < mhi; ++mm) {
     const int m = (int)mm;
-    // everything off (the evaluation before ended behind a barrier: h1, mval and t1 are idle)
-    for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
-#pragma unroll
-    for (int j = 0; j < X_EPT; ++j)
-      if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
-    __syncthreads();
+    s_reset(L, n, ne, tid);
     s_apply(L, cm, a.bg_members, bb, be, nbase, nF, K, tid);
 #pragma nounroll
     for (int k = 0; k < ng; ++k)
@@ -543,14 +578,9 @@ __global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
   const int tid = threadIdx.x;
   const int C = cm.C;
   float* const table = a.table + (size_t)blockIdx.y * (size_t)a.S * (size_t)a.B * C;      // [M][S][B][C]: the model's slice
-  const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
-  const int g = __builtin_amdgcn_readfirstlane(job[0]);
-  const int s0 = __builtin_amdgcn_readfirstlane(job[1]);
-  const int scount = __builtin_amdgcn_readfirstlane(job[2]);
-  if (g < 0 || g >= a.B) return;
-  const int gp = __builtin_amdgcn_readfirstlane(a.group_ptr[g]);
-  const int ng = __builtin_amdgcn_readfirstlane(a.group_ptr[g + 1]) - gp;
-  if (ng < 0 || ng > V_MAX_GROUPS || gp < 0 || (long long)gp + ng > a.G) return;
+  SJob jb;
+  if (!s_job(jb, a, V_MAX_GROUPS)) return;
+  const int g = jb.g, s0 = jb.first, scount = jb.count, gp = jb.gp, ng = jb.ng;
   const int nw = (ng + 31) >> 5;                           // <= 512 = XT: one word per thread
   const int wp = __builtin_amdgcn_readfirstlane(a.word_ptr[g]);
   const int W = __builtin_amdgcn_readfirstlane(a.word_ptr[a.B]);
@@ -571,25 +601,16 @@ __global__ __launch_bounds__(XT) void k_subset_values(const VArgs a) {
   float w[XD];
   float rw0[16];
   s_load_weights(w, rw0, cm, tid);
-  const int nF = n * cm.F, K = nF + ne;
   const int bb = __builtin_amdgcn_readfirstlane(a.bg_ptr[g]), be = __builtin_amdgcn_readfirstlane(a.bg_ptr[g + 1]);
   const int mb = __builtin_amdgcn_readfirstlane(a.member_ptr[gp]), me = __builtin_amdgcn_readfirstlane(a.member_ptr[gp + ng]);
   unsigned* const bits = reinterpret_cast<unsigned*>(L.pj);     // [2 S_CHUNK]: pj and pv lie side by side
 
 #pragma nounroll
   for (long long s = slo; s < shi; ++s) {
-    // the row's words, and everything off (the evaluation before ended behind a barrier: h1, mval, t1 and pj / pv are idle)
+    // the row's words (the evaluation before ended behind a barrier: pj / pv are idle), then the row
     if (tid < nw) bits[tid] = a.bits[(size_t)s * (size_t)W + wp + tid];
-    for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
-#pragma unroll
-    for (int j = 0; j < X_EPT; ++j)
-      if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
-    __syncthreads();
-    s_apply(L, cm, a.bg_members, bb, be, nbase, nF, K, tid);
-    __syncthreads();                                       // (the staging of the list before has been read)
-    s_apply_subset(L, cm, a.members, a.member_group, bits, ng, mb, me, nbase, nF, K, tid);
-    __syncthreads();
-    const int off = s_eval(L, cm, fmt, w, rw0, n, tid);
+    const int off = s_row_subset(L, cm, fmt, w, rw0, a.bg_members, bb, be, a.members, a.member_group, bits, ng, mb, me, nbase,
+                                 n, ne, tid);
     if (tid < C) table[((size_t)s * (size_t)a.B + g) * C + tid] = L.hv[off + tid];
     // (hv is next written behind the barriers of the next evaluation's conv stack)
   }
@@ -638,6 +659,7 @@ __global__ __launch_bounds__(XT) void k_greedy_round(const GArgs a) {
   const SLds L = s_carve(smem, cm.npad, cm.emax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int C = cm.C;
+  // (s_job's decode, written out: through the function this kernel takes a 169th VGPR, which costs it a wave per SIMD)
   const int32_t* const job = a.jobs + 3 * ((size_t)a.first + blockIdx.x);
   const int g = __builtin_amdgcn_readfirstlane(job[0]);
   const int y0 = __builtin_amdgcn_readfirstlane(job[1]);
@@ -673,24 +695,13 @@ __global__ __launch_bounds__(XT) void k_greedy_round(const GArgs a) {
     s_load_weights(w, rw0, cm, tid);
   }
   const XMasked fmt{L.mval};
-  const int nF = n * cm.F, K = nF + ne;
   const int bb = __builtin_amdgcn_readfirstlane(a.bg_ptr[g]), be = __builtin_amdgcn_readfirstlane(a.bg_ptr[g + 1]);
   const int mb = __builtin_amdgcn_readfirstlane(a.member_ptr[gp]), me = __builtin_amdgcn_readfirstlane(a.member_ptr[gp + ng]);
   unsigned* const bits = reinterpret_cast<unsigned*>(L.pj);     // [2 S_CHUNK]: pj and pv lie side by side
 
-  // the row in `bits`: everything off, the live background, the set groups in one filtered pass, one evaluation -- the
-  // sequence of a k_subset_values row.  Opens behind a barrier (bits written, the evaluation before done), ends behind one.
+  // the row in `bits`, as k_subset_values evaluates it
   auto row = [&]() {
-    for (int idx = tid; idx < n * XD; idx += XT) L.h1[(idx >> 6) * XS + (idx & 63)] = 0.f;
-#pragma unroll
-    for (int j = 0; j < X_EPT; ++j)
-      if (tid + j * XT < ne && L.mval[tid + j * XT] > 0.f) L.mval[tid + j * XT] = 0.f;
-    __syncthreads();
-    s_apply(L, cm, a.bg_members, bb, be, nbase, nF, K, tid);
-    __syncthreads();                                       // (the staging of the list before has been read)
-    s_apply_subset(L, cm, a.members, a.member_group, bits, ng, mb, me, nbase, nF, K, tid);
-    __syncthreads();
-    return s_eval(L, cm, fmt, w, rw0, n, tid);
+    return s_row_subset(L, cm, fmt, w, rw0, a.bg_members, bb, be, a.members, a.member_group, bits, ng, mb, me, nbase, n, ne, tid);
   };
   // a word of the state in which every group of the graph is on
   auto full_word = [&](int t) { return t == nw - 1 && (ng & 31) ? (1u << (ng & 31)) - 1u : 0xffffffffu; };
@@ -788,14 +799,45 @@ __global__ __launch_bounds__(256) void k_shapley_reduce(const float* __restrict_
 // there) meaning 1, as HCG_EXPLAIN_INTEGRATED reads it
 inline int s_models(const hcg_explain_args* p) { return p->n_models == 0 ? 1 : p->n_models; }
 
+// ---- what the four launchers share.  Each calls these where it made the check itself: the order of a launcher's checks, and
+// with it the code of every refused block, is what it was (tests/test_host_shapley_launch_codes.py).
+// a pointer of another mode is set (`perm` belongs to HCG_EXPLAIN_SHAPLEY alone)
+inline bool s_foreign(const hcg_explain_args* p, bool takes_perm) {
+  return p->edge_mask || p->node_mask || p->target || p->dout || (!takes_perm && p->perm);
+}
+
+// the shapes these kernels take -> the dynamic LDS of one workgroup, or HCG_ERR_UNSUPPORTED
+inline int s_lds(const hcg_explain_args* p) {
+  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
+  return lds > 160 * 1024 ? HCG_ERR_UNSUPPORTED : (int)lds;
+}
+
+// the group lists of a launch: none may be NULL, an empty one included
+inline bool s_lists_ok(const hcg_explain_args* p) {
+  return p->shap_group_ptr && p->shap_member_ptr && p->shap_members && p->shap_bg_ptr && p->shap_bg_members;
+}
+
+// ... into the kernel's block, whichever it is (SGArgs, CArgs, VArgs, GArgs: the same member names)
+template <class A>
+void s_fill_lists(A& a, const hcg_explain_args* p) {
+  a.group_ptr = p->shap_group_ptr;
+  a.member_ptr = p->shap_member_ptr;
+  a.members = p->shap_members;
+  a.bg_ptr = p->shap_bg_ptr;
+  a.bg_members = p->shap_bg_members;
+  if constexpr (!std::is_same_v<A, SGArgs> && !std::is_same_v<A, CArgs>) a.member_group = p->sub_member_group;
+}
+
 }  // namespace
 
 // hcg_explain, mode HCG_EXPLAIN_SHAPLEY (explain.hip dispatches here)
 int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
-  if (p->edge_mask || p->node_mask || p->target || p->dout) return HCG_ERR_INVALID_ARG;
+  if (s_foreign(p, true)) return HCG_ERR_INVALID_ARG;
   const int M = s_models(p);
   if (M < 1 || M > 65535) return HCG_ERR_INVALID_ARG;
-  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  const int lds = s_lds(p);
+  if (lds < 0) return lds;
   const bool grouped = (p->flags & HCG_EXPLAIN_GROUPED) != 0;
   const long long NF = (long long)p->N * p->F;
   // (every group has a member, so G <= N F + E)
@@ -803,9 +845,7 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   const long long row = grouped ? (long long)p->shap_n_groups : NF + p->E;   // entries of a permutation and of a workspace row
   const int count = p->perm_count > 0 ? p->perm_count : 1;
   if (row >= (1ll << 31) || count > 65535) return HCG_ERR_UNSUPPORTED;
-  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
-  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
-  p->lds_bytes = (int32_t)lds;
+  p->lds_bytes = lds;
   // one row of differences per permutation of this call and model: M times the one-model figure ([M][count][row], packed)
   p->workspace_bytes_needed = (size_t)M * hcg_align_up((size_t)count * (size_t)(row > 0 ? row : 1) * sizeof(float), 256);
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
@@ -814,11 +854,10 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
     return HCG_ERR_INVALID_ARG;
   if (p->B == 0) return HCG_OK;
   if (!x_common_ok(p) || !p->out_base || (row > 0 && (!p->perm || !p->shap_acc))) return HCG_ERR_INVALID_ARG;
-  if (grouped && (!p->shap_group_ptr || !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members))
-    return HCG_ERR_INVALID_ARG;
+  if (grouped && !s_lists_ok(p)) return HCG_ERR_INVALID_ARG;
   if (row > 0 && (!p->workspace || p->workspace_bytes < p->workspace_bytes_needed)) return HCG_ERR_WORKSPACE;
 
-  SGArgs a;
+  SGArgs a{};
   x_fill_common(a.c, p, S_NPAD_MIN);
   a.perm = p->perm;
   a.out = p->out;
@@ -829,11 +868,7 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
   a.row = row;
   a.first = p->perm_first;
   a.cls = p->class_index;
-  a.group_ptr = grouped ? p->shap_group_ptr : nullptr;      // (the union holds these in a grouped call only)
-  a.member_ptr = grouped ? p->shap_member_ptr : nullptr;
-  a.members = grouped ? p->shap_members : nullptr;
-  a.bg_ptr = grouped ? p->shap_bg_ptr : nullptr;
-  a.bg_members = grouped ? p->shap_bg_members : nullptr;
+  if (grouped) s_fill_lists(a, p);                          // (the union holds these in a grouped call only: else NULL)
   const dim3 grid((unsigned)p->B, (unsigned)p->perm_count, (unsigned)M);
   const int rc = grouped ? x_launch<k_shapley_walk<true, SGArgs>>(grid, lds, stream, a)
                          : x_launch<k_shapley_walk<false, SArgs>>(grid, lds, stream, static_cast<const SArgs&>(a));
@@ -849,32 +884,25 @@ int hcg_shapley_launch(hcg_explain_args* p, hipStream_t stream) {
 
 // hcg_explain, mode HCG_EXPLAIN_COALITIONS (explain.hip dispatches here)
 int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream) {
-  if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  if (s_foreign(p, false)) return HCG_ERR_INVALID_ARG;
   if (p->n_models > 1) return HCG_ERR_UNSUPPORTED;          // (the kernel has no model axis: never one model silently)
-  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  const int lds = s_lds(p);
+  if (lds < 0) return lds;
   if (p->coal_max_live > C_MAX_GROUPS || p->coal_rows >= (1ll << 31)) return HCG_ERR_UNSUPPORTED;
-  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
-  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
-  p->lds_bytes = (int32_t)lds;
+  p->lds_bytes = lds;
   p->workspace_bytes_needed = 0;
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (p->coal_max_live < 0 || p->coal_rows < 0 || p->shap_n_groups < 0 || p->coal_job_first < 0 || p->coal_job_count < 0)
     return HCG_ERR_INVALID_ARG;
   if (p->B == 0 || p->coal_job_count == 0) return HCG_OK;
-  if (!x_common_ok(p, false) || !p->coal_values || !p->coal_jobs || !p->coal_live_ptr || !p->shap_group_ptr ||
-      !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members)
-    return HCG_ERR_INVALID_ARG;
+  if (!x_common_ok(p, false) || !p->coal_values || !p->coal_jobs || !p->coal_live_ptr || !s_lists_ok(p)) return HCG_ERR_INVALID_ARG;
 
   CArgs a;
   x_fill_common(a.c, p, S_NPAD_MIN);
   a.table = p->coal_values;
   a.jobs = p->coal_jobs;
   a.live_ptr = reinterpret_cast<const long long*>(p->coal_live_ptr);
-  a.group_ptr = p->shap_group_ptr;
-  a.member_ptr = p->shap_member_ptr;
-  a.members = p->shap_members;
-  a.bg_ptr = p->shap_bg_ptr;
-  a.bg_members = p->shap_bg_members;
+  s_fill_lists(a, p);
   a.rows = p->coal_rows;
   a.G = p->shap_n_groups;
   a.B = p->B;
@@ -884,21 +912,20 @@ int hcg_coalitions_launch(hcg_explain_args* p, hipStream_t stream) {
 
 // hcg_explain, mode HCG_EXPLAIN_SUBSETS (explain.hip dispatches here)
 int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
-  if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  if (s_foreign(p, false)) return HCG_ERR_INVALID_ARG;
   const int M = s_models(p);
   if (M < 1 || M > 65535) return HCG_ERR_INVALID_ARG;
-  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  const int lds = s_lds(p);
+  if (lds < 0) return lds;
   if (p->sub_max_groups > V_MAX_GROUPS || p->coal_rows >= (1ll << 31)) return HCG_ERR_UNSUPPORTED;
-  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
-  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
-  p->lds_bytes = (int32_t)lds;
+  p->lds_bytes = lds;
   p->workspace_bytes_needed = 0;
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (p->sub_max_groups < 0 || p->coal_rows < 0 || p->shap_n_groups < 0 || p->coal_job_first < 0 || p->coal_job_count < 0)
     return HCG_ERR_INVALID_ARG;
   if (p->B == 0 || p->coal_job_count == 0) return HCG_OK;
   if (!x_common_ok(p, false) || !p->coal_values || !p->coal_jobs || !p->sub_bits || !p->sub_word_ptr || !p->sub_member_group ||
-      !p->shap_group_ptr || !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members)
+      !s_lists_ok(p))
     return HCG_ERR_INVALID_ARG;
 
   VArgs a;
@@ -907,12 +934,7 @@ int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
   a.jobs = p->coal_jobs;
   a.bits = p->sub_bits;
   a.word_ptr = p->sub_word_ptr;
-  a.group_ptr = p->shap_group_ptr;
-  a.member_ptr = p->shap_member_ptr;
-  a.members = p->shap_members;
-  a.member_group = p->sub_member_group;
-  a.bg_ptr = p->shap_bg_ptr;
-  a.bg_members = p->shap_bg_members;
+  s_fill_lists(a, p);
   a.S = p->coal_rows;
   a.G = p->shap_n_groups;
   a.B = p->B;
@@ -922,17 +944,16 @@ int hcg_subsets_launch(hcg_explain_args* p, hipStream_t stream) {
 
 // hcg_explain, mode HCG_EXPLAIN_GREEDY (explain.hip dispatches here)
 int hcg_greedy_launch(hcg_explain_args* p, hipStream_t stream) {
-  if (p->edge_mask || p->node_mask || p->target || p->dout || p->perm) return HCG_ERR_INVALID_ARG;
+  if (s_foreign(p, false)) return HCG_ERR_INVALID_ARG;
   // (what is wrong whatever the shapes are, by a query too: the column, the round, the flags)
   if (p->class_index < 0 || p->class_index >= p->C || p->greedy_round < 0 ||
       (p->greedy_flags & ~(HCG_GREEDY_DELETION | HCG_GREEDY_NEGATE)))
     return HCG_ERR_INVALID_ARG;
   if (p->n_models > 1) return HCG_ERR_UNSUPPORTED;          // (the pick would need a reduction over the models inside a round)
-  if (!x_shapes_ok(p) || p->max_nodes > S_MAX_NODES) return HCG_ERR_UNSUPPORTED;
+  const int lds = s_lds(p);
+  if (lds < 0) return lds;
   if (p->sub_max_groups > V_MAX_GROUPS) return HCG_ERR_UNSUPPORTED;
-  const unsigned lds = s_lds_bytes(x_round4(p->max_nodes, S_NPAD_MIN), x_round4(p->max_edges, 4));
-  if (lds > 160 * 1024) return HCG_ERR_UNSUPPORTED;
-  p->lds_bytes = (int32_t)lds;
+  p->lds_bytes = lds;
   p->workspace_bytes_needed = 0;
   if (p->flags & HCG_EXPLAIN_QUERY) return HCG_OK;
   if (p->sub_max_groups < 0 || p->shap_n_groups < 0 || p->shap_n_groups >= (1ll << 31) || p->coal_job_first < 0 ||
@@ -940,7 +961,7 @@ int hcg_greedy_launch(hcg_explain_args* p, hipStream_t stream) {
     return HCG_ERR_INVALID_ARG;
   if (p->B == 0 || p->coal_job_count == 0) return HCG_OK;
   if (!x_common_ok(p) || !p->out_base || !p->coal_values || !p->coal_jobs || !p->greedy_order || !p->greedy_cand ||
-      !p->sub_member_group || !p->shap_group_ptr || !p->shap_member_ptr || !p->shap_members || !p->shap_bg_ptr || !p->shap_bg_members)
+      !p->sub_member_group || !s_lists_ok(p))
     return HCG_ERR_INVALID_ARG;
 
   GArgs a;
@@ -951,12 +972,7 @@ int hcg_greedy_launch(hcg_explain_args* p, hipStream_t stream) {
   a.out = p->out;
   a.out_base = p->out_base;
   a.jobs = p->coal_jobs;
-  a.group_ptr = p->shap_group_ptr;
-  a.member_ptr = p->shap_member_ptr;
-  a.members = p->shap_members;
-  a.member_group = p->sub_member_group;
-  a.bg_ptr = p->shap_bg_ptr;
-  a.bg_members = p->shap_bg_members;
+  s_fill_lists(a, p);
   a.G = p->shap_n_groups;
   a.B = p->B;
   a.first = p->coal_job_first;

@@ -62,7 +62,8 @@ def weight_names(n_conv: int, n_read: int):
 
 class FrozenEnsemble(_frozen.Frozen):
     """M models of one architecture, their weights stacked once into contiguous [M, ...] buffers (`stacked`: a snapshot):
-    what `EnsemblePredict` and `attribution.EnsembleAttribution` share."""
+    what `EnsemblePredict`, `attribution.EnsembleAttribution` and the classes of ensemble_shapley.py share; the last two kinds
+    run the models in chunks (`_model_chunks`) with one moments launch per chunk (`_moments_block`)."""
     WHAT = "models"
 
     def __init__(self, models: Sequence[torch.nn.Module]):
@@ -109,6 +110,34 @@ class FrozenEnsemble(_frozen.Frozen):
         _frozen.check_weights(S.values(), device, f"{self.NAME}: the stacked weights must be on the batch's device "
                               "(construct the ensemble from models on that device)")
         return [[S[n] for n in names] for names in weight_names(self.n_conv, self.R)]
+
+    # ------------------------------------------------------------------ the model axis of the attribution classes
+    def _moments_block(self, *arrays):
+        """The argument block of the moments launches (`HCG_EXPLAIN_MOMENTS`) over one or two per-model arrays
+        [models, length]: `arrays` = (mean, m2, std, length) each, pool views."""
+        q, front = _lib.ExplainArgs(), _frozen.front
+        q.mode = _lib.HCG_EXPLAIN_MOMENTS
+        for k, (mean, m2, std, length) in enumerate(arrays):
+            for name, value in (("mom_mean", front(mean)), ("mom_m2", front(m2)), ("mom_std", front(std)), ("mom_len", length)):
+                setattr(q, f"{name}{k}", value)
+        q.mom_total = len(self.models)
+        return q
+
+    def _model_chunks(self, a, weights, per_launch: int, per_model: bool, q):
+        """The models in chunks of `per_launch`.  Per chunk: the block `a` gets the chunk's weights (`fill_weights` from its
+        first model) and `n_models`; (first model, models, first row) is yielded -- the row of the per-model arrays the
+        chunk writes from: its first model, or 0 when only one chunk's rows exist (`per_model` False); the caller sets the
+        chunk's addresses, `q.mom_values0` (`q.mom_values1`) among them, and enqueues its launches; then the moments launch
+        `q` (`_moments_block`) runs over the chunk."""
+        M = len(self.models)
+        lib, stream = _lib.load(), _lib.stream_ptr()
+        for m0 in range(0, M, per_launch):
+            count = min(per_launch, M - m0)
+            _frozen.fill_weights(a, weights, m0)
+            a.n_models = count
+            yield m0, count, (m0 if per_model else 0)
+            q.mom_first, q.mom_count = m0, count
+            _lib.check(lib.hcg_explain(ctypes.addressof(q), stream), "hcg_explain (moments)")
 
 
 class EnsembleResult(NamedTuple):

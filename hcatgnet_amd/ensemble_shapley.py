@@ -22,11 +22,11 @@ from typing import NamedTuple, Optional, Sequence
 
 import torch
 
-from . import _frozen, _lib
-from .attribution import LAUNCH_BUDGET_BYTES, EnsembleAttribution
+from . import _frozen, _groups, _lib
+from .attribution import LAUNCH_BUDGET_BYTES, EnsembleAttribution  # noqa: F401  (LAUNCH_BUDGET_BYTES: importable from here as before)
 from .ensemble import FrozenEnsemble
-from .shapley import CoalitionValues, ShapleySampling, _players
-from .subsets import MAX_SUBSET_GROUPS, AttributionCurves, SubsetValues, _member_group, _pack
+from .shapley import CoalitionValues, ShapleySampling
+from .subsets import MAX_SUBSET_GROUPS, AttributionCurves, SubsetValues
 
 
 class EnsembleShapleyResult(NamedTuple):
@@ -85,16 +85,6 @@ def _models_per_launch(value, M: int, workspace_bytes: int, entries: int) -> int
     return EnsembleAttribution.default_models_per_launch(M, workspace_bytes, entries)
 
 
-def _moments_block(mean, m2, std, length: int, M: int):
-    """The argument block of the moments launches over a [models, length] array"""
-    q = _lib.ExplainArgs()
-    q.mode = _lib.HCG_EXPLAIN_MOMENTS
-    q.mom_mean0, q.mom_m20, q.mom_std0, q.mom_len0 = _frozen.front(mean), _frozen.front(m2), _frozen.front(std), length
-    q.mom_len1 = 0
-    q.mom_total = M
-    return q
-
-
 class EnsembleShapley(FrozenEnsemble):
     """Shapley value sampling of M frozen models of one architecture for a whole batch of graphs: every (graph, permutation,
     model) triple is one workgroup, and the mean and the standard deviation over the models are taken on the device.
@@ -143,11 +133,10 @@ class EnsembleShapley(FrozenEnsemble):
     def __call__(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0, node_group=None,
                  edge_group=None, group_permutations=None, per_model: bool = False, models_per_launch: Optional[int] = None,
                  samples_per_launch: Optional[int] = None):
-        if models_per_launch is not None and int(models_per_launch) < 1:
-            raise ValueError(f"models_per_launch must be at least 1; got {models_per_launch}")
+        _frozen.positive("models_per_launch", models_per_launch)
         if samples_per_launch is not None and not 1 <= int(samples_per_launch) <= 65535:
             raise ValueError(f"samples_per_launch must lie in 1 .. 65535; got {samples_per_launch}")
-        pl, given = _players(batch, permutations, node_group, edge_group, group_permutations)
+        pl, given = _groups._players(batch, permutations, node_group, edge_group, group_permutations)
         a = self._args
         if self._shape_args(a, batch, perm_count=1, **pl.query) is not None:
             return self._loop(pl, pl.permutations(n_samples, given, generator), class_index, per_model)
@@ -174,22 +163,15 @@ class EnsembleShapley(FrozenEnsemble):
         self._fill(a, pl.flags, batch, x, None, self._bufs.workspace(Ml * ws_one, dev))
         a.perm, a.n_perm, a.class_index = _lib.ptr(perm), P, cls
         pl.fill(a)
-        q = _moments_block(mean, m2, std, row, M)
+        q = self._moments_block((mean, m2, std, row))
         lib, stream = _lib.load(), _lib.stream_ptr()
-        for m0 in range(0, M, Ml):
-            count = min(Ml, M - m0)
-            row0 = m0 if per_model else 0               # (per_model=False: every chunk reuses the one chunk's rows)
-            _frozen.fill_weights(a, weights, m0)
-            a.n_models = count
+        for m0, count, row0 in self._model_chunks(a, weights, Ml, per_model, q):
             a.out, a.out_base = front(out) + 4 * m0 * B * C, front(base) + 4 * m0 * B * C
-            a.shap_acc = front(acc) + 4 * row0 * row
+            q.mom_values0 = a.shap_acc = front(acc) + 4 * row0 * row
             spl = samples(B * count)
             for first in range(0, P, spl):
                 a.perm_first, a.perm_count = first, min(spl, P - first)
                 _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), pl.label + " (ensemble)")
-            q.mom_values0 = a.shap_acc
-            q.mom_first, q.mom_count = m0, count
-            _lib.check(lib.hcg_explain(ctypes.addressof(q), stream), "hcg_explain (moments)")
         self.last_path = "fused"
         return self._result(pl, mean, std, out, base, acc if per_model else None)
 
@@ -210,7 +192,7 @@ class EnsembleShapley(FrozenEnsemble):
              edge_group=None, group_permutations=None, per_model: bool = False):
         """`ShapleySampling(model_k).loop` per model on the models' current weights with one set of permutations, the moments
         with torch ops, whatever `reason(batch)` says."""
-        pl, given = _players(batch, permutations, node_group, edge_group, group_permutations)
+        pl, given = _groups._players(batch, permutations, node_group, edge_group, group_permutations)
         return self._loop(pl, pl.permutations(n_samples, given, generator), class_index, per_model)
 
     def _loop(self, pl, perm, class_index, per_model):
@@ -233,8 +215,8 @@ class EnsembleSubsetValues(FrozenEnsemble):
         #                      values [M, S, B, C] | None)
 
     Arguments, checks and errors are `SubsetValues`'; the group layout, the job list and the bit words are built ONCE per
-    call, with that class's own helpers, and shared by the models.  `values[m]`, `out_full[m]` and `out_base[m]` are bit for
-    bit what `SubsetValues(models[m])` returns, and everything is bitwise independent of `models_per_launch`,
+    call (`_groups._SubsetCall`, as that class builds them), and shared by the models.  `values[m]`, `out_full[m]` and
+    `out_base[m]` are bit for bit what `SubsetValues(models[m])` returns, and everything is bitwise independent of `models_per_launch`,
     `rows_per_workgroup`, `jobs_per_launch`, of the other models and of the rest of the batch.  `mean` / `std` are the
     moments over the models of the whole [S + 2, B, C] table (Welford in float32, population std, one `HCG_EXPLAIN_MOMENTS`
     launch per chunk of models): `mean` is the value of every subset under the ensemble's mean prediction.
@@ -253,7 +235,7 @@ class EnsembleSubsetValues(FrozenEnsemble):
 
     def __init__(self, models: Sequence[torch.nn.Module]):
         super().__init__(models)
-        self._singles = [SubsetValues(m) for m in self.models]             # the loop path's workers, and the shared helpers
+        self._singles = [SubsetValues(m) for m in self.models]             # the loop path's workers
 
     def _shape_args(self, a, batch, **extra) -> Optional[str]:
         return super()._shape_args(a, batch, n_models=1, **extra)
@@ -262,9 +244,8 @@ class EnsembleSubsetValues(FrozenEnsemble):
                  rows_per_workgroup: Optional[int] = None, per_model: bool = False,
                  models_per_launch: Optional[int] = None) -> EnsembleSubsetResult:
         why = self._shape_args(self._args, batch)
-        one = self._singles[0]
-        gr, counts = one._layout(batch, node_group, edge_group)
-        rp = one._check(batch, gr, subsets, rows_per_graph)
+        gr, counts = _groups.subset_layout(batch, node_group, edge_group)
+        rp = _groups.check_subsets(batch, gr, subsets, rows_per_graph, self.C)
         mean, std, full, base, values = self._tables(batch, gr, counts, subsets, rp, rows_per_workgroup, per_model,
                                                      models_per_launch, why)
         S = int(subsets.shape[0])
@@ -272,9 +253,8 @@ class EnsembleSubsetValues(FrozenEnsemble):
 
     def loop(self, batch, subsets, node_group=None, edge_group=None, rows_per_graph=None, per_model: bool = False):
         """`SubsetValues(model_k).loop` per model, the moments with torch ops, whatever `reason(batch)` says."""
-        one = self._singles[0]
-        gr, counts = one._layout(batch, node_group, edge_group)
-        rp = one._check(batch, gr, subsets, rows_per_graph)
+        gr, counts = _groups.subset_layout(batch, node_group, edge_group)
+        rp = _groups.check_subsets(batch, gr, subsets, rows_per_graph, self.C)
         mean, std, full, base, values = self._loop(batch, gr, subsets, rp, per_model)
         S = int(subsets.shape[0])
         return EnsembleSubsetResult(mean[:S], std[:S], gr.group_ptr, full, base, None if values is None else values[:, :S])
@@ -288,24 +268,20 @@ class EnsembleSubsetValues(FrozenEnsemble):
     def _tables(self, batch, gr, counts, subsets, rp, rows_per_workgroup, per_model, models_per_launch, why):
         """-> (mean [S + 2, B, C], std [S + 2, B, C], out_full [M, B, C], out_base [M, B, C], the models' tables
         [M, S + 2, B, C] or None): the rows of `subsets`, then everything on, then the background only"""
-        if rows_per_workgroup is not None and int(rows_per_workgroup) < 1:
-            raise ValueError(f"rows_per_workgroup must be at least 1; got {rows_per_workgroup}")
-        if models_per_launch is not None and int(models_per_launch) < 1:
-            raise ValueError(f"models_per_launch must be at least 1; got {models_per_launch}")
-        if self.jobs_per_launch is not None and int(self.jobs_per_launch) < 1:
-            raise ValueError(f"jobs_per_launch must be at least 1; got {self.jobs_per_launch}")
+        rpw = _frozen.positive("rows_per_workgroup", rows_per_workgroup)
+        _frozen.positive("models_per_launch", models_per_launch)
+        jpl = _frozen.positive("jobs_per_launch", self.jobs_per_launch)
         if why is not None or gr.max_groups > MAX_SUBSET_GROUPS:
             return self._loop(batch, gr, subsets, rp, per_model)
         a = self._args
         x = _frozen.batch_x(batch, subsets)
         M, B, C, dev = len(self.models), a.B, a.C, x.device
-        S, G = int(subsets.shape[0]), gr.G
-        S2 = S + 2
+        S = int(subsets.shape[0])
+        rpw = rpw or CoalitionValues.default_subsets_per_workgroup(S * B * M)
+        call = _groups._SubsetCall(B, gr, counts, subsets, rp, rpw)
+        S2, J = call.S2, call.J
         length = S2 * B * C
-        rpw = CoalitionValues.default_subsets_per_workgroup(S * B * M) if rows_per_workgroup is None else int(rows_per_workgroup)
         Ml = _models_per_launch(models_per_launch, M, 0, length)
-        jobs = SubsetValues._jobs(B, S, rp, rpw)
-        J = int(jobs.shape[0])
         take, front = self._bufs.take, _frozen.front
         tables = take("tables", (M if per_model else Ml, S2, B, C), dev)
         full, base = take("full", (M, B, C), dev), take("base", (M, B, C), dev)
@@ -315,40 +291,16 @@ class EnsembleSubsetValues(FrozenEnsemble):
         self.last_path = "fused"
         if J == 0:                                                          # (no graph: nothing to launch)
             return mean, std, full, base, tables if per_model else None
-        rows = torch.cat([subsets, torch.ones(1, G, dtype=torch.bool, device=dev), torch.zeros(1, G, dtype=torch.bool, device=dev)])
-        W = sum((c + 31) // 32 for c in counts)
-        bits, word_ptr = _pack(rows, gr.group_ptr, W)
-        L = int(gr.members.numel())
-        member_group = _member_group(gr)
-        jobs_t = jobs.to(dev)
-        group_ptr32 = gr.group_ptr.to(torch.int32)
-        _frozen.query(a, self.KERNEL, self._shape(), batch, coal_rows=S2, sub_max_groups=gr.max_groups, n_models=1)
+        _frozen.query(a, self.KERNEL, self._shape(), batch, n_models=1, **call.query)
         weights = self._weights(dev)
         self._fill(a, 0, batch, x, None)
-        p = _lib.ptr
-        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr32), p(gr.member_ptr), p(gr.bg_ptr)
-        # (a batch without features or without groups: arrays of length 0 are never read, but must not be NULL)
-        a.shap_members = a.shap_bg_members = p(gr.members) if L else p(group_ptr32)
-        a.sub_member_group = p(member_group) if L else p(group_ptr32)
-        a.shap_n_groups = G
-        a.sub_bits, a.sub_word_ptr = (p(bits) if W else p(word_ptr)), p(word_ptr)
-        a.coal_jobs, a.coal_rows, a.sub_max_groups = p(jobs_t), S2, gr.max_groups
-        q = _moments_block(mean, m2, std, length, M)
-        lib, stream = _lib.load(), _lib.stream_ptr()
-        for m0 in range(0, M, Ml):
-            count = min(Ml, M - m0)
-            row0 = m0 if per_model else 0               # (per_model=False: every chunk reuses the one chunk's tables)
-            _frozen.fill_weights(a, weights, m0)
-            a.n_models = count
-            a.coal_values = front(tables) + 4 * row0 * length
-            jpl = max(1, CoalitionValues.default_jobs_per_launch(rpw) // count) if self.jobs_per_launch is None \
-                else int(self.jobs_per_launch)
-            for first in range(0, J, jpl):
-                a.coal_job_first, a.coal_job_count = first, min(jpl, J - first)
-                _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (subsets, ensemble)")
-            q.mom_values0 = a.coal_values
-            q.mom_first, q.mom_count = m0, count
-            _lib.check(lib.hcg_explain(ctypes.addressof(q), stream), "hcg_explain (moments)")
+        call.fill(a)
+        q = self._moments_block((mean, m2, std, length))
+        for m0, count, row0 in self._model_chunks(a, weights, Ml, per_model, q):
+            q.mom_values0 = a.coal_values = front(tables) + 4 * row0 * length
+            _frozen.launch_jobs(a, 0, J, jpl or max(1, CoalitionValues.default_jobs_per_launch(rpw) // count),
+                                "hcg_explain (subsets, ensemble)")
+            # (out_full / out_base of the chunk: they read its tables, as the moments launch behind them does)
             chunk = tables[row0:row0 + count]
             full[m0:m0 + count].copy_(chunk[:, S])
             base[m0:m0 + count].copy_(chunk[:, S + 1])
@@ -391,9 +343,9 @@ class EnsembleCurves:
         why = ev._shape_args(ev._args, batch)
         cls = ev._class(class_index)
         fr = AttributionCurves._fractions(fractions)
-        gr, counts = ev._singles[0]._layout(batch, node_group, edge_group)
+        gr, counts = _groups.subset_layout(batch, node_group, edge_group)
         plan = AttributionCurves._plan(gr, counts, order, fr, batch.x.device)
-        rp = ev._singles[0]._check(batch, gr, plan.rows, torch.tensor(plan.rows_per_graph, dtype=torch.int64))
+        rp = _groups.check_subsets(batch, gr, plan.rows, torch.tensor(plan.rows_per_graph, dtype=torch.int64), ev.C)
         mean, std, _, _, _ = ev._tables(batch, gr, counts, plan.rows, rp, rows_per_workgroup, False, models_per_launch, why)
         insertion, deletion = AttributionCurves._gather(mean, plan)
         ins_std, del_std = AttributionCurves._gather(std, plan)

@@ -14,14 +14,13 @@ share of this round's candidates with the very sequence `k_subset_values` runs f
 """
 from __future__ import annotations
 
-import ctypes
 from typing import NamedTuple, Optional
 
 import torch
 
-from . import _frozen, _lib
-from .shapley import SUBSETS_PER_WORKGROUP, _group_layout
-from .subsets import MAX_SUBSET_GROUPS, SubsetValues, _group_graph, _member_group
+from . import _frozen, _groups, _lib
+from .shapley import SUBSETS_PER_WORKGROUP
+from .subsets import MAX_SUBSET_GROUPS, SubsetValues
 
 MODES = ("insertion", "deletion")
 
@@ -133,8 +132,7 @@ class GreedySelection(_frozen.FrozenModel):
             raise ValueError(f"direction must be +1 or -1; got {direction!r}")
         if steps is not None and int(steps) < 1:
             raise ValueError(f"steps must be at least 1 (or None: every live group); got {steps}")
-        if ids_per_job is not None and int(ids_per_job) < 1:
-            raise ValueError(f"ids_per_job must be at least 1; got {ids_per_job}")
+        _frozen.positive("ids_per_job", ids_per_job)
         deletion = mode == "deletion"
         return cls, deletion, float(-int(direction) if deletion else int(direction)), None if steps is None else int(steps)
 
@@ -142,10 +140,10 @@ class GreedySelection(_frozen.FrozenModel):
     def _layout(batch, node_group, edge_group, steps):
         """-> (the group layout, the graph of every group [G], per-graph counts, live counts and rounds on the host); one
         host read beside `_group_layout`'s"""
-        B, dev = int(batch.num_graphs), batch.x.device
-        gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
-        ggraph = _group_graph(gr.count, gr.G)
-        nlive = torch.zeros(B, dtype=torch.int64, device=dev).index_add_(0, ggraph, gr.live_group.to(torch.int64))
+        B = int(batch.num_graphs)
+        gr = _groups._group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
+        ggraph = _groups._group_graph(gr.count, gr.G)
+        nlive = _groups._flag_counts(ggraph, B, gr.live_group)
         counts, lives = torch.stack([gr.count, nlive]).tolist() if B > 0 else ([], [])
         rounds = [c if steps is None else min(steps, c) for c in lives]
         return gr, ggraph, counts, lives, rounds
@@ -160,10 +158,7 @@ class GreedySelection(_frozen.FrozenModel):
         if G > 0:
             lv = torch.tensor(lives, dtype=torch.int64, device=dev)
             dead = ~gr.live_group
-            d = dead.to(torch.int64)
-            dptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-            dptr[1:] = torch.zeros(B, dtype=torch.int64, device=dev).index_add_(0, ggraph, d).cumsum(0)
-            rank = d.cumsum(0) - d - dptr[ggraph]                           # a dead group's index among its graph's dead groups
+            rank = _groups._flag_ranks(ggraph, B, dead).rank                # a dead group's index among its graph's dead groups
             sel = dead & torch.tensor(full, dtype=torch.bool, device=dev)[ggraph]
             # (a scatter with a spare slot for the groups that are not appended: a boolean index would read their number)
             at = torch.where(sel, gr.group_ptr[ggraph] + lv[ggraph] + rank, torch.full_like(rank, G))
@@ -197,27 +192,22 @@ class GreedySelection(_frozen.FrozenModel):
         values.zero_()
         self.last_path, self.launches = "fused", len(lptr) - 1
         if B > 0:
-            L = int(gr.members.numel())
-            member_group = _member_group(gr, ggraph)
+            member_group = _groups._member_group(gr, ggraph)
             jobs_t = jobs.to(dev)
-            group_ptr32 = gr.group_ptr.to(torch.int32)
             _frozen.query(a, self.KERNEL, self._shape(), batch, sub_max_groups=gr.max_groups)
             self._fill(a, 0, batch, x, self._weights(dev))
             p = _lib.ptr
-            a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr32), p(gr.member_ptr), p(gr.bg_ptr)
-            # (a batch without features or without groups: arrays of length 0 are never read, but must not be NULL)
-            a.shap_members = a.shap_bg_members = p(gr.members) if L else p(group_ptr32)
-            a.sub_member_group = p(member_group) if L else p(group_ptr32)
-            a.shap_n_groups, a.sub_max_groups = G, gr.max_groups
+            keep = _groups.fill_lists(a, gr, member_group)                  # noqa: F841  (alive until the launches are enqueued)
+            a.sub_max_groups = gr.max_groups
             a.coal_values, a.coal_jobs = _frozen.front(values), p(jobs_t)
             a.greedy_order, a.greedy_cand = _frozen.front(order), _frozen.front(cand)
             a.out, a.out_base = p(out[0]), p(out[1])
             a.class_index = cls
             a.greedy_flags = (_lib.HCG_GREEDY_DELETION if deletion else 0) | (_lib.HCG_GREEDY_NEGATE if sgn < 0 else 0)
-            lib, stream = _lib.load(), _lib.stream_ptr()
-            for k in range(self.launches):
-                a.greedy_round, a.coal_job_first, a.coal_job_count = k, lptr[k], lptr[k + 1] - lptr[k]
-                _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (greedy)")
+            stream = _lib.stream_ptr()
+            for k in range(self.launches):                                  # one launch per round: the round's whole job range
+                a.greedy_round, n = k, lptr[k + 1] - lptr[k]
+                _frozen.launch_jobs(a, lptr[k], n, max(n, 1), "hcg_explain (greedy)", stream)
         return self._finish(gr, ggraph, counts, lives, rounds, deletion, order.clone(), values.clone(), out[0].clone(), out[1].clone())
 
     def loop(self, batch, node_group=None, edge_group=None, class_index: int = 0, mode: str = "insertion", direction: int = 1,
@@ -236,16 +226,11 @@ class GreedySelection(_frozen.FrozenModel):
         picked = torch.zeros(G, dtype=torch.bool, device=dev)
         y = torch.arange(G, device=dev) - gr.group_ptr[ggraph]              # the group's local id
         R = torch.tensor(rounds, dtype=torch.int64, device=dev)
-        live = gr.live_group.to(torch.int64)
-        lptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
         out_full = out_base = None
         for k in range(max(rounds, default=0) + 1):
             # the candidates of round k and their index among their graph's candidates = their row of the table
             cand = gr.live_group & ~picked & (R[ggraph] > k) if G > 0 else picked
-            ci = cand.to(torch.int64)
-            if B > 0:
-                lptr[1:] = torch.zeros(B, dtype=torch.int64, device=dev).index_add_(0, ggraph, ci).cumsum(0)
-            rank = ci.cumsum(0) - ci - lptr[ggraph]
+            rank = _groups._flag_ranks(ggraph, B, cand).rank
             rp = [lv - k if k < r else 0 for lv, r in zip(lives, rounds)]
             S = max(rp, default=0)
             if S == 0 and out_full is not None:

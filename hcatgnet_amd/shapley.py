@@ -32,58 +32,13 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _frozen, _lib
+from . import _frozen, _groups, _lib
 from ._frozen import CUS, LAUNCH_SECONDS  # noqa: F401  (their home; importable from here as before)
-from .explain import ExplainStep
+from ._groups import (GROUPED_WORKGROUPS_PER_CU, MAX_WORKGROUPS_PER_CU, GroupedShapleyResult, ShapleyResult,  # noqa: F401  (as before)
+                      _counts, _draw_segments, _group_layout, _layout, _players)
 
 WORKSPACE_CAP_BYTES = 256 << 20    # the per-permutation rows of one launch
 EVAL_SECONDS = 60e-6               # one evaluation at the shape limits: an estimate (default_samples_per_launch)
-MAX_WORKGROUPS_PER_CU = 4
-GROUPED_WORKGROUPS_PER_CU = 64     # a grouped walk is short (its steps are the groups): more of them queue on a CU per launch
-
-
-class ShapleyResult(NamedTuple):
-    node_attr: torch.Tensor      # [N, F]
-    edge_attr: torch.Tensor      # [E], the batch's edge order
-    out_full: torch.Tensor       # [B, C] the model's output with every feature on (= the plain forward)
-    out_base: torch.Tensor       # [B, C] with every feature off
-
-
-class GroupedShapleyResult(NamedTuple):
-    group_attr: torch.Tensor     # [G] graph g's groups at group_ptr[g] .. group_ptr[g + 1] - 1
-    group_ptr: torch.Tensor      # [B + 1] int64
-    node_attr: torch.Tensor      # [N, F] every member carries its group's value, the background 0 (a gather of group_attr)
-    edge_attr: torch.Tensor      # [E]
-    out_full: torch.Tensor       # [B, C] the model's output with everything on (= the plain forward)
-    out_base: torch.Tensor       # [B, C] with the background only
-
-
-def _layout(batch, F: int):
-    """-> (nodes per graph, edges per graph, graph_ptr, edge_ptr, segment start), int64 [B] / [B + 1] on the batch's
-    device.  Graph g's segment of a permutation row starts at graph_ptr[g] * F + edge_ptr[g]."""
-    B = int(batch.num_graphs)
-    n = torch.bincount(batch.batch, minlength=B)
-    e = torch.bincount(batch.batch[batch.edge_index[1]], minlength=B)
-    gptr = torch.zeros(B + 1, dtype=torch.int64, device=n.device)
-    eptr = torch.zeros(B + 1, dtype=torch.int64, device=n.device)
-    gptr[1:] = n.cumsum(0)
-    eptr[1:] = e.cumsum(0)
-    return n, e, gptr, eptr, gptr[:-1] * F + eptr[:-1]
-
-
-def _draw_segments(count, start, total: int, n_samples: int, generator, dev) -> torch.Tensor:
-    """int32 [n_samples, total]: in every row, segment g (start[g], length count[g]; the segments tile the row in order) is
-    a uniformly random permutation of 0 .. count[g] - 1: the argsort of (segment id, key), one float64 key per entry and
-    one `torch.rand` per row, on the generator's device (None: the default generator of `dev`)."""
-    gid = torch.repeat_interleave(torch.arange(count.numel(), device=dev), count)
-    first = start[gid]
-    gdev = generator.device if generator is not None else dev
-    out = torch.empty(int(n_samples), total, dtype=torch.int32, device=dev)
-    for p in range(int(n_samples)):
-        key = torch.rand(total, generator=generator, device=gdev, dtype=torch.float64).to(dev)
-        order = torch.argsort(gid.to(torch.float64) + key)
-        out[p] = (order - first).to(torch.int32)
-    return out
 
 
 def draw_permutations(batch, F: int, n_samples: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -93,76 +48,6 @@ def draw_permutations(batch, F: int, n_samples: int, generator: Optional[torch.G
     n, e, _, _, seg = _layout(batch, F)
     return _draw_segments(n * F + e, seg, int(batch.batch.numel()) * F + int(batch.edge_index.shape[1]), n_samples, generator,
                           batch.x.device)
-
-
-class _Groups(NamedTuple):
-    """The group layout of one call (`_group_layout`); every tensor on the batch's device."""
-    G: int                       # groups of the batch
-    max_groups: int              # the largest G_g
-    count: torch.Tensor          # [B] int64 G_g
-    group_ptr: torch.Tensor      # [B + 1] int64
-    slot: torch.Tensor           # [N * F + E] int64: the feature's global group (group_ptr[graph] + id), G for the background
-    live_group: torch.Tensor     # [G] bool: the group has a live member
-    member_ptr: torch.Tensor     # [G + 1] int32 into `members`
-    bg_ptr: torch.Tensor         # [B + 1] int32 into `members`
-    members: torch.Tensor        # [N * F + E] int32 local feature indices: the groups' live members, group by group,
-    #                              then the graphs' live background, then the dead features
-
-
-def _group_layout(batch, F: int, node_group, edge_group) -> _Groups:
-    """Check `node_group` / `edge_group` and build the lists the kernel reads, with torch ops on the batch's device: one
-    stable sort of all features by (group | graph of the background | dead) -- features are numbered graph by graph, node
-    entries before edges, so equal keys stay in ascending local index -- and ONE read of three scalars (G, the largest G_g,
-    whether the ids are valid) beside what `_layout` costs."""
-    x, ei = batch.x, batch.edge_index
-    N, E, B, dev = int(x.shape[0]), int(ei.shape[1]), int(batch.num_graphs), x.device
-
-    def ids_of(t, name, shapes):
-        if t is None:
-            return None
-        if not torch.is_tensor(t) or t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64) or tuple(t.shape) not in shapes:
-            raise ValueError(f"{name} must be an integer tensor of shape {' or '.join(str(list(q)) for q in shapes)}; got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, the batch on {dev}")
-        return t.to(torch.int64)
-    ng = ids_of(node_group, "node_group", ((N,), (N, F)))
-    eg = ids_of(edge_group, "edge_group", ((E,),))
-    if ng is None and eg is None:
-        raise ValueError("give node_group, edge_group or both")
-    ng = torch.full((N * F,), -1, dtype=torch.int64, device=dev) if ng is None else \
-        (ng.unsqueeze(1).expand(N, F) if ng.dim() == 1 else ng).reshape(-1)
-    eg = torch.full((E,), -1, dtype=torch.int64, device=dev) if eg is None else eg
-    n, e, gptr, eptr, _ = _layout(batch, F)
-    src, dst = ei[0], ei[1]
-    egraph = batch.batch[dst]
-    ids = torch.cat([ng, eg])
-    graph = torch.cat([batch.batch.repeat_interleave(F), egraph])
-    count = torch.zeros(B, dtype=torch.int64, device=dev).scatter_reduce(0, graph, ids + 1, reduce="amax", include_self=True)
-    group_ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-    group_ptr[1:] = count.cumsum(0)
-    grouped = ids >= 0
-    # (every group has a member, so valid ids have G <= N F + E: the used-slot table needs no size from the device, and a
-    # slot beyond it -- ids with a gap -- lands on the spare entry and leaves the count short)
-    used = torch.zeros(N * F + E + 1, dtype=torch.int64, device=dev)
-    at = group_ptr[graph] + ids
-    used[torch.where(grouped & (at < N * F + E), at, N * F + E)] = 1
-    bad = (used[:-1].sum() != group_ptr[-1]) | (ids < -1).any()
-    G, max_groups, bad = torch.stack([group_ptr[-1], count.max() if B > 0 else group_ptr[-1], bad.to(torch.int64)]).tolist()
-    if bad:
-        raise ValueError("the group ids of a graph, over node_group and edge_group, must be exactly 0 .. G_g - 1, each used "
-                         "at least once, and -1 for the background")
-    slot = torch.where(grouped, group_ptr[graph] + ids, G)
-    local = torch.cat([((torch.arange(N, device=dev) - gptr[batch.batch]) * F).repeat_interleave(F) + torch.arange(F, device=dev).repeat(N),
-                       n[egraph] * F + torch.arange(E, device=dev) - eptr[egraph]])
-    live = torch.cat([(x != 0).reshape(-1), src != dst])
-    key = torch.where(live, torch.where(grouped, slot, G + graph), G + B)
-    order = torch.sort(key, stable=True).indices
-    ptr = torch.zeros(G + B + 2, dtype=torch.int64, device=dev)
-    ptr[1:] = torch.bincount(key, minlength=G + B + 1).cumsum(0)
-    live_group = ptr[1:G + 1] > ptr[:G]
-    return _Groups(int(G), int(max_groups), count, group_ptr, slot, live_group, ptr[:G + 1].to(torch.int32).contiguous(),
-                   ptr[G:G + B + 1].to(torch.int32).contiguous(), local[order].to(torch.int32).contiguous())
 
 
 def atom_groups(batch) -> torch.Tensor:
@@ -220,126 +105,6 @@ def all_group_permutations(batch, node_group=None, edge_group=None) -> torch.Ten
     return rows.repeat(1, gr.count.numel()).to(batch.x.device).contiguous()
 
 
-class _Walk(NamedTuple):
-    """What the loop path needs of the players (`_Players.walk`); every tensor on the batch's device."""
-    count: torch.Tensor          # [B] int64 players of every graph
-    start: torch.Tensor          # [B] int64 where graph g's segment of a permutation row starts
-    steps: int                   # the largest count
-    place: object                # (graphs [A], their local players [A]) -> the players' indices in the accumulator
-    owner: torch.Tensor          # [N * F + E] int64: the player that switches the feature on, `row` for one that is always on
-    live: torch.Tensor           # [row] bool: the player can change the output
-
-
-class _Players:
-    """The players of one call: the features themselves (`_Features`) or groups of them (`_GroupPlayers`).  `row` players in
-    the batch: the width of a permutation row and of the accumulator."""
-    arg = width = label = ""     # the permutation argument, its width in a message, the launch's label in an error
-    flags = 0                    # of the launch
-    per_cu = MAX_WORKGROUPS_PER_CU
-    query: dict = {}             # what the shape query takes beside the permutation count
-
-    def __init__(self, batch):
-        self.batch = batch
-        (self.N, self.F), self.E, self.B = batch.x.shape, int(batch.edge_index.shape[1]), int(batch.num_graphs)
-
-    def permutations(self, n_samples, given, generator) -> torch.Tensor:
-        """`given`, checked, or `n_samples` rows drawn from `generator`"""
-        dev = self.batch.x.device
-        if given is None:
-            if int(n_samples) < 1:
-                raise ValueError(f"n_samples must be at least 1; got {n_samples}")
-            return _draw_segments(*self.segments(), self.row, n_samples, generator, dev)
-        t = given
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != self.row:
-            raise ValueError(f"{self.arg} must be an int32 tensor of shape [P >= 1, {self.width} = {self.row}]; got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != dev:
-            raise ValueError(f"{self.arg} are on {t.device}, the batch on {dev}")
-        return t.contiguous()
-
-
-class _Features(_Players):
-    arg, width, label = "permutations", "N * F + E", "hcg_explain (shapley)"
-
-    def __init__(self, batch):
-        super().__init__(batch)
-        self.row = self.N * self.F + self.E
-
-    def segments(self):
-        n, e, _, _, seg = _layout(self.batch, self.F)
-        return n * self.F + e, seg
-
-    def max_steps(self, a) -> int:
-        return a.max_nodes * self.F + a.max_edges
-
-    def fill(self, a):
-        pass
-
-    def walk(self) -> _Walk:
-        N, F, x, ei = self.N, self.F, self.batch.x, self.batch.edge_index
-        n, e, gptr, eptr, seg = _layout(self.batch, F)
-        nF, K = n * F, n * F + e
-
-        def place(act, j):       # a node entry before the batch's edges, as `ShapleyResult` splits the accumulator
-            return torch.where(j < nF[act], gptr[act] * F + j, N * F + eptr[act] + j - nF[act])
-        # what cannot change the output: its difference is exactly 0 by definition
-        live = torch.cat([(x != 0).reshape(-1), ei[0] != ei[1]])
-        return _Walk(K, seg, int(K.max()) if self.B > 0 else 0, place, torch.arange(self.row, device=x.device), live)
-
-    def result(self, acc, out_full, out_base) -> ShapleyResult:
-        NF = self.N * self.F
-        return ShapleyResult(acc[:NF].view(self.N, self.F), acc[NF:self.row], out_full, out_base)
-
-
-class _GroupPlayers(_Players):
-    arg, width, label = "group_permutations", "G", "hcg_explain (grouped shapley)"
-    flags, per_cu = _lib.HCG_EXPLAIN_GROUPED, GROUPED_WORKGROUPS_PER_CU
-
-    def __init__(self, batch, node_group, edge_group):
-        super().__init__(batch)
-        self.groups = gr = _group_layout(batch, self.F, node_group, edge_group)
-        self.row = gr.G
-        self.query = dict(flags=_lib.HCG_EXPLAIN_QUERY | _lib.HCG_EXPLAIN_GROUPED, shap_n_groups=gr.G)
-
-    def segments(self):
-        return self.groups.count, self.groups.group_ptr
-
-    def max_steps(self, a) -> int:
-        return self.groups.max_groups
-
-    def fill(self, a):
-        gr, p = self.groups, _lib.ptr
-        self.group_ptr32 = group_ptr = gr.group_ptr.to(torch.int32)         # (lives as long as the call's players)
-        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr), p(gr.member_ptr), p(gr.bg_ptr)
-        # one array holds the groups' members and, behind them, the background (a batch without features: never read)
-        a.shap_members = a.shap_bg_members = p(gr.members) if gr.members.numel() else p(group_ptr)
-        a.shap_n_groups = gr.G
-
-    def walk(self) -> _Walk:
-        gr = self.groups
-
-        def place(act, j):
-            return gr.group_ptr[act] + j
-        # a group without a live member cannot change the output: its difference is exactly 0 by definition
-        return _Walk(gr.count, gr.group_ptr, gr.max_groups, place, gr.slot, gr.live_group)
-
-    def result(self, acc, out_full, out_base) -> GroupedShapleyResult:
-        gr, NF = self.groups, self.N * self.F
-        flat = torch.cat([acc[:gr.G], acc.new_zeros(1)])[gr.slot]          # (the background reads the appended 0)
-        return GroupedShapleyResult(acc[:gr.G], gr.group_ptr, flat[:NF].view(self.N, self.F), flat[NF:], out_full, out_base)
-
-
-def _players(batch, permutations, node_group, edge_group, group_permutations):
-    """-> (the players of a call with these arguments, the permutations it was given or None)"""
-    if node_group is not None or edge_group is not None:
-        if permutations is not None:
-            raise ValueError("a grouped call takes group_permutations, not permutations")
-        return _GroupPlayers(batch, node_group, edge_group), group_permutations
-    if group_permutations is not None:
-        raise ValueError("group_permutations need node_group or edge_group")
-    return _Features(batch), permutations
-
-
 class ShapleySampling(_frozen.FrozenModel):
     """Shapley value sampling of a frozen model for a whole batch of graphs.
 
@@ -386,10 +151,6 @@ class ShapleySampling(_frozen.FrozenModel):
     The host checks the ids and lists the members with torch ops: one stable sort and one read of three scalars."""
 
     KERNEL, NAME = _lib.HCG_EXPLAIN_SHAPLEY, "ShapleySampling"
-
-    def __init__(self, model: torch.nn.Module):
-        super().__init__(model)
-        self._step = ExplainStep(model, apply_sigmoid=False)
 
     @staticmethod
     def default_samples_per_launch(n_perm: int, num_graphs: int, row: int, max_steps: int = 0,
@@ -439,18 +200,13 @@ class ShapleySampling(_frozen.FrozenModel):
         return pl.result(acc, out, base)
 
     # ------------------------------------------------------------------ the existing path (any shape): one forward per step
-    def _forward(self, batch, node_mask, edge_mask):
-        if not batch.x.is_cuda:
-            return _frozen.torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
-        return self._step(batch, edge_mask, node_mask).out
-
     def loop(self, batch, n_samples: int = 25, permutations=None, generator=None, class_index: int = 0, node_group=None,
              edge_group=None, group_permutations=None):
         """The batch-synchronous loop (see the class docstring), whatever `reason(batch)` says."""
         pl, given = _players(batch, permutations, node_group, edge_group, group_permutations)
         return self._walk(pl, pl.permutations(n_samples, given, generator), class_index)
 
-    def _walk(self, pl: _Players, perm, class_index):
+    def _walk(self, pl: _groups._Players, perm, class_index):
         """Step k switches on the k-th player of every graph's permutation: a feature, or every member of a group (what no
         group holds, the background, is on from the base on)."""
         batch, N, F, B, row = pl.batch, pl.N, pl.F, pl.B, pl.row
@@ -465,7 +221,7 @@ class ShapleySampling(_frozen.FrozenModel):
             for p in range(P):
                 on = background.clone()
                 phi = torch.zeros(row, dtype=torch.float32, device=dev)
-                out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
+                out = self._masked_forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
                 if p == 0:
                     out_base = out
                 vprev = out[:, class_index].clone()
@@ -475,7 +231,7 @@ class ShapleySampling(_frozen.FrozenModel):
                     step = torch.zeros(row + 1, dtype=torch.bool, device=dev)
                     step[slot] = True
                     on = torch.where(step[w.owner], torch.ones_like(on), on)
-                    out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
+                    out = self._masked_forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).clone()
                     v = out[:, class_index]
                     phi[slot] = torch.where(w.live[slot], v[act] - vprev[act], torch.zeros_like(v[act]))
                     vprev = v.clone()
@@ -513,12 +269,6 @@ def _popcount(t: torch.Tensor, bits: int) -> torch.Tensor:
 def _spread(t: torch.Tensor, at: int) -> torch.Tensor:
     """`t` with a 0 bit inserted at position `at`"""
     return ((t >> at) << (at + 1)) | (t & ((1 << at) - 1))
-
-
-def _counts(ptr) -> list:
-    """Host list of the per-graph counts of a [B + 1] prefix sum (one read)."""
-    p = ptr.tolist()
-    return [b - a for a, b in zip(p[:-1], p[1:])]
 
 
 def _by_count(counts: list):
@@ -651,10 +401,6 @@ class CoalitionValues(_frozen.FrozenModel):
     KERNEL, NAME = _lib.HCG_EXPLAIN_COALITIONS, "CoalitionValues"
     jobs_per_launch: Optional[int] = None          # None: `default_jobs_per_launch`
 
-    def __init__(self, model: torch.nn.Module):
-        super().__init__(model)
-        self._step = ExplainStep(model, apply_sigmoid=False)
-
     @staticmethod
     def default_subsets_per_workgroup(live_rows: int) -> int:
         """Masks per workgroup: up to `SUBSETS_PER_WORKGROUP` = 16, which spreads the graph's build (about the cost of one
@@ -674,25 +420,21 @@ class CoalitionValues(_frozen.FrozenModel):
     def _layout(self, batch, node_group, edge_group):
         """-> (the group layout, per-graph counts, per-graph live counts, live_group's rank inside its graph [G]); the
         limits checked.  One host read beside `_group_layout`'s."""
-        F, B, dev = int(batch.x.shape[1]), int(batch.num_graphs), batch.x.device
+        F, B = int(batch.x.shape[1]), int(batch.num_graphs)
         gr = _group_layout(batch, F, node_group, edge_group)
         if gr.max_groups > MAX_COALITION_GROUPS:
             raise ValueError(f"a graph has {gr.max_groups} groups; CoalitionValues takes at most {MAX_COALITION_GROUPS} "
                              f"(2^{MAX_COALITION_GROUPS} rows per graph)")
-        ggraph = torch.repeat_interleave(torch.arange(B, device=dev), gr.count, output_size=gr.G)
-        live = gr.live_group.to(torch.int64)
-        nlive = torch.zeros(B, dtype=torch.int64, device=dev).index_add_(0, ggraph, live)
-        lptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-        lptr[1:] = nlive.cumsum(0)
-        rank = live.cumsum(0) - live - lptr[ggraph]                         # a live group's index among its graph's live groups
-        counts, lives = torch.stack([gr.count, nlive]).tolist() if B > 0 else ([], [])
+        ggraph = _groups._group_graph(gr.count, gr.G)
+        live = _groups._flag_ranks(ggraph, B, gr.live_group)               # (rank: a live group's index among its graph's live groups)
+        counts, lives = torch.stack([gr.count, live.per_graph]).tolist() if B > 0 else ([], [])
         C = int(self.model._n_classes)
         T = sum(1 << c for c in counts)
         from . import attribution
         if T * C * 4 > attribution.LAUNCH_BUDGET_BYTES:
             raise ValueError(f"the table of this batch has {T} rows of {C} outputs, {T * C * 4} bytes, above "
                              f"LAUNCH_BUDGET_BYTES = {attribution.LAUNCH_BUDGET_BYTES}: split the batch")
-        return gr, counts, lives, (ggraph, lptr, rank)
+        return gr, counts, lives, (ggraph, live.ptr, live.rank)
 
     @staticmethod
     def _expand(gr, counts, lives, aux, dev):
@@ -732,9 +474,7 @@ class CoalitionValues(_frozen.FrozenModel):
         gr, counts, lives, aux = self._layout(batch, node_group, edge_group)
         tptr, vptr, index = self._expand(gr, counts, lives, aux, dev)
         T_live = sum(1 << c for c in lives)
-        spw = self.default_subsets_per_workgroup(T_live) if subsets_per_workgroup is None else int(subsets_per_workgroup)
-        if spw < 1:
-            raise ValueError(f"subsets_per_workgroup must be at least 1; got {subsets_per_workgroup}")
+        spw = _frozen.positive("subsets_per_workgroup", subsets_per_workgroup) or self.default_subsets_per_workgroup(T_live)
         spw = min(spw, 1 << MAX_COALITION_GROUPS)
         # the jobs (graph, first mask, masks), built on the host from the live counts
         jobs = [(g, m, min(spw, (1 << c) - m)) for g, c in enumerate(lives) for m in range(0, 1 << c, spw)]
@@ -750,27 +490,14 @@ class CoalitionValues(_frozen.FrozenModel):
             return self._result(table[index], tptr, gr, counts, cls)
         _frozen.query(a, self.KERNEL, self._shape(), batch, coal_rows=T_live, coal_max_live=max(lives))
         self._fill(a, 0, batch, x, self._weights(dev))
-        p = _lib.ptr
-        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(live_ptr32), p(member_ptr), p(gr.bg_ptr)
-        a.shap_members = a.shap_bg_members = p(gr.members) if gr.members.numel() else p(live_ptr32)
-        a.shap_n_groups = int(member_ptr.numel()) - 1
-        a.coal_values, a.coal_jobs, a.coal_live_ptr = _frozen.front(table), p(jobs_t), p(vptr)
+        _groups.fill_lists(a, gr, live=(live_ptr32, member_ptr))           # (both live in this frame until the launches are enqueued)
+        a.coal_values, a.coal_jobs, a.coal_live_ptr = _frozen.front(table), _lib.ptr(jobs_t), _lib.ptr(vptr)
         a.coal_rows, a.coal_max_live = T_live, max(lives)
-        jpl = self.default_jobs_per_launch(spw) if self.jobs_per_launch is None else int(self.jobs_per_launch)
-        if jpl < 1:
-            raise ValueError(f"jobs_per_launch must be at least 1; got {self.jobs_per_launch}")
-        lib, stream = _lib.load(), _lib.stream_ptr()
-        for first in range(0, J, jpl):
-            a.coal_job_first, a.coal_job_count = first, min(jpl, J - first)
-            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (coalitions)")
+        jpl = _frozen.positive("jobs_per_launch", self.jobs_per_launch) or self.default_jobs_per_launch(spw)
+        _frozen.launch_jobs(a, 0, J, jpl, "hcg_explain (coalitions)")
         return self._result(table[index], tptr, gr, counts, cls)
 
     # ------------------------------------------------------------------ the existing path (any shape): one forward per mask index
-    def _forward(self, batch, node_mask, edge_mask):
-        if not batch.x.is_cuda:
-            return _frozen.torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
-        return self._step(batch, edge_mask, node_mask).out
-
     def loop(self, batch, node_group=None, edge_group=None, class_index: int = 0):
         """The batch-synchronous loop (see the class docstring), whatever `reason(batch)` says."""
         (N, F), B, dev = batch.x.shape, int(batch.num_graphs), batch.x.device
@@ -788,7 +515,7 @@ class CoalitionValues(_frozen.FrozenModel):
         with torch.no_grad():
             for s in range(1 << max(counts)) if B > 0 else ():
                 on = (background | (((torch.full_like(local, s) >> local) & 1) == 1)).to(torch.float32)
-                out = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1)
+                out = self._masked_forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1)
                 act = (torch.ones_like(gr.count) << gr.count) > s
                 raw[tptr[:-1][act] + s] = out[act].to(torch.float32)
         # the rows of the live table, read back through the same gather as the fused path's: a row stands for every row

@@ -17,15 +17,14 @@ any of the five attributions into such an order.  `pack_subsets` is the bit layo
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import NamedTuple, Optional, Sequence
 
 import torch
 
-from . import _frozen, _lib
-from .explain import ExplainStep
-from .shapley import CoalitionValues, _counts, _group_layout
+from . import _frozen, _groups, _lib
+from ._groups import _group_graph, _group_layout, _member_group, _pack  # noqa: F401  (`_member_group`: reached here as before)
+from .shapley import CoalitionValues
 
 MAX_SUBSET_GROUPS = 16384          # groups of one graph: the bits the kernel's staging holds (a graph inside the shape limits
 #                                    has at most 184 * 64 + 1024 = 12800 features, so no such graph reaches it)
@@ -66,44 +65,6 @@ class _CurvePlan(NamedTuple):
 
 
 # ====================================================================== the bit layout
-def _group_graph(count: torch.Tensor, G: int) -> torch.Tensor:
-    """[G] int64: the graph of every group"""
-    return torch.repeat_interleave(torch.arange(count.numel(), device=count.device), count, output_size=G)
-
-
-def _member_group(gr, ggraph: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """int32 [len(gr.members)]: the local group id of every listed member of a `_group_layout`, -1 behind the groups' members
-    (the background and the dead, which the kernels never read as group members).  `ggraph`: `_group_graph(gr.count, gr.G)`
-    when the caller has it.  What `SubsetValues`, `GreedySelection` and `EnsembleSubsetValues` hand the library as
-    `sub_member_group`."""
-    L, G, dev = int(gr.members.numel()), gr.G, gr.members.device
-    if ggraph is None:
-        ggraph = _group_graph(gr.count, G)
-    glob = torch.bucketize(torch.arange(L, device=dev), gr.member_ptr[1:].to(torch.int64), right=True)
-    local = glob - gr.group_ptr[ggraph[glob.clamp(max=G - 1)]] if G > 0 else glob
-    return torch.where(glob < G, local, torch.full_like(glob, -1)).to(torch.int32).contiguous()
-
-
-def _pack(subsets: torch.Tensor, group_ptr: torch.Tensor, W: int):
-    """`pack_subsets` with W = the words of a row known (no host read): -> (bits [S, W] int32, word_ptr [B + 1] int32)"""
-    S, G = subsets.shape
-    dev = subsets.device
-    group_ptr = group_ptr.to(torch.int64)
-    count = group_ptr[1:] - group_ptr[:-1]
-    wptr = torch.zeros(count.numel() + 1, dtype=torch.int64, device=dev)
-    wptr[1:] = ((count + 31) // 32).cumsum(0)
-    graph = _group_graph(count, G)
-    y = torch.arange(G, device=dev) - group_ptr[graph]
-    one = torch.ones_like(y) << (y & 31)
-    # (bit 31 as the int32 that has it: the words are uint32 kept in int32 storage)
-    weight = torch.where(one >= (1 << 31), one - (1 << 32), one).to(torch.int32)
-    bits = torch.zeros(S, W, dtype=torch.int32, device=dev)
-    if G > 0 and S > 0:
-        # every (row, word) sums distinct bits: an integer sum, whatever its order
-        bits.index_add_(1, wptr[graph] + (y >> 5), subsets.to(torch.int32) * weight)
-    return bits, wptr.to(torch.int32)
-
-
 def pack_subsets(subsets: torch.Tensor, group_ptr: torch.Tensor):
     """bool [S, G] (column group_ptr[g] + y = group y of graph g, the layout of `group_permutations`) -> (bits [S, W], the
     uint32 words in int32 storage, and word_ptr int32 [B + 1], the prefix sum of ceil(G_g / 32), W = word_ptr[B]): group y of
@@ -208,130 +169,50 @@ class SubsetValues(_frozen.FrozenModel):
     KERNEL, NAME = _lib.HCG_EXPLAIN_SUBSETS, "SubsetValues"
     jobs_per_launch: Optional[int] = None          # None: `CoalitionValues.default_jobs_per_launch`
 
-    def __init__(self, model: torch.nn.Module):
-        super().__init__(model)
-        self._step = ExplainStep(model, apply_sigmoid=False)
-
-    # ------------------------------------------------------------------ what both paths share
-    def _layout(self, batch, node_group, edge_group):
-        """-> (the group layout, the per-graph group counts on the host)"""
-        gr = _group_layout(batch, int(batch.x.shape[1]), node_group, edge_group)
-        return gr, _counts(gr.group_ptr)
-
-    def _check(self, batch, gr, subsets, rows_per_graph):
-        """-> rows_per_graph as a host list (or None); `subsets` and the table size checked"""
-        dev, B = batch.x.device, int(batch.num_graphs)
-        if not torch.is_tensor(subsets) or subsets.dtype != torch.bool or subsets.dim() != 2 or subsets.shape[1] != gr.G:
-            raise ValueError(f"subsets must be a bool tensor of shape [S, G = {gr.G}]; got "
-                             f"{getattr(subsets, 'dtype', type(subsets))} {tuple(getattr(subsets, 'shape', ()))}")
-        if subsets.device != dev:
-            raise ValueError(f"subsets are on {subsets.device}, the batch on {dev}")
-        S, C = int(subsets.shape[0]), int(self.model._n_classes)
-        from . import attribution
-        if (S + 2) * B * C * 4 > attribution.LAUNCH_BUDGET_BYTES:
-            raise ValueError(f"the table of this call has {S} + 2 rows of {B} graphs and {C} outputs, {(S + 2) * B * C * 4} bytes, "
-                             f"above LAUNCH_BUDGET_BYTES = {attribution.LAUNCH_BUDGET_BYTES}: split the rows or the batch")
-        if rows_per_graph is None:
-            return None
-        t = rows_per_graph
-        if not torch.is_tensor(t) or t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64) or tuple(t.shape) != (B,):
-            raise ValueError(f"rows_per_graph must be an integer tensor of shape [B = {B}]; got {getattr(t, 'dtype', type(t))} "
-                             f"{tuple(getattr(t, 'shape', ()))}")
-        rp = t.tolist()
-        if any(not 0 <= r <= S for r in rp):
-            raise ValueError(f"rows_per_graph must lie in 0 .. S = {S}")
-        return rp
-
     # ------------------------------------------------------------------ the call
     def __call__(self, batch, subsets, node_group=None, edge_group=None, rows_per_graph=None,
                  rows_per_workgroup: Optional[int] = None) -> SubsetResult:
         why = self._shape_args(self._args, batch)
-        gr, counts = self._layout(batch, node_group, edge_group)
-        rp = self._check(batch, gr, subsets, rows_per_graph)
+        gr, counts = _groups.subset_layout(batch, node_group, edge_group)
+        rp = _groups.check_subsets(batch, gr, subsets, rows_per_graph, self._shape()[2])
         table = self._table(batch, gr, counts, subsets, rp, rows_per_workgroup, why)
         S = int(subsets.shape[0])
         return SubsetResult(table[:S], gr.group_ptr, table[S], table[S + 1])
 
     def loop(self, batch, subsets, node_group=None, edge_group=None, rows_per_graph=None) -> SubsetResult:
         """The batch-synchronous loop (see the class docstring), whatever `reason(batch)` says."""
-        gr, counts = self._layout(batch, node_group, edge_group)
-        rp = self._check(batch, gr, subsets, rows_per_graph)
+        gr, counts = _groups.subset_layout(batch, node_group, edge_group)
+        rp = _groups.check_subsets(batch, gr, subsets, rows_per_graph, self._shape()[2])
         table = self._loop(batch, gr, subsets, rp)
         S = int(subsets.shape[0])
         return SubsetResult(table[:S], gr.group_ptr, table[S], table[S + 1])
 
-    @staticmethod
-    def _jobs(B: int, S: int, rp, rpw: int) -> torch.Tensor:
-        """int32 [J, 3] on the host: the jobs (graph, first row, rows) -- every graph's rows 0 .. S + 1 (`rp` None), or its rows
-        0 .. rp[g] - 1 and the two appended ones, in runs of `rpw`"""
-        def runs(first, count):
-            # (first [B], count [B]) -> the runs of `rpw` that tile first[g] .. first[g] + count[g] - 1
-            per = (count + rpw - 1) // rpw
-            g = torch.repeat_interleave(torch.arange(B), per)
-            ptr = torch.zeros(B + 1, dtype=torch.int64)
-            ptr[1:] = per.cumsum(0)
-            at = (torch.arange(g.numel()) - ptr[g]) * rpw
-            return torch.stack([g, first[g] + at, torch.clamp(count[g] - at, max=rpw)], 1)
-        zero = torch.zeros(B, dtype=torch.int64)
-        if rp is None:
-            jobs = runs(zero, zero + (S + 2))
-        else:
-            jobs = torch.cat([runs(zero, torch.tensor(rp, dtype=torch.int64).reshape(B)), runs(zero + S, zero + 2)])
-        return jobs.to(torch.int32).contiguous()
-
     def _table(self, batch, gr, counts, subsets, rp, rows_per_workgroup, why) -> torch.Tensor:
         """[S + 2, B, C]: the rows of `subsets`, then everything on, then the background only.  `why`: `_shape_args`'
         answer for this batch (not None: the loop)."""
-        if rows_per_workgroup is not None and int(rows_per_workgroup) < 1:
-            raise ValueError(f"rows_per_workgroup must be at least 1; got {rows_per_workgroup}")
+        rpw = _frozen.positive("rows_per_workgroup", rows_per_workgroup)
         if why is not None or gr.max_groups > MAX_SUBSET_GROUPS:
             return self._loop(batch, gr, subsets, rp)
         a = self._args
         x = _frozen.batch_x(batch, subsets)
         B, C, dev = a.B, a.C, x.device
-        S, G = int(subsets.shape[0]), gr.G
-        S2 = S + 2
-        rpw = CoalitionValues.default_subsets_per_workgroup(S * B) if rows_per_workgroup is None else int(rows_per_workgroup)
-        jpl = CoalitionValues.default_jobs_per_launch(rpw) if self.jobs_per_launch is None else int(self.jobs_per_launch)
-        if jpl < 1:
-            raise ValueError(f"jobs_per_launch must be at least 1; got {self.jobs_per_launch}")
-        jobs = self._jobs(B, S, rp, rpw)
-        J = int(jobs.shape[0])
-        table = self._bufs.take("table", (S2, B, C), dev)
+        rpw = rpw or CoalitionValues.default_subsets_per_workgroup(int(subsets.shape[0]) * B)
+        jpl = _frozen.positive("jobs_per_launch", self.jobs_per_launch) or CoalitionValues.default_jobs_per_launch(rpw)
+        call = _groups._SubsetCall(B, gr, counts, subsets, rp, rpw)
+        table = self._bufs.take("table", (call.S2, B, C), dev)
         if rp is not None:
             table.zero_()
         self.last_path = "fused"
-        if J == 0:                                                          # (no graph: nothing to launch)
+        if call.J == 0:                                                     # (no graph: nothing to launch)
             return table
-        rows = torch.cat([subsets, torch.ones(1, G, dtype=torch.bool, device=dev), torch.zeros(1, G, dtype=torch.bool, device=dev)])
-        W = sum((c + 31) // 32 for c in counts)
-        bits, word_ptr = _pack(rows, gr.group_ptr, W)
-        L = int(gr.members.numel())
-        member_group = _member_group(gr)
-        jobs_t = jobs.to(dev)
-        group_ptr32 = gr.group_ptr.to(torch.int32)
-        _frozen.query(a, self.KERNEL, self._shape(), batch, coal_rows=S2, sub_max_groups=gr.max_groups)
+        _frozen.query(a, self.KERNEL, self._shape(), batch, **call.query)
         self._fill(a, 0, batch, x, self._weights(dev))
-        p = _lib.ptr
-        a.shap_group_ptr, a.shap_member_ptr, a.shap_bg_ptr = p(group_ptr32), p(gr.member_ptr), p(gr.bg_ptr)
-        # (a batch without features or without groups: arrays of length 0 are never read, but must not be NULL)
-        a.shap_members = a.shap_bg_members = p(gr.members) if L else p(group_ptr32)
-        a.sub_member_group = p(member_group) if L else p(group_ptr32)
-        a.shap_n_groups = G
-        a.sub_bits, a.sub_word_ptr = (p(bits) if W else p(word_ptr)), p(word_ptr)
-        a.coal_values, a.coal_jobs, a.coal_rows, a.sub_max_groups = _frozen.front(table), p(jobs_t), S2, gr.max_groups
-        lib, stream = _lib.load(), _lib.stream_ptr()
-        for first in range(0, J, jpl):
-            a.coal_job_first, a.coal_job_count = first, min(jpl, J - first)
-            _lib.check(lib.hcg_explain(ctypes.addressof(a), stream), "hcg_explain (subsets)")
+        call.fill(a)
+        a.coal_values = _frozen.front(table)
+        _frozen.launch_jobs(a, 0, call.J, jpl, "hcg_explain (subsets)")
         return table
 
     # ------------------------------------------------------------------ the existing path (any shape): one forward per row
-    def _forward(self, batch, node_mask, edge_mask):
-        if not batch.x.is_cuda:
-            return _frozen.torch_forward(self.model, batch.x * node_mask, batch.edge_index, batch.batch, int(batch.num_graphs), edge_mask)
-        return self._step(batch, edge_mask, node_mask).out
-
     def _loop(self, batch, gr, subsets, rp) -> torch.Tensor:
         (N, F), B, dev = batch.x.shape, int(batch.num_graphs), batch.x.device
         S, G, C = int(subsets.shape[0]), gr.G, int(self.model._n_classes)
@@ -346,7 +227,7 @@ class SubsetValues(_frozen.FrozenModel):
             for s in list(range(top)) + [S, S + 1]:
                 row = subsets[s] if s < S else extra[s - S]
                 on = torch.cat([row, on_bg])[gr.slot].to(torch.float32)
-                table[s] = self._forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).to(torch.float32)
+                table[s] = self._masked_forward(batch, on[:N * F].view(N, F), on[N * F:]).reshape(B, -1).to(torch.float32)
         if rp is not None and S > 0:
             off = torch.arange(S, device=dev).unsqueeze(1) >= torch.tensor(rp, dtype=torch.int64, device=dev).unsqueeze(0)
             table[:S][off] = 0.0
@@ -413,7 +294,7 @@ class AttributionCurves:
         why = sv._shape_args(sv._args, batch)
         cls = sv._class(class_index)
         fr = self._fractions(fractions)
-        gr, counts = sv._layout(batch, node_group, edge_group)
+        gr, counts = _groups.subset_layout(batch, node_group, edge_group)
         plan = self._plan(gr, counts, order, fr, batch.x.device)
         table = sv._table(batch, gr, counts, plan.rows, plan.rows_per_graph, rows_per_workgroup, why)
         insertion, deletion = self._gather(table, plan)

@@ -28,7 +28,8 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from hcatgnet_amd.shapley import CoalitionValues, ShapleySampling, _group_layout, all_group_permutations, atom_groups  # noqa: E402
+from hcatgnet_amd._groups import _group_layout  # noqa: E402
+from hcatgnet_amd.shapley import CoalitionValues, ShapleySampling, all_group_permutations, atom_groups  # noqa: E402
 from tools.bench_shapley import REAL, commit_hash, make_batch, make_model, stats, timed  # noqa: E402
 
 

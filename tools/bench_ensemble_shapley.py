@@ -30,7 +30,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 import hcatgnet_amd as H  # noqa: E402
-from hcatgnet_amd.shapley import _group_layout  # noqa: E402
+from hcatgnet_amd._groups import _group_layout  # noqa: E402
 from hcatgnet_amd.subsets import AttributionCurves, ranking  # noqa: E402
 from tools.bench_ensemble_attribution import REAL, KEEP, make_batch, make_models, stats, window  # noqa: E402
 from tools.bench_shapley import commit_hash  # noqa: E402

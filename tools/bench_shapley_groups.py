@@ -31,7 +31,8 @@ sys.path.insert(0, REPO)
 
 import hcatgnet_amd as H  # noqa: E402
 from hcatgnet_amd import _lib  # noqa: E402
-from hcatgnet_amd.shapley import (GROUPED_WORKGROUPS_PER_CU, ShapleySampling, _group_layout, all_group_permutations, atom_groups, bond_groups,  # noqa: E402
+from hcatgnet_amd._groups import _group_layout  # noqa: E402
+from hcatgnet_amd.shapley import (GROUPED_WORKGROUPS_PER_CU, ShapleySampling, all_group_permutations, atom_groups, bond_groups,  # noqa: E402
                                   draw_group_permutations, draw_permutations)
 from tools.bench_shapley import commit_hash, make_batch, make_model, stats, timed, REAL  # noqa: E402
 
